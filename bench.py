@@ -15,6 +15,12 @@ config "rnnt_loss_pruned s_range=5 B=32 T=1000 S=200 C=500", SURVEY.md 8d "c3"),
 With --gpus N (launched by torch.distributed.run, one rank per GPU) every rank processes its own batch of
 B utterances (the batch dimension shards with no data-path collective; weak scaling) and the scalar loss
 is all-reduced once per step over RCCL.  Rank 0 prints ONE JSON line.
+
+A plain run (`bench.py --gpus 1 --steps N --warmup W`) does only what the headline needs: set-up, W warm-up steps, N timed
+steps, the outputs of the last timed step if --dump-outputs DIR is given, and the JSON line (metric, value, unit,
+higher_is_better, dtype, ms_per_step, and what was run).  --full adds everything else the benchmark measures: HIP events
+around every native call on sampled timed steps (per-call table, roofline, PMC traffic), the dense-am_pruned steps, the
+hipGraph replay and the CPU baseline (each of these can still be dropped with its --no-* switch).
 """
 import argparse
 import contextlib
@@ -39,6 +45,9 @@ CONFIGS = {
     "c5": (8, 8000, 1000, 512, 10),
 }
 HBM_PEAK_GBS = 8000.0   # /opt/skills/guides/MI355X_MICROARCH.md: HBM3E 8.0 TB/s spec (6.29 TB/s measured copy)
+DUMP_SAMPLE = 1 << 20   # --dump-outputs: an output with more elements is written as this many of them (fixed seeded sample)
+DUMP_SEED = 0
+DUMP_LIMIT_BYTES = 64 * 10**6
 
 
 def make_inputs(B, T, S, C, seed, device, ragged=False):
@@ -61,10 +70,12 @@ def make_inputs(B, T, S, C, seed, device, ragged=False):
 
 
 def pruned_step(inp, s_range, keep=False, simple_loss_scale=0.5, first_pass="simple", process_group=None, timer=None,
-                dense_am_pruned=False):
+                dense_am_pruned=False, sink=None):
     """One full step of the hot path (see module docstring).  Returns the scalar loss (and internals).
     first_pass = "smoothed" uses rnnt_loss_smoothed (lm_only_scale 0.1, am_only_scale 0.2 as in
-    simple_rnnt_loss_test.py:291-336) for the occupancy pass (BASELINE.json configs[3], "c4")."""
+    simple_rnnt_loss_test.py:291-336) for the occupancy pass (BASELINE.json configs[3], "c4").
+    sink (a dict) receives references to what a caller of the step gets back (losses, occupancies, ranges, d am, d lm);
+    the returned loss is the same tensor as sink["loss"]."""
     import tf_fast_rnnt as ft
     am = inp["am"].detach().requires_grad_(True)
     lm = inp["lm"].detach().requires_grad_(True)
@@ -98,12 +109,16 @@ def pruned_step(inp, s_range, keep=False, simple_loss_scale=0.5, first_pass="sim
         return dict(loss=loss.detach(), simple_loss=simple_loss.detach(), pruned_loss=pruned_loss.detach(),
                     ranges=ranges, px_grad=px_grad, py_grad=py_grad, logits_grad=logits.grad,
                     am_grad=am.grad, lm_grad=lm.grad)
-    return loss.detach()
+    out = loss.detach()
+    if sink is not None:
+        sink.update(loss=out, simple_loss=simple_loss.detach(), pruned_loss=pruned_loss.detach(), px_grad=px_grad,
+                    py_grad=py_grad, ranges=ranges, am_grad=am.grad, lm_grad=lm.grad)
+    return out
 
 
-def simple_step(inp, keep=False, timer=None):
+def simple_step(inp, keep=False, timer=None, sink=None):
     """BASELINE.json configs[1] ("c2"): rnnt_loss_simple forward + backward only -- px/py builder, recursion forward and
-    backward (occupancies), and the builder's backward to d am, d lm."""
+    backward (occupancies), and the builder's backward to d am, d lm.  sink: as in pruned_step."""
     import tf_fast_rnnt as ft
     am = inp["am"].detach().requires_grad_(True)
     lm = inp["lm"].detach().requires_grad_(True)
@@ -112,7 +127,37 @@ def simple_step(inp, keep=False, timer=None):
     loss.backward()
     if keep:
         return dict(loss=loss.detach(), px_grad=px_grad, py_grad=py_grad, am_grad=am.grad, lm_grad=lm.grad)
-    return loss.detach()
+    out = loss.detach()
+    if sink is not None:
+        sink.update(loss=out, px_grad=px_grad, py_grad=py_grad, am_grad=am.grad, lm_grad=lm.grad)
+    return out
+
+
+# ------------------------------------------------------------------------------------------------ output dump
+def dump_outputs(arrays, dirpath, sample=DUMP_SAMPLE, seed=DUMP_SEED, limit_bytes=DUMP_LIMIT_BYTES):
+    """--dump-outputs: every tensor of `arrays` as dirpath/<name>.npy, float32 (float64 stays float64; integer outputs such
+    as the prune ranges are exact in float32).  A tensor of more than `sample` elements is written as a 1-D array of
+    `sample` of its flattened elements, at indices drawn without replacement by numpy's default_rng(seed) and sorted:
+    the same indices for the same shape in every run.  Returns {name: dict(shape, sampled)}."""
+    os.makedirs(dirpath, exist_ok=True)
+    total, info = 0, {}
+    for name, t in arrays.items():
+        t = t.detach()
+        flat = t.reshape(-1)
+        n = flat.numel()
+        sampled = n > sample
+        if sampled:
+            idx = np.sort(np.random.default_rng(seed).choice(n, sample, replace=False))
+            flat = flat[torch.from_numpy(idx).to(flat.device)]
+        a = flat.to(torch.float64 if t.dtype == torch.float64 else torch.float32).cpu().numpy()
+        if not sampled:
+            a = a.reshape(tuple(t.shape))
+        total += a.nbytes
+        if total > limit_bytes:
+            raise RuntimeError(f"dump_outputs: more than {limit_bytes} bytes at {name!r}")
+        np.save(os.path.join(dirpath, name + ".npy"), a)
+        info[name] = dict(shape=list(t.shape), sampled=sampled)
+    return info
 
 
 # ------------------------------------------------------------------------------------------------ profiling
@@ -442,7 +487,17 @@ def main():
                          "(BASELINE.json configs[1]; the default for --config c2)")
     ap.add_argument("--first-pass", default=None, choices=["simple", "smoothed"],
                     help="occupancy pass; default simple, smoothed for c4 (BASELINE.json configs[3])")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline does not need: per-call HIP events (kernels, roofline), the "
+                         "dense-am_pruned steps, the hipGraph replay and the CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed to DIR/<name>.npy (rank 0; float32, outputs of more than "
+                         f"{DUMP_SAMPLE} elements as a fixed seeded sample of that many)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.warmup < 0:
+        ap.error("--warmup must not be negative")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         raise SystemExit(self_launch(args))      # before this process makes any GPU call
@@ -476,11 +531,12 @@ def main():
     which = args.which or ("simple" if args.config == "c2" else "pipeline")
     group = dist.group.WORLD if (dist is not None and first_pass == "smoothed") else None
 
-    def step(dense=False):
+    def step(dense=False, sink=None):
         if which == "simple":
-            loss = simple_step(inp, timer=timer)
+            loss = simple_step(inp, timer=timer, sink=sink)
         else:
-            loss = pruned_step(inp, r, first_pass=first_pass, process_group=group, timer=timer, dense_am_pruned=dense)
+            loss = pruned_step(inp, r, first_pass=first_pass, process_group=group, timer=timer, dense_am_pruned=dense,
+                               sink=sink)
         if dist is not None:
             dist.all_reduce(loss)           # the single scalar exchange of the sharded loss
         return loss
@@ -490,7 +546,8 @@ def main():
             dist.barrier()
         torch.cuda.synchronize()
 
-    ft._lib.set_profile_hook(timer)
+    if args.full:
+        ft._lib.set_profile_hook(timer)
     # library-GEMM kernel selection (package feature, csrc/normalizer_gemm.hip): the library measures rocBLAS' candidates at
     # the second call with a shape, i.e. inside the untimed warm-up (two extra untimed steps if W < 2); --gemm-choices FILE
     # stores what was chosen / reapplies it (with --no-gemm-search nothing is measured: profiling runs)
@@ -511,19 +568,22 @@ def main():
     for _ in range(args.warmup):
         step()
     torch.cuda.reset_peak_memory_stats(dev)
-    # per-call HIP events are recorded inside the timed region on every `event_every`-th step (rank 0): ~60 event
+    # --full: per-call HIP events are recorded inside the timed region on every `event_every`-th step (rank 0): ~60 event
     # records per step are not free, and sampling keeps the timed region what a training loop would run
     sampled = [i for i in range(args.steps) if i % max(args.event_every, 1) == 0]
+    outputs = {} if args.dump_outputs else None      # the last timed step leaves references to its results here
     fence()
     t0 = time.perf_counter()
     for i in range(args.steps):
-        timer.enabled = (rank == 0) and (i % max(args.event_every, 1) == 0)
-        last = step()
+        timer.enabled = args.full and (rank == 0) and (i % max(args.event_every, 1) == 0)
+        last = step(sink=outputs if i == args.steps - 1 else None)
     fence()
     dt = time.perf_counter() - t0
     timer.enabled = False
     ft._lib.set_profile_hook(None)
     peak_mb = torch.cuda.max_memory_allocated(dev) / 2**20
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(outputs, args.dump_outputs)
     gemm_choices = {}
     for kind in range(3):
         ch = ft.normalizer_gemm_choice(kind, Bc, Tc, Sc, Cc)
@@ -535,7 +595,7 @@ def main():
     # secondary: the same step with am_pruned MATERIALISED ([B,T,r,C] written by the gather and read by the joiner), which is
     # what the reference's tf.broadcast_to costs and what a TensorFlow binding of the C ABI pays; untimed for `value`
     dense_ms = None
-    if which == "pipeline" and world == 1 and not args.no_dense:
+    if args.full and which == "pipeline" and world == 1 and not args.no_dense:
         for _ in range(2):
             step(dense=True)
         torch.cuda.synchronize()
@@ -555,42 +615,6 @@ def main():
 
     ms_per_step = 1e3 * dt / args.steps
     value = world * B * args.steps / dt
-    calls = timer.summary()
-    alg = algorithmic_bytes(B, T, S, C, r)
-    kernels = {}
-    for name, rec in calls.items():
-        per_step_calls = rec["calls"] / len(sampled)
-        kernels[name] = dict(avg_us=round(rec["avg_us"], 2), calls_per_step=per_step_calls,
-                             algorithmic_MB=round(alg[name] / 1e6, 1) if name in alg else None,
-                             GBps=round(alg[name] / (rec["avg_us"] * 1e-6) / 1e9, 1) if name in alg else None)
-    # roofline: always the kernel pair north_star names, the mutual-information recursion forward + backward (SURVEY.md
-    # 8(d): 32 bytes per lattice cell for the pair), whatever else is slow in the step -- so that the line is comparable
-    # from run to run; every other native call is in `kernels`.  avg_launch_us = the HIP-event time of the two calls
-    # (each call = its kernels back to back on the stream; the rocprofv3 --kernel-trace --stats summary of this same
-    # command under profiles/ gives the per-kernel split).
-    # the entry points the package calls (the loss nodes' backward launch also writes the reduced loss: ..._bwd_loss_ws_f32)
-    pair = ("ftr_mutual_information_fwd_ws_f32",
-            "ftr_mutual_information_bwd_loss_ws_f32" if "ftr_mutual_information_bwd_loss_ws_f32" in calls else "ftr_mutual_information_bwd_ws_f32")
-    roofline = None
-    traffic, traffic_file = pmc_traffic(args.config) if (first_pass == "simple" and not args.ragged) else (None, None)
-    if traffic:
-        for name in kernels:
-            kernels[name]["pmc_hbm_MB"] = round(traffic[name] / 1e6, 1) if name in traffic else None
-    if all(n in calls for n in pair):
-        pair_us = sum(calls[n]["avg_us"] for n in pair)
-        pair_bytes = sum(alg[n] for n in pair)
-        achieved = pair_bytes / (pair_us * 1e-6) / 1e9
-        roofline = dict(bound="hbm", kernel="+".join(pair), achieved=round(achieved, 1), peak=HBM_PEAK_GBS, unit="GB/s",
-                        frac=round(achieved / HBM_PEAK_GBS, 4),
-                        traffic=(sum(traffic[n] for n in pair) if traffic and all(n in traffic for n in pair) else None),
-                        traffic_source=traffic_file, avg_launch_us=round(pair_us, 2),
-                        avg_launch_us_each={n: round(calls[n]["avg_us"], 2) for n in pair},
-                        algorithmic_bytes=pair_bytes, launches_per_step=calls[pair[0]]["calls"] / len(sampled))
-    # the streaming share of the step against the same roofline: all native calls together
-    tot_alg = sum(alg[n] * calls[n]["calls"] for n in calls if n in alg) / len(sampled)
-    tot_us = sum(calls[n]["total_ms"] for n in calls if n in alg) * 1e3 / len(sampled)
-    joiner_us = sum(calls[n]["total_ms"] for n in calls if n.startswith("joiner_standin")) * 1e3 / len(sampled)
-    native_us = sum(rec["total_ms"] for n, rec in calls.items() if not n.startswith("joiner_standin")) * 1e3 / len(sampled)
     if which == "simple":
         workload = (f"{args.config}: rnnt_loss_simple fwd+bwd (builder + recursion forward/backward + builder backward to am, lm), "
                     f"B={B}/GPU T={T} S={S} C={C}, regular, {'ragged' if args.ragged else 'full'} boundary")
@@ -617,31 +641,71 @@ def main():
                    # do_rnnt_pruning returns am_pruned as a stride-0 broadcast view of am (values, shape and gradient as the
                    # reference's tf.broadcast_to; the reference's joiner stand-in consumes it by broadcasting)
                    "am_pruned": "broadcast view"},
-        "roofline": roofline,
-        "kernel_timing": f"HIP events around every native call on {len(sampled)} of the {args.steps} timed steps",
-        "native_us_per_step": round(native_us, 1),
-        # the joiner stand-in sigmoid(am_pruned + lm_pruned) is user code between do_rnnt_pruning and
-        # rnnt_loss_pruned; it IS inside the timed step (value/ms_per_step include it) and is reported here so that the
-        # loss-only time can be read off: ms_per_step - joiner_standin_us_per_step / 1000.
-        "joiner_standin_us_per_step": round(joiner_us, 1),
-        "loss_only_us_per_step": round(1e3 * ms_per_step - joiner_us, 1),
-        "native_aggregate": {"algorithmic_MB_per_step": round(tot_alg / 1e6, 1), "us_per_step": round(tot_us, 1),
-                             "GBps": round(tot_alg / (tot_us * 1e-6) / 1e9, 1) if tot_us > 0 else None,
-                             "frac_of_peak": round(tot_alg / (tot_us * 1e-6) / 1e9 / HBM_PEAK_GBS, 4) if tot_us > 0 else None},
-        "dense_am_pruned_ms_per_step": round(dense_ms, 4) if dense_ms is not None else None,
-        "kernels": kernels,
         "loss": float(last.item()),
         "gemm_tuning": gemm_choices if not args.no_gemm_tuning else False,
+        "full": args.full,
     }
-    if world == 1 and not args.no_graph:
-        gr = graph_replay((lambda: simple_step(inp)) if which == "simple" else (lambda: pruned_step(inp, r, first_pass=first_pass)), args.steps)
-        if gr.get("ms_per_step"):
-            gr["value"] = round(B / (gr["ms_per_step"] * 1e-3), 2)
-        out["graph_replay"] = gr
-    if not args.no_cpu_baseline and world == 1:
-        out["cpu_baseline"] = cpu_baseline(B, T, S, C, r, simple_only=(which == "simple"))
-    else:
-        out["cpu_baseline"] = None
+    if args.full:
+        calls = timer.summary()
+        alg = algorithmic_bytes(B, T, S, C, r)
+        kernels = {}
+        for name, rec in calls.items():
+            per_step_calls = rec["calls"] / len(sampled)
+            kernels[name] = dict(avg_us=round(rec["avg_us"], 2), calls_per_step=per_step_calls,
+                                 algorithmic_MB=round(alg[name] / 1e6, 1) if name in alg else None,
+                                 GBps=round(alg[name] / (rec["avg_us"] * 1e-6) / 1e9, 1) if name in alg else None)
+        # roofline: always the kernel pair north_star names, the mutual-information recursion forward + backward (SURVEY.md
+        # 8(d): 32 bytes per lattice cell for the pair), whatever else is slow in the step -- so that the line is comparable
+        # from run to run; every other native call is in `kernels`.  avg_launch_us = the HIP-event time of the two calls
+        # (each call = its kernels back to back on the stream; the rocprofv3 --kernel-trace --stats summary of this same
+        # command under profiles/ gives the per-kernel split).
+        # the entry points the package calls (the loss nodes' backward launch also writes the reduced loss: ..._bwd_loss_ws_f32)
+        pair = ("ftr_mutual_information_fwd_ws_f32",
+                "ftr_mutual_information_bwd_loss_ws_f32" if "ftr_mutual_information_bwd_loss_ws_f32" in calls else "ftr_mutual_information_bwd_ws_f32")
+        roofline = None
+        traffic, traffic_file = pmc_traffic(args.config) if (first_pass == "simple" and not args.ragged) else (None, None)
+        if traffic:
+            for name in kernels:
+                kernels[name]["pmc_hbm_MB"] = round(traffic[name] / 1e6, 1) if name in traffic else None
+        if all(n in calls for n in pair):
+            pair_us = sum(calls[n]["avg_us"] for n in pair)
+            pair_bytes = sum(alg[n] for n in pair)
+            achieved = pair_bytes / (pair_us * 1e-6) / 1e9
+            roofline = dict(bound="hbm", kernel="+".join(pair), achieved=round(achieved, 1), peak=HBM_PEAK_GBS, unit="GB/s",
+                            frac=round(achieved / HBM_PEAK_GBS, 4),
+                            traffic=(sum(traffic[n] for n in pair) if traffic and all(n in traffic for n in pair) else None),
+                            traffic_source=traffic_file, avg_launch_us=round(pair_us, 2),
+                            avg_launch_us_each={n: round(calls[n]["avg_us"], 2) for n in pair},
+                            algorithmic_bytes=pair_bytes, launches_per_step=calls[pair[0]]["calls"] / len(sampled))
+        # the streaming share of the step against the same roofline: all native calls together
+        tot_alg = sum(alg[n] * calls[n]["calls"] for n in calls if n in alg) / len(sampled)
+        tot_us = sum(calls[n]["total_ms"] for n in calls if n in alg) * 1e3 / len(sampled)
+        joiner_us = sum(calls[n]["total_ms"] for n in calls if n.startswith("joiner_standin")) * 1e3 / len(sampled)
+        native_us = sum(rec["total_ms"] for n, rec in calls.items() if not n.startswith("joiner_standin")) * 1e3 / len(sampled)
+        out.update({
+            "roofline": roofline,
+            "kernel_timing": f"HIP events around every native call on {len(sampled)} of the {args.steps} timed steps",
+            "native_us_per_step": round(native_us, 1),
+            # the joiner stand-in sigmoid(am_pruned + lm_pruned) is user code between do_rnnt_pruning and
+            # rnnt_loss_pruned; it IS inside the timed step (value/ms_per_step include it) and is reported here so that the
+            # loss-only time can be read off: ms_per_step - joiner_standin_us_per_step / 1000.
+            "joiner_standin_us_per_step": round(joiner_us, 1),
+            "loss_only_us_per_step": round(1e3 * ms_per_step - joiner_us, 1),
+            "native_aggregate": {"algorithmic_MB_per_step": round(tot_alg / 1e6, 1), "us_per_step": round(tot_us, 1),
+                                 "GBps": round(tot_alg / (tot_us * 1e-6) / 1e9, 1) if tot_us > 0 else None,
+                                 "frac_of_peak": round(tot_alg / (tot_us * 1e-6) / 1e9 / HBM_PEAK_GBS, 4) if tot_us > 0 else None},
+            "dense_am_pruned_ms_per_step": round(dense_ms, 4) if dense_ms is not None else None,
+            "kernels": kernels,
+        })
+        if world == 1 and not args.no_graph:
+            gr = graph_replay((lambda: simple_step(inp)) if which == "simple" else (lambda: pruned_step(inp, r, first_pass=first_pass)), args.steps)
+            if gr.get("ms_per_step"):
+                gr["value"] = round(B / (gr["ms_per_step"] * 1e-3), 2)
+            out["graph_replay"] = gr
+        if not args.no_cpu_baseline and world == 1:
+            out["cpu_baseline"] = cpu_baseline(B, T, S, C, r, simple_only=(which == "simple"))
+        else:
+            out["cpu_baseline"] = None
     print(json.dumps(out))
     if dist is not None:
         dist.destroy_process_group()

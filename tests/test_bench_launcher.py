@@ -40,8 +40,9 @@ def test_visible_gpu_count_matches_the_runtime(dev):
 
 @pytest.mark.gpu
 def test_self_launch_two_ranks_prints_one_line(dev):
-    """Two ranks on one card (gloo): one JSON line from rank 0 with n_gpus = 2, twice the per-rank batch, a roofline object."""
-    out = subprocess.run([sys.executable, BENCH, "--gpus", "2", "--steps", "3", "--warmup", "1", "--no-cpu-baseline", "--no-graph",
+    """Two ranks on one card (gloo): one JSON line from rank 0 with n_gpus = 2, twice the per-rank batch, a roofline object
+    (--full: the per-call events behind it are not part of a plain run)."""
+    out = subprocess.run([sys.executable, BENCH, "--gpus", "2", "--steps", "3", "--warmup", "1", "--full", "--no-cpu-baseline", "--no-graph",
                           "--no-gemm-tuning"], env=_clean_env(FTR_BENCH_BACKEND="gloo", FTR_BENCH_FORCE_DEVICE="0"),
                          capture_output=True, text=True, timeout=600, cwd=ROOT)
     assert out.returncode == 0, out.stdout[-2000:] + out.stderr[-3000:]
