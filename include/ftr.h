@@ -128,6 +128,29 @@ int ftr_mutual_information_bwd_ws_f32(const float* px, const float* py, const in
                                       float* ans_grad, int overwrite_ans_grad, int B, int S, int T, int modified,
                                       void* stream);
 
+/*
+ * Best-path (Viterbi) alignment over the same lattice (MI355X addition, no reference counterpart).  The recursion
+ * of ftr_mutual_information_fwd_f32 with LogAdd replaced by a select:
+ *   a = p[s-1, t+off] + px[s-1, t+off]   (off = 0 regular, -1 modified; -inf where the forward's guards say so)
+ *   c = p[s, t-1] + py[s, t-1]           (-inf at t = t_begin)
+ *   take_px = (a != a) || (a >= c)       (NaN propagates; ties go to the px / symbol move)
+ *   p[s,t] = take_px ? a : c             (exactly this, not fmaxf)
+ * p[s_begin,t_begin] = 0, score[b] = p[s_end,t_end].  One float32 add and one select per cell: the result does not
+ * depend on the evaluation order and equals a float32 restatement bit for bit.
+ *   frames [B,S] int32: frames[b,s] = the frame t at which the best path takes the px move out of row s, i.e. emits
+ *   symbol s (regular: (s,t)->(s+1,t), non-decreasing; modified: (s,t)->(s+1,t+1), strictly increasing).  Rows outside
+ *   [s_begin, s_end) are -1; the whole row is -1 when score[b] is -inf (no path) or NaN.  An inverted rectangle
+ *   (s_end < s_begin or t_end < t_begin) gives score 0 (as the forward's ans) and frames -1.
+ *   workspace: ftr_mutual_information_viterbi_workspace_bytes(B,S,T) bytes, uninitialised is fine (every decision bit
+ *   the backtrace reads is written by the same launch); a smaller workspace_bytes returns FTR_ERR_INVALID_ARG.
+ * Kernels only (no memset / memcpy nodes), graph-capturable.  px, py, boundary: as ftr_mutual_information_fwd_f32.
+ */
+size_t ftr_mutual_information_viterbi_workspace_bytes(int B, int S, int T);
+int ftr_mutual_information_viterbi_f32(const float* px, const float* py, const int32_t* boundary,
+                                       void* workspace, size_t workspace_bytes,
+                                       float* score, int32_t* frames,
+                                       int B, int S, int T, int modified, void* stream);
+
 /* Inclusive prefix-min along rows of an int32 [rows, cols] matrix.  Replaces CumminCuda<int32_t>
  * (mutual_information.h:164-168, mutual_information_cuda.cu:895-1012; op "Cummin",
  * tf_fast_rnnt_op.cc:36-38,135-165). */

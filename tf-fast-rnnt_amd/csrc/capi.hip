@@ -196,6 +196,31 @@ int ftr_mutual_information_status(const float* p, size_t p_floats, int B, int S,
   return mi_bidir_status(p, p_floats, B, S, T, status_host, dirty_words_host, reinterpret_cast<hipStream_t>(stream));
 }
 
+// Best-path (Viterbi) alignment over the lattice of ftr_mutual_information_fwd_f32 (MI355X addition, no reference
+// counterpart; csrc/mi_viterbi.hip).  Sizes, pointers and the workspace are checked before the device is touched.
+size_t ftr_mutual_information_viterbi_workspace_bytes(int B, int S, int T) {
+  return mi_viterbi_workspace_bytes(B, S, T);
+}
+
+int ftr_mutual_information_viterbi_f32(const float* px, const float* py, const int32_t* boundary, void* workspace,
+                                       size_t workspace_bytes, float* score, int32_t* frames, int B, int S, int T,
+                                       int modified, void* stream) {
+  clear_error();
+  FTR_REQUIRE(B >= 0 && S >= 0 && T >= 0, "mutual_information_viterbi: negative size B=%d S=%d T=%d", B, S, T);
+  FTR_REQUIRE(modified == 0 || modified == 1, "mutual_information_viterbi: modified=%d must be 0 or 1", modified);
+  if (B == 0) return FTR_OK;
+  FTR_REQUIRE(workspace_bytes >= mi_viterbi_workspace_bytes(B, S, T),
+              "mutual_information_viterbi: workspace of %zu bytes is too small, %zu needed", workspace_bytes,
+              mi_viterbi_workspace_bytes(B, S, T));
+  FTR_REQUIRE(workspace && score && (frames || S == 0), "mutual_information_viterbi: null workspace / score / frames");
+  FTR_REQUIRE(py || T == 0, "mutual_information_viterbi: null py");
+  FTR_REQUIRE(px || S == 0 || (modified && T == 0), "mutual_information_viterbi: null px");
+  int rc = device_ok();
+  if (rc != FTR_OK) return rc;
+  return mi_viterbi(px, py, boundary, workspace, workspace_bytes, score, frames, B, S, T, modified,
+                    reinterpret_cast<hipStream_t>(stream));
+}
+
 int ftr_cummin_i32(const int32_t* in, int32_t* out, int rows, int cols, void* stream) {
   clear_error();
   FTR_REQUIRE(rows >= 0 && cols >= 0, "cummin: negative size");

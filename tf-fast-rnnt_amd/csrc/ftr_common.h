@@ -144,6 +144,8 @@ int mi_bidir_ws_init(float* ws, size_t ws_floats, int B, int S, int T, hipStream
 int mi_bidir_status(const float* ws, size_t ws_floats, int B, int S, int T, int* status_host, long long* dirty_host, hipStream_t st);
 size_t mi_bidir_workspace_floats(int B, int S, int T);
 size_t mi_bidir_handoff_floats(int B, int S, int T);
+size_t mi_viterbi_workspace_bytes(int B, int S, int T);
+int mi_viterbi(const float* px, const float* py, const int32_t* boundary, void* ws, size_t ws_bytes, float* score, int32_t* frames, int B, int S, int T, int modified, hipStream_t st);
 int cummin_i32(const int32_t* in, int32_t* out, int rows, int cols, hipStream_t st);
 int prune_ranges(const float* px_grad, const float* py_grad, const int32_t* boundary, int32_t* ranges, int32_t* s_begin, int B, int S, int T, int T1, int r, hipStream_t st);
 int do_pruning(const float* am, const float* lm, const int32_t* ranges, float* am_p, float* lm_p, int B, int T, int S1, int C, int r, hipStream_t st);

@@ -4,7 +4,7 @@ rebuilt as hand-written HIP behind a C ABI (include/ftr.h).  The public names, s
 42,151); tensors are torch tensors on a HIP device (TensorFlow is not needed; a TF-ROCm op shim over the
 same C ABI is described in INTEGRATION.md)."""
 from ._lib import FtrError, lib as _load_native          # noqa: F401
-from .mutual_information import cummin, mutual_information_recursion
+from .mutual_information import cummin, mutual_information_recursion, mutual_information_viterbi   # the viterbi alignment: MI355X addition
 from .rnnt_loss import do_rnnt_pruning
 from .rnnt_loss import get_rnnt_logprobs
 from .rnnt_loss import get_rnnt_logprobs_joint
@@ -13,6 +13,7 @@ from .rnnt_loss import get_rnnt_logprobs_smoothed
 from .rnnt_loss import get_rnnt_prune_ranges
 from .rnnt_loss import rnnt_loss
 from .rnnt_loss import rnnt_loss_pruned
+from .rnnt_loss import rnnt_alignment_pruned                                   # MI355X addition: best-path alignment, see its docstring
 from .rnnt_loss import rnnt_loss_simple
 from .rnnt_loss import rnnt_loss_smoothed
 from .rnnt_loss import tune_normalizer_gemms, normalizer_gemm_choice, set_normalizer_gemm_choice                # MI355X addition: library-GEMM kernel selection, see its docstring

@@ -1,4 +1,4 @@
-"""Host wrappers of the native ops: ``mutual_information_recursion`` and ``cummin``.
+"""Host wrappers of the native ops: ``mutual_information_recursion``, ``mutual_information_viterbi`` and ``cummin``.
 
 Mirrors tf_fast_rnnt/python/tf_fast_rnnt/__init__.py:42-162 of the reference (op call + registered
 gradient) and the op kernel it drives, ``FastRNNTOpBase::Compute``
@@ -216,6 +216,56 @@ def mutual_information_recursion(
     """
     ans, px_grad, py_grad = _MutualInformation.apply(px, py, boundary, calc_gradients)
     return (ans, (px_grad, py_grad)) if calc_gradients else ans
+
+
+def mutual_information_viterbi(px: torch.Tensor, py: torch.Tensor,
+                               boundary: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+    """Best-path (Viterbi) alignment over the lattice of ``mutual_information_recursion`` (MI355X addition, no reference
+    counterpart; ftr_mutual_information_viterbi_f32, csrc/mi_viterbi.hip).
+
+    Same inputs and validation as ``mutual_information_recursion``: px [B,S,T+1] (regular) or [B,S,T] (modified),
+    py [B,S+1,T], float32; boundary int32 [B,4] rows (s_begin, t_begin, s_end, t_end) or None.  The recursion with
+    LogAdd replaced by a select::
+
+        a = p[s-1, t+off] + px[s-1, t+off]    (off = 0 regular, -1 modified; -inf where the recursion's guards say so)
+        c = p[s, t-1] + py[s, t-1]
+        take_px = (a != a) or (a >= c)        # NaN propagates, ties go to the px (symbol) move
+        p[s, t] = a if take_px else c         # exactly this, not fmax
+
+    with ``p[s_begin, t_begin] = 0``.  Returns ``(score, frames)``:
+
+    * ``score`` [B] float32 = ``p[s_end, t_end]``, bit-identical to a float32 restatement (one add and one select per
+      cell: the order of evaluation cannot change the bits);
+    * ``frames`` [B,S] int32: ``frames[b,s]`` is the frame at which the best path takes the px move out of row s, i.e.
+      emits ``symbols[b,s]`` (regular: (s,t)->(s+1,t), non-decreasing; modified: (s,t)->(s+1,t+1), strictly
+      increasing).  Rows outside [s_begin, s_end) are -1, and the whole row is -1 when ``score[b]`` is -inf (no path)
+      or NaN.  An inverted rectangle gives score 0 (as ``mutual_information_recursion``) and frames -1.
+
+    Not differentiable: both outputs are detached.  Asynchronous on torch's current stream, no host read (capturable).
+    """
+    _require_gpu(px, "px"); _require_gpu(py, "py")
+    if px.dtype != torch.float32 or py.dtype != torch.float32:
+        raise TypeError("px and py must be float32 (op registration: tf_fast_rnnt_op.cc:27-34)")
+    if px.dim() != 3 or py.dim() != 3:
+        raise ValueError("px and py must be 3-dimensional")
+    B, S, T1 = px.shape
+    T = py.shape[2]
+    if T1 not in (T, T + 1):
+        raise ValueError(f"px.shape[-1]={T1} must be T or T+1 with T=py.shape[-1]={T}")
+    if tuple(py.shape) != (B, S + 1, T):
+        raise ValueError(f"py must have shape {(B, S + 1, T)}, got {tuple(py.shape)}")
+    modified = int(T1 == T)
+    px = px.detach().contiguous(); py = py.detach().contiguous()
+    boundary = _as_boundary(boundary, B, px.device)
+    L = _lib.lib()
+    with torch.cuda.device(px.device):
+        nbytes = L.ftr_mutual_information_viterbi_workspace_bytes(B, S, T)
+        ws = torch.empty((max(nbytes, 1),), dtype=torch.uint8, device=px.device)
+        score = torch.empty((B,), dtype=torch.float32, device=px.device)
+        frames = torch.empty((B, S), dtype=torch.int32, device=px.device)
+        _lib.call("ftr_mutual_information_viterbi_f32", _ptr(px), _ptr(py), _ptr(boundary), _ptr(ws), nbytes,
+                  _ptr(score), _ptr(frames), B, S, T, modified, _stream_ptr(px))
+    return score, frames
 
 
 def cummin(x: torch.Tensor) -> torch.Tensor:

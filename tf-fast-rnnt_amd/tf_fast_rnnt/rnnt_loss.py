@@ -27,7 +27,7 @@ import torch
 
 from . import _lib
 from .mutual_information import (_as_boundary, _ptr, _require_gpu, _stream_ptr, cummin,
-                                 mi_forward_backward, mutual_information_recursion)
+                                 mi_forward_backward, mutual_information_recursion, mutual_information_viterbi)
 
 _NEG_INF = float("-inf")
 # tf.math.nextafter(0., 1.) : smallest positive float32 subnormal (rnnt_loss.py:181,1272,1280)
@@ -645,6 +645,39 @@ def get_rnnt_logprobs_pruned(
     if rnnt_type == "constrained":
         px = px + py[:, 1:, :]
     return px, py
+
+
+def rnnt_alignment_pruned(
+    logits: torch.Tensor,
+    symbols: torch.Tensor,
+    ranges: torch.Tensor,
+    termination_symbol: int,
+    boundary: Optional[torch.Tensor] = None,
+    rnnt_type: str = "regular",
+) -> Tuple[torch.Tensor, torch.Tensor]:
+    """Best-path alignment of the pruned joiner output (MI355X addition, no reference counterpart): the same lattice as
+    ``get_rnnt_logprobs_pruned`` (full-size px / py, -inf outside the band, no delay penalty), fed to
+    ``mutual_information_viterbi``.  Returns ``(score [B] float32, frames [B,S] int32)``, detached; see
+    ``mutual_information_viterbi`` for their meaning (``frames[b,s]`` = the frame that emits ``symbols[b,s]``).
+    Every step runs on the device with no host read, so the call can be captured into a graph.  For unpruned joiner
+    logits use ``mutual_information_viterbi(*get_rnnt_logprobs_joint(...))``."""
+    _check_type(rnnt_type)
+    with torch.no_grad():
+        symbols, ranges, boundary = _pruned_inputs(logits, symbols, ranges, boundary)
+        B, T, r, C = logits.shape
+        S = symbols.shape[1]
+        modified = rnnt_type != "regular"
+        x = logits.detach().contiguous()
+        lse = torch.empty((B, T, r), dtype=torch.float32, device=x.device)
+        px = torch.empty((B, S, T if modified else T + 1), dtype=torch.float32, device=x.device)
+        py = torch.empty((B, S + 1, T), dtype=torch.float32, device=x.device)
+        with torch.cuda.device(x.device):
+            _lib.call("ftr_pruned_logprobs_fwd_f32", _ptr(x), _ptr(symbols), _ptr(ranges), _ptr(boundary),
+                      int(termination_symbol), 0.0, _ptr(lse), _ptr(px), _ptr(py), B, T, S, C, r, int(modified),
+                      _stream_ptr(x))
+        if rnnt_type == "constrained":
+            px += py[:, 1:, :]
+        return mutual_information_viterbi(px, py, boundary)
 
 
 def _mark_band(ranges: torch.Tensor) -> None:
