@@ -451,6 +451,43 @@ int ftr_pruned_band_bwd_scaled_f32(const float* logits, const int32_t* symbols, 
                                    float scale_mul, float* glogits, int B, int T, int S, int C, int r, int modified,
                                    void* stream);
 
+/*
+ * HAT (hybrid autoregressive transducer) normalisation of the pruned joiner output (MI355X addition).  Each entry point
+ * takes the argument list of its ordinary twin (ftr_pruned_logprobs_fwd_f32, ftr_pruned_logprobs_bwd_scaled_f32,
+ * ftr_pruned_band_fwd_f32, ftr_pruned_band_bwd_scaled_f32), validates it the same way, and also requires C >= 2.  Only the
+ * row normalisation differs.  For one row x = logits[b,t,k,:] and blank = termination_symbol:
+ *   Z            = logsumexp over c != blank of x[c]        (lse holds Z; the blank column is excluded)
+ *   softplus(v)  = max(v,0) + log1p(exp(-|v|))
+ *   log P(blank) = -softplus(-x[blank])                     (= log sigmoid(x[blank]))
+ *   log P(c)     = x[c] - Z - softplus(x[blank]),  c != blank
+ * py[b,s,t] = log P(blank), px[b,s,t] = log P(symbols[b,s]); the lattices (or their band cells) are laid out exactly as
+ * the twins lay them out: -inf outside the band, at px[:,:,T] and at the t_end column of the regular type, delay
+ * penalty added to px.  A symbol equal to blank gets px = -inf (blank is not part of the non-blank distribution) and no
+ * gradient.  A symbol outside [0, C) is clamped into it, as the twins do in their forward, and the backward sends its
+ * gradient to that clamped column.  Backward, with gx / gy the scaled occupancies of the row's px / py cells:
+ *   g[c]     = gx (1[c == sym] - exp(x[c] - Z)),            c != blank
+ *   g[blank] = gy sigmoid(-x[blank]) - gx sigmoid(x[blank])
+ * Pass scale = NULL, scale_stride = 0, scale_mul = 1 to ftr_hat_pruned_logprobs_bwd_scaled_f32 for the plain backward.
+ */
+int ftr_hat_pruned_logprobs_fwd_f32(const float* logits, const int32_t* symbols, const int32_t* ranges,
+                                    const int32_t* boundary, int termination_symbol, double delay_penalty,
+                                    float* lse, float* px, float* py, int B, int T, int S, int C, int r,
+                                    int modified, void* stream);
+int ftr_hat_pruned_logprobs_bwd_scaled_f32(const float* logits, const int32_t* symbols, const int32_t* ranges,
+                                           const int32_t* boundary, int termination_symbol, const float* lse,
+                                           const float* gpx, const float* gpy, const float* scale, int scale_stride,
+                                           float scale_mul, float* glogits, int B, int T, int S, int C, int r,
+                                           int modified, void* stream);
+int ftr_hat_pruned_band_fwd_f32(const float* logits, const int32_t* symbols, const int32_t* ranges,
+                                const int32_t* boundary, int termination_symbol, double delay_penalty, float* lse,
+                                float* px_band, float* py_band, int B, int T, int S, int C, int r, int modified,
+                                void* stream);
+int ftr_hat_pruned_band_bwd_scaled_f32(const float* logits, const int32_t* symbols, const int32_t* ranges,
+                                       const int32_t* boundary, int termination_symbol, const float* lse,
+                                       const float* gx_band, const float* gy_band, const float* scale,
+                                       int scale_stride, float scale_mul, float* glogits, int B, int T, int S, int C,
+                                       int r, int modified, void* stream);
+
 /* Hardware self-test used by smoke()/tests: checks on the device that the primitives the wavefront
  * kernels rely on behave as assumed (full-wave DPP shift wave_shr:1 with lane 0 keeping its old value;
  * 16-byte global loads/stores at 4-byte alignment).  scratch_dev: >= 8 KiB of device memory; after the

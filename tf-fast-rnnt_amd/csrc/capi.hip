@@ -286,19 +286,36 @@ int ftr_do_pruning_bwd_ws_f32(const float* g_am_pruned, const float* g_lm_pruned
   return do_pruning_bwd_ws(g_am_pruned, g_lm_pruned, ranges, d_am, d_lm, B, T, S1, C, r, workspace, workspace_bytes, reinterpret_cast<hipStream_t>(stream));
 }
 
+// the ordinary entry point and its HAT twin (hat = 1: blank-excluded normaliser, which needs C >= 2)
+static int pruned_logprobs_fwd_entry(const float* logits, const int32_t* symbols, const int32_t* ranges,
+                                     const int32_t* boundary, int termination_symbol, double delay_penalty,
+                                     float* lse, float* px, float* py, int B, int T, int S, int C, int r,
+                                     int modified, int hat, void* stream) {
+  const char* what = hat ? "hat_pruned_logprobs_fwd" : "pruned_logprobs_fwd";
+  clear_error();
+  FTR_REQUIRE(B >= 0 && T >= 1 && S >= 1 && C >= 1 && r >= 1, "%s: bad sizes", what);
+  FTR_REQUIRE(!hat || C >= 2, "%s: C = %d, HAT needs a blank and at least one other symbol", what, C);
+  FTR_REQUIRE(termination_symbol >= 0 && termination_symbol < C, "%s: termination_symbol %d not in [0,%d)", what, termination_symbol, C);
+  FTR_REQUIRE(r <= S + 1, "%s: s_range %d > S+1 = %d", what, r, S + 1);
+  if (B == 0) return FTR_OK;
+  FTR_REQUIRE(logits && symbols && ranges && lse && px && py, "%s: null pointer", what);
+  int rc = device_ok();
+  if (rc != FTR_OK) return rc;
+  return pruned_logprobs_fwd(logits, symbols, ranges, boundary, termination_symbol, delay_penalty, lse, px, py, B, T, S, C, r, modified, hat, reinterpret_cast<hipStream_t>(stream));
+}
+
 int ftr_pruned_logprobs_fwd_f32(const float* logits, const int32_t* symbols, const int32_t* ranges,
                                 const int32_t* boundary, int termination_symbol, double delay_penalty,
                                 float* lse, float* px, float* py, int B, int T, int S, int C, int r,
                                 int modified, void* stream) {
-  clear_error();
-  FTR_REQUIRE(B >= 0 && T >= 1 && S >= 1 && C >= 1 && r >= 1, "pruned_logprobs_fwd: bad sizes");
-  FTR_REQUIRE(termination_symbol >= 0 && termination_symbol < C, "pruned_logprobs_fwd: termination_symbol %d not in [0,%d)", termination_symbol, C);
-  FTR_REQUIRE(r <= S + 1, "pruned_logprobs_fwd: s_range %d > S+1 = %d", r, S + 1);
-  if (B == 0) return FTR_OK;
-  FTR_REQUIRE(logits && symbols && ranges && lse && px && py, "pruned_logprobs_fwd: null pointer");
-  int rc = device_ok();
-  if (rc != FTR_OK) return rc;
-  return pruned_logprobs_fwd(logits, symbols, ranges, boundary, termination_symbol, delay_penalty, lse, px, py, B, T, S, C, r, modified, reinterpret_cast<hipStream_t>(stream));
+  return pruned_logprobs_fwd_entry(logits, symbols, ranges, boundary, termination_symbol, delay_penalty, lse, px, py, B, T, S, C, r, modified, 0, stream);
+}
+
+int ftr_hat_pruned_logprobs_fwd_f32(const float* logits, const int32_t* symbols, const int32_t* ranges,
+                                    const int32_t* boundary, int termination_symbol, double delay_penalty,
+                                    float* lse, float* px, float* py, int B, int T, int S, int C, int r,
+                                    int modified, void* stream) {
+  return pruned_logprobs_fwd_entry(logits, symbols, ranges, boundary, termination_symbol, delay_penalty, lse, px, py, B, T, S, C, r, modified, 1, stream);
 }
 
 int ftr_pruned_logprobs_bwd_f32(const float* logits, const int32_t* symbols, const int32_t* ranges,
@@ -312,7 +329,7 @@ int ftr_pruned_logprobs_bwd_f32(const float* logits, const int32_t* symbols, con
   FTR_REQUIRE(logits && symbols && ranges && lse && gpx && gpy && glogits, "pruned_logprobs_bwd: null pointer");
   int rc = device_ok();
   if (rc != FTR_OK) return rc;
-  return pruned_logprobs_bwd(logits, symbols, ranges, boundary, termination_symbol, lse, gpx, gpy, Scale{scale, 1, 1.0f}, glogits, B, T, S, C, r, modified, reinterpret_cast<hipStream_t>(stream));
+  return pruned_logprobs_bwd(logits, symbols, ranges, boundary, termination_symbol, lse, gpx, gpy, Scale{scale, 1, 1.0f}, glogits, B, T, S, C, r, modified, 0, reinterpret_cast<hipStream_t>(stream));
 }
 
 int ftr_rowmax_exp_f32(const float* x, float* probs, float* rowmax, long long rows, int C, void* stream) {
@@ -500,20 +517,38 @@ int ftr_negated_reduce_f32(const float* ans, int B, int reduction, float* out, v
   return negated_reduce(ans, B, reduction, out, reinterpret_cast<hipStream_t>(stream));
 }
 
+static int pruned_logprobs_bwd_scaled_entry(const float* logits, const int32_t* symbols, const int32_t* ranges,
+                                            const int32_t* boundary, int termination_symbol, const float* lse,
+                                            const float* gpx, const float* gpy, const float* scale, int scale_stride,
+                                            float scale_mul, float* glogits, int B, int T, int S, int C, int r,
+                                            int modified, int hat, void* stream) {
+  const char* what = hat ? "hat_pruned_logprobs_bwd_scaled" : "pruned_logprobs_bwd_scaled";
+  clear_error();
+  FTR_REQUIRE(B >= 0 && T >= 1 && S >= 0 && C >= 1 && r >= 1, "%s: bad sizes", what);
+  FTR_REQUIRE(!hat || C >= 2, "%s: C = %d, HAT needs a blank and at least one other symbol", what, C);
+  FTR_REQUIRE(termination_symbol >= 0 && termination_symbol < C, "%s: bad termination_symbol", what);
+  FTR_REQUIRE(scale_stride == 0 || scale_stride == 1, "%s: scale_stride must be 0 or 1", what);
+  if (B == 0) return FTR_OK;
+  FTR_REQUIRE(logits && ranges && lse && gpy && glogits && (symbols || S == 0) && (gpx || S == 0), "%s: null pointer", what);
+  int rc = device_ok();
+  if (rc != FTR_OK) return rc;
+  return pruned_logprobs_bwd(logits, symbols, ranges, boundary, termination_symbol, lse, gpx, gpy, Scale{scale, scale_stride, scale_mul}, glogits, B, T, S, C, r, modified, hat, reinterpret_cast<hipStream_t>(stream));
+}
+
 int ftr_pruned_logprobs_bwd_scaled_f32(const float* logits, const int32_t* symbols, const int32_t* ranges,
                                        const int32_t* boundary, int termination_symbol, const float* lse,
                                        const float* gpx, const float* gpy, const float* scale, int scale_stride,
                                        float scale_mul, float* glogits, int B, int T, int S, int C, int r,
                                        int modified, void* stream) {
-  clear_error();
-  FTR_REQUIRE(B >= 0 && T >= 1 && S >= 0 && C >= 1 && r >= 1, "pruned_logprobs_bwd_scaled: bad sizes");
-  FTR_REQUIRE(termination_symbol >= 0 && termination_symbol < C, "pruned_logprobs_bwd_scaled: bad termination_symbol");
-  FTR_REQUIRE(scale_stride == 0 || scale_stride == 1, "pruned_logprobs_bwd_scaled: scale_stride must be 0 or 1");
-  if (B == 0) return FTR_OK;
-  FTR_REQUIRE(logits && ranges && lse && gpy && glogits && (symbols || S == 0) && (gpx || S == 0), "pruned_logprobs_bwd_scaled: null pointer");
-  int rc = device_ok();
-  if (rc != FTR_OK) return rc;
-  return pruned_logprobs_bwd(logits, symbols, ranges, boundary, termination_symbol, lse, gpx, gpy, Scale{scale, scale_stride, scale_mul}, glogits, B, T, S, C, r, modified, reinterpret_cast<hipStream_t>(stream));
+  return pruned_logprobs_bwd_scaled_entry(logits, symbols, ranges, boundary, termination_symbol, lse, gpx, gpy, scale, scale_stride, scale_mul, glogits, B, T, S, C, r, modified, 0, stream);
+}
+
+int ftr_hat_pruned_logprobs_bwd_scaled_f32(const float* logits, const int32_t* symbols, const int32_t* ranges,
+                                           const int32_t* boundary, int termination_symbol, const float* lse,
+                                           const float* gpx, const float* gpy, const float* scale, int scale_stride,
+                                           float scale_mul, float* glogits, int B, int T, int S, int C, int r,
+                                           int modified, void* stream) {
+  return pruned_logprobs_bwd_scaled_entry(logits, symbols, ranges, boundary, termination_symbol, lse, gpx, gpy, scale, scale_stride, scale_mul, glogits, B, T, S, C, r, modified, 1, stream);
 }
 
 int ftr_simple_logprobs_bwd_w_scaled_f32(const float* gpx, const float* gpy, const float* scale, int scale_stride,
@@ -673,23 +708,37 @@ int ftr_smoothed_logprobs_bwd_am_scaled_f32(const float* gpx, const float* gpy, 
 
 int ftr_mutual_information_band_supported(int T, int S, int r) { return mi_band_supported(T, S, r); }
 
-int ftr_pruned_band_fwd_f32(const float* logits, const int32_t* symbols, const int32_t* ranges, const int32_t* boundary,
-                            int termination_symbol, double delay_penalty, float* lse, float* px_band, float* py_band,
-                            int B, int T, int S, int C, int r, int modified, void* stream) {
+static int pruned_band_fwd_entry(const float* logits, const int32_t* symbols, const int32_t* ranges, const int32_t* boundary,
+                                 int termination_symbol, double delay_penalty, float* lse, float* px_band, float* py_band,
+                                 int B, int T, int S, int C, int r, int modified, int hat, void* stream) {
+  const char* what = hat ? "hat_pruned_band_fwd" : "pruned_band_fwd";
   clear_error();
-  FTR_REQUIRE(B >= 0 && T >= 1 && S >= 0 && C >= 1 && r >= 1, "pruned_band_fwd: bad sizes");
-  FTR_REQUIRE(termination_symbol >= 0 && termination_symbol < C, "pruned_band_fwd: termination_symbol %d not in [0,%d)", termination_symbol, C);
+  FTR_REQUIRE(B >= 0 && T >= 1 && S >= 0 && C >= 1 && r >= 1, "%s: bad sizes", what);
+  FTR_REQUIRE(!hat || C >= 2, "%s: C = %d, HAT needs a blank and at least one other symbol", what, C);
+  FTR_REQUIRE(termination_symbol >= 0 && termination_symbol < C, "%s: termination_symbol %d not in [0,%d)", what, termination_symbol, C);
   if (B == 0) return FTR_OK;
-  FTR_REQUIRE(logits && ranges && lse && px_band && py_band && (symbols || S == 0), "pruned_band_fwd: null pointer");
+  FTR_REQUIRE(logits && ranges && lse && px_band && py_band && (symbols || S == 0), "%s: null pointer", what);
   int rc = device_ok();
   if (rc != FTR_OK) return rc;
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
   // lse and the band gather are two launches: folding the gather into the lse pass (picking the blank / symbol entries out
   // of the registers that hold the row) was built and measured -- 93 - 95 us against 73 + 9 at c3: the extra per-row scalar
   // work (two divisions, the ranges -> symbols dependency) costs the streaming pass more than the second kernel does
-  rc = lse_rows(logits, lse, (size_t)B * T * r, C, st);
+  rc = lse_rows(logits, lse, (size_t)B * T * r, C, termination_symbol, hat, st);
   if (rc != FTR_OK) return rc;
-  return band_gather(logits, symbols, ranges, boundary, lse, termination_symbol, delay_penalty, px_band, py_band, B, T, S, C, r, modified, st);
+  return band_gather(logits, symbols, ranges, boundary, lse, termination_symbol, delay_penalty, px_band, py_band, B, T, S, C, r, modified, hat, st);
+}
+
+int ftr_pruned_band_fwd_f32(const float* logits, const int32_t* symbols, const int32_t* ranges, const int32_t* boundary,
+                            int termination_symbol, double delay_penalty, float* lse, float* px_band, float* py_band,
+                            int B, int T, int S, int C, int r, int modified, void* stream) {
+  return pruned_band_fwd_entry(logits, symbols, ranges, boundary, termination_symbol, delay_penalty, lse, px_band, py_band, B, T, S, C, r, modified, 0, stream);
+}
+
+int ftr_hat_pruned_band_fwd_f32(const float* logits, const int32_t* symbols, const int32_t* ranges, const int32_t* boundary,
+                                int termination_symbol, double delay_penalty, float* lse, float* px_band, float* py_band,
+                                int B, int T, int S, int C, int r, int modified, void* stream) {
+  return pruned_band_fwd_entry(logits, symbols, ranges, boundary, termination_symbol, delay_penalty, lse, px_band, py_band, B, T, S, C, r, modified, 1, stream);
 }
 
 int ftr_band_ranges_check_i32(const int32_t* ranges, const int32_t* boundary, int32_t* flags, int B, int T, int r, void* stream) {
@@ -724,20 +773,38 @@ int ftr_mutual_information_band_ws_f32(const float* px_band, const float* py_ban
   return mi_band(px_band, py_band, ranges, boundary, workspace, workspace_floats, ans, gx_band, gy_band, B, T, S, r, modified, reinterpret_cast<hipStream_t>(stream));
 }
 
+static int pruned_band_bwd_scaled_entry(const float* logits, const int32_t* symbols, const int32_t* ranges,
+                                        const int32_t* boundary, int termination_symbol, const float* lse,
+                                        const float* gx_band, const float* gy_band, const float* scale, int scale_stride,
+                                        float scale_mul, float* glogits, int B, int T, int S, int C, int r, int modified,
+                                        int hat, void* stream) {
+  const char* what = hat ? "hat_pruned_band_bwd_scaled" : "pruned_band_bwd_scaled";
+  clear_error();
+  FTR_REQUIRE(B >= 0 && T >= 1 && S >= 0 && C >= 1 && r >= 1, "%s: bad sizes", what);
+  FTR_REQUIRE(!hat || C >= 2, "%s: C = %d, HAT needs a blank and at least one other symbol", what, C);
+  FTR_REQUIRE(termination_symbol >= 0 && termination_symbol < C, "%s: bad termination_symbol", what);
+  FTR_REQUIRE(scale_stride == 0 || scale_stride == 1, "%s: scale_stride must be 0 or 1", what);
+  if (B == 0) return FTR_OK;
+  FTR_REQUIRE(logits && ranges && lse && gx_band && gy_band && glogits && (symbols || S == 0), "%s: null pointer", what);
+  int rc = device_ok();
+  if (rc != FTR_OK) return rc;
+  return band_grad_banded(logits, symbols, ranges, boundary, termination_symbol, lse, gx_band, gy_band, Scale{scale, scale_stride, scale_mul}, glogits, B, T, S, C, r, modified, hat, reinterpret_cast<hipStream_t>(stream));
+}
+
 int ftr_pruned_band_bwd_scaled_f32(const float* logits, const int32_t* symbols, const int32_t* ranges,
                                    const int32_t* boundary, int termination_symbol, const float* lse,
                                    const float* gx_band, const float* gy_band, const float* scale, int scale_stride,
                                    float scale_mul, float* glogits, int B, int T, int S, int C, int r, int modified,
                                    void* stream) {
-  clear_error();
-  FTR_REQUIRE(B >= 0 && T >= 1 && S >= 0 && C >= 1 && r >= 1, "pruned_band_bwd_scaled: bad sizes");
-  FTR_REQUIRE(termination_symbol >= 0 && termination_symbol < C, "pruned_band_bwd_scaled: bad termination_symbol");
-  FTR_REQUIRE(scale_stride == 0 || scale_stride == 1, "pruned_band_bwd_scaled: scale_stride must be 0 or 1");
-  if (B == 0) return FTR_OK;
-  FTR_REQUIRE(logits && ranges && lse && gx_band && gy_band && glogits && (symbols || S == 0), "pruned_band_bwd_scaled: null pointer");
-  int rc = device_ok();
-  if (rc != FTR_OK) return rc;
-  return band_grad_banded(logits, symbols, ranges, boundary, termination_symbol, lse, gx_band, gy_band, Scale{scale, scale_stride, scale_mul}, glogits, B, T, S, C, r, modified, reinterpret_cast<hipStream_t>(stream));
+  return pruned_band_bwd_scaled_entry(logits, symbols, ranges, boundary, termination_symbol, lse, gx_band, gy_band, scale, scale_stride, scale_mul, glogits, B, T, S, C, r, modified, 0, stream);
+}
+
+int ftr_hat_pruned_band_bwd_scaled_f32(const float* logits, const int32_t* symbols, const int32_t* ranges,
+                                       const int32_t* boundary, int termination_symbol, const float* lse,
+                                       const float* gx_band, const float* gy_band, const float* scale, int scale_stride,
+                                       float scale_mul, float* glogits, int B, int T, int S, int C, int r, int modified,
+                                       void* stream) {
+  return pruned_band_bwd_scaled_entry(logits, symbols, ranges, boundary, termination_symbol, lse, gx_band, gy_band, scale, scale_stride, scale_mul, glogits, B, T, S, C, r, modified, 1, stream);
 }
 
 int ftr_selftest(void* scratch_dev, void* stream) {

@@ -132,6 +132,22 @@ __device__ __forceinline__ Bound load_boundary(const int32_t* __restrict__ bound
   return r;
 }
 
+// HAT normalisation of one joiner row (pruned_logprobs.hip, mi_band.hip)
+// softplus(v) = log(1 + e^v), with relative accuracy in both tails (log1pf, never logf(1 + ...))
+__device__ __forceinline__ float softplus(float v) { return fmaxf(v, 0.0f) + log1pf(expf(-fabsf(v))); }
+// HAT log-probs of one row from its blank logit xb, the symbol's logit xs and Z: *vy = log sigmoid(xb),
+// *vx = xs - Z - softplus(xb), -inf for a symbol that is the blank
+__device__ __forceinline__ void hat_logprobs(float xb, float xs, float Z, bool sym_is_blank, float* vx, float* vy) {
+  *vy = -softplus(-xb);
+  *vx = sym_is_blank ? -INFINITY : (xs - Z) - softplus(xb);
+}
+// sigmoid(xb) and sigmoid(-xb), each accurate in its small tail
+__device__ __forceinline__ void hat_sigmoids(float xb, float* sp, float* sn) {
+  const float e = expf(-fabsf(xb)), big = 1.0f / (1.0f + e), small = e / (1.0f + e);
+  *sp = xb >= 0.0f ? big : small;
+  *sn = xb >= 0.0f ? small : big;
+}
+
 }  // namespace ftr
 
 // launchers implemented in the kernel files (all return FTR_OK / FTR_ERR_*), called from capi.hip
@@ -152,8 +168,9 @@ int do_pruning(const float* am, const float* lm, const int32_t* ranges, float* a
 size_t do_pruning_bwd_workspace_bytes(int B, int T, int S1, int C, int r);
 int do_pruning_bwd_ws(const float* g_am_p, const float* g_lm_p, const int32_t* ranges, float* d_am, float* d_lm, int B, int T, int S1, int C, int r, void* ws, size_t ws_bytes, hipStream_t st);
 int do_pruning_bwd(const float* g_am_p, const float* g_lm_p, const int32_t* ranges, float* d_am, float* d_lm, int B, int T, int S1, int C, int r, hipStream_t st);
-int pruned_logprobs_fwd(const float* logits, const int32_t* symbols, const int32_t* ranges, const int32_t* boundary, int blank, double delay_penalty, float* lse, float* px, float* py, int B, int T, int S, int C, int r, int modified, hipStream_t st);
-int pruned_logprobs_bwd(const float* logits, const int32_t* symbols, const int32_t* ranges, const int32_t* boundary, int blank, const float* lse, const float* gpx, const float* gpy, Scale scale, float* glogits, int B, int T, int S, int C, int r, int modified, hipStream_t st);
+// hat != 0: the HAT normalisation (lse = non-blank normaliser Z, see pruned_logprobs.hip); hat == 0: the ordinary kernels
+int pruned_logprobs_fwd(const float* logits, const int32_t* symbols, const int32_t* ranges, const int32_t* boundary, int blank, double delay_penalty, float* lse, float* px, float* py, int B, int T, int S, int C, int r, int modified, int hat, hipStream_t st);
+int pruned_logprobs_bwd(const float* logits, const int32_t* symbols, const int32_t* ranges, const int32_t* boundary, int blank, const float* lse, const float* gpx, const float* gpy, Scale scale, float* glogits, int B, int T, int S, int C, int r, int modified, int hat, hipStream_t st);
 int simple_rowmax_exp(const float* x, float* probs, float* rowmax, float* rowsum, const float* dotvec, float* dot, size_t rows, int C, hipStream_t st);
 int simple_rowmax_exp_pair(const float* x1, float* probs1, float* rowmax1, size_t rows1, const float* x2, float* probs2, float* rowmax2, size_t rows2, int C, hipStream_t st);
 int simple_rowdot(const float* x, const float* v, float* dot, size_t rows, int C, hipStream_t st);
@@ -171,16 +188,16 @@ int normalizer_gemm_set_choice(int kind, int B, int T, int S1, int C, int soluti
 int simple_fused_fwd(const float* am, const float* lm, const int32_t* symbols, const float* am_probs, const float* lm_probs, const float* am_max, const float* lm_max, const int32_t* boundary, int blank, double delay_penalty, const float* lmonly_norm, const float* amonly_norm, const float* ulog, float cs, float ls, float as, float* px, float* py, float* prod_out, int B, int T, int S, int C, int modified, hipStream_t st);
 int simple_fused_bwd_am(const float* gpx, const float* gpy, Scale scale, const float* prod, const float* lm_probs, const float* am_probs, const int32_t* symbols, const int32_t* boundary, int blank, float cs, float kdir, const float* uvec, const float* amdot, float as, float* Rout, float* d_am, int B, int T, int S, int C, int modified, hipStream_t st);
 int negated_reduce(const float* ans, int B, int reduction, float* out, hipStream_t st);
-int lse_rows(const float* logits, float* lse, size_t rows, int C, hipStream_t st);
+int lse_rows(const float* logits, float* lse, size_t rows, int C, int blank, int hat, hipStream_t st);
 int mi_band_supported(int T, int S, int r);
 int band_ranges_check(const int32_t* ranges, const int32_t* boundary, int* flags, int B, int T, int r, hipStream_t st);
-int band_gather(const float* logits, const int32_t* symbols, const int32_t* ranges, const int32_t* boundary, const float* lse, int blank, double delay_penalty, float* pxb, float* pyb, int B, int T, int S, int C, int r, int modified, hipStream_t st);
+int band_gather(const float* logits, const int32_t* symbols, const int32_t* ranges, const int32_t* boundary, const float* lse, int blank, double delay_penalty, float* pxb, float* pyb, int B, int T, int S, int C, int r, int modified, int hat, hipStream_t st);
 size_t mi_band_workspace_floats(int B, int T, int S, int r);
 int mi_band_seg_supported(int T, int S, int r);
 size_t mi_band_seg_workspace_floats(int B, int T, int S, int r);
 int mi_band_seg(const float* pxb, const float* pyb, const int32_t* ranges, const int32_t* boundary, float* ws, size_t ws_floats, float* ans, float* gxb, float* gyb, int B, int T, int S, int r, int modified, hipStream_t st);
 int mi_band(const float* pxb, const float* pyb, const int32_t* ranges, const int32_t* boundary, float* ws, size_t ws_floats, float* ans, float* gxb, float* gyb, int B, int T, int S, int r, int modified, hipStream_t st);
-int band_grad_banded(const float* logits, const int32_t* symbols, const int32_t* ranges, const int32_t* boundary, int blank, const float* lse, const float* gxb, const float* gyb, Scale scale, float* glogits, int B, int T, int S, int C, int r, int modified, hipStream_t st);
+int band_grad_banded(const float* logits, const int32_t* symbols, const int32_t* ranges, const int32_t* boundary, int blank, const float* lse, const float* gxb, const float* gyb, Scale scale, float* glogits, int B, int T, int S, int C, int r, int modified, int hat, hipStream_t st);
 int selftest(hipStream_t st, int* result_dev);
 int debug_stamps(unsigned long long* out16);
 int debug_trace(unsigned long long* out, int n);

@@ -57,7 +57,9 @@ __device__ __forceinline__ float row16_sum(float v) {
 // px_band[b,t,k] = px[b, s0+k, t], py_band[b,t,k] = py[b, s0+k, t] of get_rnnt_logprobs_pruned (rnnt_loss.py:942-1016)
 // + the delay-penalty block (:1097-1114): logits[row, symbol] - lse, -inf where the lattice has none (s >= S, the
 // boundary column of the regular type), one thread per band cell.
-template <bool MOD>
+// HAT: lse holds Z (non-blank normaliser), py = log sigmoid(x[blank]), px = x[sym] - Z - softplus(x[blank]), -inf when
+// sym == blank (the helpers of ftr_common.h, shared with band_to_lattice_kernel).
+template <bool MOD, bool HAT>
 __global__ void band_gather_kernel(const float* __restrict__ logits, const int32_t* __restrict__ symbols,
                                    const int32_t* __restrict__ ranges, const int32_t* __restrict__ boundary,
                                    const float* __restrict__ lse, int blank, double delay_penalty,
@@ -73,9 +75,16 @@ __global__ void band_gather_kernel(const float* __restrict__ logits, const int32
   const float l = lse[row];
   float vy = -INFINITY, vx = -INFINITY;
   if (s >= 0 && s <= S) {
-    vy = logits[row * C + blank] - l;
+    if (HAT) {
+      const float xb = logits[row * C + blank];
+      int c = blank;
+      if (s < S) c = min(max(symbols[(size_t)b * S + s], 0), C - 1);
+      hat_logprobs(xb, logits[row * C + c], l, c == blank, &vx, &vy);   // s == S: c == blank, vx = -inf
+    } else {
+      vy = logits[row * C + blank] - l;
+    }
     if (s < S) {
-      vx = logits[row * C + min(max(symbols[(size_t)b * S + s], 0), C - 1)] - l;
+      if (!HAT) vx = logits[row * C + min(max(symbols[(size_t)b * S + s], 0), C - 1)] - l;
       if (!MOD && t == te) vx = -INFINITY;
       if (delay_penalty > 0.0) vx += (float)((((double)te - 1.0) / 2.0 - (double)t) * delay_penalty);
     }
@@ -712,7 +721,8 @@ __global__ __launch_bounds__(kBandThreads) void mi_band_stream_kernel(
 
 // ---------------------------------------------------------------------------------------- gradient w.r.t. logits
 // the band_grad_kernel of pruned_logprobs.hip with the occupancies read band shaped (row = (b,t,k)); one wave per row.
-template <bool VEC>
+// HAT: g[c] = gx (1[c == sym] - exp(x[c] - Z)) for c != blank, g[blank] = gy sigmoid(-x[blank]) - gx sigmoid(x[blank]).
+template <bool VEC, bool HAT>
 __global__ void band_grad_banded_kernel(const float* __restrict__ logits, const int32_t* __restrict__ symbols,
                                         const int32_t* __restrict__ ranges, const int32_t* __restrict__ boundary,
                                         const float* __restrict__ lse, const float* __restrict__ gxb,
@@ -740,8 +750,13 @@ __global__ void band_grad_banded_kernel(const float* __restrict__ logits, const 
     if (modified || t != te) gx = gxb[row] * sc;
   }
   const float gy = sok ? gyb[row] * sc : 0.0f;
-  const float tot = gx + gy;
+  float tot = gx + gy;
   const float l = lse[row];
+  if (HAT) {   // after the row's loads are issued, so none of them waits for the symbol
+    sym = min(max(sym, 0), C - 1);       // the column the forward read
+    if (sym == blank) gx = 0.0f;         // px is -inf there
+    tot = gx;
+  }
   const float* x = logits + row * C;
   float* g = glogits + row * C;
   if (VEC) {
@@ -756,7 +771,15 @@ __global__ void band_grad_banded_kernel(const float* __restrict__ logits, const 
         const int cc = 4 * i + e;
         float val = -tot * __expf(v[e] - l);
         if (cc == sym) val += gx;
-        if (cc == blank) val += gy;
+        if (cc == blank) {
+          if (HAT) {    // sigmoid(x[blank]) once per row, by the lane that holds the blank column
+            float sp, sn;
+            hat_sigmoids(v[e], &sp, &sn);
+            val = gy * sn - gx * sp;
+          } else {
+            val += gy;
+          }
+        }
         o[e] = val;
       }
       g4[i] = o;
@@ -765,7 +788,15 @@ __global__ void band_grad_banded_kernel(const float* __restrict__ logits, const 
     for (int cc = lane; cc < C; cc += 64) {
       float val = -tot * __expf(x[cc] - l);
       if (cc == sym) val += gx;
-      if (cc == blank) val += gy;
+      if (cc == blank) {
+        if (HAT) {
+          float sp, sn;
+          hat_sigmoids(x[cc], &sp, &sn);
+          val = gy * sn - gx * sp;
+        } else {
+          val += gy;
+        }
+      }
       g[cc] = val;
     }
   }
@@ -815,12 +846,15 @@ int band_ranges_check(const int32_t* ranges, const int32_t* boundary, int* flags
 
 int band_gather(const float* logits, const int32_t* symbols, const int32_t* ranges, const int32_t* boundary,
                 const float* lse, int blank, double delay_penalty, float* pxb, float* pyb, int B, int T, int S, int C,
-                int r, int modified, hipStream_t st) {
+                int r, int modified, int hat, hipStream_t st) {
   const size_t rows = (size_t)B * T * r;
   if (rows == 0) return FTR_OK;
   const unsigned blocks = (unsigned)((rows + 255) / 256);
-  if (modified) hipLaunchKernelGGL(band_gather_kernel<true>, dim3(blocks), dim3(256), 0, st, logits, symbols, ranges, boundary, lse, blank, delay_penalty, pxb, pyb, rows, T, S, C, r);
-  else hipLaunchKernelGGL(band_gather_kernel<false>, dim3(blocks), dim3(256), 0, st, logits, symbols, ranges, boundary, lse, blank, delay_penalty, pxb, pyb, rows, T, S, C, r);
+#define FTR_LAUNCH_BGA(MODV, HATV) hipLaunchKernelGGL((band_gather_kernel<MODV, HATV>), dim3(blocks), dim3(256), 0, st, \
+    logits, symbols, ranges, boundary, lse, blank, delay_penalty, pxb, pyb, rows, T, S, C, r)
+  if (modified) { if (hat) FTR_LAUNCH_BGA(true, true); else FTR_LAUNCH_BGA(true, false); }
+  else { if (hat) FTR_LAUNCH_BGA(false, true); else FTR_LAUNCH_BGA(false, false); }
+#undef FTR_LAUNCH_BGA
   return check_launch("band_gather");
 }
 
@@ -884,13 +918,16 @@ extern "C" int ftr_debug_band_stamps(unsigned long long* out) {
 
 int band_grad_banded(const float* logits, const int32_t* symbols, const int32_t* ranges, const int32_t* boundary,
                      int blank, const float* lse, const float* gxb, const float* gyb, Scale scale, float* glogits, int B,
-                     int T, int S, int C, int r, int modified, hipStream_t st) {
+                     int T, int S, int C, int r, int modified, int hat, hipStream_t st) {
   const size_t rows = (size_t)B * T * r;
   if (rows == 0) return FTR_OK;
   const int wpb = 4;
   const unsigned blocks = (unsigned)((rows + wpb - 1) / wpb);
-  if ((C & 3) == 0) hipLaunchKernelGGL(band_grad_banded_kernel<true>, dim3(blocks), dim3(64 * wpb), 0, st, logits, symbols, ranges, boundary, lse, gxb, gyb, scale, blank, modified, glogits, rows, T, S, C, r);
-  else hipLaunchKernelGGL(band_grad_banded_kernel<false>, dim3(blocks), dim3(64 * wpb), 0, st, logits, symbols, ranges, boundary, lse, gxb, gyb, scale, blank, modified, glogits, rows, T, S, C, r);
+#define FTR_LAUNCH_BGB(VECV, HATV) hipLaunchKernelGGL((band_grad_banded_kernel<VECV, HATV>), dim3(blocks), dim3(64 * wpb), 0, st, \
+    logits, symbols, ranges, boundary, lse, gxb, gyb, scale, blank, modified, glogits, rows, T, S, C, r)
+  if ((C & 3) == 0) { if (hat) FTR_LAUNCH_BGB(true, true); else FTR_LAUNCH_BGB(true, false); }
+  else { if (hat) FTR_LAUNCH_BGB(false, true); else FTR_LAUNCH_BGB(false, false); }
+#undef FTR_LAUNCH_BGB
   return check_launch("band_grad_banded");
 }
 

@@ -6,6 +6,9 @@
 //   band_to_lattice_kernel :943-1016 gathers + pad + roll + transpose + fix_for_boundary, one thread per
 //                          lattice cell, coalesced along t: px/py are written exactly once, complete
 //   band_grad_kernel       gradient w.r.t. logits: -(gx+gy) softmax + gx 1[sym] + gy 1[blank]
+// HAT (hybrid autoregressive transducer, MI355X addition): each kernel has a `bool HAT` twin that normalises the row
+// differently -- lse holds Z = logsumexp over the non-blank columns, py = log sigmoid(x[blank]),
+// px = x[sym] - Z - softplus(x[blank]) (-inf when sym == blank); the HAT = false instantiations are the ordinary kernels.
 #include "ftr_common.h"
 
 namespace ftr {
@@ -20,9 +23,10 @@ __device__ __forceinline__ float wave_sum(float v) { return wave_sum_dpp(v); }
 // while one is reduced: 73 us at c3 = 4.4 TB/s; scripts/probes/stream_probe.hip measures the plain form below at 55 us =
 // 5.8 TB/s on the same tensor -- a flat read reaches 6.7 -- and 205 against 250 us at c4.  The memory system likes many short
 // waves better than few clever ones.)
-template <int NQ>
+// HAT: the blank column is masked to -inf before the max and the sum (lse = Z, the non-blank normaliser).
+template <int NQ, bool HAT>
 __global__ __launch_bounds__(256) void lse_rows_reg_kernel(const float* __restrict__ logits, float* __restrict__ lse,
-                                                           size_t rows, int C) {
+                                                           size_t rows, int C, int blank) {
   const int lane = threadIdx.x & 63;
   // LAST ROWS FIRST.  The joiner has just written `logits` front to back, 320 MB at c3 against 256 MB of memory-side cache:
   // what is still in the cache is the tail.  Walking front to back misses the cache on the head AND pushes the dirty tail out
@@ -39,6 +43,10 @@ __global__ __launch_bounds__(256) void lse_rows_reg_kernel(const float* __restri
   for (int q = 0; q < NQ; ++q) {
     const int i = lane + 64 * q;
     v[q] = (i < n4) ? (f4)x4[i] : ninf;
+    if (HAT) {
+#pragma unroll
+      for (int e = 0; e < 4; ++e) v[q][e] = (4 * i + e == blank) ? -INFINITY : v[q][e];
+    }
   }
   float m = -INFINITY;
 #pragma unroll
@@ -55,8 +63,8 @@ __global__ __launch_bounds__(256) void lse_rows_reg_kernel(const float* __restri
 }
 
 // logsumexp of each row of length C; rows = B*T*r.  One wave per row (any C).
-template <bool VEC>
-__global__ void lse_rows_kernel(const float* __restrict__ logits, float* __restrict__ lse, size_t rows, int C) {
+template <bool VEC, bool HAT>
+__global__ void lse_rows_kernel(const float* __restrict__ logits, float* __restrict__ lse, size_t rows, int C, int blank) {
   const int lane = threadIdx.x & 63;
   const size_t row = (size_t)blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
   if (row >= rows) return;
@@ -65,27 +73,38 @@ __global__ void lse_rows_kernel(const float* __restrict__ logits, float* __restr
   if (VEC) {
     const f4u* x4 = reinterpret_cast<const f4u*>(x);
     const int n4 = C >> 2;
-    for (int i = lane; i < n4; i += 64) { const f4 v = x4[i]; m = fmaxf(fmaxf(m, fmaxf(v[0], v[1])), fmaxf(v[2], v[3])); }
+    for (int i = lane; i < n4; i += 64) {
+      f4 v = x4[i];
+      if (HAT) {
+#pragma unroll
+        for (int e = 0; e < 4; ++e) v[e] = (4 * i + e == blank) ? -INFINITY : v[e];
+      }
+      m = fmaxf(fmaxf(m, fmaxf(v[0], v[1])), fmaxf(v[2], v[3]));
+    }
     m = wave_max(m);
     float s = 0.0f;
     for (int i = lane; i < n4; i += 64) {  // second pass hits L1/L2: a row is 2-4 KB
-      const f4 v = x4[i];
+      f4 v = x4[i];
+      if (HAT) {
+#pragma unroll
+        for (int e = 0; e < 4; ++e) v[e] = (4 * i + e == blank) ? -INFINITY : v[e];
+      }
       s += __expf(v[0] - m) + __expf(v[1] - m) + __expf(v[2] - m) + __expf(v[3] - m);
     }
     s = wave_sum(s);
     if (lane == 0) lse[row] = m + __logf(s);
   } else {
-    for (int i = lane; i < C; i += 64) m = fmaxf(m, x[i]);
+    for (int i = lane; i < C; i += 64) m = fmaxf(m, (HAT && i == blank) ? -INFINITY : x[i]);
     m = wave_max(m);
     float s = 0.0f;
-    for (int i = lane; i < C; i += 64) s += __expf(x[i] - m);
+    for (int i = lane; i < C; i += 64) s += __expf(((HAT && i == blank) ? -INFINITY : x[i]) - m);
     s = wave_sum(s);
     if (lane == 0) lse[row] = m + __logf(s);
   }
 }
 
 // grid: (ceil((T+1)/256), S+1, B); thread <-> (b, s, t).  Writes py[b,s,t] (t < T) and px[b,s,t] (s < S, t < T1).
-template <bool MOD>
+template <bool MOD, bool HAT>
 __global__ void band_to_lattice_kernel(const float* __restrict__ logits, const int32_t* __restrict__ symbols,
                                        const int32_t* __restrict__ ranges, const int32_t* __restrict__ boundary,
                                        const float* __restrict__ lse, int blank, double delay_penalty,
@@ -104,8 +123,18 @@ __global__ void band_to_lattice_kernel(const float* __restrict__ logits, const i
     if (k < r) {
       const size_t row = bt * r + k;
       const float l = lse[row];
-      vy = logits[row * C + blank] - l;                       // :995-996
-      if (s < S) vx = logits[row * C + min(max(symbols[(size_t)b * S + s], 0), C - 1)] - l;   // :961-965 (symbol kept in bounds)
+      if (HAT) {
+        const float xb = logits[row * C + blank];
+        int c = blank;
+        if (s < S) c = min(max(symbols[(size_t)b * S + s], 0), C - 1);
+        float hx, hy;
+        hat_logprobs(xb, logits[row * C + c], l, c == blank, &hx, &hy);
+        vy = hy;
+        if (s < S) vx = hx;
+      } else {
+        vy = logits[row * C + blank] - l;                       // :995-996
+        if (s < S) vx = logits[row * C + min(max(symbols[(size_t)b * S + s], 0), C - 1)] - l;   // :961-965 (symbol kept in bounds)
+      }
     }
   }
   if (t < T) py[((size_t)b * (S + 1) + s) * T + t] = vy;
@@ -120,7 +149,8 @@ __global__ void band_to_lattice_kernel(const float* __restrict__ logits, const i
 }
 
 // one wave per (b,t,k) row of glogits.
-template <bool MOD, bool VEC>
+// HAT: g[c] = gx (1[c == sym] - exp(x[c] - Z)) for c != blank, g[blank] = gy sigmoid(-x[blank]) - gx sigmoid(x[blank]).
+template <bool MOD, bool VEC, bool HAT>
 __global__ void band_grad_kernel(const float* __restrict__ logits, const int32_t* __restrict__ symbols,
                                  const int32_t* __restrict__ ranges, const int32_t* __restrict__ boundary,
                                  const float* __restrict__ lse, const float* __restrict__ gpx,
@@ -147,8 +177,13 @@ __global__ void band_grad_kernel(const float* __restrict__ logits, const int32_t
     if (MOD || t != te) gx = gpx[((size_t)b * S + s) * T1 + t] * sc;   // overwritten cells get no gradient
   }
   const float gy = sok ? gpy[((size_t)b * (S + 1) + s) * T + t] * sc : 0.0f;
-  const float tot = gx + gy;
+  float tot = gx + gy;
   const float l = lse[row];
+  if (HAT) {   // after the row's loads are issued, so none of them waits for the symbol
+    sym = min(max(sym, 0), C - 1);       // the column the forward read
+    if (sym == blank) gx = 0.0f;         // px is -inf there
+    tot = gx;
+  }
   const float* x = logits + row * C;
   float* g = glogits + row * C;
   if (VEC) {
@@ -163,7 +198,15 @@ __global__ void band_grad_kernel(const float* __restrict__ logits, const int32_t
         const int c = 4 * i + e;
         float val = -tot * __expf(v[e] - l);
         if (c == sym) val += gx;
-        if (c == blank) val += gy;
+        if (c == blank) {
+          if (HAT) {    // sigmoid(x[blank]) once per row, by the lane that holds the blank column
+            float sp, sn;
+            hat_sigmoids(v[e], &sp, &sn);
+            val = gy * sn - gx * sp;
+          } else {
+            val += gy;
+          }
+        }
         o[e] = val;
       }
       g4[i] = o;
@@ -172,7 +215,15 @@ __global__ void band_grad_kernel(const float* __restrict__ logits, const int32_t
     for (int c = lane; c < C; c += 64) {
       float val = -tot * __expf(x[c] - l);
       if (c == sym) val += gx;
-      if (c == blank) val += gy;
+      if (c == blank) {
+        if (HAT) {
+          float sp, sn;
+          hat_sigmoids(x[c], &sp, &sn);
+          val = gy * sn - gx * sp;
+        } else {
+          val += gy;
+        }
+      }
       g[c] = val;
     }
   }
@@ -205,46 +256,57 @@ int negated_reduce(const float* ans, int B, int reduction, float* out, hipStream
 }
 
 // logsumexp over the last axis of [rows, C] (rnnt_loss.py:942): picks the register-resident kernel where it fits
-int lse_rows(const float* logits, float* lse, size_t rows, int C, hipStream_t st) {
-  if (rows == 0) return FTR_OK;
+// (hat: over the non-blank columns only, the normaliser Z of the HAT factorisation)
+template <bool HAT>
+static void lse_rows_launch(const float* logits, float* lse, size_t rows, int C, int blank, hipStream_t st) {
   const int wpb = 4;
   const unsigned blocks = (unsigned)((rows + wpb - 1) / wpb);
-  if ((C & 3) == 0 && C <= 256) hipLaunchKernelGGL((lse_rows_reg_kernel<1>), dim3(blocks), dim3(64 * wpb), 0, st, logits, lse, rows, C);
-  else if ((C & 3) == 0 && C <= 512) hipLaunchKernelGGL((lse_rows_reg_kernel<2>), dim3(blocks), dim3(64 * wpb), 0, st, logits, lse, rows, C);
-  else if ((C & 3) == 0 && C <= 1024) hipLaunchKernelGGL((lse_rows_reg_kernel<4>), dim3(blocks), dim3(64 * wpb), 0, st, logits, lse, rows, C);
-  else if ((C & 3) == 0 && C <= 2048) hipLaunchKernelGGL((lse_rows_reg_kernel<8>), dim3(blocks), dim3(64 * wpb), 0, st, logits, lse, rows, C);
-  else if ((C & 3) == 0) hipLaunchKernelGGL(lse_rows_kernel<true>, dim3(blocks), dim3(64 * wpb), 0, st, logits, lse, rows, C);
-  else hipLaunchKernelGGL(lse_rows_kernel<false>, dim3(blocks), dim3(64 * wpb), 0, st, logits, lse, rows, C);
+  if ((C & 3) == 0 && C <= 256) hipLaunchKernelGGL((lse_rows_reg_kernel<1, HAT>), dim3(blocks), dim3(64 * wpb), 0, st, logits, lse, rows, C, blank);
+  else if ((C & 3) == 0 && C <= 512) hipLaunchKernelGGL((lse_rows_reg_kernel<2, HAT>), dim3(blocks), dim3(64 * wpb), 0, st, logits, lse, rows, C, blank);
+  else if ((C & 3) == 0 && C <= 1024) hipLaunchKernelGGL((lse_rows_reg_kernel<4, HAT>), dim3(blocks), dim3(64 * wpb), 0, st, logits, lse, rows, C, blank);
+  else if ((C & 3) == 0 && C <= 2048) hipLaunchKernelGGL((lse_rows_reg_kernel<8, HAT>), dim3(blocks), dim3(64 * wpb), 0, st, logits, lse, rows, C, blank);
+  else if ((C & 3) == 0) hipLaunchKernelGGL((lse_rows_kernel<true, HAT>), dim3(blocks), dim3(64 * wpb), 0, st, logits, lse, rows, C, blank);
+  else hipLaunchKernelGGL((lse_rows_kernel<false, HAT>), dim3(blocks), dim3(64 * wpb), 0, st, logits, lse, rows, C, blank);
+}
+int lse_rows(const float* logits, float* lse, size_t rows, int C, int blank, int hat, hipStream_t st) {
+  if (rows == 0) return FTR_OK;
+  if (hat) lse_rows_launch<true>(logits, lse, rows, C, blank, st);
+  else lse_rows_launch<false>(logits, lse, rows, C, blank, st);
   return check_launch("lse_rows");
 }
 
 int pruned_logprobs_fwd(const float* logits, const int32_t* symbols, const int32_t* ranges,
                         const int32_t* boundary, int blank, double delay_penalty, float* lse, float* px,
-                        float* py, int B, int T, int S, int C, int r, int modified, hipStream_t st) {
+                        float* py, int B, int T, int S, int C, int r, int modified, int hat, hipStream_t st) {
   const size_t rows = (size_t)B * T * r;
   if (rows == 0) return FTR_OK;
-  int rc = lse_rows(logits, lse, rows, C, st);
+  int rc = lse_rows(logits, lse, rows, C, blank, hat, st);
   if (rc != FTR_OK) return rc;
   const int threads = 256;
   const dim3 grid((T + 1 + threads - 1) / threads, S + 1, B);
-  if (modified) hipLaunchKernelGGL(band_to_lattice_kernel<true>, grid, dim3(threads), 0, st, logits, symbols, ranges, boundary, lse, blank, delay_penalty, px, py, T, S, C, r);
-  else hipLaunchKernelGGL(band_to_lattice_kernel<false>, grid, dim3(threads), 0, st, logits, symbols, ranges, boundary, lse, blank, delay_penalty, px, py, T, S, C, r);
+#define FTR_LAUNCH_BL(MODV, HATV) hipLaunchKernelGGL((band_to_lattice_kernel<MODV, HATV>), grid, dim3(threads), 0, st, \
+    logits, symbols, ranges, boundary, lse, blank, delay_penalty, px, py, T, S, C, r)
+  if (modified) { if (hat) FTR_LAUNCH_BL(true, true); else FTR_LAUNCH_BL(true, false); }
+  else { if (hat) FTR_LAUNCH_BL(false, true); else FTR_LAUNCH_BL(false, false); }
+#undef FTR_LAUNCH_BL
   return check_launch("band_to_lattice");
 }
 
 int pruned_logprobs_bwd(const float* logits, const int32_t* symbols, const int32_t* ranges,
                         const int32_t* boundary, int blank, const float* lse, const float* gpx,
                         const float* gpy, Scale scale, float* glogits, int B, int T, int S, int C,
-                        int r, int modified, hipStream_t st) {
+                        int r, int modified, int hat, hipStream_t st) {
   const size_t rows = (size_t)B * T * r;
   if (rows == 0) return FTR_OK;
   const int wpb = 4;
   const unsigned blocks = (unsigned)((rows + wpb - 1) / wpb);
   const bool vec = (C & 3) == 0;
-#define FTR_LAUNCH_BG(MODV, VECV) hipLaunchKernelGGL((band_grad_kernel<MODV, VECV>), dim3(blocks), dim3(64 * wpb), 0, st, \
+#define FTR_LAUNCH_BG(MODV, VECV, HATV) hipLaunchKernelGGL((band_grad_kernel<MODV, VECV, HATV>), dim3(blocks), dim3(64 * wpb), 0, st, \
     logits, symbols, ranges, boundary, lse, gpx, gpy, scale, blank, glogits, rows, T, S, C, r)
-  if (modified) { if (vec) FTR_LAUNCH_BG(true, true); else FTR_LAUNCH_BG(true, false); }
-  else { if (vec) FTR_LAUNCH_BG(false, true); else FTR_LAUNCH_BG(false, false); }
+#define FTR_LAUNCH_BGV(MODV, HATV) do { if (vec) FTR_LAUNCH_BG(MODV, true, HATV); else FTR_LAUNCH_BG(MODV, false, HATV); } while (0)
+  if (modified) { if (hat) FTR_LAUNCH_BGV(true, true); else FTR_LAUNCH_BGV(true, false); }
+  else { if (hat) FTR_LAUNCH_BGV(false, true); else FTR_LAUNCH_BGV(false, false); }
+#undef FTR_LAUNCH_BGV
 #undef FTR_LAUNCH_BG
   return check_launch("band_grad");
 }

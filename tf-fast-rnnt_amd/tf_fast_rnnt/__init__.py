@@ -11,6 +11,7 @@ from .rnnt_loss import get_rnnt_logprobs_joint
 from .rnnt_loss import get_rnnt_logprobs_pruned
 from .rnnt_loss import get_rnnt_logprobs_smoothed
 from .rnnt_loss import get_rnnt_prune_ranges
+from .rnnt_loss import get_hat_logprobs_joint, get_hat_logprobs_pruned, hat_loss, hat_loss_pruned  # MI355X addition: HAT loss, see hat_loss_pruned
 from .rnnt_loss import rnnt_loss
 from .rnnt_loss import rnnt_loss_pruned
 from .rnnt_loss import rnnt_alignment_pruned                                   # MI355X addition: best-path alignment, see its docstring

@@ -12,6 +12,8 @@ What runs where:
   terms folded in; only the [C]- and [rows]-sized batch statistics (unigram mean, two matvecs) are torch ops;
 * ``get_rnnt_logprobs_joint`` / ``rnnt_loss`` (unpruned, joiner logits [B,T,S+1,C]): the pruned builder's kernels
   with identity ranges (s_range = S+1).
+* ``get_hat_logprobs_pruned`` / ``get_hat_logprobs_joint`` / ``hat_loss_pruned`` / ``hat_loss`` (MI355X addition, no
+  reference counterpart): the same kernels and routes with the HAT normalisation of the joiner output.
 
 Reference bugs that are NOT reproduced: ``rnnt_loss_simple(reduction="mean")``
 raises NameError there (rnnt_loss.py:331) -- here it is the mean; ``boundary=None`` works; the
@@ -429,6 +431,27 @@ def get_rnnt_logprobs_joint(
                                     termination_symbol=termination_symbol, boundary=boundary, rnnt_type=rnnt_type)
 
 
+def get_hat_logprobs_joint(
+    logits: torch.Tensor,
+    symbols: torch.Tensor,
+    termination_symbol: int,
+    boundary: Optional[torch.Tensor] = None,
+    rnnt_type: str = "regular",
+) -> Tuple[torch.Tensor, torch.Tensor]:
+    """HAT form of ``get_rnnt_logprobs_joint`` (MI355X addition): logits [B,T,S+1,C] -> px [B,S,T+1|T], py [B,S+1,T]
+    with the normalisation of ``get_hat_logprobs_pruned``, on identity ranges.  The best path of a HAT model is
+    ``mutual_information_viterbi(*get_hat_logprobs_joint(...), boundary)``."""
+    _check_type(rnnt_type)
+    if logits.dim() != 4:
+        raise ValueError("logits must be [B,T,S+1,C]")
+    B, T, S1, C = logits.shape
+    if tuple(torch.as_tensor(symbols).shape) != (B, S1 - 1):
+        raise ValueError(f"symbols must have shape {(B, S1 - 1)}, got {tuple(torch.as_tensor(symbols).shape)}")
+    _require_gpu(logits, "logits")
+    return get_hat_logprobs_pruned(logits=logits, symbols=symbols, ranges=_identity_ranges(B, T, S1, logits.device),
+                                   termination_symbol=termination_symbol, boundary=boundary, rnnt_type=rnnt_type)
+
+
 def rnnt_loss(
     logits: torch.Tensor,
     symbols: torch.Tensor,
@@ -570,10 +593,11 @@ def do_rnnt_pruning(am: torch.Tensor, lm: torch.Tensor, ranges: torch.Tensor, de
 
 
 class _PrunedLogprobs(torch.autograd.Function):
-    """get_rnnt_logprobs_pruned for regular/modified as two native launches each way."""
+    """get_rnnt_logprobs_pruned for regular/modified as two native launches each way (``hat``: the ftr_hat_* twins,
+    get_hat_logprobs_pruned)."""
 
     @staticmethod
-    def forward(ctx, logits, symbols, ranges, termination_symbol, boundary, modified, delay_penalty):
+    def forward(ctx, logits, symbols, ranges, termination_symbol, boundary, modified, delay_penalty, hat):
         B, T, r, C = logits.shape
         S = symbols.shape[1]
         T1 = T if modified else T + 1
@@ -582,13 +606,15 @@ class _PrunedLogprobs(torch.autograd.Function):
         px = torch.empty((B, S, T1), dtype=torch.float32, device=x.device)
         py = torch.empty((B, S + 1, T), dtype=torch.float32, device=x.device)
         with torch.cuda.device(x.device):
-            _lib.call("ftr_pruned_logprobs_fwd_f32", _ptr(x), _ptr(symbols), _ptr(ranges), _ptr(boundary),
+            _lib.call("ftr_hat_pruned_logprobs_fwd_f32" if hat else "ftr_pruned_logprobs_fwd_f32",
+                                                              _ptr(x), _ptr(symbols), _ptr(ranges), _ptr(boundary),
                                                               int(termination_symbol), float(delay_penalty), _ptr(lse),
                                                               _ptr(px), _ptr(py), B, T, S, C, r, int(modified),
                                                               _stream_ptr(x))
         ctx.save_for_backward(x, symbols, ranges, lse, boundary if boundary is not None else torch.empty(0))
         ctx.has_boundary = boundary is not None
         ctx.meta = (int(termination_symbol), int(modified))
+        ctx.hat = bool(hat)
         return px, py
 
     @staticmethod
@@ -602,10 +628,15 @@ class _PrunedLogprobs(torch.autograd.Function):
         g = torch.empty_like(x)
         gpx = gpx.contiguous(); gpy = gpy.contiguous()
         with torch.cuda.device(x.device):
-            _lib.call("ftr_pruned_logprobs_bwd_f32", _ptr(x), _ptr(symbols), _ptr(ranges), _ptr(boundary), blank,
-                                                              _ptr(lse), _ptr(gpx), _ptr(gpy), None, _ptr(g),
-                                                              B, T, S, C, r, modified, _stream_ptr(x))
-        return g, None, None, None, None, None, None
+            if ctx.hat:   # the HAT twin exists in the _scaled form only: no scale, stride 0, multiplier 1
+                _lib.call("ftr_hat_pruned_logprobs_bwd_scaled_f32", _ptr(x), _ptr(symbols), _ptr(ranges), _ptr(boundary),
+                          blank, _ptr(lse), _ptr(gpx), _ptr(gpy), None, 0, 1.0, _ptr(g), B, T, S, C, r, modified,
+                          _stream_ptr(x))
+            else:
+                _lib.call("ftr_pruned_logprobs_bwd_f32", _ptr(x), _ptr(symbols), _ptr(ranges), _ptr(boundary), blank,
+                                                                  _ptr(lse), _ptr(gpx), _ptr(gpy), None, _ptr(g),
+                                                                  B, T, S, C, r, modified, _stream_ptr(x))
+        return g, None, None, None, None, None, None, None
 
 
 def _pruned_inputs(logits, symbols, ranges, boundary):
@@ -638,13 +669,34 @@ def get_rnnt_logprobs_pruned(
 ) -> Tuple[torch.Tensor, torch.Tensor]:
     """rnnt_loss.py:853-1020.  logits [B,T,s_range,C] -> full-size px [B,S,T+1|T], py [B,S+1,T] with
     -inf outside the pruned band."""
+    return _pruned_logprobs(logits, symbols, ranges, termination_symbol, boundary, rnnt_type, False)
+
+
+def _pruned_logprobs(logits, symbols, ranges, termination_symbol, boundary, rnnt_type, hat):
     _check_type(rnnt_type)
     symbols, ranges, boundary = _pruned_inputs(logits, symbols, ranges, boundary)
     modified = rnnt_type != "regular"
-    px, py = _PrunedLogprobs.apply(logits, symbols, ranges, termination_symbol, boundary, modified, 0.0)
+    px, py = _PrunedLogprobs.apply(logits, symbols, ranges, termination_symbol, boundary, modified, 0.0, hat)
     if rnnt_type == "constrained":
         px = px + py[:, 1:, :]
     return px, py
+
+
+def get_hat_logprobs_pruned(
+    logits: torch.Tensor,
+    symbols: torch.Tensor,
+    ranges: torch.Tensor,
+    termination_symbol: int,
+    boundary: torch.Tensor,
+    rnnt_type: str = "regular",
+) -> Tuple[torch.Tensor, torch.Tensor]:
+    """HAT (hybrid autoregressive transducer) form of ``get_rnnt_logprobs_pruned`` (MI355X addition, no reference
+    counterpart).  The same full-size lattices (-inf outside the band, at px[:,:,T] and at the t_end column of the regular
+    type), but each joiner row x = logits[b,t,k,:] is normalised as HAT does, with blank = termination_symbol:
+    ``py = log sigmoid(x[blank])`` and ``px = x[sym] - logsumexp_{c != blank} x[c] - softplus(x[blank])``, so the blank
+    probability is a separate Bernoulli and the symbols share the rest through a softmax over the non-blank columns.
+    A symbol equal to blank gets px = -inf (and no gradient).  Needs C >= 2.  Differentiable w.r.t. ``logits``."""
+    return _pruned_logprobs(logits, symbols, ranges, termination_symbol, boundary, rnnt_type, True)
 
 
 def rnnt_alignment_pruned(
@@ -731,10 +783,11 @@ class _PrunedLoss(torch.autograd.Function):
     exists) -> in backward() one streaming kernel turns the band-shaped occupancies * upstream gradient into
     d loss / d logits.
     Lattice path (any other ranges): logsumexp + band->lattice, recursion forward / backward on the full-size lattices
-    (what the reference does, rnnt_loss.py:968-1013), the same streaming kernel fed from the lattices."""
+    (what the reference does, rnnt_loss.py:968-1013), the same streaming kernel fed from the lattices.
+    ``hat``: the ftr_hat_* twins of the three logits-reading entry points (hat_loss_pruned); the recursion is the same."""
 
     @staticmethod
-    def forward(ctx, logits, symbols, ranges, termination_symbol, boundary, modified, delay_penalty, code):
+    def forward(ctx, logits, symbols, ranges, termination_symbol, boundary, modified, delay_penalty, code, hat):
         B, T, r, C = logits.shape
         S = symbols.shape[1]
         T1 = T if modified else T + 1
@@ -750,7 +803,8 @@ class _PrunedLoss(torch.autograd.Function):
             ans = torch.empty((B,), dtype=torch.float32, device=x.device)
             with torch.cuda.device(x.device):
                 st = _stream_ptr(x)
-                _lib.call("ftr_pruned_band_fwd_f32", _ptr(x), _ptr(symbols), _ptr(ranges), _ptr(boundary),
+                _lib.call("ftr_hat_pruned_band_fwd_f32" if hat else "ftr_pruned_band_fwd_f32",
+                          _ptr(x), _ptr(symbols), _ptr(ranges), _ptr(boundary),
                           int(termination_symbol), float(delay_penalty), _ptr(lse), _ptr(pxb), _ptr(pyb),
                           B, T, S, C, r, int(modified), st)
                 nws = _lib.lib().ftr_mutual_information_band_workspace_floats(B, T, S, r)   # 0: the LDS-resident kernel
@@ -766,7 +820,8 @@ class _PrunedLoss(torch.autograd.Function):
             px = torch.empty((B, S, T1), dtype=torch.float32, device=x.device)
             py = torch.empty((B, S + 1, T), dtype=torch.float32, device=x.device)
             with torch.cuda.device(x.device):
-                _lib.call("ftr_pruned_logprobs_fwd_f32", _ptr(x), _ptr(symbols), _ptr(ranges), _ptr(boundary),
+                _lib.call("ftr_hat_pruned_logprobs_fwd_f32" if hat else "ftr_pruned_logprobs_fwd_f32",
+                                                                  _ptr(x), _ptr(symbols), _ptr(ranges), _ptr(boundary),
                                                                   int(termination_symbol), float(delay_penalty), _ptr(lse),
                                                                   _ptr(px), _ptr(py), B, T, S, C, r, int(modified),
                                                                   _stream_ptr(x))
@@ -777,6 +832,7 @@ class _PrunedLoss(torch.autograd.Function):
                                       boundary if boundary is not None else torch.empty(0))
         ctx.has_boundary = boundary is not None
         ctx.meta = (int(termination_symbol), int(modified), int(code))
+        ctx.hat = bool(hat)
         return _negated_reduce_native(ans, code)
 
     @staticmethod
@@ -790,11 +846,13 @@ class _PrunedLoss(torch.autograd.Function):
         g = torch.empty_like(x)
         scale, stride, mul = _upstream_scale(g_loss, code, B)
         name = "ftr_pruned_band_bwd_scaled_f32" if ctx.band else "ftr_pruned_logprobs_bwd_scaled_f32"
+        if ctx.hat:
+            name = name.replace("ftr_", "ftr_hat_", 1)
         with torch.cuda.device(x.device):
             _lib.call(name, _ptr(x), _ptr(symbols), _ptr(ranges), _ptr(boundary), blank,
                       _ptr(lse), _ptr(px_grad), _ptr(py_grad), _ptr(scale), stride, mul, _ptr(g),
                       B, T, S, C, r, modified, _stream_ptr(x))
-        return g, None, None, None, None, None, None, None
+        return g, None, None, None, None, None, None, None, None
 
 
 def rnnt_loss_pruned(
@@ -810,17 +868,59 @@ def rnnt_loss_pruned(
 ) -> torch.Tensor:
     """rnnt_loss.py:1022-1130.  Returns the loss only (``calc_gradients`` is accepted and, as in the
     reference, only selects whether the op computes occupancies; here that follows ``requires_grad``)."""
+    return _pruned_loss(logits, symbols, ranges, termination_symbol, boundary, rnnt_type, delay_penalty, reduction, False)
+
+
+def _pruned_loss(logits, symbols, ranges, termination_symbol, boundary, rnnt_type, delay_penalty, reduction, hat):
     _check_type(rnnt_type)
     code = _reduction_code(reduction)
     symbols_i, ranges_i, boundary_i = _pruned_inputs(logits, symbols, ranges, boundary)
     if rnnt_type == "constrained":
-        px, py = get_rnnt_logprobs_pruned(logits=logits, symbols=symbols_i, ranges=ranges_i,
-                                          termination_symbol=termination_symbol, boundary=boundary_i, rnnt_type=rnnt_type)
+        px, py = _pruned_logprobs(logits, symbols_i, ranges_i, termination_symbol, boundary_i, rnnt_type, hat)
         px = _apply_delay_penalty(px, boundary_i, rnnt_type, delay_penalty)
         negated_loss = mutual_information_recursion(px=px, py=py, boundary=boundary_i, calc_gradients=False)
         return _reduce(negated_loss, reduction)
     return _PrunedLoss.apply(logits, symbols_i, ranges_i, termination_symbol, boundary_i, rnnt_type != "regular",
-                             float(delay_penalty) if delay_penalty > 0.0 else 0.0, code)
+                             float(delay_penalty) if delay_penalty > 0.0 else 0.0, code, hat)
+
+
+def hat_loss_pruned(
+    logits: torch.Tensor,
+    symbols: torch.Tensor,
+    ranges: torch.Tensor,
+    termination_symbol: int,
+    boundary: torch.Tensor = None,
+    rnnt_type: str = "regular",
+    delay_penalty: float = 0.0,
+    reduction: Optional[str] = "mean",
+) -> torch.Tensor:
+    """HAT form of ``rnnt_loss_pruned`` (MI355X addition, no reference counterpart): the lattices of
+    ``get_hat_logprobs_pruned`` through the same routes (the band-native recursion for ranges that are a band with
+    r <= 15, the full-size lattices otherwise), delay penalty and reduction as there.  Prune ranges come from the
+    ordinary ``rnnt_loss_simple``, as in the usual pruned HAT recipe."""
+    return _pruned_loss(logits, symbols, ranges, termination_symbol, boundary, rnnt_type, delay_penalty, reduction, True)
+
+
+def hat_loss(
+    logits: torch.Tensor,
+    symbols: torch.Tensor,
+    termination_symbol: int,
+    boundary: Optional[torch.Tensor] = None,
+    rnnt_type: str = "regular",
+    delay_penalty: float = 0.0,
+    reduction: Optional[str] = "mean",
+) -> torch.Tensor:
+    """HAT form of ``rnnt_loss`` on unpruned joiner logits [B,T,S+1,C] (MI355X addition): ``hat_loss_pruned`` with
+    identity ranges."""
+    _check_type(rnnt_type)
+    boundary = _as_boundary(boundary, logits.shape[0], logits.device)
+    _require_gpu(logits, "logits")
+    if logits.dim() != 4:
+        raise ValueError("logits must be [B,T,S+1,C]")
+    B, T, S1, _ = logits.shape
+    return hat_loss_pruned(logits=logits, symbols=symbols, ranges=_identity_ranges(B, T, S1, logits.device),
+                           termination_symbol=termination_symbol, boundary=boundary, rnnt_type=rnnt_type,
+                           delay_penalty=delay_penalty, reduction=reduction)
 
 
 def _colsum_weighted(x: torch.Tensor, w: torch.Tensor, rows: int, C: int, st) -> torch.Tensor:
