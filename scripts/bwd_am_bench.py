@@ -1,5 +1,5 @@
 """Times ftr_simple_logprobs_bwd_am_f32 (the d am epilogue behind the library GEMM) alone on one shape and prints a checksum
-of its output (bit-equality across study builds).  python scripts/bwd_am_bench.py [B T S C]"""
+of its output (bit-equality across builds).  python scripts/bwd_am_bench.py [B T S C]"""
 import hashlib, os, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "tf-fast-rnnt_amd"))

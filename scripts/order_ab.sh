@@ -1,5 +1,5 @@
-# A/B of study builds inside the step: product against _build/libftr_<name>.so for every name in VARIANTS
-# (make -C tf-fast-rnnt_amd/csrc variant NAME=<name> SRC=... DEFS=...); two interleaved rounds; CALLS = native calls to print
+# A/B inside the step: product against _build/libftr_<name>.so (a build of another revision) for every name in VARIANTS;
+# two interleaved rounds; CALLS = native calls to print
 export OUT=$(realpath -m "${OUT:-bench_out}")   # bench lines and profiler output
 mkdir -p "$OUT"
 for cfg in ${CFGS:-c3}; do

@@ -1,5 +1,5 @@
-# A/B of do_pruning_bwd: VARIANTS = default | segN (FTR_PRUNE_SEG=N frames per segment) | NAME of a study build
-# (make -C tf-fast-rnnt_amd/csrc variant NAME=... SRC=prune DEFS=...); per-kernel times by rocprofv3
+# A/B of do_pruning_bwd: VARIANTS = default | segN (FTR_PRUNE_SEG=N frames per segment) | NAME of a build of another
+# revision of prune.hip (_build/libftr_NAME.so); per-kernel times by rocprofv3
 R=${GRAFT_REPO_ROOT:-$PWD}
 B=$R/tf-fast-rnnt_amd/csrc/_build
 cd /tmp && export TMPDIR=/tmp

@@ -67,15 +67,9 @@ namespace {
 // lead at the ~0.75 us slots the 4-wave workgroup reaches (3 left the IO-in wave waiting on memory, 76.8 -> 62.0 us
 // at c3); the flow pass has one stream and is not helped; a short poll back-off (128 instead of 1536 cycles) trims the
 // detection delay of every band hop.
-#ifndef FTR_NPF_FWD
-#define FTR_NPF_FWD 4
-#endif
-#ifndef FTR_NPF_FLOW
-#define FTR_NPF_FLOW 4
-#endif
-#ifndef FTR_POLL_SLEEP
-#define FTR_POLL_SLEEP 2
-#endif
+constexpr int kNpfFwd = 4;      // forward kernel: chunks in flight in the IO-in wave
+constexpr int kNpfFlow = 4;     // flow kernel: the same
+constexpr int kPollSleep = 2;   // s_sleep argument (units of 64 cycles) between two polls
 #ifndef FTR_MAX_SPIN
 #define FTR_MAX_SPIN 400000
 #endif
@@ -144,7 +138,7 @@ __device__ __forceinline__ bool comm_wait(u64* gran_in, int m, int lane, u64& g,
       if (lane == 0) __hip_atomic_fetch_or(status, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);   // sticky
       return false;
     }
-    __builtin_amdgcn_s_sleep(FTR_POLL_SLEEP);
+    __builtin_amdgcn_s_sleep(kPollSleep);
     g = __hip_atomic_load(gran_in + idx, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
   }
   return true;
@@ -207,7 +201,7 @@ __device__ __forceinline__ void bidir_fwd_body(unsigned char* smem, const float*
                                                int S, int T, int jstop) {
   constexpr int SKEW = MOD ? 0 : 1;
   constexpr int NOFF = MOD ? 1 : 0;
-  constexpr int NPF = FTR_NPF_FWD;
+  constexpr int NPF = kNpfFwd;
   // at slot kc the COMM wave imports the upper band's chunk kc + LOOK: the compute wave reads it from the ring at the
   // start of slot kc + 1 for its chunk kc + 1, which needs the upper chunk kc + 1 + 4 (regular: lane 0's neighbour is
   // 63 steps ahead, plus one carried element) / kc + 1 (modified)
@@ -333,9 +327,7 @@ __device__ __forceinline__ void bidir_fwd_body(unsigned char* smem, const float*
         // the element in front of chunk 0's first ring value: the band above's step 63 (regular; imported with its
         // chunk 3 by now), nothing (modified: the ring still holds its initial -inf there)
         if (kc == 0) ecarry = in_ring[RINGN - 1];
-#ifndef FTR_EXP_NOCOMPUTE
         compute_chunk(kc, cur);
-#endif
       }
       FTR_SYNC();
 #if defined(FTR_TRACE) && FTR_TRACE == 1
@@ -403,9 +395,6 @@ __device__ __forceinline__ void bidir_fwd_body(unsigned char* smem, const float*
           if (shift_sample_ok(smp_y[u])) { sy += smp_y[u]; ny += 1.0f; }
         }
         Shift sh = shift_from_sums<MOD>(wave_sum_dpp(sx), wave_sum_dpp(nx), wave_sum_dpp(sy), wave_sum_dpp(ny), Sn, Tn);
-#ifdef FTR_EXP_NOSTATIC   // study build: no operand shift
-        sh.cx2 = 0.0f; sh.cy2 = 0.0f;
-#endif
         if (lane == 0) {
           shift_lds[0] = sh.cx2; shift_lds[1] = sh.cy2;
           if (w == 0 && !REVM) { pmid_store(cxy_b, sh.cx2); pmid_store(cxy_b + 1, sh.cy2); }   // for the cut reduction
@@ -427,19 +416,12 @@ __device__ __forceinline__ void bidir_fwd_body(unsigned char* smem, const float*
             const float drift = (mx_prev > kNegThresh) ? (mx - mx_prev) + (float)step_0 : 0.0f;
             step_3 = min(max((int)__builtin_rintf(mx + 2.5f * drift) - step_1 - step_2, -kStepMax), kStepMax);
           }
-#ifdef FTR_EXP_NOFRAMES   // study build: no renormalisation
-          step_3 = 0;
-#endif
           mx_prev = mx;
           if (lane == 0) sring[(k + 3) & 7] = (float)step_3;
           step_0 = step_1; step_1 = step_2; step_2 = step_3;      // now: step_0 = step[k + 1], step_1 = step[k + 2], step_2 = step[k + 3]
         }
       }
-#ifdef FTR_EXP_NOPOLL
-      if (false) {
-#else
       if (has_up && !dead && m >= 0 && m < klast_up) {
-#endif
         // the values are for local chunk kc + 1, whose step this wave set one slot ago (step[kc + 1] = step_1 after the shift
         // above; zero in the warm-up slots)
         if (kc + 1 >= 0 && kc + 1 < klast) frame_rel -= step_1;
@@ -457,9 +439,6 @@ __device__ __forceinline__ void bidir_fwd_body(unsigned char* smem, const float*
             const float mx = wave_max_dpp((lane < CH && v > kNegThresh) ? v : -INFINITY);
             int f0 = 0;
             if (mx > kNegThresh) f0 = min(max(frame_rel + (int)__builtin_rintf(mx), -kStepMax), kStepMax);
-#ifdef FTR_EXP_NOFRAMES
-            f0 = 0;
-#endif
             frame_rel -= f0;
             if (lane == 0) sring[8] = (float)f0;
           }
@@ -707,11 +686,7 @@ __device__ __forceinline__ void bidir_fwd_body(unsigned char* smem, const float*
   };
 
   const int K0 = MOD ? 1 : 4;                                      // 16k - 63*SKEW >= 1
-#ifdef FTR_EXP_ALLGENERIC
-  const int K1 = 0;
-#else
   const int K1 = min((Tn >= CH) ? (Tn - CH) / CH + 1 : 0, klast);  // 16k + 15 < Tn
-#endif
 
   if (wid == 3) {
     // ------------------------------------------------------------------------- IO-out: G, and every store of the hand-off
@@ -738,15 +713,13 @@ __device__ __forceinline__ void bidir_fwd_body(unsigned char* smem, const float*
     for (int gg = 0; gg < NIT * NPF; ++gg) {
       const int kc = base + gg;
       const int k = kc - 1;                 // the chunk the compute wave finished in the previous slot
-#ifndef FTR_EXP_NOTOUCH
       if (has_up && 64 * gg + lane < klast_up) touched = __hip_atomic_load(gran_in + CH * (64 * gg + lane), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-#endif
       if (k >= 0 && k < klast) {
         const float* tp = reinterpret_cast<const float*>(FTR_TP(k));
         // chunk 0: the base frame the COMM wave chose (slots ago) counts as chunk 0's step
         const int step_k = (int)sring[k & 7] + (k == 0 ? (int)sring[8] : 0);
         frame_k += step_k;
-#ifdef FTR_EXP_NOPUBLISH   // test build (tests/test_gpu_mi.py poison path): the first alpha band never publishes
+#ifdef FTR_TEST_NOPUBLISH  // test build (tests/test_gpu_mi.py poison path): the first alpha band never publishes
         if (has_down && lane < CH && !(w == 0 && !REVM)) {
 #else
         if (has_down && lane < CH) {   // lane 63's p of the 16 steps of chunk k -> granules of the band below (first: latency critical)
@@ -983,7 +956,7 @@ __device__ __forceinline__ void bidir_flow_body(unsigned char* smem, const Bound
                                                 int S, int T, int jinj) {
   constexpr int SKEW = MOD ? 0 : 1;
   constexpr int NOFF = MOD ? 1 : 0;
-  constexpr int NPF = FTR_NPF_FLOW;
+  constexpr int NPF = kNpfFlow;
   constexpr int LOOK = MOD ? 1 : 5;      // see the forward body
   constexpr int PRE = NPF + kAhead;
   const int lane = threadIdx.x & 63;
@@ -1076,7 +1049,6 @@ __device__ __forceinline__ void bidir_flow_body(unsigned char* smem, const Bound
     Ops oa, ob;
     auto slot = [&](int kc, const Ops& cur, Ops& nxt) {
       if (kc + 1 >= kfirst && kc + 1 < nchunks) fetch(kc + 1, nxt);
-#ifndef FTR_EXP_FLOW_NOCOMPUTE
       if (kc >= kfirst && kc < nchunks) {
         if (kc == kfirst) {
           ecarry = in_ring[(CH * kfirst - 1) & (RINGN - 1)];   // the element in front of the first chunk
@@ -1085,7 +1057,6 @@ __device__ __forceinline__ void bidir_flow_body(unsigned char* smem, const Bound
           compute_chunk(kc, cur, std::false_type{});
         }
       }
-#endif
       FTR_FSYNC();
 #if defined(FTR_TRACE) && FTR_TRACE == 2
       if (b == 0 && REVM == (FTR_TRACE_DIR == 0) && w == FTR_STAMP_BAND && lane == 0 && 16 + (kc - base) < kTraceN) { g_trace[16 + (kc - base)] = trace_now(); g_trace[4] = kc - base + 1; }
@@ -1207,9 +1178,6 @@ __device__ __forceinline__ void bidir_flow_body(unsigned char* smem, const Bound
     xvalid[m] = r >= 1 && r < Sn;
   }
   auto load_fast = [&](int k, f4 (&gq)[4]) {
-#ifdef FTR_EXP_FLOW_NOLOAD
-    return;
-#endif
     const float* ws_k = REVM ? wsb - CH * k : wsb + CH * k;
 #pragma unroll
     for (int m = 0; m < 4; ++m) {
@@ -1229,9 +1197,6 @@ __device__ __forceinline__ void bidir_flow_body(unsigned char* smem, const Bound
       if (DOY) gy[m] = sY[fq * PLANE + 16 * m + frow];
     }
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");   // all LDS reads in flight together, see the forward body
-#ifdef FTR_EXP_FLOW_NOSTORE
-    if ((DOX ? gx[0][0] : gy[0][0]) != 12345.678f) return;
-#endif
 #pragma unroll
     for (int m = 0; m < 4; ++m) {
       if (DOX && xvalid[m]) *reinterpret_cast<f4u*>(px_k + offPX[m]) = REVM ? rev4(gx[m]) : gx[m];
@@ -1240,11 +1205,7 @@ __device__ __forceinline__ void bidir_flow_body(unsigned char* smem, const Bound
   };
 
   const int K0 = max(MOD ? 1 : 4, kfirst);
-#ifdef FTR_EXP_ALLGENERIC
-  const int K1 = 0;
-#else
   const int K1 = (Tn >= CH) ? (Tn - CH) / CH + 1 : 0;
-#endif
 
   const int K0d = max(MOD ? 1 : 4, kfirst + 1);     // the cut's chunk is drained with the per-step mask
 
@@ -1290,9 +1251,7 @@ __device__ __forceinline__ void bidir_flow_body(unsigned char* smem, const Bound
     for (int gg = 0; gg < NIT * NPF; ++gg) {
       const int kc = base + gg;
       const int k = kc - 1;
-#ifndef FTR_EXP_NOTOUCH
       if (has_up && kfirst_up + 64 * gg + lane < nchunks) touched = __hip_atomic_load(gran_in + CH * (kfirst_up + 64 * gg + lane), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-#endif
       if (k >= kfirst && k < nchunks) {
         if (has_down && k >= kpub && lane < CH) {
           const float* txo = reinterpret_cast<const float*>(FTR_TXO(k));

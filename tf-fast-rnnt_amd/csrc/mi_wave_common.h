@@ -1,4 +1,13 @@
 // csrc/mi_wave_common.h -- constants and helpers of the wavefront kernels (mi_wave_bidir.hip).
+//
+// Build flavours (csrc/Makefile); there are no others, and no macro changes what a kernel computes:
+//   product          `make`: libftr_hip.so, no -D at all
+//   diag             `make tests`: the product + the symbols of include/ftr_diag.h (capi.hip with -DFTR_DIAG, mi_plain.hip)
+//   no-publish       `make tests`: diag whose first alpha band never publishes (-DFTR_TEST_NOPUBLISH, with a lowered
+//                    -DFTR_MAX_SPIN), for the bounded-poll test only
+//   instrumentation  `make STAMPS=1` / `make variant DEFS=...`: -DFTR_STAMPS [-DFTR_STAMP_FLOW], -DFTR_TRACE=1|2|3,
+//                    -DFTR_BAND_STAMPS (mi_band.hip), with -DFTR_STAMP_BAND=n / -DFTR_TRACE_DIR=d to pick what is
+//                    observed: timestamps into g_stamps / g_trace / g_bstamp, the results are the product's
 #pragma once
 #include "ftr_common.h"
 

@@ -10,7 +10,6 @@
 // All integer results are bit-exact with oracle/mi_oracle.c; the float window sums use the same
 // canonical order (sequential f32 cumsum along S, additions only -> no contraction possible).
 #include "ftr_common.h"
-#include <cstring>
 #include <cstdlib>
 #include <limits.h>
 
@@ -177,9 +176,7 @@ __global__ __launch_bounds__(512) void prune_argmax_split_kernel(const float* __
   }
 }
 
-#ifndef FTR_PRUNE_CHK
-#define FTR_PRUNE_CHK 64
-#endif
+constexpr int kPruneChk = 64;   // prune_argmax_once_kernel: rows in flight per array and register set
 // The same with the window length as a template parameter (1 <= R <= 16): every py_grad value is LOADED ONCE.  The lag
 // cumsum consumes, R rows later, what the lead cumsum loaded (carried in registers across chunks), in the same order
 // and with the same additions, so the sums -- and the ranges -- are bit-identical to the kernel above.
@@ -194,7 +191,7 @@ __global__ __launch_bounds__(64) void prune_argmax_once_kernel(const float* __re
   const int nwin = S1 - R + 1;
   const float* pyc = py_grad + (size_t)b * S1 * T + t;
   const float* pxc = px_grad + (size_t)b * S * T1 + t;
-  constexpr int CHK = FTR_PRUNE_CHK;   // rows in flight per array and register set: the walk is sequential, so its time is (rows / CHK) memory round trips
+  constexpr int CHK = kPruneChk;   // the walk is sequential, so its time is (rows / CHK) memory round trips
   // v[i] of a chunk starting at window c0 is py_grad row c0 + i (i < CHK + R): rows c0 .. c0+R-1 come from the previous
   // chunk's tail (`carry`), rows c0+R .. c0+CHK+R-1 are loaded (the "lead" rows of this chunk's windows)
   float carry[R];
@@ -500,9 +497,7 @@ __global__ void do_pruning_bwd_lm_kernel(const float* __restrict__ g_lm_p, const
 // in segment order, or -- irregular segments, or segments that disagree about who owns the row -- rescans the ranges of the
 // segments that touch the row and adds the matching rows of g directly.
 constexpr int kSegIrregular = INT_MAX;
-#ifndef FTR_SEG_ROWS
-#define FTR_SEG_ROWS 16
-#endif
+constexpr int kSegRows = 16;   // rows per batch of pass 1 (frames per batch = kSegRows / R, rounded up)
 
 template <int R, bool FUSE>
 __global__ __launch_bounds__(128) void do_pruning_bwd_seg_kernel(
@@ -553,7 +548,7 @@ __global__ __launch_bounds__(128) void do_pruning_bwd_seg_kernel(
   float* pseg = partial + ((size_t)b * nseg + seg) * (size_t)(2 * r) * C;
   float* dlm_b = d_lm + (size_t)b * S1 * C;
   const f4 z = {0.f, 0.f, 0.f, 0.f};
-  constexpr int FB = (FTR_SEG_ROWS + R - 1) / R;    // frames per batch: about 16 rows; two batches in flight
+  constexpr int FB = (kSegRows + R - 1) / R;    // frames per batch: about 16 rows; two batches in flight
   for (int cb = 0; cb < n4; cb += 128) {
     const int c4 = cb + (int)threadIdx.x;
     const bool live = c4 < n4;
@@ -624,10 +619,7 @@ __global__ __launch_bounds__(128) void do_pruning_bwd_seg_kernel(
 
 // items of the reduction list: bit 31 clear = row index into `partial`, bit 31 set = row index into g_lm_p
 constexpr int RED_CAP = 512;
-#ifndef FTR_RED_WAVES
-#define FTR_RED_WAVES 2
-#endif
-constexpr int RED_WAVES = FTR_RED_WAVES;   // 1, 2 or 4 (c3 / c4 / c5 with 128-frame segments: 8.4 / 16.0 / 27.4, 8.6 / 15.1 / 22.9, 11.0 / 18.2 / 21.8 us)
+constexpr int RED_WAVES = 2;   // 1, 2 or 4 (c3 / c4 / c5 with 128-frame segments: 8.4 / 16.0 / 27.4, 8.6 / 15.1 / 22.9, 11.0 / 18.2 / 21.8 us)
 // One block of RED_WAVES waves per (b,s).  Wave 0 lists the segments that touch the row with ballots and decides: nobody -> zeros;
 // one band segment that owns the row -> pass 1 has written it; band segments that all hold a partial row for it -> those, in
 // segment order; anything else (an irregular segment, or band segments that disagree about the owner: only caller data that is
@@ -846,11 +838,10 @@ int prune_ranges(const float* px_grad, const float* py_grad, const int32_t* boun
   const dim3 grid((T + threads - 1) / threads, B);
 #define FTR_ARGMAX_ONCE(R) case R: hipLaunchKernelGGL(prune_argmax_once_kernel<R>, grid, dim3(threads), 0, st, px_grad, py_grad, boundary, s_begin, B, S, T, T1); break;
   const int nwin = S + 1 - r + 1;
-  static const bool split_off = getenv("FTR_PRUNE_ARGMAX_SPLIT") && !strcmp(getenv("FTR_PRUNE_ARGMAX_SPLIT"), "0");   // A/B knob
-  // ... where one wave per 64 columns leaves the chip short of waves (c3: 512 of them on 256 CUs, 41.5 -> 34 us); with a
+  // the split kernel, where one wave per 64 columns leaves the chip short of waves (c3: 512 of them on 256 CUs, 41.5 -> 34 us); with a
   // thousand and more the one-wave kernel already keeps 8 waves per CU loading and the split only costs (c4 67 -> 109 us,
   // c5 191 -> 436)
-  if (nwin > ftr::kSplitQ && (size_t)((T + 63) / 64) * B <= 768 && !split_off) {
+  if (nwin > ftr::kSplitQ && (size_t)((T + 63) / 64) * B <= 768) {
     const int nc = (nwin + ftr::kSplitQ - 1) / ftr::kSplitQ;
     const int nw = nc < 8 ? nc : 8;
     hipLaunchKernelGGL(prune_argmax_split_kernel, dim3((T + 63) / 64, B), dim3(64 * nw), 0, st, px_grad, py_grad, boundary, s_begin, B, S, T, T1, r);

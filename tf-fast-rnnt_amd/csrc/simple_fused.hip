@@ -65,7 +65,6 @@ __global__ __launch_bounds__(256, 2) void simple_fused_fwd_kernel(
   {
     const unsigned total = gridDim.x * gridDim.y * gridDim.z;
     const size_t rowset = (size_t)16 * NS * C * sizeof(float);
-#ifndef FTR_EXP_FUSED_ORDER_OLD
     // Several symbol tiles per utterance (S + 1 > 16 NS): the tiles of ONE frame block run next to each other on one XCD, so
     // that the frame block's am_probs rows (the A operand) and am rows (the epilogue's gathers) come from memory once instead
     // of once per symbol tile, while the utterance's lm_probs rows -- all of them now -- stay in that L2 (<= 3 MB of its 4).
@@ -74,9 +73,7 @@ __global__ __launch_bounds__(256, 2) void simple_fused_fwd_kernel(
       const unsigned j = (lin & 7u) * (total >> 3) + (lin >> 3);
       by = j % gridDim.y; bx = (j / gridDim.y) % gridDim.x; bz = j / (gridDim.x * gridDim.y);
     }
-    else
-#endif
-    if ((total & 31u) == 0 && rowset <= 512 * 1024) {
+    else if ((total & 31u) == 0 && rowset <= 512 * 1024) {
       const unsigned lin = blockIdx.x + gridDim.x * (blockIdx.y + gridDim.y * blockIdx.z);
       const unsigned per = total >> 3, slot = lin >> 3;
       const unsigned j = (lin & 7u) * per + (slot & 3u) * (per >> 2) + (slot >> 2);
@@ -155,11 +152,7 @@ __global__ __launch_bounds__(256, 2) void simple_fused_fwd_kernel(
     if (SMOOTH) r_ulog = ulog[r_sym];
   }
   const int frag = (lane & 15) * kFLD + 4 * (lane >> 4);   // this lane's row and its 4 of every 16 columns
-#if defined(FTR_FUSED_EXP) && FTR_FUSED_EXP >= 2   // diagnostic: no contraction
-  for (int kc = 0; kc < 0; ++kc) {
-#else
   for (int kc = 0; kc < nk; ++kc) {
-#endif
     if (kc + 1 < nk) gload(kc + 1, v);
     const int cur = NBUF == 2 ? (kc & 1) : 0;
     const float* A = smem + cur * ROWS * kFLD + 16 * wave * kFLD + frag;
@@ -207,9 +200,6 @@ __global__ __launch_bounds__(256, 2) void simple_fused_fwd_kernel(
     __syncthreads();
   }
 
-#if defined(FTR_FUSED_EXP) && FTR_FUSED_EXP == 1   // diagnostic: no epilogue (accumulators summed into one store)
-  { float t = 0.f; for (int m = 0; m < MB; ++m) for (int i = 0; i < NS; ++i) t += acc[m][i][0] + acc[m][i][1] + acc[m][i][2] + acc[m][i][3]; if (t == 123.456f) py[0] = t; return; }
-#endif
   // ---- epilogue: lane (n = lane & 15, q = lane >> 4) holds, per frame block m and symbol block i, frames tq .. tq+3 of row
   // s0 + 16 i + n, tq = t0 + 64 m + 16 wave + 4 q
   const int n = lane & 15;
@@ -217,7 +207,7 @@ __global__ __launch_bounds__(256, 2) void simple_fused_fwd_kernel(
   const float ulog_blank = SMOOTH ? ulog[blank] : 0.0f;
   // am[t, sym(s)] for the 64 x 16 NS cells of a frame block: taken lane by lane in accumulator layout these are 4 NS gathers
   // per lane whose 64 addresses per instruction lie in 64 different lines (4 frames x 16 symbols) -- 105 of the kernel's 540 us
-  // at c4, 23 of 105 at c3 (scripts/fused_split.sh).  Instead the workgroup gathers FRAME by FRAME into the tile's LDS (free
+  // at c4, 23 of 105 at c3 (study build, removed; see the history of scripts/fused_split.sh).  Instead the workgroup gathers FRAME by FRAME into the tile's LDS (free
   // now): one instruction covers 64 symbols of ONE am row (<= 32 lines, the next instruction of the frame hits the same ones),
   // every line of the am tile comes from L2 once, and each lane then reads its four consecutive frames with one ds_read_b128.
   float* asym = smem;                                             // [16 NS][kGLD]
@@ -246,7 +236,6 @@ __global__ __launch_bounds__(256, 2) void simple_fused_fwd_kernel(
 #pragma unroll
   for (int m = 0; m < MB; ++m) {
     if (m > 0) __syncthreads();                                   // the previous block's values have been read
-#if !(defined(FTR_FUSED_EXP) && (FTR_FUSED_EXP == 3 || FTR_FUSED_EXP == 5))
     {                                                             // 16 frames per wave, NSL gathers each, GB frames' worth in
       constexpr int GB = (MB == 2 && NS > 10) ? 8 : 16;                        // flight together (all 16 where the registers allow): taken four
 #pragma unroll                                                    // frames at a time the phase is four memory round trips long
@@ -267,7 +256,6 @@ __global__ __launch_bounds__(256, 2) void simple_fused_fwd_kernel(
           }
       }
     }
-#endif
     __syncthreads();
     const int tq = t0 + 64 * m + 16 * wave + 4 * (lane >> 4);
     if (tq >= T1) continue;                                       // (no barrier below this point inside the block)
@@ -304,9 +292,6 @@ __global__ __launch_bounds__(256, 2) void simple_fused_fwd_kernel(
         if (delay_penalty > 0.0) x += pen[j];
         vx[j] = x;
       }
-#if defined(FTR_FUSED_EXP) && (FTR_FUSED_EXP == 4 || FTR_FUSED_EXP == 5)    // diagnostic: one store per WG instead of all of them
-      if (vy[0] + vx[1] + vp[2] != 123.456f) continue;
-#endif
       float* yrow = py + ((size_t)b * (S + 1) + s) * T + tq;
       if (tq + 3 < T) *reinterpret_cast<f4u*>(yrow) = vy;
       else { for (int j = 0; j < 4; ++j) if (tq + j < T) yrow[j] = vy[j]; }
@@ -478,12 +463,8 @@ __global__ __launch_bounds__(256, 2) void simple_fused_bwd_am_kernel(
     park(0, g);
     __syncthreads();
     for (int kc = 0; kc < nk; ++kc) {
-#if !(defined(FTR_FUSED_BWD_EXP) && FTR_FUSED_BWD_EXP == 3)   // study build 3: no loads in the loop (the first chunk's operands again)
       if (kc + 1 < nk) load(kc + 1, g, true);
-#endif
-#if !(defined(FTR_FUSED_BWD_EXP) && FTR_FUSED_BWD_EXP == 2)   // study build 2: no MFMAs in pass 1
       compute(kc);
-#endif
       if (kc + 1 < nk) park(kc + 1, g);
       __syncthreads();
     }
@@ -559,11 +540,7 @@ __global__ __launch_bounds__(256, 2) void simple_fused_bwd_am_kernel(
     if (all_rows) count = S;
     auto row_of = [&](int i) { return all_rows ? i : (int)rlist[i]; };
     constexpr int NX = kB2 * (kBT / 4) / 256;      // 8 quads per thread and stage
-#if defined(FTR_FUSED_BWD_EXP) && FTR_FUSED_BWD_EXP == 1       // study build 1: no pass 2
-    for (int r0 = 0; r0 < 0; r0 += kB2) {
-#else
     for (int r0 = 0; r0 < count; r0 += kB2) {
-#endif
       f4 xv[NX];
 #pragma unroll
       for (int u = 0; u < NX; ++u) {

@@ -21,11 +21,9 @@ namespace ftr {
 namespace {
 
 constexpr float kTiny = 1.401298464324817e-45f;  // tf.math.nextafter(0., 1.)  (rnnt_loss.py:181)
-#ifndef FTR_TT_NARROW_ABOVE
-#define FTR_TT_NARROW_ABOVE 300
-#endif
+constexpr int kTTnarrowAbove = 300;
 constexpr int kTTwide = 32;                      // frames per tile for small vocabularies
-constexpr int kTTnarrow = 16;                    // above FTR_TT_NARROW_ABOVE columns: more workgroups per CU (LDS) beats longer
+constexpr int kTTnarrow = 16;                    // above kTTnarrowAbove columns: more workgroups per CU (LDS) beats longer
                                                  // row segments (measured at C = 500: fwd 60 -> 47 us, bwd_am 73 -> 65 us; C = 1024: 374 -> 242, 546 -> 420)
 
 __device__ __forceinline__ float wave_max(float v) { return wave_max_dpp(v); }
@@ -304,20 +302,17 @@ __global__ __launch_bounds__(256) void simple_bwd_w_kernel(const float* __restri
   if (lane == 0) { rsx[rowid] = sx; rsy[rowid] = sy; }
 }
 
-#ifndef FTR_BWD_AM_PF
-#define FTR_BWD_AM_PF 1     // frames whose write-out operands are fetched at the top of the kernel.  Measured (scripts/bwd_am_ab.sh,
+constexpr int kBwdAmPF = 1;   // frames whose write-out operands are fetched at the top of the kernel.  Measured (study builds,
+                            // removed; see the history of scripts/bwd_am_ab.sh;
                             // c3 / c2 / c5 / c4 in us): 1 -> 53 / 23.6 / 370 / 281, 4 -> 54.7 / 24.2 / 369 / 277, 6 -> 58.7 / 26.5 / 383 / 290,
                             // 8 at three workgroups per CU -> 63 / 34.5 / 370 / 281 (170 registers), 2 -> 57 / 25.5 / 488 / 306 (!);
                             // 0 -> 51.5 / 24.0 / 402 / 284 (one frame's operands are what gives the write-out its head start);
                             // the previous revision (no prefetch, four loads in flight in the sweeps): 54 / 23.0 / 431 / 299.
-#endif
-#ifndef FTR_BWD_AM_WGS
-#define FTR_BWD_AM_WGS 4    // workgroups per CU the register budget is set for
-#endif
+constexpr int kBwdAmWGs = 4;  // workgroups per CU the register budget is set for
 // grid (ceil(T / TT), B); block 256 = (256/TT) column-owner groups x TT frames.  LDS: acc [TT][C + 1] + csy/csx [256].
 // Thread (ty, tx) owns the accumulator cells acc[tx][c] with c % 8 == ty: every cell has one owner.
 template <bool MOD, int TT>
-__global__ __launch_bounds__(256, FTR_BWD_AM_WGS) void simple_bwd_am_kernel(const float* __restrict__ gpx, const float* __restrict__ gpy, const Scale scale,
+__global__ __launch_bounds__(256, kBwdAmWGs) void simple_bwd_am_kernel(const float* __restrict__ gpx, const float* __restrict__ gpy, const Scale scale,
                                      const float* __restrict__ damp, const float* __restrict__ am_probs,
                                      const int32_t* __restrict__ symbols, const int32_t* __restrict__ boundary,
                                      int blank, float kdir, const float* __restrict__ uvec,
@@ -332,7 +327,6 @@ __global__ __launch_bounds__(256, FTR_BWD_AM_WGS) void simple_bwd_am_kernel(cons
   // the two halves of a line are fetched by two different L2s (PMC: 1.37 x the algorithmic bytes).  Within every 16
   // consecutive linear ids (two per XCD) XCD x now takes the tiles 2x and 2x + 1 of the (utterance-major) tile list.
   int tile = blockIdx.x, b = blockIdx.y;
-#ifndef FTR_EXP_BWD_AM_LAUNCH_ORDER
   if (TT == 16) {
     const unsigned total = gridDim.x * gridDim.y;
     const unsigned lin = blockIdx.x + gridDim.x * blockIdx.y;
@@ -341,15 +335,14 @@ __global__ __launch_bounds__(256, FTR_BWD_AM_WGS) void simple_bwd_am_kernel(cons
       tile = (int)(nl % gridDim.x); b = (int)(nl / gridDim.x);
     }
   }
-#endif
   const int t0 = tile * TT;
   const int T1 = MOD ? T : T + 1;
   const int ld = C + 1;
   // A workgroup is a chain of dependent memory round trips (symbols -> row lists -> the g_px sweep -> the g_py sweep -> the
   // write-out's operands).  With long symbol sequences the sweeps are most of it: they keep 8 loads in flight now instead
   // of 4 (c5 431 -> 369 us, c4 299 -> 278).  Fetching the write-out's operands up here, before the sweeps, buys nothing that
-  // four workgroups per CU do not already hide, and costs occupancy beyond a frame or two (see FTR_BWD_AM_PF).
-  constexpr int NF = TT / 2, PF = NF < FTR_BWD_AM_PF ? NF : FTR_BWD_AM_PF;   // write-out: frames per thread, of which prefetched
+  // four workgroups per CU do not already hide, and costs occupancy beyond a frame or two (see kBwdAmPF).
+  constexpr int NF = TT / 2, PF = NF < kBwdAmPF ? NF : kBwdAmPF;   // write-out: frames per thread, of which prefetched
   const int wo_half = threadIdx.x >> 7, wo_cl = threadIdx.x & 127;
   f4 pdp[PF > 0 ? PF : 1], pap[PF > 0 ? PF : 1];   // (PF = 0: no prefetch, the arrays are unused)
   if ((C & 3) == 0) {
@@ -619,7 +612,7 @@ int simple_logprobs_fwd(const float* am, const float* lm, const int32_t* symbols
                         float cs, float ls, float as, float* px, float* py, int B, int T, int S, int C, int modified,
                         hipStream_t st) {
   const int T1 = modified ? T : T + 1;
-  const bool narrow = C > FTR_TT_NARROW_ABOVE;
+  const bool narrow = C > kTTnarrowAbove;
   const int TT = narrow ? kTTnarrow : kTTwide;
   const size_t lds = sizeof(float) * ((size_t)TT * (C + 1) + 6 * (size_t)(S + 1));
   int rc = tile_lds_ok(lds, "simple_logprobs_fwd");
@@ -651,7 +644,7 @@ int simple_logprobs_bwd_am(const float* gpx, const float* gpy, Scale scale, cons
                            const float* amdot, float as, float* Rout, float* d_am, int B, int T, int S, int C,
                            int modified, hipStream_t st) {
   if (S > 65535) { set_error("simple_logprobs_bwd_am: S = %d > 65535 is not supported", S); return FTR_ERR_UNSUPPORTED; }
-  const bool narrow = C > FTR_TT_NARROW_ABOVE;
+  const bool narrow = C > kTTnarrowAbove;
   const int TT = narrow ? kTTnarrow : kTTwide;
   const size_t lds = sizeof(float) * ((size_t)TT * (C + 1) + 2 * 256) + sizeof(unsigned short) * (256 / TT) * (size_t)S;
   int rc = tile_lds_ok(lds, "simple_logprobs_bwd_am");
