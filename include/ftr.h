@@ -488,6 +488,47 @@ int ftr_hat_pruned_band_bwd_scaled_f32(const float* logits, const int32_t* symbo
                                        int scale_stride, float scale_mul, float* glogits, int B, int T, int S, int C,
                                        int r, int modified, void* stream);
 
+/*
+ * Multi-blank transducer (MI355X addition, no reference counterpart; Xu et al., "Multi-blank Transducers for Speech
+ * Recognition", ICASSP 2023): besides the standard blank, which advances one frame, K "big blanks" advance d_k >= 2
+ * frames.  Regular type only.  D = K + 1 blanks, 1 <= D <= 8; `durations` is a HOST array of D strictly increasing
+ * values in 1..32 (read at launch time: no device read, no host synchronisation, graph-capturable).
+ *
+ * Recursion (csrc/mi_multiblank.hip):
+ *   px [B,S,T+1], py [B,D,S+1,T]  (py[b,j,s,t]: the move (s,t) -> (s,t+durations[j]))
+ *   p[s,t] = logadd(p[s-1,t] + px[s-1,t], (+)_j p[s,t-d_j] + py[j,s,t-d_j]),  p[s_begin,t_begin] = 0,
+ *   ans[b] = p[s_end,t_end]; moves that leave the boundary rectangle are ignored whatever value they carry.
+ *   fwd writes ans [B] and keeps p in `workspace` (ftr_mutual_information_multiblank_workspace_floats(B,S,T) floats,
+ *   8-byte aligned, uninitialised is fine); bwd needs the workspace of the fwd call on the same inputs and writes
+ *   the occupancies px_grad [B,S,T+1], py_grad [B,D,S+1,T] times ans_grad[b] (NULL = ones), zero outside the rectangle.
+ *   A no-path utterance gives ans = -inf and zero gradients.  p and the backward chain are float64 inside.
+ * Builder (csrc/pruned_logprobs.hip): the multi-blank form of ftr_pruned_logprobs_fwd_f32 / _bwd_scaled_f32.  Here
+ *   durations[0] must be 1 (the standard blank, termination_symbol) and big_blank_ids is a HOST array of D - 1 distinct
+ *   column ids in [0,C), none equal to termination_symbol.  Every row is normalised by the ordinary softmax over C;
+ *   sigma >= 0 is subtracted from every log-probability; py[b,j,s,t] = -inf where t + durations[j] > t_end; a symbol
+ *   that is a big-blank id gets px = -inf and no gradient.  gpx / gpy have the shapes of px / py.
+ * Invalid D, durations or ids return FTR_ERR_INVALID_ARG (before any device check) with a message naming the argument.
+ */
+size_t ftr_mutual_information_multiblank_workspace_floats(int B, int S, int T);
+int ftr_mutual_information_multiblank_fwd_f32(const float* px, const float* py, const int32_t* boundary,
+                                              const int32_t* durations, int D, float* workspace,
+                                              size_t workspace_floats, float* ans, int B, int S, int T, void* stream);
+int ftr_mutual_information_multiblank_bwd_f32(const float* px, const float* py, const int32_t* boundary,
+                                              const int32_t* durations, int D, float* workspace,
+                                              size_t workspace_floats, const float* ans_grad, float* px_grad,
+                                              float* py_grad, int B, int S, int T, void* stream);
+int ftr_multiblank_pruned_logprobs_fwd_f32(const float* logits, const int32_t* symbols, const int32_t* ranges,
+                                           const int32_t* boundary, int termination_symbol,
+                                           const int32_t* big_blank_ids, const int32_t* durations, int D, double sigma,
+                                           double delay_penalty, float* lse, float* px, float* py, int B, int T, int S,
+                                           int C, int r, void* stream);
+int ftr_multiblank_pruned_logprobs_bwd_scaled_f32(const float* logits, const int32_t* symbols, const int32_t* ranges,
+                                                  const int32_t* boundary, int termination_symbol,
+                                                  const int32_t* big_blank_ids, const int32_t* durations, int D,
+                                                  const float* lse, const float* gpx, const float* gpy,
+                                                  const float* scale, int scale_stride, float scale_mul,
+                                                  float* glogits, int B, int T, int S, int C, int r, void* stream);
+
 /* Hardware self-test used by smoke()/tests: checks on the device that the primitives the wavefront
  * kernels rely on behave as assumed (full-wave DPP shift wave_shr:1 with lane 0 keeping its old value;
  * 16-byte global loads/stores at 4-byte alignment).  scratch_dev: >= 8 KiB of device memory; after the

@@ -807,6 +807,121 @@ int ftr_hat_pruned_band_bwd_scaled_f32(const float* logits, const int32_t* symbo
   return pruned_band_bwd_scaled_entry(logits, symbols, ranges, boundary, termination_symbol, lse, gx_band, gy_band, scale, scale_stride, scale_mul, glogits, B, T, S, C, r, modified, 1, stream);
 }
 
+// ---- multi-blank transducer (MI355X addition; csrc/mi_multiblank.hip, the mb_* kernels of csrc/pruned_logprobs.hip).
+// D, the durations and the big-blank ids are host data and are validated first, then sizes and pointers, then the device.
+namespace {
+int mb_check_durations(const char* what, const int32_t* durations, int D, bool first_is_one) {
+  FTR_REQUIRE(D >= 1 && D <= 8, "%s: D = %d, the number of blanks must be in 1..8", what, D);
+  FTR_REQUIRE(durations, "%s: null durations", what);
+  for (int j = 0; j < D; ++j) {
+    FTR_REQUIRE(durations[j] >= 1 && durations[j] <= 32, "%s: durations[%d] = %d is outside 1..32", what, j, durations[j]);
+    FTR_REQUIRE(j == 0 || durations[j] > durations[j - 1], "%s: durations must be strictly increasing (durations[%d] = %d after %d)",
+                what, j, durations[j], durations[j - 1]);
+  }
+  FTR_REQUIRE(!first_is_one || durations[0] == 1, "%s: durations[0] = %d, the standard blank advances one frame", what, durations[0]);
+  return FTR_OK;
+}
+int mb_check_ids(const char* what, const int32_t* ids, int D, int blank, int C) {
+  FTR_REQUIRE(C >= 1 && blank >= 0 && blank < C, "%s: termination_symbol %d not in [0,%d)", what, blank, C);
+  FTR_REQUIRE(ids || D == 1, "%s: null big_blank_ids", what);
+  for (int j = 0; j + 1 < D; ++j) {
+    FTR_REQUIRE(ids[j] >= 0 && ids[j] < C, "%s: big_blank_ids[%d] = %d not in [0,%d)", what, j, ids[j], C);
+    FTR_REQUIRE(ids[j] != blank, "%s: big_blank_ids[%d] = %d is the termination_symbol", what, j, ids[j]);
+    for (int i = 0; i < j; ++i)
+      FTR_REQUIRE(ids[i] != ids[j], "%s: big_blank_ids[%d] = %d is a duplicate of big_blank_ids[%d]", what, j, ids[j], i);
+  }
+  return FTR_OK;
+}
+}  // namespace
+
+size_t ftr_mutual_information_multiblank_workspace_floats(int B, int S, int T) {
+  return mi_multiblank_workspace_floats(B, S, T);
+}
+
+int ftr_mutual_information_multiblank_fwd_f32(const float* px, const float* py, const int32_t* boundary,
+                                              const int32_t* durations, int D, float* workspace, size_t workspace_floats,
+                                              float* ans, int B, int S, int T, void* stream) {
+  const char* what = "mutual_information_multiblank_fwd";
+  clear_error();
+  int rc = mb_check_durations(what, durations, D, false);
+  if (rc != FTR_OK) return rc;
+  FTR_REQUIRE(B >= 0 && S >= 0 && T >= 0, "%s: negative size B=%d S=%d T=%d", what, B, S, T);
+  if (B == 0) return FTR_OK;
+  FTR_REQUIRE(workspace_floats >= mi_multiblank_workspace_floats(B, S, T), "%s: workspace of %zu floats is too small, %zu needed",
+              what, workspace_floats, mi_multiblank_workspace_floats(B, S, T));
+  FTR_REQUIRE(workspace && ans && (py || T == 0) && (px || S == 0), "%s: null px / py / workspace / ans", what);
+  FTR_REQUIRE(((uintptr_t)workspace & 7) == 0, "%s: workspace must be 8-byte aligned", what);
+  rc = device_ok();
+  if (rc != FTR_OK) return rc;
+  return mi_multiblank_fwd(px, py, boundary, durations, D, workspace, workspace_floats, ans, B, S, T, reinterpret_cast<hipStream_t>(stream));
+}
+
+int ftr_mutual_information_multiblank_bwd_f32(const float* px, const float* py, const int32_t* boundary,
+                                              const int32_t* durations, int D, float* workspace, size_t workspace_floats,
+                                              const float* ans_grad, float* px_grad, float* py_grad, int B, int S, int T,
+                                              void* stream) {
+  const char* what = "mutual_information_multiblank_bwd";
+  clear_error();
+  int rc = mb_check_durations(what, durations, D, false);
+  if (rc != FTR_OK) return rc;
+  FTR_REQUIRE(B >= 0 && S >= 0 && T >= 0, "%s: negative size B=%d S=%d T=%d", what, B, S, T);
+  if (B == 0) return FTR_OK;
+  FTR_REQUIRE(workspace_floats >= mi_multiblank_workspace_floats(B, S, T), "%s: workspace of %zu floats is too small, %zu needed",
+              what, workspace_floats, mi_multiblank_workspace_floats(B, S, T));
+  FTR_REQUIRE(workspace && (py || T == 0) && (px || S == 0), "%s: null px / py / workspace", what);
+  FTR_REQUIRE((py_grad || T == 0) && (px_grad || S == 0), "%s: null px_grad / py_grad", what);
+  FTR_REQUIRE(((uintptr_t)workspace & 7) == 0, "%s: workspace must be 8-byte aligned", what);
+  rc = device_ok();
+  if (rc != FTR_OK) return rc;
+  return mi_multiblank_bwd(px, py, boundary, durations, D, workspace, workspace_floats, ans_grad, px_grad, py_grad, B, S, T,
+                           reinterpret_cast<hipStream_t>(stream));
+}
+
+int ftr_multiblank_pruned_logprobs_fwd_f32(const float* logits, const int32_t* symbols, const int32_t* ranges,
+                                           const int32_t* boundary, int termination_symbol, const int32_t* big_blank_ids,
+                                           const int32_t* durations, int D, double sigma, double delay_penalty, float* lse,
+                                           float* px, float* py, int B, int T, int S, int C, int r, void* stream) {
+  const char* what = "multiblank_pruned_logprobs_fwd";
+  clear_error();
+  int rc = mb_check_durations(what, durations, D, true);
+  if (rc != FTR_OK) return rc;
+  rc = mb_check_ids(what, big_blank_ids, D, termination_symbol, C);
+  if (rc != FTR_OK) return rc;
+  FTR_REQUIRE(B >= 0 && T >= 1 && S >= 0 && r >= 1, "%s: bad sizes", what);
+  FTR_REQUIRE(r <= S + 1, "%s: s_range %d > S+1 = %d", what, r, S + 1);
+  FTR_REQUIRE(sigma >= 0.0, "%s: sigma = %g must not be negative", what, sigma);
+  if (B == 0) return FTR_OK;
+  FTR_REQUIRE(logits && ranges && lse && py && (symbols || S == 0) && (px || S == 0), "%s: null pointer", what);
+  rc = device_ok();
+  if (rc != FTR_OK) return rc;
+  return multiblank_logprobs_fwd(logits, symbols, ranges, boundary, termination_symbol, big_blank_ids, durations, D, sigma,
+                                 delay_penalty, lse, px, py, B, T, S, C, r, reinterpret_cast<hipStream_t>(stream));
+}
+
+int ftr_multiblank_pruned_logprobs_bwd_scaled_f32(const float* logits, const int32_t* symbols, const int32_t* ranges,
+                                                  const int32_t* boundary, int termination_symbol,
+                                                  const int32_t* big_blank_ids, const int32_t* durations, int D,
+                                                  const float* lse, const float* gpx, const float* gpy, const float* scale,
+                                                  int scale_stride, float scale_mul, float* glogits, int B, int T, int S,
+                                                  int C, int r, void* stream) {
+  const char* what = "multiblank_pruned_logprobs_bwd_scaled";
+  clear_error();
+  int rc = mb_check_durations(what, durations, D, true);
+  if (rc != FTR_OK) return rc;
+  rc = mb_check_ids(what, big_blank_ids, D, termination_symbol, C);
+  if (rc != FTR_OK) return rc;
+  FTR_REQUIRE(B >= 0 && T >= 1 && S >= 0 && r >= 1, "%s: bad sizes", what);
+  FTR_REQUIRE(scale_stride == 0 || scale_stride == 1, "%s: scale_stride must be 0 or 1", what);
+  if (B == 0) return FTR_OK;
+  FTR_REQUIRE(logits && ranges && lse && gpy && glogits && (symbols || S == 0) && (gpx || S == 0), "%s: null pointer", what);
+  rc = device_ok();
+  if (rc != FTR_OK) return rc;
+  return multiblank_logprobs_bwd(logits, symbols, ranges, boundary, termination_symbol, big_blank_ids, durations, D, lse, gpx,
+                                 gpy, Scale{scale, scale_stride, scale_mul}, glogits, B, T, S, C, r,
+                                 reinterpret_cast<hipStream_t>(stream));
+}
+
+
 int ftr_selftest(void* scratch_dev, void* stream) {
   clear_error();
   FTR_REQUIRE(scratch_dev, "selftest: need >= 8 KiB of device scratch");

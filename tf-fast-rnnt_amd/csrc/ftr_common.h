@@ -162,6 +162,12 @@ size_t mi_bidir_workspace_floats(int B, int S, int T);
 size_t mi_bidir_handoff_floats(int B, int S, int T);
 size_t mi_viterbi_workspace_bytes(int B, int S, int T);
 int mi_viterbi(const float* px, const float* py, const int32_t* boundary, void* ws, size_t ws_bytes, float* score, int32_t* frames, int B, int S, int T, int modified, hipStream_t st);
+size_t mi_multiblank_workspace_floats(int B, int S, int T);
+int mi_multiblank_fwd(const float* px, const float* py, const int32_t* boundary, const int32_t* durations, int D, float* ws, size_t ws_floats, float* ans, int B, int S, int T, hipStream_t st);
+int mi_multiblank_bwd(const float* px, const float* py, const int32_t* boundary, const int32_t* durations, int D, float* ws, size_t ws_floats, const float* ans_grad, float* px_grad, float* py_grad, int B, int S, int T, hipStream_t st);
+// multi-blank twins of pruned_logprobs_fwd / _bwd (regular type): big_ids[D-1] and durations[D] are host arrays
+int multiblank_logprobs_fwd(const float* logits, const int32_t* symbols, const int32_t* ranges, const int32_t* boundary, int blank, const int32_t* big_ids, const int32_t* durations, int D, double sigma, double delay_penalty, float* lse, float* px, float* py, int B, int T, int S, int C, int r, hipStream_t st);
+int multiblank_logprobs_bwd(const float* logits, const int32_t* symbols, const int32_t* ranges, const int32_t* boundary, int blank, const int32_t* big_ids, const int32_t* durations, int D, const float* lse, const float* gpx, const float* gpy, Scale scale, float* glogits, int B, int T, int S, int C, int r, hipStream_t st);
 int cummin_i32(const int32_t* in, int32_t* out, int rows, int cols, hipStream_t st);
 int prune_ranges(const float* px_grad, const float* py_grad, const int32_t* boundary, int32_t* ranges, int32_t* s_begin, int B, int S, int T, int T1, int r, hipStream_t st);
 int do_pruning(const float* am, const float* lm, const int32_t* ranges, float* am_p, float* lm_p, int B, int T, int S1, int C, int r, hipStream_t st);

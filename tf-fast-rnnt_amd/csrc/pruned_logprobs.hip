@@ -311,4 +311,177 @@ int pruned_logprobs_bwd(const float* logits, const int32_t* symbols, const int32
   return check_launch("band_grad");
 }
 
+// ---- multi-blank twins (MI355X addition, regular type only): D blank columns per row, blank j advancing d[j] frames.
+// The row is normalised by the ordinary softmax over all C columns (lse_rows, unchanged); `sigma` is subtracted from
+// every log-probability.  py has D planes [B,D,S+1,T]; py[b,j,s,t] = -inf where t + d[j] > t_end.  A symbol that is a
+// big blank gets px = -inf and no gradient.  Kernels of their own, so the ordinary instantiations above stay as they are.
+namespace {
+
+struct MbCols { int id[8]; int d[8]; int D; };   // id[0] = the standard blank, d[0] = 1
+
+__device__ __forceinline__ bool mb_is_big_blank(const MbCols& mc, int c) {
+  bool hit = false;
+  for (int j = 1; j < mc.D; ++j) hit |= (c == mc.id[j]);
+  return hit;
+}
+
+// grid: (ceil((T+1)/256), S+1, B); thread <-> (b, s, t).  Writes py[b,:,s,t] (t < T) and px[b,s,t] (s < S, t <= T).
+__global__ void mb_to_lattice_kernel(const float* __restrict__ logits, const int32_t* __restrict__ symbols,
+                                     const int32_t* __restrict__ ranges, const int32_t* __restrict__ boundary,
+                                     const float* __restrict__ lse, const MbCols mc, float sigma, double delay_penalty,
+                                     float* __restrict__ px, float* __restrict__ py, int T, int S, int C, int r) {
+  const int t = blockIdx.x * blockDim.x + threadIdx.x;
+  const int s = blockIdx.y, b = blockIdx.z;
+  if (t > T) return;
+  const int te = boundary ? boundary[4 * b + 3] : T;
+  float vx = -INFINITY;
+  bool inband = false;
+  size_t row = 0;
+  float l = 0.0f;
+  if (t < T) {
+    const size_t bt = (size_t)b * T + t;
+    const int s0 = ranges[bt * r];
+    int k = s - s0;
+    if (k < 0) k += S + 1;
+    if (k < r) {
+      inband = true;
+      row = bt * r + k;
+      l = lse[row] + sigma;
+      if (s < S) {
+        const int c = min(max(symbols[(size_t)b * S + s], 0), C - 1);
+        if (!mb_is_big_blank(mc, c)) vx = logits[row * C + c] - l;
+      }
+    }
+    for (int j = 0; j < mc.D; ++j) {
+      float vy = -INFINITY;
+      if (inband && t + mc.d[j] <= te) vy = logits[row * C + mc.id[j]] - l;
+      py[(((size_t)b * mc.D + j) * (S + 1) + s) * T + t] = vy;
+    }
+  }
+  if (s < S) {
+    if (t == te) vx = -INFINITY;
+    if (delay_penalty > 0.0) {
+      const double offset = ((double)te - 1.0) / 2.0;
+      vx += (float)((offset - (double)t) * delay_penalty);
+    }
+    px[((size_t)b * S + s) * (T + 1) + t] = vx;
+  }
+}
+
+// one wave per (b,t,k) row of glogits, as band_grad_kernel: g[c] = -softmax(x)[c] (gx + sum_j gy_j) + 1[c == sym] gx
+// + sum_j 1[c == id_j] gy_j; each blank column takes its term in the lane that holds the column.
+template <bool VEC>
+__global__ void mb_grad_kernel(const float* __restrict__ logits, const int32_t* __restrict__ symbols,
+                               const int32_t* __restrict__ ranges, const int32_t* __restrict__ boundary,
+                               const float* __restrict__ lse, const float* __restrict__ gpx,
+                               const float* __restrict__ gpy, const Scale scale, const MbCols mc,
+                               float* __restrict__ glogits, size_t rows, int T, int S, int C, int r) {
+  const int lane = threadIdx.x & 63;
+  const size_t row = (size_t)blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
+  if (row >= rows) return;
+  const int T1 = T + 1;
+  const size_t bt = row / r;
+  const int k = (int)(row - bt * r);
+  const int b = (int)(bt / T);
+  const int t = (int)(bt - (size_t)b * T);
+  const int s0 = ranges[bt * r];
+  int s = s0 + k;
+  if (s > S) s -= S + 1;
+  const int te = boundary ? boundary[4 * b + 3] : T;
+  const float sc = scale.at(b);
+  float gx = 0.0f;
+  int sym = -1;
+  const bool sok = s >= 0 && s <= S;
+  if (sok && s < S) {
+    sym = min(max(symbols[(size_t)b * S + s], 0), C - 1);   // the column the forward read
+    if (t != te && !mb_is_big_blank(mc, sym)) gx = gpx[((size_t)b * S + s) * T1 + t] * sc;
+  }
+  float gy[8];
+  float tot = gx;
+#pragma unroll
+  for (int j = 0; j < 8; ++j) {
+    gy[j] = 0.0f;
+    if (j < mc.D && sok && t + mc.d[j] <= te) gy[j] = gpy[(((size_t)b * mc.D + j) * (S + 1) + s) * T + t] * sc;
+    tot += gy[j];
+  }
+  const float l = lse[row];
+  const float* x = logits + row * C;
+  float* g = glogits + row * C;
+  if (VEC) {
+    const f4u* x4 = reinterpret_cast<const f4u*>(x);
+    f4u* g4 = reinterpret_cast<f4u*>(g);
+    const int n4 = C >> 2;
+    for (int i = lane; i < n4; i += 64) {
+      const f4 v = x4[i];
+      f4 o;
+#pragma unroll
+      for (int e = 0; e < 4; ++e) {
+        o[e] = -tot * __expf(v[e] - l);
+        if (4 * i + e == sym) o[e] += gx;
+      }
+#pragma unroll
+      for (int j = 0; j < 8; ++j) {
+        if (j < mc.D && (mc.id[j] >> 2) == i) {
+#pragma unroll
+          for (int e = 0; e < 4; ++e) o[e] += ((mc.id[j] & 3) == e) ? gy[j] : 0.0f;
+        }
+      }
+      g4[i] = o;
+    }
+  } else {
+    for (int c = lane; c < C; c += 64) {
+      float val = -tot * __expf(x[c] - l);
+      if (c == sym) val += gx;
+#pragma unroll
+      for (int j = 0; j < 8; ++j)
+        if (j < mc.D && c == mc.id[j]) val += gy[j];
+      g[c] = val;
+    }
+  }
+}
+
+MbCols mb_cols(int blank, const int32_t* big_ids, const int32_t* durations, int D) {
+  MbCols mc;
+  for (int j = 0; j < 8; ++j) {
+    mc.id[j] = j == 0 ? blank : (j < D ? big_ids[j - 1] : -1);
+    mc.d[j] = j < D ? durations[j] : 1;
+  }
+  mc.D = D;
+  return mc;
+}
+}  // namespace
+
+int multiblank_logprobs_fwd(const float* logits, const int32_t* symbols, const int32_t* ranges, const int32_t* boundary,
+                            int blank, const int32_t* big_ids, const int32_t* durations, int D, double sigma,
+                            double delay_penalty, float* lse, float* px, float* py, int B, int T, int S, int C, int r,
+                            hipStream_t st) {
+  const size_t rows = (size_t)B * T * r;
+  if (rows == 0) return FTR_OK;
+  int rc = lse_rows(logits, lse, rows, C, blank, 0, st);
+  if (rc != FTR_OK) return rc;
+  const int threads = 256;
+  const dim3 grid((T + 1 + threads - 1) / threads, S + 1, B);
+  hipLaunchKernelGGL(mb_to_lattice_kernel, grid, dim3(threads), 0, st, logits, symbols, ranges, boundary, lse,
+                     mb_cols(blank, big_ids, durations, D), (float)sigma, delay_penalty, px, py, T, S, C, r);
+  return check_launch("multiblank_to_lattice");
+}
+
+int multiblank_logprobs_bwd(const float* logits, const int32_t* symbols, const int32_t* ranges, const int32_t* boundary,
+                            int blank, const int32_t* big_ids, const int32_t* durations, int D, const float* lse,
+                            const float* gpx, const float* gpy, Scale scale, float* glogits, int B, int T, int S, int C,
+                            int r, hipStream_t st) {
+  const size_t rows = (size_t)B * T * r;
+  if (rows == 0) return FTR_OK;
+  const int wpb = 4;
+  const unsigned blocks = (unsigned)((rows + wpb - 1) / wpb);
+  const MbCols mc = mb_cols(blank, big_ids, durations, D);
+  if ((C & 3) == 0)
+    hipLaunchKernelGGL((mb_grad_kernel<true>), dim3(blocks), dim3(64 * wpb), 0, st, logits, symbols, ranges, boundary, lse,
+                       gpx, gpy, scale, mc, glogits, rows, T, S, C, r);
+  else
+    hipLaunchKernelGGL((mb_grad_kernel<false>), dim3(blocks), dim3(64 * wpb), 0, st, logits, symbols, ranges, boundary, lse,
+                       gpx, gpy, scale, mc, glogits, rows, T, S, C, r);
+  return check_launch("multiblank_grad");
+}
+
 }  // namespace ftr

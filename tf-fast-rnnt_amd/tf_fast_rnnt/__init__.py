@@ -5,6 +5,7 @@ rebuilt as hand-written HIP behind a C ABI (include/ftr.h).  The public names, s
 same C ABI is described in INTEGRATION.md)."""
 from ._lib import FtrError, lib as _load_native          # noqa: F401
 from .mutual_information import cummin, mutual_information_recursion, mutual_information_viterbi   # the viterbi alignment: MI355X addition
+from .mutual_information import mutual_information_recursion_multiblank   # MI355X addition: multi-blank (big blank) lattice
 from .rnnt_loss import do_rnnt_pruning
 from .rnnt_loss import get_rnnt_logprobs
 from .rnnt_loss import get_rnnt_logprobs_joint
@@ -12,6 +13,8 @@ from .rnnt_loss import get_rnnt_logprobs_pruned
 from .rnnt_loss import get_rnnt_logprobs_smoothed
 from .rnnt_loss import get_rnnt_prune_ranges
 from .rnnt_loss import get_hat_logprobs_joint, get_hat_logprobs_pruned, hat_loss, hat_loss_pruned  # MI355X addition: HAT loss, see hat_loss_pruned
+from .rnnt_loss import get_rnnt_logprobs_multiblank_joint, get_rnnt_logprobs_multiblank_pruned   # MI355X addition: multi-blank
+from .rnnt_loss import rnnt_loss_multiblank, rnnt_loss_multiblank_pruned                           # transducer loss, see there
 from .rnnt_loss import rnnt_loss
 from .rnnt_loss import rnnt_loss_pruned
 from .rnnt_loss import rnnt_alignment_pruned                                   # MI355X addition: best-path alignment, see its docstring

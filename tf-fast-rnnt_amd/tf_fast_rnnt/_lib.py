@@ -18,6 +18,7 @@ _lib = None
 _c_fp = ctypes.c_void_p   # const float* (device)
 _c_ip = ctypes.c_void_p   # const int32_t* (device)
 _c_st = ctypes.c_void_p   # hipStream_t
+_c_hi = ctypes.POINTER(ctypes.c_int32)   # const int32_t* (HOST array, read at launch time)
 _i = ctypes.c_int
 _f = ctypes.c_float
 
@@ -82,6 +83,11 @@ _SIGNATURES = {
     "ftr_hat_pruned_logprobs_bwd_scaled_f32": (_i, [_c_fp, _c_ip, _c_ip, _c_ip, _i, _c_fp, _c_fp, _c_fp, _c_fp, _i, _f, _c_fp, _i, _i, _i, _i, _i, _i, _c_st]),
     "ftr_hat_pruned_band_fwd_f32": (_i, [_c_fp, _c_ip, _c_ip, _c_ip, _i, ctypes.c_double, _c_fp, _c_fp, _c_fp, _i, _i, _i, _i, _i, _i, _c_st]),
     "ftr_hat_pruned_band_bwd_scaled_f32": (_i, [_c_fp, _c_ip, _c_ip, _c_ip, _i, _c_fp, _c_fp, _c_fp, _c_fp, _i, _f, _c_fp, _i, _i, _i, _i, _i, _i, _c_st]),
+    "ftr_mutual_information_multiblank_workspace_floats": (ctypes.c_size_t, [_i, _i, _i]),
+    "ftr_mutual_information_multiblank_fwd_f32": (_i, [_c_fp, _c_fp, _c_ip, _c_hi, _i, _c_fp, ctypes.c_size_t, _c_fp, _i, _i, _i, _c_st]),
+    "ftr_mutual_information_multiblank_bwd_f32": (_i, [_c_fp, _c_fp, _c_ip, _c_hi, _i, _c_fp, ctypes.c_size_t, _c_fp, _c_fp, _c_fp, _i, _i, _i, _c_st]),
+    "ftr_multiblank_pruned_logprobs_fwd_f32": (_i, [_c_fp, _c_ip, _c_ip, _c_ip, _i, _c_hi, _c_hi, _i, ctypes.c_double, ctypes.c_double, _c_fp, _c_fp, _c_fp, _i, _i, _i, _i, _i, _c_st]),
+    "ftr_multiblank_pruned_logprobs_bwd_scaled_f32": (_i, [_c_fp, _c_ip, _c_ip, _c_ip, _i, _c_hi, _c_hi, _i, _c_fp, _c_fp, _c_fp, _c_fp, _i, _f, _c_fp, _i, _i, _i, _i, _i, _c_st]),
     "ftr_simple_logprobs_fwd_f32": (_i, [_c_fp, _c_fp, _c_ip, _c_fp, _c_fp, _c_fp, _c_ip, _i, ctypes.c_double, _c_fp, _c_fp, _i, _i, _i, _i, _i, _c_st]),
     "ftr_simple_logprobs_bwd_w_f32": (_i, [_c_fp, _c_fp, _c_fp, _c_ip, _c_fp, _c_fp, _c_fp, _i, _i, _i, _i, _c_st]),
     "ftr_simple_logprobs_bwd_am_f32": (_i, [_c_fp, _c_fp, _c_fp, _c_fp, _c_ip, _c_ip, _i, _c_fp, _i, _i, _i, _i, _i, _c_st]),

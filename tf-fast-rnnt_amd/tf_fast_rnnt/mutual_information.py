@@ -218,6 +218,103 @@ def mutual_information_recursion(
     return (ans, (px_grad, py_grad)) if calc_gradients else ans
 
 
+def _check_durations(durations) -> Tuple[int, ...]:
+    durs = tuple(int(d) for d in durations)
+    if not 1 <= len(durs) <= 8:
+        raise ValueError(f"durations must hold 1..8 values, got {len(durs)}")
+    if any(d < 1 or d > 32 for d in durs) or any(b <= a for a, b in zip(durs, durs[1:])):
+        raise ValueError(f"durations must be strictly increasing values in 1..32, got {durs}")
+    return durs
+
+
+def mb_forward_backward(px: torch.Tensor, py: torch.Tensor, durations, boundary: Optional[torch.Tensor], need_grads: bool):
+    """The multi-blank recursion on raw tensors (no autograd): forward and, when wanted, the backward seeded with ones,
+    back to back on torch's current stream.  Returns (ans, px_grad|None, py_grad|None)."""
+    import ctypes
+    _require_gpu(px, "px"); _require_gpu(py, "py")
+    if px.dtype != torch.float32 or py.dtype != torch.float32:
+        raise TypeError("px and py must be float32")
+    durs = _check_durations(durations)
+    D = len(durs)
+    if px.dim() != 3 or py.dim() != 4:
+        raise ValueError("px must be [B,S,T+1] and py [B,D,S+1,T]")
+    B, S, T1 = px.shape
+    T = py.shape[3]
+    if T1 != T + 1:
+        raise ValueError(f"px.shape[-1]={T1} must be T+1 with T=py.shape[-1]={T} (regular type only)")
+    if tuple(py.shape) != (B, D, S + 1, T):
+        raise ValueError(f"py must have shape {(B, D, S + 1, T)}, got {tuple(py.shape)}")
+    px = px.contiguous(); py = py.contiguous()
+    boundary = _as_boundary(boundary, B, px.device)
+    dur_arr = (ctypes.c_int32 * D)(*durs)       # read by the launch itself: no device copy, no host synchronisation
+    L = _lib.lib()
+    with torch.cuda.device(px.device):
+        st = _stream_ptr(px)
+        nws = L.ftr_mutual_information_multiblank_workspace_floats(B, S, T)
+        ws = torch.empty((max(nws, 2) + 1) // 2, dtype=torch.float64, device=px.device)
+        ans = torch.empty((B,), dtype=torch.float32, device=px.device)
+        _lib.call("ftr_mutual_information_multiblank_fwd_f32", _ptr(px), _ptr(py), _ptr(boundary), dur_arr, D, _ptr(ws), nws,
+                  _ptr(ans), B, S, T, st)
+        if not need_grads:
+            return ans, None, None
+        px_grad = torch.empty_like(px)
+        py_grad = torch.empty_like(py)
+        _lib.call("ftr_mutual_information_multiblank_bwd_f32", _ptr(px), _ptr(py), _ptr(boundary), dur_arr, D, _ptr(ws), nws,
+                  None, _ptr(px_grad), _ptr(py_grad), B, S, T, st)
+    return ans, px_grad, py_grad
+
+
+class _MutualInformationMultiblank(torch.autograd.Function):
+    """The multi-blank recursion and its gradient, as _MutualInformation."""
+
+    @staticmethod
+    def forward(ctx, px, py, durations, boundary, calc_gradients):
+        need = bool(calc_gradients) or px.requires_grad or py.requires_grad
+        ans, px_grad, py_grad = mb_forward_backward(px.detach(), py.detach(), durations, boundary, need)
+        if need:
+            ctx.save_for_backward(px_grad, py_grad)
+        ctx.have_grads = need
+        if px_grad is None:
+            px_grad = torch.zeros_like(px)
+            py_grad = torch.zeros_like(py)
+        ctx.mark_non_differentiable(px_grad, py_grad)
+        ctx.set_materialize_grads(False)
+        return ans, px_grad, py_grad
+
+    @staticmethod
+    def backward(ctx, g_ans, _g1, _g2):
+        if not ctx.have_grads:
+            raise RuntimeError("mutual_information_recursion_multiblank: backward without saved occupancies")
+        px_grad, py_grad = ctx.saved_tensors
+        if g_ans is None:
+            return None, None, None, None, None
+        return g_ans.reshape(-1, 1, 1) * px_grad, g_ans.reshape(-1, 1, 1, 1) * py_grad, None, None, None
+
+
+def mutual_information_recursion_multiblank(
+    px: torch.Tensor,
+    py: torch.Tensor,
+    durations,
+    boundary: Optional[torch.Tensor] = None,
+    calc_gradients: bool = False,
+) -> Union[Tuple[torch.Tensor, Tuple[torch.Tensor, torch.Tensor]], torch.Tensor]:
+    """``mutual_information_recursion`` over a lattice with big blanks (multi-blank transducer; MI355X addition, no
+    reference counterpart; csrc/mi_multiblank.hip).  Regular type only.
+
+    px: [B,S,T+1]; py: [B,D,S+1,T], ``py[b,j,s,t]`` being the log-probability of the move (s,t) -> (s,t+durations[j]);
+    durations: D = 1..8 strictly increasing ints in 1..32 (they need not contain 1); boundary: int32 [B,4] or None.
+
+        p[s,t] = logadd(p[s-1,t] + px[s-1,t], logadd_j p[s,t-d_j] + py[j,s,t-d_j]),   p[s_begin,t_begin] = 0
+
+    Moves that would leave the boundary rectangle are ignored whatever value they carry.  Returns ``ans`` [B] =
+    ``p[s_end,t_end]`` (-inf when no path exists; the gradients are then zero, never NaN); with ``calc_gradients`` also
+    ``(px_grad, py_grad)``, the occupancies, in the shapes of px and py and zero outside the rectangle.  With
+    ``durations=(1,)`` and ``py[:,None]`` this is the lattice of ``mutual_information_recursion``.  Differentiable
+    w.r.t. px and py; asynchronous on torch's current stream, no host read (capturable)."""
+    ans, px_grad, py_grad = _MutualInformationMultiblank.apply(px, py, tuple(durations), boundary, calc_gradients)
+    return (ans, (px_grad, py_grad)) if calc_gradients else ans
+
+
 def mutual_information_viterbi(px: torch.Tensor, py: torch.Tensor,
                                boundary: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor]:
     """Best-path (Viterbi) alignment over the lattice of ``mutual_information_recursion`` (MI355X addition, no reference

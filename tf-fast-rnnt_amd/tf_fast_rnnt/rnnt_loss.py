@@ -29,7 +29,8 @@ import torch
 
 from . import _lib
 from .mutual_information import (_as_boundary, _ptr, _require_gpu, _stream_ptr, cummin,
-                                 mi_forward_backward, mutual_information_recursion, mutual_information_viterbi)
+                                 mb_forward_backward, mi_forward_backward, mutual_information_recursion,
+                                 mutual_information_viterbi)
 
 _NEG_INF = float("-inf")
 # tf.math.nextafter(0., 1.) : smallest positive float32 subnormal (rnnt_loss.py:181,1272,1280)
@@ -921,6 +922,209 @@ def hat_loss(
     return hat_loss_pruned(logits=logits, symbols=symbols, ranges=_identity_ranges(B, T, S1, logits.device),
                            termination_symbol=termination_symbol, boundary=boundary, rnnt_type=rnnt_type,
                            delay_penalty=delay_penalty, reduction=reduction)
+
+
+# ---- multi-blank transducer (MI355X addition, no reference counterpart): big blanks that advance several frames
+
+def _big_blank_args(big_blanks, termination_symbol: int, C: int):
+    """(ids, durations) as host int32 arrays for the C ABI, durations[0] = 1 being the standard blank's.  The checks are
+    those of the native entry points, raised here as ValueError before anything is allocated."""
+    import ctypes
+    pairs = [(int(i), int(d)) for i, d in big_blanks]
+    ids = [i for i, _ in pairs]
+    durs = [1] + [d for _, d in pairs]
+    if len(durs) > 8:
+        raise ValueError(f"at most 7 big blanks are supported, got {len(pairs)}")
+    if any(d < 2 or d > 32 for d in durs[1:]) or any(b <= a for a, b in zip(durs, durs[1:])):
+        raise ValueError(f"big-blank durations must be strictly increasing values in 2..32, got {durs[1:]}")
+    if not 0 <= int(termination_symbol) < C:
+        raise ValueError(f"termination_symbol {termination_symbol} not in [0,{C})")
+    if any(i < 0 or i >= C or i == int(termination_symbol) for i in ids) or len(set(ids)) != len(ids):
+        raise ValueError(f"big-blank ids must be distinct, in [0,{C}) and differ from termination_symbol, got {ids}")
+    D = len(durs)
+    return (ctypes.c_int32 * max(D - 1, 1))(*ids), (ctypes.c_int32 * D)(*durs), tuple(durs)
+
+
+def _mb_builder_fwd(x, symbols, ranges, boundary, blank, ids, durs, D, sigma, delay_penalty):
+    B, T, r, C = x.shape
+    S = symbols.shape[1]
+    lse = torch.empty((B, T, r), dtype=torch.float32, device=x.device)
+    px = torch.empty((B, S, T + 1), dtype=torch.float32, device=x.device)
+    py = torch.empty((B, D, S + 1, T), dtype=torch.float32, device=x.device)
+    with torch.cuda.device(x.device):
+        _lib.call("ftr_multiblank_pruned_logprobs_fwd_f32", _ptr(x), _ptr(symbols), _ptr(ranges), _ptr(boundary), blank,
+                  ids, durs, D, float(sigma), float(delay_penalty), _ptr(lse), _ptr(px), _ptr(py), B, T, S, C, r,
+                  _stream_ptr(x))
+    return lse, px, py
+
+
+def _mb_builder_bwd(x, symbols, ranges, boundary, blank, ids, durs, D, lse, gpx, gpy, scale, stride, mul):
+    B, T, r, C = x.shape
+    S = symbols.shape[1]
+    g = torch.empty_like(x)
+    with torch.cuda.device(x.device):
+        _lib.call("ftr_multiblank_pruned_logprobs_bwd_scaled_f32", _ptr(x), _ptr(symbols), _ptr(ranges), _ptr(boundary),
+                  blank, ids, durs, D, _ptr(lse), _ptr(gpx), _ptr(gpy), _ptr(scale), stride, mul, _ptr(g), B, T, S, C, r,
+                  _stream_ptr(x))
+    return g
+
+
+class _MultiblankLogprobs(torch.autograd.Function):
+    """get_rnnt_logprobs_multiblank_pruned: one gather launch (after the ordinary logsumexp) and one gradient launch."""
+
+    @staticmethod
+    def forward(ctx, logits, symbols, ranges, termination_symbol, big_blanks, boundary, sigma):
+        x = logits.detach().contiguous()
+        ids, durs, dt = _big_blank_args(big_blanks, termination_symbol, x.shape[3])
+        lse, px, py = _mb_builder_fwd(x, symbols, ranges, boundary, int(termination_symbol), ids, durs, len(dt), sigma, 0.0)
+        ctx.save_for_backward(x, symbols, ranges, lse, boundary if boundary is not None else torch.empty(0))
+        ctx.has_boundary = boundary is not None
+        ctx.meta = (int(termination_symbol), ids, durs, len(dt))
+        return px, py
+
+    @staticmethod
+    def backward(ctx, gpx, gpy):
+        x, symbols, ranges, lse, boundary = ctx.saved_tensors
+        if not ctx.has_boundary:
+            boundary = None
+        blank, ids, durs, D = ctx.meta
+        g = _mb_builder_bwd(x, symbols, ranges, boundary, blank, ids, durs, D, lse, gpx.contiguous(), gpy.contiguous(),
+                            None, 0, 1.0)
+        return g, None, None, None, None, None, None
+
+
+class _MultiblankLoss(torch.autograd.Function):
+    """rnnt_loss_multiblank_pruned with the whole chain native, as _PrunedLoss's lattice route: logsumexp + gather ->
+    multi-blank recursion forward and backward on the full-size lattices -> in backward() one streaming kernel turns the
+    occupancies * upstream gradient into d loss / d logits."""
+
+    @staticmethod
+    def forward(ctx, logits, symbols, ranges, termination_symbol, big_blanks, boundary, sigma, delay_penalty, code):
+        x = logits.detach().contiguous()
+        need = logits.requires_grad
+        ids, durs, dt = _big_blank_args(big_blanks, termination_symbol, x.shape[3])
+        lse, px, py = _mb_builder_fwd(x, symbols, ranges, boundary, int(termination_symbol), ids, durs, len(dt), sigma,
+                                      delay_penalty)
+        ans, px_grad, py_grad = mb_forward_backward(px, py, dt, boundary, need)
+        del px, py
+        if need:
+            ctx.save_for_backward(x, symbols, ranges, lse, px_grad, py_grad,
+                                  boundary if boundary is not None else torch.empty(0))
+        ctx.has_boundary = boundary is not None
+        ctx.meta = (int(termination_symbol), ids, durs, len(dt), int(code))
+        return _negated_reduce_native(ans, code)
+
+    @staticmethod
+    def backward(ctx, g_loss):
+        x, symbols, ranges, lse, px_grad, py_grad, boundary = ctx.saved_tensors
+        if not ctx.has_boundary:
+            boundary = None
+        blank, ids, durs, D, code = ctx.meta
+        scale, stride, mul = _upstream_scale(g_loss, code, x.shape[0])
+        g = _mb_builder_bwd(x, symbols, ranges, boundary, blank, ids, durs, D, lse, px_grad, py_grad, scale, stride, mul)
+        return g, None, None, None, None, None, None, None, None
+
+
+def _check_sigma(sigma) -> float:
+    sigma = float(sigma)
+    if not sigma >= 0.0:
+        raise ValueError(f"sigma must not be negative, got {sigma}")
+    return sigma
+
+
+def get_rnnt_logprobs_multiblank_pruned(
+    logits: torch.Tensor,
+    symbols: torch.Tensor,
+    ranges: torch.Tensor,
+    termination_symbol: int,
+    big_blanks,
+    boundary: torch.Tensor,
+    sigma: float = 0.0,
+) -> Tuple[torch.Tensor, torch.Tensor]:
+    """Multi-blank form of ``get_rnnt_logprobs_pruned`` (Xu et al., "Multi-blank Transducers for Speech Recognition",
+    ICASSP 2023; MI355X addition, regular type only).  ``big_blanks`` is a sequence of ``(symbol_id, duration)`` pairs:
+    ordinary vocabulary entries whose emission advances ``duration`` frames; ids distinct, in [0,C), not the
+    termination_symbol; durations strictly increasing in 2..32; at most 7 pairs; ``()`` is valid.
+
+    logits [B,T,s_range,C] -> ``px`` [B,S,T+1] and ``py`` [B,D,S+1,T] with D = 1 + len(big_blanks) and
+    durations = (1, d_1, ...): ``py[b,j,s,t]`` is the log-probability of blank j at (s,t), the move to (s,t+d_j), and
+    is -inf where ``t + d_j > t_end``.  Each row is normalised by the ordinary softmax over all C columns and ``sigma``
+    (>= 0, the paper's logit under-normalisation) is subtracted from every log-probability.  Both are -inf outside the
+    band, px also at column t_end; a symbol that is a big-blank id gets px = -inf and no gradient.  Feed them to
+    ``mutual_information_recursion_multiblank(px, py, (1, d_1, ...), boundary)``.  Differentiable w.r.t. ``logits``."""
+    symbols, ranges, boundary = _pruned_inputs(logits, symbols, ranges, boundary)
+    return _MultiblankLogprobs.apply(logits, symbols, ranges, termination_symbol, tuple(map(tuple, big_blanks)), boundary,
+                                     _check_sigma(sigma))
+
+
+def _joint_inputs(logits, symbols):
+    _require_gpu(logits, "logits")
+    if logits.dim() != 4:
+        raise ValueError("logits must be [B,T,S+1,C]")
+    B, T, S1, _ = logits.shape
+    if tuple(torch.as_tensor(symbols).shape) != (B, S1 - 1):
+        raise ValueError(f"symbols must have shape {(B, S1 - 1)}, got {tuple(torch.as_tensor(symbols).shape)}")
+    return _identity_ranges(B, T, S1, logits.device)
+
+
+def get_rnnt_logprobs_multiblank_joint(
+    logits: torch.Tensor,
+    symbols: torch.Tensor,
+    termination_symbol: int,
+    big_blanks,
+    boundary: Optional[torch.Tensor] = None,
+    sigma: float = 0.0,
+) -> Tuple[torch.Tensor, torch.Tensor]:
+    """``get_rnnt_logprobs_multiblank_pruned`` for unpruned joiner logits [B,T,S+1,C], through identity ranges."""
+    ranges = _joint_inputs(logits, symbols)
+    return get_rnnt_logprobs_multiblank_pruned(logits=logits, symbols=symbols, ranges=ranges,
+                                               termination_symbol=termination_symbol, big_blanks=big_blanks,
+                                               boundary=boundary, sigma=sigma)
+
+
+def rnnt_loss_multiblank_pruned(
+    logits: torch.Tensor,
+    symbols: torch.Tensor,
+    ranges: torch.Tensor,
+    termination_symbol: int,
+    big_blanks,
+    boundary: torch.Tensor = None,
+    sigma: float = 0.0,
+    delay_penalty: float = 0.0,
+    reduction: Optional[str] = "mean",
+    rnnt_type: str = "regular",
+) -> torch.Tensor:
+    """Multi-blank transducer loss on pruned joiner logits (MI355X addition): the lattices of
+    ``get_rnnt_logprobs_multiblank_pruned`` (with the delay penalty on px as in ``rnnt_loss_pruned``) through
+    ``mutual_information_recursion_multiblank``, negated and reduced.  Prune ranges come from the ordinary
+    ``rnnt_loss_simple``, as for ``hat_loss_pruned``.  Only ``rnnt_type="regular"`` exists; anything else raises
+    ValueError.  With ``big_blanks=()`` and ``sigma=0`` this is ``rnnt_loss_pruned`` on the full-size lattices."""
+    if rnnt_type != "regular":
+        raise ValueError(f"the multi-blank loss is defined for rnnt_type 'regular' only, given {rnnt_type}")
+    code = _reduction_code(reduction)
+    symbols_i, ranges_i, boundary_i = _pruned_inputs(logits, symbols, ranges, boundary)
+    return _MultiblankLoss.apply(logits, symbols_i, ranges_i, termination_symbol, tuple(map(tuple, big_blanks)), boundary_i,
+                                 _check_sigma(sigma), float(delay_penalty) if delay_penalty > 0.0 else 0.0, code)
+
+
+def rnnt_loss_multiblank(
+    logits: torch.Tensor,
+    symbols: torch.Tensor,
+    termination_symbol: int,
+    big_blanks,
+    boundary: Optional[torch.Tensor] = None,
+    sigma: float = 0.0,
+    delay_penalty: float = 0.0,
+    reduction: Optional[str] = "mean",
+    rnnt_type: str = "regular",
+) -> torch.Tensor:
+    """``rnnt_loss_multiblank_pruned`` for unpruned joiner logits [B,T,S+1,C], through identity ranges."""
+    if rnnt_type != "regular":
+        raise ValueError(f"the multi-blank loss is defined for rnnt_type 'regular' only, given {rnnt_type}")
+    ranges = _joint_inputs(logits, symbols)
+    return rnnt_loss_multiblank_pruned(logits=logits, symbols=symbols, ranges=ranges, termination_symbol=termination_symbol,
+                                       big_blanks=big_blanks, boundary=boundary, sigma=sigma, delay_penalty=delay_penalty,
+                                       reduction=reduction)
 
 
 def _colsum_weighted(x: torch.Tensor, w: torch.Tensor, rows: int, C: int, st) -> torch.Tensor:
