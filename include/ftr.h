@@ -9,6 +9,14 @@
  *     current device), int sizes, an opaque `void* stream` (a hipStream_t; NULL = default stream);
  *   - dense row-major tensors, last axis contiguous, float32 / int32 exactly as the reference's op
  *     registration (tf_fast_rnnt/python/csrc/tf_fast_rnnt_op.cc:27-38);
+ *   - DATA pointers (inputs, outputs, gradients; float32 or int32) need the element's natural alignment only, 4
+ *     bytes: a tensor may start anywhere inside a larger buffer (a slice of a packed batch, a view at a storage
+ *     offset).  The kernels' 16-byte accesses are issued at 4-byte alignment and no kernel chooses a summation order
+ *     by the alignment of an operand, so results do not depend on it (tests/test_gpu_views.py: bit-identical).  Only
+ *     WORKSPACES have a stricter rule, stated where they are declared.  Element counts and offsets are size_t: a
+ *     [B,T,s_range,C] tensor may hold more than 2^32 elements (tests/test_gpu_large.py).  What stays 32-bit is the
+ *     number of its ROWS: B*T*s_range (and so B*T) must not exceed 2^31 - 1, and the sizes themselves are int; an
+ *     entry point given more rows returns FTR_ERR_INVALID_ARG before it launches anything;
  *   - asynchronous on `stream`, no host synchronisation, no allocation inside (graph-capturable);
  *     scratch is passed in by the caller (the reference allocates it with allocate_temp,
  *     tf_fast_rnnt_op.cc:66-67,90-91);

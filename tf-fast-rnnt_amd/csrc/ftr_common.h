@@ -22,6 +22,16 @@ inline int check_launch(const char* what) {
   return FTR_OK;
 }
 
+// Element counts and offsets of the [B,T,s_range,C]-shaped tensors are size_t everywhere; the number of their ROWS (B*T*s_range,
+// and the B*T frames of the prune gather) stays 32-bit: grid sizes are unsigned, and the kernels derive int b / t from a row.
+inline int require_rows_32bit(const char* what, size_t rows) {
+  if (rows > 0x7fffffffull) {
+    set_error("%s: %zu rows (B*T*s_range) exceed the 2^31 - 1 that the launch grids index", what, rows);
+    return FTR_ERR_INVALID_ARG;
+  }
+  return FTR_OK;
+}
+
 // Zero fill / device copy of 32-bit words as KERNELS.  Not hipMemsetAsync / hipMemcpyAsync: a memset node captured into a
 // hipGraph writes the right value on the first replay only on this ROCm (scripts/graph_memset_probe.py: garbage from the
 // second replay on), and every launch of this library must be capturable -- the recursion's hand-off region is cleared by

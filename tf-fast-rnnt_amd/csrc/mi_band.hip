@@ -849,6 +849,7 @@ int band_gather(const float* logits, const int32_t* symbols, const int32_t* rang
                 int r, int modified, int hat, hipStream_t st) {
   const size_t rows = (size_t)B * T * r;
   if (rows == 0) return FTR_OK;
+  { const int rc32 = require_rows_32bit("pruned_band_fwd", rows); if (rc32 != FTR_OK) return rc32; }
   const unsigned blocks = (unsigned)((rows + 255) / 256);
 #define FTR_LAUNCH_BGA(MODV, HATV) hipLaunchKernelGGL((band_gather_kernel<MODV, HATV>), dim3(blocks), dim3(256), 0, st, \
     logits, symbols, ranges, boundary, lse, blank, delay_penalty, pxb, pyb, rows, T, S, C, r)
@@ -921,6 +922,7 @@ int band_grad_banded(const float* logits, const int32_t* symbols, const int32_t*
                      int T, int S, int C, int r, int modified, int hat, hipStream_t st) {
   const size_t rows = (size_t)B * T * r;
   if (rows == 0) return FTR_OK;
+  { const int rc32 = require_rows_32bit("pruned_band_bwd", rows); if (rc32 != FTR_OK) return rc32; }
   const int wpb = 4;
   const unsigned blocks = (unsigned)((rows + wpb - 1) / wpb);
 #define FTR_LAUNCH_BGB(VECV, HATV) hipLaunchKernelGGL((band_grad_banded_kernel<VECV, HATV>), dim3(blocks), dim3(64 * wpb), 0, st, \

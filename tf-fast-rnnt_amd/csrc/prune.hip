@@ -864,7 +864,7 @@ int do_pruning(const float* am, const float* lm, const int32_t* ranges, float* a
                int C, int r, hipStream_t st) {
   const size_t frames = (size_t)B * T;
   if (frames == 0 || C == 0 || r == 0) return FTR_OK;
-  if (frames > 0x7fffffffull) { set_error("do_pruning: B*T = %zu exceeds the grid limit", frames); return FTR_ERR_UNSUPPORTED; }
+  { const int rc32 = require_rows_32bit("do_pruning", frames * (size_t)r); if (rc32 != FTR_OK) return rc32; }
   if ((C & 3) == 0) hipLaunchKernelGGL(do_pruning_kernel<true>, dim3((unsigned)frames), dim3(128), 0, st, am, lm, ranges, am_p, lm_p, T, S1, C, r);
   else hipLaunchKernelGGL(do_pruning_kernel<false>, dim3((unsigned)frames), dim3(128), 0, st, am, lm, ranges, am_p, lm_p, T, S1, C, r);
   return check_launch("do_pruning");

@@ -270,6 +270,7 @@ static void lse_rows_launch(const float* logits, float* lse, size_t rows, int C,
 }
 int lse_rows(const float* logits, float* lse, size_t rows, int C, int blank, int hat, hipStream_t st) {
   if (rows == 0) return FTR_OK;
+  { const int rc32 = require_rows_32bit("lse_rows", rows); if (rc32 != FTR_OK) return rc32; }
   if (hat) lse_rows_launch<true>(logits, lse, rows, C, blank, st);
   else lse_rows_launch<false>(logits, lse, rows, C, blank, st);
   return check_launch("lse_rows");
@@ -280,6 +281,7 @@ int pruned_logprobs_fwd(const float* logits, const int32_t* symbols, const int32
                         float* py, int B, int T, int S, int C, int r, int modified, int hat, hipStream_t st) {
   const size_t rows = (size_t)B * T * r;
   if (rows == 0) return FTR_OK;
+  { const int rc32 = require_rows_32bit("pruned_logprobs_fwd", rows); if (rc32 != FTR_OK) return rc32; }
   int rc = lse_rows(logits, lse, rows, C, blank, hat, st);
   if (rc != FTR_OK) return rc;
   const int threads = 256;
@@ -298,6 +300,7 @@ int pruned_logprobs_bwd(const float* logits, const int32_t* symbols, const int32
                         int r, int modified, int hat, hipStream_t st) {
   const size_t rows = (size_t)B * T * r;
   if (rows == 0) return FTR_OK;
+  { const int rc32 = require_rows_32bit("pruned_logprobs_bwd", rows); if (rc32 != FTR_OK) return rc32; }
   const int wpb = 4;
   const unsigned blocks = (unsigned)((rows + wpb - 1) / wpb);
   const bool vec = (C & 3) == 0;
@@ -457,6 +460,7 @@ int multiblank_logprobs_fwd(const float* logits, const int32_t* symbols, const i
                             hipStream_t st) {
   const size_t rows = (size_t)B * T * r;
   if (rows == 0) return FTR_OK;
+  { const int rc32 = require_rows_32bit("multiblank_logprobs_fwd", rows); if (rc32 != FTR_OK) return rc32; }
   int rc = lse_rows(logits, lse, rows, C, blank, 0, st);
   if (rc != FTR_OK) return rc;
   const int threads = 256;
@@ -472,6 +476,7 @@ int multiblank_logprobs_bwd(const float* logits, const int32_t* symbols, const i
                             int r, hipStream_t st) {
   const size_t rows = (size_t)B * T * r;
   if (rows == 0) return FTR_OK;
+  { const int rc32 = require_rows_32bit("multiblank_logprobs_bwd", rows); if (rc32 != FTR_OK) return rc32; }
   const int wpb = 4;
   const unsigned blocks = (unsigned)((rows + wpb - 1) / wpb);
   const MbCols mc = mb_cols(blank, big_ids, durations, D);
