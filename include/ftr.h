@@ -537,6 +537,65 @@ int ftr_multiblank_pruned_logprobs_bwd_scaled_f32(const float* logits, const int
                                                   const float* scale, int scale_stride, float scale_mul,
                                                   float* glogits, int B, int T, int S, int C, int r, void* stream);
 
+/*
+ * Token-and-duration transducer, TDT (MI355X addition, no reference counterpart; Xu et al., "Efficient Sequence
+ * Transduction by Jointly Predicting Tokens and Durations", ICML 2023): every emission, symbol or blank, also says how
+ * many frames it advances.  Regular type only.  All duration lists are HOST arrays, read at launch time (no device
+ * read, no host synchronisation, graph-capturable).
+ *
+ * Durations and normalisation: durations = (e_0 < ... < e_{N-1}), integers in 0..16, 1 <= N <= 5, at least one
+ *   positive.  Token moves use all N, blank moves only the positive ones (blank_durations, Ny = N or N - 1 entries).
+ *   A joiner row has C + N columns, C token logits (termination_symbol among them) then N duration logits, the two
+ *   heads normalised independently: tok = log_softmax(row[:C]) - sigma (sigma >= 0, token head only),
+ *   dur = log_softmax(row[C:]).
+ * Lattice operands:
+ *   px [B,N,S,T+1]: px[b,i,s,t] = tok[symbols[b,s]] + dur[i], the move (s,t) -> (s+1, t+e_i); -inf where
+ *     t + e_i > t_end, at column t_end and outside the band; delay_penalty is added as in
+ *     ftr_multiblank_pruned_logprobs_fwd_f32, by source frame t.
+ *   py [B,Ny,S+1,T]: py[b,j,s,t] = tok[termination_symbol] + dur[index of d_j], the move (s,t) -> (s, t+d_j); -inf
+ *     where t + d_j > t_end and outside the band.
+ *   A symbol equal to termination_symbol is gathered as ftr_pruned_logprobs_fwd_f32 gathers it.
+ * Recursion (csrc/mi_tdt.hip), with the two lists given separately -- token_durations: Dx >= 1 strictly increasing
+ *   values in 0..16; blank_durations: Dy >= 1 strictly increasing values in 1..16; Dx + Dy <= 9; px [B,Dx,S,T+1],
+ *   py [B,Dy,S+1,T]:
+ *   p[s_begin,t_begin] = 0
+ *   p[s,t] = logadd( (+)_i p[s-1,t-e_i] + px[i,s-1,t-e_i],  (+)_j p[s,t-d_j] + py[j,s,t-d_j] ),  ans = p[s_end,t_end]
+ *   A term whose source lies outside the boundary rectangle is absent, whatever it carries.  No path gives ans = -inf
+ *   and zero gradients, an inverted rectangle ans = 0, a NaN stays in its utterance.  token_durations = (0,) is the
+ *   multi-blank recursion, (0,) with (1,) the ordinary one.
+ *   Occupancies: px_grad[i,s,t] = exp(p[s,t] + px[i,s,t] + q[s+1,t+e_i] - ans), py_grad[j,s,t] likewise with
+ *   q[s,t+d_j], q being the same recursion run from the end; both times ans_grad[b] (NULL = ones) and exactly zero
+ *   outside the rectangle.  fwd keeps p in `workspace` (ftr_mutual_information_tdt_workspace_floats(B,S,T) floats,
+ *   8-byte aligned, uninitialised is fine); bwd needs the workspace of the fwd call on the same inputs.  p, q and ans
+ *   are float64 inside.
+ * Builder (csrc/tdt_logprobs.hip): logits [B,T,r,C+N]; lse_tok / lse_dur [B,T,r] receive the two log-sum-exps (fwd)
+ *   and are read back (bwd).  With gx_i, gy_j the upstream gradients of a cell (gpx / gpy in the shapes of px / py,
+ *   times the per-utterance scale as in ftr_pruned_logprobs_bwd_scaled_f32), GX = sum_i gx_i, GY = sum_j gy_j:
+ *   g_tok[c] = -softmax_tok[c] (GX + GY) + 1[c == sym] GX + 1[c == termination_symbol] GY
+ *   g_dur[n] = -softmax_dur[n] (GX + GY) + gx_n + gy_j(n)        (no gy term for duration 0)
+ * Invalid, unsorted or out-of-range lists, Dx + Dy > 9 or sigma < 0 return FTR_ERR_INVALID_ARG (before any device
+ * check) with a message naming the argument.
+ */
+size_t ftr_mutual_information_tdt_workspace_floats(int B, int S, int T);
+int ftr_mutual_information_tdt_fwd_f32(const float* px, const float* py, const int32_t* boundary,
+                                       const int32_t* token_durations, int Dx, const int32_t* blank_durations, int Dy,
+                                       float* workspace, size_t workspace_floats, float* ans, int B, int S, int T,
+                                       void* stream);
+int ftr_mutual_information_tdt_bwd_f32(const float* px, const float* py, const int32_t* boundary,
+                                       const int32_t* token_durations, int Dx, const int32_t* blank_durations, int Dy,
+                                       float* workspace, size_t workspace_floats, const float* ans_grad, float* px_grad,
+                                       float* py_grad, int B, int S, int T, void* stream);
+int ftr_tdt_pruned_logprobs_fwd_f32(const float* logits, const int32_t* symbols, const int32_t* ranges,
+                                    const int32_t* boundary, int termination_symbol, const int32_t* durations, int N,
+                                    double sigma, double delay_penalty, float* lse_tok, float* lse_dur, float* px,
+                                    float* py, int B, int T, int S, int C, int r, void* stream);
+int ftr_tdt_pruned_logprobs_bwd_scaled_f32(const float* logits, const int32_t* symbols, const int32_t* ranges,
+                                           const int32_t* boundary, int termination_symbol, const int32_t* durations,
+                                           int N, double sigma, double delay_penalty, const float* lse_tok,
+                                           const float* lse_dur, const float* gpx, const float* gpy, const float* scale,
+                                           int scale_stride, float scale_mul, float* glogits, int B, int T, int S, int C,
+                                           int r, void* stream);
+
 /* Hardware self-test used by smoke()/tests: checks on the device that the primitives the wavefront
  * kernels rely on behave as assumed (full-wave DPP shift wave_shr:1 with lane 0 keeping its old value;
  * 16-byte global loads/stores at 4-byte alignment).  scratch_dev: >= 8 KiB of device memory; after the

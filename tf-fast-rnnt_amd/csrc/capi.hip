@@ -922,6 +922,122 @@ int ftr_multiblank_pruned_logprobs_bwd_scaled_f32(const float* logits, const int
 }
 
 
+// ---- token-and-duration transducer, TDT (MI355X addition; csrc/mi_tdt.hip, csrc/tdt_logprobs.hip).  The duration lists
+// are host data and are validated first, then sizes and pointers, then the device.
+namespace {
+int tdt_check_list(const char* what, const char* name, const int32_t* v, int n, int nmax, int lo) {
+  FTR_REQUIRE(n >= 1 && n <= nmax, "%s: %s holds %d values, must be 1..%d", what, name, n, nmax);
+  FTR_REQUIRE(v, "%s: null %s", what, name);
+  for (int j = 0; j < n; ++j) {
+    FTR_REQUIRE(v[j] >= lo && v[j] <= 16, "%s: %s[%d] = %d is outside %d..16", what, name, j, v[j], lo);
+    FTR_REQUIRE(j == 0 || v[j] > v[j - 1], "%s: %s must be strictly increasing (%s[%d] = %d after %d)", what, name, name, j,
+                v[j], v[j - 1]);
+  }
+  return FTR_OK;
+}
+int tdt_check_moves(const char* what, const int32_t* token_durations, int Dx, const int32_t* blank_durations, int Dy) {
+  int rc = tdt_check_list(what, "token_durations", token_durations, Dx, 8, 0);
+  if (rc != FTR_OK) return rc;
+  rc = tdt_check_list(what, "blank_durations", blank_durations, Dy, 8, 1);
+  if (rc != FTR_OK) return rc;
+  FTR_REQUIRE(Dx + Dy <= 9, "%s: Dx + Dy = %d moves (token_durations and blank_durations together), at most 9", what, Dx + Dy);
+  return FTR_OK;
+}
+int tdt_check_head(const char* what, const int32_t* durations, int N, double sigma, int blank, int C) {
+  int rc = tdt_check_list(what, "durations", durations, N, 5, 0);
+  if (rc != FTR_OK) return rc;
+  FTR_REQUIRE(durations[N - 1] >= 1, "%s: durations holds no positive value: no move advances a frame", what);
+  FTR_REQUIRE(sigma >= 0.0, "%s: sigma = %g must not be negative", what, sigma);
+  FTR_REQUIRE(C >= 1 && blank >= 0 && blank < C, "%s: termination_symbol %d not in [0,%d)", what, blank, C);
+  return FTR_OK;
+}
+}  // namespace
+
+size_t ftr_mutual_information_tdt_workspace_floats(int B, int S, int T) { return mi_tdt_workspace_floats(B, S, T); }
+
+int ftr_mutual_information_tdt_fwd_f32(const float* px, const float* py, const int32_t* boundary,
+                                       const int32_t* token_durations, int Dx, const int32_t* blank_durations, int Dy,
+                                       float* workspace, size_t workspace_floats, float* ans, int B, int S, int T,
+                                       void* stream) {
+  const char* what = "mutual_information_tdt_fwd";
+  clear_error();
+  int rc = tdt_check_moves(what, token_durations, Dx, blank_durations, Dy);
+  if (rc != FTR_OK) return rc;
+  FTR_REQUIRE(B >= 0 && S >= 0 && T >= 0, "%s: negative size B=%d S=%d T=%d", what, B, S, T);
+  if (B == 0) return FTR_OK;
+  FTR_REQUIRE(workspace_floats >= mi_tdt_workspace_floats(B, S, T), "%s: workspace of %zu floats is too small, %zu needed",
+              what, workspace_floats, mi_tdt_workspace_floats(B, S, T));
+  FTR_REQUIRE(workspace && ans && (py || T == 0) && (px || S == 0), "%s: null px / py / workspace / ans", what);
+  FTR_REQUIRE(((uintptr_t)workspace & 7) == 0, "%s: workspace must be 8-byte aligned", what);
+  rc = device_ok();
+  if (rc != FTR_OK) return rc;
+  return mi_tdt_fwd(px, py, boundary, token_durations, Dx, blank_durations, Dy, workspace, workspace_floats, ans, B, S, T,
+                    reinterpret_cast<hipStream_t>(stream));
+}
+
+int ftr_mutual_information_tdt_bwd_f32(const float* px, const float* py, const int32_t* boundary,
+                                       const int32_t* token_durations, int Dx, const int32_t* blank_durations, int Dy,
+                                       float* workspace, size_t workspace_floats, const float* ans_grad, float* px_grad,
+                                       float* py_grad, int B, int S, int T, void* stream) {
+  const char* what = "mutual_information_tdt_bwd";
+  clear_error();
+  int rc = tdt_check_moves(what, token_durations, Dx, blank_durations, Dy);
+  if (rc != FTR_OK) return rc;
+  FTR_REQUIRE(B >= 0 && S >= 0 && T >= 0, "%s: negative size B=%d S=%d T=%d", what, B, S, T);
+  if (B == 0) return FTR_OK;
+  FTR_REQUIRE(workspace_floats >= mi_tdt_workspace_floats(B, S, T), "%s: workspace of %zu floats is too small, %zu needed",
+              what, workspace_floats, mi_tdt_workspace_floats(B, S, T));
+  FTR_REQUIRE(workspace && (py || T == 0) && (px || S == 0), "%s: null px / py / workspace", what);
+  FTR_REQUIRE((py_grad || T == 0) && (px_grad || S == 0), "%s: null px_grad / py_grad", what);
+  FTR_REQUIRE(((uintptr_t)workspace & 7) == 0, "%s: workspace must be 8-byte aligned", what);
+  rc = device_ok();
+  if (rc != FTR_OK) return rc;
+  return mi_tdt_bwd(px, py, boundary, token_durations, Dx, blank_durations, Dy, workspace, workspace_floats, ans_grad,
+                    px_grad, py_grad, B, S, T, reinterpret_cast<hipStream_t>(stream));
+}
+
+int ftr_tdt_pruned_logprobs_fwd_f32(const float* logits, const int32_t* symbols, const int32_t* ranges,
+                                    const int32_t* boundary, int termination_symbol, const int32_t* durations, int N,
+                                    double sigma, double delay_penalty, float* lse_tok, float* lse_dur, float* px,
+                                    float* py, int B, int T, int S, int C, int r, void* stream) {
+  const char* what = "tdt_pruned_logprobs_fwd";
+  clear_error();
+  int rc = tdt_check_head(what, durations, N, sigma, termination_symbol, C);
+  if (rc != FTR_OK) return rc;
+  FTR_REQUIRE(B >= 0 && T >= 1 && S >= 0 && r >= 1, "%s: bad sizes", what);
+  FTR_REQUIRE(r <= S + 1, "%s: s_range %d > S+1 = %d", what, r, S + 1);
+  if (B == 0) return FTR_OK;
+  FTR_REQUIRE(logits && ranges && lse_tok && lse_dur && py && (symbols || S == 0) && (px || S == 0), "%s: null pointer", what);
+  rc = device_ok();
+  if (rc != FTR_OK) return rc;
+  return tdt_logprobs_fwd(logits, symbols, ranges, boundary, termination_symbol, durations, N, sigma, delay_penalty, lse_tok,
+                          lse_dur, px, py, B, T, S, C, r, reinterpret_cast<hipStream_t>(stream));
+}
+
+int ftr_tdt_pruned_logprobs_bwd_scaled_f32(const float* logits, const int32_t* symbols, const int32_t* ranges,
+                                           const int32_t* boundary, int termination_symbol, const int32_t* durations,
+                                           int N, double sigma, double delay_penalty, const float* lse_tok,
+                                           const float* lse_dur, const float* gpx, const float* gpy, const float* scale,
+                                           int scale_stride, float scale_mul, float* glogits, int B, int T, int S, int C,
+                                           int r, void* stream) {
+  const char* what = "tdt_pruned_logprobs_bwd_scaled";
+  clear_error();
+  (void)delay_penalty;   // a constant added to px: no gradient
+  int rc = tdt_check_head(what, durations, N, sigma, termination_symbol, C);
+  if (rc != FTR_OK) return rc;
+  FTR_REQUIRE(B >= 0 && T >= 1 && S >= 0 && r >= 1, "%s: bad sizes", what);
+  FTR_REQUIRE(scale_stride == 0 || scale_stride == 1, "%s: scale_stride must be 0 or 1", what);
+  if (B == 0) return FTR_OK;
+  FTR_REQUIRE(logits && ranges && lse_tok && lse_dur && gpy && glogits && (symbols || S == 0) && (gpx || S == 0),
+              "%s: null pointer", what);
+  rc = device_ok();
+  if (rc != FTR_OK) return rc;
+  return tdt_logprobs_bwd(logits, symbols, ranges, boundary, termination_symbol, durations, N, lse_tok, lse_dur, gpx, gpy,
+                          Scale{scale, scale_stride, scale_mul}, glogits, B, T, S, C, r,
+                          reinterpret_cast<hipStream_t>(stream));
+}
+
+
 int ftr_selftest(void* scratch_dev, void* stream) {
   clear_error();
   FTR_REQUIRE(scratch_dev, "selftest: need >= 8 KiB of device scratch");

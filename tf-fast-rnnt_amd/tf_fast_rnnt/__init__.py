@@ -15,6 +15,9 @@ from .rnnt_loss import get_rnnt_prune_ranges
 from .rnnt_loss import get_hat_logprobs_joint, get_hat_logprobs_pruned, hat_loss, hat_loss_pruned  # MI355X addition: HAT loss, see hat_loss_pruned
 from .rnnt_loss import get_rnnt_logprobs_multiblank_joint, get_rnnt_logprobs_multiblank_pruned   # MI355X addition: multi-blank
 from .rnnt_loss import rnnt_loss_multiblank, rnnt_loss_multiblank_pruned                           # transducer loss, see there
+from .mutual_information import mutual_information_recursion_tdt           # MI355X addition: token-and-duration (TDT) lattice
+from .rnnt_loss import get_rnnt_logprobs_tdt_joint, get_rnnt_logprobs_tdt_pruned   # MI355X addition: TDT loss, a separate
+from .rnnt_loss import rnnt_loss_tdt, rnnt_loss_tdt_pruned                         # duration head, see there
 from .rnnt_loss import rnnt_loss
 from .rnnt_loss import rnnt_loss_pruned
 from .rnnt_loss import rnnt_alignment_pruned                                   # MI355X addition: best-path alignment, see its docstring

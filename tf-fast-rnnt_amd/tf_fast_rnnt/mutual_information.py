@@ -315,6 +315,118 @@ def mutual_information_recursion_multiblank(
     return (ans, (px_grad, py_grad)) if calc_gradients else ans
 
 
+def _check_tdt_moves(token_durations, blank_durations) -> Tuple[Tuple[int, ...], Tuple[int, ...]]:
+    tok = tuple(int(d) for d in token_durations)
+    blk = tuple(int(d) for d in blank_durations)
+    for name, v, lo in (("token_durations", tok, 0), ("blank_durations", blk, 1)):
+        if len(v) < 1:
+            raise ValueError(f"{name} must hold at least one value")
+        if any(d < lo or d > 16 for d in v) or any(b <= a for a, b in zip(v, v[1:])):
+            raise ValueError(f"{name} must be strictly increasing values in {lo}..16, got {v}")
+    if len(tok) + len(blk) > 9:
+        raise ValueError(f"token_durations and blank_durations hold {len(tok) + len(blk)} moves together, at most 9 are supported")
+    return tok, blk
+
+
+def tdt_forward_backward(px: torch.Tensor, py: torch.Tensor, token_durations, blank_durations,
+                         boundary: Optional[torch.Tensor], need_grads: bool):
+    """The TDT recursion on raw tensors (no autograd): forward and, when wanted, the backward seeded with ones, back to
+    back on torch's current stream.  Returns (ans, px_grad|None, py_grad|None)."""
+    import ctypes
+    _require_gpu(px, "px"); _require_gpu(py, "py")
+    if px.dtype != torch.float32 or py.dtype != torch.float32:
+        raise TypeError("px and py must be float32")
+    tok, blk = _check_tdt_moves(token_durations, blank_durations)
+    Dx, Dy = len(tok), len(blk)
+    if px.dim() != 4 or py.dim() != 4:
+        raise ValueError("px must be [B,Dx,S,T+1] and py [B,Dy,S+1,T]")
+    B, _, S, T1 = px.shape
+    T = py.shape[3]
+    if T1 != T + 1:
+        raise ValueError(f"px.shape[-1]={T1} must be T+1 with T=py.shape[-1]={T} (regular type only)")
+    if tuple(px.shape) != (B, Dx, S, T + 1):
+        raise ValueError(f"px must have shape {(B, Dx, S, T + 1)}, got {tuple(px.shape)}")
+    if tuple(py.shape) != (B, Dy, S + 1, T):
+        raise ValueError(f"py must have shape {(B, Dy, S + 1, T)}, got {tuple(py.shape)}")
+    px = px.contiguous(); py = py.contiguous()
+    boundary = _as_boundary(boundary, B, px.device)
+    tok_arr = (ctypes.c_int32 * Dx)(*tok)       # read by the launch itself: no device copy, no host synchronisation
+    blk_arr = (ctypes.c_int32 * Dy)(*blk)
+    L = _lib.lib()
+    with torch.cuda.device(px.device):
+        st = _stream_ptr(px)
+        nws = L.ftr_mutual_information_tdt_workspace_floats(B, S, T)
+        ws = torch.empty((max(nws, 2) + 1) // 2, dtype=torch.float64, device=px.device)
+        ans = torch.empty((B,), dtype=torch.float32, device=px.device)
+        _lib.call("ftr_mutual_information_tdt_fwd_f32", _ptr(px), _ptr(py), _ptr(boundary), tok_arr, Dx, blk_arr, Dy,
+                  _ptr(ws), nws, _ptr(ans), B, S, T, st)
+        if not need_grads:
+            return ans, None, None
+        px_grad = torch.empty_like(px)
+        py_grad = torch.empty_like(py)
+        _lib.call("ftr_mutual_information_tdt_bwd_f32", _ptr(px), _ptr(py), _ptr(boundary), tok_arr, Dx, blk_arr, Dy,
+                  _ptr(ws), nws, None, _ptr(px_grad), _ptr(py_grad), B, S, T, st)
+    return ans, px_grad, py_grad
+
+
+class _MutualInformationTdt(torch.autograd.Function):
+    """The TDT recursion and its gradient, as _MutualInformationMultiblank."""
+
+    @staticmethod
+    def forward(ctx, px, py, token_durations, blank_durations, boundary, calc_gradients):
+        need = bool(calc_gradients) or px.requires_grad or py.requires_grad
+        ans, px_grad, py_grad = tdt_forward_backward(px.detach(), py.detach(), token_durations, blank_durations, boundary, need)
+        if need:
+            ctx.save_for_backward(px_grad, py_grad)
+        ctx.have_grads = need
+        if px_grad is None:
+            px_grad = torch.zeros_like(px)
+            py_grad = torch.zeros_like(py)
+        ctx.mark_non_differentiable(px_grad, py_grad)
+        ctx.set_materialize_grads(False)
+        return ans, px_grad, py_grad
+
+    @staticmethod
+    def backward(ctx, g_ans, _g1, _g2):
+        if not ctx.have_grads:
+            raise RuntimeError("mutual_information_recursion_tdt: backward without saved occupancies")
+        px_grad, py_grad = ctx.saved_tensors
+        if g_ans is None:
+            return None, None, None, None, None, None
+        g = g_ans.reshape(-1, 1, 1, 1)
+        return g * px_grad, g * py_grad, None, None, None, None
+
+
+def mutual_information_recursion_tdt(
+    px: torch.Tensor,
+    py: torch.Tensor,
+    token_durations,
+    blank_durations,
+    boundary: Optional[torch.Tensor] = None,
+    calc_gradients: bool = False,
+) -> Union[Tuple[torch.Tensor, Tuple[torch.Tensor, torch.Tensor]], torch.Tensor]:
+    """``mutual_information_recursion`` over the lattice of the token-and-duration transducer (TDT; Xu et al., "Efficient
+    Sequence Transduction by Jointly Predicting Tokens and Durations", ICML 2023; MI355X addition, no reference
+    counterpart; csrc/mi_tdt.hip): every move, symbol or blank, also says how many frames it advances.  Regular type only.
+
+    px: [B,Dx,S,T+1], ``px[b,i,s,t]`` being the log-probability of the move (s,t) -> (s+1,t+token_durations[i]);
+    py: [B,Dy,S+1,T], ``py[b,j,s,t]`` that of the move (s,t) -> (s,t+blank_durations[j]).  token_durations: Dx >= 1
+    strictly increasing ints in 0..16; blank_durations: Dy >= 1 strictly increasing ints in 1..16; Dx + Dy <= 9;
+    boundary: int32 [B,4] or None.
+
+        p[s,t] = logadd(logadd_i p[s-1,t-e_i] + px[i,s-1,t-e_i], logadd_j p[s,t-d_j] + py[j,s,t-d_j]),  p[s_begin,t_begin] = 0
+
+    Moves that would leave the boundary rectangle are ignored whatever value they carry.  Returns ``ans`` [B] =
+    ``p[s_end,t_end]`` (-inf when no path exists; the gradients are then zero, never NaN; 0 for an inverted rectangle);
+    with ``calc_gradients`` also ``(px_grad, py_grad)``, the occupancies, in the shapes of px and py and zero outside
+    the rectangle.  With ``token_durations=(0,)`` this is ``mutual_information_recursion_multiblank``, with ``(0,)`` and
+    ``(1,)`` the lattice of ``mutual_information_recursion``.  Differentiable w.r.t. px and py; asynchronous on torch's
+    current stream, no host read (capturable)."""
+    ans, px_grad, py_grad = _MutualInformationTdt.apply(px, py, tuple(token_durations), tuple(blank_durations), boundary,
+                                                        calc_gradients)
+    return (ans, (px_grad, py_grad)) if calc_gradients else ans
+
+
 def mutual_information_viterbi(px: torch.Tensor, py: torch.Tensor,
                                boundary: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor]:
     """Best-path (Viterbi) alignment over the lattice of ``mutual_information_recursion`` (MI355X addition, no reference

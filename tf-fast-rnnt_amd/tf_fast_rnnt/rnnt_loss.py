@@ -30,7 +30,7 @@ import torch
 from . import _lib
 from .mutual_information import (_as_boundary, _ptr, _require_gpu, _stream_ptr, cummin,
                                  mb_forward_backward, mi_forward_backward, mutual_information_recursion,
-                                 mutual_information_viterbi)
+                                 mutual_information_viterbi, tdt_forward_backward)
 
 _NEG_INF = float("-inf")
 # tf.math.nextafter(0., 1.) : smallest positive float32 subnormal (rnnt_loss.py:181,1272,1280)
@@ -1125,6 +1125,206 @@ def rnnt_loss_multiblank(
     return rnnt_loss_multiblank_pruned(logits=logits, symbols=symbols, ranges=ranges, termination_symbol=termination_symbol,
                                        big_blanks=big_blanks, boundary=boundary, sigma=sigma, delay_penalty=delay_penalty,
                                        reduction=reduction)
+
+
+# ---- token-and-duration transducer, TDT (MI355X addition, no reference counterpart): a separate duration head
+
+def _tdt_args(durations, termination_symbol: int, width: int):
+    """(host int32 array, durations, blank_durations, C) for a joiner row of ``width`` = C + N columns.  The checks are
+    those of the native entry points, raised here as ValueError before anything is allocated."""
+    import ctypes
+    durs = tuple(int(d) for d in durations)
+    if not 1 <= len(durs) <= 5:
+        raise ValueError(f"durations must hold 1..5 values, got {len(durs)}")
+    if any(d < 0 or d > 16 for d in durs) or any(b <= a for a, b in zip(durs, durs[1:])):
+        raise ValueError(f"durations must be strictly increasing values in 0..16, got {durs}")
+    if durs[-1] < 1:
+        raise ValueError(f"durations must hold a positive value, got {durs}")
+    C = int(width) - len(durs)
+    if C < 1:
+        raise ValueError(f"logits have {width} columns, fewer than one token column and {len(durs)} duration columns")
+    if not 0 <= int(termination_symbol) < C:
+        raise ValueError(f"termination_symbol {termination_symbol} not in [0,{C})")
+    return (ctypes.c_int32 * len(durs))(*durs), durs, tuple(d for d in durs if d > 0), C
+
+
+def _tdt_builder_fwd(x, symbols, ranges, boundary, blank, arr, durs, blank_durs, C, sigma, delay_penalty):
+    B, T, r, _ = x.shape
+    S = symbols.shape[1]
+    lse_tok = torch.empty((B, T, r), dtype=torch.float32, device=x.device)
+    lse_dur = torch.empty((B, T, r), dtype=torch.float32, device=x.device)
+    px = torch.empty((B, len(durs), S, T + 1), dtype=torch.float32, device=x.device)
+    py = torch.empty((B, len(blank_durs), S + 1, T), dtype=torch.float32, device=x.device)
+    with torch.cuda.device(x.device):
+        _lib.call("ftr_tdt_pruned_logprobs_fwd_f32", _ptr(x), _ptr(symbols), _ptr(ranges), _ptr(boundary), blank, arr,
+                  len(durs), float(sigma), float(delay_penalty), _ptr(lse_tok), _ptr(lse_dur), _ptr(px), _ptr(py), B, T, S, C,
+                  r, _stream_ptr(x))
+    return lse_tok, lse_dur, px, py
+
+
+def _tdt_builder_bwd(x, symbols, ranges, boundary, blank, arr, N, C, sigma, delay_penalty, lse_tok, lse_dur, gpx, gpy, scale,
+                     stride, mul):
+    B, T, r, _ = x.shape
+    S = symbols.shape[1]
+    g = torch.empty_like(x)
+    with torch.cuda.device(x.device):
+        _lib.call("ftr_tdt_pruned_logprobs_bwd_scaled_f32", _ptr(x), _ptr(symbols), _ptr(ranges), _ptr(boundary), blank, arr,
+                  N, float(sigma), float(delay_penalty), _ptr(lse_tok), _ptr(lse_dur), _ptr(gpx), _ptr(gpy), _ptr(scale),
+                  stride, mul, _ptr(g), B, T, S, C, r, _stream_ptr(x))
+    return g
+
+
+class _TdtLogprobs(torch.autograd.Function):
+    """get_rnnt_logprobs_tdt_pruned: the two log-sum-exps and one gather launch, one gradient launch."""
+
+    @staticmethod
+    def forward(ctx, logits, symbols, ranges, termination_symbol, durations, boundary, sigma, delay_penalty):
+        x = logits.detach().contiguous()
+        arr, durs, blank_durs, C = _tdt_args(durations, termination_symbol, x.shape[3])
+        lse_tok, lse_dur, px, py = _tdt_builder_fwd(x, symbols, ranges, boundary, int(termination_symbol), arr, durs,
+                                                    blank_durs, C, sigma, delay_penalty)
+        ctx.save_for_backward(x, symbols, ranges, lse_tok, lse_dur, boundary if boundary is not None else torch.empty(0))
+        ctx.has_boundary = boundary is not None
+        ctx.meta = (int(termination_symbol), arr, len(durs), C, sigma, delay_penalty)
+        return px, py
+
+    @staticmethod
+    def backward(ctx, gpx, gpy):
+        x, symbols, ranges, lse_tok, lse_dur, boundary = ctx.saved_tensors
+        if not ctx.has_boundary:
+            boundary = None
+        blank, arr, N, C, sigma, delay_penalty = ctx.meta
+        g = _tdt_builder_bwd(x, symbols, ranges, boundary, blank, arr, N, C, sigma, delay_penalty, lse_tok, lse_dur,
+                             gpx.contiguous(), gpy.contiguous(), None, 0, 1.0)
+        return g, None, None, None, None, None, None, None
+
+
+class _TdtLoss(torch.autograd.Function):
+    """rnnt_loss_tdt_pruned with the whole chain native, as _MultiblankLoss: log-sum-exps + gather -> TDT recursion
+    forward and backward on the full-size lattices -> in backward() one streaming kernel turns the occupancies * upstream
+    gradient into d loss / d logits."""
+
+    @staticmethod
+    def forward(ctx, logits, symbols, ranges, termination_symbol, durations, boundary, sigma, delay_penalty, code):
+        x = logits.detach().contiguous()
+        need = logits.requires_grad
+        arr, durs, blank_durs, C = _tdt_args(durations, termination_symbol, x.shape[3])
+        lse_tok, lse_dur, px, py = _tdt_builder_fwd(x, symbols, ranges, boundary, int(termination_symbol), arr, durs,
+                                                    blank_durs, C, sigma, delay_penalty)
+        ans, px_grad, py_grad = tdt_forward_backward(px, py, durs, blank_durs, boundary, need)
+        del px, py
+        if need:
+            ctx.save_for_backward(x, symbols, ranges, lse_tok, lse_dur, px_grad, py_grad,
+                                  boundary if boundary is not None else torch.empty(0))
+        ctx.has_boundary = boundary is not None
+        ctx.meta = (int(termination_symbol), arr, len(durs), C, sigma, delay_penalty, int(code))
+        return _negated_reduce_native(ans, code)
+
+    @staticmethod
+    def backward(ctx, g_loss):
+        x, symbols, ranges, lse_tok, lse_dur, px_grad, py_grad, boundary = ctx.saved_tensors
+        if not ctx.has_boundary:
+            boundary = None
+        blank, arr, N, C, sigma, delay_penalty, code = ctx.meta
+        scale, stride, mul = _upstream_scale(g_loss, code, x.shape[0])
+        g = _tdt_builder_bwd(x, symbols, ranges, boundary, blank, arr, N, C, sigma, delay_penalty, lse_tok, lse_dur, px_grad,
+                             py_grad, scale, stride, mul)
+        return g, None, None, None, None, None, None, None, None
+
+
+def get_rnnt_logprobs_tdt_pruned(
+    logits: torch.Tensor,
+    symbols: torch.Tensor,
+    ranges: torch.Tensor,
+    termination_symbol: int,
+    durations,
+    boundary: torch.Tensor,
+    sigma: float = 0.0,
+    delay_penalty: float = 0.0,
+) -> Tuple[torch.Tensor, torch.Tensor]:
+    """TDT form of ``get_rnnt_logprobs_pruned`` (token-and-duration transducer; Xu et al., "Efficient Sequence
+    Transduction by Jointly Predicting Tokens and Durations", ICML 2023; MI355X addition, regular type only).
+    ``durations`` = (e_0 < ... < e_{N-1}): N = 1..5 ints in 0..16, at least one positive.
+
+    logits [B,T,s_range,C+N]: the first C columns of a row are token logits (``termination_symbol`` among them), the last
+    N duration logits, and the two heads are normalised independently: ``tok = log_softmax(row[:C]) - sigma`` (sigma >= 0,
+    token head only), ``dur = log_softmax(row[C:])``.  Returns
+
+    * ``px`` [B,N,S,T+1]: ``px[b,i,s,t] = tok[symbols[b,s]] + dur[i]``, the move (s,t) -> (s+1, t+e_i); -inf where
+      ``t + e_i > t_end``, at column t_end and outside the band; ``delay_penalty`` is added as in ``rnnt_loss_pruned``,
+      by source frame t;
+    * ``py`` [B,Ny,S+1,T]: ``py[b,j,s,t] = tok[termination_symbol] + dur[index of d_j]``, the move (s,t) -> (s, t+d_j),
+      d_j running over the positive durations (Ny = N or N - 1); -inf where ``t + d_j > t_end`` and outside the band.
+
+    Feed them to ``mutual_information_recursion_tdt(px, py, durations, positive durations, boundary)``.  Differentiable
+    w.r.t. ``logits``."""
+    symbols, ranges, boundary = _pruned_inputs(logits, symbols, ranges, boundary)
+    return _TdtLogprobs.apply(logits, symbols, ranges, termination_symbol, tuple(durations), boundary, _check_sigma(sigma),
+                              float(delay_penalty) if delay_penalty > 0.0 else 0.0)
+
+
+def get_rnnt_logprobs_tdt_joint(
+    logits: torch.Tensor,
+    symbols: torch.Tensor,
+    termination_symbol: int,
+    durations,
+    boundary: Optional[torch.Tensor] = None,
+    sigma: float = 0.0,
+    delay_penalty: float = 0.0,
+) -> Tuple[torch.Tensor, torch.Tensor]:
+    """``get_rnnt_logprobs_tdt_pruned`` for unpruned joiner logits [B,T,S+1,C+N], through identity ranges."""
+    ranges = _joint_inputs(logits, symbols)
+    return get_rnnt_logprobs_tdt_pruned(logits=logits, symbols=symbols, ranges=ranges, termination_symbol=termination_symbol,
+                                        durations=durations, boundary=boundary, sigma=sigma, delay_penalty=delay_penalty)
+
+
+def rnnt_loss_tdt_pruned(
+    logits: torch.Tensor,
+    symbols: torch.Tensor,
+    ranges: torch.Tensor,
+    termination_symbol: int,
+    durations,
+    boundary: torch.Tensor = None,
+    sigma: float = 0.0,
+    rnnt_type: str = "regular",
+    delay_penalty: float = 0.0,
+    reduction: Optional[str] = "mean",
+) -> torch.Tensor:
+    """TDT loss on pruned joiner logits [B,T,s_range,C+N] (MI355X addition): the lattices of
+    ``get_rnnt_logprobs_tdt_pruned`` through ``mutual_information_recursion_tdt``, negated and reduced.  Only
+    ``rnnt_type="regular"`` exists; anything else raises ValueError, as does a bad ``durations`` or a negative ``sigma``.
+
+    Prune ranges come from the ordinary ``rnnt_loss_simple``.  They guarantee a path through the band only when
+    ``durations`` contains 0 and 1 (the moves of the lattice they were computed on): with other sets a path may have to
+    leave the band, and an utterance without one gets a loss of +inf and zero gradients.  NeMo's ``omega`` is not
+    built in: mix in ``rnnt_loss_pruned`` on the token columns yourself."""
+    if rnnt_type != "regular":
+        raise ValueError(f"the TDT loss is defined for rnnt_type 'regular' only, given {rnnt_type}")
+    code = _reduction_code(reduction)
+    symbols_i, ranges_i, boundary_i = _pruned_inputs(logits, symbols, ranges, boundary)
+    _tdt_args(durations, termination_symbol, logits.shape[3])
+    return _TdtLoss.apply(logits, symbols_i, ranges_i, termination_symbol, tuple(durations), boundary_i, _check_sigma(sigma),
+                          float(delay_penalty) if delay_penalty > 0.0 else 0.0, code)
+
+
+def rnnt_loss_tdt(
+    logits: torch.Tensor,
+    symbols: torch.Tensor,
+    termination_symbol: int,
+    durations,
+    boundary: Optional[torch.Tensor] = None,
+    sigma: float = 0.0,
+    rnnt_type: str = "regular",
+    delay_penalty: float = 0.0,
+    reduction: Optional[str] = "mean",
+) -> torch.Tensor:
+    """``rnnt_loss_tdt_pruned`` for unpruned joiner logits [B,T,S+1,C+N], through identity ranges."""
+    if rnnt_type != "regular":
+        raise ValueError(f"the TDT loss is defined for rnnt_type 'regular' only, given {rnnt_type}")
+    ranges = _joint_inputs(logits, symbols)
+    return rnnt_loss_tdt_pruned(logits=logits, symbols=symbols, ranges=ranges, termination_symbol=termination_symbol,
+                                durations=durations, boundary=boundary, sigma=sigma, delay_penalty=delay_penalty,
+                                reduction=reduction)
 
 
 def _colsum_weighted(x: torch.Tensor, w: torch.Tensor, rows: int, C: int, st) -> torch.Tensor:
