@@ -596,6 +596,45 @@ int ftr_tdt_pruned_logprobs_bwd_scaled_f32(const float* logits, const int32_t* s
                                            int scale_stride, float scale_mul, float* glogits, int B, int T, int S, int C,
                                            int r, void* stream);
 
+/*
+ * Best-path (Viterbi) alignment over the TDT lattice above (MI355X addition, no reference counterpart;
+ * csrc/mi_viterbi_tdt.hip).  token_durations = (0,) is the multi-blank lattice, (0,) with (1,) the ordinary one.
+ *   px [B,Dx,S,T+1], py [B,Dy,S+1,T] float32; token_durations: Dx >= 1 strictly increasing values in 0..16;
+ *   blank_durations: Dy >= 1 strictly increasing values in 1..32 (a big blank of the multi-blank builder may advance 32
+ *   frames); Dx + Dy <= 9; both lists are host arrays read at launch; boundary int32 [B,4] or NULL.  Regular type only.
+ * Moves m = 0 .. M-1 are the token moves in list order, then the blank moves in list order.  For every cell (s,t) other
+ * than (s_begin,t_begin):
+ *   cand[m] = p[src_m] + op_m[src_m]       one float32 add; src_m = (s-1, t-e_i) with op = px[i] for a token move,
+ *                                          (s, t-d_j) with op = py[j] for a blank move; -inf when src_m lies outside the
+ *                                          boundary rectangle, whatever the operand holds
+ *   best = cand[M-1]; move = M-1
+ *   for m = M-2 .. 0:  take = (cand[m] != cand[m]) || (cand[m] >= best);  if (take) { best = cand[m]; move = m; }
+ *   p[s,t] = best
+ * p[s_begin,t_begin] = 0, score[b] = p[s_end,t_end].  A NaN propagates; a tie goes to the lowest-index move (tokens
+ * before blanks, shorter durations before longer).  One add per move and ordered selects: the result does not depend on
+ * the evaluation order and equals a float32 restatement bit for bit; with (0,) / (1,) it is the rule, and gives the
+ * score and frames, of ftr_mutual_information_viterbi_f32.
+ *   frames [B,S] int32: the source frame t of the token move the best path takes out of row s;
+ *   durations [B,S] int32: the number of frames that move advances, a member of token_durations;
+ *   blank_steps [B,T] int32: the duration of the blank move the best path takes out of frame t, 0 when it leaves t by a
+ *     token move or skips it (every blank move advances at least one frame, so at most one leaves a frame).
+ *   Rows outside [s_begin, s_end) are -1 in frames and durations, frames outside [t_begin, t_end) are -1 in
+ *   blank_steps, and all three are entirely -1 when score[b] is -inf (no path) or NaN.  An inverted rectangle gives
+ *   score 0 and -1 everywhere.
+ *   workspace: ftr_mutual_information_viterbi_tdt_workspace_bytes(B,S,T) bytes, 8-byte aligned, uninitialised is fine
+ *   (every decision word the backtrace uses is written by the same launch): 32 bytes per 64 rows and step, T + 72 steps
+ *   per block of 64 rows -- half a byte per cell of the skewed blocks -- plus two float32 rows of T + 1 per utterance
+ *   for the strip carry.  A smaller workspace_bytes returns FTR_ERR_INVALID_ARG.
+ * Invalid, unsorted or out-of-range lists and Dx + Dy > 9 return FTR_ERR_INVALID_ARG (before any device check) with a
+ * message naming the argument.  Kernels only (no memset / memcpy nodes), graph-capturable.
+ */
+size_t ftr_mutual_information_viterbi_tdt_workspace_bytes(int B, int S, int T);
+int ftr_mutual_information_viterbi_tdt_f32(const float* px, const float* py, const int32_t* boundary,
+                                           const int32_t* token_durations, int Dx, const int32_t* blank_durations, int Dy,
+                                           void* workspace, size_t workspace_bytes,
+                                           float* score, int32_t* frames, int32_t* durations, int32_t* blank_steps,
+                                           int B, int S, int T, void* stream);
+
 /* Hardware self-test used by smoke()/tests: checks on the device that the primitives the wavefront
  * kernels rely on behave as assumed (full-wave DPP shift wave_shr:1 with lane 0 keeping its old value;
  * 16-byte global loads/stores at 4-byte alignment).  scratch_dev: >= 8 KiB of device memory; after the

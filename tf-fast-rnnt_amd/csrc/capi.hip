@@ -925,20 +925,21 @@ int ftr_multiblank_pruned_logprobs_bwd_scaled_f32(const float* logits, const int
 // ---- token-and-duration transducer, TDT (MI355X addition; csrc/mi_tdt.hip, csrc/tdt_logprobs.hip).  The duration lists
 // are host data and are validated first, then sizes and pointers, then the device.
 namespace {
-int tdt_check_list(const char* what, const char* name, const int32_t* v, int n, int nmax, int lo) {
+int tdt_check_list(const char* what, const char* name, const int32_t* v, int n, int nmax, int lo, int hi = 16) {
   FTR_REQUIRE(n >= 1 && n <= nmax, "%s: %s holds %d values, must be 1..%d", what, name, n, nmax);
   FTR_REQUIRE(v, "%s: null %s", what, name);
   for (int j = 0; j < n; ++j) {
-    FTR_REQUIRE(v[j] >= lo && v[j] <= 16, "%s: %s[%d] = %d is outside %d..16", what, name, j, v[j], lo);
+    FTR_REQUIRE(v[j] >= lo && v[j] <= hi, "%s: %s[%d] = %d is outside %d..%d", what, name, j, v[j], lo, hi);
     FTR_REQUIRE(j == 0 || v[j] > v[j - 1], "%s: %s must be strictly increasing (%s[%d] = %d after %d)", what, name, name, j,
                 v[j], v[j - 1]);
   }
   return FTR_OK;
 }
-int tdt_check_moves(const char* what, const int32_t* token_durations, int Dx, const int32_t* blank_durations, int Dy) {
+int tdt_check_moves(const char* what, const int32_t* token_durations, int Dx, const int32_t* blank_durations, int Dy,
+                    int blank_hi = 16) {
   int rc = tdt_check_list(what, "token_durations", token_durations, Dx, 8, 0);
   if (rc != FTR_OK) return rc;
-  rc = tdt_check_list(what, "blank_durations", blank_durations, Dy, 8, 1);
+  rc = tdt_check_list(what, "blank_durations", blank_durations, Dy, 8, 1, blank_hi);
   if (rc != FTR_OK) return rc;
   FTR_REQUIRE(Dx + Dy <= 9, "%s: Dx + Dy = %d moves (token_durations and blank_durations together), at most 9", what, Dx + Dy);
   return FTR_OK;
@@ -994,6 +995,34 @@ int ftr_mutual_information_tdt_bwd_f32(const float* px, const float* py, const i
   if (rc != FTR_OK) return rc;
   return mi_tdt_bwd(px, py, boundary, token_durations, Dx, blank_durations, Dy, workspace, workspace_floats, ans_grad,
                     px_grad, py_grad, B, S, T, reinterpret_cast<hipStream_t>(stream));
+}
+
+// Best-path alignment over the TDT / multi-blank lattice (csrc/mi_viterbi_tdt.hip).  A blank may advance 32 frames here,
+// as a big blank of the multi-blank builder does.
+size_t ftr_mutual_information_viterbi_tdt_workspace_bytes(int B, int S, int T) {
+  return mi_viterbi_tdt_workspace_bytes(B, S, T);
+}
+
+int ftr_mutual_information_viterbi_tdt_f32(const float* px, const float* py, const int32_t* boundary,
+                                           const int32_t* token_durations, int Dx, const int32_t* blank_durations, int Dy,
+                                           void* workspace, size_t workspace_bytes, float* score, int32_t* frames,
+                                           int32_t* durations, int32_t* blank_steps, int B, int S, int T, void* stream) {
+  const char* what = "mutual_information_viterbi_tdt";
+  clear_error();
+  int rc = tdt_check_moves(what, token_durations, Dx, blank_durations, Dy, 32);
+  if (rc != FTR_OK) return rc;
+  FTR_REQUIRE(B >= 0 && S >= 0 && T >= 0, "%s: negative size B=%d S=%d T=%d", what, B, S, T);
+  if (B == 0) return FTR_OK;
+  FTR_REQUIRE(workspace_bytes >= mi_viterbi_tdt_workspace_bytes(B, S, T), "%s: workspace of %zu bytes is too small, %zu needed",
+              what, workspace_bytes, mi_viterbi_tdt_workspace_bytes(B, S, T));
+  FTR_REQUIRE(workspace && score && (py || T == 0) && (px || S == 0), "%s: null px / py / workspace / score", what);
+  FTR_REQUIRE((frames && durations) || S == 0, "%s: null frames / durations", what);
+  FTR_REQUIRE(blank_steps || T == 0, "%s: null blank_steps", what);
+  FTR_REQUIRE(((uintptr_t)workspace & 7) == 0, "%s: workspace must be 8-byte aligned", what);
+  rc = device_ok();
+  if (rc != FTR_OK) return rc;
+  return mi_viterbi_tdt(px, py, boundary, token_durations, Dx, blank_durations, Dy, workspace, workspace_bytes, score, frames,
+                        durations, blank_steps, B, S, T, reinterpret_cast<hipStream_t>(stream));
 }
 
 int ftr_tdt_pruned_logprobs_fwd_f32(const float* logits, const int32_t* symbols, const int32_t* ranges,

@@ -184,6 +184,9 @@ int mi_tdt_fwd(const float* px, const float* py, const int32_t* boundary, const 
 int mi_tdt_bwd(const float* px, const float* py, const int32_t* boundary, const int32_t* token_durations, int Dx, const int32_t* blank_durations, int Dy, float* ws, size_t ws_floats, const float* ans_grad, float* px_grad, float* py_grad, int B, int S, int T, hipStream_t st);
 int tdt_logprobs_fwd(const float* logits, const int32_t* symbols, const int32_t* ranges, const int32_t* boundary, int blank, const int32_t* durations, int N, double sigma, double delay_penalty, float* lse_tok, float* lse_dur, float* px, float* py, int B, int T, int S, int C, int r, hipStream_t st);
 int tdt_logprobs_bwd(const float* logits, const int32_t* symbols, const int32_t* ranges, const int32_t* boundary, int blank, const int32_t* durations, int N, const float* lse_tok, const float* lse_dur, const float* gpx, const float* gpy, Scale scale, float* glogits, int B, int T, int S, int C, int r, hipStream_t st);
+// best-path alignment over the TDT / multi-blank lattice: csrc/mi_viterbi_tdt.hip; the duration lists are host arrays
+size_t mi_viterbi_tdt_workspace_bytes(int B, int S, int T);
+int mi_viterbi_tdt(const float* px, const float* py, const int32_t* boundary, const int32_t* token_durations, int Dx, const int32_t* blank_durations, int Dy, void* ws, size_t ws_bytes, float* score, int32_t* frames, int32_t* durations, int32_t* blank_steps, int B, int S, int T, hipStream_t st);
 int cummin_i32(const int32_t* in, int32_t* out, int rows, int cols, hipStream_t st);
 int prune_ranges(const float* px_grad, const float* py_grad, const int32_t* boundary, int32_t* ranges, int32_t* s_begin, int B, int S, int T, int T1, int r, hipStream_t st);
 int do_pruning(const float* am, const float* lm, const int32_t* ranges, float* am_p, float* lm_p, int B, int T, int S1, int C, int r, hipStream_t st);

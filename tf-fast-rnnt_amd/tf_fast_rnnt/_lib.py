@@ -91,6 +91,8 @@ _SIGNATURES = {
     "ftr_mutual_information_tdt_workspace_floats": (ctypes.c_size_t, [_i, _i, _i]),
     "ftr_mutual_information_tdt_fwd_f32": (_i, [_c_fp, _c_fp, _c_ip, _c_hi, _i, _c_hi, _i, _c_fp, ctypes.c_size_t, _c_fp, _i, _i, _i, _c_st]),
     "ftr_mutual_information_tdt_bwd_f32": (_i, [_c_fp, _c_fp, _c_ip, _c_hi, _i, _c_hi, _i, _c_fp, ctypes.c_size_t, _c_fp, _c_fp, _c_fp, _i, _i, _i, _c_st]),
+    "ftr_mutual_information_viterbi_tdt_workspace_bytes": (ctypes.c_size_t, [_i, _i, _i]),
+    "ftr_mutual_information_viterbi_tdt_f32": (_i, [_c_fp, _c_fp, _c_ip, _c_hi, _i, _c_hi, _i, ctypes.c_void_p, ctypes.c_size_t, _c_fp, _c_ip, _c_ip, _c_ip, _i, _i, _i, _c_st]),
     "ftr_tdt_pruned_logprobs_fwd_f32": (_i, [_c_fp, _c_ip, _c_ip, _c_ip, _i, _c_hi, _i, ctypes.c_double, ctypes.c_double, _c_fp, _c_fp, _c_fp, _c_fp, _i, _i, _i, _i, _i, _c_st]),
     "ftr_tdt_pruned_logprobs_bwd_scaled_f32": (_i, [_c_fp, _c_ip, _c_ip, _c_ip, _i, _c_hi, _i, ctypes.c_double, ctypes.c_double, _c_fp, _c_fp, _c_fp, _c_fp, _c_fp, _i, _f, _c_fp, _i, _i, _i, _i, _i, _c_st]),
     "ftr_simple_logprobs_fwd_f32": (_i, [_c_fp, _c_fp, _c_ip, _c_fp, _c_fp, _c_fp, _c_ip, _i, ctypes.c_double, _c_fp, _c_fp, _i, _i, _i, _i, _i, _c_st]),

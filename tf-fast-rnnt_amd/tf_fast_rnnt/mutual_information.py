@@ -315,14 +315,14 @@ def mutual_information_recursion_multiblank(
     return (ans, (px_grad, py_grad)) if calc_gradients else ans
 
 
-def _check_tdt_moves(token_durations, blank_durations) -> Tuple[Tuple[int, ...], Tuple[int, ...]]:
+def _check_tdt_moves(token_durations, blank_durations, blank_hi: int = 16) -> Tuple[Tuple[int, ...], Tuple[int, ...]]:
     tok = tuple(int(d) for d in token_durations)
     blk = tuple(int(d) for d in blank_durations)
-    for name, v, lo in (("token_durations", tok, 0), ("blank_durations", blk, 1)):
+    for name, v, lo, hi in (("token_durations", tok, 0, 16), ("blank_durations", blk, 1, blank_hi)):
         if len(v) < 1:
             raise ValueError(f"{name} must hold at least one value")
-        if any(d < lo or d > 16 for d in v) or any(b <= a for a, b in zip(v, v[1:])):
-            raise ValueError(f"{name} must be strictly increasing values in {lo}..16, got {v}")
+        if any(d < lo or d > hi for d in v) or any(b <= a for a, b in zip(v, v[1:])):
+            raise ValueError(f"{name} must be strictly increasing values in {lo}..{hi}, got {v}")
     if len(tok) + len(blk) > 9:
         raise ValueError(f"token_durations and blank_durations hold {len(tok) + len(blk)} moves together, at most 9 are supported")
     return tok, blk
@@ -475,6 +475,75 @@ def mutual_information_viterbi(px: torch.Tensor, py: torch.Tensor,
         _lib.call("ftr_mutual_information_viterbi_f32", _ptr(px), _ptr(py), _ptr(boundary), _ptr(ws), nbytes,
                   _ptr(score), _ptr(frames), B, S, T, modified, _stream_ptr(px))
     return score, frames
+
+
+def mutual_information_viterbi_tdt(px: torch.Tensor, py: torch.Tensor, token_durations, blank_durations,
+                                   boundary: Optional[torch.Tensor] = None
+                                   ) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]:
+    """Best-path (Viterbi) alignment over the lattice of ``mutual_information_recursion_tdt`` (MI355X addition, no
+    reference counterpart; ftr_mutual_information_viterbi_tdt_f32, csrc/mi_viterbi_tdt.hip).  ``token_durations=(0,)``
+    is the multi-blank lattice, ``(0,)`` with ``(1,)`` the ordinary one.  Regular type only.
+
+    px [B,Dx,S,T+1], py [B,Dy,S+1,T], float32, as ``mutual_information_recursion_tdt``; token_durations: Dx >= 1
+    strictly increasing ints in 0..16; blank_durations: Dy >= 1 strictly increasing ints in 1..32 (a big blank may
+    advance 32 frames); Dx + Dy <= 9; boundary int32 [B,4] or None.  The moves m = 0..M-1 are the token moves in list
+    order, then the blank moves in list order, and for every cell but (s_begin,t_begin)::
+
+        cand[m] = p[src_m] + op_m[src_m]      # one float32 add; src_m = (s-1, t-e_i) or (s, t-d_j); -inf when src_m
+                                              # lies outside the boundary rectangle, whatever the operand holds
+        best, move = cand[M-1], M-1
+        for m in M-2 .. 0:
+            take = (cand[m] != cand[m]) or (cand[m] >= best)
+            if take: best, move = cand[m], m
+        p[s, t] = best
+
+    with ``p[s_begin, t_begin] = 0``: a NaN propagates and a tie goes to the lowest-index move (tokens before blanks,
+    shorter durations before longer).  With ``(0,)`` / ``(1,)`` this is the rule of ``mutual_information_viterbi``.
+    Returns ``(score, frames, durations, blank_steps)``:
+
+    * ``score`` [B] float32 = ``p[s_end, t_end]``, bit-identical to a float32 restatement;
+    * ``frames`` [B,S] int32: the source frame of the token move the best path takes out of row s (it emits
+      ``symbols[b,s]`` there);
+    * ``durations`` [B,S] int32: the number of frames that move advances, a member of ``token_durations``;
+    * ``blank_steps`` [B,T] int32: the duration of the blank move the best path takes out of frame t, 0 when it leaves
+      t by a token move or skips it.
+
+    Rows outside [s_begin, s_end) are -1 in ``frames`` and ``durations``, frames outside [t_begin, t_end) are -1 in
+    ``blank_steps``, all three are entirely -1 for an utterance whose score is -inf (no path) or NaN, and an inverted
+    rectangle gives score 0 and -1 everywhere.  Not differentiable: the outputs are detached.  Asynchronous on torch's
+    current stream, no host read (capturable)."""
+    import ctypes
+    _require_gpu(px, "px"); _require_gpu(py, "py")
+    if px.dtype != torch.float32 or py.dtype != torch.float32:
+        raise TypeError("px and py must be float32")
+    tok, blk = _check_tdt_moves(token_durations, blank_durations, blank_hi=32)   # a blank above 16: this entry alone
+    Dx, Dy = len(tok), len(blk)
+    if px.dim() != 4 or py.dim() != 4:
+        raise ValueError("px must be [B,Dx,S,T+1] and py [B,Dy,S+1,T]")
+    B, _, S, T1 = px.shape
+    T = py.shape[3]
+    if T1 != T + 1:
+        raise ValueError(f"px.shape[-1]={T1} must be T+1 with T=py.shape[-1]={T} (regular type only)")
+    if tuple(px.shape) != (B, Dx, S, T + 1):
+        raise ValueError(f"px must have shape {(B, Dx, S, T + 1)}, got {tuple(px.shape)}")
+    if tuple(py.shape) != (B, Dy, S + 1, T):
+        raise ValueError(f"py must have shape {(B, Dy, S + 1, T)}, got {tuple(py.shape)}")
+    px = px.detach().contiguous(); py = py.detach().contiguous()
+    boundary = _as_boundary(boundary, B, px.device)
+    tok_arr = (ctypes.c_int32 * Dx)(*tok)       # read by the launch itself: no device copy, no host synchronisation
+    blk_arr = (ctypes.c_int32 * Dy)(*blk)
+    L = _lib.lib()
+    with torch.cuda.device(px.device):
+        nbytes = L.ftr_mutual_information_viterbi_tdt_workspace_bytes(B, S, T)
+        ws = torch.empty(((max(nbytes, 8) + 7) // 8,), dtype=torch.int64, device=px.device)
+        score = torch.empty((B,), dtype=torch.float32, device=px.device)
+        frames = torch.empty((B, S), dtype=torch.int32, device=px.device)
+        durations = torch.empty((B, S), dtype=torch.int32, device=px.device)
+        blank_steps = torch.empty((B, T), dtype=torch.int32, device=px.device)
+        _lib.call("ftr_mutual_information_viterbi_tdt_f32", _ptr(px), _ptr(py), _ptr(boundary), tok_arr, Dx, blk_arr, Dy,
+                  _ptr(ws), nbytes, _ptr(score), _ptr(frames), _ptr(durations), _ptr(blank_steps), B, S, T,
+                  _stream_ptr(px))
+    return score, frames, durations, blank_steps
 
 
 def cummin(x: torch.Tensor) -> torch.Tensor:

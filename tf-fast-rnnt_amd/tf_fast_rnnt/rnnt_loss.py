@@ -30,7 +30,7 @@ import torch
 from . import _lib
 from .mutual_information import (_as_boundary, _ptr, _require_gpu, _stream_ptr, cummin,
                                  mb_forward_backward, mi_forward_backward, mutual_information_recursion,
-                                 mutual_information_viterbi, tdt_forward_backward)
+                                 mutual_information_viterbi, mutual_information_viterbi_tdt, tdt_forward_backward)
 
 _NEG_INF = float("-inf")
 # tf.math.nextafter(0., 1.) : smallest positive float32 subnormal (rnnt_loss.py:181,1272,1280)
@@ -1325,6 +1325,59 @@ def rnnt_loss_tdt(
     return rnnt_loss_tdt_pruned(logits=logits, symbols=symbols, ranges=ranges, termination_symbol=termination_symbol,
                                 durations=durations, boundary=boundary, sigma=sigma, delay_penalty=delay_penalty,
                                 reduction=reduction)
+
+
+# ---- best-path alignment over the TDT and multi-blank lattices (MI355X addition, no reference counterpart)
+
+def rnnt_alignment_tdt_pruned(
+    logits: torch.Tensor,
+    symbols: torch.Tensor,
+    ranges: torch.Tensor,
+    termination_symbol: int,
+    durations,
+    boundary: Optional[torch.Tensor] = None,
+    sigma: float = 0.0,
+) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]:
+    """Best-path alignment of a TDT model's pruned joiner output [B,T,s_range,C+N]: the lattice of
+    ``get_rnnt_logprobs_tdt_pruned`` (no delay penalty) fed to ``mutual_information_viterbi_tdt``.  Returns
+    ``(score [B] float32, frames [B,S], durations [B,S], blank_steps [B,T] int32)``, detached; see
+    ``mutual_information_viterbi_tdt`` for their meaning: ``frames[b,s]`` is the frame that emits ``symbols[b,s]`` and
+    ``durations[b,s]`` the duration it was emitted with.  As for the loss, ranges of the ordinary simple loss guarantee
+    a path inside the band only when ``durations`` contains 0 and 1; an utterance without one gets score -inf and -1
+    everywhere.  Every step runs on the device with no host read, so the call can be captured into a graph.  For
+    unpruned joiner logits use
+    ``mutual_information_viterbi_tdt(*get_rnnt_logprobs_tdt_joint(...), durations, positive durations, boundary)``."""
+    with torch.no_grad():
+        symbols, ranges, boundary = _pruned_inputs(logits, symbols, ranges, boundary)
+        arr, durs, blank_durs, C = _tdt_args(durations, termination_symbol, logits.shape[3])
+        x = logits.detach().contiguous()
+        _, _, px, py = _tdt_builder_fwd(x, symbols, ranges, boundary, int(termination_symbol), arr, durs, blank_durs, C,
+                                        _check_sigma(sigma), 0.0)
+        return mutual_information_viterbi_tdt(px, py, durs, blank_durs, boundary)
+
+
+def rnnt_alignment_multiblank_pruned(
+    logits: torch.Tensor,
+    symbols: torch.Tensor,
+    ranges: torch.Tensor,
+    termination_symbol: int,
+    big_blanks,
+    boundary: Optional[torch.Tensor] = None,
+    sigma: float = 0.0,
+) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]:
+    """Best-path alignment of a multi-blank model's pruned joiner output [B,T,s_range,C]: the lattice of
+    ``get_rnnt_logprobs_multiblank_pruned`` fed to ``mutual_information_viterbi_tdt`` with token durations ``(0,)`` and
+    blank durations ``(1, d_1, ...)``.  Returns ``(score, frames, durations, blank_steps)`` as
+    ``rnnt_alignment_tdt_pruned`` does; ``durations`` is 0 on every valid row (a symbol stays on its frame) and
+    ``blank_steps[b,t]`` tells which blank, the standard one (1) or a big one (its duration), left frame t.  No host
+    read; capturable."""
+    with torch.no_grad():
+        symbols, ranges, boundary = _pruned_inputs(logits, symbols, ranges, boundary)
+        x = logits.detach().contiguous()
+        ids, durs, dt = _big_blank_args(tuple(map(tuple, big_blanks)), termination_symbol, x.shape[3])
+        _, px, py = _mb_builder_fwd(x, symbols, ranges, boundary, int(termination_symbol), ids, durs, len(dt),
+                                    _check_sigma(sigma), 0.0)
+        return mutual_information_viterbi_tdt(px.unsqueeze(1), py, (0,), dt, boundary)
 
 
 def _colsum_weighted(x: torch.Tensor, w: torch.Tensor, rows: int, C: int, st) -> torch.Tensor:
