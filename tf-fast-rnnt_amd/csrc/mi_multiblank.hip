@@ -14,44 +14,23 @@
 // so a cell adds ~1e-7 of absolute error instead of one float32 ulp of a p of magnitude 1e2..1e3; the occupancies are
 // exp of a float64 sum p + w + q - ans.  Float32 p-differences miss the project's 1e-4 at T = 200.
 //
-// Layout: that of mi_viterbi.hip.  One workgroup per utterance, NW waves.  Relative row r lives in wave (r / 64) % NW,
-// lane r % 64 of strip r / (64 NW).  Wave w at step k handles column t = k - lane - E w, E = 64 + CH - 1: the symbol
-// predecessor is the lower lane's value of the previous step (DPP shift), lane 0's comes from the wave below as computed
-// one chunk of CH steps earlier (one LDS slot and one barrier per chunk), the top row of a strip goes to the next strip
-// through the workspace.  The blank predecessors p[s,t-d_j] are the lane's own values of d_j steps earlier: an LDS ring
-// of depth 2^ceil(log2(max d)) per lane, which is what limits a workgroup to 256 rows (128 with a duration above 16).
-// Operands of chunk c + 1 are loaded (unconditionally, from clamped addresses) while chunk c computes.
-#include "ftr_common.h"
+// Layout: the row-per-lane sweep of mi_rowlane.h.  The symbol predecessor is the lower lane's value of the previous step
+// (DPP shift), lane 0's comes from the wave below as computed one chunk of CH steps earlier (one LDS slot and one barrier
+// per chunk), the top row of a strip goes to the next strip through the workspace.  The blank predecessors p[s,t-d_j] are
+// the lane's own values of d_j steps earlier: the history ring of mi_rowlane.h (own-lane rule only), of depth
+// 2^ceil(log2(max d)) per lane, which is what limits a workgroup to 256 rows (128 with a duration above 16).
+#include "mi_rowlane.h"
 #include "mi_wave_common.h"
 
 namespace ftr {
 namespace {
+using namespace rowlane;
 
-constexpr int MCH = 8;                 // steps per chunk
-constexpr int MBE = 64 + MCH - 1;      // skew between consecutive waves
-constexpr int MBMAXW = 4;              // waves per workgroup
 constexpr int MBMAXD = 8;              // blanks (D)
-constexpr float kLog2eF = 1.4426950408889634f;
-constexpr float kLn2F = 0.6931471805599453f;
 
 struct MbDur { int d[MBMAXD]; };
 
 inline int mb_depth(int maxd) { int n = 1; while (n < maxd) n *= 2; return n; }
-inline int mb_waves(int S, int maxd) {
-  const int cap = mb_depth(maxd) > 16 ? MBMAXW / 2 : MBMAXW;   // 32 KB of ring either way
-  const int blocks = (S + 1 + 63) / 64;
-  return blocks < cap ? blocks : cap;
-}
-
-struct MbLayout { size_t p_off, ans_off, carry_off, total; };   // in doubles
-inline MbLayout mb_layout(int B, int S, int T) {
-  MbLayout L;
-  L.p_off = 0;
-  L.ans_off = (size_t)B * (S + 1) * (T + 1);
-  L.carry_off = L.ans_off + (size_t)B;
-  L.total = L.carry_off + (size_t)B * 2 * (T + 1);
-  return L;
-}
 
 __device__ __forceinline__ double dpp_shr1_f64(double old_for_lane0, double src) {
   const long long o = __builtin_bit_cast(long long, old_for_lane0), s = __builtin_bit_cast(long long, src);
@@ -60,24 +39,21 @@ __device__ __forceinline__ double dpp_shr1_f64(double old_for_lane0, double src)
   return __builtin_bit_cast(double, ((long long)hi << 32) | (long long)(unsigned)lo);
 }
 
-// exp(v) for v a float64 log-quantity that is <= ~0 where it matters: the float32 exp2 unit
-__device__ __forceinline__ float exp_of(double v) { return __builtin_amdgcn_exp2f((float)v * kLog2eF); }
-
 template <int D>
 struct MbOps {
-  float x[MCH], y[D][MCH];
-  double pc[MCH];   // backward: p of the cell
+  float x[CH], y[D][CH];
+  double pc[CH];   // backward: p of the cell
   double cin;       // wave 0 of a strip above the first: lane q < CH holds the strip below's top row for step q
 };
 
 template <int D, bool BWD>
-__global__ void __launch_bounds__(64 * MBMAXW) mi_multiblank_kernel(
+__global__ void __launch_bounds__(64 * MAXW) mi_multiblank_kernel(
     const float* __restrict__ px, const float* __restrict__ py, const int32_t* __restrict__ boundary, const MbDur dur,
     double* __restrict__ p, double* __restrict__ ansd, double* __restrict__ carry, float* __restrict__ ans,
     const float* __restrict__ ans_grad, float* __restrict__ px_grad, float* __restrict__ py_grad, int S, int T, int NW,
     int DEP) {
   extern __shared__ double hist[];                    // [DEP][blockDim.x]: the lane's own values of the last DEP steps
-  __shared__ double ring[MBMAXW + 1][2][MCH];         // ring[w]: the row below wave w's lane 0, per step of a chunk
+  __shared__ double ring[MAXW + 1][2][CH];         // ring[w]: the row below wave w's lane 0, per step of a chunk
   __shared__ double sh_ans;
 
   const int b = blockIdx.x;
@@ -110,35 +86,24 @@ __global__ void __launch_bounds__(64 * MBMAXW) mi_multiblank_kernel(
   if (!BWD && tid == 0) sh_ans = __builtin_nan("");             // always overwritten: the loop covers (Sn-1, Tn-1)
   __syncthreads();
 
-  const int R = 64 * NW;                              // rows per strip
-  const int nst = (Sn + R - 1) / R;
+  const int nst = strips(Sn, NW);
   for (int j = 0; j < nst; ++j) {
-    const int rows = min(R, Sn - j * R);
-    const int nwact = (rows + 63) >> 6;
-    const int nk = Tn + 63 + MBE * (nwact - 1);
-    const int nch = (nk + MCH - 1) / MCH;
-    const bool active = w < nwact;
-    const int r = j * R + 64 * w + lane;              // relative row (backward: counted down from s_end)
-    const bool rowok = r < Sn;
-    const int skew = lane + MBE * w;                  // t = k - skew
-    const int s_act = BWD ? bd.se - r : bd.sb + r;
-    const double* carry_in = carry + ((size_t)b * 2 + ((j + 1) & 1)) * T1;   // written by strip j - 1
-    double* carry_out = carry + ((size_t)b * 2 + (j & 1)) * T1;
-    const bool want_cin = active && w == 0 && j > 0;
-    const bool give_carry = active && w == NW - 1 && j + 1 < nst;
+    const Strip<double> s(bd, j, NW, w, lane, b, carry, T1, BWD);
+    const int r = s.r, skew = s.skew, s_act = s.s_act;
+    const bool rowok = s.rowok, want_cin = s.want_cin, give_carry = s.give_carry;
 
     // every load is unconditional (a masked lane reads the workspace instead), so chunk c + 1's stay in flight while
     // chunk c computes; every unmasked index lies inside the boundary rectangle, which load_boundary clamps to the lattice
     auto load = [&](MbOps<D>& o, int c) {
       {
-        const int t = MCH * c + (lane & (MCH - 1));
+        const int t = CH * c + (lane & (CH - 1));
         const bool ok = want_cin && t < Tn;
-        o.cin = *(ok ? carry_in + t : p_b);
+        o.cin = *(ok ? s.carry_in + t : p_b);
         o.cin = ok ? o.cin : NEG;
       }
 #pragma unroll
-      for (int q = 0; q < MCH; ++q) {
-        const int t = MCH * c + q - skew;
+      for (int q = 0; q < CH; ++q) {
+        const int t = CH * c + q - skew;
         const bool valid = rowok && t >= 0 && t < Tn;
         const int t_act = BWD ? bd.te - t : bd.tb + t;
         const bool xok = valid && r >= 1;
@@ -156,13 +121,13 @@ __global__ void __launch_bounds__(64 * MBMAXW) mi_multiblank_kernel(
 
     double pv = NEG;
     auto chunk = [&](const MbOps<D>& o, int c) {
-      if (w == 0 && lane < MCH) ring[0][c & 1][lane] = o.cin;   // the strip below's top row (-inf for the first strip)
-      double up0[MCH];
+      if (w == 0 && lane < CH) ring[0][c & 1][lane] = o.cin;   // the strip below's top row (-inf for the first strip)
+      double up0[CH];
 #pragma unroll
-      for (int q = 0; q < MCH; ++q) up0[q] = (w > 0 && c == 0) ? NEG : ring[w][(w > 0 ? c - 1 : c) & 1][q];
+      for (int q = 0; q < CH; ++q) up0[q] = (w > 0 && c == 0) ? NEG : ring[w][(w > 0 ? c - 1 : c) & 1][q];
 #pragma unroll
-      for (int q = 0; q < MCH; ++q) {
-        const int k = MCH * c + q;
+      for (int q = 0; q < CH; ++q) {
+        const int k = CH * c + q;
         const int t = k - skew;
         const bool valid = rowok && t >= 0 && t < Tn;
         const int t_act = BWD ? bd.te - t : bd.tb + t;
@@ -181,7 +146,7 @@ __global__ void __launch_bounds__(64 * MBMAXW) mi_multiblank_kernel(
         float sum = exp_of(a - m);
 #pragma unroll
         for (int jj = 0; jj < D; ++jj) sum += exp_of(term[jj] - m);
-        double v = m + (double)(__builtin_amdgcn_logf(sum) * kLn2F);
+        double v = m + (double)(__builtin_amdgcn_logf(sum) * kLn2);
         if (m == NEG) v = plain;                      // all -inf (or a NaN among them, which the sum keeps)
         if (r == 0 && t == 0) v = 0.0;
         if (valid) {
@@ -203,23 +168,13 @@ __global__ void __launch_bounds__(64 * MBMAXW) mi_multiblank_kernel(
         pv = v;
         if (lane == 63) ring[w + 1][c & 1][q] = v;    // for wave w + 1 in the next chunk
       }
-      if (give_carry && lane < MCH) {
-        const int t = MCH * c + lane - 63 - MBE * w;
-        if (t >= 0 && t < Tn) carry_out[t] = ring[w + 1][c & 1][lane];
+      if (give_carry && lane < CH) {
+        const int t = CH * c + lane - 63 - E * w;
+        if (t >= 0 && t < Tn) s.carry_out[t] = ring[w + 1][c & 1][lane];
       }
     };
 
-    MbOps<D> A0, B0;
-    load(A0, 0);
-    for (int c = 0; c < nch; c += 2) {
-      load(B0, c + 1);
-      if (active) chunk(A0, c);
-      __syncthreads();
-      if (c + 1 >= nch) break;
-      load(A0, c + 2);
-      if (active) chunk(B0, c + 1);
-      __syncthreads();
-    }
+    run_chunks<MbOps<D>>(s.nch, s.active, load, chunk);
   }
   if (!BWD && tid == 0) {
     const double a = sh_ans;
@@ -233,18 +188,10 @@ int mb_launch(const float* px, const float* py, const int32_t* boundary, const i
               size_t ws_floats, float* ans, const float* ans_grad, float* px_grad, float* py_grad, int B, int S, int T,
               hipStream_t st) {
   const char* what = BWD ? "mutual_information_multiblank_bwd" : "mutual_information_multiblank_fwd";
-  if (B == 0) return FTR_OK;
-  const MbLayout L = mb_layout(B, S, T);
-  if (ws_floats < 2 * L.total) {
-    set_error("%s: workspace of %zu floats is too small, %zu needed", what, ws_floats, 2 * L.total);
-    return FTR_ERR_INVALID_ARG;
-  }
-  if ((size_t)(S + 1) * (size_t)(T + 1) >= (1ull << 31)) {
-    set_error("%s: one utterance's lattice (S=%d, T=%d) exceeds 2^31 cells", what, S, T);
-    return FTR_ERR_UNSUPPORTED;
-  }
+  int rc;
+  if (launch_done(what, B, S, T, ws_floats, f64_workspace_floats(B, S, T), "floats", &rc)) return rc;
   if (BWD) {   // the kernel writes the cells of the boundary rectangle only
-    int rc = zero_words(px_grad, (size_t)B * S * (T + 1), st, what);
+    rc = zero_words(px_grad, (size_t)B * S * (T + 1), st, what);
     if (rc != FTR_OK) return rc;
     rc = zero_words(py_grad, (size_t)B * D * (S + 1) * T, st, what);
     if (rc != FTR_OK) return rc;
@@ -252,26 +199,21 @@ int mb_launch(const float* px, const float* py, const int32_t* boundary, const i
   MbDur dur;
   for (int j = 0; j < MBMAXD; ++j) dur.d[j] = j < D ? durations[j] : 1;
   const int maxd = durations[D - 1];
-  const int DEP = mb_depth(maxd), NW = mb_waves(S, maxd);
+  const int DEP = mb_depth(maxd), NW = ring_waves_f64(S, DEP);
+  const F64Layout L = f64_layout(B, S, T);
   double* wsd = reinterpret_cast<double*>(ws);
   double *p = wsd + L.p_off, *ansd = wsd + L.ans_off, *carry = wsd + L.carry_off;
   const size_t lds = (size_t)DEP * 64 * NW * sizeof(double);
-#define FTR_MB_CASE(DV) case DV: hipLaunchKernelGGL((mi_multiblank_kernel<DV, BWD>), dim3(B), dim3(64 * NW), lds, st, px, py, \
-    boundary, dur, p, ansd, carry, ans, ans_grad, px_grad, py_grad, S, T, NW, DEP); break
-  switch (D) {
-    FTR_MB_CASE(1); FTR_MB_CASE(2); FTR_MB_CASE(3); FTR_MB_CASE(4);
-    FTR_MB_CASE(5); FTR_MB_CASE(6); FTR_MB_CASE(7); FTR_MB_CASE(8);
-  }
-#undef FTR_MB_CASE
+  dispatch_arity<1, MBMAXD>(D, [&](auto d) {
+    hipLaunchKernelGGL((mi_multiblank_kernel<decltype(d)::value, BWD>), dim3(B), dim3(64 * NW), lds, st, px, py, boundary,
+                       dur, p, ansd, carry, ans, ans_grad, px_grad, py_grad, S, T, NW, DEP);
+  });
   return check_launch(what);
 }
 
 }  // namespace
 
-size_t mi_multiblank_workspace_floats(int B, int S, int T) {
-  if (B < 0 || S < 0 || T < 0) return 0;
-  return 2 * mb_layout(B, S, T).total;
-}
+size_t mi_multiblank_workspace_floats(int B, int S, int T) { return rowlane::f64_workspace_floats(B, S, T); }
 
 int mi_multiblank_fwd(const float* px, const float* py, const int32_t* boundary, const int32_t* durations, int D, float* ws,
                       size_t ws_floats, float* ans, int B, int S, int T, hipStream_t st) {

@@ -10,72 +10,27 @@
 // outside the boundary rectangle absent, and q the same recursion run from (s_end,t_end) backwards.  token_durations =
 // (0,) is the multi-blank recursion of mi_multiblank.hip, and this file follows it: one kernel for both directions (the
 // backward pass is the forward pass in mirrored coordinates r = s_end - s, t = t_end - t with the operands read at the
-// cell itself), float64 p / q / ans with the bounded remainder of a logadd through the float32 exp2 / log2 units, one
-// workgroup per utterance, relative row r in wave (r / 64) % NW, lane r % 64 of strip r / (64 NW), wave w at step k on
-// column t = k - lane - E w with E = 64 + CH - 1, operands of chunk c + 1 loaded unconditionally while chunk c computes.
+// cell itself), float64 p / q / ans with the bounded remainder of a logadd through the float32 exp2 / log2 units, the
+// row-per-lane sweep of mi_rowlane.h.
 //
-// What differs is the symbol predecessor p[s-1,t-e]: the value of the row below at step k - 1 - e.  Every lane keeps
-// its last DEP values in an LDS ring hist[step & (DEP-1)][thread], so ALL moves are ring reads, of thread tid - ds
-// (ds = 1 for a symbol move, 0 for a blank) -- a single move list of M = Dx + Dy entries, the kernel templated on M.
-//   * lane >= 1: the lower lane of the same wave wrote step k - 1 - e earlier in program order (LDS is in order per wave).
-//   * lane 0 of wave w > 0: the row below is lane 63 of wave w - 1, i.e. thread tid - 1 all the same; with the skew E it
-//     handled column t - e at step k - CH - e.  Both waves run chunk c between the same two barriers, so that step lies
-//     in a chunk that is complete, and it is still in the ring while wave w - 1 writes up to step CH c + CH - 1 if
-//     DEP > 2 CH - 1 + e_max: DEP = 16 for e_max = 0, 32 otherwise (32 KB of ring: 4 waves at depth 16, 2 at depth 32).
-//   * lane 0 of wave 0 in a strip above the first: the strip below's top row is complete in `carry`; the CH + 16 values
-//     a chunk can ask for are loaded with the operands and staged in LDS.
-#include "ftr_common.h"
+// What differs is the symbol predecessor p[s-1,t-e]: the value of the row below at step k - 1 - e.  ALL moves are reads
+// of the history ring of mi_rowlane.h, of thread tid - ds (ds = 1 for a symbol move, 0 for a blank) -- a single move list
+// of M = Dx + Dy entries, the kernel templated on M.  The layout, the ring and why its depth is safe are stated there;
+// the depth is ring_depth(e_max): 16 for e_max = 0, 32 otherwise (32 KB of ring: 4 waves at depth 16, 2 at depth 32).
+#include "mi_rowlane.h"
 
 namespace ftr {
 namespace {
-
-constexpr int TCH = 8;                 // steps per chunk
-constexpr int TDE = 64 + TCH - 1;      // skew between consecutive waves
-constexpr int TMAXW = 4;               // waves per workgroup
-constexpr int TMAXM = 9;               // moves (Dx + Dy)
-constexpr int TMAXDUR = 16;            // largest duration
-constexpr int TCW = TCH + TMAXDUR;     // carry window of a chunk
-constexpr float kLog2eF = 1.4426950408889634f;
-constexpr float kLn2F = 0.6931471805599453f;
-
-// moves 0 .. Dx-1 are the symbol moves (px planes), Dx .. Dx+Dy-1 the blank moves (py planes)
-struct TdtMoves { int dur[TMAXM]; int Dx; };
-
-inline int tdt_depth(int emax) { return emax == 0 ? 16 : 32; }   // > 2 CH - 1 + e_max, and >= every duration
-inline int tdt_waves(int S, int emax) {
-  const int cap = tdt_depth(emax) > 16 ? TMAXW / 2 : TMAXW;      // 32 KB of ring either way
-  const int blocks = (S + 1 + 63) / 64;
-  return blocks < cap ? blocks : cap;
-}
-
-struct TdtLayout { size_t p_off, ans_off, carry_off, total; };   // in doubles
-inline TdtLayout tdt_layout(int B, int S, int T) {
-  TdtLayout L;
-  L.p_off = 0;
-  L.ans_off = (size_t)B * (S + 1) * (T + 1);
-  L.carry_off = L.ans_off + (size_t)B;
-  L.total = L.carry_off + (size_t)B * 2 * (T + 1);
-  return L;
-}
-
-// exp(v) for v a float64 log-quantity that is <= ~0 where it matters: the float32 exp2 unit
-__device__ __forceinline__ float exp_of(double v) { return __builtin_amdgcn_exp2f((float)v * kLog2eF); }
-
-template <int M>
-struct TdtOps {
-  float w[M][TCH];
-  double pc[TCH];   // backward: p of the cell
-  double cin;       // wave 0 of a strip above the first: lane l < TCW holds the strip below's top row at t = CH c - 16 + l
-};
+using namespace rowlane;
 
 template <int M, bool BWD>
-__global__ void __launch_bounds__(64 * TMAXW) mi_tdt_kernel(
-    const float* __restrict__ px, const float* __restrict__ py, const int32_t* __restrict__ boundary, const TdtMoves mv,
+__global__ void __launch_bounds__(64 * MAXW) mi_tdt_kernel(
+    const float* __restrict__ px, const float* __restrict__ py, const int32_t* __restrict__ boundary, const Moves mv,
     double* __restrict__ p, double* __restrict__ ansd, double* __restrict__ carry, float* __restrict__ ans,
     const float* __restrict__ ans_grad, float* __restrict__ px_grad, float* __restrict__ py_grad, int S, int T, int NW,
     int DEP) {
   extern __shared__ double hist[];                    // [DEP][blockDim.x]: every thread's values of the last DEP steps
-  __shared__ double cwin[TCW];                        // wave 0: the strip below's top row around this chunk
+  __shared__ double cwin[CW];                        // wave 0: the strip below's top row around this chunk
   __shared__ double sh_ans;
 
   const int b = blockIdx.x;
@@ -109,19 +64,20 @@ __global__ void __launch_bounds__(64 * TMAXW) mi_tdt_kernel(
   if (!BWD && tid == 0) sh_ans = __builtin_nan("");             // always overwritten: the loop covers (Sn-1, Tn-1)
   __syncthreads();
 
-  const int R = 64 * NW;                              // rows per strip
-  const int nst = (Sn + R - 1) / R;
+  const int nst = strips(Sn, NW);
   const int below = tid > 0 ? tid - 1 : 0;            // the thread that holds the row below
-  const int sback = lane == 0 ? TCH : 1;              // ... and how many steps ago it was on this column
+  const int sback = lane == 0 ? CH : 1;              // ... and how many steps ago it was on this column
   for (int j = 0; j < nst; ++j) {
+    // the geometry of Strip (mi_rowlane.h), written out: through the struct mi_tdt_kernel<3,true> gains a VGPR
+    const int R = 64 * NW;                              // rows per strip
     const int rows = min(R, Sn - j * R);
     const int nwact = (rows + 63) >> 6;
-    const int nk = Tn + 63 + TDE * (nwact - 1);
-    const int nch = (nk + TCH - 1) / TCH;
+    const int nk = Tn + 63 + E * (nwact - 1);
+    const int nch = (nk + CH - 1) / CH;
     const bool active = w < nwact;
     const int r = j * R + 64 * w + lane;              // relative row (backward: counted down from s_end)
     const bool rowok = r < Sn;
-    const int skew = lane + TDE * w;                  // t = k - skew
+    const int skew = lane + E * w;                    // t = k - skew
     const int s_act = BWD ? bd.se - r : bd.sb + r;
     const double* carry_in = carry + ((size_t)b * 2 + ((j + 1) & 1)) * T1;   // written by strip j - 1
     double* carry_out = carry + ((size_t)b * 2 + (j & 1)) * T1;
@@ -138,16 +94,16 @@ __global__ void __launch_bounds__(64 * TMAXW) mi_tdt_kernel(
 
     // every load is unconditional (a masked lane reads the workspace instead), so chunk c + 1's stay in flight while
     // chunk c computes; every unmasked index lies inside the boundary rectangle, which load_boundary clamps to the lattice
-    auto load = [&](TdtOps<M>& o, int c) {
+    auto load = [&](Ops<M, double>& o, int c) {
       {
-        const int t = TCH * c - TMAXDUR + lane;
-        const bool ok = want_cin && lane < TCW && t >= 0 && t < Tn;
+        const int t = CH * c - MAXTOK + lane;
+        const bool ok = want_cin && lane < CW && t >= 0 && t < Tn;
         o.cin = *(ok ? carry_in + t : p_b);
         o.cin = ok ? o.cin : NEG;
       }
 #pragma unroll
-      for (int q = 0; q < TCH; ++q) {
-        const int t = TCH * c + q - skew;
+      for (int q = 0; q < CH; ++q) {
+        const int t = CH * c + q - skew;
         const bool valid = rowok && t >= 0 && t < Tn;
 #pragma unroll
         for (int m = 0; m < M; ++m) {
@@ -158,14 +114,14 @@ __global__ void __launch_bounds__(64 * TMAXW) mi_tdt_kernel(
       }
     };
 
-    auto chunk = [&](const TdtOps<M>& o, int c) {
+    auto chunk = [&](const Ops<M, double>& o, int c) {
       if (want_cin) {
-        if (lane < TCW) cwin[lane] = o.cin;
+        if (lane < CW) cwin[lane] = o.cin;
         __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
       }
 #pragma unroll
-      for (int q = 0; q < TCH; ++q) {
-        const int k = TCH * c + q;
+      for (int q = 0; q < CH; ++q) {
+        const int k = CH * c + q;
         const int t = k - skew;
         const bool valid = rowok && t >= 0 && t < Tn;
         double src[M], term[M];
@@ -177,7 +133,7 @@ __global__ void __launch_bounds__(64 * TMAXW) mi_tdt_kernel(
           const bool ok = valid && t >= e && (!sym || r >= 1);
           src[m] = hist[(size_t)((k - e - (sym ? sback : 0)) & (DEP - 1)) * nthr + (sym ? below : tid)];
           if (want_cin && sym) {                      // uniform per wave; wave 0's lane 0 is on column t = k
-            const double cv = cwin[TMAXDUR + q - e];
+            const double cv = cwin[MAXTOK + q - e];
             src[m] = tid == 0 ? cv : src[m];
           }
           term[m] = ok ? src[m] + (double)o.w[m][q] : NEG;
@@ -187,7 +143,7 @@ __global__ void __launch_bounds__(64 * TMAXW) mi_tdt_kernel(
         float sum = 0.0f;
 #pragma unroll
         for (int m = 0; m < M; ++m) sum += exp_of(term[m] - m0);
-        double v = m0 + (double)(__builtin_amdgcn_logf(sum) * kLn2F);
+        double v = m0 + (double)(__builtin_amdgcn_logf(sum) * kLn2);
         if (m0 == NEG) v = plain;                     // all -inf (or a NaN among them, which the sum keeps)
         if (r == 0 && t == 0) v = 0.0;
         if (valid) {
@@ -214,17 +170,7 @@ __global__ void __launch_bounds__(64 * TMAXW) mi_tdt_kernel(
       }
     };
 
-    TdtOps<M> A0, B0;
-    load(A0, 0);
-    for (int c = 0; c < nch; c += 2) {
-      load(B0, c + 1);
-      if (active) chunk(A0, c);
-      __syncthreads();
-      if (c + 1 >= nch) break;
-      load(A0, c + 2);
-      if (active) chunk(B0, c + 1);
-      __syncthreads();
-    }
+    run_chunks<Ops<M, double>>(nch, active, load, chunk);
   }
   if (!BWD && tid == 0) {
     const double a = sh_ans;
@@ -238,47 +184,30 @@ int tdt_launch(const float* px, const float* py, const int32_t* boundary, const 
                const int32_t* blank_durations, int Dy, float* ws, size_t ws_floats, float* ans, const float* ans_grad,
                float* px_grad, float* py_grad, int B, int S, int T, hipStream_t st) {
   const char* what = BWD ? "mutual_information_tdt_bwd" : "mutual_information_tdt_fwd";
-  if (B == 0) return FTR_OK;
-  const TdtLayout L = tdt_layout(B, S, T);
-  if (ws_floats < 2 * L.total) {
-    set_error("%s: workspace of %zu floats is too small, %zu needed", what, ws_floats, 2 * L.total);
-    return FTR_ERR_INVALID_ARG;
-  }
-  if ((size_t)(S + 1) * (size_t)(T + 1) >= (1ull << 31)) {
-    set_error("%s: one utterance's lattice (S=%d, T=%d) exceeds 2^31 cells", what, S, T);
-    return FTR_ERR_UNSUPPORTED;
-  }
+  int rc;
+  if (launch_done(what, B, S, T, ws_floats, f64_workspace_floats(B, S, T), "floats", &rc)) return rc;
   if (BWD) {   // the kernel writes the moves that stay inside the boundary rectangle only
-    int rc = zero_words(px_grad, (size_t)B * Dx * S * (T + 1), st, what);
+    rc = zero_words(px_grad, (size_t)B * Dx * S * (T + 1), st, what);
     if (rc != FTR_OK) return rc;
     rc = zero_words(py_grad, (size_t)B * Dy * (S + 1) * T, st, what);
     if (rc != FTR_OK) return rc;
   }
-  const int M = Dx + Dy;
-  TdtMoves mv;
-  for (int m = 0; m < TMAXM; ++m) mv.dur[m] = m < Dx ? token_durations[m] : (m < M ? blank_durations[m - Dx] : 1);
-  mv.Dx = Dx;
-  const int emax = token_durations[Dx - 1];
-  const int DEP = tdt_depth(emax), NW = tdt_waves(S, emax);
+  const Moves mv = make_moves(token_durations, Dx, blank_durations, Dy);
+  const int DEP = ring_depth(token_durations[Dx - 1]), NW = ring_waves_f64(S, DEP);
+  const F64Layout L = f64_layout(B, S, T);
   double* wsd = reinterpret_cast<double*>(ws);
   double *p = wsd + L.p_off, *ansd = wsd + L.ans_off, *carry = wsd + L.carry_off;
   const size_t lds = (size_t)DEP * 64 * NW * sizeof(double);
-#define FTR_TDT_CASE(MV) case MV: hipLaunchKernelGGL((mi_tdt_kernel<MV, BWD>), dim3(B), dim3(64 * NW), lds, st, px, py, \
-    boundary, mv, p, ansd, carry, ans, ans_grad, px_grad, py_grad, S, T, NW, DEP); break
-  switch (M) {
-    FTR_TDT_CASE(2); FTR_TDT_CASE(3); FTR_TDT_CASE(4); FTR_TDT_CASE(5);
-    FTR_TDT_CASE(6); FTR_TDT_CASE(7); FTR_TDT_CASE(8); FTR_TDT_CASE(9);
-  }
-#undef FTR_TDT_CASE
+  dispatch_arity<2, MAXM>(Dx + Dy, [&](auto m) {
+    hipLaunchKernelGGL((mi_tdt_kernel<decltype(m)::value, BWD>), dim3(B), dim3(64 * NW), lds, st, px, py, boundary, mv, p,
+                       ansd, carry, ans, ans_grad, px_grad, py_grad, S, T, NW, DEP);
+  });
   return check_launch(what);
 }
 
 }  // namespace
 
-size_t mi_tdt_workspace_floats(int B, int S, int T) {
-  if (B < 0 || S < 0 || T < 0) return 0;
-  return 2 * tdt_layout(B, S, T).total;
-}
+size_t mi_tdt_workspace_floats(int B, int S, int T) { return rowlane::f64_workspace_floats(B, S, T); }
 
 int mi_tdt_fwd(const float* px, const float* py, const int32_t* boundary, const int32_t* token_durations, int Dx,
                const int32_t* blank_durations, int Dy, float* ws, size_t ws_floats, float* ans, int B, int S, int T,

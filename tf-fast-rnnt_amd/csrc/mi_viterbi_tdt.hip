@@ -13,21 +13,9 @@
 // is one add per move and ordered selects, so any dependency-respecting order gives the same bits; with (0,) / (1,) the
 // rule is mi_viterbi.hip's.
 //
-// Forward sweep: the layout of mi_tdt.hip.  One workgroup per utterance, relative row r in wave (r / 64) % NW, lane
-// r % 64 of strip r / (64 NW), wave w at step k on column t = k - lane - E w with E = 64 + CH - 1, chunks of CH steps
-// between barriers, operands of chunk c + 1 loaded unconditionally while chunk c computes, the top row of a strip carried
-// to the next strip through the workspace.  Every lane keeps its last DEP values in an LDS ring
-// hist[step & (DEP-1)][thread] and every predecessor is a ring read of thread tid - ds (ds = 1 token, 0 blank).  The chain
-// is float32, so DEP = 32 with four waves is the 32 KB that mi_tdt.hip spends on two.  DEP = 32 is enough for every
-// move list:
-//   * own lane, blank d: step k - d.  The thread reads before it writes step k, and the slot of step k - d is next
-//     written at step k - d + DEP >= k: DEP >= d_max = 32.
-//   * lane >= 1, token e: thread tid - 1 at step k - 1 - e, written earlier in program order by the same wave (LDS is in
-//     order per wave) and next overwritten at step k - 1 - e + DEP > k - 1: DEP > e_max = 16.
-//   * lane 0 of wave w > 0, token e: thread tid - 1 (lane 63 of wave w - 1) at step k - CH - e.  Both waves run chunk c
-//     between the same barriers, so that step lies in a complete chunk, and wave w - 1 writes at most step CH c + CH - 1
-//     meanwhile: DEP > 2 CH - 1 + e_max = 31.
-//   * lane 0 of wave 0 in a strip above the first: the strip below's top row, from `carry`, staged in LDS per chunk.
+// Forward sweep: the row-per-lane sweep and the history ring of mi_rowlane.h, as mi_tdt.hip, every predecessor a ring
+// read of thread tid - ds (ds = 1 token, 0 blank).  The chain is float32, so DEP = 32 with four waves is the 32 KB that
+// mi_tdt.hip spends on two, and 32 meets every depth requirement stated there for blanks up to 32 and tokens up to 16.
 //
 // Decisions: the move index has 4 bits; one ballot per bit plane per wave and step = four 64-bit words per (block of 64
 // rows, local step kl = t + lane), staged in LDS and stored once per chunk by 32 lanes (256 contiguous bytes).  Every
@@ -38,30 +26,23 @@
 // window in flight: a stride is at most 33) and walks it with readlane.  frames / durations are collected per block in
 // registers (lane = row) and stored 64 at a time; blank_steps is first set to 0 on [t_begin,t_end) by the whole
 // workgroup, then the walk overwrites the frames it leaves by a blank move.
-#include "ftr_common.h"
+#include "mi_rowlane.h"
 
 namespace ftr {
 namespace {
+using namespace rowlane;
 
-constexpr int QCH = 8;                 // steps per chunk
-constexpr int QE = 64 + QCH - 1;       // skew between consecutive waves
-constexpr int QMAXW = 4;               // waves per workgroup
-constexpr int QMAXM = 9;               // moves (Dx + Dy)
-constexpr int QMAXTOK = 16;            // largest token duration
 constexpr int QMAXBLK = 32;            // largest blank duration
-constexpr int QDEP = 32;               // ring depth: >= QMAXBLK and > 2 QCH - 1 + QMAXTOK (see above)
-constexpr int QCW = QCH + QMAXTOK;     // carry window of a chunk
+constexpr int QDEP = 32;               // ring depth
 typedef unsigned long long u64;
 
-static_assert(QDEP >= QMAXBLK && QDEP > 2 * QCH - 1 + QMAXTOK && (QDEP & (QDEP - 1)) == 0, "ring depth");
+static_assert(QDEP >= QMAXBLK && QDEP > MAXTOK && QDEP > 2 * CH - 1 + MAXTOK && (QDEP & (QDEP - 1)) == 0, "ring depth");
 static_assert(QMAXBLK + 1 <= 64, "a backtrace stride must stay inside the prefetched window");
-
-struct VtMoves { int dur[QMAXM]; int Dx; };
 
 __host__ __device__ inline int vt_blocks(int S) { return (S + 1 + 63) / 64; }
 // local steps kl = t + lane of a block: 0 .. T + 63, plus the tail of the last chunk that touches them
-__host__ __device__ inline size_t vt_steps_per_block(int T) { return (size_t)T + 1 + 63 + QCH; }
-inline int vt_waves(int S) { return vt_blocks(S) < QMAXW ? vt_blocks(S) : QMAXW; }
+__host__ __device__ inline size_t vt_steps_per_block(int T) { return (size_t)T + 1 + 63 + CH; }
+inline int vt_waves(int S) { return vt_blocks(S) < MAXW ? vt_blocks(S) : MAXW; }
 
 struct VtLayout { size_t dec_bytes, carry_off, total; };
 inline VtLayout vt_layout(int B, int S, int T) {
@@ -73,19 +54,13 @@ inline VtLayout vt_layout(int B, int S, int T) {
 }
 
 template <int M>
-struct VtOps {
-  float w[M][QCH];
-  float cin;   // wave 0 of a strip above the first: lane l < QCW holds the strip below's top row at t = CH c - 16 + l
-};
-
-template <int M>
-__global__ void __launch_bounds__(64 * QMAXW) mi_viterbi_tdt_kernel(
-    const float* __restrict__ px, const float* __restrict__ py, const int32_t* __restrict__ boundary, const VtMoves mv,
+__global__ void __launch_bounds__(64 * MAXW) mi_viterbi_tdt_kernel(
+    const float* __restrict__ px, const float* __restrict__ py, const int32_t* __restrict__ boundary, const Moves mv,
     u64* __restrict__ dec, float* __restrict__ carry, float* __restrict__ score, int32_t* __restrict__ frames,
     int32_t* __restrict__ durations, int32_t* __restrict__ blank_steps, int S, int T, int NW) {
   extern __shared__ float hist[];                     // [QDEP][blockDim.x]: every thread's values of the last QDEP steps
-  __shared__ float cwin[QCW];                         // wave 0: the strip below's top row around this chunk
-  __shared__ u64 words[QMAXW][QCH][4];                // the decision bit planes of the current chunk
+  __shared__ float cwin[CW];                         // wave 0: the strip below's top row around this chunk
+  __shared__ u64 words[MAXW][CH][4];                // the decision bit planes of the current chunk
   __shared__ float sh_score;
 
   const int b = blockIdx.x;
@@ -117,25 +92,14 @@ __global__ void __launch_bounds__(64 * QMAXW) mi_viterbi_tdt_kernel(
   if (tid == 0) sh_score = __builtin_nanf("");                    // always overwritten: the loop covers (Sn-1, Tn-1)
   __syncthreads();
 
-  const int R = 64 * NW;                              // rows per strip
-  const int nst = (Sn + R - 1) / R;
+  const int nst = strips(Sn, NW);
   const int below = tid > 0 ? tid - 1 : 0;            // the thread that holds the row below
-  const int sback = lane == 0 ? QCH : 1;              // ... and how many steps ago it was on this column
+  const int sback = lane == 0 ? CH : 1;              // ... and how many steps ago it was on this column
   for (int j = 0; j < nst; ++j) {
-    const int rows = min(R, Sn - j * R);
-    const int nwact = (rows + 63) >> 6;
-    const int nk = Tn + 63 + QE * (nwact - 1);
-    const int nch = (nk + QCH - 1) / QCH;
-    const bool active = w < nwact;
-    const int r = j * R + 64 * w + lane;              // relative row
-    const bool rowok = r < Sn;
-    const int skew = lane + QE * w;                   // t = k - skew
-    const int s_act = bd.sb + r;
+    const Strip<float> s(bd, j, NW, w, lane, b, carry, T1, false);
+    const int r = s.r, skew = s.skew, s_act = s.s_act;
+    const bool rowok = s.rowok, want_cin = s.want_cin, give_carry = s.give_carry && lane == 63;
     u64* dec_g = dec_b + (size_t)(j * NW + w) * KW * 4;
-    const float* carry_in = carry + ((size_t)b * 2 + ((j + 1) & 1)) * T1;   // written by strip j - 1
-    float* carry_out = carry + ((size_t)b * 2 + (j & 1)) * T1;
-    const bool want_cin = active && w == 0 && j > 0;
-    const bool give_carry = active && w == NW - 1 && lane == 63 && j + 1 < nst;
 
     // move m's operand at the predecessor of this lane's cell at relative column t
     auto operand = [&](int m, int t) -> const float* {
@@ -146,16 +110,16 @@ __global__ void __launch_bounds__(64 * QMAXW) mi_viterbi_tdt_kernel(
 
     // every load is unconditional (a masked lane reads the workspace instead), so chunk c + 1's stay in flight while
     // chunk c computes; every unmasked index lies inside the boundary rectangle, which load_boundary clamps to the lattice
-    auto load = [&](VtOps<M>& o, int c) {
+    auto load = [&](Ops<M, float>& o, int c) {
       {
-        const int t = QCH * c - QMAXTOK + lane;
-        const bool ok = want_cin && lane < QCW && t >= 0 && t < Tn;
-        o.cin = *(ok ? carry_in + t : safe_f);
+        const int t = CH * c - MAXTOK + lane;
+        const bool ok = want_cin && lane < CW && t >= 0 && t < Tn;
+        o.cin = *(ok ? s.carry_in + t : safe_f);
         o.cin = ok ? o.cin : NEG;
       }
 #pragma unroll
-      for (int q = 0; q < QCH; ++q) {
-        const int t = QCH * c + q - skew;
+      for (int q = 0; q < CH; ++q) {
+        const int t = CH * c + q - skew;
         const bool valid = rowok && t >= 0 && t < Tn;
 #pragma unroll
         for (int m = 0; m < M; ++m) {
@@ -165,14 +129,14 @@ __global__ void __launch_bounds__(64 * QMAXW) mi_viterbi_tdt_kernel(
       }
     };
 
-    auto chunk = [&](const VtOps<M>& o, int c) {
+    auto chunk = [&](const Ops<M, float>& o, int c) {
       if (want_cin) {
-        if (lane < QCW) cwin[lane] = o.cin;
+        if (lane < CW) cwin[lane] = o.cin;
         __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
       }
 #pragma unroll
-      for (int q = 0; q < QCH; ++q) {
-        const int k = QCH * c + q;
+      for (int q = 0; q < CH; ++q) {
+        const int k = CH * c + q;
         const int t = k - skew;
         const bool valid = rowok && t >= 0 && t < Tn;
         float cand[M];
@@ -183,7 +147,7 @@ __global__ void __launch_bounds__(64 * QMAXW) mi_viterbi_tdt_kernel(
           const bool ok = valid && t >= e && (!sym || r >= 1);
           float src = hist[(size_t)((k - e - (sym ? sback : 0)) & (QDEP - 1)) * nthr + (sym ? below : tid)];
           if (want_cin && sym) {                      // uniform per wave; wave 0's lane 0 is on column t = k
-            const float cv = cwin[QMAXTOK + q - e];
+            const float cv = cwin[MAXTOK + q - e];
             src = tid == 0 ? cv : src;
           }
           cand[m] = ok ? src + o.w[m][q] : NEG;
@@ -199,7 +163,7 @@ __global__ void __launch_bounds__(64 * QMAXW) mi_viterbi_tdt_kernel(
         if (r == 0 && t == 0) v = 0.0f;
         if (valid) {
           if (r == Sn - 1 && t == Tn - 1) sh_score = v;
-          if (give_carry) carry_out[t] = v;           // the strip's top row, for the strip above
+          if (give_carry) s.carry_out[t] = v;           // the strip's top row, for the strip above
         }
 #pragma unroll
         for (int pl = 0; pl < 4; ++pl) {
@@ -209,23 +173,13 @@ __global__ void __launch_bounds__(64 * QMAXW) mi_viterbi_tdt_kernel(
         hist[(size_t)(k & (QDEP - 1)) * nthr + tid] = v;
         __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");   // the upper lane reads it in a later step
       }
-      if (lane < 4 * QCH) {                           // the chunk's 32 words, contiguous in the workspace
-        const int kl = QCH * c - QE * w + (lane >> 2);
+      if (lane < 4 * CH) {                           // the chunk's 32 words, contiguous in the workspace
+        const int kl = CH * c - E * w + (lane >> 2);
         if (kl >= 0 && kl < (int)KW) dec_g[(size_t)kl * 4 + (lane & 3)] = words[w][lane >> 2][lane & 3];
       }
     };
 
-    VtOps<M> A0, B0;
-    load(A0, 0);
-    for (int c = 0; c < nch; c += 2) {
-      load(B0, c + 1);
-      if (active) chunk(A0, c);
-      __syncthreads();
-      if (c + 1 >= nch) break;
-      load(A0, c + 2);
-      if (active) chunk(B0, c + 1);
-      __syncthreads();
-    }
+    run_chunks<Ops<M, float>>(s.nch, s.active, load, chunk);
   }
 
   // ---- outputs outside the path: -1 outside the rectangle or without a path, blank_steps 0 inside
@@ -304,31 +258,18 @@ int mi_viterbi_tdt(const float* px, const float* py, const int32_t* boundary, co
                    const int32_t* blank_durations, int Dy, void* ws, size_t ws_bytes, float* score, int32_t* frames,
                    int32_t* durations, int32_t* blank_steps, int B, int S, int T, hipStream_t st) {
   const char* what = "mutual_information_viterbi_tdt";
-  if (B == 0) return FTR_OK;
   const VtLayout L = vt_layout(B, S, T);
-  if (ws_bytes < L.total) {
-    set_error("%s: workspace of %zu bytes is too small, %zu needed", what, ws_bytes, L.total);
-    return FTR_ERR_INVALID_ARG;
-  }
-  if ((size_t)(S + 1) * (size_t)(T + 1) >= (1ull << 31)) {
-    set_error("%s: one utterance's lattice (S=%d, T=%d) exceeds 2^31 cells", what, S, T);
-    return FTR_ERR_UNSUPPORTED;
-  }
-  const int M = Dx + Dy;
-  VtMoves mv;
-  for (int m = 0; m < QMAXM; ++m) mv.dur[m] = m < Dx ? token_durations[m] : (m < M ? blank_durations[m - Dx] : 1);
-  mv.Dx = Dx;
+  int rc;
+  if (launch_done(what, B, S, T, ws_bytes, L.total, "bytes", &rc)) return rc;
+  const Moves mv = make_moves(token_durations, Dx, blank_durations, Dy);
   const int NW = vt_waves(S);
   u64* dec = static_cast<u64*>(ws);
   float* carry = reinterpret_cast<float*>(static_cast<char*>(ws) + L.carry_off);
   const size_t lds = (size_t)QDEP * 64 * NW * sizeof(float);
-#define FTR_VT_CASE(MV) case MV: hipLaunchKernelGGL((mi_viterbi_tdt_kernel<MV>), dim3(B), dim3(64 * NW), lds, st, px, py, \
-    boundary, mv, dec, carry, score, frames, durations, blank_steps, S, T, NW); break
-  switch (M) {
-    FTR_VT_CASE(2); FTR_VT_CASE(3); FTR_VT_CASE(4); FTR_VT_CASE(5);
-    FTR_VT_CASE(6); FTR_VT_CASE(7); FTR_VT_CASE(8); FTR_VT_CASE(9);
-  }
-#undef FTR_VT_CASE
+  dispatch_arity<2, MAXM>(Dx + Dy, [&](auto m) {
+    hipLaunchKernelGGL((mi_viterbi_tdt_kernel<decltype(m)::value>), dim3(B), dim3(64 * NW), lds, st, px, py, boundary, mv,
+                       dec, carry, score, frames, durations, blank_steps, S, T, NW);
+  });
   return check_launch(what);
 }
 

@@ -172,16 +172,18 @@ def mi_forward_backward(px: torch.Tensor, py: torch.Tensor, boundary: Optional[t
     return (ans, px_grad, py_grad, ag) if return_ans_grad_check else (ans, px_grad, py_grad)
 
 
-class _MutualInformation(torch.autograd.Function):
-    """Op "FastRNNTLoss" + its registered gradient (__init__.py:154-162)."""
+class _Occupancies(torch.autograd.Function):
+    """Op "FastRNNTLoss" + its registered gradient (__init__.py:154-162), for every lattice: ``raw(px, py, need)`` is the
+    forward / backward pair on raw tensors, ``name`` the public function's."""
 
     @staticmethod
-    def forward(ctx, px, py, boundary, calc_gradients):
+    def forward(ctx, px, py, calc_gradients, name, raw):
         need = bool(calc_gradients) or px.requires_grad or py.requires_grad
-        ans, px_grad, py_grad = mi_forward_backward(px.detach(), py.detach(), boundary, need)
+        ans, px_grad, py_grad = raw(px.detach(), py.detach(), need)
         if need:
             ctx.save_for_backward(px_grad, py_grad)
         ctx.have_grads = need
+        ctx.name = name
         if px_grad is None:
             px_grad = torch.zeros_like(px)
             py_grad = torch.zeros_like(py)
@@ -192,12 +194,12 @@ class _MutualInformation(torch.autograd.Function):
     @staticmethod
     def backward(ctx, g_ans, _g1, _g2):
         if not ctx.have_grads:
-            raise RuntimeError("mutual_information_recursion: backward without saved occupancies")
-        px_grad, py_grad = ctx.saved_tensors
+            raise RuntimeError(f"{ctx.name}: backward without saved occupancies")
         if g_ans is None:
-            return None, None, None, None
-        g = g_ans.reshape(-1, 1, 1)            # _RNNTLossGrad: ans_grad * gradpx, ans_grad * gradpy
-        return g * px_grad, g * py_grad, None, None
+            return None, None, None, None, None
+        # _RNNTLossGrad: ans_grad * gradpx, ans_grad * gradpy, broadcast over each occupancy's own rank
+        gx, gy = (g_ans.reshape((-1,) + (1,) * (o.dim() - 1)) * o for o in ctx.saved_tensors)
+        return gx, gy, None, None, None
 
 
 def mutual_information_recursion(
@@ -214,7 +216,8 @@ def mutual_information_recursion(
     ``ans[b] = p[b,s_end,t_end]``; with ``calc_gradients`` also ``(px_grad, py_grad)``, the occupation
     probabilities (gradient of ``ans.sum()``).  Differentiable w.r.t. px and py.
     """
-    ans, px_grad, py_grad = _MutualInformation.apply(px, py, boundary, calc_gradients)
+    ans, px_grad, py_grad = _Occupancies.apply(px, py, calc_gradients, "mutual_information_recursion",
+                                               lambda x, y, need: mi_forward_backward(x, y, boundary, need))
     return (ans, (px_grad, py_grad)) if calc_gradients else ans
 
 
@@ -264,33 +267,6 @@ def mb_forward_backward(px: torch.Tensor, py: torch.Tensor, durations, boundary:
     return ans, px_grad, py_grad
 
 
-class _MutualInformationMultiblank(torch.autograd.Function):
-    """The multi-blank recursion and its gradient, as _MutualInformation."""
-
-    @staticmethod
-    def forward(ctx, px, py, durations, boundary, calc_gradients):
-        need = bool(calc_gradients) or px.requires_grad or py.requires_grad
-        ans, px_grad, py_grad = mb_forward_backward(px.detach(), py.detach(), durations, boundary, need)
-        if need:
-            ctx.save_for_backward(px_grad, py_grad)
-        ctx.have_grads = need
-        if px_grad is None:
-            px_grad = torch.zeros_like(px)
-            py_grad = torch.zeros_like(py)
-        ctx.mark_non_differentiable(px_grad, py_grad)
-        ctx.set_materialize_grads(False)
-        return ans, px_grad, py_grad
-
-    @staticmethod
-    def backward(ctx, g_ans, _g1, _g2):
-        if not ctx.have_grads:
-            raise RuntimeError("mutual_information_recursion_multiblank: backward without saved occupancies")
-        px_grad, py_grad = ctx.saved_tensors
-        if g_ans is None:
-            return None, None, None, None, None
-        return g_ans.reshape(-1, 1, 1) * px_grad, g_ans.reshape(-1, 1, 1, 1) * py_grad, None, None, None
-
-
 def mutual_information_recursion_multiblank(
     px: torch.Tensor,
     py: torch.Tensor,
@@ -311,7 +287,9 @@ def mutual_information_recursion_multiblank(
     ``(px_grad, py_grad)``, the occupancies, in the shapes of px and py and zero outside the rectangle.  With
     ``durations=(1,)`` and ``py[:,None]`` this is the lattice of ``mutual_information_recursion``.  Differentiable
     w.r.t. px and py; asynchronous on torch's current stream, no host read (capturable)."""
-    ans, px_grad, py_grad = _MutualInformationMultiblank.apply(px, py, tuple(durations), boundary, calc_gradients)
+    durations = tuple(durations)
+    ans, px_grad, py_grad = _Occupancies.apply(px, py, calc_gradients, "mutual_information_recursion_multiblank",
+                                               lambda x, y, need: mb_forward_backward(x, y, durations, boundary, need))
     return (ans, (px_grad, py_grad)) if calc_gradients else ans
 
 
@@ -328,15 +306,14 @@ def _check_tdt_moves(token_durations, blank_durations, blank_hi: int = 16) -> Tu
     return tok, blk
 
 
-def tdt_forward_backward(px: torch.Tensor, py: torch.Tensor, token_durations, blank_durations,
-                         boundary: Optional[torch.Tensor], need_grads: bool):
-    """The TDT recursion on raw tensors (no autograd): forward and, when wanted, the backward seeded with ones, back to
-    back on torch's current stream.  Returns (ans, px_grad|None, py_grad|None)."""
+def _duration_lattice_inputs(px: torch.Tensor, py: torch.Tensor, token_durations, blank_durations, blank_hi: int):
+    """Validation of the TDT-shaped entries and the host arrays the launches read.  Returns
+    (px, py, B, S, T, tok, blk, tok_arr, blk_arr) with px and py contiguous."""
     import ctypes
     _require_gpu(px, "px"); _require_gpu(py, "py")
     if px.dtype != torch.float32 or py.dtype != torch.float32:
         raise TypeError("px and py must be float32")
-    tok, blk = _check_tdt_moves(token_durations, blank_durations)
+    tok, blk = _check_tdt_moves(token_durations, blank_durations, blank_hi)
     Dx, Dy = len(tok), len(blk)
     if px.dim() != 4 or py.dim() != 4:
         raise ValueError("px must be [B,Dx,S,T+1] and py [B,Dy,S+1,T]")
@@ -348,10 +325,18 @@ def tdt_forward_backward(px: torch.Tensor, py: torch.Tensor, token_durations, bl
         raise ValueError(f"px must have shape {(B, Dx, S, T + 1)}, got {tuple(px.shape)}")
     if tuple(py.shape) != (B, Dy, S + 1, T):
         raise ValueError(f"py must have shape {(B, Dy, S + 1, T)}, got {tuple(py.shape)}")
-    px = px.contiguous(); py = py.contiguous()
-    boundary = _as_boundary(boundary, B, px.device)
     tok_arr = (ctypes.c_int32 * Dx)(*tok)       # read by the launch itself: no device copy, no host synchronisation
     blk_arr = (ctypes.c_int32 * Dy)(*blk)
+    return px.contiguous(), py.contiguous(), B, S, T, tok, blk, tok_arr, blk_arr
+
+
+def tdt_forward_backward(px: torch.Tensor, py: torch.Tensor, token_durations, blank_durations,
+                         boundary: Optional[torch.Tensor], need_grads: bool):
+    """The TDT recursion on raw tensors (no autograd): forward and, when wanted, the backward seeded with ones, back to
+    back on torch's current stream.  Returns (ans, px_grad|None, py_grad|None)."""
+    px, py, B, S, T, tok, blk, tok_arr, blk_arr = _duration_lattice_inputs(px, py, token_durations, blank_durations, 16)
+    Dx, Dy = len(tok), len(blk)
+    boundary = _as_boundary(boundary, B, px.device)
     L = _lib.lib()
     with torch.cuda.device(px.device):
         st = _stream_ptr(px)
@@ -367,34 +352,6 @@ def tdt_forward_backward(px: torch.Tensor, py: torch.Tensor, token_durations, bl
         _lib.call("ftr_mutual_information_tdt_bwd_f32", _ptr(px), _ptr(py), _ptr(boundary), tok_arr, Dx, blk_arr, Dy,
                   _ptr(ws), nws, None, _ptr(px_grad), _ptr(py_grad), B, S, T, st)
     return ans, px_grad, py_grad
-
-
-class _MutualInformationTdt(torch.autograd.Function):
-    """The TDT recursion and its gradient, as _MutualInformationMultiblank."""
-
-    @staticmethod
-    def forward(ctx, px, py, token_durations, blank_durations, boundary, calc_gradients):
-        need = bool(calc_gradients) or px.requires_grad or py.requires_grad
-        ans, px_grad, py_grad = tdt_forward_backward(px.detach(), py.detach(), token_durations, blank_durations, boundary, need)
-        if need:
-            ctx.save_for_backward(px_grad, py_grad)
-        ctx.have_grads = need
-        if px_grad is None:
-            px_grad = torch.zeros_like(px)
-            py_grad = torch.zeros_like(py)
-        ctx.mark_non_differentiable(px_grad, py_grad)
-        ctx.set_materialize_grads(False)
-        return ans, px_grad, py_grad
-
-    @staticmethod
-    def backward(ctx, g_ans, _g1, _g2):
-        if not ctx.have_grads:
-            raise RuntimeError("mutual_information_recursion_tdt: backward without saved occupancies")
-        px_grad, py_grad = ctx.saved_tensors
-        if g_ans is None:
-            return None, None, None, None, None, None
-        g = g_ans.reshape(-1, 1, 1, 1)
-        return g * px_grad, g * py_grad, None, None, None, None
 
 
 def mutual_information_recursion_tdt(
@@ -422,8 +379,9 @@ def mutual_information_recursion_tdt(
     the rectangle.  With ``token_durations=(0,)`` this is ``mutual_information_recursion_multiblank``, with ``(0,)`` and
     ``(1,)`` the lattice of ``mutual_information_recursion``.  Differentiable w.r.t. px and py; asynchronous on torch's
     current stream, no host read (capturable)."""
-    ans, px_grad, py_grad = _MutualInformationTdt.apply(px, py, tuple(token_durations), tuple(blank_durations), boundary,
-                                                        calc_gradients)
+    tok, blk = tuple(token_durations), tuple(blank_durations)
+    ans, px_grad, py_grad = _Occupancies.apply(px, py, calc_gradients, "mutual_information_recursion_tdt",
+                                               lambda x, y, need: tdt_forward_backward(x, y, tok, blk, boundary, need))
     return (ans, (px_grad, py_grad)) if calc_gradients else ans
 
 
@@ -512,26 +470,10 @@ def mutual_information_viterbi_tdt(px: torch.Tensor, py: torch.Tensor, token_dur
     ``blank_steps``, all three are entirely -1 for an utterance whose score is -inf (no path) or NaN, and an inverted
     rectangle gives score 0 and -1 everywhere.  Not differentiable: the outputs are detached.  Asynchronous on torch's
     current stream, no host read (capturable)."""
-    import ctypes
-    _require_gpu(px, "px"); _require_gpu(py, "py")
-    if px.dtype != torch.float32 or py.dtype != torch.float32:
-        raise TypeError("px and py must be float32")
-    tok, blk = _check_tdt_moves(token_durations, blank_durations, blank_hi=32)   # a blank above 16: this entry alone
+    px, py, B, S, T, tok, blk, tok_arr, blk_arr = _duration_lattice_inputs(px.detach(), py.detach(), token_durations,
+                                                                           blank_durations, 32)   # a blank above 16: this entry alone
     Dx, Dy = len(tok), len(blk)
-    if px.dim() != 4 or py.dim() != 4:
-        raise ValueError("px must be [B,Dx,S,T+1] and py [B,Dy,S+1,T]")
-    B, _, S, T1 = px.shape
-    T = py.shape[3]
-    if T1 != T + 1:
-        raise ValueError(f"px.shape[-1]={T1} must be T+1 with T=py.shape[-1]={T} (regular type only)")
-    if tuple(px.shape) != (B, Dx, S, T + 1):
-        raise ValueError(f"px must have shape {(B, Dx, S, T + 1)}, got {tuple(px.shape)}")
-    if tuple(py.shape) != (B, Dy, S + 1, T):
-        raise ValueError(f"py must have shape {(B, Dy, S + 1, T)}, got {tuple(py.shape)}")
-    px = px.detach().contiguous(); py = py.detach().contiguous()
     boundary = _as_boundary(boundary, B, px.device)
-    tok_arr = (ctypes.c_int32 * Dx)(*tok)       # read by the launch itself: no device copy, no host synchronisation
-    blk_arr = (ctypes.c_int32 * Dy)(*blk)
     L = _lib.lib()
     with torch.cuda.device(px.device):
         nbytes = L.ftr_mutual_information_viterbi_tdt_workspace_bytes(B, S, T)
