@@ -122,12 +122,8 @@ def check_workspace_status() -> int:
     return bad
 
 
-def mi_forward_backward(px: torch.Tensor, py: torch.Tensor, boundary: Optional[torch.Tensor],
-                        need_grads: bool, ans_grad: Optional[torch.Tensor] = None,
-                        return_ans_grad_check: bool = False, ans_grad_is_one: bool = False, loss_code: Optional[int] = None):
-    """FastRNNTOpBase::Compute on raw tensors (no autograd).  Returns (ans, px_grad|None, py_grad|None[, check]).
-    ``loss_code`` (0 none / 1 mean / 2 sum, with ``ans_grad_is_one`` and ``need_grads``): the backward launch also writes the
-    negated / reduced loss (ftr_mutual_information_bwd_loss_ws_f32) and it is returned as a fourth element."""
+def _lattice_inputs(px: torch.Tensor, py: torch.Tensor):
+    """Validation of the ordinary lattice's entries.  Returns (px, py, B, S, T, modified) with px and py contiguous."""
     _require_gpu(px, "px"); _require_gpu(py, "py")
     if px.dtype != torch.float32 or py.dtype != torch.float32:
         raise TypeError("px and py must be float32 (op registration: tf_fast_rnnt_op.cc:27-34)")
@@ -140,7 +136,16 @@ def mi_forward_backward(px: torch.Tensor, py: torch.Tensor, boundary: Optional[t
     if tuple(py.shape) != (B, S + 1, T):
         raise ValueError(f"py must have shape {(B, S + 1, T)}, got {tuple(py.shape)}")
     modified = int(T1 == T)
-    px = px.contiguous(); py = py.contiguous()
+    return px.contiguous(), py.contiguous(), B, S, T, modified
+
+
+def mi_forward_backward(px: torch.Tensor, py: torch.Tensor, boundary: Optional[torch.Tensor],
+                        need_grads: bool, ans_grad: Optional[torch.Tensor] = None,
+                        return_ans_grad_check: bool = False, ans_grad_is_one: bool = False, loss_code: Optional[int] = None):
+    """FastRNNTOpBase::Compute on raw tensors (no autograd).  Returns (ans, px_grad|None, py_grad|None[, check]).
+    ``loss_code`` (0 none / 1 mean / 2 sum, with ``ans_grad_is_one`` and ``need_grads``): the backward launch also writes the
+    negated / reduced loss (ftr_mutual_information_bwd_loss_ws_f32) and it is returned as a fourth element."""
+    px, py, B, S, T, modified = _lattice_inputs(px, py)
     boundary = _as_boundary(boundary, B, px.device)
     L = _lib.lib()
     with torch.cuda.device(px.device):
@@ -410,19 +415,7 @@ def mutual_information_viterbi(px: torch.Tensor, py: torch.Tensor,
 
     Not differentiable: both outputs are detached.  Asynchronous on torch's current stream, no host read (capturable).
     """
-    _require_gpu(px, "px"); _require_gpu(py, "py")
-    if px.dtype != torch.float32 or py.dtype != torch.float32:
-        raise TypeError("px and py must be float32 (op registration: tf_fast_rnnt_op.cc:27-34)")
-    if px.dim() != 3 or py.dim() != 3:
-        raise ValueError("px and py must be 3-dimensional")
-    B, S, T1 = px.shape
-    T = py.shape[2]
-    if T1 not in (T, T + 1):
-        raise ValueError(f"px.shape[-1]={T1} must be T or T+1 with T=py.shape[-1]={T}")
-    if tuple(py.shape) != (B, S + 1, T):
-        raise ValueError(f"py must have shape {(B, S + 1, T)}, got {tuple(py.shape)}")
-    modified = int(T1 == T)
-    px = px.detach().contiguous(); py = py.detach().contiguous()
+    px, py, B, S, T, modified = _lattice_inputs(px.detach(), py.detach())
     boundary = _as_boundary(boundary, B, px.device)
     L = _lib.lib()
     with torch.cuda.device(px.device):

@@ -24,7 +24,9 @@ from __future__ import annotations
 
 from typing import Optional, Tuple, Union
 
+import ctypes
 import os
+
 import torch
 
 from . import _lib
@@ -57,7 +59,6 @@ def normalizer_gemm_choice(kind: int, B: int, T: int, S: int, C: int):
     """What the library chose for the GEMM ``kind`` (0 forward product, 1 towards lm, 2 towards am) of this shape on the
     current device: None if the shape has not run, else dict(solution, us, us_default, candidates) -- solution 0 is
     rocBLAS' own choice, candidates -1 means not measured yet."""
-    import ctypes
     sol, cand = ctypes.c_int(0), ctypes.c_int(0)
     us, usd = ctypes.c_float(0), ctypes.c_float(0)
     if not _lib.lib().ftr_normalizer_gemm_choice(int(kind), int(B), int(T), int(S) + 1, int(C), ctypes.byref(sol), ctypes.byref(us),
@@ -132,62 +133,73 @@ def _simple_builder(amc, lmc, symbols, am_probs, lm_probs, am_max, lm_max, bound
     return prod
 
 
+def _simple_forward(lm, am, symbols, termination_symbol, boundary, modified, delay_penalty):
+    """Forward of the simple builder (rnnt_loss.py:175-221).  Returns px, py and what the backward needs."""
+    B, T, C = am.shape
+    S = lm.shape[1] - 1
+    T1 = T if modified else T + 1
+    amc = am.detach().contiguous(); lmc = lm.detach().contiguous()
+    dev = amc.device
+    am_probs = torch.empty_like(amc); lm_probs = torch.empty_like(lmc)
+    am_max = torch.empty((B, T), dtype=torch.float32, device=dev)
+    lm_max = torch.empty((B, S + 1), dtype=torch.float32, device=dev)
+    px = torch.empty((B, S, T1), dtype=torch.float32, device=dev)
+    py = torch.empty((B, S + 1, T), dtype=torch.float32, device=dev)
+    with torch.cuda.device(dev):
+        st = _stream_ptr(amc)
+        _lib.call("ftr_rowmax_exp_pair_f32", _ptr(amc), _ptr(am_probs), _ptr(am_max), B * T,              # :175-178
+                  _ptr(lmc), _ptr(lm_probs), _ptr(lm_max), B * (S + 1), C, st)
+        prod = _simple_builder(amc, lmc, symbols, am_probs, lm_probs, am_max, lm_max, boundary, termination_symbol,
+                               delay_penalty, px, py, B, T, S, C, modified, st)
+    return px, py, (am_probs, lm_probs, prod, symbols, boundary), (int(termination_symbol), int(modified))
+
+
+def _simple_backward(saved, meta, gpx, gpy, scale=None, stride=0, mul=1.0):
+    """Hand-written backward of the simple builder; gpx / gpy are d/d px, d/d py, multiplied on the fly by
+    (scale ? scale[b * stride] : 1) * mul (the upstream gradient of the loss that owns the occupancies)."""
+    am_probs, lm_probs, prod, symbols, boundary = saved
+    blank, modified = meta
+    B, T, C = am_probs.shape
+    S = lm_probs.shape[1] - 1
+    dev = am_probs.device
+    gpx = gpx.contiguous(); gpy = gpy.contiguous()
+    W = torch.empty_like(prod)
+    rsx = torch.empty((B, S + 1), dtype=torch.float32, device=dev)
+    rsy = torch.empty((B, S + 1), dtype=torch.float32, device=dev)
+    d_am = torch.empty_like(am_probs); d_lm = torch.empty_like(lm_probs)
+    with torch.cuda.device(dev):
+        st = _stream_ptr(am_probs)
+        _lib.call("ftr_simple_logprobs_bwd_w_scaled_f32", _ptr(gpx), _ptr(gpy), _ptr(scale), stride, mul,
+                  _ptr(prod), _ptr(boundary), _ptr(W), _ptr(rsx), _ptr(rsy), B, T, S, modified, st)
+        dlmp = _gemm(1, W, am_probs, B, T, S, C, st)         # [B,S+1,C]
+        if _use_fused_builder_bwd(T, C):                       # W^T lm_probs inside the d am kernel (opt-in)
+            _lib.call("ftr_simple_logprobs_fused_bwd_am_f32", _ptr(gpx), _ptr(gpy), _ptr(scale), stride, mul,
+                      _ptr(prod), _ptr(lm_probs), _ptr(am_probs), _ptr(symbols), _ptr(boundary), blank, _ptr(d_am),
+                      B, T, S, C, modified, st)
+        else:
+            damp = _gemm(2, W, lm_probs, B, T, S, C, st)    # [B,T,C]
+            _lib.call("ftr_simple_logprobs_bwd_am_scaled_f32", _ptr(gpx), _ptr(gpy), _ptr(scale), stride, mul,
+                      _ptr(damp), _ptr(am_probs), _ptr(symbols), _ptr(boundary), blank, _ptr(d_am), B, T, S, C,
+                      modified, st)
+        _lib.call("ftr_simple_logprobs_bwd_lm_f32", _ptr(dlmp), _ptr(lm_probs), _ptr(symbols), _ptr(rsx), _ptr(rsy),
+                  blank, _ptr(d_lm), B, S, C, st)
+    return d_lm, d_am
+
+
 class _SimpleLogprobs(torch.autograd.Function):
     """get_rnnt_logprobs (+ fix_for_boundary + delay penalty) for regular/modified: native prologue and
     epilogue kernels around the normaliser GEMM (ftr_normalizer_gemm_f32 -> rocBLAS), hand-written backward."""
 
     @staticmethod
     def forward(ctx, lm, am, symbols, termination_symbol, boundary, modified, delay_penalty):
-        B, T, C = am.shape
-        S = lm.shape[1] - 1
-        T1 = T if modified else T + 1
-        amc = am.detach().contiguous(); lmc = lm.detach().contiguous()
-        dev = amc.device
-        am_probs = torch.empty_like(amc); lm_probs = torch.empty_like(lmc)
-        am_max = torch.empty((B, T), dtype=torch.float32, device=dev)
-        lm_max = torch.empty((B, S + 1), dtype=torch.float32, device=dev)
-        px = torch.empty((B, S, T1), dtype=torch.float32, device=dev)
-        py = torch.empty((B, S + 1, T), dtype=torch.float32, device=dev)
-        with torch.cuda.device(dev):
-            st = _stream_ptr(amc)
-            _lib.call("ftr_rowmax_exp_pair_f32", _ptr(amc), _ptr(am_probs), _ptr(am_max), B * T,              # :175-178
-                      _ptr(lmc), _ptr(lm_probs), _ptr(lm_max), B * (S + 1), C, st)
-            prod = _simple_builder(amc, lmc, symbols, am_probs, lm_probs, am_max, lm_max, boundary, termination_symbol,
-                                   delay_penalty, px, py, B, T, S, C, modified, st)
-        ctx.save_for_backward(am_probs, lm_probs, prod, symbols, boundary if boundary is not None else torch.empty(0))
-        ctx.has_boundary = boundary is not None
-        ctx.meta = (int(termination_symbol), int(modified))
+        px, py, saved, meta = _simple_forward(lm, am, symbols, termination_symbol, boundary, modified, delay_penalty)
+        ctx.save_for_backward(*saved)
+        ctx.meta = meta
         return px, py
 
     @staticmethod
     def backward(ctx, gpx, gpy):
-        am_probs, lm_probs, prod, symbols, boundary = ctx.saved_tensors
-        if not ctx.has_boundary:
-            boundary = None
-        blank, modified = ctx.meta
-        B, T, C = am_probs.shape
-        S = lm_probs.shape[1] - 1
-        dev = am_probs.device
-        gpx = gpx.contiguous(); gpy = gpy.contiguous()
-        W = torch.empty_like(prod)
-        rsx = torch.empty((B, S + 1), dtype=torch.float32, device=dev)
-        rsy = torch.empty((B, S + 1), dtype=torch.float32, device=dev)
-        d_am = torch.empty_like(am_probs); d_lm = torch.empty_like(lm_probs)
-        with torch.cuda.device(dev):
-            st = _stream_ptr(am_probs)
-            _lib.call("ftr_simple_logprobs_bwd_w_f32", _ptr(gpx), _ptr(gpy), _ptr(prod), _ptr(boundary), _ptr(W),
-                      _ptr(rsx), _ptr(rsy), B, T, S, modified, st)
-            dlmp = _gemm(1, W, am_probs, B, T, S, C, st)         # [B,S+1,C]
-            if _use_fused_builder_bwd(T, C):                       # W^T lm_probs inside the d am kernel (opt-in)
-                _lib.call("ftr_simple_logprobs_fused_bwd_am_f32", _ptr(gpx), _ptr(gpy), None, 0, 1.0, _ptr(prod),
-                          _ptr(lm_probs), _ptr(am_probs), _ptr(symbols), _ptr(boundary), blank, _ptr(d_am), B, T, S, C,
-                          modified, st)
-            else:
-                damp = _gemm(2, W, lm_probs, B, T, S, C, st)    # [B,T,C]
-                _lib.call("ftr_simple_logprobs_bwd_am_f32", _ptr(gpx), _ptr(gpy), _ptr(damp), _ptr(am_probs),
-                          _ptr(symbols), _ptr(boundary), blank, _ptr(d_am), B, T, S, C, modified, st)
-            _lib.call("ftr_simple_logprobs_bwd_lm_f32", _ptr(dlmp), _ptr(lm_probs), _ptr(symbols), _ptr(rsx), _ptr(rsy),
-                      blank, _ptr(d_lm), B, S, C, st)
+        d_lm, d_am = _simple_backward(ctx.saved_tensors, ctx.meta, gpx, gpy)
         return d_lm, d_am, None, None, None, None, None
 
 
@@ -198,22 +210,7 @@ class _SimpleLoss(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, lm, am, symbols, termination_symbol, boundary, modified, delay_penalty, code, want_occupancies):
-        B, T, C = am.shape
-        S = lm.shape[1] - 1
-        T1 = T if modified else T + 1
-        amc = am.detach().contiguous(); lmc = lm.detach().contiguous()
-        dev = amc.device
-        am_probs = torch.empty_like(amc); lm_probs = torch.empty_like(lmc)
-        am_max = torch.empty((B, T), dtype=torch.float32, device=dev)
-        lm_max = torch.empty((B, S + 1), dtype=torch.float32, device=dev)
-        px = torch.empty((B, S, T1), dtype=torch.float32, device=dev)
-        py = torch.empty((B, S + 1, T), dtype=torch.float32, device=dev)
-        with torch.cuda.device(dev):
-            st = _stream_ptr(amc)
-            _lib.call("ftr_rowmax_exp_pair_f32", _ptr(amc), _ptr(am_probs), _ptr(am_max), B * T,              # :175-178
-                      _ptr(lmc), _ptr(lm_probs), _ptr(lm_max), B * (S + 1), C, st)
-            prod = _simple_builder(amc, lmc, symbols, am_probs, lm_probs, am_max, lm_max, boundary, termination_symbol,
-                                   delay_penalty, px, py, B, T, S, C, modified, st)
+        px, py, saved, meta = _simple_forward(lm, am, symbols, termination_symbol, boundary, modified, delay_penalty)
         # the recursion backward (occupancies) only when somebody wants them: the caller (calc_gradients) or autograd
         need = bool(want_occupancies) or ctx.needs_input_grad[0] or ctx.needs_input_grad[1]
         if need:      # the loss tail rides along with the recursion's backward launch
@@ -221,15 +218,15 @@ class _SimpleLoss(torch.autograd.Function):
         else:
             ans, px_grad, py_grad = mi_forward_backward(px, py, boundary, False, ans_grad_is_one=True)
             loss = _negated_reduce_native(ans, code)
+        shape_x, shape_y = px.shape, py.shape
         del px, py
         if need:
-            ctx.save_for_backward(am_probs, lm_probs, prod, symbols, boundary if boundary is not None else torch.empty(0),
-                                  px_grad, py_grad)
+            ctx.save_for_backward(*saved, px_grad, py_grad)
         else:
-            px_grad = torch.zeros((B, S, T1), dtype=torch.float32, device=dev)
-            py_grad = torch.zeros((B, S + 1, T), dtype=torch.float32, device=dev)
-        ctx.has_boundary = boundary is not None
-        ctx.meta = (int(termination_symbol), int(modified), int(code))
+            px_grad = torch.zeros(shape_x, dtype=torch.float32, device=loss.device)
+            py_grad = torch.zeros(shape_y, dtype=torch.float32, device=loss.device)
+        ctx.meta = meta
+        ctx.code = int(code)
         ctx.mark_non_differentiable(px_grad, py_grad)
         ctx.set_materialize_grads(False)          # no zero tensors for the two occupancy outputs in backward
         return loss, px_grad, py_grad
@@ -238,34 +235,9 @@ class _SimpleLoss(torch.autograd.Function):
     def backward(ctx, g_loss, _g1, _g2):
         if g_loss is None:
             return (None,) * 9
-        am_probs, lm_probs, prod, symbols, boundary, px_grad, py_grad = ctx.saved_tensors
-        if not ctx.has_boundary:
-            boundary = None
-        blank, modified, code = ctx.meta
-        B, T, C = am_probs.shape
-        S = lm_probs.shape[1] - 1
-        dev = am_probs.device
-        scale, stride, mul = _upstream_scale(g_loss, code, B)
-        W = torch.empty_like(prod)
-        rsx = torch.empty((B, S + 1), dtype=torch.float32, device=dev)
-        rsy = torch.empty((B, S + 1), dtype=torch.float32, device=dev)
-        d_am = torch.empty_like(am_probs); d_lm = torch.empty_like(lm_probs)
-        with torch.cuda.device(dev):
-            st = _stream_ptr(am_probs)
-            _lib.call("ftr_simple_logprobs_bwd_w_scaled_f32", _ptr(px_grad), _ptr(py_grad), _ptr(scale), stride, mul,
-                      _ptr(prod), _ptr(boundary), _ptr(W), _ptr(rsx), _ptr(rsy), B, T, S, modified, st)
-            dlmp = _gemm(1, W, am_probs, B, T, S, C, st)         # [B,S+1,C]
-            if _use_fused_builder_bwd(T, C):                       # W^T lm_probs inside the d am kernel (opt-in)
-                _lib.call("ftr_simple_logprobs_fused_bwd_am_f32", _ptr(px_grad), _ptr(py_grad), _ptr(scale), stride, mul,
-                          _ptr(prod), _ptr(lm_probs), _ptr(am_probs), _ptr(symbols), _ptr(boundary), blank, _ptr(d_am),
-                          B, T, S, C, modified, st)
-            else:
-                damp = _gemm(2, W, lm_probs, B, T, S, C, st)    # [B,T,C]
-                _lib.call("ftr_simple_logprobs_bwd_am_scaled_f32", _ptr(px_grad), _ptr(py_grad), _ptr(scale), stride, mul,
-                          _ptr(damp), _ptr(am_probs), _ptr(symbols), _ptr(boundary), blank, _ptr(d_am), B, T, S, C,
-                          modified, st)
-            _lib.call("ftr_simple_logprobs_bwd_lm_f32", _ptr(dlmp), _ptr(lm_probs), _ptr(symbols), _ptr(rsx), _ptr(rsy),
-                      blank, _ptr(d_lm), B, S, C, st)
+        *saved, px_grad, py_grad = ctx.saved_tensors
+        scale, stride, mul = _upstream_scale(g_loss, ctx.code, px_grad.shape[0])
+        d_lm, d_am = _simple_backward(saved, ctx.meta, px_grad, py_grad, scale, stride, mul)
         return d_lm, d_am, None, None, None, None, None, None, None
 
 
@@ -286,23 +258,10 @@ def _check_simple_inputs(lm, am, symbols, termination_symbol):
 
 
 def _simple_logprobs_native(lm, am, symbols, termination_symbol, rnnt_type, boundary, delay_penalty=0.0):
-    _require_gpu(am, "am"); _require_gpu(lm, "lm")
-    if am.dtype != torch.float32 or lm.dtype != torch.float32:
-        raise TypeError("am and lm must be float32")
-    B, T, C = am.shape
-    S = lm.shape[1] - 1
-    if lm.shape[0] != B or lm.shape[2] != C:
-        raise ValueError(f"lm {tuple(lm.shape)} and am {tuple(am.shape)} disagree")
-    symbols = torch.as_tensor(symbols, device=am.device)
-    if tuple(symbols.shape) != (B, S):
-        raise ValueError(f"symbols must have shape {(B, S)}, got {tuple(symbols.shape)}")
-    if not 0 <= int(termination_symbol) < C:
-        raise ValueError(f"termination_symbol {termination_symbol} not in [0, {C})")
-    symbols = symbols.to(torch.int32).contiguous()
-    boundary = _as_boundary(boundary, B, am.device)
-    modified = rnnt_type != "regular"
-    pen = float(delay_penalty) if delay_penalty > 0.0 else 0.0
-    px, py = _SimpleLogprobs.apply(lm, am, symbols, termination_symbol, boundary, modified, pen)
+    symbols = _check_simple_inputs(lm, am, symbols, termination_symbol)
+    boundary = _as_boundary(boundary, am.shape[0], am.device)
+    px, py = _SimpleLogprobs.apply(lm, am, symbols, termination_symbol, boundary, rnnt_type != "regular",
+                                   _penalty(delay_penalty))
     if rnnt_type == "constrained":
         px = px + py[:, 1:, :]
     return px, py
@@ -322,6 +281,11 @@ def get_rnnt_logprobs(
     return _simple_logprobs_native(lm, am, symbols, termination_symbol, rnnt_type, boundary)
 
 
+def _penalty(delay_penalty) -> float:
+    """The delay penalty as the lattice writers take it: 0.0 switches it off, as any value that is not positive does."""
+    return float(delay_penalty) if delay_penalty > 0.0 else 0.0
+
+
 def _apply_delay_penalty(px, boundary, rnnt_type, delay_penalty):
     """rnnt_loss.py:305-321 (also :518-534, :1097-1114, :1461-1478): float64 offsets, cast to px.dtype."""
     if not delay_penalty > 0.0:
@@ -337,16 +301,6 @@ def _apply_delay_penalty(px, boundary, rnnt_type, delay_penalty):
     return px + penalty.to(px.dtype)
 
 
-def _reduce(negated_loss: torch.Tensor, reduction: Optional[str]) -> torch.Tensor:
-    if reduction == "none":
-        return -negated_loss
-    if reduction == "mean":
-        return -torch.mean(negated_loss)
-    if reduction == "sum":
-        return -torch.sum(negated_loss)
-    raise ValueError(f"reduction should be ('none' | 'mean' | 'sum'), given {reduction}")
-
-
 _REDUCTIONS = {"none": 0, "mean": 1, "sum": 2}
 
 
@@ -354,6 +308,13 @@ def _reduction_code(reduction: Optional[str]) -> int:
     if reduction not in _REDUCTIONS:
         raise ValueError(f"reduction should be ('none' | 'mean' | 'sum'), given {reduction}")
     return _REDUCTIONS[reduction]
+
+
+def _reduce(negated_loss: torch.Tensor, reduction: Optional[str]) -> torch.Tensor:
+    code = _reduction_code(reduction)
+    if code == 0:
+        return -negated_loss
+    return -torch.mean(negated_loss) if code == 1 else -torch.sum(negated_loss)
 
 
 def _negated_reduce_native(ans: torch.Tensor, code: int) -> torch.Tensor:
@@ -398,15 +359,21 @@ def rnnt_loss_simple(
         px = _apply_delay_penalty(px, boundary, rnnt_type, delay_penalty)
         return _drive(px, py, boundary, reduction, calc_gradients)
     symbols_i = _check_simple_inputs(lm, am, symbols, termination_symbol)
-    pen = float(delay_penalty) if delay_penalty > 0.0 else 0.0
     loss, px_grad, py_grad = _SimpleLoss.apply(lm, am, symbols_i, termination_symbol, boundary, rnnt_type != "regular",
-                                               pen, code, bool(calc_gradients))
+                                               _penalty(delay_penalty), code, bool(calc_gradients))
     return (loss, (px_grad, py_grad)) if calc_gradients else loss
 
 
-def _identity_ranges(B: int, T: int, S1: int, device) -> torch.Tensor:
-    """ranges[b,t,:] = 0..S: with every row in range the pruned builder IS the joint builder (its band is the lattice)."""
-    ranges = torch.arange(S1, dtype=torch.int32, device=device).expand(B, T, S1).contiguous()
+def _joint_inputs(logits, symbols) -> torch.Tensor:
+    """Checks unpruned joiner logits [B,T,S+1,C] against symbols [B,S] and returns the identity ranges, ranges[b,t,:] =
+    0..S: with every row in range the pruned builder IS the joint builder (its band is the lattice)."""
+    _require_gpu(logits, "logits")
+    if logits.dim() != 4:
+        raise ValueError("logits must be [B,T,S+1,C]")
+    B, T, S1, _ = logits.shape
+    if tuple(torch.as_tensor(symbols).shape) != (B, S1 - 1):
+        raise ValueError(f"symbols must have shape {(B, S1 - 1)}, got {tuple(torch.as_tensor(symbols).shape)}")
+    ranges = torch.arange(S1, dtype=torch.int32, device=logits.device).expand(B, T, S1).contiguous()
     _mark_band(ranges)
     return ranges
 
@@ -422,13 +389,7 @@ def get_rnnt_logprobs_joint(
     log-sum-exp + lattice writer of the pruned builder with s_range = S+1 (identity ranges), and the same
     hand-written backward (d/d logits = scattered gradient - softmax * row sum)."""
     _check_type(rnnt_type)
-    if logits.dim() != 4:
-        raise ValueError("logits must be [B,T,S+1,C]")
-    B, T, S1, C = logits.shape
-    if tuple(torch.as_tensor(symbols).shape) != (B, S1 - 1):
-        raise ValueError(f"symbols must have shape {(B, S1 - 1)}, got {tuple(torch.as_tensor(symbols).shape)}")
-    _require_gpu(logits, "logits")
-    return get_rnnt_logprobs_pruned(logits=logits, symbols=symbols, ranges=_identity_ranges(B, T, S1, logits.device),
+    return get_rnnt_logprobs_pruned(logits=logits, symbols=symbols, ranges=_joint_inputs(logits, symbols),
                                     termination_symbol=termination_symbol, boundary=boundary, rnnt_type=rnnt_type)
 
 
@@ -443,13 +404,7 @@ def get_hat_logprobs_joint(
     with the normalisation of ``get_hat_logprobs_pruned``, on identity ranges.  The best path of a HAT model is
     ``mutual_information_viterbi(*get_hat_logprobs_joint(...), boundary)``."""
     _check_type(rnnt_type)
-    if logits.dim() != 4:
-        raise ValueError("logits must be [B,T,S+1,C]")
-    B, T, S1, C = logits.shape
-    if tuple(torch.as_tensor(symbols).shape) != (B, S1 - 1):
-        raise ValueError(f"symbols must have shape {(B, S1 - 1)}, got {tuple(torch.as_tensor(symbols).shape)}")
-    _require_gpu(logits, "logits")
-    return get_hat_logprobs_pruned(logits=logits, symbols=symbols, ranges=_identity_ranges(B, T, S1, logits.device),
+    return get_hat_logprobs_pruned(logits=logits, symbols=symbols, ranges=_joint_inputs(logits, symbols),
                                    termination_symbol=termination_symbol, boundary=boundary, rnnt_type=rnnt_type)
 
 
@@ -468,9 +423,7 @@ def rnnt_loss(
     _check_type(rnnt_type)
     boundary = _as_boundary(boundary, logits.shape[0], logits.device)
     if not calc_gradients:
-        _require_gpu(logits, "logits")
-        B, T, S1, _ = logits.shape
-        return rnnt_loss_pruned(logits=logits, symbols=symbols, ranges=_identity_ranges(B, T, S1, logits.device),
+        return rnnt_loss_pruned(logits=logits, symbols=symbols, ranges=_joint_inputs(logits, symbols),
                                 termination_symbol=termination_symbol, boundary=boundary, rnnt_type=rnnt_type,
                                 delay_penalty=delay_penalty, reduction=reduction)
     px, py = get_rnnt_logprobs_joint(logits=logits, symbols=symbols, termination_symbol=termination_symbol,
@@ -524,7 +477,6 @@ def get_rnnt_prune_ranges(
     boundary = _as_boundary(boundary, B, px_grad.device)
     ranges = torch.empty((B, T, r), dtype=torch.int32, device=px_grad.device)
     scratch = torch.empty((B, T), dtype=torch.int32, device=px_grad.device)
-    import ctypes
     r_eff = ctypes.c_int(0)
     with torch.cuda.device(px_grad.device):
         _lib.call("ftr_prune_ranges_i32", _ptr(px_grad), _ptr(py_grad), _ptr(boundary), _ptr(ranges),
@@ -593,50 +545,54 @@ def do_rnnt_pruning(am: torch.Tensor, lm: torch.Tensor, ranges: torch.Tensor, de
     return _DoPruning.apply(am, lm, ranges, bool(dense))
 
 
+def _pruned_builder_fwd(x, symbols, ranges, boundary, blank, delay_penalty, modified, hat):
+    """lse [B,T,r] and the full-size px / py of the pruned builder (``hat``: the ftr_hat_* twin), one launch."""
+    B, T, r, C = x.shape
+    S = symbols.shape[1]
+    lse = torch.empty((B, T, r), dtype=torch.float32, device=x.device)
+    px = torch.empty((B, S, T if modified else T + 1), dtype=torch.float32, device=x.device)
+    py = torch.empty((B, S + 1, T), dtype=torch.float32, device=x.device)
+    with torch.cuda.device(x.device):
+        _lib.call("ftr_hat_pruned_logprobs_fwd_f32" if hat else "ftr_pruned_logprobs_fwd_f32", _ptr(x), _ptr(symbols),
+                  _ptr(ranges), _ptr(boundary), int(blank), float(delay_penalty), _ptr(lse), _ptr(px), _ptr(py), B, T, S, C, r,
+                  int(modified), _stream_ptr(x))
+    return lse, px, py
+
+
+_PRUNED_BWD = {(False, False): "ftr_pruned_logprobs_bwd_scaled_f32", (False, True): "ftr_hat_pruned_logprobs_bwd_scaled_f32",
+               (True, False): "ftr_pruned_band_bwd_scaled_f32", (True, True): "ftr_hat_pruned_band_bwd_scaled_f32"}
+
+
+def _pruned_builder_bwd(x, symbols, ranges, boundary, blank, modified, lse, gpx, gpy, scale, stride, mul, band, hat):
+    """d/d logits from d/d px, d/d py (``band``: band-shaped [B,T,r], else the full-size lattices), multiplied on the fly
+    by (scale ? scale[b * stride] : 1) * mul; one streaming launch."""
+    B, T, r, C = x.shape
+    S = symbols.shape[1]
+    g = torch.empty_like(x)
+    with torch.cuda.device(x.device):
+        _lib.call(_PRUNED_BWD[band, hat], _ptr(x), _ptr(symbols), _ptr(ranges), _ptr(boundary), blank, _ptr(lse), _ptr(gpx),
+                  _ptr(gpy), _ptr(scale), stride, mul, _ptr(g), B, T, S, C, r, modified, _stream_ptr(x))
+    return g
+
+
 class _PrunedLogprobs(torch.autograd.Function):
     """get_rnnt_logprobs_pruned for regular/modified as two native launches each way (``hat``: the ftr_hat_* twins,
     get_hat_logprobs_pruned)."""
 
     @staticmethod
     def forward(ctx, logits, symbols, ranges, termination_symbol, boundary, modified, delay_penalty, hat):
-        B, T, r, C = logits.shape
-        S = symbols.shape[1]
-        T1 = T if modified else T + 1
         x = logits.detach().contiguous()
-        lse = torch.empty((B, T, r), dtype=torch.float32, device=x.device)
-        px = torch.empty((B, S, T1), dtype=torch.float32, device=x.device)
-        py = torch.empty((B, S + 1, T), dtype=torch.float32, device=x.device)
-        with torch.cuda.device(x.device):
-            _lib.call("ftr_hat_pruned_logprobs_fwd_f32" if hat else "ftr_pruned_logprobs_fwd_f32",
-                                                              _ptr(x), _ptr(symbols), _ptr(ranges), _ptr(boundary),
-                                                              int(termination_symbol), float(delay_penalty), _ptr(lse),
-                                                              _ptr(px), _ptr(py), B, T, S, C, r, int(modified),
-                                                              _stream_ptr(x))
-        ctx.save_for_backward(x, symbols, ranges, lse, boundary if boundary is not None else torch.empty(0))
-        ctx.has_boundary = boundary is not None
-        ctx.meta = (int(termination_symbol), int(modified))
-        ctx.hat = bool(hat)
+        lse, px, py = _pruned_builder_fwd(x, symbols, ranges, boundary, termination_symbol, delay_penalty, modified, hat)
+        ctx.save_for_backward(x, symbols, ranges, lse, boundary)
+        ctx.meta = (int(termination_symbol), int(modified), bool(hat))
         return px, py
 
     @staticmethod
     def backward(ctx, gpx, gpy):
         x, symbols, ranges, lse, boundary = ctx.saved_tensors
-        if not ctx.has_boundary:
-            boundary = None
-        blank, modified = ctx.meta
-        B, T, r, C = x.shape
-        S = symbols.shape[1]
-        g = torch.empty_like(x)
-        gpx = gpx.contiguous(); gpy = gpy.contiguous()
-        with torch.cuda.device(x.device):
-            if ctx.hat:   # the HAT twin exists in the _scaled form only: no scale, stride 0, multiplier 1
-                _lib.call("ftr_hat_pruned_logprobs_bwd_scaled_f32", _ptr(x), _ptr(symbols), _ptr(ranges), _ptr(boundary),
-                          blank, _ptr(lse), _ptr(gpx), _ptr(gpy), None, 0, 1.0, _ptr(g), B, T, S, C, r, modified,
-                          _stream_ptr(x))
-            else:
-                _lib.call("ftr_pruned_logprobs_bwd_f32", _ptr(x), _ptr(symbols), _ptr(ranges), _ptr(boundary), blank,
-                                                                  _ptr(lse), _ptr(gpx), _ptr(gpy), None, _ptr(g),
-                                                                  B, T, S, C, r, modified, _stream_ptr(x))
+        blank, modified, hat = ctx.meta
+        g = _pruned_builder_bwd(x, symbols, ranges, boundary, blank, modified, lse, gpx.contiguous(), gpy.contiguous(),
+                                None, 0, 1.0, False, hat)
         return g, None, None, None, None, None, None, None
 
 
@@ -717,17 +673,8 @@ def rnnt_alignment_pruned(
     _check_type(rnnt_type)
     with torch.no_grad():
         symbols, ranges, boundary = _pruned_inputs(logits, symbols, ranges, boundary)
-        B, T, r, C = logits.shape
-        S = symbols.shape[1]
-        modified = rnnt_type != "regular"
-        x = logits.detach().contiguous()
-        lse = torch.empty((B, T, r), dtype=torch.float32, device=x.device)
-        px = torch.empty((B, S, T if modified else T + 1), dtype=torch.float32, device=x.device)
-        py = torch.empty((B, S + 1, T), dtype=torch.float32, device=x.device)
-        with torch.cuda.device(x.device):
-            _lib.call("ftr_pruned_logprobs_fwd_f32", _ptr(x), _ptr(symbols), _ptr(ranges), _ptr(boundary),
-                      int(termination_symbol), 0.0, _ptr(lse), _ptr(px), _ptr(py), B, T, S, C, r, int(modified),
-                      _stream_ptr(x))
+        _, px, py = _pruned_builder_fwd(logits.detach().contiguous(), symbols, ranges, boundary, termination_symbol, 0.0,
+                                        rnnt_type != "regular", False)
         if rnnt_type == "constrained":
             px += py[:, 1:, :]
         return mutual_information_viterbi(px, py, boundary)
@@ -770,7 +717,6 @@ def _is_band(ranges: torch.Tensor, boundary) -> bool:
 def _band_path_ok(ranges, boundary, T: int, S: int, r: int) -> bool:
     """The band-native recursion needs a band that its kernels cover (r <= 15) and ranges that ARE a band (_is_band).
     FTR_PRUNED_ROUTE=lattice (a test knob, read at call time) sends everything through the full-size lattices."""
-    import os
     if os.environ.get("FTR_PRUNED_ROUTE") == "lattice":
         return False
     return _lib.lib().ftr_mutual_information_band_supported(int(T), int(S), int(r)) != 0 and _is_band(ranges, boundary)
@@ -791,12 +737,11 @@ class _PrunedLoss(torch.autograd.Function):
     def forward(ctx, logits, symbols, ranges, termination_symbol, boundary, modified, delay_penalty, code, hat):
         B, T, r, C = logits.shape
         S = symbols.shape[1]
-        T1 = T if modified else T + 1
         x = logits.detach().contiguous()
         need = logits.requires_grad
-        lse = torch.empty((B, T, r), dtype=torch.float32, device=x.device)
         ctx.band = _band_path_ok(ranges, boundary, T, S, r)
         if ctx.band:
+            lse = torch.empty((B, T, r), dtype=torch.float32, device=x.device)
             pxb = torch.empty((B, T, r), dtype=torch.float32, device=x.device)
             pyb = torch.empty((B, T, r), dtype=torch.float32, device=x.device)
             gxb = torch.empty((B, T, r), dtype=torch.float32, device=x.device)
@@ -815,44 +760,23 @@ class _PrunedLoss(torch.autograd.Function):
                 del bws
             del pxb, pyb
             if need:
-                ctx.save_for_backward(x, symbols, ranges, lse, gxb, gyb,
-                                      boundary if boundary is not None else torch.empty(0))
+                ctx.save_for_backward(x, symbols, ranges, lse, gxb, gyb, boundary)
         else:
-            px = torch.empty((B, S, T1), dtype=torch.float32, device=x.device)
-            py = torch.empty((B, S + 1, T), dtype=torch.float32, device=x.device)
-            with torch.cuda.device(x.device):
-                _lib.call("ftr_hat_pruned_logprobs_fwd_f32" if hat else "ftr_pruned_logprobs_fwd_f32",
-                                                                  _ptr(x), _ptr(symbols), _ptr(ranges), _ptr(boundary),
-                                                                  int(termination_symbol), float(delay_penalty), _ptr(lse),
-                                                                  _ptr(px), _ptr(py), B, T, S, C, r, int(modified),
-                                                                  _stream_ptr(x))
+            lse, px, py = _pruned_builder_fwd(x, symbols, ranges, boundary, termination_symbol, delay_penalty, modified, hat)
             ans, px_grad, py_grad = mi_forward_backward(px, py, boundary, need, ans_grad_is_one=True)
             del px, py
             if need:
-                ctx.save_for_backward(x, symbols, ranges, lse, px_grad, py_grad,
-                                      boundary if boundary is not None else torch.empty(0))
-        ctx.has_boundary = boundary is not None
-        ctx.meta = (int(termination_symbol), int(modified), int(code))
-        ctx.hat = bool(hat)
+                ctx.save_for_backward(x, symbols, ranges, lse, px_grad, py_grad, boundary)
+        ctx.meta = (int(termination_symbol), int(modified), int(code), bool(hat))
         return _negated_reduce_native(ans, code)
 
     @staticmethod
     def backward(ctx, g_loss):
         x, symbols, ranges, lse, px_grad, py_grad, boundary = ctx.saved_tensors
-        if not ctx.has_boundary:
-            boundary = None
-        blank, modified, code = ctx.meta
-        B, T, r, C = x.shape
-        S = symbols.shape[1]
-        g = torch.empty_like(x)
-        scale, stride, mul = _upstream_scale(g_loss, code, B)
-        name = "ftr_pruned_band_bwd_scaled_f32" if ctx.band else "ftr_pruned_logprobs_bwd_scaled_f32"
-        if ctx.hat:
-            name = name.replace("ftr_", "ftr_hat_", 1)
-        with torch.cuda.device(x.device):
-            _lib.call(name, _ptr(x), _ptr(symbols), _ptr(ranges), _ptr(boundary), blank,
-                      _ptr(lse), _ptr(px_grad), _ptr(py_grad), _ptr(scale), stride, mul, _ptr(g),
-                      B, T, S, C, r, modified, _stream_ptr(x))
+        blank, modified, code, hat = ctx.meta
+        scale, stride, mul = _upstream_scale(g_loss, code, x.shape[0])
+        g = _pruned_builder_bwd(x, symbols, ranges, boundary, blank, modified, lse, px_grad, py_grad, scale, stride, mul,
+                                ctx.band, hat)
         return g, None, None, None, None, None, None, None, None
 
 
@@ -882,7 +806,7 @@ def _pruned_loss(logits, symbols, ranges, termination_symbol, boundary, rnnt_typ
         negated_loss = mutual_information_recursion(px=px, py=py, boundary=boundary_i, calc_gradients=False)
         return _reduce(negated_loss, reduction)
     return _PrunedLoss.apply(logits, symbols_i, ranges_i, termination_symbol, boundary_i, rnnt_type != "regular",
-                             float(delay_penalty) if delay_penalty > 0.0 else 0.0, code, hat)
+                             _penalty(delay_penalty), code, hat)
 
 
 def hat_loss_pruned(
@@ -915,11 +839,7 @@ def hat_loss(
     identity ranges."""
     _check_type(rnnt_type)
     boundary = _as_boundary(boundary, logits.shape[0], logits.device)
-    _require_gpu(logits, "logits")
-    if logits.dim() != 4:
-        raise ValueError("logits must be [B,T,S+1,C]")
-    B, T, S1, _ = logits.shape
-    return hat_loss_pruned(logits=logits, symbols=symbols, ranges=_identity_ranges(B, T, S1, logits.device),
+    return hat_loss_pruned(logits=logits, symbols=symbols, ranges=_joint_inputs(logits, symbols),
                            termination_symbol=termination_symbol, boundary=boundary, rnnt_type=rnnt_type,
                            delay_penalty=delay_penalty, reduction=reduction)
 
@@ -929,7 +849,6 @@ def hat_loss(
 def _big_blank_args(big_blanks, termination_symbol: int, C: int):
     """(ids, durations) as host int32 arrays for the C ABI, durations[0] = 1 being the standard blank's.  The checks are
     those of the native entry points, raised here as ValueError before anything is allocated."""
-    import ctypes
     pairs = [(int(i), int(d)) for i, d in big_blanks]
     ids = [i for i, _ in pairs]
     durs = [1] + [d for _, d in pairs]
@@ -977,16 +896,13 @@ class _MultiblankLogprobs(torch.autograd.Function):
         x = logits.detach().contiguous()
         ids, durs, dt = _big_blank_args(big_blanks, termination_symbol, x.shape[3])
         lse, px, py = _mb_builder_fwd(x, symbols, ranges, boundary, int(termination_symbol), ids, durs, len(dt), sigma, 0.0)
-        ctx.save_for_backward(x, symbols, ranges, lse, boundary if boundary is not None else torch.empty(0))
-        ctx.has_boundary = boundary is not None
+        ctx.save_for_backward(x, symbols, ranges, lse, boundary)
         ctx.meta = (int(termination_symbol), ids, durs, len(dt))
         return px, py
 
     @staticmethod
     def backward(ctx, gpx, gpy):
         x, symbols, ranges, lse, boundary = ctx.saved_tensors
-        if not ctx.has_boundary:
-            boundary = None
         blank, ids, durs, D = ctx.meta
         g = _mb_builder_bwd(x, symbols, ranges, boundary, blank, ids, durs, D, lse, gpx.contiguous(), gpy.contiguous(),
                             None, 0, 1.0)
@@ -1008,17 +924,13 @@ class _MultiblankLoss(torch.autograd.Function):
         ans, px_grad, py_grad = mb_forward_backward(px, py, dt, boundary, need)
         del px, py
         if need:
-            ctx.save_for_backward(x, symbols, ranges, lse, px_grad, py_grad,
-                                  boundary if boundary is not None else torch.empty(0))
-        ctx.has_boundary = boundary is not None
+            ctx.save_for_backward(x, symbols, ranges, lse, px_grad, py_grad, boundary)
         ctx.meta = (int(termination_symbol), ids, durs, len(dt), int(code))
         return _negated_reduce_native(ans, code)
 
     @staticmethod
     def backward(ctx, g_loss):
         x, symbols, ranges, lse, px_grad, py_grad, boundary = ctx.saved_tensors
-        if not ctx.has_boundary:
-            boundary = None
         blank, ids, durs, D, code = ctx.meta
         scale, stride, mul = _upstream_scale(g_loss, code, x.shape[0])
         g = _mb_builder_bwd(x, symbols, ranges, boundary, blank, ids, durs, D, lse, px_grad, py_grad, scale, stride, mul)
@@ -1055,16 +967,6 @@ def get_rnnt_logprobs_multiblank_pruned(
     symbols, ranges, boundary = _pruned_inputs(logits, symbols, ranges, boundary)
     return _MultiblankLogprobs.apply(logits, symbols, ranges, termination_symbol, tuple(map(tuple, big_blanks)), boundary,
                                      _check_sigma(sigma))
-
-
-def _joint_inputs(logits, symbols):
-    _require_gpu(logits, "logits")
-    if logits.dim() != 4:
-        raise ValueError("logits must be [B,T,S+1,C]")
-    B, T, S1, _ = logits.shape
-    if tuple(torch.as_tensor(symbols).shape) != (B, S1 - 1):
-        raise ValueError(f"symbols must have shape {(B, S1 - 1)}, got {tuple(torch.as_tensor(symbols).shape)}")
-    return _identity_ranges(B, T, S1, logits.device)
 
 
 def get_rnnt_logprobs_multiblank_joint(
@@ -1104,7 +1006,7 @@ def rnnt_loss_multiblank_pruned(
     code = _reduction_code(reduction)
     symbols_i, ranges_i, boundary_i = _pruned_inputs(logits, symbols, ranges, boundary)
     return _MultiblankLoss.apply(logits, symbols_i, ranges_i, termination_symbol, tuple(map(tuple, big_blanks)), boundary_i,
-                                 _check_sigma(sigma), float(delay_penalty) if delay_penalty > 0.0 else 0.0, code)
+                                 _check_sigma(sigma), _penalty(delay_penalty), code)
 
 
 def rnnt_loss_multiblank(
@@ -1132,7 +1034,6 @@ def rnnt_loss_multiblank(
 def _tdt_args(durations, termination_symbol: int, width: int):
     """(host int32 array, durations, blank_durations, C) for a joiner row of ``width`` = C + N columns.  The checks are
     those of the native entry points, raised here as ValueError before anything is allocated."""
-    import ctypes
     durs = tuple(int(d) for d in durations)
     if not 1 <= len(durs) <= 5:
         raise ValueError(f"durations must hold 1..5 values, got {len(durs)}")
@@ -1183,16 +1084,13 @@ class _TdtLogprobs(torch.autograd.Function):
         arr, durs, blank_durs, C = _tdt_args(durations, termination_symbol, x.shape[3])
         lse_tok, lse_dur, px, py = _tdt_builder_fwd(x, symbols, ranges, boundary, int(termination_symbol), arr, durs,
                                                     blank_durs, C, sigma, delay_penalty)
-        ctx.save_for_backward(x, symbols, ranges, lse_tok, lse_dur, boundary if boundary is not None else torch.empty(0))
-        ctx.has_boundary = boundary is not None
+        ctx.save_for_backward(x, symbols, ranges, lse_tok, lse_dur, boundary)
         ctx.meta = (int(termination_symbol), arr, len(durs), C, sigma, delay_penalty)
         return px, py
 
     @staticmethod
     def backward(ctx, gpx, gpy):
         x, symbols, ranges, lse_tok, lse_dur, boundary = ctx.saved_tensors
-        if not ctx.has_boundary:
-            boundary = None
         blank, arr, N, C, sigma, delay_penalty = ctx.meta
         g = _tdt_builder_bwd(x, symbols, ranges, boundary, blank, arr, N, C, sigma, delay_penalty, lse_tok, lse_dur,
                              gpx.contiguous(), gpy.contiguous(), None, 0, 1.0)
@@ -1214,17 +1112,13 @@ class _TdtLoss(torch.autograd.Function):
         ans, px_grad, py_grad = tdt_forward_backward(px, py, durs, blank_durs, boundary, need)
         del px, py
         if need:
-            ctx.save_for_backward(x, symbols, ranges, lse_tok, lse_dur, px_grad, py_grad,
-                                  boundary if boundary is not None else torch.empty(0))
-        ctx.has_boundary = boundary is not None
+            ctx.save_for_backward(x, symbols, ranges, lse_tok, lse_dur, px_grad, py_grad, boundary)
         ctx.meta = (int(termination_symbol), arr, len(durs), C, sigma, delay_penalty, int(code))
         return _negated_reduce_native(ans, code)
 
     @staticmethod
     def backward(ctx, g_loss):
         x, symbols, ranges, lse_tok, lse_dur, px_grad, py_grad, boundary = ctx.saved_tensors
-        if not ctx.has_boundary:
-            boundary = None
         blank, arr, N, C, sigma, delay_penalty, code = ctx.meta
         scale, stride, mul = _upstream_scale(g_loss, code, x.shape[0])
         g = _tdt_builder_bwd(x, symbols, ranges, boundary, blank, arr, N, C, sigma, delay_penalty, lse_tok, lse_dur, px_grad,
@@ -1260,7 +1154,7 @@ def get_rnnt_logprobs_tdt_pruned(
     w.r.t. ``logits``."""
     symbols, ranges, boundary = _pruned_inputs(logits, symbols, ranges, boundary)
     return _TdtLogprobs.apply(logits, symbols, ranges, termination_symbol, tuple(durations), boundary, _check_sigma(sigma),
-                              float(delay_penalty) if delay_penalty > 0.0 else 0.0)
+                              _penalty(delay_penalty))
 
 
 def get_rnnt_logprobs_tdt_joint(
@@ -1304,7 +1198,7 @@ def rnnt_loss_tdt_pruned(
     symbols_i, ranges_i, boundary_i = _pruned_inputs(logits, symbols, ranges, boundary)
     _tdt_args(durations, termination_symbol, logits.shape[3])
     return _TdtLoss.apply(logits, symbols_i, ranges_i, termination_symbol, tuple(durations), boundary_i, _check_sigma(sigma),
-                          float(delay_penalty) if delay_penalty > 0.0 else 0.0, code)
+                          _penalty(delay_penalty), code)
 
 
 def rnnt_loss_tdt(
@@ -1440,17 +1334,15 @@ def _smoothed_forward(lm, am, symbols, termination_symbol, boundary, modified, l
             _lib.call("ftr_smoothed_logprobs_fwd_pen_f32", _ptr(amc), _ptr(lmc), _ptr(symbols), _ptr(prod), _ptr(am_max),
                       _ptr(lm_max), _ptr(lmonly), _ptr(amonly), _ptr(ulog), _ptr(boundary), int(termination_symbol),
                       float(delay_penalty), cs, ls, a_s, _ptr(px), _ptr(py), B, T, S, C, int(modified), st)
-    saved = (am_probs, lm_probs, prod, symbols, boundary if boundary is not None else torch.empty(0), inv, u, am_dot)
+    saved = (am_probs, lm_probs, prod, symbols, boundary, inv, u, am_dot)
     meta = (int(termination_symbol), int(modified), cs, ls, a_s, count, process_group)
     return px, py, saved, meta
 
 
-def _smoothed_backward(saved, has_boundary, meta, gpx, gpy, scale=None, stride=0, mul=1.0):
+def _smoothed_backward(saved, meta, gpx, gpy, scale=None, stride=0, mul=1.0):
     """Hand-written backward of the smoothed builder; gpx / gpy are d/d px, d/d py, multiplied on the fly by
     (scale ? scale[b * stride] : 1) * mul (the upstream gradient of the loss that owns the occupancies)."""
     am_probs, lm_probs, prod, symbols, boundary, inv, u, am_dot = saved
-    if not has_boundary:
-        boundary = None
     blank, modified, cs, ls, a_s, count, group = meta
     B, T, C = am_probs.shape
     S = lm_probs.shape[1] - 1
@@ -1519,13 +1411,12 @@ class _SmoothedLogprobs(torch.autograd.Function):
         px, py, saved, meta = _smoothed_forward(lm, am, symbols, termination_symbol, boundary, modified, lm_only_scale,
                                                 am_only_scale, process_group, 0.0)
         ctx.save_for_backward(*saved)
-        ctx.has_boundary = boundary is not None
         ctx.meta = meta
         return px, py
 
     @staticmethod
     def backward(ctx, gpx, gpy):
-        d_lm, d_am = _smoothed_backward(ctx.saved_tensors, ctx.has_boundary, ctx.meta, gpx, gpy)
+        d_lm, d_am = _smoothed_backward(ctx.saved_tensors, ctx.meta, gpx, gpy)
         return d_lm, d_am, None, None, None, None, None, None, None
 
 
@@ -1550,7 +1441,6 @@ class _SmoothedLoss(torch.autograd.Function):
         else:
             px_grad = torch.zeros_like(px); py_grad = torch.zeros_like(py)
         del px, py
-        ctx.has_boundary = boundary is not None
         ctx.meta = meta
         ctx.code = int(code)
         ctx.mark_non_differentiable(px_grad, py_grad)
@@ -1562,9 +1452,8 @@ class _SmoothedLoss(torch.autograd.Function):
         if g_loss is None:
             return (None,) * 12
         *saved, px_grad, py_grad = ctx.saved_tensors
-        B = saved[0].shape[0]
-        scale, stride, mul = _upstream_scale(g_loss, ctx.code, B)
-        d_lm, d_am = _smoothed_backward(tuple(saved), ctx.has_boundary, ctx.meta, px_grad, py_grad, scale, stride, mul)
+        scale, stride, mul = _upstream_scale(g_loss, ctx.code, px_grad.shape[0])
+        d_lm, d_am = _smoothed_backward(saved, ctx.meta, px_grad, py_grad, scale, stride, mul)
         return d_lm, d_am, None, None, None, None, None, None, None, None, None, None
 
 
@@ -1584,20 +1473,8 @@ def get_rnnt_logprobs_smoothed(
     ``unigram_lm`` mean (rnnt_loss.py:1279-1280) is all-reduced (one [C] vector over RCCL forward, one backward)
     so every shard sees the global-batch value."""
     _check_type(rnnt_type)
-    _require_gpu(am, "am"); _require_gpu(lm, "lm")
-    if am.dtype != torch.float32 or lm.dtype != torch.float32:
-        raise TypeError("am and lm must be float32")
-    B, T, C = am.shape
-    S = lm.shape[1] - 1
-    if lm.shape[0] != B or lm.shape[2] != C:
-        raise ValueError(f"lm {tuple(lm.shape)} and am {tuple(am.shape)} disagree")
-    symbols = torch.as_tensor(symbols, device=am.device)
-    if tuple(symbols.shape) != (B, S):
-        raise ValueError(f"symbols must have shape {(B, S)}, got {tuple(symbols.shape)}")
-    if not 0 <= int(termination_symbol) < C:
-        raise ValueError(f"termination_symbol {termination_symbol} not in [0, {C})")
-    symbols = symbols.to(torch.int32).contiguous()
-    boundary = _as_boundary(boundary, B, am.device)
+    symbols = _check_simple_inputs(lm, am, symbols, termination_symbol)
+    boundary = _as_boundary(boundary, am.shape[0], am.device)
     px, py = _SmoothedLogprobs.apply(lm, am, symbols, termination_symbol, boundary, rnnt_type != "regular",
                                      float(lm_only_scale), float(am_only_scale), process_group)
     if rnnt_type == "constrained":
@@ -1621,6 +1498,7 @@ def rnnt_loss_smoothed(
 ) -> Union[Tuple[torch.Tensor, Tuple[torch.Tensor, torch.Tensor]], torch.Tensor]:
     """rnnt_loss.py:1369-1494.  regular / modified: one fused node (no framework-side pass over a lattice)."""
     _check_type(rnnt_type)
+    code = _reduction_code(reduction)
     boundary = _as_boundary(boundary, am.shape[0], am.device)
     if rnnt_type == "constrained":   # the penalty applies after px += py[:, 1:, :]  (:1362-1363, :1461-1478)
         px, py = get_rnnt_logprobs_smoothed(lm=lm, am=am, symbols=symbols, termination_symbol=termination_symbol,
@@ -1628,10 +1506,8 @@ def rnnt_loss_smoothed(
                                             boundary=boundary, rnnt_type=rnnt_type, process_group=process_group)
         px = _apply_delay_penalty(px, boundary, rnnt_type, delay_penalty)
         return _drive(px, py, boundary, reduction, calc_gradients)
-    code = _reduction_code(reduction)
     symbols_i = _check_simple_inputs(lm, am, symbols, termination_symbol)
-    pen = float(delay_penalty) if delay_penalty > 0.0 else 0.0
     loss, px_grad, py_grad = _SmoothedLoss.apply(lm, am, symbols_i, termination_symbol, boundary, rnnt_type != "regular",
-                                                 float(lm_only_scale), float(am_only_scale), process_group, pen, code,
-                                                 bool(calc_gradients))
+                                                 float(lm_only_scale), float(am_only_scale), process_group,
+                                                 _penalty(delay_penalty), code, bool(calc_gradients))
     return (loss, (px_grad, py_grad)) if calc_gradients else loss
