@@ -427,6 +427,25 @@ def test_do_pruning_backward_chunked(ft, dev, kind, same_tensor):
     np.testing.assert_allclose(lm.grad.cpu().numpy(), want.cpu().numpy(), rtol=1e-5, atol=1e-5)
 
 
+def test_do_pruning_backward_row_list_above_64kb(ft, dev):
+    """The workspace-free backward of the prune gather keeps one row's (t, k) list in LDS: T * s_range ints.  T * r = 16400
+    is the smallest size class past 64 KB (65600 bytes), where the launcher has to raise the kernel's dynamic-LDS limit
+    first.  S1 = r, so every frame selects every row and each list is as long as it can get.  float64 sums as reference."""
+    B, T, S1, C, r = 1, 4100, 4, 4, 4
+    g = torch.Generator(device="cpu").manual_seed(29)
+    ranges = torch.arange(r, dtype=torch.int32).expand(B, T, r).contiguous().to(dev)
+    w = torch.randn((B, T, r, C), generator=g).to(dev)
+    d_am = torch.full((B, T, C), float("nan"), device=dev); d_lm = torch.full((B, S1, C), float("nan"), device=dev)
+    ft._lib.call("ftr_do_pruning_bwd_f32", w.data_ptr(), w.data_ptr(), ranges.data_ptr(), d_am.data_ptr(), d_lm.data_ptr(),
+                 B, T, S1, C, r, torch.cuda.current_stream().cuda_stream)
+    np.testing.assert_allclose(d_am.cpu().numpy(), w.double().sum(dim=2).cpu().numpy(), rtol=1e-5, atol=1e-5)
+    # a float32 sum of T terms in any order: rounding error ~ sqrt(T) 2^-24 ||terms||_2 (random walk); the bound, 1e-5 ||terms||_2,
+    # is 2.6 times that
+    want = w.double().sum(dim=1)
+    scale = float(w.double().pow(2).sum(dim=1).sqrt().max())
+    assert np.abs(d_lm.cpu().numpy() - want.cpu().numpy()).max() <= 1e-5 * scale
+
+
 @pytest.mark.parametrize("kind", ["flat_then_steep", "gaps", "half_garbage", "owner_conflict", "out_of_range"])
 @pytest.mark.parametrize("shape", [(3, 150, 60, 24, 5), (2, 90, 50, 520, 3), (2, 64, 80, 40, 10), (1, 50, 90, 16, 17)])
 def test_do_pruning_backward_segments(ft, dev, kind, shape, monkeypatch):
@@ -730,6 +749,27 @@ def test_fused_builder_matches_library_gemm_route(ft, dev, oracle, rnnt_type, cf
         fin = np.isfinite(l)
         if fin.any():      # (S > T with the modified type has no path: every loss is -inf)
             assert np.abs(f[fin] - l[fin]).max() <= 2e-5 * max(1.0, np.abs(l[fin]).max())
+
+
+@pytest.mark.parametrize("rnnt_type", ["regular", "modified"])
+def test_library_gemm_builder_tile_above_64kb(ft, dev, rnnt_type, monkeypatch):
+    """The epilogue kernel of the library-GEMM route (csrc/simple_logprobs.hip) keeps 6 (S + 1) floats of per-symbol terms
+    next to its 32 x (C + 1) tile: S = 2800, C = 12 is 68.9 KB, past the 64 KB up to which a launch needs no raised
+    dynamic-LDS limit.  Against the fused kernel, as test_fused_builder_matches_library_gemm_route: same -inf pattern,
+    values to 2e-5."""
+    B, T, S, C = 1, 8, 2800, 12
+    d = synthetic(11 + S, B, T, S, C, ragged=True)
+    lm, am, sym, bnd = (_t(d[k], dev) for k in ("lm", "am", "symbols", "boundary"))
+
+    def run():
+        return [x.cpu().numpy() for x in ft.get_rnnt_logprobs(lm, am, sym, d["termination_symbol"], rnnt_type=rnnt_type, boundary=bnd)]
+
+    fused = run()
+    monkeypatch.setenv("FTR_BUILDER_GEMM", "library")
+    for f, l in zip(fused, run()):
+        assert f.shape == l.shape and np.array_equal(np.isneginf(f), np.isneginf(l))
+        fin = np.isfinite(l)
+        assert np.abs(f[fin] - l[fin]).max() <= 2e-5 * max(1.0, np.abs(l[fin]).max())
 
 
 @pytest.mark.parametrize("rnnt_type", ["regular", "modified"])

@@ -59,6 +59,63 @@ using namespace ftr;
       return FTR_ERR_INVALID_ARG;              \
     }                                          \
   } while (0)
+#define FTR_TRY(expr)                          \
+  do {                                         \
+    const int rc_ = (expr);                    \
+    if (rc_ != FTR_OK) return rc_;             \
+  } while (0)
+
+// The argument checks that many entry points share.  Each returns FTR_OK or FTR_ERR_INVALID_ARG with the error text set;
+// an entry runs them in its own order (the first failing check is the reply) and touches the device only after the last.
+namespace {
+hipStream_t stream_of(void* stream) { return reinterpret_cast<hipStream_t>(stream); }
+
+int check_lattice(const char* what, int B, int S, int T) {
+  FTR_REQUIRE(B >= 0 && S >= 0 && T >= 0, "%s: negative size B=%d S=%d T=%d", what, B, S, T);
+  return FTR_OK;
+}
+int check_sizes(const char* what, bool ok) {
+  FTR_REQUIRE(ok, "%s: bad sizes", what);
+  return FTR_OK;
+}
+// terse: the wording of the backward entries, which do not print the value
+int check_blank(const char* what, int blank, int C, bool terse = false) {
+  if (blank >= 0 && blank < C) return FTR_OK;
+  if (terse) set_error("%s: bad termination_symbol", what);
+  else set_error("%s: termination_symbol %d not in [0,%d)", what, blank, C);
+  return FTR_ERR_INVALID_ARG;
+}
+// the head of a builder entry: its sizes, the HAT twins' C >= 2, the termination symbol -- in this order
+int check_builder(const char* what, bool sizes_ok, int blank, int C, bool terse = false, int hat = 0) {
+  FTR_TRY(check_sizes(what, sizes_ok));
+  FTR_REQUIRE(!hat || C >= 2, "%s: C = %d, HAT needs a blank and at least one other symbol", what, C);
+  return check_blank(what, blank, C, terse);
+}
+int check_s_range(const char* what, int r, int S) {
+  FTR_REQUIRE(r <= S + 1, "%s: s_range %d > S+1 = %d", what, r, S + 1);
+  return FTR_OK;
+}
+int check_scale_stride(const char* what, int scale_stride) {
+  FTR_REQUIRE(scale_stride == 0 || scale_stride == 1, "%s: scale_stride must be 0 or 1", what);
+  return FTR_OK;
+}
+// the last step of most entries: the pointers, and only then the device
+int pointers_then_device(const char* what, bool all_there) {
+  FTR_REQUIRE(all_there, "%s: null pointer", what);
+  return device_ok();
+}
+// the workspace of the duration-lattice entries (multi-blank, TDT, TDT Viterbi): its size before the entry's null
+// checks, its alignment after them
+int check_ws_size(const char* what, size_t have, size_t need, const char* unit) {
+  FTR_REQUIRE(have >= need, "%s: workspace of %zu %s is too small, %zu needed", what, have, unit, need);
+  return FTR_OK;
+}
+int check_ws_aligned(const char* what, const void* workspace) {
+  FTR_REQUIRE(((uintptr_t)workspace & 7) == 0, "%s: workspace must be 8-byte aligned", what);
+  return FTR_OK;
+}
+}  // namespace
+
 
 extern "C" {
 
@@ -91,44 +148,40 @@ namespace {
 int mi_fwd_common(const char* what, const float* px, const float* py, const int32_t* boundary, float* p, size_t p_floats,
                   int flags, float* ans, int B, int S, int T, int modified, void* stream) {
   clear_error();
-  FTR_REQUIRE(B >= 0 && S >= 0 && T >= 0, "%s: negative size B=%d S=%d T=%d", what, B, S, T);
+  FTR_TRY(check_lattice(what, B, S, T));
   FTR_REQUIRE((flags & ~FTR_MI_WS_CLEAN) == 0, "%s: unknown flag bits 0x%x", what, flags);
   if (B == 0) return FTR_OK;
   FTR_REQUIRE(py && p && ans, "%s: null py/p/ans", what);
   FTR_REQUIRE(px || S == 0 || (modified ? T == 0 : false), "%s: null px", what);
-  int rc = device_ok();
-  if (rc != FTR_OK) return rc;
-  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  FTR_TRY(device_ok());
 #ifdef FTR_DIAG
   if (mi_impl() == 1) {
     FTR_REQUIRE(p_floats >= (size_t)B * (S + 1) * (T + 1), "%s: workspace too small for the plain family", what);
-    return mi_plain_fwd(px, py, boundary, p, ans, B, S, T, modified, st);
+    return mi_plain_fwd(px, py, boundary, p, ans, B, S, T, modified, stream_of(stream));
   }
 #endif
-  return mi_bidir_fwd(px, py, boundary, p, p_floats, flags, ans, B, S, T, modified, st);
+  return mi_bidir_fwd(px, py, boundary, p, p_floats, flags, ans, B, S, T, modified, stream_of(stream));
 }
 
 int mi_bwd_common(const char* what, const float* px, const float* py, const int32_t* boundary, const float* p,
                   size_t p_floats, int flags, float* p_grad, float* px_grad, float* py_grad, float* ans_grad,
                   int overwrite_ans_grad, int B, int S, int T, int modified, void* stream) {
   clear_error();
-  FTR_REQUIRE(B >= 0 && S >= 0 && T >= 0, "%s: negative size B=%d S=%d T=%d", what, B, S, T);
+  FTR_TRY(check_lattice(what, B, S, T));
   FTR_REQUIRE((flags & ~FTR_MI_WS_CLEAN) == 0, "%s: unknown flag bits 0x%x", what, flags);
   if (B == 0) return FTR_OK;
   FTR_REQUIRE(p && py_grad, "%s: null p/py_grad", what);
   FTR_REQUIRE(ans_grad || mi_impl() == 0, "%s: ans_grad may be NULL (= ones) only with the default kernel family", what);
   FTR_REQUIRE(px_grad || S == 0 || (modified && T == 0), "%s: null px_grad", what);
-  int rc = device_ok();
-  if (rc != FTR_OK) return rc;
-  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  FTR_TRY(device_ok());
 #ifdef FTR_DIAG
   if (mi_impl() == 1) {
     FTR_REQUIRE((px || S == 0) && py, "%s: the plain family needs px and py", what);
     FTR_REQUIRE(p_grad, "%s: the plain family needs the p_grad scratch lattice", what);
-    return mi_plain_bwd(px, py, boundary, p, p_grad, px_grad, py_grad, ans_grad, overwrite_ans_grad, B, S, T, modified, st);
+    return mi_plain_bwd(px, py, boundary, p, p_grad, px_grad, py_grad, ans_grad, overwrite_ans_grad, B, S, T, modified, stream_of(stream));
   }
 #endif
-  return mi_bidir_bwd(boundary, p, p_floats, flags, px_grad, py_grad, ans_grad, overwrite_ans_grad, B, S, T, modified, st);
+  return mi_bidir_bwd(boundary, p, p_floats, flags, px_grad, py_grad, ans_grad, overwrite_ans_grad, B, S, T, modified, stream_of(stream));
 }
 }  // namespace
 
@@ -162,28 +215,26 @@ int ftr_mutual_information_bwd_ws_f32(const float* px, const float* py, const in
 int ftr_mutual_information_bwd_loss_ws_f32(const float* px, const float* py, const int32_t* boundary, const float* p,
                                            size_t p_floats, int flags, float* px_grad, float* py_grad, const float* ans,
                                            int reduction, float* loss_out, int B, int S, int T, int modified, void* stream) {
+  const char* what = "mutual_information_bwd_loss_ws";
   clear_error();
   (void)px; (void)py;
-  FTR_REQUIRE(B >= 0 && S >= 0 && T >= 0, "mutual_information_bwd_loss_ws: negative size B=%d S=%d T=%d", B, S, T);
-  FTR_REQUIRE((flags & ~FTR_MI_WS_CLEAN) == 0, "mutual_information_bwd_loss_ws: unknown flag bits 0x%x", flags);
-  FTR_REQUIRE(reduction >= 0 && reduction <= 2, "mutual_information_bwd_loss_ws: reduction %d is not 0 (none), 1 (mean) or 2 (sum)", reduction);
+  FTR_TRY(check_lattice(what, B, S, T));
+  FTR_REQUIRE((flags & ~FTR_MI_WS_CLEAN) == 0, "%s: unknown flag bits 0x%x", what, flags);
+  FTR_REQUIRE(reduction >= 0 && reduction <= 2, "%s: reduction %d is not 0 (none), 1 (mean) or 2 (sum)", what, reduction);
   if (B == 0) return FTR_OK;
-  FTR_REQUIRE(p && py_grad && ans && loss_out, "mutual_information_bwd_loss_ws: null p / py_grad / ans / loss_out");
-  FTR_REQUIRE(px_grad || S == 0 || (modified && T == 0), "mutual_information_bwd_loss_ws: null px_grad");
-  FTR_REQUIRE(mi_impl() == 0, "mutual_information_bwd_loss_ws: only with the default kernel family");
-  int rc = device_ok();
-  if (rc != FTR_OK) return rc;
-  return mi_bidir_bwd(boundary, p, p_floats, flags, px_grad, py_grad, nullptr, 0, B, S, T, modified, reinterpret_cast<hipStream_t>(stream),
-                      ans, loss_out, reduction);
+  FTR_REQUIRE(p && py_grad && ans && loss_out, "%s: null p / py_grad / ans / loss_out", what);
+  FTR_REQUIRE(px_grad || S == 0 || (modified && T == 0), "%s: null px_grad", what);
+  FTR_REQUIRE(mi_impl() == 0, "%s: only with the default kernel family", what);
+  FTR_TRY(device_ok());
+  return mi_bidir_bwd(boundary, p, p_floats, flags, px_grad, py_grad, nullptr, 0, B, S, T, modified, stream_of(stream), ans, loss_out, reduction);
 }
 
 int ftr_mutual_information_workspace_init(float* p, size_t p_floats, int B, int S, int T, void* stream) {
   clear_error();
   FTR_REQUIRE(B >= 0 && S >= 0 && T >= 0, "mutual_information_workspace_init: negative size");
   FTR_REQUIRE(p, "mutual_information_workspace_init: null workspace");
-  int rc = device_ok();
-  if (rc != FTR_OK) return rc;
-  return mi_bidir_ws_init(p, p_floats, B, S, T, reinterpret_cast<hipStream_t>(stream));
+  FTR_TRY(device_ok());
+  return mi_bidir_ws_init(p, p_floats, B, S, T, stream_of(stream));
 }
 
 int ftr_mutual_information_status(const float* p, size_t p_floats, int B, int S, int T, int* status_host,
@@ -191,9 +242,8 @@ int ftr_mutual_information_status(const float* p, size_t p_floats, int B, int S,
   clear_error();
   FTR_REQUIRE(B >= 0 && S >= 0 && T >= 0, "mutual_information_status: negative size");
   FTR_REQUIRE(p && status_host, "mutual_information_status: null pointer");
-  int rc = device_ok();
-  if (rc != FTR_OK) return rc;
-  return mi_bidir_status(p, p_floats, B, S, T, status_host, dirty_words_host, reinterpret_cast<hipStream_t>(stream));
+  FTR_TRY(device_ok());
+  return mi_bidir_status(p, p_floats, B, S, T, status_host, dirty_words_host, stream_of(stream));
 }
 
 // Best-path (Viterbi) alignment over the lattice of ftr_mutual_information_fwd_f32 (MI355X addition, no reference
@@ -205,30 +255,25 @@ size_t ftr_mutual_information_viterbi_workspace_bytes(int B, int S, int T) {
 int ftr_mutual_information_viterbi_f32(const float* px, const float* py, const int32_t* boundary, void* workspace,
                                        size_t workspace_bytes, float* score, int32_t* frames, int B, int S, int T,
                                        int modified, void* stream) {
+  const char* what = "mutual_information_viterbi";
   clear_error();
-  FTR_REQUIRE(B >= 0 && S >= 0 && T >= 0, "mutual_information_viterbi: negative size B=%d S=%d T=%d", B, S, T);
-  FTR_REQUIRE(modified == 0 || modified == 1, "mutual_information_viterbi: modified=%d must be 0 or 1", modified);
+  FTR_TRY(check_lattice(what, B, S, T));
+  FTR_REQUIRE(modified == 0 || modified == 1, "%s: modified=%d must be 0 or 1", what, modified);
   if (B == 0) return FTR_OK;
-  FTR_REQUIRE(workspace_bytes >= mi_viterbi_workspace_bytes(B, S, T),
-              "mutual_information_viterbi: workspace of %zu bytes is too small, %zu needed", workspace_bytes,
-              mi_viterbi_workspace_bytes(B, S, T));
-  FTR_REQUIRE(workspace && score && (frames || S == 0), "mutual_information_viterbi: null workspace / score / frames");
-  FTR_REQUIRE(py || T == 0, "mutual_information_viterbi: null py");
-  FTR_REQUIRE(px || S == 0 || (modified && T == 0), "mutual_information_viterbi: null px");
-  int rc = device_ok();
-  if (rc != FTR_OK) return rc;
-  return mi_viterbi(px, py, boundary, workspace, workspace_bytes, score, frames, B, S, T, modified,
-                    reinterpret_cast<hipStream_t>(stream));
+  FTR_TRY(check_ws_size(what, workspace_bytes, mi_viterbi_workspace_bytes(B, S, T), "bytes"));
+  FTR_REQUIRE(workspace && score && (frames || S == 0), "%s: null workspace / score / frames", what);
+  FTR_REQUIRE(py || T == 0, "%s: null py", what);
+  FTR_REQUIRE(px || S == 0 || (modified && T == 0), "%s: null px", what);
+  FTR_TRY(device_ok());
+  return mi_viterbi(px, py, boundary, workspace, workspace_bytes, score, frames, B, S, T, modified, stream_of(stream));
 }
 
 int ftr_cummin_i32(const int32_t* in, int32_t* out, int rows, int cols, void* stream) {
   clear_error();
   FTR_REQUIRE(rows >= 0 && cols >= 0, "cummin: negative size");
   if (rows == 0 || cols == 0) return FTR_OK;
-  FTR_REQUIRE(in && out, "cummin: null pointer");
-  int rc = device_ok();
-  if (rc != FTR_OK) return rc;
-  return cummin_i32(in, out, rows, cols, reinterpret_cast<hipStream_t>(stream));
+  FTR_TRY(pointers_then_device("cummin", in && out));
+  return cummin_i32(in, out, rows, cols, stream_of(stream));
 }
 
 int ftr_prune_ranges_i32(const float* px_grad, const float* py_grad, const int32_t* boundary,
@@ -242,31 +287,17 @@ int ftr_prune_ranges_i32(const float* px_grad, const float* py_grad, const int32
   if (r_eff_out) *r_eff_out = r;
   if (B == 0) return FTR_OK;
   FTR_REQUIRE(px_grad && py_grad && boundary && ranges && s_begin_scratch, "prune_ranges: null pointer (boundary is mandatory)");
-  int rc = device_ok();
-  if (rc != FTR_OK) return rc;
-  return prune_ranges(px_grad, py_grad, boundary, ranges, s_begin_scratch, B, S, T, T1, r, reinterpret_cast<hipStream_t>(stream));
+  FTR_TRY(device_ok());
+  return prune_ranges(px_grad, py_grad, boundary, ranges, s_begin_scratch, B, S, T, T1, r, stream_of(stream));
 }
 
 int ftr_do_pruning_f32(const float* am, const float* lm, const int32_t* ranges, float* am_pruned,
                        float* lm_pruned, int B, int T, int S1, int C, int r, void* stream) {
   clear_error();
-  FTR_REQUIRE(B >= 0 && T >= 0 && S1 >= 1 && C >= 0 && r >= 0, "do_pruning: bad sizes");
+  FTR_TRY(check_sizes("do_pruning", B >= 0 && T >= 0 && S1 >= 1 && C >= 0 && r >= 0));
   if ((size_t)B * T * r * C == 0) return FTR_OK;
-  FTR_REQUIRE(am && lm && ranges && lm_pruned, "do_pruning: null pointer");   // am_pruned may be NULL: gather only
-  int rc = device_ok();
-  if (rc != FTR_OK) return rc;
-  return do_pruning(am, lm, ranges, am_pruned, lm_pruned, B, T, S1, C, r, reinterpret_cast<hipStream_t>(stream));
-}
-
-int ftr_do_pruning_bwd_f32(const float* g_am_pruned, const float* g_lm_pruned, const int32_t* ranges, float* d_am,
-                           float* d_lm, int B, int T, int S1, int C, int r, void* stream) {
-  clear_error();
-  FTR_REQUIRE(B >= 0 && T >= 0 && S1 >= 1 && C >= 0 && r >= 0, "do_pruning_bwd: bad sizes");
-  if ((size_t)B * C == 0) return FTR_OK;
-  FTR_REQUIRE(g_am_pruned && g_lm_pruned && ranges && d_am && d_lm, "do_pruning_bwd: null pointer");
-  int rc = device_ok();
-  if (rc != FTR_OK) return rc;
-  return do_pruning_bwd(g_am_pruned, g_lm_pruned, ranges, d_am, d_lm, B, T, S1, C, r, reinterpret_cast<hipStream_t>(stream));
+  FTR_TRY(pointers_then_device("do_pruning", am && lm && ranges && lm_pruned));   // am_pruned may be NULL: gather only
+  return do_pruning(am, lm, ranges, am_pruned, lm_pruned, B, T, S1, C, r, stream_of(stream));
 }
 
 size_t ftr_do_pruning_bwd_workspace_bytes(int B, int T, int S1, int C, int r) {
@@ -274,16 +305,27 @@ size_t ftr_do_pruning_bwd_workspace_bytes(int B, int T, int S1, int C, int r) {
   return do_pruning_bwd_workspace_bytes(B, T, S1, C, r);
 }
 
+// the entry without a workspace and the one with (has_ws; a NULL or short workspace is the launcher's to judge)
+static int do_pruning_bwd_entry(const char* what, const float* g_am_pruned, const float* g_lm_pruned, const int32_t* ranges,
+                                float* d_am, float* d_lm, int B, int T, int S1, int C, int r, bool has_ws, void* workspace,
+                                size_t workspace_bytes, void* stream) {
+  clear_error();
+  FTR_TRY(check_sizes(what, B >= 0 && T >= 0 && S1 >= 1 && C >= 0 && r >= 0));
+  if ((size_t)B * C == 0) return FTR_OK;
+  FTR_TRY(pointers_then_device(what, g_am_pruned && g_lm_pruned && ranges && d_am && d_lm));
+  if (!has_ws) return do_pruning_bwd(g_am_pruned, g_lm_pruned, ranges, d_am, d_lm, B, T, S1, C, r, stream_of(stream));
+  return do_pruning_bwd_ws(g_am_pruned, g_lm_pruned, ranges, d_am, d_lm, B, T, S1, C, r, workspace, workspace_bytes, stream_of(stream));
+}
+
+int ftr_do_pruning_bwd_f32(const float* g_am_pruned, const float* g_lm_pruned, const int32_t* ranges, float* d_am,
+                           float* d_lm, int B, int T, int S1, int C, int r, void* stream) {
+  return do_pruning_bwd_entry("do_pruning_bwd", g_am_pruned, g_lm_pruned, ranges, d_am, d_lm, B, T, S1, C, r, false, nullptr, 0, stream);
+}
+
 int ftr_do_pruning_bwd_ws_f32(const float* g_am_pruned, const float* g_lm_pruned, const int32_t* ranges, float* d_am,
                               float* d_lm, int B, int T, int S1, int C, int r, void* workspace,
                               size_t workspace_bytes, void* stream) {
-  clear_error();
-  FTR_REQUIRE(B >= 0 && T >= 0 && S1 >= 1 && C >= 0 && r >= 0, "do_pruning_bwd_ws: bad sizes");
-  if ((size_t)B * C == 0) return FTR_OK;
-  FTR_REQUIRE(g_am_pruned && g_lm_pruned && ranges && d_am && d_lm, "do_pruning_bwd_ws: null pointer");
-  int rc = device_ok();
-  if (rc != FTR_OK) return rc;
-  return do_pruning_bwd_ws(g_am_pruned, g_lm_pruned, ranges, d_am, d_lm, B, T, S1, C, r, workspace, workspace_bytes, reinterpret_cast<hipStream_t>(stream));
+  return do_pruning_bwd_entry("do_pruning_bwd_ws", g_am_pruned, g_lm_pruned, ranges, d_am, d_lm, B, T, S1, C, r, true, workspace, workspace_bytes, stream);
 }
 
 // the ordinary entry point and its HAT twin (hat = 1: blank-excluded normaliser, which needs C >= 2)
@@ -293,15 +335,11 @@ static int pruned_logprobs_fwd_entry(const float* logits, const int32_t* symbols
                                      int modified, int hat, void* stream) {
   const char* what = hat ? "hat_pruned_logprobs_fwd" : "pruned_logprobs_fwd";
   clear_error();
-  FTR_REQUIRE(B >= 0 && T >= 1 && S >= 1 && C >= 1 && r >= 1, "%s: bad sizes", what);
-  FTR_REQUIRE(!hat || C >= 2, "%s: C = %d, HAT needs a blank and at least one other symbol", what, C);
-  FTR_REQUIRE(termination_symbol >= 0 && termination_symbol < C, "%s: termination_symbol %d not in [0,%d)", what, termination_symbol, C);
-  FTR_REQUIRE(r <= S + 1, "%s: s_range %d > S+1 = %d", what, r, S + 1);
+  FTR_TRY(check_builder(what, B >= 0 && T >= 1 && S >= 1 && C >= 1 && r >= 1, termination_symbol, C, false, hat));
+  FTR_TRY(check_s_range(what, r, S));
   if (B == 0) return FTR_OK;
-  FTR_REQUIRE(logits && symbols && ranges && lse && px && py, "%s: null pointer", what);
-  int rc = device_ok();
-  if (rc != FTR_OK) return rc;
-  return pruned_logprobs_fwd(logits, symbols, ranges, boundary, termination_symbol, delay_penalty, lse, px, py, B, T, S, C, r, modified, hat, reinterpret_cast<hipStream_t>(stream));
+  FTR_TRY(pointers_then_device(what, logits && symbols && ranges && lse && px && py));
+  return pruned_logprobs_fwd(logits, symbols, ranges, boundary, termination_symbol, delay_penalty, lse, px, py, B, T, S, C, r, modified, hat, stream_of(stream));
 }
 
 int ftr_pruned_logprobs_fwd_f32(const float* logits, const int32_t* symbols, const int32_t* ranges,
@@ -322,24 +360,36 @@ int ftr_pruned_logprobs_bwd_f32(const float* logits, const int32_t* symbols, con
                                 const int32_t* boundary, int termination_symbol, const float* lse,
                                 const float* gpx, const float* gpy, const float* scale, float* glogits,
                                 int B, int T, int S, int C, int r, int modified, void* stream) {
+  const char* what = "pruned_logprobs_bwd";
   clear_error();
-  FTR_REQUIRE(B >= 0 && T >= 1 && S >= 1 && C >= 1 && r >= 1, "pruned_logprobs_bwd: bad sizes");
-  FTR_REQUIRE(termination_symbol >= 0 && termination_symbol < C, "pruned_logprobs_bwd: termination_symbol %d not in [0,%d)", termination_symbol, C);
+  FTR_TRY(check_builder(what, B >= 0 && T >= 1 && S >= 1 && C >= 1 && r >= 1, termination_symbol, C));
   if (B == 0) return FTR_OK;
-  FTR_REQUIRE(logits && symbols && ranges && lse && gpx && gpy && glogits, "pruned_logprobs_bwd: null pointer");
-  int rc = device_ok();
-  if (rc != FTR_OK) return rc;
-  return pruned_logprobs_bwd(logits, symbols, ranges, boundary, termination_symbol, lse, gpx, gpy, Scale{scale, 1, 1.0f}, glogits, B, T, S, C, r, modified, 0, reinterpret_cast<hipStream_t>(stream));
+  FTR_TRY(pointers_then_device(what, logits && symbols && ranges && lse && gpx && gpy && glogits));
+  return pruned_logprobs_bwd(logits, symbols, ranges, boundary, termination_symbol, lse, gpx, gpy, Scale{scale, 1, 1.0f}, glogits, B, T, S, C, r, modified, 0, stream_of(stream));
+}
+
+// rowmax_exp, _sum (rowsum) and _dot (dotvec, dot): one pass, the outputs the entry asks for
+static int rowmax_exp_entry(const char* what, const float* x, float* probs, float* rowmax, float* rowsum, const float* dotvec,
+                            float* dot, bool extras_there, long long rows, int C, void* stream) {
+  clear_error();
+  FTR_REQUIRE(rows >= 0 && C >= 0, "%s: negative size", what);
+  if (rows == 0 || C == 0) return FTR_OK;
+  FTR_TRY(pointers_then_device(what, x && probs && rowmax && extras_there));
+  return simple_rowmax_exp(x, probs, rowmax, rowsum, dotvec, dot, (size_t)rows, C, stream_of(stream));
 }
 
 int ftr_rowmax_exp_f32(const float* x, float* probs, float* rowmax, long long rows, int C, void* stream) {
-  clear_error();
-  FTR_REQUIRE(rows >= 0 && C >= 0, "rowmax_exp: negative size");
-  if (rows == 0 || C == 0) return FTR_OK;
-  FTR_REQUIRE(x && probs && rowmax, "rowmax_exp: null pointer");
-  int rc = device_ok();
-  if (rc != FTR_OK) return rc;
-  return simple_rowmax_exp(x, probs, rowmax, nullptr, nullptr, nullptr, (size_t)rows, C, reinterpret_cast<hipStream_t>(stream));
+  return rowmax_exp_entry("rowmax_exp", x, probs, rowmax, nullptr, nullptr, nullptr, true, rows, C, stream);
+}
+
+int ftr_rowmax_exp_sum_f32(const float* x, float* probs, float* rowmax, float* rowsum, long long rows, int C,
+                           void* stream) {
+  return rowmax_exp_entry("rowmax_exp_sum", x, probs, rowmax, rowsum, nullptr, nullptr, rowsum != nullptr, rows, C, stream);
+}
+
+int ftr_rowmax_exp_dot_f32(const float* x, float* probs, float* rowmax, const float* dotvec, float* dot, long long rows,
+                           int C, void* stream) {
+  return rowmax_exp_entry("rowmax_exp_dot", x, probs, rowmax, nullptr, dotvec, dot, dotvec && dot, rows, C, stream);
 }
 
 int ftr_rowmax_exp_pair_f32(const float* x1, float* probs1, float* rowmax1, long long rows1, const float* x2, float* probs2,
@@ -347,42 +397,16 @@ int ftr_rowmax_exp_pair_f32(const float* x1, float* probs1, float* rowmax1, long
   clear_error();
   FTR_REQUIRE(rows1 >= 0 && rows2 >= 0 && C >= 0, "rowmax_exp_pair: negative size");
   if (rows1 + rows2 == 0 || C == 0) return FTR_OK;
-  FTR_REQUIRE((rows1 == 0 || (x1 && probs1 && rowmax1)) && (rows2 == 0 || (x2 && probs2 && rowmax2)), "rowmax_exp_pair: null pointer");
-  int rc = device_ok();
-  if (rc != FTR_OK) return rc;
-  return simple_rowmax_exp_pair(x1, probs1, rowmax1, (size_t)rows1, x2, probs2, rowmax2, (size_t)rows2, C, reinterpret_cast<hipStream_t>(stream));
-}
-
-int ftr_rowmax_exp_sum_f32(const float* x, float* probs, float* rowmax, float* rowsum, long long rows, int C,
-                           void* stream) {
-  clear_error();
-  FTR_REQUIRE(rows >= 0 && C >= 0, "rowmax_exp_sum: negative size");
-  if (rows == 0 || C == 0) return FTR_OK;
-  FTR_REQUIRE(x && probs && rowmax && rowsum, "rowmax_exp_sum: null pointer");
-  int rc = device_ok();
-  if (rc != FTR_OK) return rc;
-  return simple_rowmax_exp(x, probs, rowmax, rowsum, nullptr, nullptr, (size_t)rows, C, reinterpret_cast<hipStream_t>(stream));
-}
-
-int ftr_rowmax_exp_dot_f32(const float* x, float* probs, float* rowmax, const float* dotvec, float* dot, long long rows,
-                           int C, void* stream) {
-  clear_error();
-  FTR_REQUIRE(rows >= 0 && C >= 0, "rowmax_exp_dot: negative size");
-  if (rows == 0 || C == 0) return FTR_OK;
-  FTR_REQUIRE(x && probs && rowmax && dotvec && dot, "rowmax_exp_dot: null pointer");
-  int rc = device_ok();
-  if (rc != FTR_OK) return rc;
-  return simple_rowmax_exp(x, probs, rowmax, nullptr, dotvec, dot, (size_t)rows, C, reinterpret_cast<hipStream_t>(stream));
+  FTR_TRY(pointers_then_device("rowmax_exp_pair", (rows1 == 0 || (x1 && probs1 && rowmax1)) && (rows2 == 0 || (x2 && probs2 && rowmax2))));
+  return simple_rowmax_exp_pair(x1, probs1, rowmax1, (size_t)rows1, x2, probs2, rowmax2, (size_t)rows2, C, stream_of(stream));
 }
 
 int ftr_rowdot_f32(const float* x, const float* v, float* dot, long long rows, int C, void* stream) {
   clear_error();
   FTR_REQUIRE(rows >= 0 && C >= 0, "rowdot: negative size");
   if (rows == 0) return FTR_OK;
-  FTR_REQUIRE(dot && ((x && v) || C == 0), "rowdot: null pointer");
-  int rc = device_ok();
-  if (rc != FTR_OK) return rc;
-  return simple_rowdot(x, v, dot, (size_t)rows, C, reinterpret_cast<hipStream_t>(stream));
+  FTR_TRY(pointers_then_device("rowdot", dot && ((x && v) || C == 0)));
+  return simple_rowdot(x, v, dot, (size_t)rows, C, stream_of(stream));
 }
 
 size_t ftr_colsum_weighted_workspace_floats(long long rows, int C) {
@@ -394,24 +418,29 @@ int ftr_colsum_weighted_f32(const float* x, const float* w, float* out, float* w
   clear_error();
   FTR_REQUIRE(rows >= 0 && C >= 0, "colsum_weighted: negative size");
   if (C == 0) return FTR_OK;
-  FTR_REQUIRE(out && ((x && w && workspace) || rows == 0), "colsum_weighted: null pointer");
-  int rc = device_ok();
-  if (rc != FTR_OK) return rc;
-  return simple_colsum_weighted(x, w, out, workspace, workspace_floats, (size_t)rows, C, reinterpret_cast<hipStream_t>(stream));
+  FTR_TRY(pointers_then_device("colsum_weighted", out && ((x && w && workspace) || rows == 0)));
+  return simple_colsum_weighted(x, w, out, workspace, workspace_floats, (size_t)rows, C, stream_of(stream));
+}
+
+// ---- the simple / smoothed builder.  The smoothed entries are the simple ones with three more inputs and three scales:
+// each pair shares a body, which takes the name, whether the smoothing inputs are required, and the constants to forward.
+static int simple_fwd_entry(const char* what, bool smoothed, const float* am, const float* lm, const int32_t* symbols,
+                            const float* prod, const float* am_max, const float* lm_max, const float* lmonly_norm,
+                            const float* amonly_norm, const float* unigram_log, const int32_t* boundary,
+                            int termination_symbol, double delay_penalty, float combined_scale, float lm_only_scale,
+                            float am_only_scale, float* px, float* py, int B, int T, int S, int C, int modified, void* stream) {
+  clear_error();
+  FTR_TRY(check_builder(what, B >= 0 && T >= 1 && S >= 0 && C >= 1, termination_symbol, C));
+  if (B == 0) return FTR_OK;
+  FTR_TRY(pointers_then_device(what, am && lm && prod && am_max && lm_max && (!smoothed || (lmonly_norm && amonly_norm && unigram_log)) && py && (symbols || S == 0) && (px || S == 0)));
+  return simple_logprobs_fwd(am, lm, symbols, prod, am_max, lm_max, boundary, termination_symbol, delay_penalty, lmonly_norm, amonly_norm, unigram_log, combined_scale, lm_only_scale, am_only_scale, px, py, B, T, S, C, modified, stream_of(stream));
 }
 
 int ftr_simple_logprobs_fwd_f32(const float* am, const float* lm, const int32_t* symbols, const float* prod,
                                 const float* am_max, const float* lm_max, const int32_t* boundary,
                                 int termination_symbol, double delay_penalty, float* px, float* py, int B, int T,
                                 int S, int C, int modified, void* stream) {
-  clear_error();
-  FTR_REQUIRE(B >= 0 && T >= 1 && S >= 0 && C >= 1, "simple_logprobs_fwd: bad sizes");
-  FTR_REQUIRE(termination_symbol >= 0 && termination_symbol < C, "simple_logprobs_fwd: termination_symbol %d not in [0,%d)", termination_symbol, C);
-  if (B == 0) return FTR_OK;
-  FTR_REQUIRE(am && lm && prod && am_max && lm_max && py && (symbols || S == 0) && (px || S == 0), "simple_logprobs_fwd: null pointer");
-  int rc = device_ok();
-  if (rc != FTR_OK) return rc;
-  return simple_logprobs_fwd(am, lm, symbols, prod, am_max, lm_max, boundary, termination_symbol, delay_penalty, nullptr, nullptr, nullptr, 1.0f, 0.0f, 0.0f, px, py, B, T, S, C, modified, reinterpret_cast<hipStream_t>(stream));
+  return simple_fwd_entry("simple_logprobs_fwd", false, am, lm, symbols, prod, am_max, lm_max, nullptr, nullptr, nullptr, boundary, termination_symbol, delay_penalty, 1.0f, 0.0f, 0.0f, px, py, B, T, S, C, modified, stream);
 }
 
 int ftr_smoothed_logprobs_fwd_f32(const float* am, const float* lm, const int32_t* symbols, const float* prod,
@@ -420,50 +449,71 @@ int ftr_smoothed_logprobs_fwd_f32(const float* am, const float* lm, const int32_
                                   int termination_symbol, float combined_scale, float lm_only_scale,
                                   float am_only_scale, float* px, float* py, int B, int T, int S, int C,
                                   int modified, void* stream) {
+  return simple_fwd_entry("smoothed_logprobs_fwd", true, am, lm, symbols, prod, am_max, lm_max, lmonly_norm, amonly_norm, unigram_log, boundary, termination_symbol, 0.0, combined_scale, lm_only_scale, am_only_scale, px, py, B, T, S, C, modified, stream);
+}
+
+int ftr_smoothed_logprobs_fwd_pen_f32(const float* am, const float* lm, const int32_t* symbols, const float* prod,
+                                      const float* am_max, const float* lm_max, const float* lmonly_norm,
+                                      const float* amonly_norm, const float* unigram_log, const int32_t* boundary,
+                                      int termination_symbol, double delay_penalty, float combined_scale,
+                                      float lm_only_scale, float am_only_scale, float* px, float* py, int B, int T,
+                                      int S, int C, int modified, void* stream) {
+  return simple_fwd_entry("smoothed_logprobs_fwd_pen", true, am, lm, symbols, prod, am_max, lm_max, lmonly_norm, amonly_norm, unigram_log, boundary, termination_symbol, delay_penalty, combined_scale, lm_only_scale, am_only_scale, px, py, B, T, S, C, modified, stream);
+}
+
+// the entries without a scale pass {NULL, stride 0, 1.0}, which passes the stride check and multiplies by one
+static int bwd_w_entry(const char* what, const float* gpx, const float* gpy, const float* scale, int scale_stride,
+                       float scale_mul, const float* prod, const int32_t* boundary, float combined_scale, float* W,
+                       float* rsx, float* rsy, int B, int T, int S, int modified, void* stream) {
   clear_error();
-  FTR_REQUIRE(B >= 0 && T >= 1 && S >= 0 && C >= 1, "smoothed_logprobs_fwd: bad sizes");
-  FTR_REQUIRE(termination_symbol >= 0 && termination_symbol < C, "smoothed_logprobs_fwd: termination_symbol %d not in [0,%d)", termination_symbol, C);
+  FTR_TRY(check_sizes(what, B >= 0 && T >= 1 && S >= 0));
+  FTR_TRY(check_scale_stride(what, scale_stride));
   if (B == 0) return FTR_OK;
-  FTR_REQUIRE(am && lm && prod && am_max && lm_max && lmonly_norm && amonly_norm && unigram_log && py && (symbols || S == 0) && (px || S == 0), "smoothed_logprobs_fwd: null pointer");
-  int rc = device_ok();
-  if (rc != FTR_OK) return rc;
-  return simple_logprobs_fwd(am, lm, symbols, prod, am_max, lm_max, boundary, termination_symbol, 0.0, lmonly_norm, amonly_norm, unigram_log, combined_scale, lm_only_scale, am_only_scale, px, py, B, T, S, C, modified, reinterpret_cast<hipStream_t>(stream));
+  FTR_TRY(pointers_then_device(what, gpy && prod && W && rsx && rsy && (gpx || S == 0)));
+  return simple_logprobs_bwd_w(gpx, gpy, Scale{scale, scale_stride, scale_mul}, prod, boundary, W, rsx, rsy, combined_scale, B, T, S, modified, stream_of(stream));
 }
 
 int ftr_simple_logprobs_bwd_w_f32(const float* gpx, const float* gpy, const float* prod, const int32_t* boundary,
                                   float* W, float* rsx, float* rsy, int B, int T, int S, int modified, void* stream) {
-  clear_error();
-  FTR_REQUIRE(B >= 0 && T >= 1 && S >= 0, "simple_logprobs_bwd_w: bad sizes");
-  if (B == 0) return FTR_OK;
-  FTR_REQUIRE(gpy && prod && W && rsx && rsy && (gpx || S == 0), "simple_logprobs_bwd_w: null pointer");
-  int rc = device_ok();
-  if (rc != FTR_OK) return rc;
-  return simple_logprobs_bwd_w(gpx, gpy, scale_none(), prod, boundary, W, rsx, rsy, 1.0f, B, T, S, modified, reinterpret_cast<hipStream_t>(stream));
+  return bwd_w_entry("simple_logprobs_bwd_w", gpx, gpy, nullptr, 0, 1.0f, prod, boundary, 1.0f, W, rsx, rsy, B, T, S, modified, stream);
 }
 
 int ftr_smoothed_logprobs_bwd_w_f32(const float* gpx, const float* gpy, const float* prod, const int32_t* boundary,
                                     float combined_scale, float* W, float* rsx, float* rsy, int B, int T, int S,
                                     int modified, void* stream) {
+  return bwd_w_entry("smoothed_logprobs_bwd_w", gpx, gpy, nullptr, 0, 1.0f, prod, boundary, combined_scale, W, rsx, rsy, B, T, S, modified, stream);
+}
+
+int ftr_simple_logprobs_bwd_w_scaled_f32(const float* gpx, const float* gpy, const float* scale, int scale_stride,
+                                         float scale_mul, const float* prod, const int32_t* boundary, float* W,
+                                         float* rsx, float* rsy, int B, int T, int S, int modified, void* stream) {
+  return bwd_w_entry("simple_logprobs_bwd_w_scaled", gpx, gpy, scale, scale_stride, scale_mul, prod, boundary, 1.0f, W, rsx, rsy, B, T, S, modified, stream);
+}
+
+int ftr_smoothed_logprobs_bwd_w_scaled_f32(const float* gpx, const float* gpy, const float* scale, int scale_stride,
+                                           float scale_mul, const float* prod, const int32_t* boundary,
+                                           float combined_scale, float* W, float* rsx, float* rsy, int B, int T, int S,
+                                           int modified, void* stream) {
+  return bwd_w_entry("smoothed_logprobs_bwd_w_scaled", gpx, gpy, scale, scale_stride, scale_mul, prod, boundary, combined_scale, W, rsx, rsy, B, T, S, modified, stream);
+}
+
+static int bwd_am_entry(const char* what, bool smoothed, const float* gpx, const float* gpy, const float* scale,
+                        int scale_stride, float scale_mul, const float* damp, const float* am_probs,
+                        const int32_t* symbols, const int32_t* boundary, int termination_symbol, float direct_scale,
+                        const float* unigram, const float* am_dot, float am_only_scale, float* R, float* d_am, int B,
+                        int T, int S, int C, int modified, void* stream) {
   clear_error();
-  FTR_REQUIRE(B >= 0 && T >= 1 && S >= 0, "smoothed_logprobs_bwd_w: bad sizes");
+  FTR_TRY(check_builder(what, B >= 0 && T >= 1 && S >= 0 && C >= 1, termination_symbol, C, true));
+  FTR_TRY(check_scale_stride(what, scale_stride));
   if (B == 0) return FTR_OK;
-  FTR_REQUIRE(gpy && prod && W && rsx && rsy && (gpx || S == 0), "smoothed_logprobs_bwd_w: null pointer");
-  int rc = device_ok();
-  if (rc != FTR_OK) return rc;
-  return simple_logprobs_bwd_w(gpx, gpy, scale_none(), prod, boundary, W, rsx, rsy, combined_scale, B, T, S, modified, reinterpret_cast<hipStream_t>(stream));
+  FTR_TRY(pointers_then_device(what, gpy && damp && am_probs && d_am && (!smoothed || (unigram && am_dot && R)) && (gpx || S == 0) && (symbols || S == 0)));
+  return simple_logprobs_bwd_am(gpx, gpy, Scale{scale, scale_stride, scale_mul}, damp, am_probs, symbols, boundary, termination_symbol, direct_scale, unigram, am_dot, am_only_scale, R, d_am, B, T, S, C, modified, stream_of(stream));
 }
 
 int ftr_simple_logprobs_bwd_am_f32(const float* gpx, const float* gpy, const float* damp, const float* am_probs,
                                    const int32_t* symbols, const int32_t* boundary, int termination_symbol,
                                    float* d_am, int B, int T, int S, int C, int modified, void* stream) {
-  clear_error();
-  FTR_REQUIRE(B >= 0 && T >= 1 && S >= 0 && C >= 1, "simple_logprobs_bwd_am: bad sizes");
-  FTR_REQUIRE(termination_symbol >= 0 && termination_symbol < C, "simple_logprobs_bwd_am: bad termination_symbol");
-  if (B == 0) return FTR_OK;
-  FTR_REQUIRE(gpy && damp && am_probs && d_am && (gpx || S == 0) && (symbols || S == 0), "simple_logprobs_bwd_am: null pointer");
-  int rc = device_ok();
-  if (rc != FTR_OK) return rc;
-  return simple_logprobs_bwd_am(gpx, gpy, scale_none(), damp, am_probs, symbols, boundary, termination_symbol, 1.0f, nullptr, nullptr, 0.0f, nullptr, d_am, B, T, S, C, modified, reinterpret_cast<hipStream_t>(stream));
+  return bwd_am_entry("simple_logprobs_bwd_am", false, gpx, gpy, nullptr, 0, 1.0f, damp, am_probs, symbols, boundary, termination_symbol, 1.0f, nullptr, nullptr, 0.0f, nullptr, d_am, B, T, S, C, modified, stream);
 }
 
 int ftr_smoothed_logprobs_bwd_am_f32(const float* gpx, const float* gpy, const float* damp, const float* am_probs,
@@ -471,50 +521,54 @@ int ftr_smoothed_logprobs_bwd_am_f32(const float* gpx, const float* gpy, const f
                                      float direct_scale, const float* unigram, const float* am_dot,
                                      float am_only_scale, float* R, float* d_am, int B, int T, int S, int C,
                                      int modified, void* stream) {
+  return bwd_am_entry("smoothed_logprobs_bwd_am", true, gpx, gpy, nullptr, 0, 1.0f, damp, am_probs, symbols, boundary, termination_symbol, direct_scale, unigram, am_dot, am_only_scale, R, d_am, B, T, S, C, modified, stream);
+}
+
+int ftr_simple_logprobs_bwd_am_scaled_f32(const float* gpx, const float* gpy, const float* scale, int scale_stride,
+                                          float scale_mul, const float* damp, const float* am_probs,
+                                          const int32_t* symbols, const int32_t* boundary, int termination_symbol,
+                                          float* d_am, int B, int T, int S, int C, int modified, void* stream) {
+  return bwd_am_entry("simple_logprobs_bwd_am_scaled", false, gpx, gpy, scale, scale_stride, scale_mul, damp, am_probs, symbols, boundary, termination_symbol, 1.0f, nullptr, nullptr, 0.0f, nullptr, d_am, B, T, S, C, modified, stream);
+}
+
+int ftr_smoothed_logprobs_bwd_am_scaled_f32(const float* gpx, const float* gpy, const float* scale, int scale_stride,
+                                            float scale_mul, const float* damp, const float* am_probs,
+                                            const int32_t* symbols, const int32_t* boundary, int termination_symbol,
+                                            float direct_scale, const float* unigram, const float* am_dot,
+                                            float am_only_scale, float* R, float* d_am, int B, int T, int S, int C,
+                                            int modified, void* stream) {
+  return bwd_am_entry("smoothed_logprobs_bwd_am_scaled", true, gpx, gpy, scale, scale_stride, scale_mul, damp, am_probs, symbols, boundary, termination_symbol, direct_scale, unigram, am_dot, am_only_scale, R, d_am, B, T, S, C, modified, stream);
+}
+
+static int bwd_lm_entry(const char* what, bool smoothed, const float* dlmp, const float* lm_probs, const int32_t* symbols,
+                        const float* rsx, const float* rsy, int termination_symbol, float direct_scale,
+                        const float* row_term, const float* inv_rowsum, const float* unigram_grad, float* d_lm, int B,
+                        int S, int C, void* stream) {
   clear_error();
-  FTR_REQUIRE(B >= 0 && T >= 1 && S >= 0 && C >= 1, "smoothed_logprobs_bwd_am: bad sizes");
-  FTR_REQUIRE(termination_symbol >= 0 && termination_symbol < C, "smoothed_logprobs_bwd_am: bad termination_symbol");
+  FTR_TRY(check_builder(what, B >= 0 && S >= 0 && C >= 1, termination_symbol, C, true));
   if (B == 0) return FTR_OK;
-  FTR_REQUIRE(gpy && damp && am_probs && d_am && unigram && am_dot && R && (gpx || S == 0) && (symbols || S == 0), "smoothed_logprobs_bwd_am: null pointer");
-  int rc = device_ok();
-  if (rc != FTR_OK) return rc;
-  return simple_logprobs_bwd_am(gpx, gpy, scale_none(), damp, am_probs, symbols, boundary, termination_symbol, direct_scale, unigram, am_dot, am_only_scale, R, d_am, B, T, S, C, modified, reinterpret_cast<hipStream_t>(stream));
+  FTR_TRY(pointers_then_device(what, dlmp && lm_probs && rsx && rsy && d_lm && (!smoothed || (row_term && inv_rowsum && unigram_grad)) && (symbols || S == 0)));
+  return simple_logprobs_bwd_lm(dlmp, lm_probs, symbols, rsx, rsy, termination_symbol, direct_scale, row_term, inv_rowsum, unigram_grad, d_lm, B, S, C, stream_of(stream));
 }
 
 int ftr_simple_logprobs_bwd_lm_f32(const float* dlmp, const float* lm_probs, const int32_t* symbols,
                                    const float* rsx, const float* rsy, int termination_symbol, float* d_lm, int B,
                                    int S, int C, void* stream) {
-  clear_error();
-  FTR_REQUIRE(B >= 0 && S >= 0 && C >= 1, "simple_logprobs_bwd_lm: bad sizes");
-  FTR_REQUIRE(termination_symbol >= 0 && termination_symbol < C, "simple_logprobs_bwd_lm: bad termination_symbol");
-  if (B == 0) return FTR_OK;
-  FTR_REQUIRE(dlmp && lm_probs && rsx && rsy && d_lm && (symbols || S == 0), "simple_logprobs_bwd_lm: null pointer");
-  int rc = device_ok();
-  if (rc != FTR_OK) return rc;
-  return simple_logprobs_bwd_lm(dlmp, lm_probs, symbols, rsx, rsy, termination_symbol, 1.0f, nullptr, nullptr, nullptr, d_lm, B, S, C, reinterpret_cast<hipStream_t>(stream));
+  return bwd_lm_entry("simple_logprobs_bwd_lm", false, dlmp, lm_probs, symbols, rsx, rsy, termination_symbol, 1.0f, nullptr, nullptr, nullptr, d_lm, B, S, C, stream);
 }
 
 int ftr_smoothed_logprobs_bwd_lm_f32(const float* dlmp, const float* lm_probs, const int32_t* symbols,
                                      const float* rsx, const float* rsy, int termination_symbol, float direct_scale,
                                      const float* row_term, const float* inv_rowsum, const float* unigram_grad,
                                      float* d_lm, int B, int S, int C, void* stream) {
-  clear_error();
-  FTR_REQUIRE(B >= 0 && S >= 0 && C >= 1, "smoothed_logprobs_bwd_lm: bad sizes");
-  FTR_REQUIRE(termination_symbol >= 0 && termination_symbol < C, "smoothed_logprobs_bwd_lm: bad termination_symbol");
-  if (B == 0) return FTR_OK;
-  FTR_REQUIRE(dlmp && lm_probs && rsx && rsy && d_lm && row_term && inv_rowsum && unigram_grad && (symbols || S == 0), "smoothed_logprobs_bwd_lm: null pointer");
-  int rc = device_ok();
-  if (rc != FTR_OK) return rc;
-  return simple_logprobs_bwd_lm(dlmp, lm_probs, symbols, rsx, rsy, termination_symbol, direct_scale, row_term, inv_rowsum, unigram_grad, d_lm, B, S, C, reinterpret_cast<hipStream_t>(stream));
+  return bwd_lm_entry("smoothed_logprobs_bwd_lm", true, dlmp, lm_probs, symbols, rsx, rsy, termination_symbol, direct_scale, row_term, inv_rowsum, unigram_grad, d_lm, B, S, C, stream);
 }
 
 int ftr_negated_reduce_f32(const float* ans, int B, int reduction, float* out, void* stream) {
   clear_error();
   FTR_REQUIRE(B >= 1 && reduction >= 0 && reduction <= 2, "negated_reduce: bad arguments B=%d reduction=%d", B, reduction);
-  FTR_REQUIRE(ans && out, "negated_reduce: null pointer");
-  int rc = device_ok();
-  if (rc != FTR_OK) return rc;
-  return negated_reduce(ans, B, reduction, out, reinterpret_cast<hipStream_t>(stream));
+  FTR_TRY(pointers_then_device("negated_reduce", ans && out));
+  return negated_reduce(ans, B, reduction, out, stream_of(stream));
 }
 
 static int pruned_logprobs_bwd_scaled_entry(const float* logits, const int32_t* symbols, const int32_t* ranges,
@@ -524,15 +578,11 @@ static int pruned_logprobs_bwd_scaled_entry(const float* logits, const int32_t* 
                                             int modified, int hat, void* stream) {
   const char* what = hat ? "hat_pruned_logprobs_bwd_scaled" : "pruned_logprobs_bwd_scaled";
   clear_error();
-  FTR_REQUIRE(B >= 0 && T >= 1 && S >= 0 && C >= 1 && r >= 1, "%s: bad sizes", what);
-  FTR_REQUIRE(!hat || C >= 2, "%s: C = %d, HAT needs a blank and at least one other symbol", what, C);
-  FTR_REQUIRE(termination_symbol >= 0 && termination_symbol < C, "%s: bad termination_symbol", what);
-  FTR_REQUIRE(scale_stride == 0 || scale_stride == 1, "%s: scale_stride must be 0 or 1", what);
+  FTR_TRY(check_builder(what, B >= 0 && T >= 1 && S >= 0 && C >= 1 && r >= 1, termination_symbol, C, true, hat));
+  FTR_TRY(check_scale_stride(what, scale_stride));
   if (B == 0) return FTR_OK;
-  FTR_REQUIRE(logits && ranges && lse && gpy && glogits && (symbols || S == 0) && (gpx || S == 0), "%s: null pointer", what);
-  int rc = device_ok();
-  if (rc != FTR_OK) return rc;
-  return pruned_logprobs_bwd(logits, symbols, ranges, boundary, termination_symbol, lse, gpx, gpy, Scale{scale, scale_stride, scale_mul}, glogits, B, T, S, C, r, modified, hat, reinterpret_cast<hipStream_t>(stream));
+  FTR_TRY(pointers_then_device(what, logits && ranges && lse && gpy && glogits && (symbols || S == 0) && (gpx || S == 0)));
+  return pruned_logprobs_bwd(logits, symbols, ranges, boundary, termination_symbol, lse, gpx, gpy, Scale{scale, scale_stride, scale_mul}, glogits, B, T, S, C, r, modified, hat, stream_of(stream));
 }
 
 int ftr_pruned_logprobs_bwd_scaled_f32(const float* logits, const int32_t* symbols, const int32_t* ranges,
@@ -549,50 +599,6 @@ int ftr_hat_pruned_logprobs_bwd_scaled_f32(const float* logits, const int32_t* s
                                            float scale_mul, float* glogits, int B, int T, int S, int C, int r,
                                            int modified, void* stream) {
   return pruned_logprobs_bwd_scaled_entry(logits, symbols, ranges, boundary, termination_symbol, lse, gpx, gpy, scale, scale_stride, scale_mul, glogits, B, T, S, C, r, modified, 1, stream);
-}
-
-int ftr_simple_logprobs_bwd_w_scaled_f32(const float* gpx, const float* gpy, const float* scale, int scale_stride,
-                                         float scale_mul, const float* prod, const int32_t* boundary, float* W,
-                                         float* rsx, float* rsy, int B, int T, int S, int modified, void* stream) {
-  clear_error();
-  FTR_REQUIRE(B >= 0 && T >= 1 && S >= 0, "simple_logprobs_bwd_w_scaled: bad sizes");
-  FTR_REQUIRE(scale_stride == 0 || scale_stride == 1, "simple_logprobs_bwd_w_scaled: scale_stride must be 0 or 1");
-  if (B == 0) return FTR_OK;
-  FTR_REQUIRE(gpy && prod && W && rsx && rsy && (gpx || S == 0), "simple_logprobs_bwd_w_scaled: null pointer");
-  int rc = device_ok();
-  if (rc != FTR_OK) return rc;
-  return simple_logprobs_bwd_w(gpx, gpy, Scale{scale, scale_stride, scale_mul}, prod, boundary, W, rsx, rsy, 1.0f, B, T, S, modified, reinterpret_cast<hipStream_t>(stream));
-}
-
-int ftr_simple_logprobs_bwd_am_scaled_f32(const float* gpx, const float* gpy, const float* scale, int scale_stride,
-                                          float scale_mul, const float* damp, const float* am_probs,
-                                          const int32_t* symbols, const int32_t* boundary, int termination_symbol,
-                                          float* d_am, int B, int T, int S, int C, int modified, void* stream) {
-  clear_error();
-  FTR_REQUIRE(B >= 0 && T >= 1 && S >= 0 && C >= 1, "simple_logprobs_bwd_am_scaled: bad sizes");
-  FTR_REQUIRE(termination_symbol >= 0 && termination_symbol < C, "simple_logprobs_bwd_am_scaled: bad termination_symbol");
-  FTR_REQUIRE(scale_stride == 0 || scale_stride == 1, "simple_logprobs_bwd_am_scaled: scale_stride must be 0 or 1");
-  if (B == 0) return FTR_OK;
-  FTR_REQUIRE(gpy && damp && am_probs && d_am && (gpx || S == 0) && (symbols || S == 0), "simple_logprobs_bwd_am_scaled: null pointer");
-  int rc = device_ok();
-  if (rc != FTR_OK) return rc;
-  return simple_logprobs_bwd_am(gpx, gpy, Scale{scale, scale_stride, scale_mul}, damp, am_probs, symbols, boundary, termination_symbol, 1.0f, nullptr, nullptr, 0.0f, nullptr, d_am, B, T, S, C, modified, reinterpret_cast<hipStream_t>(stream));
-}
-
-int ftr_smoothed_logprobs_fwd_pen_f32(const float* am, const float* lm, const int32_t* symbols, const float* prod,
-                                      const float* am_max, const float* lm_max, const float* lmonly_norm,
-                                      const float* amonly_norm, const float* unigram_log, const int32_t* boundary,
-                                      int termination_symbol, double delay_penalty, float combined_scale,
-                                      float lm_only_scale, float am_only_scale, float* px, float* py, int B, int T,
-                                      int S, int C, int modified, void* stream) {
-  clear_error();
-  FTR_REQUIRE(B >= 0 && T >= 1 && S >= 0 && C >= 1, "smoothed_logprobs_fwd_pen: bad sizes");
-  FTR_REQUIRE(termination_symbol >= 0 && termination_symbol < C, "smoothed_logprobs_fwd_pen: termination_symbol %d not in [0,%d)", termination_symbol, C);
-  if (B == 0) return FTR_OK;
-  FTR_REQUIRE(am && lm && prod && am_max && lm_max && lmonly_norm && amonly_norm && unigram_log && py && (symbols || S == 0) && (px || S == 0), "smoothed_logprobs_fwd_pen: null pointer");
-  int rc = device_ok();
-  if (rc != FTR_OK) return rc;
-  return simple_logprobs_fwd(am, lm, symbols, prod, am_max, lm_max, boundary, termination_symbol, delay_penalty, lmonly_norm, amonly_norm, unigram_log, combined_scale, lm_only_scale, am_only_scale, px, py, B, T, S, C, modified, reinterpret_cast<hipStream_t>(stream));
 }
 
 int ftr_simple_logprobs_fused_supported(int C) { return simple_fused_supported(C); }
@@ -613,18 +619,24 @@ int ftr_normalizer_gemm_set_choice(int kind, int B, int T, int S1, int C, int so
   return normalizer_gemm_set_choice(kind, B, T, S1, C, solution);
 }
 
+static int fused_fwd_entry(const char* what, bool smoothed, const float* am, const float* lm, const int32_t* symbols,
+                           const float* am_probs, const float* lm_probs, const float* am_max, const float* lm_max,
+                           const float* lmonly_norm, const float* amonly_norm, const float* unigram_log,
+                           const int32_t* boundary, int termination_symbol, double delay_penalty, float combined_scale,
+                           float lm_only_scale, float am_only_scale, float* px, float* py, float* prod, int B, int T,
+                           int S, int C, int modified, void* stream) {
+  clear_error();
+  FTR_TRY(check_builder(what, B >= 0 && T >= 1 && S >= 0 && C >= 1, termination_symbol, C));
+  if (B == 0) return FTR_OK;
+  FTR_TRY(pointers_then_device(what, am && lm && am_probs && lm_probs && am_max && lm_max && (!smoothed || (lmonly_norm && amonly_norm && unigram_log)) && py && (symbols || S == 0) && (px || S == 0)));
+  return simple_fused_fwd(am, lm, symbols, am_probs, lm_probs, am_max, lm_max, boundary, termination_symbol, delay_penalty, lmonly_norm, amonly_norm, unigram_log, combined_scale, lm_only_scale, am_only_scale, px, py, prod, B, T, S, C, modified, stream_of(stream));
+}
+
 int ftr_simple_logprobs_fused_fwd_f32(const float* am, const float* lm, const int32_t* symbols, const float* am_probs,
                                       const float* lm_probs, const float* am_max, const float* lm_max,
                                       const int32_t* boundary, int termination_symbol, double delay_penalty, float* px,
                                       float* py, float* prod, int B, int T, int S, int C, int modified, void* stream) {
-  clear_error();
-  FTR_REQUIRE(B >= 0 && T >= 1 && S >= 0 && C >= 1, "simple_logprobs_fused_fwd: bad sizes");
-  FTR_REQUIRE(termination_symbol >= 0 && termination_symbol < C, "simple_logprobs_fused_fwd: termination_symbol %d not in [0,%d)", termination_symbol, C);
-  if (B == 0) return FTR_OK;
-  FTR_REQUIRE(am && lm && am_probs && lm_probs && am_max && lm_max && py && (symbols || S == 0) && (px || S == 0), "simple_logprobs_fused_fwd: null pointer");
-  int rc = device_ok();
-  if (rc != FTR_OK) return rc;
-  return simple_fused_fwd(am, lm, symbols, am_probs, lm_probs, am_max, lm_max, boundary, termination_symbol, delay_penalty, nullptr, nullptr, nullptr, 1.0f, 0.0f, 0.0f, px, py, prod, B, T, S, C, modified, reinterpret_cast<hipStream_t>(stream));
+  return fused_fwd_entry("simple_logprobs_fused_fwd", false, am, lm, symbols, am_probs, lm_probs, am_max, lm_max, nullptr, nullptr, nullptr, boundary, termination_symbol, delay_penalty, 1.0f, 0.0f, 0.0f, px, py, prod, B, T, S, C, modified, stream);
 }
 
 int ftr_smoothed_logprobs_fused_fwd_f32(const float* am, const float* lm, const int32_t* symbols, const float* am_probs,
@@ -633,29 +645,28 @@ int ftr_smoothed_logprobs_fused_fwd_f32(const float* am, const float* lm, const 
                                         const int32_t* boundary, int termination_symbol, double delay_penalty,
                                         float combined_scale, float lm_only_scale, float am_only_scale, float* px,
                                         float* py, float* prod, int B, int T, int S, int C, int modified, void* stream) {
+  return fused_fwd_entry("smoothed_logprobs_fused_fwd", true, am, lm, symbols, am_probs, lm_probs, am_max, lm_max, lmonly_norm, amonly_norm, unigram_log, boundary, termination_symbol, delay_penalty, combined_scale, lm_only_scale, am_only_scale, px, py, prod, B, T, S, C, modified, stream);
+}
+
+static int fused_bwd_am_entry(const char* what, bool smoothed, const float* gpx, const float* gpy, const float* scale,
+                              int scale_stride, float scale_mul, const float* prod, const float* lm_probs,
+                              const float* am_probs, const int32_t* symbols, const int32_t* boundary,
+                              int termination_symbol, float combined_scale, float direct_scale, const float* unigram,
+                              const float* am_dot, float am_only_scale, float* R, float* d_am, int B, int T, int S, int C,
+                              int modified, void* stream) {
   clear_error();
-  FTR_REQUIRE(B >= 0 && T >= 1 && S >= 0 && C >= 1, "smoothed_logprobs_fused_fwd: bad sizes");
-  FTR_REQUIRE(termination_symbol >= 0 && termination_symbol < C, "smoothed_logprobs_fused_fwd: termination_symbol %d not in [0,%d)", termination_symbol, C);
+  FTR_TRY(check_builder(what, B >= 0 && T >= 1 && S >= 0 && C >= 1, termination_symbol, C, true));
+  FTR_TRY(check_scale_stride(what, scale_stride));
   if (B == 0) return FTR_OK;
-  FTR_REQUIRE(am && lm && am_probs && lm_probs && am_max && lm_max && lmonly_norm && amonly_norm && unigram_log && py && (symbols || S == 0) && (px || S == 0), "smoothed_logprobs_fused_fwd: null pointer");
-  int rc = device_ok();
-  if (rc != FTR_OK) return rc;
-  return simple_fused_fwd(am, lm, symbols, am_probs, lm_probs, am_max, lm_max, boundary, termination_symbol, delay_penalty, lmonly_norm, amonly_norm, unigram_log, combined_scale, lm_only_scale, am_only_scale, px, py, prod, B, T, S, C, modified, reinterpret_cast<hipStream_t>(stream));
+  FTR_TRY(pointers_then_device(what, gpy && prod && lm_probs && am_probs && d_am && (!smoothed || (unigram && am_dot && R)) && (gpx || S == 0) && (symbols || S == 0)));
+  return simple_fused_bwd_am(gpx, gpy, Scale{scale, scale_stride, scale_mul}, prod, lm_probs, am_probs, symbols, boundary, termination_symbol, combined_scale, direct_scale, unigram, am_dot, am_only_scale, R, d_am, B, T, S, C, modified, stream_of(stream));
 }
 
 int ftr_simple_logprobs_fused_bwd_am_f32(const float* gpx, const float* gpy, const float* scale, int scale_stride,
                                          float scale_mul, const float* prod, const float* lm_probs, const float* am_probs,
                                          const int32_t* symbols, const int32_t* boundary, int termination_symbol,
                                          float* d_am, int B, int T, int S, int C, int modified, void* stream) {
-  clear_error();
-  FTR_REQUIRE(B >= 0 && T >= 1 && S >= 0 && C >= 1, "simple_logprobs_fused_bwd_am: bad sizes");
-  FTR_REQUIRE(termination_symbol >= 0 && termination_symbol < C, "simple_logprobs_fused_bwd_am: bad termination_symbol");
-  FTR_REQUIRE(scale_stride == 0 || scale_stride == 1, "simple_logprobs_fused_bwd_am: scale_stride must be 0 or 1");
-  if (B == 0) return FTR_OK;
-  FTR_REQUIRE(gpy && prod && lm_probs && am_probs && d_am && (gpx || S == 0) && (symbols || S == 0), "simple_logprobs_fused_bwd_am: null pointer");
-  int rc = device_ok();
-  if (rc != FTR_OK) return rc;
-  return simple_fused_bwd_am(gpx, gpy, Scale{scale, scale_stride, scale_mul}, prod, lm_probs, am_probs, symbols, boundary, termination_symbol, 1.0f, 1.0f, nullptr, nullptr, 0.0f, nullptr, d_am, B, T, S, C, modified, reinterpret_cast<hipStream_t>(stream));
+  return fused_bwd_am_entry("simple_logprobs_fused_bwd_am", false, gpx, gpy, scale, scale_stride, scale_mul, prod, lm_probs, am_probs, symbols, boundary, termination_symbol, 1.0f, 1.0f, nullptr, nullptr, 0.0f, nullptr, d_am, B, T, S, C, modified, stream);
 }
 
 int ftr_smoothed_logprobs_fused_bwd_am_f32(const float* gpx, const float* gpy, const float* scale, int scale_stride,
@@ -664,46 +675,7 @@ int ftr_smoothed_logprobs_fused_bwd_am_f32(const float* gpx, const float* gpy, c
                                            int termination_symbol, float combined_scale, float direct_scale,
                                            const float* unigram, const float* am_dot, float am_only_scale, float* R,
                                            float* d_am, int B, int T, int S, int C, int modified, void* stream) {
-  clear_error();
-  FTR_REQUIRE(B >= 0 && T >= 1 && S >= 0 && C >= 1, "smoothed_logprobs_fused_bwd_am: bad sizes");
-  FTR_REQUIRE(termination_symbol >= 0 && termination_symbol < C, "smoothed_logprobs_fused_bwd_am: bad termination_symbol");
-  FTR_REQUIRE(scale_stride == 0 || scale_stride == 1, "smoothed_logprobs_fused_bwd_am: scale_stride must be 0 or 1");
-  if (B == 0) return FTR_OK;
-  FTR_REQUIRE(gpy && prod && lm_probs && am_probs && d_am && unigram && am_dot && R && (gpx || S == 0) && (symbols || S == 0), "smoothed_logprobs_fused_bwd_am: null pointer");
-  int rc = device_ok();
-  if (rc != FTR_OK) return rc;
-  return simple_fused_bwd_am(gpx, gpy, Scale{scale, scale_stride, scale_mul}, prod, lm_probs, am_probs, symbols, boundary, termination_symbol, combined_scale, direct_scale, unigram, am_dot, am_only_scale, R, d_am, B, T, S, C, modified, reinterpret_cast<hipStream_t>(stream));
-}
-
-int ftr_smoothed_logprobs_bwd_w_scaled_f32(const float* gpx, const float* gpy, const float* scale, int scale_stride,
-                                           float scale_mul, const float* prod, const int32_t* boundary,
-                                           float combined_scale, float* W, float* rsx, float* rsy, int B, int T, int S,
-                                           int modified, void* stream) {
-  clear_error();
-  FTR_REQUIRE(B >= 0 && T >= 1 && S >= 0, "smoothed_logprobs_bwd_w_scaled: bad sizes");
-  FTR_REQUIRE(scale_stride == 0 || scale_stride == 1, "smoothed_logprobs_bwd_w_scaled: scale_stride must be 0 or 1");
-  if (B == 0) return FTR_OK;
-  FTR_REQUIRE(gpy && prod && W && rsx && rsy && (gpx || S == 0), "smoothed_logprobs_bwd_w_scaled: null pointer");
-  int rc = device_ok();
-  if (rc != FTR_OK) return rc;
-  return simple_logprobs_bwd_w(gpx, gpy, Scale{scale, scale_stride, scale_mul}, prod, boundary, W, rsx, rsy, combined_scale, B, T, S, modified, reinterpret_cast<hipStream_t>(stream));
-}
-
-int ftr_smoothed_logprobs_bwd_am_scaled_f32(const float* gpx, const float* gpy, const float* scale, int scale_stride,
-                                            float scale_mul, const float* damp, const float* am_probs,
-                                            const int32_t* symbols, const int32_t* boundary, int termination_symbol,
-                                            float direct_scale, const float* unigram, const float* am_dot,
-                                            float am_only_scale, float* R, float* d_am, int B, int T, int S, int C,
-                                            int modified, void* stream) {
-  clear_error();
-  FTR_REQUIRE(B >= 0 && T >= 1 && S >= 0 && C >= 1, "smoothed_logprobs_bwd_am_scaled: bad sizes");
-  FTR_REQUIRE(termination_symbol >= 0 && termination_symbol < C, "smoothed_logprobs_bwd_am_scaled: bad termination_symbol");
-  FTR_REQUIRE(scale_stride == 0 || scale_stride == 1, "smoothed_logprobs_bwd_am_scaled: scale_stride must be 0 or 1");
-  if (B == 0) return FTR_OK;
-  FTR_REQUIRE(gpy && damp && am_probs && d_am && unigram && am_dot && R && (gpx || S == 0) && (symbols || S == 0), "smoothed_logprobs_bwd_am_scaled: null pointer");
-  int rc = device_ok();
-  if (rc != FTR_OK) return rc;
-  return simple_logprobs_bwd_am(gpx, gpy, Scale{scale, scale_stride, scale_mul}, damp, am_probs, symbols, boundary, termination_symbol, direct_scale, unigram, am_dot, am_only_scale, R, d_am, B, T, S, C, modified, reinterpret_cast<hipStream_t>(stream));
+  return fused_bwd_am_entry("smoothed_logprobs_fused_bwd_am", true, gpx, gpy, scale, scale_stride, scale_mul, prod, lm_probs, am_probs, symbols, boundary, termination_symbol, combined_scale, direct_scale, unigram, am_dot, am_only_scale, R, d_am, B, T, S, C, modified, stream);
 }
 
 int ftr_mutual_information_band_supported(int T, int S, int r) { return mi_band_supported(T, S, r); }
@@ -713,20 +685,14 @@ static int pruned_band_fwd_entry(const float* logits, const int32_t* symbols, co
                                  int B, int T, int S, int C, int r, int modified, int hat, void* stream) {
   const char* what = hat ? "hat_pruned_band_fwd" : "pruned_band_fwd";
   clear_error();
-  FTR_REQUIRE(B >= 0 && T >= 1 && S >= 0 && C >= 1 && r >= 1, "%s: bad sizes", what);
-  FTR_REQUIRE(!hat || C >= 2, "%s: C = %d, HAT needs a blank and at least one other symbol", what, C);
-  FTR_REQUIRE(termination_symbol >= 0 && termination_symbol < C, "%s: termination_symbol %d not in [0,%d)", what, termination_symbol, C);
+  FTR_TRY(check_builder(what, B >= 0 && T >= 1 && S >= 0 && C >= 1 && r >= 1, termination_symbol, C, false, hat));
   if (B == 0) return FTR_OK;
-  FTR_REQUIRE(logits && ranges && lse && px_band && py_band && (symbols || S == 0), "%s: null pointer", what);
-  int rc = device_ok();
-  if (rc != FTR_OK) return rc;
-  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  FTR_TRY(pointers_then_device(what, logits && ranges && lse && px_band && py_band && (symbols || S == 0)));
   // lse and the band gather are two launches: folding the gather into the lse pass (picking the blank / symbol entries out
   // of the registers that hold the row) was built and measured -- 93 - 95 us against 73 + 9 at c3: the extra per-row scalar
   // work (two divisions, the ranges -> symbols dependency) costs the streaming pass more than the second kernel does
-  rc = lse_rows(logits, lse, (size_t)B * T * r, C, termination_symbol, hat, st);
-  if (rc != FTR_OK) return rc;
-  return band_gather(logits, symbols, ranges, boundary, lse, termination_symbol, delay_penalty, px_band, py_band, B, T, S, C, r, modified, hat, st);
+  FTR_TRY(lse_rows(logits, lse, (size_t)B * T * r, C, termination_symbol, hat, stream_of(stream)));
+  return band_gather(logits, symbols, ranges, boundary, lse, termination_symbol, delay_penalty, px_band, py_band, B, T, S, C, r, modified, hat, stream_of(stream));
 }
 
 int ftr_pruned_band_fwd_f32(const float* logits, const int32_t* symbols, const int32_t* ranges, const int32_t* boundary,
@@ -743,11 +709,9 @@ int ftr_hat_pruned_band_fwd_f32(const float* logits, const int32_t* symbols, con
 
 int ftr_band_ranges_check_i32(const int32_t* ranges, const int32_t* boundary, int32_t* flags, int B, int T, int r, void* stream) {
   clear_error();
-  FTR_REQUIRE(B >= 0 && T >= 0 && r >= 1, "band_ranges_check: bad sizes");
-  FTR_REQUIRE(flags && (ranges || B == 0 || T == 0), "band_ranges_check: null pointer");
-  int rc = device_ok();
-  if (rc != FTR_OK) return rc;
-  return band_ranges_check(ranges, boundary, flags, B, T, r, reinterpret_cast<hipStream_t>(stream));
+  FTR_TRY(check_sizes("band_ranges_check", B >= 0 && T >= 0 && r >= 1));
+  FTR_TRY(pointers_then_device("band_ranges_check", flags && (ranges || B == 0 || T == 0)));
+  return band_ranges_check(ranges, boundary, flags, B, T, r, stream_of(stream));
 }
 
 int ftr_mutual_information_band_f32(const float* px_band, const float* py_band, const int32_t* ranges,
@@ -765,12 +729,10 @@ int ftr_mutual_information_band_ws_f32(const float* px_band, const float* py_ban
                                        float* gx_band, float* gy_band, int B, int T, int S, int r, int modified,
                                        void* stream) {
   clear_error();
-  FTR_REQUIRE(B >= 0 && T >= 1 && S >= 0 && r >= 1, "mutual_information_band: bad sizes");
+  FTR_TRY(check_sizes("mutual_information_band", B >= 0 && T >= 1 && S >= 0 && r >= 1));
   if (B == 0) return FTR_OK;
-  FTR_REQUIRE(px_band && py_band && ranges && ans && gx_band && gy_band, "mutual_information_band: null pointer");
-  int rc = device_ok();
-  if (rc != FTR_OK) return rc;
-  return mi_band(px_band, py_band, ranges, boundary, workspace, workspace_floats, ans, gx_band, gy_band, B, T, S, r, modified, reinterpret_cast<hipStream_t>(stream));
+  FTR_TRY(pointers_then_device("mutual_information_band", px_band && py_band && ranges && ans && gx_band && gy_band));
+  return mi_band(px_band, py_band, ranges, boundary, workspace, workspace_floats, ans, gx_band, gy_band, B, T, S, r, modified, stream_of(stream));
 }
 
 static int pruned_band_bwd_scaled_entry(const float* logits, const int32_t* symbols, const int32_t* ranges,
@@ -780,15 +742,11 @@ static int pruned_band_bwd_scaled_entry(const float* logits, const int32_t* symb
                                         int hat, void* stream) {
   const char* what = hat ? "hat_pruned_band_bwd_scaled" : "pruned_band_bwd_scaled";
   clear_error();
-  FTR_REQUIRE(B >= 0 && T >= 1 && S >= 0 && C >= 1 && r >= 1, "%s: bad sizes", what);
-  FTR_REQUIRE(!hat || C >= 2, "%s: C = %d, HAT needs a blank and at least one other symbol", what, C);
-  FTR_REQUIRE(termination_symbol >= 0 && termination_symbol < C, "%s: bad termination_symbol", what);
-  FTR_REQUIRE(scale_stride == 0 || scale_stride == 1, "%s: scale_stride must be 0 or 1", what);
+  FTR_TRY(check_builder(what, B >= 0 && T >= 1 && S >= 0 && C >= 1 && r >= 1, termination_symbol, C, true, hat));
+  FTR_TRY(check_scale_stride(what, scale_stride));
   if (B == 0) return FTR_OK;
-  FTR_REQUIRE(logits && ranges && lse && gx_band && gy_band && glogits && (symbols || S == 0), "%s: null pointer", what);
-  int rc = device_ok();
-  if (rc != FTR_OK) return rc;
-  return band_grad_banded(logits, symbols, ranges, boundary, termination_symbol, lse, gx_band, gy_band, Scale{scale, scale_stride, scale_mul}, glogits, B, T, S, C, r, modified, hat, reinterpret_cast<hipStream_t>(stream));
+  FTR_TRY(pointers_then_device(what, logits && ranges && lse && gx_band && gy_band && glogits && (symbols || S == 0)));
+  return band_grad_banded(logits, symbols, ranges, boundary, termination_symbol, lse, gx_band, gy_band, Scale{scale, scale_stride, scale_mul}, glogits, B, T, S, C, r, modified, hat, stream_of(stream));
 }
 
 int ftr_pruned_band_bwd_scaled_f32(const float* logits, const int32_t* symbols, const int32_t* ranges,
@@ -834,94 +792,6 @@ int mb_check_ids(const char* what, const int32_t* ids, int D, int blank, int C) 
 }
 }  // namespace
 
-size_t ftr_mutual_information_multiblank_workspace_floats(int B, int S, int T) {
-  return mi_multiblank_workspace_floats(B, S, T);
-}
-
-int ftr_mutual_information_multiblank_fwd_f32(const float* px, const float* py, const int32_t* boundary,
-                                              const int32_t* durations, int D, float* workspace, size_t workspace_floats,
-                                              float* ans, int B, int S, int T, void* stream) {
-  const char* what = "mutual_information_multiblank_fwd";
-  clear_error();
-  int rc = mb_check_durations(what, durations, D, false);
-  if (rc != FTR_OK) return rc;
-  FTR_REQUIRE(B >= 0 && S >= 0 && T >= 0, "%s: negative size B=%d S=%d T=%d", what, B, S, T);
-  if (B == 0) return FTR_OK;
-  FTR_REQUIRE(workspace_floats >= mi_multiblank_workspace_floats(B, S, T), "%s: workspace of %zu floats is too small, %zu needed",
-              what, workspace_floats, mi_multiblank_workspace_floats(B, S, T));
-  FTR_REQUIRE(workspace && ans && (py || T == 0) && (px || S == 0), "%s: null px / py / workspace / ans", what);
-  FTR_REQUIRE(((uintptr_t)workspace & 7) == 0, "%s: workspace must be 8-byte aligned", what);
-  rc = device_ok();
-  if (rc != FTR_OK) return rc;
-  return mi_multiblank_fwd(px, py, boundary, durations, D, workspace, workspace_floats, ans, B, S, T, reinterpret_cast<hipStream_t>(stream));
-}
-
-int ftr_mutual_information_multiblank_bwd_f32(const float* px, const float* py, const int32_t* boundary,
-                                              const int32_t* durations, int D, float* workspace, size_t workspace_floats,
-                                              const float* ans_grad, float* px_grad, float* py_grad, int B, int S, int T,
-                                              void* stream) {
-  const char* what = "mutual_information_multiblank_bwd";
-  clear_error();
-  int rc = mb_check_durations(what, durations, D, false);
-  if (rc != FTR_OK) return rc;
-  FTR_REQUIRE(B >= 0 && S >= 0 && T >= 0, "%s: negative size B=%d S=%d T=%d", what, B, S, T);
-  if (B == 0) return FTR_OK;
-  FTR_REQUIRE(workspace_floats >= mi_multiblank_workspace_floats(B, S, T), "%s: workspace of %zu floats is too small, %zu needed",
-              what, workspace_floats, mi_multiblank_workspace_floats(B, S, T));
-  FTR_REQUIRE(workspace && (py || T == 0) && (px || S == 0), "%s: null px / py / workspace", what);
-  FTR_REQUIRE((py_grad || T == 0) && (px_grad || S == 0), "%s: null px_grad / py_grad", what);
-  FTR_REQUIRE(((uintptr_t)workspace & 7) == 0, "%s: workspace must be 8-byte aligned", what);
-  rc = device_ok();
-  if (rc != FTR_OK) return rc;
-  return mi_multiblank_bwd(px, py, boundary, durations, D, workspace, workspace_floats, ans_grad, px_grad, py_grad, B, S, T,
-                           reinterpret_cast<hipStream_t>(stream));
-}
-
-int ftr_multiblank_pruned_logprobs_fwd_f32(const float* logits, const int32_t* symbols, const int32_t* ranges,
-                                           const int32_t* boundary, int termination_symbol, const int32_t* big_blank_ids,
-                                           const int32_t* durations, int D, double sigma, double delay_penalty, float* lse,
-                                           float* px, float* py, int B, int T, int S, int C, int r, void* stream) {
-  const char* what = "multiblank_pruned_logprobs_fwd";
-  clear_error();
-  int rc = mb_check_durations(what, durations, D, true);
-  if (rc != FTR_OK) return rc;
-  rc = mb_check_ids(what, big_blank_ids, D, termination_symbol, C);
-  if (rc != FTR_OK) return rc;
-  FTR_REQUIRE(B >= 0 && T >= 1 && S >= 0 && r >= 1, "%s: bad sizes", what);
-  FTR_REQUIRE(r <= S + 1, "%s: s_range %d > S+1 = %d", what, r, S + 1);
-  FTR_REQUIRE(sigma >= 0.0, "%s: sigma = %g must not be negative", what, sigma);
-  if (B == 0) return FTR_OK;
-  FTR_REQUIRE(logits && ranges && lse && py && (symbols || S == 0) && (px || S == 0), "%s: null pointer", what);
-  rc = device_ok();
-  if (rc != FTR_OK) return rc;
-  return multiblank_logprobs_fwd(logits, symbols, ranges, boundary, termination_symbol, big_blank_ids, durations, D, sigma,
-                                 delay_penalty, lse, px, py, B, T, S, C, r, reinterpret_cast<hipStream_t>(stream));
-}
-
-int ftr_multiblank_pruned_logprobs_bwd_scaled_f32(const float* logits, const int32_t* symbols, const int32_t* ranges,
-                                                  const int32_t* boundary, int termination_symbol,
-                                                  const int32_t* big_blank_ids, const int32_t* durations, int D,
-                                                  const float* lse, const float* gpx, const float* gpy, const float* scale,
-                                                  int scale_stride, float scale_mul, float* glogits, int B, int T, int S,
-                                                  int C, int r, void* stream) {
-  const char* what = "multiblank_pruned_logprobs_bwd_scaled";
-  clear_error();
-  int rc = mb_check_durations(what, durations, D, true);
-  if (rc != FTR_OK) return rc;
-  rc = mb_check_ids(what, big_blank_ids, D, termination_symbol, C);
-  if (rc != FTR_OK) return rc;
-  FTR_REQUIRE(B >= 0 && T >= 1 && S >= 0 && r >= 1, "%s: bad sizes", what);
-  FTR_REQUIRE(scale_stride == 0 || scale_stride == 1, "%s: scale_stride must be 0 or 1", what);
-  if (B == 0) return FTR_OK;
-  FTR_REQUIRE(logits && ranges && lse && gpy && glogits && (symbols || S == 0) && (gpx || S == 0), "%s: null pointer", what);
-  rc = device_ok();
-  if (rc != FTR_OK) return rc;
-  return multiblank_logprobs_bwd(logits, symbols, ranges, boundary, termination_symbol, big_blank_ids, durations, D, lse, gpx,
-                                 gpy, Scale{scale, scale_stride, scale_mul}, glogits, B, T, S, C, r,
-                                 reinterpret_cast<hipStream_t>(stream));
-}
-
-
 // ---- token-and-duration transducer, TDT (MI355X addition; csrc/mi_tdt.hip, csrc/tdt_logprobs.hip).  The duration lists
 // are host data and are validated first, then sizes and pointers, then the device.
 namespace {
@@ -937,22 +807,90 @@ int tdt_check_list(const char* what, const char* name, const int32_t* v, int n, 
 }
 int tdt_check_moves(const char* what, const int32_t* token_durations, int Dx, const int32_t* blank_durations, int Dy,
                     int blank_hi = 16) {
-  int rc = tdt_check_list(what, "token_durations", token_durations, Dx, 8, 0);
-  if (rc != FTR_OK) return rc;
-  rc = tdt_check_list(what, "blank_durations", blank_durations, Dy, 8, 1, blank_hi);
-  if (rc != FTR_OK) return rc;
+  FTR_TRY(tdt_check_list(what, "token_durations", token_durations, Dx, 8, 0));
+  FTR_TRY(tdt_check_list(what, "blank_durations", blank_durations, Dy, 8, 1, blank_hi));
   FTR_REQUIRE(Dx + Dy <= 9, "%s: Dx + Dy = %d moves (token_durations and blank_durations together), at most 9", what, Dx + Dy);
   return FTR_OK;
 }
 int tdt_check_head(const char* what, const int32_t* durations, int N, double sigma, int blank, int C) {
-  int rc = tdt_check_list(what, "durations", durations, N, 5, 0);
-  if (rc != FTR_OK) return rc;
+  FTR_TRY(tdt_check_list(what, "durations", durations, N, 5, 0));
   FTR_REQUIRE(durations[N - 1] >= 1, "%s: durations holds no positive value: no move advances a frame", what);
   FTR_REQUIRE(sigma >= 0.0, "%s: sigma = %g must not be negative", what, sigma);
   FTR_REQUIRE(C >= 1 && blank >= 0 && blank < C, "%s: termination_symbol %d not in [0,%d)", what, blank, C);
   return FTR_OK;
 }
 }  // namespace
+
+size_t ftr_mutual_information_multiblank_workspace_floats(int B, int S, int T) {
+  return mi_multiblank_workspace_floats(B, S, T);
+}
+
+int ftr_mutual_information_multiblank_fwd_f32(const float* px, const float* py, const int32_t* boundary,
+                                              const int32_t* durations, int D, float* workspace, size_t workspace_floats,
+                                              float* ans, int B, int S, int T, void* stream) {
+  const char* what = "mutual_information_multiblank_fwd";
+  clear_error();
+  FTR_TRY(mb_check_durations(what, durations, D, false));
+  FTR_TRY(check_lattice(what, B, S, T));
+  if (B == 0) return FTR_OK;
+  FTR_TRY(check_ws_size(what, workspace_floats, mi_multiblank_workspace_floats(B, S, T), "floats"));
+  FTR_REQUIRE(workspace && ans && (py || T == 0) && (px || S == 0), "%s: null px / py / workspace / ans", what);
+  FTR_TRY(check_ws_aligned(what, workspace));
+  FTR_TRY(device_ok());
+  return mi_multiblank_fwd(px, py, boundary, durations, D, workspace, workspace_floats, ans, B, S, T, stream_of(stream));
+}
+
+int ftr_mutual_information_multiblank_bwd_f32(const float* px, const float* py, const int32_t* boundary,
+                                              const int32_t* durations, int D, float* workspace, size_t workspace_floats,
+                                              const float* ans_grad, float* px_grad, float* py_grad, int B, int S, int T,
+                                              void* stream) {
+  const char* what = "mutual_information_multiblank_bwd";
+  clear_error();
+  FTR_TRY(mb_check_durations(what, durations, D, false));
+  FTR_TRY(check_lattice(what, B, S, T));
+  if (B == 0) return FTR_OK;
+  FTR_TRY(check_ws_size(what, workspace_floats, mi_multiblank_workspace_floats(B, S, T), "floats"));
+  FTR_REQUIRE(workspace && (py || T == 0) && (px || S == 0), "%s: null px / py / workspace", what);
+  FTR_REQUIRE((py_grad || T == 0) && (px_grad || S == 0), "%s: null px_grad / py_grad", what);
+  FTR_TRY(check_ws_aligned(what, workspace));
+  FTR_TRY(device_ok());
+  return mi_multiblank_bwd(px, py, boundary, durations, D, workspace, workspace_floats, ans_grad, px_grad, py_grad, B, S, T, stream_of(stream));
+}
+
+int ftr_multiblank_pruned_logprobs_fwd_f32(const float* logits, const int32_t* symbols, const int32_t* ranges,
+                                           const int32_t* boundary, int termination_symbol, const int32_t* big_blank_ids,
+                                           const int32_t* durations, int D, double sigma, double delay_penalty, float* lse,
+                                           float* px, float* py, int B, int T, int S, int C, int r, void* stream) {
+  const char* what = "multiblank_pruned_logprobs_fwd";
+  clear_error();
+  FTR_TRY(mb_check_durations(what, durations, D, true));
+  FTR_TRY(mb_check_ids(what, big_blank_ids, D, termination_symbol, C));
+  FTR_TRY(check_sizes(what, B >= 0 && T >= 1 && S >= 0 && r >= 1));
+  FTR_TRY(check_s_range(what, r, S));
+  FTR_REQUIRE(sigma >= 0.0, "%s: sigma = %g must not be negative", what, sigma);
+  if (B == 0) return FTR_OK;
+  FTR_TRY(pointers_then_device(what, logits && ranges && lse && py && (symbols || S == 0) && (px || S == 0)));
+  return multiblank_logprobs_fwd(logits, symbols, ranges, boundary, termination_symbol, big_blank_ids, durations, D, sigma,
+                                 delay_penalty, lse, px, py, B, T, S, C, r, stream_of(stream));
+}
+
+int ftr_multiblank_pruned_logprobs_bwd_scaled_f32(const float* logits, const int32_t* symbols, const int32_t* ranges,
+                                                  const int32_t* boundary, int termination_symbol,
+                                                  const int32_t* big_blank_ids, const int32_t* durations, int D,
+                                                  const float* lse, const float* gpx, const float* gpy, const float* scale,
+                                                  int scale_stride, float scale_mul, float* glogits, int B, int T, int S,
+                                                  int C, int r, void* stream) {
+  const char* what = "multiblank_pruned_logprobs_bwd_scaled";
+  clear_error();
+  FTR_TRY(mb_check_durations(what, durations, D, true));
+  FTR_TRY(mb_check_ids(what, big_blank_ids, D, termination_symbol, C));
+  FTR_TRY(check_sizes(what, B >= 0 && T >= 1 && S >= 0 && r >= 1));
+  FTR_TRY(check_scale_stride(what, scale_stride));
+  if (B == 0) return FTR_OK;
+  FTR_TRY(pointers_then_device(what, logits && ranges && lse && gpy && glogits && (symbols || S == 0) && (gpx || S == 0)));
+  return multiblank_logprobs_bwd(logits, symbols, ranges, boundary, termination_symbol, big_blank_ids, durations, D, lse, gpx,
+                                 gpy, Scale{scale, scale_stride, scale_mul}, glogits, B, T, S, C, r, stream_of(stream));
+}
 
 size_t ftr_mutual_information_tdt_workspace_floats(int B, int S, int T) { return mi_tdt_workspace_floats(B, S, T); }
 
@@ -962,18 +900,15 @@ int ftr_mutual_information_tdt_fwd_f32(const float* px, const float* py, const i
                                        void* stream) {
   const char* what = "mutual_information_tdt_fwd";
   clear_error();
-  int rc = tdt_check_moves(what, token_durations, Dx, blank_durations, Dy);
-  if (rc != FTR_OK) return rc;
-  FTR_REQUIRE(B >= 0 && S >= 0 && T >= 0, "%s: negative size B=%d S=%d T=%d", what, B, S, T);
+  FTR_TRY(tdt_check_moves(what, token_durations, Dx, blank_durations, Dy));
+  FTR_TRY(check_lattice(what, B, S, T));
   if (B == 0) return FTR_OK;
-  FTR_REQUIRE(workspace_floats >= mi_tdt_workspace_floats(B, S, T), "%s: workspace of %zu floats is too small, %zu needed",
-              what, workspace_floats, mi_tdt_workspace_floats(B, S, T));
+  FTR_TRY(check_ws_size(what, workspace_floats, mi_tdt_workspace_floats(B, S, T), "floats"));
   FTR_REQUIRE(workspace && ans && (py || T == 0) && (px || S == 0), "%s: null px / py / workspace / ans", what);
-  FTR_REQUIRE(((uintptr_t)workspace & 7) == 0, "%s: workspace must be 8-byte aligned", what);
-  rc = device_ok();
-  if (rc != FTR_OK) return rc;
+  FTR_TRY(check_ws_aligned(what, workspace));
+  FTR_TRY(device_ok());
   return mi_tdt_fwd(px, py, boundary, token_durations, Dx, blank_durations, Dy, workspace, workspace_floats, ans, B, S, T,
-                    reinterpret_cast<hipStream_t>(stream));
+                    stream_of(stream));
 }
 
 int ftr_mutual_information_tdt_bwd_f32(const float* px, const float* py, const int32_t* boundary,
@@ -982,19 +917,16 @@ int ftr_mutual_information_tdt_bwd_f32(const float* px, const float* py, const i
                                        float* py_grad, int B, int S, int T, void* stream) {
   const char* what = "mutual_information_tdt_bwd";
   clear_error();
-  int rc = tdt_check_moves(what, token_durations, Dx, blank_durations, Dy);
-  if (rc != FTR_OK) return rc;
-  FTR_REQUIRE(B >= 0 && S >= 0 && T >= 0, "%s: negative size B=%d S=%d T=%d", what, B, S, T);
+  FTR_TRY(tdt_check_moves(what, token_durations, Dx, blank_durations, Dy));
+  FTR_TRY(check_lattice(what, B, S, T));
   if (B == 0) return FTR_OK;
-  FTR_REQUIRE(workspace_floats >= mi_tdt_workspace_floats(B, S, T), "%s: workspace of %zu floats is too small, %zu needed",
-              what, workspace_floats, mi_tdt_workspace_floats(B, S, T));
+  FTR_TRY(check_ws_size(what, workspace_floats, mi_tdt_workspace_floats(B, S, T), "floats"));
   FTR_REQUIRE(workspace && (py || T == 0) && (px || S == 0), "%s: null px / py / workspace", what);
   FTR_REQUIRE((py_grad || T == 0) && (px_grad || S == 0), "%s: null px_grad / py_grad", what);
-  FTR_REQUIRE(((uintptr_t)workspace & 7) == 0, "%s: workspace must be 8-byte aligned", what);
-  rc = device_ok();
-  if (rc != FTR_OK) return rc;
+  FTR_TRY(check_ws_aligned(what, workspace));
+  FTR_TRY(device_ok());
   return mi_tdt_bwd(px, py, boundary, token_durations, Dx, blank_durations, Dy, workspace, workspace_floats, ans_grad,
-                    px_grad, py_grad, B, S, T, reinterpret_cast<hipStream_t>(stream));
+                    px_grad, py_grad, B, S, T, stream_of(stream));
 }
 
 // Best-path alignment over the TDT / multi-blank lattice (csrc/mi_viterbi_tdt.hip).  A blank may advance 32 frames here,
@@ -1009,20 +941,17 @@ int ftr_mutual_information_viterbi_tdt_f32(const float* px, const float* py, con
                                            int32_t* durations, int32_t* blank_steps, int B, int S, int T, void* stream) {
   const char* what = "mutual_information_viterbi_tdt";
   clear_error();
-  int rc = tdt_check_moves(what, token_durations, Dx, blank_durations, Dy, 32);
-  if (rc != FTR_OK) return rc;
-  FTR_REQUIRE(B >= 0 && S >= 0 && T >= 0, "%s: negative size B=%d S=%d T=%d", what, B, S, T);
+  FTR_TRY(tdt_check_moves(what, token_durations, Dx, blank_durations, Dy, 32));
+  FTR_TRY(check_lattice(what, B, S, T));
   if (B == 0) return FTR_OK;
-  FTR_REQUIRE(workspace_bytes >= mi_viterbi_tdt_workspace_bytes(B, S, T), "%s: workspace of %zu bytes is too small, %zu needed",
-              what, workspace_bytes, mi_viterbi_tdt_workspace_bytes(B, S, T));
+  FTR_TRY(check_ws_size(what, workspace_bytes, mi_viterbi_tdt_workspace_bytes(B, S, T), "bytes"));
   FTR_REQUIRE(workspace && score && (py || T == 0) && (px || S == 0), "%s: null px / py / workspace / score", what);
   FTR_REQUIRE((frames && durations) || S == 0, "%s: null frames / durations", what);
   FTR_REQUIRE(blank_steps || T == 0, "%s: null blank_steps", what);
-  FTR_REQUIRE(((uintptr_t)workspace & 7) == 0, "%s: workspace must be 8-byte aligned", what);
-  rc = device_ok();
-  if (rc != FTR_OK) return rc;
+  FTR_TRY(check_ws_aligned(what, workspace));
+  FTR_TRY(device_ok());
   return mi_viterbi_tdt(px, py, boundary, token_durations, Dx, blank_durations, Dy, workspace, workspace_bytes, score, frames,
-                        durations, blank_steps, B, S, T, reinterpret_cast<hipStream_t>(stream));
+                        durations, blank_steps, B, S, T, stream_of(stream));
 }
 
 int ftr_tdt_pruned_logprobs_fwd_f32(const float* logits, const int32_t* symbols, const int32_t* ranges,
@@ -1031,16 +960,13 @@ int ftr_tdt_pruned_logprobs_fwd_f32(const float* logits, const int32_t* symbols,
                                     float* py, int B, int T, int S, int C, int r, void* stream) {
   const char* what = "tdt_pruned_logprobs_fwd";
   clear_error();
-  int rc = tdt_check_head(what, durations, N, sigma, termination_symbol, C);
-  if (rc != FTR_OK) return rc;
-  FTR_REQUIRE(B >= 0 && T >= 1 && S >= 0 && r >= 1, "%s: bad sizes", what);
-  FTR_REQUIRE(r <= S + 1, "%s: s_range %d > S+1 = %d", what, r, S + 1);
+  FTR_TRY(tdt_check_head(what, durations, N, sigma, termination_symbol, C));
+  FTR_TRY(check_sizes(what, B >= 0 && T >= 1 && S >= 0 && r >= 1));
+  FTR_TRY(check_s_range(what, r, S));
   if (B == 0) return FTR_OK;
-  FTR_REQUIRE(logits && ranges && lse_tok && lse_dur && py && (symbols || S == 0) && (px || S == 0), "%s: null pointer", what);
-  rc = device_ok();
-  if (rc != FTR_OK) return rc;
+  FTR_TRY(pointers_then_device(what, logits && ranges && lse_tok && lse_dur && py && (symbols || S == 0) && (px || S == 0)));
   return tdt_logprobs_fwd(logits, symbols, ranges, boundary, termination_symbol, durations, N, sigma, delay_penalty, lse_tok,
-                          lse_dur, px, py, B, T, S, C, r, reinterpret_cast<hipStream_t>(stream));
+                          lse_dur, px, py, B, T, S, C, r, stream_of(stream));
 }
 
 int ftr_tdt_pruned_logprobs_bwd_scaled_f32(const float* logits, const int32_t* symbols, const int32_t* ranges,
@@ -1052,43 +978,32 @@ int ftr_tdt_pruned_logprobs_bwd_scaled_f32(const float* logits, const int32_t* s
   const char* what = "tdt_pruned_logprobs_bwd_scaled";
   clear_error();
   (void)delay_penalty;   // a constant added to px: no gradient
-  int rc = tdt_check_head(what, durations, N, sigma, termination_symbol, C);
-  if (rc != FTR_OK) return rc;
-  FTR_REQUIRE(B >= 0 && T >= 1 && S >= 0 && r >= 1, "%s: bad sizes", what);
-  FTR_REQUIRE(scale_stride == 0 || scale_stride == 1, "%s: scale_stride must be 0 or 1", what);
+  FTR_TRY(tdt_check_head(what, durations, N, sigma, termination_symbol, C));
+  FTR_TRY(check_sizes(what, B >= 0 && T >= 1 && S >= 0 && r >= 1));
+  FTR_TRY(check_scale_stride(what, scale_stride));
   if (B == 0) return FTR_OK;
-  FTR_REQUIRE(logits && ranges && lse_tok && lse_dur && gpy && glogits && (symbols || S == 0) && (gpx || S == 0),
-              "%s: null pointer", what);
-  rc = device_ok();
-  if (rc != FTR_OK) return rc;
+  FTR_TRY(pointers_then_device(what, logits && ranges && lse_tok && lse_dur && gpy && glogits && (symbols || S == 0) && (gpx || S == 0)));
   return tdt_logprobs_bwd(logits, symbols, ranges, boundary, termination_symbol, durations, N, lse_tok, lse_dur, gpx, gpy,
-                          Scale{scale, scale_stride, scale_mul}, glogits, B, T, S, C, r,
-                          reinterpret_cast<hipStream_t>(stream));
+                          Scale{scale, scale_stride, scale_mul}, glogits, B, T, S, C, r, stream_of(stream));
 }
-
 
 int ftr_selftest(void* scratch_dev, void* stream) {
   clear_error();
   FTR_REQUIRE(scratch_dev, "selftest: need >= 8 KiB of device scratch");
-  int rc = device_ok();
-  if (rc != FTR_OK) return rc;
-  return selftest(reinterpret_cast<hipStream_t>(stream), reinterpret_cast<int*>(scratch_dev));
+  FTR_TRY(device_ok());
+  return selftest(stream_of(stream), reinterpret_cast<int*>(scratch_dev));
 }
 
 #ifdef FTR_DIAG
 int ftr_debug_stamps(unsigned long long* out16) {
   clear_error();
-  FTR_REQUIRE(out16, "debug_stamps: null pointer");
-  int rc = device_ok();
-  if (rc != FTR_OK) return rc;
+  FTR_TRY(pointers_then_device("debug_stamps", out16));
   return debug_stamps(out16);
 }
 
 int ftr_debug_trace(unsigned long long* out, int n) {
   clear_error();
-  FTR_REQUIRE(out || n == 0, "debug_trace: null pointer");
-  int rc = device_ok();
-  if (rc != FTR_OK) return rc;
+  FTR_TRY(pointers_then_device("debug_trace", out || n == 0));
   return debug_trace(out, n);
 }
 #endif

@@ -28,6 +28,7 @@
 // LDS (per utterance): lo[T+1] (band start per column) and three arrays of (S_n + T_n + 1) x LANES floats: OX, OY
 // (operands, later the two flow outputs) and G.  LANES = 8 while r <= 7, 16 up to r = 15 (r + 1 lanes: see in_band in the kernel).
 #include "ftr_common.h"
+#include "launch.h"
 #include <type_traits>
 #include <cstdlib>
 
@@ -851,13 +852,17 @@ int band_gather(const float* logits, const int32_t* symbols, const int32_t* rang
   if (rows == 0) return FTR_OK;
   { const int rc32 = require_rows_32bit("pruned_band_fwd", rows); if (rc32 != FTR_OK) return rc32; }
   const unsigned blocks = (unsigned)((rows + 255) / 256);
-#define FTR_LAUNCH_BGA(MODV, HATV) hipLaunchKernelGGL((band_gather_kernel<MODV, HATV>), dim3(blocks), dim3(256), 0, st, \
-    logits, symbols, ranges, boundary, lse, blank, delay_penalty, pxb, pyb, rows, T, S, C, r)
-  if (modified) { if (hat) FTR_LAUNCH_BGA(true, true); else FTR_LAUNCH_BGA(true, false); }
-  else { if (hat) FTR_LAUNCH_BGA(false, true); else FTR_LAUNCH_BGA(false, false); }
-#undef FTR_LAUNCH_BGA
+  dispatch(modified != 0, [&](auto mod) {
+    dispatch(hat != 0, [&](auto h) {
+      hipLaunchKernelGGL((band_gather_kernel<decltype(mod)::value, decltype(h)::value>), dim3(blocks), dim3(256), 0, st,
+                         logits, symbols, ranges, boundary, lse, blank, delay_penalty, pxb, pyb, rows, T, S, C, r);
+    });
+  });
   return check_launch("band_gather");
 }
+
+// the dynamic-LDS limit of the chain kernels: 156 KB, not 160 -- they also have a few bytes of static LDS (__syncthreads_or)
+constexpr size_t kBandLdsCeiling = 156 * 1024;
 
 int mi_band(const float* pxb, const float* pyb, const int32_t* ranges, const int32_t* boundary, float* ws, size_t ws_floats,
             float* ans, float* gxb, float* gyb, int B, int T, int S, int r, int modified, hipStream_t st) {
@@ -875,40 +880,26 @@ int mi_band(const float* pxb, const float* pyb, const int32_t* ranges, const int
       return FTR_ERR_INVALID_ARG;
     }
     const size_t lds = band_stream_lds_bytes(T);
-    static bool big_ok = false;
-    if (!big_ok) {
-      const void* ks[4] = {reinterpret_cast<const void*>(mi_band_stream_kernel<true, 8>), reinterpret_cast<const void*>(mi_band_stream_kernel<false, 8>),
-                           reinterpret_cast<const void*>(mi_band_stream_kernel<true, 16>), reinterpret_cast<const void*>(mi_band_stream_kernel<false, 16>)};
-      for (const void* k : ks)
-        if (hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, 156 * 1024) != hipSuccess) {
-          (void)hipGetLastError(); set_error("mutual_information_band: cannot raise the dynamic LDS limit"); return FTR_ERR_LAUNCH;
-        }
-      big_ok = true;
-    }
-#define FTR_BANDS_LAUNCH(MODV, LV) hipLaunchKernelGGL((mi_band_stream_kernel<MODV, LV>), dim3(B), dim3(kBandThreads), lds, st, \
-    pxb, pyb, ranges, boundary, ws, ans, gxb, gyb, B, T, S, r, rinv)
-    if (band_stream_lanes(T, r) == 8) { if (modified) FTR_BANDS_LAUNCH(true, 8); else FTR_BANDS_LAUNCH(false, 8); }
-    else { if (modified) FTR_BANDS_LAUNCH(true, 16); else FTR_BANDS_LAUNCH(false, 16); }
-#undef FTR_BANDS_LAUNCH
-    return check_launch("mi_band_stream");
+    return dispatch_among<8, 16>(band_stream_lanes(T, r), [&](auto lanes) {
+      return dispatch(modified != 0, [&](auto mod) {
+        constexpr auto kernel = mi_band_stream_kernel<decltype(mod)::value, decltype(lanes)::value>;
+        const int rc = reserve_lds<kernel>(kBandLdsCeiling, "mutual_information_band");
+        if (rc != FTR_OK) return rc;
+        hipLaunchKernelGGL(kernel, dim3(B), dim3(kBandThreads), lds, st, pxb, pyb, ranges, boundary, ws, ans, gxb, gyb, B, T, S, r, rinv);
+        return check_launch("mi_band_stream");
+      });
+    });
   }
-  const int lanes = band_lanes(T, S, r);
-  static bool big_ok = false;
-  if (!big_ok) {   // 156 KB: the kernel also has a few bytes of static LDS (__syncthreads_or)
-    const void* ks[4] = {reinterpret_cast<const void*>(mi_band_kernel<true, 8>), reinterpret_cast<const void*>(mi_band_kernel<false, 8>),
-                         reinterpret_cast<const void*>(mi_band_kernel<true, 16>), reinterpret_cast<const void*>(mi_band_kernel<false, 16>)};
-    for (const void* k : ks)
-      if (hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, 156 * 1024) != hipSuccess) {
-        (void)hipGetLastError(); set_error("mutual_information_band: cannot raise the dynamic LDS limit"); return FTR_ERR_LAUNCH;
-      }
-    big_ok = true;
-  }
-#define FTR_BAND_LAUNCH(MODV, LV) hipLaunchKernelGGL((mi_band_kernel<MODV, LV>), dim3(B), dim3(kBandThreads), band_lds_bytes<LV>(T, S), st, \
-    pxb, pyb, ranges, boundary, ans, gxb, gyb, B, T, S, r, rinv)
-  if (lanes == 8) { if (modified) FTR_BAND_LAUNCH(true, 8); else FTR_BAND_LAUNCH(false, 8); }
-  else { if (modified) FTR_BAND_LAUNCH(true, 16); else FTR_BAND_LAUNCH(false, 16); }
-#undef FTR_BAND_LAUNCH
-  return check_launch("mi_band");
+  return dispatch_among<8, 16>(band_lanes(T, S, r), [&](auto lanes) {
+    return dispatch(modified != 0, [&](auto mod) {
+      constexpr int L = decltype(lanes)::value;
+      constexpr auto kernel = mi_band_kernel<decltype(mod)::value, L>;
+      const int rc = reserve_lds<kernel>(kBandLdsCeiling, "mutual_information_band");
+      if (rc != FTR_OK) return rc;
+      hipLaunchKernelGGL(kernel, dim3(B), dim3(kBandThreads), band_lds_bytes<L>(T, S), st, pxb, pyb, ranges, boundary, ans, gxb, gyb, B, T, S, r, rinv);
+      return check_launch("mi_band");
+    });
+  });
 }
 
 #ifdef FTR_BAND_STAMPS
@@ -925,11 +916,12 @@ int band_grad_banded(const float* logits, const int32_t* symbols, const int32_t*
   { const int rc32 = require_rows_32bit("pruned_band_bwd", rows); if (rc32 != FTR_OK) return rc32; }
   const int wpb = 4;
   const unsigned blocks = (unsigned)((rows + wpb - 1) / wpb);
-#define FTR_LAUNCH_BGB(VECV, HATV) hipLaunchKernelGGL((band_grad_banded_kernel<VECV, HATV>), dim3(blocks), dim3(64 * wpb), 0, st, \
-    logits, symbols, ranges, boundary, lse, gxb, gyb, scale, blank, modified, glogits, rows, T, S, C, r)
-  if ((C & 3) == 0) { if (hat) FTR_LAUNCH_BGB(true, true); else FTR_LAUNCH_BGB(true, false); }
-  else { if (hat) FTR_LAUNCH_BGB(false, true); else FTR_LAUNCH_BGB(false, false); }
-#undef FTR_LAUNCH_BGB
+  dispatch((C & 3) == 0, [&](auto vec) {
+    dispatch(hat != 0, [&](auto h) {
+      hipLaunchKernelGGL((band_grad_banded_kernel<decltype(vec)::value, decltype(h)::value>), dim3(blocks), dim3(64 * wpb), 0, st,
+                         logits, symbols, ranges, boundary, lse, gxb, gyb, scale, blank, modified, glogits, rows, T, S, C, r);
+    });
+  });
   return check_launch("band_grad_banded");
 }
 

@@ -28,6 +28,7 @@
 // The geometry (walk length D, K, steps per segment) depends on the utterance's boundary, i.e. on device data: every kernel
 // derives it the same way (seg_geom) and surplus workgroups leave.
 #include "ftr_common.h"
+#include "launch.h"
 #include <cstdlib>
 #include <cstring>
 
@@ -493,34 +494,31 @@ int mi_band_seg(const float* pxb, const float* pyb, const int32_t* ranges, const
   }
   const int lanes = seg_lanes(r);
   const size_t lds_t = seg_lds_bytes(T, S, lanes, false), lds_f = seg_lds_bytes(T, S, lanes, true);
-  static bool big_ok = false;
-  if (!big_ok) {
-    const void* ks[8] = {reinterpret_cast<const void*>(band_seg_transfer_kernel<true, 8>), reinterpret_cast<const void*>(band_seg_transfer_kernel<false, 8>),
-                         reinterpret_cast<const void*>(band_seg_transfer_kernel<true, 16>), reinterpret_cast<const void*>(band_seg_transfer_kernel<false, 16>),
-                         reinterpret_cast<const void*>(band_seg_final_kernel<true, 8>), reinterpret_cast<const void*>(band_seg_final_kernel<false, 8>),
-                         reinterpret_cast<const void*>(band_seg_final_kernel<true, 16>), reinterpret_cast<const void*>(band_seg_final_kernel<false, 16>)};
-    for (const void* k : ks)
-      if (hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, 156 * 1024) != hipSuccess) {
-        (void)hipGetLastError(); set_error("mutual_information_band (segments): cannot raise the dynamic LDS limit"); return FTR_ERR_LAUNCH;
-      }
-    big_ok = true;
-  }
   const unsigned cells_blocks = (unsigned)(((size_t)(T + 1) * r + 255) / 256);
   const unsigned fill_blocks = (unsigned)((2 * seg_rows(T, S) * lanes + 255) / 256);
   const dim3 gseg(kSegMaxK, 2, B);
-#define FTR_SEG_RUN(MODV, LV)                                                                                                         \
-  do {                                                                                                                                \
-    hipLaunchKernelGGL((band_seg_init_kernel<MODV, LV>), dim3(fill_blocks, B), dim3(256), 0, st, pxb, pyb, ranges, boundary, ws, T, S, r); \
-    hipLaunchKernelGGL((band_seg_scatter_kernel<MODV, LV>), dim3(cells_blocks, B), dim3(256), 0, st, pxb, pyb, ranges, boundary, ws, T, S, r); \
-    hipLaunchKernelGGL((band_seg_transfer_kernel<MODV, LV>), gseg, dim3(16 * LV), lds_t, st, boundary, ws, T, S);                      \
-    hipLaunchKernelGGL((band_seg_prefix_kernel<MODV, LV>), dim3(2, B), dim3(64), sizeof(double) * (kSegMaxK - 1) * LV * LV, st, boundary, ws, T, S); \
-    hipLaunchKernelGGL((band_seg_final_kernel<MODV, LV>), gseg, dim3(64), lds_f, st, boundary, ws, T, S);                              \
-    hipLaunchKernelGGL((band_seg_occupancy_kernel<MODV, LV>), dim3((unsigned)(((size_t)T * r + 255) / 256), B), dim3(256), 0, st,    \
-                       ranges, boundary, ws, ans, gxb, gyb, T, S, r);                                                                 \
-  } while (0)
-  if (lanes == 8) { if (modified) FTR_SEG_RUN(true, 8); else FTR_SEG_RUN(false, 8); }
-  else { if (modified) FTR_SEG_RUN(true, 16); else FTR_SEG_RUN(false, 16); }
-#undef FTR_SEG_RUN
+  constexpr size_t ceiling = 156 * 1024;   // as the chain kernels of mi_band.hip: room for a few bytes of static LDS
+  const char* what = "mutual_information_band (segments)";
+  const int rc = dispatch_among<8, 16>(lanes, [&](auto lv) {
+    return dispatch(modified != 0, [&](auto mod) {
+      constexpr bool MODV = decltype(mod)::value;
+      constexpr int LV = decltype(lv)::value;
+      constexpr auto transfer = band_seg_transfer_kernel<MODV, LV>;
+      constexpr auto final_k = band_seg_final_kernel<MODV, LV>;
+      int rcl = reserve_lds<transfer>(ceiling, what);
+      if (rcl == FTR_OK) rcl = reserve_lds<final_k>(ceiling, what);
+      if (rcl != FTR_OK) return rcl;
+      hipLaunchKernelGGL((band_seg_init_kernel<MODV, LV>), dim3(fill_blocks, B), dim3(256), 0, st, pxb, pyb, ranges, boundary, ws, T, S, r);
+      hipLaunchKernelGGL((band_seg_scatter_kernel<MODV, LV>), dim3(cells_blocks, B), dim3(256), 0, st, pxb, pyb, ranges, boundary, ws, T, S, r);
+      hipLaunchKernelGGL(transfer, gseg, dim3(16 * LV), lds_t, st, boundary, ws, T, S);
+      hipLaunchKernelGGL((band_seg_prefix_kernel<MODV, LV>), dim3(2, B), dim3(64), sizeof(double) * (kSegMaxK - 1) * LV * LV, st, boundary, ws, T, S);
+      hipLaunchKernelGGL(final_k, gseg, dim3(64), lds_f, st, boundary, ws, T, S);
+      hipLaunchKernelGGL((band_seg_occupancy_kernel<MODV, LV>), dim3((unsigned)(((size_t)T * r + 255) / 256), B), dim3(256), 0, st,
+                         ranges, boundary, ws, ans, gxb, gyb, T, S, r);
+      return FTR_OK;
+    });
+  });
+  if (rc != FTR_OK) return rc;
   return check_launch("mi_band_seg");
 }
 

@@ -204,10 +204,10 @@ int mb_launch(const float* px, const float* py, const int32_t* boundary, const i
   double* wsd = reinterpret_cast<double*>(ws);
   double *p = wsd + L.p_off, *ansd = wsd + L.ans_off, *carry = wsd + L.carry_off;
   const size_t lds = (size_t)DEP * 64 * NW * sizeof(double);
-  dispatch_arity<1, MBMAXD>(D, [&](auto d) {
+  dispatch_range<1, MBMAXD>(D, [&](auto d) {
     hipLaunchKernelGGL((mi_multiblank_kernel<decltype(d)::value, BWD>), dim3(B), dim3(64 * NW), lds, st, px, py, boundary,
                        dur, p, ansd, carry, ans, ans_grad, px_grad, py_grad, S, T, NW, DEP);
-  });
+  }, [] {});   // the entry points admit no other arity
   return check_launch(what);
 }
 

@@ -9,6 +9,7 @@
 //   safe_exp / backward mutual_information_cuda.cu:430-439, 608-660, 692-704, 719-720, 733-758
 // The tiling of the reference (32x32 tiles, one launch per tile diagonal) is NOT reproduced.
 #include "ftr_common.h"
+#include "launch.h"
 
 namespace ftr {
 namespace {
@@ -147,8 +148,9 @@ int mi_plain_fwd(const float* px, const float* py, const int32_t* boundary, floa
   const size_t lds = sizeof(float) * 2 * (size_t)(S + 2);
   if (lds > 64 * 1024) { set_error("mi_plain_fwd: S=%d too large for the plain family", S); return FTR_ERR_UNSUPPORTED; }
   const int threads = 256;
-  if (modified) hipLaunchKernelGGL(mi_plain_fwd_kernel<true>, dim3(B), dim3(threads), lds, st, px, py, boundary, p, ans, S, T);
-  else hipLaunchKernelGGL(mi_plain_fwd_kernel<false>, dim3(B), dim3(threads), lds, st, px, py, boundary, p, ans, S, T);
+  dispatch(modified != 0, [&](auto mod) {
+    hipLaunchKernelGGL(mi_plain_fwd_kernel<decltype(mod)::value>, dim3(B), dim3(threads), lds, st, px, py, boundary, p, ans, S, T);
+  });
   return check_launch("mi_plain_fwd");
 }
 
@@ -162,8 +164,9 @@ int mi_plain_bwd(const float* px, const float* py, const int32_t* boundary, cons
   if (zero_words(px_grad, (size_t)B * S * T1, st, "mi_plain_bwd") != FTR_OK ||
       zero_words(py_grad, (size_t)B * (S + 1) * T, st, "mi_plain_bwd") != FTR_OK) return FTR_ERR_LAUNCH;
   const int threads = 256;
-  if (modified) hipLaunchKernelGGL(mi_plain_bwd_kernel<true>, dim3(B), dim3(threads), lds, st, px, py, boundary, p, p_grad, px_grad, py_grad, ans_grad, overwrite, S, T);
-  else hipLaunchKernelGGL(mi_plain_bwd_kernel<false>, dim3(B), dim3(threads), lds, st, px, py, boundary, p, p_grad, px_grad, py_grad, ans_grad, overwrite, S, T);
+  dispatch(modified != 0, [&](auto mod) {
+    hipLaunchKernelGGL(mi_plain_bwd_kernel<decltype(mod)::value>, dim3(B), dim3(threads), lds, st, px, py, boundary, p, p_grad, px_grad, py_grad, ans_grad, overwrite, S, T);
+  });
   return check_launch("mi_plain_bwd");
 }
 

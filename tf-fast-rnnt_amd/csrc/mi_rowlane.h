@@ -30,6 +30,7 @@
 #pragma once
 #include <type_traits>
 #include "ftr_common.h"
+#include "launch.h"
 
 namespace ftr {
 namespace rowlane {
@@ -89,15 +90,6 @@ inline bool launch_done(const char* what, int B, int S, int T, size_t have, size
     return true;
   }
   return false;
-}
-
-// f(std::integral_constant<int, n>) for LO <= n <= HI, nothing otherwise: the launchers' switch over a template arity
-template <int LO, int HI, typename F>
-inline void dispatch_arity(int n, F&& f) {
-  if constexpr (LO <= HI) {
-    if (n == LO) f(std::integral_constant<int, LO>{});
-    else dispatch_arity<LO + 1, HI>(n, f);
-  }
 }
 
 // exp(v) for v a float64 log-quantity that is <= ~0 where it matters: the float32 exp2 unit

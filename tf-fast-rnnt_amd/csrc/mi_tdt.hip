@@ -198,10 +198,10 @@ int tdt_launch(const float* px, const float* py, const int32_t* boundary, const 
   double* wsd = reinterpret_cast<double*>(ws);
   double *p = wsd + L.p_off, *ansd = wsd + L.ans_off, *carry = wsd + L.carry_off;
   const size_t lds = (size_t)DEP * 64 * NW * sizeof(double);
-  dispatch_arity<2, MAXM>(Dx + Dy, [&](auto m) {
+  dispatch_range<2, MAXM>(Dx + Dy, [&](auto m) {
     hipLaunchKernelGGL((mi_tdt_kernel<decltype(m)::value, BWD>), dim3(B), dim3(64 * NW), lds, st, px, py, boundary, mv, p,
                        ansd, carry, ans, ans_grad, px_grad, py_grad, S, T, NW, DEP);
-  });
+  }, [] {});   // the entry points admit no other arity
   return check_launch(what);
 }
 

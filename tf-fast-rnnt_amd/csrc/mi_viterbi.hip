@@ -21,6 +21,7 @@
 // by exactly one (py: t-1; px: l-1 and, regular, t / modified, t-1), so the backtrace wave holds a window of 64
 // consecutive words of its block in its 64 lanes (the next lower window in flight) and walks with readlane.
 #include "ftr_common.h"
+#include "launch.h"
 #include "mi_wave_common.h"
 
 namespace ftr {
@@ -259,10 +260,9 @@ int mi_viterbi(const float* px, const float* py, const int32_t* boundary, void* 
   u64* dec = static_cast<u64*>(ws);
   float* carry = reinterpret_cast<float*>(static_cast<char*>(ws) + L.carry_off);
   const int NW = vit_waves(S);
-  if (modified)
-    hipLaunchKernelGGL(mi_viterbi_kernel<true>, dim3(B), dim3(64 * NW), 0, st, px, py, boundary, dec, carry, score, frames, S, T, NW);
-  else
-    hipLaunchKernelGGL(mi_viterbi_kernel<false>, dim3(B), dim3(64 * NW), 0, st, px, py, boundary, dec, carry, score, frames, S, T, NW);
+  dispatch(modified != 0, [&](auto mod) {
+    hipLaunchKernelGGL(mi_viterbi_kernel<decltype(mod)::value>, dim3(B), dim3(64 * NW), 0, st, px, py, boundary, dec, carry, score, frames, S, T, NW);
+  });
   return check_launch("mutual_information_viterbi");
 }
 

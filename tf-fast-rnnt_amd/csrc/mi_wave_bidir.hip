@@ -38,6 +38,7 @@
 //   done[b]  bands of utterance b that have delivered their cut values (the last one runs the cut reduction)
 //   uflags[b] bit 1 = a NaN was read from px / py inside the boundary rectangle of utterance b  ->  ans[b] = NaN
 #include "ftr_common.h"
+#include "launch.h"
 #include "mi_wave_common.h"
 #include <type_traits>
 
@@ -1449,22 +1450,13 @@ inline size_t bidir_lds_bytes() { return (size_t)kFwdTiles * TILE_F4 * sizeof(f4
 // workgroups on a 256-CU chip (profiles/r01_h).  Asking for more LDS than a fair share caps the workgroups per CU at
 // ceil(total / CUs): one per CU while the grid fits the chip.
 inline size_t spread_lds(size_t need, int total_wgs) {
-  static int ncu = 0;
-  if (ncu == 0) {
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || ncu <= 0) ncu = 256;
-  }
+  const int ncu = current_device_cus();
   int target = (total_wgs + ncu - 1) / ncu;
   if (target < 1) target = 1;
   const size_t cap = (size_t)160 * 1024 / (target + 1) + 1024;   // > 1/(target+1) of a CU's 160 KB
   return need > cap ? need : cap;
 }
-template <typename K>
-inline int allow_big_lds(K kernel, const char* what) {
-  hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-  if (e != hipSuccess) { set_error("%s: cannot raise the dynamic LDS limit: %s", what, hipGetErrorString(e)); return FTR_ERR_LAUNCH; }
-  return FTR_OK;
-}
+constexpr size_t kBidirLdsCeiling = 160 * 1024;   // what spread_lds may ask for: the limit is raised to a CU's whole LDS
 
 struct BidirLayout {
   size_t lat;       // floats per ratio lattice (padded)
@@ -1590,16 +1582,13 @@ int mi_bidir_fwd(const float* px, const float* py, const int32_t* boundary, floa
   int* ctrl = reinterpret_cast<int*>(ws + l.ctrl_off);
   const dim3 grid(2 * B * l.NB);
   const size_t lds = spread_lds(bidir_lds_bytes(), (int)grid.x);
-  static bool big_ok = false;
-  if (!big_ok) {
-    rc = allow_big_lds(mi_bidir_fwd_kernel<true>, "mi_bidir_fwd");
-    if (rc == FTR_OK) rc = allow_big_lds(mi_bidir_fwd_kernel<false>, "mi_bidir_fwd");
-    if (rc != FTR_OK) return rc;
-    big_ok = true;
-  }
-  if (modified) hipLaunchKernelGGL(mi_bidir_fwd_kernel<true>, grid, dim3(256), lds, st, px, py, boundary, ws, gran, ws + l.pmid_off, ws + l.occ_off, ws + l.cxy_off, reinterpret_cast<int*>(ws + l.phi_off), ctrl, (int)(status_off(l) - l.ctrl_off), ans, B, l.NB, l.Tg, S, T);
-  else hipLaunchKernelGGL(mi_bidir_fwd_kernel<false>, grid, dim3(256), lds, st, px, py, boundary, ws, gran, ws + l.pmid_off, ws + l.occ_off, ws + l.cxy_off, reinterpret_cast<int*>(ws + l.phi_off), ctrl, (int)(status_off(l) - l.ctrl_off), ans, B, l.NB, l.Tg, S, T);
-  return check_launch("mi_bidir_fwd");
+  return dispatch(modified != 0, [&](auto mod) {
+    constexpr auto kernel = mi_bidir_fwd_kernel<decltype(mod)::value>;
+    const int rcl = reserve_lds<kernel>(kBidirLdsCeiling, "mi_bidir_fwd", LdsText::raise_why);
+    if (rcl != FTR_OK) return rcl;
+    hipLaunchKernelGGL(kernel, grid, dim3(256), lds, st, px, py, boundary, ws, gran, ws + l.pmid_off, ws + l.occ_off, ws + l.cxy_off, reinterpret_cast<int*>(ws + l.phi_off), ctrl, (int)(status_off(l) - l.ctrl_off), ans, B, l.NB, l.Tg, S, T);
+    return check_launch("mi_bidir_fwd");
+  });
 }
 
 int mi_bidir_bwd(const int32_t* boundary, const float* ws, size_t ws_floats, int flags, float* px_grad, float* py_grad,
@@ -1626,16 +1615,13 @@ int mi_bidir_bwd(const int32_t* boundary, const float* ws, size_t ws_floats, int
   int* ctrl = reinterpret_cast<int*>(wsm + l.ctrl_off);
   const dim3 grid(2 * B * l.NB);
   const size_t lds = spread_lds(bidir_lds_bytes(), (int)grid.x);
-  static bool big_ok = false;
-  if (!big_ok) {
-    rc = allow_big_lds(mi_bidir_flow_kernel<true>, "mi_bidir_bwd");
-    if (rc == FTR_OK) rc = allow_big_lds(mi_bidir_flow_kernel<false>, "mi_bidir_bwd");
-    if (rc != FTR_OK) return rc;
-    big_ok = true;
-  }
-  if (modified) hipLaunchKernelGGL(mi_bidir_flow_kernel<true>, grid, dim3(kFlowThreads), lds, st, boundary, ws, gran, ws + l.occ_off, px_grad, py_grad, seed, check, ctrl + (status_off(l) - l.ctrl_off), ans, loss_out, loss_code, B, l.NB, l.Tg, S, T);
-  else hipLaunchKernelGGL(mi_bidir_flow_kernel<false>, grid, dim3(kFlowThreads), lds, st, boundary, ws, gran, ws + l.occ_off, px_grad, py_grad, seed, check, ctrl + (status_off(l) - l.ctrl_off), ans, loss_out, loss_code, B, l.NB, l.Tg, S, T);
-  return check_launch("mi_bidir_bwd");
+  return dispatch(modified != 0, [&](auto mod) {
+    constexpr auto kernel = mi_bidir_flow_kernel<decltype(mod)::value>;
+    const int rcl = reserve_lds<kernel>(kBidirLdsCeiling, "mi_bidir_bwd", LdsText::raise_why);
+    if (rcl != FTR_OK) return rcl;
+    hipLaunchKernelGGL(kernel, grid, dim3(kFlowThreads), lds, st, boundary, ws, gran, ws + l.occ_off, px_grad, py_grad, seed, check, ctrl + (status_off(l) - l.ctrl_off), ans, loss_out, loss_code, B, l.NB, l.Tg, S, T);
+    return check_launch("mi_bidir_bwd");
+  });
 }
 
 int selftest(hipStream_t st, int* result_dev) {

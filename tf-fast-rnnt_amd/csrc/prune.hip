@@ -10,6 +10,7 @@
 // All integer results are bit-exact with oracle/mi_oracle.c; the float window sums use the same
 // canonical order (sequential f32 cumsum along S, additions only -> no contraction possible).
 #include "ftr_common.h"
+#include "launch.h"
 #include <cstdlib>
 #include <limits.h>
 
@@ -801,26 +802,22 @@ int do_pruning_bwd(const float* g_am_p, const float* g_lm_p, const int32_t* rang
                    int T, int S1, int C, int r, hipStream_t st) {
   if ((size_t)B * T * C == 0) return FTR_OK;
   const int threads = 256;
-  if ((C & 3) == 0) {
-    const size_t total = (size_t)B * T * (C >> 2);
-    hipLaunchKernelGGL(do_pruning_bwd_am_kernel<true>, dim3((unsigned)((total + threads - 1) / threads)), dim3(threads), 0, st, g_am_p, d_am, C, r, total);
-  } else {
-    const size_t total = (size_t)B * T * C;
-    hipLaunchKernelGGL(do_pruning_bwd_am_kernel<false>, dim3((unsigned)((total + threads - 1) / threads)), dim3(threads), 0, st, g_am_p, d_am, C, r, total);
-  }
+  const bool vec = (C & 3) == 0;
+  dispatch(vec, [&](auto v) {
+    const size_t total = (size_t)B * T * (decltype(v)::value ? C >> 2 : C);
+    hipLaunchKernelGGL(do_pruning_bwd_am_kernel<decltype(v)::value>, dim3((unsigned)((total + threads - 1) / threads)), dim3(threads), 0, st, g_am_p, d_am, C, r, total);
+  });
   int rc = check_launch("do_pruning_bwd_am");
   if (rc != FTR_OK) return rc;
   const size_t lds = sizeof(int) * (size_t)T * r;   // worst case: every (t,k) selects the same row
   if (lds > 150 * 1024) { set_error("do_pruning_bwd: T*s_range = %d too large for the LDS row list", T * r); return FTR_ERR_UNSUPPORTED; }
-  const bool vec = (C & 3) == 0;
-  if (lds > 64 * 1024) {
-    hipError_t e = vec ? hipFuncSetAttribute(reinterpret_cast<const void*>(do_pruning_bwd_lm_kernel<true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)
-                       : hipFuncSetAttribute(reinterpret_cast<const void*>(do_pruning_bwd_lm_kernel<false>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) { set_error("do_pruning_bwd: cannot reserve LDS: %s", hipGetErrorString(e)); return FTR_ERR_LAUNCH; }
-  }
-  if (vec) hipLaunchKernelGGL(do_pruning_bwd_lm_kernel<true>, dim3(S1, B), dim3(64), lds, st, g_lm_p, ranges, d_lm, T, S1, C, r);
-  else hipLaunchKernelGGL(do_pruning_bwd_lm_kernel<false>, dim3(S1, B), dim3(64), lds, st, g_lm_p, ranges, d_lm, T, S1, C, r);
-  return check_launch("do_pruning_bwd_lm");
+  return dispatch(vec, [&](auto v) {
+    constexpr auto kernel = do_pruning_bwd_lm_kernel<decltype(v)::value>;
+    const int rcl = reserve_lds<kernel>(lds, "do_pruning_bwd", LdsText::reserve_why);
+    if (rcl != FTR_OK) return rcl;
+    hipLaunchKernelGGL(kernel, dim3(S1, B), dim3(64), lds, st, g_lm_p, ranges, d_lm, T, S1, C, r);
+    return check_launch("do_pruning_bwd_lm");
+  });
 }
 
 int cummin_i32(const int32_t* in, int32_t* out, int rows, int cols, hipStream_t st) {
@@ -836,7 +833,6 @@ int prune_ranges(const float* px_grad, const float* py_grad, const int32_t* boun
   if (B == 0 || T == 0) return FTR_OK;
   const int threads = 64;  // small blocks: B*T threads is only ~32k at the headline shape, spread them
   const dim3 grid((T + threads - 1) / threads, B);
-#define FTR_ARGMAX_ONCE(R) case R: hipLaunchKernelGGL(prune_argmax_once_kernel<R>, grid, dim3(threads), 0, st, px_grad, py_grad, boundary, s_begin, B, S, T, T1); break;
   const int nwin = S + 1 - r + 1;
   // the split kernel, where one wave per 64 columns leaves the chip short of waves (c3: 512 of them on 256 CUs, 41.5 -> 34 us); with a
   // thousand and more the one-wave kernel already keeps 8 waves per CU loading and the split only costs (c4 67 -> 109 us,
@@ -846,13 +842,9 @@ int prune_ranges(const float* px_grad, const float* py_grad, const int32_t* boun
     const int nw = nc < 8 ? nc : 8;
     hipLaunchKernelGGL(prune_argmax_split_kernel, dim3((T + 63) / 64, B), dim3(64 * nw), 0, st, px_grad, py_grad, boundary, s_begin, B, S, T, T1, r);
   } else
-  switch (r) {   // window lengths up to 16: py_grad is loaded once; longer windows: the generic kernel
-    FTR_ARGMAX_ONCE(1) FTR_ARGMAX_ONCE(2) FTR_ARGMAX_ONCE(3) FTR_ARGMAX_ONCE(4) FTR_ARGMAX_ONCE(5) FTR_ARGMAX_ONCE(6)
-    FTR_ARGMAX_ONCE(7) FTR_ARGMAX_ONCE(8) FTR_ARGMAX_ONCE(9) FTR_ARGMAX_ONCE(10) FTR_ARGMAX_ONCE(11) FTR_ARGMAX_ONCE(12)
-    FTR_ARGMAX_ONCE(13) FTR_ARGMAX_ONCE(14) FTR_ARGMAX_ONCE(15) FTR_ARGMAX_ONCE(16)
-    default: hipLaunchKernelGGL(prune_argmax_kernel, grid, dim3(threads), 0, st, px_grad, py_grad, boundary, s_begin, B, S, T, T1, r);
-  }
-#undef FTR_ARGMAX_ONCE
+    dispatch_range<1, 16>(r,   // window lengths up to 16: py_grad is loaded once; longer windows: the generic kernel
+      [&](auto rr) { hipLaunchKernelGGL(prune_argmax_once_kernel<decltype(rr)::value>, grid, dim3(threads), 0, st, px_grad, py_grad, boundary, s_begin, B, S, T, T1); },
+      [&] { hipLaunchKernelGGL(prune_argmax_kernel, grid, dim3(threads), 0, st, px_grad, py_grad, boundary, s_begin, B, S, T, T1, r); });
   int rc = check_launch("prune_argmax");
   if (rc != FTR_OK) return rc;
   const int r_con = (T1 == T) ? 2 : r;  // rnnt_loss.py:756
@@ -865,8 +857,9 @@ int do_pruning(const float* am, const float* lm, const int32_t* ranges, float* a
   const size_t frames = (size_t)B * T;
   if (frames == 0 || C == 0 || r == 0) return FTR_OK;
   { const int rc32 = require_rows_32bit("do_pruning", frames * (size_t)r); if (rc32 != FTR_OK) return rc32; }
-  if ((C & 3) == 0) hipLaunchKernelGGL(do_pruning_kernel<true>, dim3((unsigned)frames), dim3(128), 0, st, am, lm, ranges, am_p, lm_p, T, S1, C, r);
-  else hipLaunchKernelGGL(do_pruning_kernel<false>, dim3((unsigned)frames), dim3(128), 0, st, am, lm, ranges, am_p, lm_p, T, S1, C, r);
+  dispatch((C & 3) == 0, [&](auto vec) {
+    hipLaunchKernelGGL(do_pruning_kernel<decltype(vec)::value>, dim3((unsigned)frames), dim3(128), 0, st, am, lm, ranges, am_p, lm_p, T, S1, C, r);
+  });
   return check_launch("do_pruning");
 }
 
@@ -901,15 +894,11 @@ int do_pruning_bwd_ws(const float* g_am_p, const float* g_lm_p, const int32_t* r
     int rc = check_launch("do_pruning_bwd_am");
     if (rc != FTR_OK) return rc;
   }
-#define FTR_SEG(R) case R: \
-    if (fuse) hipLaunchKernelGGL((ftr::do_pruning_bwd_seg_kernel<R, true>), dim3(nseg, B), dim3(128), lds, st, g_lm_p, ranges, d_am, d_lm, partial, meta, T, S1, C, seg); \
-    else hipLaunchKernelGGL((ftr::do_pruning_bwd_seg_kernel<R, false>), dim3(nseg, B), dim3(128), lds, st, g_lm_p, ranges, d_am, d_lm, partial, meta, T, S1, C, seg); \
-    break;
-  switch (r) {
-    FTR_SEG(1) FTR_SEG(2) FTR_SEG(3) FTR_SEG(4) FTR_SEG(5) FTR_SEG(6) FTR_SEG(7) FTR_SEG(8)
-    FTR_SEG(9) FTR_SEG(10) FTR_SEG(11) FTR_SEG(12) FTR_SEG(13) FTR_SEG(14) FTR_SEG(15) FTR_SEG(16)
-  }
-#undef FTR_SEG
+  dispatch_range<1, ftr::kSegMaxR>(r, [&](auto rr) {   // r <= kSegMaxR was checked above
+    dispatch(fuse, [&](auto fu) {
+      hipLaunchKernelGGL((ftr::do_pruning_bwd_seg_kernel<decltype(rr)::value, decltype(fu)::value>), dim3(nseg, B), dim3(128), lds, st, g_lm_p, ranges, d_am, d_lm, partial, meta, T, S1, C, seg);
+    });
+  }, [] {});
   int rc = check_launch("do_pruning_bwd_seg");
   if (rc != FTR_OK) return rc;
   hipLaunchKernelGGL(ftr::do_pruning_bwd_reduce_kernel, dim3(S1, B), dim3(64 * ftr::RED_WAVES),

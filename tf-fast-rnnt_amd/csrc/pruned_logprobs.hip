@@ -10,6 +10,7 @@
 // differently -- lse holds Z = logsumexp over the non-blank columns, py = log sigmoid(x[blank]),
 // px = x[sym] - Z - softplus(x[blank]) (-inf when sym == blank); the HAT = false instantiations are the ordinary kernels.
 #include "ftr_common.h"
+#include "launch.h"
 
 namespace ftr {
 namespace {
@@ -257,22 +258,22 @@ int negated_reduce(const float* ans, int B, int reduction, float* out, hipStream
 
 // logsumexp over the last axis of [rows, C] (rnnt_loss.py:942): picks the register-resident kernel where it fits
 // (hat: over the non-blank columns only, the normaliser Z of the HAT factorisation)
-template <bool HAT>
-static void lse_rows_launch(const float* logits, float* lse, size_t rows, int C, int blank, hipStream_t st) {
-  const int wpb = 4;
-  const unsigned blocks = (unsigned)((rows + wpb - 1) / wpb);
-  if ((C & 3) == 0 && C <= 256) hipLaunchKernelGGL((lse_rows_reg_kernel<1, HAT>), dim3(blocks), dim3(64 * wpb), 0, st, logits, lse, rows, C, blank);
-  else if ((C & 3) == 0 && C <= 512) hipLaunchKernelGGL((lse_rows_reg_kernel<2, HAT>), dim3(blocks), dim3(64 * wpb), 0, st, logits, lse, rows, C, blank);
-  else if ((C & 3) == 0 && C <= 1024) hipLaunchKernelGGL((lse_rows_reg_kernel<4, HAT>), dim3(blocks), dim3(64 * wpb), 0, st, logits, lse, rows, C, blank);
-  else if ((C & 3) == 0 && C <= 2048) hipLaunchKernelGGL((lse_rows_reg_kernel<8, HAT>), dim3(blocks), dim3(64 * wpb), 0, st, logits, lse, rows, C, blank);
-  else if ((C & 3) == 0) hipLaunchKernelGGL((lse_rows_kernel<true, HAT>), dim3(blocks), dim3(64 * wpb), 0, st, logits, lse, rows, C, blank);
-  else hipLaunchKernelGGL((lse_rows_kernel<false, HAT>), dim3(blocks), dim3(64 * wpb), 0, st, logits, lse, rows, C, blank);
-}
 int lse_rows(const float* logits, float* lse, size_t rows, int C, int blank, int hat, hipStream_t st) {
   if (rows == 0) return FTR_OK;
   { const int rc32 = require_rows_32bit("lse_rows", rows); if (rc32 != FTR_OK) return rc32; }
-  if (hat) lse_rows_launch<true>(logits, lse, rows, C, blank, st);
-  else lse_rows_launch<false>(logits, lse, rows, C, blank, st);
+  const int wpb = 4;
+  const unsigned blocks = (unsigned)((rows + wpb - 1) / wpb);
+  dispatch(hat != 0, [&](auto h) {
+    constexpr bool HAT = decltype(h)::value;
+    if ((C & 3) == 0 && C <= 2048)   // the row fits the registers of a wave: 1, 2, 4 or 8 float4 per lane
+      dispatch_among<1, 2, 4, 8>(C <= 256 ? 1 : C <= 512 ? 2 : C <= 1024 ? 4 : 8, [&](auto n) {
+        hipLaunchKernelGGL((lse_rows_reg_kernel<decltype(n)::value, HAT>), dim3(blocks), dim3(64 * wpb), 0, st, logits, lse, rows, C, blank);
+      });
+    else
+      dispatch((C & 3) == 0, [&](auto vec) {
+        hipLaunchKernelGGL((lse_rows_kernel<decltype(vec)::value, HAT>), dim3(blocks), dim3(64 * wpb), 0, st, logits, lse, rows, C, blank);
+      });
+  });
   return check_launch("lse_rows");
 }
 
@@ -286,11 +287,12 @@ int pruned_logprobs_fwd(const float* logits, const int32_t* symbols, const int32
   if (rc != FTR_OK) return rc;
   const int threads = 256;
   const dim3 grid((T + 1 + threads - 1) / threads, S + 1, B);
-#define FTR_LAUNCH_BL(MODV, HATV) hipLaunchKernelGGL((band_to_lattice_kernel<MODV, HATV>), grid, dim3(threads), 0, st, \
-    logits, symbols, ranges, boundary, lse, blank, delay_penalty, px, py, T, S, C, r)
-  if (modified) { if (hat) FTR_LAUNCH_BL(true, true); else FTR_LAUNCH_BL(true, false); }
-  else { if (hat) FTR_LAUNCH_BL(false, true); else FTR_LAUNCH_BL(false, false); }
-#undef FTR_LAUNCH_BL
+  dispatch(modified != 0, [&](auto mod) {
+    dispatch(hat != 0, [&](auto h) {
+      hipLaunchKernelGGL((band_to_lattice_kernel<decltype(mod)::value, decltype(h)::value>), grid, dim3(threads), 0, st,
+                         logits, symbols, ranges, boundary, lse, blank, delay_penalty, px, py, T, S, C, r);
+    });
+  });
   return check_launch("band_to_lattice");
 }
 
@@ -303,14 +305,14 @@ int pruned_logprobs_bwd(const float* logits, const int32_t* symbols, const int32
   { const int rc32 = require_rows_32bit("pruned_logprobs_bwd", rows); if (rc32 != FTR_OK) return rc32; }
   const int wpb = 4;
   const unsigned blocks = (unsigned)((rows + wpb - 1) / wpb);
-  const bool vec = (C & 3) == 0;
-#define FTR_LAUNCH_BG(MODV, VECV, HATV) hipLaunchKernelGGL((band_grad_kernel<MODV, VECV, HATV>), dim3(blocks), dim3(64 * wpb), 0, st, \
-    logits, symbols, ranges, boundary, lse, gpx, gpy, scale, blank, glogits, rows, T, S, C, r)
-#define FTR_LAUNCH_BGV(MODV, HATV) do { if (vec) FTR_LAUNCH_BG(MODV, true, HATV); else FTR_LAUNCH_BG(MODV, false, HATV); } while (0)
-  if (modified) { if (hat) FTR_LAUNCH_BGV(true, true); else FTR_LAUNCH_BGV(true, false); }
-  else { if (hat) FTR_LAUNCH_BGV(false, true); else FTR_LAUNCH_BGV(false, false); }
-#undef FTR_LAUNCH_BGV
-#undef FTR_LAUNCH_BG
+  dispatch(modified != 0, [&](auto mod) {
+    dispatch((C & 3) == 0, [&](auto vec) {
+      dispatch(hat != 0, [&](auto h) {
+        hipLaunchKernelGGL((band_grad_kernel<decltype(mod)::value, decltype(vec)::value, decltype(h)::value>), dim3(blocks), dim3(64 * wpb), 0, st,
+                           logits, symbols, ranges, boundary, lse, gpx, gpy, scale, blank, glogits, rows, T, S, C, r);
+      });
+    });
+  });
   return check_launch("band_grad");
 }
 
@@ -480,12 +482,10 @@ int multiblank_logprobs_bwd(const float* logits, const int32_t* symbols, const i
   const int wpb = 4;
   const unsigned blocks = (unsigned)((rows + wpb - 1) / wpb);
   const MbCols mc = mb_cols(blank, big_ids, durations, D);
-  if ((C & 3) == 0)
-    hipLaunchKernelGGL((mb_grad_kernel<true>), dim3(blocks), dim3(64 * wpb), 0, st, logits, symbols, ranges, boundary, lse,
+  dispatch((C & 3) == 0, [&](auto vec) {
+    hipLaunchKernelGGL((mb_grad_kernel<decltype(vec)::value>), dim3(blocks), dim3(64 * wpb), 0, st, logits, symbols, ranges, boundary, lse,
                        gpx, gpy, scale, mc, glogits, rows, T, S, C, r);
-  else
-    hipLaunchKernelGGL((mb_grad_kernel<false>), dim3(blocks), dim3(64 * wpb), 0, st, logits, symbols, ranges, boundary, lse,
-                       gpx, gpy, scale, mc, glogits, rows, T, S, C, r);
+  });
   return check_launch("multiblank_grad");
 }
 

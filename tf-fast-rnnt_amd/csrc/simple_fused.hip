@@ -15,6 +15,7 @@
 // MFMA operand roles: A = am_probs tile (M = frames), B = lm_probs tile (N = symbol rows), so that an accumulator
 // register quad holds four CONSECUTIVE FRAMES of one symbol row: px / py / prod rows are written 16 bytes per lane.
 #include "ftr_common.h"
+#include "launch.h"
 #include <cstdlib>
 
 namespace ftr {
@@ -623,33 +624,21 @@ int simple_fused_fwd(const float* am, const float* lm, const int32_t* symbols, c
   const dim3 grid((T1 + 64 * mb - 1) / (64 * mb), (blocks + ns - 1) / ns, B);
   if (grid.z > 65535) { set_error("simple_logprobs_fused_fwd: B = %d > 65535", B); return FTR_ERR_UNSUPPORTED; }
   const bool smooth = lmonly_norm != nullptr;
-#define FTR_FUSED_LAUNCH(MODV, SMV, NSV, MBV)                                                                              \
-  do {                                                                                                                     \
-    static bool raised = false;                                                                                            \
-    if (!raised && fused_lds_bytes<NSV, MBV>() > 64 * 1024) {                                                              \
-      if (hipFuncSetAttribute(reinterpret_cast<const void*>(simple_fused_fwd_kernel<MODV, SMV, NSV, MBV>),                  \
-                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)fused_lds_bytes<NSV, MBV>()) != hipSuccess) { \
-        (void)hipGetLastError(); set_error("simple_logprobs_fused_fwd: cannot raise the dynamic LDS limit"); return FTR_ERR_LAUNCH; \
-      }                                                                                                                    \
-      raised = true;                                                                                                       \
-    }                                                                                                                      \
-    hipLaunchKernelGGL((simple_fused_fwd_kernel<MODV, SMV, NSV, MBV>), grid, dim3(256), (fused_lds_bytes<NSV, MBV>()), st,   \
-                       am, lm, symbols, am_probs, lm_probs, am_max, lm_max, boundary, blank, delay_penalty, lmonly_norm,   \
-                       amonly_norm, ulog, cs, ls, as, px, py, prod_out, T, S, C);                                         \
-  } while (0)
-#define FTR_FUSED_MB(MODV, SMV, NSV)                                                                                       \
-  do { if (mb == 2) FTR_FUSED_LAUNCH(MODV, SMV, NSV, 2); else FTR_FUSED_LAUNCH(MODV, SMV, NSV, 1); } while (0)
-#define FTR_FUSED_NS(MODV, SMV)                                                                                            \
-  do {                                                                                                                     \
-    if (ns == 4) FTR_FUSED_MB(MODV, SMV, 4); else if (ns == 7) FTR_FUSED_MB(MODV, SMV, 7);                                  \
-    else if (ns == 10) FTR_FUSED_MB(MODV, SMV, 10); else FTR_FUSED_MB(MODV, SMV, 13);                                       \
-  } while (0)
-  if (modified) { if (smooth) FTR_FUSED_NS(true, true); else FTR_FUSED_NS(true, false); }
-  else { if (smooth) FTR_FUSED_NS(false, true); else FTR_FUSED_NS(false, false); }
-#undef FTR_FUSED_NS
-#undef FTR_FUSED_MB
-#undef FTR_FUSED_LAUNCH
-  return check_launch("simple_logprobs_fused_fwd");
+  return dispatch(modified != 0, [&](auto mod) {
+    return dispatch(smooth, [&](auto sm) {
+      return dispatch_among<4, 7, 10, 13>(ns, [&](auto nsv) {
+        return dispatch_among<2, 1>(mb, [&](auto mbv) {
+          constexpr auto kernel = simple_fused_fwd_kernel<decltype(mod)::value, decltype(sm)::value, decltype(nsv)::value, decltype(mbv)::value>;
+          constexpr size_t lds = fused_lds_bytes<decltype(nsv)::value, decltype(mbv)::value>();
+          const int rc = reserve_lds<kernel>(lds, "simple_logprobs_fused_fwd");
+          if (rc != FTR_OK) return rc;
+          hipLaunchKernelGGL(kernel, grid, dim3(256), lds, st, am, lm, symbols, am_probs, lm_probs, am_max, lm_max, boundary, blank,
+                             delay_penalty, lmonly_norm, amonly_norm, ulog, cs, ls, as, px, py, prod_out, T, S, C);
+          return check_launch("simple_logprobs_fused_fwd");
+        });
+      });
+    });
+  });
 }
 
 // 0: outside the fused backward kernel's domain (needs C % 4 == 0, T % 4 == 0, C >= 4, T >= 4): the caller then takes
@@ -668,8 +657,9 @@ int simple_fused_bwd_am(const float* gpx, const float* gpy, Scale scale, const f
   }
   const dim3 grid((T + kBT - 1) / kBT, (C + 16 * kBCB - 1) / (16 * kBCB), B);
   if (grid.z > 65535) { set_error("simple_logprobs_fused_bwd_am: B = %d > 65535", B); return FTR_ERR_UNSUPPORTED; }
-  if (modified) hipLaunchKernelGGL(simple_fused_bwd_am_kernel<true>, grid, dim3(256), fused_bwd_lds_bytes(), st, gpx, gpy, scale, prod, lm_probs, am_probs, symbols, boundary, blank, cs, kdir, uvec, amdot, as, Rout, d_am, T, S, C);
-  else hipLaunchKernelGGL(simple_fused_bwd_am_kernel<false>, grid, dim3(256), fused_bwd_lds_bytes(), st, gpx, gpy, scale, prod, lm_probs, am_probs, symbols, boundary, blank, cs, kdir, uvec, amdot, as, Rout, d_am, T, S, C);
+  dispatch(modified != 0, [&](auto mod) {
+    hipLaunchKernelGGL(simple_fused_bwd_am_kernel<decltype(mod)::value>, grid, dim3(256), fused_bwd_lds_bytes(), st, gpx, gpy, scale, prod, lm_probs, am_probs, symbols, boundary, blank, cs, kdir, uvec, amdot, as, Rout, d_am, T, S, C);
+  });
   return check_launch("simple_logprobs_fused_bwd_am");
 }
 

@@ -16,6 +16,7 @@
 //                          (each accumulator cell is owned by exactly one thread: deterministic, no atomics)
 //   simple_bwd_lm_kernel   d lm = (W am_probs) * lm_probs + row sums at the symbol / blank columns
 #include "ftr_common.h"
+#include "launch.h"
 
 namespace ftr {
 namespace {
@@ -550,8 +551,9 @@ int simple_rowmax_exp(const float* x, float* probs, float* rowmax, float* rowsum
   if (rows == 0 || C == 0) return FTR_OK;
   const int wpb = 4;
   const unsigned blocks = (unsigned)((rows + wpb - 1) / wpb);
-  if ((C & 3) == 0) hipLaunchKernelGGL(rowmax_exp_kernel<true>, dim3(blocks), dim3(64 * wpb), 0, st, x, probs, rowmax, rowsum, dotvec, dot, rows, C);
-  else hipLaunchKernelGGL(rowmax_exp_kernel<false>, dim3(blocks), dim3(64 * wpb), 0, st, x, probs, rowmax, rowsum, dotvec, dot, rows, C);
+  dispatch((C & 3) == 0, [&](auto vec) {
+    hipLaunchKernelGGL(rowmax_exp_kernel<decltype(vec)::value>, dim3(blocks), dim3(64 * wpb), 0, st, x, probs, rowmax, rowsum, dotvec, dot, rows, C);
+  });
   return check_launch("rowmax_exp");
 }
 
@@ -560,8 +562,9 @@ int simple_rowmax_exp_pair(const float* x1, float* probs1, float* rowmax1, size_
   if (rows1 + rows2 == 0 || C == 0) return FTR_OK;
   const int wpb = 4;
   const unsigned blocks = (unsigned)((rows1 + rows2 + wpb - 1) / wpb);
-  if ((C & 3) == 0) hipLaunchKernelGGL(rowmax_exp_pair_kernel<true>, dim3(blocks), dim3(64 * wpb), 0, st, x1, probs1, rowmax1, rows1, x2, probs2, rowmax2, rows2, C);
-  else hipLaunchKernelGGL(rowmax_exp_pair_kernel<false>, dim3(blocks), dim3(64 * wpb), 0, st, x1, probs1, rowmax1, rows1, x2, probs2, rowmax2, rows2, C);
+  dispatch((C & 3) == 0, [&](auto vec) {
+    hipLaunchKernelGGL(rowmax_exp_pair_kernel<decltype(vec)::value>, dim3(blocks), dim3(64 * wpb), 0, st, x1, probs1, rowmax1, rows1, x2, probs2, rowmax2, rows2, C);
+  });
   return check_launch("rowmax_exp_pair");
 }
 
@@ -569,8 +572,9 @@ int simple_rowdot(const float* x, const float* v, float* dot, size_t rows, int C
   if (rows == 0) return FTR_OK;
   const int wpb = 4;
   const unsigned blocks = (unsigned)((rows + wpb - 1) / wpb);
-  if ((C & 3) == 0) hipLaunchKernelGGL(rowdot_kernel<true>, dim3(blocks), dim3(64 * wpb), 0, st, x, v, dot, rows, C);
-  else hipLaunchKernelGGL(rowdot_kernel<false>, dim3(blocks), dim3(64 * wpb), 0, st, x, v, dot, rows, C);
+  dispatch((C & 3) == 0, [&](auto vec) {
+    hipLaunchKernelGGL(rowdot_kernel<decltype(vec)::value>, dim3(blocks), dim3(64 * wpb), 0, st, x, v, dot, rows, C);
+  });
   return check_launch("rowdot");
 }
 
@@ -583,8 +587,10 @@ int simple_colsum_weighted(const float* x, const float* w, float* out, float* ws
   if (ws_floats < nslab * (size_t)C) { set_error("colsum_weighted: workspace of %zu floats, %zu needed", ws_floats, nslab * (size_t)C); return FTR_ERR_INVALID_ARG; }
   if (nslab > 0x7fffffff) { set_error("colsum_weighted: too many rows"); return FTR_ERR_UNSUPPORTED; }
   if (nslab > 0) {
-    if ((C & 3) == 0) hipLaunchKernelGGL(colsum_partial_kernel<true>, dim3((unsigned)nslab, (C / 4 + 255) / 256), dim3(256), 0, st, x, w, ws, rows, C);
-    else hipLaunchKernelGGL(colsum_partial_kernel<false>, dim3((unsigned)nslab, (C + 255) / 256), dim3(256), 0, st, x, w, ws, rows, C);
+    dispatch((C & 3) == 0, [&](auto vec) {
+      const int cols = decltype(vec)::value ? C / 4 : C;   // a thread takes four columns or one
+      hipLaunchKernelGGL(colsum_partial_kernel<decltype(vec)::value>, dim3((unsigned)nslab, (cols + 255) / 256), dim3(256), 0, st, x, w, ws, rows, C);
+    });
     int rc = check_launch("colsum_weighted (partial)");
     if (rc != FTR_OK) return rc;
   }
@@ -597,45 +603,36 @@ static int tile_lds_ok(size_t lds, const char* what) {
   return FTR_OK;
 }
 
-template <typename K>
-static int reserve_lds(K kernel, size_t lds, const char* what) {
-  if (lds > 64 * 1024) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) { set_error("%s: cannot reserve %zu bytes of LDS: %s", what, lds, hipGetErrorString(e)); return FTR_ERR_LAUNCH; }
-  }
-  return FTR_OK;
-}
-
 int simple_logprobs_fwd(const float* am, const float* lm, const int32_t* symbols, const float* prod,
                         const float* am_max, const float* lm_max, const int32_t* boundary, int blank,
                         double delay_penalty, const float* lmonly_norm, const float* amonly_norm, const float* ulog,
                         float cs, float ls, float as, float* px, float* py, int B, int T, int S, int C, int modified,
                         hipStream_t st) {
   const int T1 = modified ? T : T + 1;
-  const bool narrow = C > kTTnarrowAbove;
-  const int TT = narrow ? kTTnarrow : kTTwide;
+  const int TT = C > kTTnarrowAbove ? kTTnarrow : kTTwide;
   const size_t lds = sizeof(float) * ((size_t)TT * (C + 1) + 6 * (size_t)(S + 1));
   int rc = tile_lds_ok(lds, "simple_logprobs_fwd");
   if (rc != FTR_OK) return rc;
   const dim3 grid((T1 + TT - 1) / TT, B);
-#define FTR_LAUNCH_FWD(MODV, TTV)                                                                                       \
-  do {                                                                                                                  \
-    if ((rc = reserve_lds(simple_fwd_kernel<MODV, TTV>, lds, "simple_logprobs_fwd")) != FTR_OK) return rc;              \
-    hipLaunchKernelGGL((simple_fwd_kernel<MODV, TTV>), grid, dim3(256), lds, st, am, lm, symbols, prod, am_max, lm_max, \
-                       boundary, blank, delay_penalty, lmonly_norm, amonly_norm, ulog, cs, ls, as, px, py, T, S, C);    \
-  } while (0)
-  if (modified) { if (narrow) FTR_LAUNCH_FWD(true, kTTnarrow); else FTR_LAUNCH_FWD(true, kTTwide); }
-  else { if (narrow) FTR_LAUNCH_FWD(false, kTTnarrow); else FTR_LAUNCH_FWD(false, kTTwide); }
-#undef FTR_LAUNCH_FWD
-  return check_launch("simple_logprobs_fwd");
+  return dispatch(modified != 0, [&](auto mod) {
+    return dispatch_among<kTTnarrow, kTTwide>(TT, [&](auto tt) {
+      constexpr auto kernel = simple_fwd_kernel<decltype(mod)::value, decltype(tt)::value>;
+      const int rcl = reserve_lds<kernel>(lds, "simple_logprobs_fwd", LdsText::reserve_bytes_why);
+      if (rcl != FTR_OK) return rcl;
+      hipLaunchKernelGGL(kernel, grid, dim3(256), lds, st, am, lm, symbols, prod, am_max, lm_max,
+                         boundary, blank, delay_penalty, lmonly_norm, amonly_norm, ulog, cs, ls, as, px, py, T, S, C);
+      return check_launch("simple_logprobs_fwd");
+    });
+  });
 }
 
 int simple_logprobs_bwd_w(const float* gpx, const float* gpy, Scale scale, const float* prod, const int32_t* boundary,
                           float* W, float* rsx, float* rsy, float cs, int B, int T, int S, int modified, hipStream_t st) {
   const size_t rows = (size_t)B * (S + 1);
   const dim3 grid((unsigned)((rows + 3) / 4));
-  if (modified) hipLaunchKernelGGL(simple_bwd_w_kernel<true>, grid, dim3(256), 0, st, gpx, gpy, scale, prod, boundary, W, rsx, rsy, cs, T, S, B);
-  else hipLaunchKernelGGL(simple_bwd_w_kernel<false>, grid, dim3(256), 0, st, gpx, gpy, scale, prod, boundary, W, rsx, rsy, cs, T, S, B);
+  dispatch(modified != 0, [&](auto mod) {
+    hipLaunchKernelGGL(simple_bwd_w_kernel<decltype(mod)::value>, grid, dim3(256), 0, st, gpx, gpy, scale, prod, boundary, W, rsx, rsy, cs, T, S, B);
+  });
   return check_launch("simple_logprobs_bwd_w");
 }
 
@@ -644,22 +641,21 @@ int simple_logprobs_bwd_am(const float* gpx, const float* gpy, Scale scale, cons
                            const float* amdot, float as, float* Rout, float* d_am, int B, int T, int S, int C,
                            int modified, hipStream_t st) {
   if (S > 65535) { set_error("simple_logprobs_bwd_am: S = %d > 65535 is not supported", S); return FTR_ERR_UNSUPPORTED; }
-  const bool narrow = C > kTTnarrowAbove;
-  const int TT = narrow ? kTTnarrow : kTTwide;
+  const int TT = C > kTTnarrowAbove ? kTTnarrow : kTTwide;
   const size_t lds = sizeof(float) * ((size_t)TT * (C + 1) + 2 * 256) + sizeof(unsigned short) * (256 / TT) * (size_t)S;
   int rc = tile_lds_ok(lds, "simple_logprobs_bwd_am");
   if (rc != FTR_OK) return rc;
   const dim3 grid((T + TT - 1) / TT, B);
-#define FTR_LAUNCH_AM(MODV, TTV)                                                                                        \
-  do {                                                                                                                  \
-    if ((rc = reserve_lds(simple_bwd_am_kernel<MODV, TTV>, lds, "simple_logprobs_bwd_am")) != FTR_OK) return rc;        \
-    hipLaunchKernelGGL((simple_bwd_am_kernel<MODV, TTV>), grid, dim3(256), lds, st, gpx, gpy, scale, damp, am_probs,    \
-                       symbols, boundary, blank, kdir, uvec, amdot, as, Rout, d_am, T, S, C);                           \
-  } while (0)
-  if (modified) { if (narrow) FTR_LAUNCH_AM(true, kTTnarrow); else FTR_LAUNCH_AM(true, kTTwide); }
-  else { if (narrow) FTR_LAUNCH_AM(false, kTTnarrow); else FTR_LAUNCH_AM(false, kTTwide); }
-#undef FTR_LAUNCH_AM
-  return check_launch("simple_logprobs_bwd_am");
+  return dispatch(modified != 0, [&](auto mod) {
+    return dispatch_among<kTTnarrow, kTTwide>(TT, [&](auto tt) {
+      constexpr auto kernel = simple_bwd_am_kernel<decltype(mod)::value, decltype(tt)::value>;
+      const int rcl = reserve_lds<kernel>(lds, "simple_logprobs_bwd_am", LdsText::reserve_bytes_why);
+      if (rcl != FTR_OK) return rcl;
+      hipLaunchKernelGGL(kernel, grid, dim3(256), lds, st, gpx, gpy, scale, damp, am_probs,
+                         symbols, boundary, blank, kdir, uvec, amdot, as, Rout, d_am, T, S, C);
+      return check_launch("simple_logprobs_bwd_am");
+    });
+  });
 }
 
 int simple_logprobs_bwd_lm(const float* dlmp, const float* lm_probs, const int32_t* symbols, const float* rsx,

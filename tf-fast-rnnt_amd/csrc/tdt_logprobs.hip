@@ -12,6 +12,7 @@
 //                          g_dur[n] = -softmax_dur[n] (GX + GY) + gx_n + gy_j(n)        (no gy term for duration 0)
 // Kernels of their own, in the manner of the mb_* kernels of pruned_logprobs.hip, whose instantiations stay as they are.
 #include "ftr_common.h"
+#include "launch.h"
 
 namespace ftr {
 namespace {
@@ -197,10 +198,9 @@ int tdt_logprobs_fwd(const float* logits, const int32_t* symbols, const int32_t*
   { const int rc32 = require_rows_32bit("tdt_logprobs_fwd", rows); if (rc32 != FTR_OK) return rc32; }
   const int wpb = 4;
   const unsigned blocks = (unsigned)((rows + wpb - 1) / wpb);
-  if (((C + N) & 3) == 0)
-    hipLaunchKernelGGL((tdt_lse_kernel<true>), dim3(blocks), dim3(64 * wpb), 0, st, logits, lse_tok, lse_dur, rows, C, N);
-  else
-    hipLaunchKernelGGL((tdt_lse_kernel<false>), dim3(blocks), dim3(64 * wpb), 0, st, logits, lse_tok, lse_dur, rows, C, N);
+  dispatch(((C + N) & 3) == 0, [&](auto vec) {
+    hipLaunchKernelGGL((tdt_lse_kernel<decltype(vec)::value>), dim3(blocks), dim3(64 * wpb), 0, st, logits, lse_tok, lse_dur, rows, C, N);
+  });
   int rc = check_launch("tdt_lse");
   if (rc != FTR_OK) return rc;
   const int threads = 256;
@@ -219,12 +219,10 @@ int tdt_logprobs_bwd(const float* logits, const int32_t* symbols, const int32_t*
   const int wpb = 4;
   const unsigned blocks = (unsigned)((rows + wpb - 1) / wpb);
   const TdtCols tc = tdt_cols(durations, N);
-  if (((C + N) & 3) == 0)
-    hipLaunchKernelGGL((tdt_grad_kernel<true>), dim3(blocks), dim3(64 * wpb), 0, st, logits, symbols, ranges, boundary,
+  dispatch(((C + N) & 3) == 0, [&](auto vec) {
+    hipLaunchKernelGGL((tdt_grad_kernel<decltype(vec)::value>), dim3(blocks), dim3(64 * wpb), 0, st, logits, symbols, ranges, boundary,
                        lse_tok, lse_dur, gpx, gpy, scale, blank, tc, glogits, rows, T, S, C, r);
-  else
-    hipLaunchKernelGGL((tdt_grad_kernel<false>), dim3(blocks), dim3(64 * wpb), 0, st, logits, symbols, ranges, boundary,
-                       lse_tok, lse_dur, gpx, gpy, scale, blank, tc, glogits, rows, T, S, C, r);
+  });
   return check_launch("tdt_grad");
 }
 
