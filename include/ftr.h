@@ -497,6 +497,8 @@ int ftr_hat_pruned_band_bwd_scaled_f32(const float* logits, const int32_t* symbo
                                        int scale_stride, float scale_mul, float* glogits, int B, int T, int S, int C,
                                        int r, int modified, void* stream);
 
+/* The same four operations (and their HAT forms) on bfloat16 / float16 logits: include/ftr_lowp.h. */
+
 /*
  * Multi-blank transducer (MI355X addition, no reference counterpart; Xu et al., "Multi-blank Transducers for Speech
  * Recognition", ICASSP 2023): besides the standard blank, which advances one frame, K "big blanks" advance d_k >= 2

@@ -1,6 +1,6 @@
-// csrc/capi.hip -- the extern "C" surface declared in include/ftr.h: argument validation and error reporting.  No
+// csrc/capi.hip -- the extern "C" surface declared in include/ftr.h and include/ftr_lowp.h: argument validation and error reporting.  No
 // allocation, no host synchronisation, no CPU fallback.  Built twice: into libftr_hip.so (the product: the symbols of
-// ftr.h and nothing else) and, with -DFTR_DIAG, into the test-only _build/libftr_hip_diag.so, which adds the symbols of
+// ftr.h and ftr_lowp.h and nothing else) and, with -DFTR_DIAG, into the test-only _build/libftr_hip_diag.so, which adds the symbols of
 // include/ftr_diag.h: the "plain" kernel family (the reference's arithmetic on the device, mi_plain.hip), its
 // process-global switch, and the read-out of the trace / stamp builds.
 #include "ftr_common.h"
@@ -97,6 +97,13 @@ int check_s_range(const char* what, int r, int S) {
 }
 int check_scale_stride(const char* what, int scale_stride) {
   FTR_REQUIRE(scale_stride == 0 || scale_stride == 1, "%s: scale_stride must be 0 or 1", what);
+  return FTR_OK;
+}
+// the _dt entries: the element type code and the flags word, before everything else
+int check_dtype(const char* what, int dtype, int flags) {
+  FTR_REQUIRE(dtype == FTR_DTYPE_F32 || dtype == FTR_DTYPE_BF16 || dtype == FTR_DTYPE_FP16,
+              "%s: unknown element type code %d (FTR_DTYPE_F32 = 0, FTR_DTYPE_BF16 = 1, FTR_DTYPE_FP16 = 2)", what, dtype);
+  FTR_REQUIRE((flags & ~FTR_PRUNED_HAT) == 0, "%s: unknown bits in flags %d", what, flags);
   return FTR_OK;
 }
 // the last step of most entries: the pointers, and only then the device
@@ -329,7 +336,7 @@ int ftr_do_pruning_bwd_ws_f32(const float* g_am_pruned, const float* g_lm_pruned
 }
 
 // the ordinary entry point and its HAT twin (hat = 1: blank-excluded normaliser, which needs C >= 2)
-static int pruned_logprobs_fwd_entry(const float* logits, const int32_t* symbols, const int32_t* ranges,
+static int pruned_logprobs_fwd_entry(const void* logits, int dtype, const int32_t* symbols, const int32_t* ranges,
                                      const int32_t* boundary, int termination_symbol, double delay_penalty,
                                      float* lse, float* px, float* py, int B, int T, int S, int C, int r,
                                      int modified, int hat, void* stream) {
@@ -339,21 +346,30 @@ static int pruned_logprobs_fwd_entry(const float* logits, const int32_t* symbols
   FTR_TRY(check_s_range(what, r, S));
   if (B == 0) return FTR_OK;
   FTR_TRY(pointers_then_device(what, logits && symbols && ranges && lse && px && py));
-  return pruned_logprobs_fwd(logits, symbols, ranges, boundary, termination_symbol, delay_penalty, lse, px, py, B, T, S, C, r, modified, hat, stream_of(stream));
+  return pruned_logprobs_fwd(logits, dtype, symbols, ranges, boundary, termination_symbol, delay_penalty, lse, px, py, B, T, S, C, r, modified, hat, stream_of(stream));
 }
 
 int ftr_pruned_logprobs_fwd_f32(const float* logits, const int32_t* symbols, const int32_t* ranges,
                                 const int32_t* boundary, int termination_symbol, double delay_penalty,
                                 float* lse, float* px, float* py, int B, int T, int S, int C, int r,
                                 int modified, void* stream) {
-  return pruned_logprobs_fwd_entry(logits, symbols, ranges, boundary, termination_symbol, delay_penalty, lse, px, py, B, T, S, C, r, modified, 0, stream);
+  return pruned_logprobs_fwd_entry(logits, FTR_DTYPE_F32, symbols, ranges, boundary, termination_symbol, delay_penalty, lse, px, py, B, T, S, C, r, modified, 0, stream);
 }
 
 int ftr_hat_pruned_logprobs_fwd_f32(const float* logits, const int32_t* symbols, const int32_t* ranges,
                                     const int32_t* boundary, int termination_symbol, double delay_penalty,
                                     float* lse, float* px, float* py, int B, int T, int S, int C, int r,
                                     int modified, void* stream) {
-  return pruned_logprobs_fwd_entry(logits, symbols, ranges, boundary, termination_symbol, delay_penalty, lse, px, py, B, T, S, C, r, modified, 1, stream);
+  return pruned_logprobs_fwd_entry(logits, FTR_DTYPE_F32, symbols, ranges, boundary, termination_symbol, delay_penalty, lse, px, py, B, T, S, C, r, modified, 1, stream);
+}
+
+int ftr_pruned_logprobs_fwd_dt(const void* logits, int kind, const int32_t* symbols, const int32_t* ranges,
+                               const int32_t* boundary, int termination_symbol, double delay_penalty, float* lse,
+                               float* px, float* py, int B, int T, int S, int C, int r, int modified, int flags,
+                               void* stream) {
+  clear_error();
+  FTR_TRY(check_dtype("pruned_logprobs_fwd_dt", kind, flags));
+  return pruned_logprobs_fwd_entry(logits, kind, symbols, ranges, boundary, termination_symbol, delay_penalty, lse, px, py, B, T, S, C, r, modified, flags & FTR_PRUNED_HAT, stream);
 }
 
 int ftr_pruned_logprobs_bwd_f32(const float* logits, const int32_t* symbols, const int32_t* ranges,
@@ -365,7 +381,7 @@ int ftr_pruned_logprobs_bwd_f32(const float* logits, const int32_t* symbols, con
   FTR_TRY(check_builder(what, B >= 0 && T >= 1 && S >= 1 && C >= 1 && r >= 1, termination_symbol, C));
   if (B == 0) return FTR_OK;
   FTR_TRY(pointers_then_device(what, logits && symbols && ranges && lse && gpx && gpy && glogits));
-  return pruned_logprobs_bwd(logits, symbols, ranges, boundary, termination_symbol, lse, gpx, gpy, Scale{scale, 1, 1.0f}, glogits, B, T, S, C, r, modified, 0, stream_of(stream));
+  return pruned_logprobs_bwd(logits, FTR_DTYPE_F32, symbols, ranges, boundary, termination_symbol, lse, gpx, gpy, Scale{scale, 1, 1.0f}, glogits, B, T, S, C, r, modified, 0, stream_of(stream));
 }
 
 // rowmax_exp, _sum (rowsum) and _dot (dotvec, dot): one pass, the outputs the entry asks for
@@ -571,10 +587,10 @@ int ftr_negated_reduce_f32(const float* ans, int B, int reduction, float* out, v
   return negated_reduce(ans, B, reduction, out, stream_of(stream));
 }
 
-static int pruned_logprobs_bwd_scaled_entry(const float* logits, const int32_t* symbols, const int32_t* ranges,
+static int pruned_logprobs_bwd_scaled_entry(const void* logits, int dtype, const int32_t* symbols, const int32_t* ranges,
                                             const int32_t* boundary, int termination_symbol, const float* lse,
                                             const float* gpx, const float* gpy, const float* scale, int scale_stride,
-                                            float scale_mul, float* glogits, int B, int T, int S, int C, int r,
+                                            float scale_mul, void* glogits, int B, int T, int S, int C, int r,
                                             int modified, int hat, void* stream) {
   const char* what = hat ? "hat_pruned_logprobs_bwd_scaled" : "pruned_logprobs_bwd_scaled";
   clear_error();
@@ -582,7 +598,7 @@ static int pruned_logprobs_bwd_scaled_entry(const float* logits, const int32_t* 
   FTR_TRY(check_scale_stride(what, scale_stride));
   if (B == 0) return FTR_OK;
   FTR_TRY(pointers_then_device(what, logits && ranges && lse && gpy && glogits && (symbols || S == 0) && (gpx || S == 0)));
-  return pruned_logprobs_bwd(logits, symbols, ranges, boundary, termination_symbol, lse, gpx, gpy, Scale{scale, scale_stride, scale_mul}, glogits, B, T, S, C, r, modified, hat, stream_of(stream));
+  return pruned_logprobs_bwd(logits, dtype, symbols, ranges, boundary, termination_symbol, lse, gpx, gpy, Scale{scale, scale_stride, scale_mul}, glogits, B, T, S, C, r, modified, hat, stream_of(stream));
 }
 
 int ftr_pruned_logprobs_bwd_scaled_f32(const float* logits, const int32_t* symbols, const int32_t* ranges,
@@ -590,7 +606,7 @@ int ftr_pruned_logprobs_bwd_scaled_f32(const float* logits, const int32_t* symbo
                                        const float* gpx, const float* gpy, const float* scale, int scale_stride,
                                        float scale_mul, float* glogits, int B, int T, int S, int C, int r,
                                        int modified, void* stream) {
-  return pruned_logprobs_bwd_scaled_entry(logits, symbols, ranges, boundary, termination_symbol, lse, gpx, gpy, scale, scale_stride, scale_mul, glogits, B, T, S, C, r, modified, 0, stream);
+  return pruned_logprobs_bwd_scaled_entry(logits, FTR_DTYPE_F32, symbols, ranges, boundary, termination_symbol, lse, gpx, gpy, scale, scale_stride, scale_mul, glogits, B, T, S, C, r, modified, 0, stream);
 }
 
 int ftr_hat_pruned_logprobs_bwd_scaled_f32(const float* logits, const int32_t* symbols, const int32_t* ranges,
@@ -598,7 +614,17 @@ int ftr_hat_pruned_logprobs_bwd_scaled_f32(const float* logits, const int32_t* s
                                            const float* gpx, const float* gpy, const float* scale, int scale_stride,
                                            float scale_mul, float* glogits, int B, int T, int S, int C, int r,
                                            int modified, void* stream) {
-  return pruned_logprobs_bwd_scaled_entry(logits, symbols, ranges, boundary, termination_symbol, lse, gpx, gpy, scale, scale_stride, scale_mul, glogits, B, T, S, C, r, modified, 1, stream);
+  return pruned_logprobs_bwd_scaled_entry(logits, FTR_DTYPE_F32, symbols, ranges, boundary, termination_symbol, lse, gpx, gpy, scale, scale_stride, scale_mul, glogits, B, T, S, C, r, modified, 1, stream);
+}
+
+int ftr_pruned_logprobs_bwd_scaled_dt(const void* logits, int kind, const int32_t* symbols, const int32_t* ranges,
+                                      const int32_t* boundary, int termination_symbol, const float* lse,
+                                      const float* gpx, const float* gpy, const float* scale, int scale_stride,
+                                      float scale_mul, void* glogits, int B, int T, int S, int C, int r, int modified,
+                                      int flags, void* stream) {
+  clear_error();
+  FTR_TRY(check_dtype("pruned_logprobs_bwd_scaled_dt", kind, flags));
+  return pruned_logprobs_bwd_scaled_entry(logits, kind, symbols, ranges, boundary, termination_symbol, lse, gpx, gpy, scale, scale_stride, scale_mul, glogits, B, T, S, C, r, modified, flags & FTR_PRUNED_HAT, stream);
 }
 
 int ftr_simple_logprobs_fused_supported(int C) { return simple_fused_supported(C); }
@@ -680,7 +706,7 @@ int ftr_smoothed_logprobs_fused_bwd_am_f32(const float* gpx, const float* gpy, c
 
 int ftr_mutual_information_band_supported(int T, int S, int r) { return mi_band_supported(T, S, r); }
 
-static int pruned_band_fwd_entry(const float* logits, const int32_t* symbols, const int32_t* ranges, const int32_t* boundary,
+static int pruned_band_fwd_entry(const void* logits, int dtype, const int32_t* symbols, const int32_t* ranges, const int32_t* boundary,
                                  int termination_symbol, double delay_penalty, float* lse, float* px_band, float* py_band,
                                  int B, int T, int S, int C, int r, int modified, int hat, void* stream) {
   const char* what = hat ? "hat_pruned_band_fwd" : "pruned_band_fwd";
@@ -691,20 +717,29 @@ static int pruned_band_fwd_entry(const float* logits, const int32_t* symbols, co
   // lse and the band gather are two launches: folding the gather into the lse pass (picking the blank / symbol entries out
   // of the registers that hold the row) was built and measured -- 93 - 95 us against 73 + 9 at c3: the extra per-row scalar
   // work (two divisions, the ranges -> symbols dependency) costs the streaming pass more than the second kernel does
-  FTR_TRY(lse_rows(logits, lse, (size_t)B * T * r, C, termination_symbol, hat, stream_of(stream)));
-  return band_gather(logits, symbols, ranges, boundary, lse, termination_symbol, delay_penalty, px_band, py_band, B, T, S, C, r, modified, hat, stream_of(stream));
+  FTR_TRY(lse_rows_dtype(logits, dtype, lse, (size_t)B * T * r, C, termination_symbol, hat, stream_of(stream)));
+  return band_gather(logits, dtype, symbols, ranges, boundary, lse, termination_symbol, delay_penalty, px_band, py_band, B, T, S, C, r, modified, hat, stream_of(stream));
 }
 
 int ftr_pruned_band_fwd_f32(const float* logits, const int32_t* symbols, const int32_t* ranges, const int32_t* boundary,
                             int termination_symbol, double delay_penalty, float* lse, float* px_band, float* py_band,
                             int B, int T, int S, int C, int r, int modified, void* stream) {
-  return pruned_band_fwd_entry(logits, symbols, ranges, boundary, termination_symbol, delay_penalty, lse, px_band, py_band, B, T, S, C, r, modified, 0, stream);
+  return pruned_band_fwd_entry(logits, FTR_DTYPE_F32, symbols, ranges, boundary, termination_symbol, delay_penalty, lse, px_band, py_band, B, T, S, C, r, modified, 0, stream);
 }
 
 int ftr_hat_pruned_band_fwd_f32(const float* logits, const int32_t* symbols, const int32_t* ranges, const int32_t* boundary,
                                 int termination_symbol, double delay_penalty, float* lse, float* px_band, float* py_band,
                                 int B, int T, int S, int C, int r, int modified, void* stream) {
-  return pruned_band_fwd_entry(logits, symbols, ranges, boundary, termination_symbol, delay_penalty, lse, px_band, py_band, B, T, S, C, r, modified, 1, stream);
+  return pruned_band_fwd_entry(logits, FTR_DTYPE_F32, symbols, ranges, boundary, termination_symbol, delay_penalty, lse, px_band, py_band, B, T, S, C, r, modified, 1, stream);
+}
+
+int ftr_pruned_band_fwd_dt(const void* logits, int kind, const int32_t* symbols, const int32_t* ranges,
+                           const int32_t* boundary, int termination_symbol, double delay_penalty, float* lse,
+                           float* px_band, float* py_band, int B, int T, int S, int C, int r, int modified, int flags,
+                           void* stream) {
+  clear_error();
+  FTR_TRY(check_dtype("pruned_band_fwd_dt", kind, flags));
+  return pruned_band_fwd_entry(logits, kind, symbols, ranges, boundary, termination_symbol, delay_penalty, lse, px_band, py_band, B, T, S, C, r, modified, flags & FTR_PRUNED_HAT, stream);
 }
 
 int ftr_band_ranges_check_i32(const int32_t* ranges, const int32_t* boundary, int32_t* flags, int B, int T, int r, void* stream) {
@@ -735,10 +770,10 @@ int ftr_mutual_information_band_ws_f32(const float* px_band, const float* py_ban
   return mi_band(px_band, py_band, ranges, boundary, workspace, workspace_floats, ans, gx_band, gy_band, B, T, S, r, modified, stream_of(stream));
 }
 
-static int pruned_band_bwd_scaled_entry(const float* logits, const int32_t* symbols, const int32_t* ranges,
+static int pruned_band_bwd_scaled_entry(const void* logits, int dtype, const int32_t* symbols, const int32_t* ranges,
                                         const int32_t* boundary, int termination_symbol, const float* lse,
                                         const float* gx_band, const float* gy_band, const float* scale, int scale_stride,
-                                        float scale_mul, float* glogits, int B, int T, int S, int C, int r, int modified,
+                                        float scale_mul, void* glogits, int B, int T, int S, int C, int r, int modified,
                                         int hat, void* stream) {
   const char* what = hat ? "hat_pruned_band_bwd_scaled" : "pruned_band_bwd_scaled";
   clear_error();
@@ -746,7 +781,7 @@ static int pruned_band_bwd_scaled_entry(const float* logits, const int32_t* symb
   FTR_TRY(check_scale_stride(what, scale_stride));
   if (B == 0) return FTR_OK;
   FTR_TRY(pointers_then_device(what, logits && ranges && lse && gx_band && gy_band && glogits && (symbols || S == 0)));
-  return band_grad_banded(logits, symbols, ranges, boundary, termination_symbol, lse, gx_band, gy_band, Scale{scale, scale_stride, scale_mul}, glogits, B, T, S, C, r, modified, hat, stream_of(stream));
+  return band_grad_banded(logits, dtype, symbols, ranges, boundary, termination_symbol, lse, gx_band, gy_band, Scale{scale, scale_stride, scale_mul}, glogits, B, T, S, C, r, modified, hat, stream_of(stream));
 }
 
 int ftr_pruned_band_bwd_scaled_f32(const float* logits, const int32_t* symbols, const int32_t* ranges,
@@ -754,7 +789,7 @@ int ftr_pruned_band_bwd_scaled_f32(const float* logits, const int32_t* symbols, 
                                    const float* gx_band, const float* gy_band, const float* scale, int scale_stride,
                                    float scale_mul, float* glogits, int B, int T, int S, int C, int r, int modified,
                                    void* stream) {
-  return pruned_band_bwd_scaled_entry(logits, symbols, ranges, boundary, termination_symbol, lse, gx_band, gy_band, scale, scale_stride, scale_mul, glogits, B, T, S, C, r, modified, 0, stream);
+  return pruned_band_bwd_scaled_entry(logits, FTR_DTYPE_F32, symbols, ranges, boundary, termination_symbol, lse, gx_band, gy_band, scale, scale_stride, scale_mul, glogits, B, T, S, C, r, modified, 0, stream);
 }
 
 int ftr_hat_pruned_band_bwd_scaled_f32(const float* logits, const int32_t* symbols, const int32_t* ranges,
@@ -762,7 +797,17 @@ int ftr_hat_pruned_band_bwd_scaled_f32(const float* logits, const int32_t* symbo
                                        const float* gx_band, const float* gy_band, const float* scale, int scale_stride,
                                        float scale_mul, float* glogits, int B, int T, int S, int C, int r, int modified,
                                        void* stream) {
-  return pruned_band_bwd_scaled_entry(logits, symbols, ranges, boundary, termination_symbol, lse, gx_band, gy_band, scale, scale_stride, scale_mul, glogits, B, T, S, C, r, modified, 1, stream);
+  return pruned_band_bwd_scaled_entry(logits, FTR_DTYPE_F32, symbols, ranges, boundary, termination_symbol, lse, gx_band, gy_band, scale, scale_stride, scale_mul, glogits, B, T, S, C, r, modified, 1, stream);
+}
+
+int ftr_pruned_band_bwd_scaled_dt(const void* logits, int kind, const int32_t* symbols, const int32_t* ranges,
+                                  const int32_t* boundary, int termination_symbol, const float* lse,
+                                  const float* gx_band, const float* gy_band, const float* scale, int scale_stride,
+                                  float scale_mul, void* glogits, int B, int T, int S, int C, int r, int modified,
+                                  int flags, void* stream) {
+  clear_error();
+  FTR_TRY(check_dtype("pruned_band_bwd_scaled_dt", kind, flags));
+  return pruned_band_bwd_scaled_entry(logits, kind, symbols, ranges, boundary, termination_symbol, lse, gx_band, gy_band, scale, scale_stride, scale_mul, glogits, B, T, S, C, r, modified, flags & FTR_PRUNED_HAT, stream);
 }
 
 // ---- multi-blank transducer (MI355X addition; csrc/mi_multiblank.hip, the mb_* kernels of csrc/pruned_logprobs.hip).

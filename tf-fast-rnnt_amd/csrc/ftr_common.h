@@ -4,7 +4,7 @@
 #include <stdint.h>
 #include <stdio.h>
 #include <stdarg.h>
-#include "../../include/ftr.h"
+#include "../../include/ftr_lowp.h"  // and, through it, ftr.h
 
 namespace ftr {
 
@@ -63,6 +63,43 @@ constexpr float kLn2 = 0.6931471805599453f;
 // dword aligned; amdhsa runs in unaligned-access mode and these lower to global_load/store_dwordx4.
 typedef float f4u __attribute__((ext_vector_type(4), aligned(4)));
 typedef float f4 __attribute__((ext_vector_type(4)));
+
+// ---- element types of the joiner logits and of their gradient (the FTR_DTYPE_* codes of ftr_lowp.h): float, or 16 bits of
+// storage.  A 16-bit value is up-converted on load (exact), every kernel computes in float32 as before, and a store
+// rounds once, to nearest-even (NaN stays NaN, -inf stays -inf, overflow goes to inf, fp16 subnormals are kept).  Plain C++
+// conversions: the compiler picks v_cvt_f32_f16 / v_cvt_f16_f32 and the bf16 forms of gfx950.
+struct bf16_t { uint16_t bits; };
+struct fp16_t { uint16_t bits; };
+// four 16-bit elements, one 8-byte access.  Naturally aligned: the launchers take the vector path of a 16-bit tensor only when
+// its base is 8-byte aligned and C % 4 == 0 (every row then is), since a contiguous 16-bit view may start at an odd element
+typedef uint16_t h4 __attribute__((ext_vector_type(4)));
+
+__device__ __forceinline__ float elem_to_float(float v) { return v; }
+__device__ __forceinline__ float elem_to_float(bf16_t v) { return (float)__builtin_bit_cast(__bf16, v.bits); }
+__device__ __forceinline__ float elem_to_float(fp16_t v) { return (float)__builtin_bit_cast(_Float16, v.bits); }
+template <typename E> __device__ __forceinline__ E elem_from_float(float v);
+template <> __device__ __forceinline__ float elem_from_float<float>(float v) { return v; }
+template <> __device__ __forceinline__ bf16_t elem_from_float<bf16_t>(float v) { return bf16_t{__builtin_bit_cast(uint16_t, (__bf16)v)}; }
+template <> __device__ __forceinline__ fp16_t elem_from_float<fp16_t>(float v) { return fp16_t{__builtin_bit_cast(uint16_t, (_Float16)v)}; }
+
+// elements 4i .. 4i+3 of a row as floats, and back (float rows: the f4u access above, any dword-aligned row)
+__device__ __forceinline__ f4 load4(const float* row, int i) { return reinterpret_cast<const f4u*>(row)[i]; }
+__device__ __forceinline__ void store4(float* row, int i, f4 v) { reinterpret_cast<f4u*>(row)[i] = v; }
+template <typename E>
+__device__ __forceinline__ f4 load4(const E* row, int i) {
+  const h4 h = reinterpret_cast<const h4*>(row)[i];
+  f4 v;
+#pragma unroll
+  for (int e = 0; e < 4; ++e) v[e] = elem_to_float(E{h[e]});
+  return v;
+}
+template <typename E>
+__device__ __forceinline__ void store4(E* row, int i, f4 v) {
+  h4 h;
+#pragma unroll
+  for (int e = 0; e < 4; ++e) h[e] = elem_from_float<E>(v[e]).bits;
+  reinterpret_cast<h4*>(row)[i] = h;
+}
 
 // Per-utterance factor applied to incoming lattice gradients on the fly: (p ? p[b * stride] : 1) * mul.
 // stride 0 = one scalar for the whole batch (reduction "sum"/"mean"), mul carries the sign and the 1/B of "mean".
@@ -194,8 +231,9 @@ size_t do_pruning_bwd_workspace_bytes(int B, int T, int S1, int C, int r);
 int do_pruning_bwd_ws(const float* g_am_p, const float* g_lm_p, const int32_t* ranges, float* d_am, float* d_lm, int B, int T, int S1, int C, int r, void* ws, size_t ws_bytes, hipStream_t st);
 int do_pruning_bwd(const float* g_am_p, const float* g_lm_p, const int32_t* ranges, float* d_am, float* d_lm, int B, int T, int S1, int C, int r, hipStream_t st);
 // hat != 0: the HAT normalisation (lse = non-blank normaliser Z, see pruned_logprobs.hip); hat == 0: the ordinary kernels
-int pruned_logprobs_fwd(const float* logits, const int32_t* symbols, const int32_t* ranges, const int32_t* boundary, int blank, double delay_penalty, float* lse, float* px, float* py, int B, int T, int S, int C, int r, int modified, int hat, hipStream_t st);
-int pruned_logprobs_bwd(const float* logits, const int32_t* symbols, const int32_t* ranges, const int32_t* boundary, int blank, const float* lse, const float* gpx, const float* gpy, Scale scale, float* glogits, int B, int T, int S, int C, int r, int modified, int hat, hipStream_t st);
+// dtype: the element type of logits / glogits (FTR_DTYPE_*, validated by the caller: dtype_ok)
+int pruned_logprobs_fwd(const void* logits, int dtype, const int32_t* symbols, const int32_t* ranges, const int32_t* boundary, int blank, double delay_penalty, float* lse, float* px, float* py, int B, int T, int S, int C, int r, int modified, int hat, hipStream_t st);
+int pruned_logprobs_bwd(const void* logits, int dtype, const int32_t* symbols, const int32_t* ranges, const int32_t* boundary, int blank, const float* lse, const float* gpx, const float* gpy, Scale scale, void* glogits, int B, int T, int S, int C, int r, int modified, int hat, hipStream_t st);
 int simple_rowmax_exp(const float* x, float* probs, float* rowmax, float* rowsum, const float* dotvec, float* dot, size_t rows, int C, hipStream_t st);
 int simple_rowmax_exp_pair(const float* x1, float* probs1, float* rowmax1, size_t rows1, const float* x2, float* probs2, float* rowmax2, size_t rows2, int C, hipStream_t st);
 int simple_rowdot(const float* x, const float* v, float* dot, size_t rows, int C, hipStream_t st);
@@ -214,15 +252,16 @@ int simple_fused_fwd(const float* am, const float* lm, const int32_t* symbols, c
 int simple_fused_bwd_am(const float* gpx, const float* gpy, Scale scale, const float* prod, const float* lm_probs, const float* am_probs, const int32_t* symbols, const int32_t* boundary, int blank, float cs, float kdir, const float* uvec, const float* amdot, float as, float* Rout, float* d_am, int B, int T, int S, int C, int modified, hipStream_t st);
 int negated_reduce(const float* ans, int B, int reduction, float* out, hipStream_t st);
 int lse_rows(const float* logits, float* lse, size_t rows, int C, int blank, int hat, hipStream_t st);
+int lse_rows_dtype(const void* logits, int dtype, float* lse, size_t rows, int C, int blank, int hat, hipStream_t st);
 int mi_band_supported(int T, int S, int r);
 int band_ranges_check(const int32_t* ranges, const int32_t* boundary, int* flags, int B, int T, int r, hipStream_t st);
-int band_gather(const float* logits, const int32_t* symbols, const int32_t* ranges, const int32_t* boundary, const float* lse, int blank, double delay_penalty, float* pxb, float* pyb, int B, int T, int S, int C, int r, int modified, int hat, hipStream_t st);
+int band_gather(const void* logits, int dtype, const int32_t* symbols, const int32_t* ranges, const int32_t* boundary, const float* lse, int blank, double delay_penalty, float* pxb, float* pyb, int B, int T, int S, int C, int r, int modified, int hat, hipStream_t st);
 size_t mi_band_workspace_floats(int B, int T, int S, int r);
 int mi_band_seg_supported(int T, int S, int r);
 size_t mi_band_seg_workspace_floats(int B, int T, int S, int r);
 int mi_band_seg(const float* pxb, const float* pyb, const int32_t* ranges, const int32_t* boundary, float* ws, size_t ws_floats, float* ans, float* gxb, float* gyb, int B, int T, int S, int r, int modified, hipStream_t st);
 int mi_band(const float* pxb, const float* pyb, const int32_t* ranges, const int32_t* boundary, float* ws, size_t ws_floats, float* ans, float* gxb, float* gyb, int B, int T, int S, int r, int modified, hipStream_t st);
-int band_grad_banded(const float* logits, const int32_t* symbols, const int32_t* ranges, const int32_t* boundary, int blank, const float* lse, const float* gxb, const float* gyb, Scale scale, float* glogits, int B, int T, int S, int C, int r, int modified, int hat, hipStream_t st);
+int band_grad_banded(const void* logits, int dtype, const int32_t* symbols, const int32_t* ranges, const int32_t* boundary, int blank, const float* lse, const float* gxb, const float* gyb, Scale scale, void* glogits, int B, int T, int S, int C, int r, int modified, int hat, hipStream_t st);
 int selftest(hipStream_t st, int* result_dev);
 int debug_stamps(unsigned long long* out16);
 int debug_trace(unsigned long long* out, int n);

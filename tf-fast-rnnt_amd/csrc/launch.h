@@ -61,6 +61,23 @@ inline auto dispatch(bool flag, F&& f) {
   if (flag) return f(std::true_type{});
   return f(std::false_type{});
 }
+// an FTR_DTYPE_* code -> the element type: f is called with an elem_tag<float | bf16_t | fp16_t>.  The entry points of
+// capi.hip reject unknown codes (check_dtype) before a launcher sees them; here any other code is float.
+template <typename E> struct elem_tag { using type = E; };
+template <typename F>
+inline auto dispatch_dtype(int dtype, F&& f) {
+  if (dtype == FTR_DTYPE_BF16) return f(elem_tag<bf16_t>{});
+  if (dtype == FTR_DTYPE_FP16) return f(elem_tag<fp16_t>{});
+  return f(elem_tag<float>{});
+}
+// may rows of C elements starting at `a` (and at `b`, if given) be read four elements at a time?  float rows are dword
+// aligned whatever C is; a 16-bit row needs its 8-byte alignment, which a view at an odd element offset does not have.
+template <typename E>
+inline bool rows_vec4(int C, const void* a, const void* b = nullptr) {
+  if ((C & 3) != 0) return false;
+  if (std::is_same<E, float>::value) return true;
+  return ((reinterpret_cast<uintptr_t>(a) | reinterpret_cast<uintptr_t>(b)) & 7) == 0;
+}
 // v among V, Rest...: that one; any other v: the last of the list
 template <int V, int... Rest, typename F>
 inline auto dispatch_among(int v, F&& f) {

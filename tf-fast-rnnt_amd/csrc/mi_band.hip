@@ -27,6 +27,11 @@
 //
 // LDS (per utterance): lo[T+1] (band start per column) and three arrays of (S_n + T_n + 1) x LANES floats: OX, OY
 // (operands, later the two flow outputs) and G.  LANES = 8 while r <= 7, 16 up to r = 15 (r + 1 lanes: see in_band in the kernel).
+//
+// The two kernels of this file that touch the joiner logits, band_gather_kernel and band_grad_banded_kernel, take the element
+// type of `logits` / `glogits` as a template argument (float, bf16_t, fp16_t; ftr_common.h): 16-bit values are up-converted on
+// load, the band arrays and all arithmetic are float32, the gradient row is rounded once when it is stored.  The recursion
+// kernels never see the logits and are float32 only.
 #include "ftr_common.h"
 #include "launch.h"
 #include <type_traits>
@@ -60,8 +65,9 @@ __device__ __forceinline__ float row16_sum(float v) {
 // boundary column of the regular type), one thread per band cell.
 // HAT: lse holds Z (non-blank normaliser), py = log sigmoid(x[blank]), px = x[sym] - Z - softplus(x[blank]), -inf when
 // sym == blank (the helpers of ftr_common.h, shared with band_to_lattice_kernel).
-template <bool MOD, bool HAT>
-__global__ void band_gather_kernel(const float* __restrict__ logits, const int32_t* __restrict__ symbols,
+// E: the element type of `logits` (float, bf16_t, fp16_t of ftr_common.h), up-converted on load.
+template <typename E, bool MOD, bool HAT>
+__global__ void band_gather_kernel(const E* __restrict__ logits, const int32_t* __restrict__ symbols,
                                    const int32_t* __restrict__ ranges, const int32_t* __restrict__ boundary,
                                    const float* __restrict__ lse, int blank, double delay_penalty,
                                    float* __restrict__ pxb, float* __restrict__ pyb, size_t rows, int T, int S, int C, int r) {
@@ -77,15 +83,15 @@ __global__ void band_gather_kernel(const float* __restrict__ logits, const int32
   float vy = -INFINITY, vx = -INFINITY;
   if (s >= 0 && s <= S) {
     if (HAT) {
-      const float xb = logits[row * C + blank];
+      const float xb = elem_to_float(logits[row * C + blank]);
       int c = blank;
       if (s < S) c = min(max(symbols[(size_t)b * S + s], 0), C - 1);
-      hat_logprobs(xb, logits[row * C + c], l, c == blank, &vx, &vy);   // s == S: c == blank, vx = -inf
+      hat_logprobs(xb, elem_to_float(logits[row * C + c]), l, c == blank, &vx, &vy);   // s == S: c == blank, vx = -inf
     } else {
-      vy = logits[row * C + blank] - l;
+      vy = elem_to_float(logits[row * C + blank]) - l;
     }
     if (s < S) {
-      if (!HAT) vx = logits[row * C + min(max(symbols[(size_t)b * S + s], 0), C - 1)] - l;
+      if (!HAT) vx = elem_to_float(logits[row * C + min(max(symbols[(size_t)b * S + s], 0), C - 1)]) - l;
       if (!MOD && t == te) vx = -INFINITY;
       if (delay_penalty > 0.0) vx += (float)((((double)te - 1.0) / 2.0 - (double)t) * delay_penalty);
     }
@@ -723,12 +729,14 @@ __global__ __launch_bounds__(kBandThreads) void mi_band_stream_kernel(
 // ---------------------------------------------------------------------------------------- gradient w.r.t. logits
 // the band_grad_kernel of pruned_logprobs.hip with the occupancies read band shaped (row = (b,t,k)); one wave per row.
 // HAT: g[c] = gx (1[c == sym] - exp(x[c] - Z)) for c != blank, g[blank] = gy sigmoid(-x[blank]) - gx sigmoid(x[blank]).
-template <bool VEC, bool HAT>
-__global__ void band_grad_banded_kernel(const float* __restrict__ logits, const int32_t* __restrict__ symbols,
+// E: the element type of logits and glogits (16 bits: 8-byte loads and stores of four elements, the row computed in float32
+// and rounded once, to nearest-even, when it is stored).
+template <typename E, bool VEC, bool HAT>
+__global__ void band_grad_banded_kernel(const E* __restrict__ logits, const int32_t* __restrict__ symbols,
                                         const int32_t* __restrict__ ranges, const int32_t* __restrict__ boundary,
                                         const float* __restrict__ lse, const float* __restrict__ gxb,
                                         const float* __restrict__ gyb, const Scale scale, int blank, int modified,
-                                        float* __restrict__ glogits, size_t rows, int T, int S, int C, int r) {
+                                        E* __restrict__ glogits, size_t rows, int T, int S, int C, int r) {
   const int lane = threadIdx.x & 63;
   // LAST ROWS FIRST: the caller's backward reads `glogits` front to back right after this kernel, and what a 320 MB stream
   // leaves in the 256 MB memory-side cache is what was written last (see lse_rows_reg_kernel, pruned_logprobs.hip): 121 -> 117 us
@@ -758,14 +766,12 @@ __global__ void band_grad_banded_kernel(const float* __restrict__ logits, const 
     if (sym == blank) gx = 0.0f;         // px is -inf there
     tot = gx;
   }
-  const float* x = logits + row * C;
-  float* g = glogits + row * C;
+  const E* x = logits + row * C;
+  E* g = glogits + row * C;
   if (VEC) {
-    const f4u* x4 = reinterpret_cast<const f4u*>(x);
-    f4u* g4 = reinterpret_cast<f4u*>(g);
     const int n4 = C >> 2;
     for (int i = lane; i < n4; i += 64) {
-      const f4 v = x4[i];
+      const f4 v = load4(x, i);
       f4 o;
 #pragma unroll
       for (int e = 0; e < 4; ++e) {
@@ -783,22 +789,23 @@ __global__ void band_grad_banded_kernel(const float* __restrict__ logits, const 
         }
         o[e] = val;
       }
-      g4[i] = o;
+      store4(g, i, o);
     }
   } else {
     for (int cc = lane; cc < C; cc += 64) {
-      float val = -tot * __expf(x[cc] - l);
+      const float xc = elem_to_float(x[cc]);
+      float val = -tot * __expf(xc - l);
       if (cc == sym) val += gx;
       if (cc == blank) {
         if (HAT) {
           float sp, sn;
-          hat_sigmoids(x[cc], &sp, &sn);
+          hat_sigmoids(xc, &sp, &sn);
           val = gy * sn - gx * sp;
         } else {
           val += gy;
         }
       }
-      g[cc] = val;
+      g[cc] = elem_from_float<E>(val);
     }
   }
 }
@@ -845,17 +852,20 @@ int band_ranges_check(const int32_t* ranges, const int32_t* boundary, int* flags
   return check_launch("band_ranges_check");
 }
 
-int band_gather(const float* logits, const int32_t* symbols, const int32_t* ranges, const int32_t* boundary,
+int band_gather(const void* logits, int dtype, const int32_t* symbols, const int32_t* ranges, const int32_t* boundary,
                 const float* lse, int blank, double delay_penalty, float* pxb, float* pyb, int B, int T, int S, int C,
                 int r, int modified, int hat, hipStream_t st) {
   const size_t rows = (size_t)B * T * r;
   if (rows == 0) return FTR_OK;
   { const int rc32 = require_rows_32bit("pruned_band_fwd", rows); if (rc32 != FTR_OK) return rc32; }
   const unsigned blocks = (unsigned)((rows + 255) / 256);
-  dispatch(modified != 0, [&](auto mod) {
-    dispatch(hat != 0, [&](auto h) {
-      hipLaunchKernelGGL((band_gather_kernel<decltype(mod)::value, decltype(h)::value>), dim3(blocks), dim3(256), 0, st,
-                         logits, symbols, ranges, boundary, lse, blank, delay_penalty, pxb, pyb, rows, T, S, C, r);
+  dispatch_dtype(dtype, [&](auto tag) {
+    using E = typename decltype(tag)::type;
+    dispatch(modified != 0, [&](auto mod) {
+      dispatch(hat != 0, [&](auto h) {
+        hipLaunchKernelGGL((band_gather_kernel<E, decltype(mod)::value, decltype(h)::value>), dim3(blocks), dim3(256), 0, st,
+                           static_cast<const E*>(logits), symbols, ranges, boundary, lse, blank, delay_penalty, pxb, pyb, rows, T, S, C, r);
+      });
     });
   });
   return check_launch("band_gather");
@@ -908,18 +918,21 @@ extern "C" int ftr_debug_band_stamps(unsigned long long* out) {
 }
 #endif
 
-int band_grad_banded(const float* logits, const int32_t* symbols, const int32_t* ranges, const int32_t* boundary,
-                     int blank, const float* lse, const float* gxb, const float* gyb, Scale scale, float* glogits, int B,
+int band_grad_banded(const void* logits, int dtype, const int32_t* symbols, const int32_t* ranges, const int32_t* boundary,
+                     int blank, const float* lse, const float* gxb, const float* gyb, Scale scale, void* glogits, int B,
                      int T, int S, int C, int r, int modified, int hat, hipStream_t st) {
   const size_t rows = (size_t)B * T * r;
   if (rows == 0) return FTR_OK;
   { const int rc32 = require_rows_32bit("pruned_band_bwd", rows); if (rc32 != FTR_OK) return rc32; }
   const int wpb = 4;
   const unsigned blocks = (unsigned)((rows + wpb - 1) / wpb);
-  dispatch((C & 3) == 0, [&](auto vec) {
-    dispatch(hat != 0, [&](auto h) {
-      hipLaunchKernelGGL((band_grad_banded_kernel<decltype(vec)::value, decltype(h)::value>), dim3(blocks), dim3(64 * wpb), 0, st,
-                         logits, symbols, ranges, boundary, lse, gxb, gyb, scale, blank, modified, glogits, rows, T, S, C, r);
+  dispatch_dtype(dtype, [&](auto tag) {
+    using E = typename decltype(tag)::type;
+    dispatch(rows_vec4<E>(C, logits, glogits), [&](auto vec) {
+      dispatch(hat != 0, [&](auto h) {
+        hipLaunchKernelGGL((band_grad_banded_kernel<E, decltype(vec)::value, decltype(h)::value>), dim3(blocks), dim3(64 * wpb), 0, st,
+                           static_cast<const E*>(logits), symbols, ranges, boundary, lse, gxb, gyb, scale, blank, modified, static_cast<E*>(glogits), rows, T, S, C, r);
+      });
     });
   });
   return check_launch("band_grad_banded");

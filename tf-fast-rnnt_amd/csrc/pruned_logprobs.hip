@@ -9,6 +9,11 @@
 // HAT (hybrid autoregressive transducer, MI355X addition): each kernel has a `bool HAT` twin that normalises the row
 // differently -- lse holds Z = logsumexp over the non-blank columns, py = log sigmoid(x[blank]),
 // px = x[sym] - Z - softplus(x[blank]) (-inf when sym == blank); the HAT = false instantiations are the ordinary kernels.
+// 16-bit logits: the four kernels above also take an element type E (float, bf16_t, fp16_t of ftr_common.h).  A 16-bit
+// row is read four elements (8 bytes) per lane where C % 4 == 0 and the tensor's base is 8-byte aligned, element by element
+// otherwise; values are up-converted on load, lse / px / py and all arithmetic stay float32, and the gradient row is rounded
+// once (nearest-even) when it is stored in E.  The float instantiations are the kernels as they were.  The multi-blank
+// kernels below are float only.
 #include "ftr_common.h"
 #include "launch.h"
 
@@ -25,8 +30,10 @@ __device__ __forceinline__ float wave_sum(float v) { return wave_sum_dpp(v); }
 // 5.8 TB/s on the same tensor -- a flat read reaches 6.7 -- and 205 against 250 us at c4.  The memory system likes many short
 // waves better than few clever ones.)
 // HAT: the blank column is masked to -inf before the max and the sum (lse = Z, the non-blank normaliser).
-template <int NQ, bool HAT>
-__global__ __launch_bounds__(256) void lse_rows_reg_kernel(const float* __restrict__ logits, float* __restrict__ lse,
+// E: the element type of `logits` (float, bf16_t, fp16_t): a 16-bit row is one 8-byte load per lane and quad instead of a
+// 16-byte one, up-converted into the same float registers, so the same NQ keeps the same C <= 2048 register-resident.
+template <typename E, int NQ, bool HAT>
+__global__ __launch_bounds__(256) void lse_rows_reg_kernel(const E* __restrict__ logits, float* __restrict__ lse,
                                                            size_t rows, int C, int blank) {
   const int lane = threadIdx.x & 63;
   // LAST ROWS FIRST.  The joiner has just written `logits` front to back, 320 MB at c3 against 256 MB of memory-side cache:
@@ -38,12 +45,12 @@ __global__ __launch_bounds__(256) void lse_rows_reg_kernel(const float* __restri
   const size_t row = rows - 1 - rowi;
   const int n4 = C >> 2;
   const f4 ninf = {-INFINITY, -INFINITY, -INFINITY, -INFINITY};
-  const f4u* x4 = reinterpret_cast<const f4u*>(logits + row * C);
+  const E* x = logits + row * C;
   f4 v[NQ];
 #pragma unroll
   for (int q = 0; q < NQ; ++q) {
     const int i = lane + 64 * q;
-    v[q] = (i < n4) ? (f4)x4[i] : ninf;
+    v[q] = (i < n4) ? load4(x, i) : ninf;
     if (HAT) {
 #pragma unroll
       for (int e = 0; e < 4; ++e) v[q][e] = (4 * i + e == blank) ? -INFINITY : v[q][e];
@@ -64,18 +71,17 @@ __global__ __launch_bounds__(256) void lse_rows_reg_kernel(const float* __restri
 }
 
 // logsumexp of each row of length C; rows = B*T*r.  One wave per row (any C).
-template <bool VEC, bool HAT>
-__global__ void lse_rows_kernel(const float* __restrict__ logits, float* __restrict__ lse, size_t rows, int C, int blank) {
+template <typename E, bool VEC, bool HAT>
+__global__ void lse_rows_kernel(const E* __restrict__ logits, float* __restrict__ lse, size_t rows, int C, int blank) {
   const int lane = threadIdx.x & 63;
   const size_t row = (size_t)blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
   if (row >= rows) return;
-  const float* x = logits + row * C;
+  const E* x = logits + row * C;
   float m = -INFINITY;
   if (VEC) {
-    const f4u* x4 = reinterpret_cast<const f4u*>(x);
     const int n4 = C >> 2;
     for (int i = lane; i < n4; i += 64) {
-      f4 v = x4[i];
+      f4 v = load4(x, i);
       if (HAT) {
 #pragma unroll
         for (int e = 0; e < 4; ++e) v[e] = (4 * i + e == blank) ? -INFINITY : v[e];
@@ -85,7 +91,7 @@ __global__ void lse_rows_kernel(const float* __restrict__ logits, float* __restr
     m = wave_max(m);
     float s = 0.0f;
     for (int i = lane; i < n4; i += 64) {  // second pass hits L1/L2: a row is 2-4 KB
-      f4 v = x4[i];
+      f4 v = load4(x, i);
       if (HAT) {
 #pragma unroll
         for (int e = 0; e < 4; ++e) v[e] = (4 * i + e == blank) ? -INFINITY : v[e];
@@ -95,18 +101,18 @@ __global__ void lse_rows_kernel(const float* __restrict__ logits, float* __restr
     s = wave_sum(s);
     if (lane == 0) lse[row] = m + __logf(s);
   } else {
-    for (int i = lane; i < C; i += 64) m = fmaxf(m, (HAT && i == blank) ? -INFINITY : x[i]);
+    for (int i = lane; i < C; i += 64) m = fmaxf(m, (HAT && i == blank) ? -INFINITY : elem_to_float(x[i]));
     m = wave_max(m);
     float s = 0.0f;
-    for (int i = lane; i < C; i += 64) s += __expf(((HAT && i == blank) ? -INFINITY : x[i]) - m);
+    for (int i = lane; i < C; i += 64) s += __expf(((HAT && i == blank) ? -INFINITY : elem_to_float(x[i])) - m);
     s = wave_sum(s);
     if (lane == 0) lse[row] = m + __logf(s);
   }
 }
 
 // grid: (ceil((T+1)/256), S+1, B); thread <-> (b, s, t).  Writes py[b,s,t] (t < T) and px[b,s,t] (s < S, t < T1).
-template <bool MOD, bool HAT>
-__global__ void band_to_lattice_kernel(const float* __restrict__ logits, const int32_t* __restrict__ symbols,
+template <typename E, bool MOD, bool HAT>
+__global__ void band_to_lattice_kernel(const E* __restrict__ logits, const int32_t* __restrict__ symbols,
                                        const int32_t* __restrict__ ranges, const int32_t* __restrict__ boundary,
                                        const float* __restrict__ lse, int blank, double delay_penalty,
                                        float* __restrict__ px, float* __restrict__ py, int T, int S, int C, int r) {
@@ -125,16 +131,16 @@ __global__ void band_to_lattice_kernel(const float* __restrict__ logits, const i
       const size_t row = bt * r + k;
       const float l = lse[row];
       if (HAT) {
-        const float xb = logits[row * C + blank];
+        const float xb = elem_to_float(logits[row * C + blank]);
         int c = blank;
         if (s < S) c = min(max(symbols[(size_t)b * S + s], 0), C - 1);
         float hx, hy;
-        hat_logprobs(xb, logits[row * C + c], l, c == blank, &hx, &hy);
+        hat_logprobs(xb, elem_to_float(logits[row * C + c]), l, c == blank, &hx, &hy);
         vy = hy;
         if (s < S) vx = hx;
       } else {
-        vy = logits[row * C + blank] - l;                       // :995-996
-        if (s < S) vx = logits[row * C + min(max(symbols[(size_t)b * S + s], 0), C - 1)] - l;   // :961-965 (symbol kept in bounds)
+        vy = elem_to_float(logits[row * C + blank]) - l;                       // :995-996
+        if (s < S) vx = elem_to_float(logits[row * C + min(max(symbols[(size_t)b * S + s], 0), C - 1)]) - l;   // :961-965 (symbol kept in bounds)
       }
     }
   }
@@ -151,12 +157,13 @@ __global__ void band_to_lattice_kernel(const float* __restrict__ logits, const i
 
 // one wave per (b,t,k) row of glogits.
 // HAT: g[c] = gx (1[c == sym] - exp(x[c] - Z)) for c != blank, g[blank] = gy sigmoid(-x[blank]) - gx sigmoid(x[blank]).
-template <bool MOD, bool VEC, bool HAT>
-__global__ void band_grad_kernel(const float* __restrict__ logits, const int32_t* __restrict__ symbols,
+// E: the element type of logits and glogits; the row is computed in float32 and rounded once when it is stored.
+template <typename E, bool MOD, bool VEC, bool HAT>
+__global__ void band_grad_kernel(const E* __restrict__ logits, const int32_t* __restrict__ symbols,
                                  const int32_t* __restrict__ ranges, const int32_t* __restrict__ boundary,
                                  const float* __restrict__ lse, const float* __restrict__ gpx,
                                  const float* __restrict__ gpy, const Scale scale, int blank,
-                                 float* __restrict__ glogits, size_t rows, int T, int S, int C, int r) {
+                                 E* __restrict__ glogits, size_t rows, int T, int S, int C, int r) {
   const int lane = threadIdx.x & 63;
   const size_t row = (size_t)blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
   if (row >= rows) return;
@@ -185,14 +192,12 @@ __global__ void band_grad_kernel(const float* __restrict__ logits, const int32_t
     if (sym == blank) gx = 0.0f;         // px is -inf there
     tot = gx;
   }
-  const float* x = logits + row * C;
-  float* g = glogits + row * C;
+  const E* x = logits + row * C;
+  E* g = glogits + row * C;
   if (VEC) {
-    const f4u* x4 = reinterpret_cast<const f4u*>(x);
-    f4u* g4 = reinterpret_cast<f4u*>(g);
     const int n4 = C >> 2;
     for (int i = lane; i < n4; i += 64) {
-      const f4 v = x4[i];
+      const f4 v = load4(x, i);
       f4 o;
 #pragma unroll
       for (int e = 0; e < 4; ++e) {
@@ -210,22 +215,23 @@ __global__ void band_grad_kernel(const float* __restrict__ logits, const int32_t
         }
         o[e] = val;
       }
-      g4[i] = o;
+      store4(g, i, o);
     }
   } else {
     for (int c = lane; c < C; c += 64) {
-      float val = -tot * __expf(x[c] - l);
+      const float xc = elem_to_float(x[c]);
+      float val = -tot * __expf(xc - l);
       if (c == sym) val += gx;
       if (c == blank) {
         if (HAT) {
           float sp, sn;
-          hat_sigmoids(x[c], &sp, &sn);
+          hat_sigmoids(xc, &sp, &sn);
           val = gy * sn - gx * sp;
         } else {
           val += gy;
         }
       }
-      g[c] = val;
+      g[c] = elem_from_float<E>(val);
     }
   }
 }
@@ -258,58 +264,78 @@ int negated_reduce(const float* ans, int B, int reduction, float* out, hipStream
 
 // logsumexp over the last axis of [rows, C] (rnnt_loss.py:942): picks the register-resident kernel where it fits
 // (hat: over the non-blank columns only, the normaliser Z of the HAT factorisation)
-int lse_rows(const float* logits, float* lse, size_t rows, int C, int blank, int hat, hipStream_t st) {
+namespace {
+template <typename E>
+int lse_rows_of(const E* logits, float* lse, size_t rows, int C, int blank, int hat, hipStream_t st) {
   if (rows == 0) return FTR_OK;
   { const int rc32 = require_rows_32bit("lse_rows", rows); if (rc32 != FTR_OK) return rc32; }
   const int wpb = 4;
   const unsigned blocks = (unsigned)((rows + wpb - 1) / wpb);
   dispatch(hat != 0, [&](auto h) {
     constexpr bool HAT = decltype(h)::value;
-    if ((C & 3) == 0 && C <= 2048)   // the row fits the registers of a wave: 1, 2, 4 or 8 float4 per lane
+    const bool vec4 = rows_vec4<E>(C, logits);
+    if (vec4 && C <= 2048)   // the row fits the registers of a wave: 1, 2, 4 or 8 quads of elements per lane
       dispatch_among<1, 2, 4, 8>(C <= 256 ? 1 : C <= 512 ? 2 : C <= 1024 ? 4 : 8, [&](auto n) {
-        hipLaunchKernelGGL((lse_rows_reg_kernel<decltype(n)::value, HAT>), dim3(blocks), dim3(64 * wpb), 0, st, logits, lse, rows, C, blank);
+        hipLaunchKernelGGL((lse_rows_reg_kernel<E, decltype(n)::value, HAT>), dim3(blocks), dim3(64 * wpb), 0, st, logits, lse, rows, C, blank);
       });
     else
-      dispatch((C & 3) == 0, [&](auto vec) {
-        hipLaunchKernelGGL((lse_rows_kernel<decltype(vec)::value, HAT>), dim3(blocks), dim3(64 * wpb), 0, st, logits, lse, rows, C, blank);
+      dispatch(vec4, [&](auto vec) {
+        hipLaunchKernelGGL((lse_rows_kernel<E, decltype(vec)::value, HAT>), dim3(blocks), dim3(64 * wpb), 0, st, logits, lse, rows, C, blank);
       });
   });
   return check_launch("lse_rows");
 }
+}  // namespace
 
-int pruned_logprobs_fwd(const float* logits, const int32_t* symbols, const int32_t* ranges,
+int lse_rows(const float* logits, float* lse, size_t rows, int C, int blank, int hat, hipStream_t st) {
+  return lse_rows_of(logits, lse, rows, C, blank, hat, st);
+}
+int lse_rows_dtype(const void* logits, int dtype, float* lse, size_t rows, int C, int blank, int hat, hipStream_t st) {
+  return dispatch_dtype(dtype, [&](auto tag) {
+    using E = typename decltype(tag)::type;
+    return lse_rows_of(static_cast<const E*>(logits), lse, rows, C, blank, hat, st);
+  });
+}
+
+int pruned_logprobs_fwd(const void* logits, int dtype, const int32_t* symbols, const int32_t* ranges,
                         const int32_t* boundary, int blank, double delay_penalty, float* lse, float* px,
                         float* py, int B, int T, int S, int C, int r, int modified, int hat, hipStream_t st) {
   const size_t rows = (size_t)B * T * r;
   if (rows == 0) return FTR_OK;
   { const int rc32 = require_rows_32bit("pruned_logprobs_fwd", rows); if (rc32 != FTR_OK) return rc32; }
-  int rc = lse_rows(logits, lse, rows, C, blank, hat, st);
+  int rc = lse_rows_dtype(logits, dtype, lse, rows, C, blank, hat, st);
   if (rc != FTR_OK) return rc;
   const int threads = 256;
   const dim3 grid((T + 1 + threads - 1) / threads, S + 1, B);
-  dispatch(modified != 0, [&](auto mod) {
-    dispatch(hat != 0, [&](auto h) {
-      hipLaunchKernelGGL((band_to_lattice_kernel<decltype(mod)::value, decltype(h)::value>), grid, dim3(threads), 0, st,
-                         logits, symbols, ranges, boundary, lse, blank, delay_penalty, px, py, T, S, C, r);
+  dispatch_dtype(dtype, [&](auto tag) {
+    using E = typename decltype(tag)::type;
+    dispatch(modified != 0, [&](auto mod) {
+      dispatch(hat != 0, [&](auto h) {
+        hipLaunchKernelGGL((band_to_lattice_kernel<E, decltype(mod)::value, decltype(h)::value>), grid, dim3(threads), 0, st,
+                           static_cast<const E*>(logits), symbols, ranges, boundary, lse, blank, delay_penalty, px, py, T, S, C, r);
+      });
     });
   });
   return check_launch("band_to_lattice");
 }
 
-int pruned_logprobs_bwd(const float* logits, const int32_t* symbols, const int32_t* ranges,
+int pruned_logprobs_bwd(const void* logits, int dtype, const int32_t* symbols, const int32_t* ranges,
                         const int32_t* boundary, int blank, const float* lse, const float* gpx,
-                        const float* gpy, Scale scale, float* glogits, int B, int T, int S, int C,
+                        const float* gpy, Scale scale, void* glogits, int B, int T, int S, int C,
                         int r, int modified, int hat, hipStream_t st) {
   const size_t rows = (size_t)B * T * r;
   if (rows == 0) return FTR_OK;
   { const int rc32 = require_rows_32bit("pruned_logprobs_bwd", rows); if (rc32 != FTR_OK) return rc32; }
   const int wpb = 4;
   const unsigned blocks = (unsigned)((rows + wpb - 1) / wpb);
-  dispatch(modified != 0, [&](auto mod) {
-    dispatch((C & 3) == 0, [&](auto vec) {
-      dispatch(hat != 0, [&](auto h) {
-        hipLaunchKernelGGL((band_grad_kernel<decltype(mod)::value, decltype(vec)::value, decltype(h)::value>), dim3(blocks), dim3(64 * wpb), 0, st,
-                           logits, symbols, ranges, boundary, lse, gpx, gpy, scale, blank, glogits, rows, T, S, C, r);
+  dispatch_dtype(dtype, [&](auto tag) {
+    using E = typename decltype(tag)::type;
+    dispatch(modified != 0, [&](auto mod) {
+      dispatch(rows_vec4<E>(C, logits, glogits), [&](auto vec) {
+        dispatch(hat != 0, [&](auto h) {
+          hipLaunchKernelGGL((band_grad_kernel<E, decltype(mod)::value, decltype(vec)::value, decltype(h)::value>), dim3(blocks), dim3(64 * wpb), 0, st,
+                             static_cast<const E*>(logits), symbols, ranges, boundary, lse, gpx, gpy, scale, blank, static_cast<E*>(glogits), rows, T, S, C, r);
+        });
       });
     });
   });

@@ -101,8 +101,18 @@ _SIGNATURES = {
     "ftr_simple_logprobs_bwd_lm_f32": (_i, [_c_fp, _c_fp, _c_ip, _c_fp, _c_fp, _i, _c_fp, _i, _i, _i, _c_st]),
     "ftr_selftest": (_i, [ctypes.c_void_p, _c_st]),
 }
-EXPORTED_SYMBOLS = tuple(_SIGNATURES)
+# include/ftr_lowp.h, 16-bit joiner logits: (logits, kind = FTR_DTYPE_*, ...the _f32 twin's arguments..., flags = FTR_PRUNED_HAT, stream)
+_LOWP_SIGNATURES = {
+    "ftr_pruned_logprobs_fwd_dt": (_i, [_c_fp, _i, _c_ip, _c_ip, _c_ip, _i, ctypes.c_double, _c_fp, _c_fp, _c_fp, _i, _i, _i, _i, _i, _i, _i, _c_st]),
+    "ftr_pruned_logprobs_bwd_scaled_dt": (_i, [_c_fp, _i, _c_ip, _c_ip, _c_ip, _i, _c_fp, _c_fp, _c_fp, _c_fp, _i, _f, _c_fp, _i, _i, _i, _i, _i, _i, _i, _c_st]),
+    "ftr_pruned_band_fwd_dt": (_i, [_c_fp, _i, _c_ip, _c_ip, _c_ip, _i, ctypes.c_double, _c_fp, _c_fp, _c_fp, _i, _i, _i, _i, _i, _i, _i, _c_st]),
+    "ftr_pruned_band_bwd_scaled_dt": (_i, [_c_fp, _i, _c_ip, _c_ip, _c_ip, _i, _c_fp, _c_fp, _c_fp, _c_fp, _i, _f, _c_fp, _i, _i, _i, _i, _i, _i, _i, _c_st]),
+}
+EXPORTED_SYMBOLS = tuple(_SIGNATURES)            # the symbols of include/ftr.h
+LOWP_SYMBOLS = tuple(_LOWP_SIGNATURES)           # those of include/ftr_lowp.h
 FTR_MI_WS_CLEAN = 1   # include/ftr.h
+FTR_DTYPE_F32, FTR_DTYPE_BF16, FTR_DTYPE_FP16 = 0, 1, 2   # include/ftr_lowp.h: the `kind` of the _dt entry points
+FTR_PRUNED_HAT = 1    # include/ftr_lowp.h: their `flags` bit
 
 
 def lib() -> ctypes.CDLL:
@@ -114,7 +124,7 @@ def lib() -> ctypes.CDLL:
                 f"{LIB_PATH} is missing: build the HIP extension first (python -c 'import __graft_entry__ as g; "
                 "g.build()' or make -C tf-fast-rnnt_amd/csrc).  tf_fast_rnnt has no CPU fallback.")
         handle = ctypes.CDLL(LIB_PATH)
-        for name, (restype, argtypes) in _SIGNATURES.items():
+        for name, (restype, argtypes) in {**_SIGNATURES, **_LOWP_SIGNATURES}.items():
             fn = getattr(handle, name)   # AttributeError here = header/library mismatch
             fn.restype = restype
             fn.argtypes = argtypes

@@ -545,6 +545,20 @@ def do_rnnt_pruning(am: torch.Tensor, lm: torch.Tensor, ranges: torch.Tensor, de
     return _DoPruning.apply(am, lm, ranges, bool(dense))
 
 
+# 16-bit joiner logits go through the _dt entry points (element type code, HAT as a flag); float32 keeps its _f32 ones
+_LOWP_KIND = {torch.bfloat16: _lib.FTR_DTYPE_BF16, torch.float16: _lib.FTR_DTYPE_FP16}
+
+
+def _pruned_call(name, hat, x, head, tail):
+    """One logits-reading entry point on ``x``: ``ftr_[hat_]<name>_f32(x, *head, *tail)`` for float32 logits,
+    ``ftr_<name>_dt(x, kind, *head, flags, *tail)`` for bfloat16 / float16 (``tail``: the stream)."""
+    kind = _LOWP_KIND.get(x.dtype)
+    if kind is None:
+        _lib.call(f"ftr_{'hat_' if hat else ''}{name}_f32", _ptr(x), *head, *tail)
+    else:
+        _lib.call(f"ftr_{name}_dt", _ptr(x), kind, *head, _lib.FTR_PRUNED_HAT if hat else 0, *tail)
+
+
 def _pruned_builder_fwd(x, symbols, ranges, boundary, blank, delay_penalty, modified, hat):
     """lse [B,T,r] and the full-size px / py of the pruned builder (``hat``: the ftr_hat_* twin), one launch."""
     B, T, r, C = x.shape
@@ -553,25 +567,21 @@ def _pruned_builder_fwd(x, symbols, ranges, boundary, blank, delay_penalty, modi
     px = torch.empty((B, S, T if modified else T + 1), dtype=torch.float32, device=x.device)
     py = torch.empty((B, S + 1, T), dtype=torch.float32, device=x.device)
     with torch.cuda.device(x.device):
-        _lib.call("ftr_hat_pruned_logprobs_fwd_f32" if hat else "ftr_pruned_logprobs_fwd_f32", _ptr(x), _ptr(symbols),
-                  _ptr(ranges), _ptr(boundary), int(blank), float(delay_penalty), _ptr(lse), _ptr(px), _ptr(py), B, T, S, C, r,
-                  int(modified), _stream_ptr(x))
+        _pruned_call("pruned_logprobs_fwd", hat, x, (_ptr(symbols), _ptr(ranges), _ptr(boundary), int(blank),
+                     float(delay_penalty), _ptr(lse), _ptr(px), _ptr(py), B, T, S, C, r, int(modified)), (_stream_ptr(x),))
     return lse, px, py
-
-
-_PRUNED_BWD = {(False, False): "ftr_pruned_logprobs_bwd_scaled_f32", (False, True): "ftr_hat_pruned_logprobs_bwd_scaled_f32",
-               (True, False): "ftr_pruned_band_bwd_scaled_f32", (True, True): "ftr_hat_pruned_band_bwd_scaled_f32"}
 
 
 def _pruned_builder_bwd(x, symbols, ranges, boundary, blank, modified, lse, gpx, gpy, scale, stride, mul, band, hat):
     """d/d logits from d/d px, d/d py (``band``: band-shaped [B,T,r], else the full-size lattices), multiplied on the fly
-    by (scale ? scale[b * stride] : 1) * mul; one streaming launch."""
+    by (scale ? scale[b * stride] : 1) * mul; one streaming launch.  The gradient has the dtype of ``x``."""
     B, T, r, C = x.shape
     S = symbols.shape[1]
     g = torch.empty_like(x)
     with torch.cuda.device(x.device):
-        _lib.call(_PRUNED_BWD[band, hat], _ptr(x), _ptr(symbols), _ptr(ranges), _ptr(boundary), blank, _ptr(lse), _ptr(gpx),
-                  _ptr(gpy), _ptr(scale), stride, mul, _ptr(g), B, T, S, C, r, modified, _stream_ptr(x))
+        _pruned_call("pruned_band_bwd_scaled" if band else "pruned_logprobs_bwd_scaled", hat, x,
+                     (_ptr(symbols), _ptr(ranges), _ptr(boundary), blank, _ptr(lse), _ptr(gpx), _ptr(gpy), _ptr(scale), stride,
+                      mul, _ptr(g), B, T, S, C, r, modified), (_stream_ptr(x),))
     return g
 
 
@@ -596,12 +606,15 @@ class _PrunedLogprobs(torch.autograd.Function):
         return g, None, None, None, None, None, None, None
 
 
-def _pruned_inputs(logits, symbols, ranges, boundary):
+def _pruned_inputs(logits, symbols, ranges, boundary, lowp=False):
+    """``lowp``: bfloat16 / float16 logits are accepted too (the ordinary and HAT builders; not multi-blank, not TDT)."""
     _require_gpu(logits, "logits")
     if logits.dim() != 4:
         raise ValueError("logits must be [B,T,s_range,C]")
-    if logits.dtype != torch.float32:
-        raise TypeError("logits must be float32")
+    if lowp and logits.dtype in _LOWP_KIND:
+        pass
+    elif logits.dtype != torch.float32:
+        raise TypeError("logits must be float32, bfloat16 or float16" if lowp else "logits must be float32")
     B, T, r, C = logits.shape
     symbols = torch.as_tensor(symbols, device=logits.device).to(torch.int32).contiguous()
     ranges_in = ranges
@@ -631,7 +644,7 @@ def get_rnnt_logprobs_pruned(
 
 def _pruned_logprobs(logits, symbols, ranges, termination_symbol, boundary, rnnt_type, hat):
     _check_type(rnnt_type)
-    symbols, ranges, boundary = _pruned_inputs(logits, symbols, ranges, boundary)
+    symbols, ranges, boundary = _pruned_inputs(logits, symbols, ranges, boundary, lowp=True)
     modified = rnnt_type != "regular"
     px, py = _PrunedLogprobs.apply(logits, symbols, ranges, termination_symbol, boundary, modified, 0.0, hat)
     if rnnt_type == "constrained":
@@ -672,7 +685,7 @@ def rnnt_alignment_pruned(
     logits use ``mutual_information_viterbi(*get_rnnt_logprobs_joint(...))``."""
     _check_type(rnnt_type)
     with torch.no_grad():
-        symbols, ranges, boundary = _pruned_inputs(logits, symbols, ranges, boundary)
+        symbols, ranges, boundary = _pruned_inputs(logits, symbols, ranges, boundary, lowp=True)
         _, px, py = _pruned_builder_fwd(logits.detach().contiguous(), symbols, ranges, boundary, termination_symbol, 0.0,
                                         rnnt_type != "regular", False)
         if rnnt_type == "constrained":
@@ -749,10 +762,9 @@ class _PrunedLoss(torch.autograd.Function):
             ans = torch.empty((B,), dtype=torch.float32, device=x.device)
             with torch.cuda.device(x.device):
                 st = _stream_ptr(x)
-                _lib.call("ftr_hat_pruned_band_fwd_f32" if hat else "ftr_pruned_band_fwd_f32",
-                          _ptr(x), _ptr(symbols), _ptr(ranges), _ptr(boundary),
-                          int(termination_symbol), float(delay_penalty), _ptr(lse), _ptr(pxb), _ptr(pyb),
-                          B, T, S, C, r, int(modified), st)
+                _pruned_call("pruned_band_fwd", hat, x, (_ptr(symbols), _ptr(ranges), _ptr(boundary),
+                             int(termination_symbol), float(delay_penalty), _ptr(lse), _ptr(pxb), _ptr(pyb),
+                             B, T, S, C, r, int(modified)), (st,))
                 nws = _lib.lib().ftr_mutual_information_band_workspace_floats(B, T, S, r)   # 0: the LDS-resident kernel
                 bws = torch.empty((nws,), dtype=torch.float32, device=x.device) if nws else None
                 _lib.call("ftr_mutual_information_band_ws_f32", _ptr(pxb), _ptr(pyb), _ptr(ranges), _ptr(boundary), _ptr(bws),
@@ -799,7 +811,7 @@ def rnnt_loss_pruned(
 def _pruned_loss(logits, symbols, ranges, termination_symbol, boundary, rnnt_type, delay_penalty, reduction, hat):
     _check_type(rnnt_type)
     code = _reduction_code(reduction)
-    symbols_i, ranges_i, boundary_i = _pruned_inputs(logits, symbols, ranges, boundary)
+    symbols_i, ranges_i, boundary_i = _pruned_inputs(logits, symbols, ranges, boundary, lowp=True)
     if rnnt_type == "constrained":
         px, py = _pruned_logprobs(logits, symbols_i, ranges_i, termination_symbol, boundary_i, rnnt_type, hat)
         px = _apply_delay_penalty(px, boundary_i, rnnt_type, delay_penalty)
