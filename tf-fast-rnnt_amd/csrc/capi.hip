@@ -1,4 +1,4 @@
-// csrc/capi.hip -- the extern "C" surface declared in include/ftr.h and include/ftr_lowp.h: argument validation and error reporting.  No
+// csrc/capi.hip -- the extern "C" surface declared in include/ftr.h, include/ftr_lowp.h and include/ftr_kd.h: argument validation and error reporting.  No
 // allocation, no host synchronisation, no CPU fallback.  Built twice: into libftr_hip.so (the product: the symbols of
 // ftr.h and ftr_lowp.h and nothing else) and, with -DFTR_DIAG, into the test-only _build/libftr_hip_diag.so, which adds the symbols of
 // include/ftr_diag.h: the "plain" kernel family (the reference's arithmetic on the device, mi_plain.hip), its
@@ -1030,6 +1030,53 @@ int ftr_tdt_pruned_logprobs_bwd_scaled_f32(const float* logits, const int32_t* s
   FTR_TRY(pointers_then_device(what, logits && ranges && lse_tok && lse_dur && gpy && glogits && (symbols || S == 0) && (gpx || S == 0)));
   return tdt_logprobs_bwd(logits, symbols, ranges, boundary, termination_symbol, durations, N, lse_tok, lse_dur, gpx, gpy,
                           Scale{scale, scale_stride, scale_mul}, glogits, B, T, S, C, r, stream_of(stream));
+}
+
+// ---- include/ftr_kd.h: knowledge distillation on the pruned band (csrc/pruned_kd.hip)
+// element type codes, mode and temperature, before everything else
+static int kd_check_head(const char* what, int kind, int teacher_kind, int mode, float temperature) {
+  FTR_TRY(check_dtype(what, kind, 0));
+  FTR_TRY(check_dtype(what, teacher_kind, 0));
+  FTR_REQUIRE(mode == FTR_KD_FULL || mode == FTR_KD_COLLAPSED, "%s: unknown mode %d (FTR_KD_FULL = 0, FTR_KD_COLLAPSED = 1)", what, mode);
+  FTR_REQUIRE(temperature > 0.0f && temperature <= 3.0e38f, "%s: temperature %g is not a finite number > 0", what, (double)temperature);
+  return FTR_OK;
+}
+
+int ftr_pruned_kd_fwd_dt(const void* logits, int kind, const void* teacher_logits, int teacher_kind,
+                         const int32_t* symbols, const int32_t* ranges, const int32_t* boundary, int termination_symbol,
+                         float temperature, int mode, float* node_loss, float* saved, float* utt_loss, int B, int T, int S,
+                         int C, int r, void* stream) {
+  const char* what = "pruned_kd_fwd_dt";
+  clear_error();
+  FTR_TRY(kd_check_head(what, kind, teacher_kind, mode, temperature));
+  FTR_TRY(check_builder(what, B >= 0 && T >= 1 && S >= 0 && C >= 1 && r >= 1, termination_symbol, C));
+  if (B == 0) return FTR_OK;
+  FTR_TRY(pointers_then_device(what, logits && teacher_logits && ranges && node_loss && saved && utt_loss && (symbols || S == 0)));
+  return pruned_kd_fwd(logits, kind, teacher_logits, teacher_kind, symbols, ranges, boundary, termination_symbol, temperature,
+                       mode == FTR_KD_COLLAPSED, node_loss, saved, utt_loss, B, T, S, C, r, stream_of(stream));
+}
+
+int ftr_pruned_kd_bwd_scaled_dt(const void* logits, int kind, const void* teacher_logits, int teacher_kind,
+                                const int32_t* symbols, const int32_t* ranges, const int32_t* boundary,
+                                int termination_symbol, float temperature, int mode, const float* saved,
+                                const float* scale, int scale_stride, float scale_mul, void* glogits, int B, int T, int S,
+                                int C, int r, void* stream) {
+  const char* what = "pruned_kd_bwd_scaled_dt";
+  clear_error();
+  FTR_TRY(kd_check_head(what, kind, teacher_kind, mode, temperature));
+  FTR_TRY(check_builder(what, B >= 0 && T >= 1 && S >= 0 && C >= 1 && r >= 1, termination_symbol, C, true));
+  FTR_TRY(check_scale_stride(what, scale_stride));
+  if (B == 0) return FTR_OK;
+  FTR_TRY(pointers_then_device(what, logits && teacher_logits && ranges && saved && glogits && (symbols || S == 0)));
+  return pruned_kd_bwd(logits, kind, teacher_logits, teacher_kind, symbols, ranges, boundary, termination_symbol, temperature,
+                       mode == FTR_KD_COLLAPSED, saved, Scale{scale, scale_stride, scale_mul}, glogits, B, T, S, C, r, stream_of(stream));
+}
+
+int ftr_pruned_kd_reduce_f32(const float* utt_loss, int B, int reduction, float* out, void* stream) {
+  clear_error();
+  FTR_REQUIRE(B >= 1 && reduction >= 0 && reduction <= 2, "pruned_kd_reduce: bad arguments B=%d reduction=%d", B, reduction);
+  FTR_TRY(pointers_then_device("pruned_kd_reduce", utt_loss && out));
+  return negated_reduce(utt_loss, B, reduction, out, stream_of(stream), 1.0f);
 }
 
 int ftr_selftest(void* scratch_dev, void* stream) {

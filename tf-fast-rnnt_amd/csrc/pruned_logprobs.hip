@@ -237,12 +237,13 @@ __global__ void band_grad_kernel(const E* __restrict__ logits, const int32_t* __
 }
 
 // loss tail (rnnt_loss.py:333,544-546,1124-1126,1487-1489): out = -ans (reduction 0), -mean (1) or -sum (2) over the
-// batch, one block, fixed summation tree (deterministic).
+// batch, one block, fixed summation tree (deterministic).  sign = -1 is that tail; sign = +1 reduces per-utterance values
+// that already are a loss (pruned_kd.hip).  sign * v with sign = -1 is -v, bit for bit.
 __global__ __launch_bounds__(256) void negated_reduce_kernel(const float* __restrict__ ans, int B, int reduction,
-                                                             float* __restrict__ out) {
+                                                             float* __restrict__ out, float sign) {
   __shared__ float red[4];
   if (reduction == 0) {
-    for (int b = threadIdx.x; b < B; b += 256) out[b] = -ans[b];
+    for (int b = threadIdx.x; b < B; b += 256) out[b] = sign * ans[b];
     return;
   }
   float s = 0.0f;
@@ -252,13 +253,13 @@ __global__ __launch_bounds__(256) void negated_reduce_kernel(const float* __rest
   __syncthreads();
   if (threadIdx.x == 0) {
     const float t = (red[0] + red[1]) + (red[2] + red[3]);
-    out[0] = (reduction == 1) ? -(t / (float)B) : -t;
+    out[0] = sign * ((reduction == 1) ? t / (float)B : t);
   }
 }
 }  // namespace
 
-int negated_reduce(const float* ans, int B, int reduction, float* out, hipStream_t st) {
-  hipLaunchKernelGGL(negated_reduce_kernel, dim3(1), dim3(256), 0, st, ans, B, reduction, out);
+int negated_reduce(const float* ans, int B, int reduction, float* out, hipStream_t st, float sign) {
+  hipLaunchKernelGGL(negated_reduce_kernel, dim3(1), dim3(256), 0, st, ans, B, reduction, out, sign);
   return check_launch("negated_reduce");
 }
 

@@ -22,6 +22,7 @@ from .mutual_information import mutual_information_viterbi_tdt              # MI
 from .rnnt_loss import rnnt_alignment_tdt_pruned, rnnt_alignment_multiblank_pruned   # TDT / multi-blank lattices, see there
 from .rnnt_loss import rnnt_loss
 from .rnnt_loss import rnnt_loss_pruned
+from .rnnt_loss import rnnt_kd_loss_pruned                                     # MI355X addition: distillation on the pruned band, see its docstring
 from .rnnt_loss import rnnt_alignment_pruned                                   # MI355X addition: best-path alignment, see its docstring
 from .rnnt_loss import rnnt_loss_simple
 from .rnnt_loss import rnnt_loss_smoothed

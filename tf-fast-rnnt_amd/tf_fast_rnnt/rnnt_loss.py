@@ -14,6 +14,8 @@ What runs where:
   with identity ranges (s_range = S+1).
 * ``get_hat_logprobs_pruned`` / ``get_hat_logprobs_joint`` / ``hat_loss_pruned`` / ``hat_loss`` (MI355X addition, no
   reference counterpart): the same kernels and routes with the HAT normalisation of the joiner output.
+* ``rnnt_kd_loss_pruned`` (MI355X addition, no reference counterpart): knowledge distillation on the pruned band, two
+  stream kernels of its own (include/ftr_kd.h, csrc/pruned_kd.hip).
 
 Reference bugs that are NOT reproduced: ``rnnt_loss_simple(reduction="mean")``
 raises NameError there (rnnt_loss.py:331) -- here it is the mean; ``boundary=None`` works; the
@@ -854,6 +856,114 @@ def hat_loss(
     return hat_loss_pruned(logits=logits, symbols=symbols, ranges=_joint_inputs(logits, symbols),
                            termination_symbol=termination_symbol, boundary=boundary, rnnt_type=rnnt_type,
                            delay_penalty=delay_penalty, reduction=reduction)
+
+
+# ---- knowledge distillation on the pruned band (MI355X addition, no reference counterpart)
+
+_KD_MODES = {"full": _lib.FTR_KD_FULL, "collapsed": _lib.FTR_KD_COLLAPSED}
+_KD_DTYPES = (torch.float32, torch.bfloat16, torch.float16)
+
+
+def _kd_head(x, y):
+    """(logits, kind, teacher_logits, teacher_kind) of the ftr_pruned_kd_* entry points"""
+    return (_ptr(x), _LOWP_KIND.get(x.dtype, _lib.FTR_DTYPE_F32), _ptr(y), _LOWP_KIND.get(y.dtype, _lib.FTR_DTYPE_F32))
+
+
+class _PrunedKdLoss(torch.autograd.Function):
+    """rnnt_kd_loss_pruned as one node: forward = one pass over both tensors (node losses and the row normalisers the
+    backward needs) + the per-utterance sum [+ the batch reduction]; backward = one streaming pass that writes d loss / d
+    logits in the student's dtype, the upstream gradient folded in.  The teacher gets no gradient."""
+
+    @staticmethod
+    def forward(ctx, logits, teacher_logits, symbols, ranges, termination_symbol, boundary, mode, temperature, code):
+        B, T, r, C = logits.shape
+        S = symbols.shape[1]
+        x = logits.detach().contiguous()
+        y = teacher_logits.detach().contiguous()
+        node = torch.empty((B, T, r), dtype=torch.float32, device=x.device)
+        saved = torch.empty((4 if mode == _lib.FTR_KD_COLLAPSED else 2, B, T, r), dtype=torch.float32, device=x.device)
+        utt = torch.empty((B,), dtype=torch.float32, device=x.device)
+        out = utt
+        with torch.cuda.device(x.device):
+            st = _stream_ptr(x)
+            _lib.call("ftr_pruned_kd_fwd_dt", *_kd_head(x, y), _ptr(symbols), _ptr(ranges), _ptr(boundary),
+                      int(termination_symbol), float(temperature), mode, _ptr(node), _ptr(saved), _ptr(utt), B, T, S, C, r, st)
+            if code != 0:
+                out = torch.empty((), dtype=torch.float32, device=x.device)
+                _lib.call("ftr_pruned_kd_reduce_f32", _ptr(utt), B, code, _ptr(out), st)
+        if logits.requires_grad:
+            ctx.save_for_backward(x, y, symbols, ranges, saved, boundary)
+        ctx.meta = (int(termination_symbol), mode, float(temperature), int(code))
+        return out
+
+    @staticmethod
+    def backward(ctx, g_loss):
+        x, y, symbols, ranges, saved, boundary = ctx.saved_tensors
+        blank, mode, temperature, code = ctx.meta
+        B, T, r, C = x.shape
+        scale, stride, mul = _upstream_scale(g_loss, code, B)   # its multiplier negates: this loss is not a negated score
+        g = torch.empty_like(x)
+        with torch.cuda.device(x.device):
+            _lib.call("ftr_pruned_kd_bwd_scaled_dt", *_kd_head(x, y), _ptr(symbols), _ptr(ranges), _ptr(boundary), blank,
+                      temperature, mode, _ptr(saved), _ptr(scale), stride, -mul, _ptr(g), B, T, symbols.shape[1], C, r,
+                      _stream_ptr(x))
+        return g, None, None, None, None, None, None, None, None
+
+
+def rnnt_kd_loss_pruned(
+    logits: torch.Tensor,
+    teacher_logits: torch.Tensor,
+    symbols: torch.Tensor,
+    ranges: torch.Tensor,
+    termination_symbol: int,
+    boundary: Optional[torch.Tensor] = None,
+    mode: str = "full",
+    temperature: float = 1.0,
+    reduction: Optional[str] = "mean",
+) -> torch.Tensor:
+    """Knowledge distillation on the pruned band (MI355X addition, no reference counterpart): the KL divergence between a
+    teacher's and the student's joiner distributions at every node of the band, to be added to the transducer loss::
+
+        loss = rnnt_loss_pruned(logits, ...) + lam * rnnt_kd_loss_pruned(logits, teacher_logits, ...)
+
+    ``logits`` (student) and ``teacher_logits`` are both [B,T,s_range,C], the teacher's joiner evaluated on the student's
+    ``ranges``; each is float32, bfloat16 or float16, independently (a 16-bit tensor means its exact float32 values).
+
+    Node (b,t,k) with s = ranges[b,t,k] is valid iff t_begin <= t < t_end and s_begin <= s <= s_end (``boundary[b]`` =
+    (s_begin, t_begin, s_end, t_end); None = the whole lattice).  An invalid node adds nothing, gets a zero gradient
+    row, and its logits are never read, so padding frames may hold anything, NaN included.
+
+    ``mode="full"``: KL(p || q) = sum_c p_c (log p_c - log q_c) over the C columns, p = softmax(teacher / temperature),
+    q = softmax(student / temperature).  ``mode="collapsed"`` (Panchapagesan et al., ICASSP 2021): the same over three
+    classes -- blank, the correct next symbol ``symbols[b,s]`` (only where s < s_end and it is not the blank), and the
+    rest, summed over the other columns.  Terms of teacher probability 0 are 0.  The loss is NOT multiplied by
+    temperature ** 2; scale ``lam`` if you follow that convention.
+
+    The loss of an utterance is the sum over its valid nodes; ``reduction``: "none" ([B]), "sum", or "mean" (over the
+    batch).  Float32, bit-identical from run to run.  The gradient goes to ``logits`` only, in its dtype (computed in
+    float32, rounded once); ``teacher_logits`` never gets one.  A NaN in a valid row makes its utterance's loss NaN; a
+    student logit of -inf where the teacher has mass makes it +inf."""
+    for name, t in (("logits", logits), ("teacher_logits", teacher_logits)):
+        if t.dtype not in _KD_DTYPES:
+            raise TypeError(f"{name} must be float32, bfloat16 or float16, got {t.dtype}")
+    if logits.dim() != 4:
+        raise ValueError("logits must be [B,T,s_range,C]")
+    if tuple(teacher_logits.shape) != tuple(logits.shape):
+        raise ValueError(f"teacher_logits must have the shape of logits {tuple(logits.shape)}, got {tuple(teacher_logits.shape)}")
+    if mode not in _KD_MODES:
+        raise ValueError(f"mode should be ('full' | 'collapsed'), given {mode}")
+    temperature = float(temperature)
+    if not (0.0 < temperature < float("inf")):
+        raise ValueError(f"temperature must be a finite number > 0, given {temperature}")
+    code = _reduction_code(reduction)
+    if not 0 <= int(termination_symbol) < logits.shape[3]:
+        raise ValueError(f"termination_symbol {termination_symbol} not in [0,{logits.shape[3]})")
+    symbols, ranges, boundary = _pruned_inputs(logits, symbols, ranges, boundary, lowp=True)
+    _require_gpu(teacher_logits, "teacher_logits")
+    if teacher_logits.device != logits.device:
+        raise ValueError("teacher_logits and logits must be on the same device")
+    return _PrunedKdLoss.apply(logits, teacher_logits, symbols, ranges, int(termination_symbol), boundary, _KD_MODES[mode],
+                               temperature, code)
 
 
 # ---- multi-blank transducer (MI355X addition, no reference counterpart): big blanks that advance several frames
