@@ -480,6 +480,7 @@ def test_absent_producer_poisons_loudly(ft, dev):
 def _band_case(ft, dev, B, T, S, r, modified, seed, offsets=False, break_end=False):
     """Random band arrays on hand-built monotone ranges -> (band kernel results, lattice kernel results mapped to the band)."""
     from tf_fast_rnnt import _lib
+    from band_cases import band_to_lattice, lattice_to_band
     rng = np.random.default_rng(seed)
     s0 = np.zeros((B, T), np.int64)
     for b in range(B):
@@ -498,20 +499,7 @@ def _band_case(ft, dev, B, T, S, r, modified, seed, offsets=False, break_end=Fal
             lo, hi = int(s0[b, tb]), int(min(s0[b, te - 1] + r - 1, S))
             sb = int(rng.integers(lo, min(lo + r, hi + 1))); se = int(rng.integers(max(sb, hi - r + 1), hi + 1))
             bd[b] = (sb, tb, se, te)
-    T1 = T if modified else T + 1
-    px = np.full((B, S, T1), -np.inf, np.float32); py = np.full((B, S + 1, T), -np.inf, np.float32)
-    for b in range(B):
-        for t in range(T):
-            for k in range(r):
-                s = s0[b, t] + k
-                if s < S: px[b, s, t] = pxb[b, t, k]
-                if s <= S: py[b, s, t] = pyb[b, t, k]
-                if s >= S: pxb[b, t, k] = -np.inf                     # what the band builder writes there
-                if s > S: pyb[b, t, k] = -np.inf
-    if not modified:                                                   # fix_for_boundary (rnnt_loss.py:28-61): no symbol in column t_end
-        for b in range(B):
-            te = int(bd[b, 3])
-            if te < T: px[b, :, te] = -np.inf; pxb[b, te, :] = -np.inf
+    px, py = band_to_lattice(pxb, pyb, s0, bd, S, modified)         # also writes the band builder's -inf into pxb / pyb
     t_ = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)
     tpx, tpy, tbd, trg = t_(pxb), t_(pyb), t_(bd), t_(ranges)
     ans = torch.empty(B, device=dev); gxb = torch.empty_like(tpx); gyb = torch.empty_like(tpy)
@@ -527,13 +515,7 @@ def _band_case(ft, dev, B, T, S, r, modified, seed, offsets=False, break_end=Fal
     if fin.any(): lans[fin].sum().backward()
     lgx = np.zeros_like(px) if lpx.grad is None else lpx.grad.cpu().numpy()
     lgy = np.zeros_like(py) if lpy.grad is None else lpy.grad.cpu().numpy()
-    egx = np.zeros((B, T, r), np.float32); egy = np.zeros((B, T, r), np.float32)
-    for b in range(B):
-        for t in range(T):
-            for k in range(r):
-                s = s0[b, t] + k
-                if s < S and t < T1: egx[b, t, k] = lgx[b, s, t]
-                if s <= S: egy[b, t, k] = lgy[b, s, t]
+    egx, egy = lattice_to_band(lgx, lgy, s0, r)
     return ans.cpu().numpy(), gxb.cpu().numpy(), gyb.cpu().numpy(), lans.detach().cpu().numpy(), egx, egy, fin.cpu().numpy()
 
 
@@ -590,13 +572,16 @@ def test_recursion_fuzz_against_plain_kernels(ft, dev):
 
 def test_streaming_band_kernel_on_every_size(dev):
     """The streaming band kernel (long utterances: arrays in a global workspace) on the SMALL cases too: FTR_BAND_FORCE_STREAM
-    (read once per process, hence child processes) sends every size through it -- the edge-case test above and the
+    (read once per process, hence child processes) sends every size through it -- the edge-case test above, the `chain`
+    cases of test_gpu_band_structured.py on its shapes with S + T < 1100 (structured bands against float64), and the
     route-vs-route fuzz of scripts/band_fuzz.py."""
     import os, subprocess, sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = dict(os.environ, FTR_BAND_FORCE_STREAM="1")
-    r1 = subprocess.run([sys.executable, "-m", "pytest", os.path.join(root, "tests", "test_gpu_mi.py"), "-q", "-x", "-m", "gpu", "-k",
-                         "band_recursion_kernel_edge_cases", "-p", "no:cacheprovider"], env=env, cwd=root, capture_output=True, text=True, timeout=600)
+    r1 = subprocess.run([sys.executable, "-m", "pytest", os.path.join(root, "tests", "test_gpu_mi.py"),
+                         os.path.join(root, "tests", "test_gpu_band_structured.py"), "-q", "-x", "-m", "gpu", "-k",
+                         "band_recursion_kernel_edge_cases or ((band_recursion_vs_float64 or band_shift_is_invisible) and chain and short)",
+                         "-p", "no:cacheprovider"], env=env, cwd=root, capture_output=True, text=True, timeout=600)
     assert r1.returncode == 0, r1.stdout[-2000:] + r1.stderr[-2000:]
     r2 = subprocess.run([sys.executable, os.path.join(root, "scripts", "band_fuzz.py"), "150", "31"], env=env, cwd=root, capture_output=True,
                         text=True, timeout=600)
