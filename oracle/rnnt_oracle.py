@@ -446,6 +446,9 @@ def rnnt_loss_pruned_grad(logits, symbols, ranges, termination_symbol, boundary,
     # dtype=float64 runs the recursion (the long dependent chain) in double: the "exact" comparison point
     ans, (px_grad, py_grad) = mutual_information_recursion(px, py, boundary, True, dtype)
     loss = _reduce(ans.astype(F32), reduction)
+    if rnnt_type == "constrained":     # px = px' + py[:, 1:, :] (rnnt_loss.py:1015-1016): what reaches px also reaches py one row below
+        py_grad = py_grad.copy()
+        py_grad[:, 1:, :] += px_grad
     px_grad = px_grad.astype(F32); py_grad = py_grad.astype(F32)
     scale = {"none": -1.0, "sum": -1.0, "mean": -1.0 / B}[reduction]   # d loss / d ans[b]
     # band gradients: px[b,s,t] came from logits[b,t,s-s0,:] for s0 <= s < s0+r (s < S, t < T)
@@ -458,8 +461,6 @@ def rnnt_loss_pruned_grad(logits, symbols, ranges, termination_symbol, boundary,
         ok_x = s < S
         gx[:, :, k] = np.where(ok_x, px_grad[bb, np.minimum(s, S - 1), tt], 0.0)
         gy[:, :, k] = py_grad[bb, np.minimum(s, S), tt]
-    if rnnt_type == "constrained":
-        raise NotImplementedError
     gx *= F32(scale); gy *= F32(scale)
     lse = _logsumexp(logits, 3)
     g = np.empty_like(logits)
