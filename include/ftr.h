@@ -401,6 +401,7 @@ int ftr_smoothed_logprobs_fused_bwd_am_f32(const float* gpx, const float* gpy, c
                                            int termination_symbol, float combined_scale, float direct_scale,
                                            const float* unigram, const float* am_dot, float am_only_scale, float* R,
                                            float* d_am, int B, int T, int S, int C, int modified, void* stream);
+/* The same kernel with W (what ftr_*_logprobs_bwd_w_scaled_f32 wrote) as an operand: include/ftr_fused.h. */
 int ftr_smoothed_logprobs_bwd_w_scaled_f32(const float* gpx, const float* gpy, const float* scale, int scale_stride,
                                            float scale_mul, const float* prod, const int32_t* boundary,
                                            float combined_scale, float* W, float* rsx, float* rsy, int B, int T, int S,

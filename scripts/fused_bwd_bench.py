@@ -1,6 +1,7 @@
-"""Times the backward of the simple builder on one shape: the fused d am kernel against W kernel + library GEMM + epilogue
-kernel, and the whole backward (both routes).  python scripts/fused_bwd_bench.py [B T S C]"""
+"""Times the backward of the simple builder on one shape: the fused d am kernel (W formed on the fly, and W as an operand
+at each column tiling) against W kernel + library GEMM + epilogue kernel.  python scripts/fused_bwd_bench.py [B T S C]"""
 import os, sys
+os.environ.setdefault("FTR_GEMM_TUNE", "first")   # the library GEMMs with their measured kernel choice, as in a training loop
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "tf-fast-rnnt_amd"))
 import torch
@@ -18,12 +19,14 @@ W = torch.empty_like(prod); rsx = torch.empty(B, S + 1, device=dev); rsy = torch
 d_am = torch.empty_like(amp); d_am2 = torch.empty_like(amp); d_lm = torch.empty_like(lmp)
 st = torch.cuda.current_stream().cuda_stream
 def fused_am(): _lib.call("ftr_simple_logprobs_fused_bwd_am_f32", _ptr(gx), _ptr(gy), None, 0, 1.0, _ptr(prod), _ptr(lmp), _ptr(amp), _ptr(sym), None, C - 1, _ptr(d_am), B, T, S, C, 0, st)
+def fused_am_w(): _lib.call("ftr_simple_logprobs_fused_bwd_am_w_f32", _ptr(gx), _ptr(gy), None, 0, 1.0, _ptr(W), _ptr(lmp), _ptr(amp), _ptr(sym), None, C - 1, _ptr(d_am), B, T, S, C, 0, st)
 def wk(): _lib.call("ftr_simple_logprobs_bwd_w_f32", _ptr(gx), _ptr(gy), _ptr(prod), None, _ptr(W), _ptr(rsx), _ptr(rsy), B, T, S, 0, st)
+damp = torch.empty_like(amp); dlmp = torch.empty_like(lmp)
 def lib_am():
-    damp = torch.bmm(W.transpose(1, 2), lmp)
+    _lib.call("ftr_normalizer_gemm_f32", 2, _ptr(W), _ptr(lmp), _ptr(damp), B, T, S + 1, C, st)
     _lib.call("ftr_simple_logprobs_bwd_am_f32", _ptr(gx), _ptr(gy), _ptr(damp), _ptr(amp), _ptr(sym), None, C - 1, _ptr(d_am2), B, T, S, C, 0, st)
 def lib_lm():
-    dlmp = torch.bmm(W, amp)
+    _lib.call("ftr_normalizer_gemm_f32", 1, _ptr(W), _ptr(amp), _ptr(dlmp), B, T, S + 1, C, st)
     _lib.call("ftr_simple_logprobs_bwd_lm_f32", _ptr(dlmp), _ptr(lmp), _ptr(sym), _ptr(rsx), _ptr(rsy), C - 1, _ptr(d_lm), B, S, C, st)
 def timeit(f, n=20):
     for _ in range(3): f()
@@ -38,5 +41,14 @@ fl = 2.0 * B * (S + 1) * T * C
 tf = timeit(fused_am) if _lib.lib().ftr_simple_logprobs_fused_bwd_supported(T, C) else float("nan")
 tw, ta, tl = timeit(wk), timeit(lib_am), timeit(lib_lm)
 lib_am()
+tws = {}
+if tf == tf:
+    for ct in (128, 256):
+        os.environ["FTR_FUSED_BWD_CT"] = str(ct)
+        tws[ct] = timeit(fused_am_w)
+    os.environ.pop("FTR_FUSED_BWD_CT")
+    fused_am_w()
+auto = _lib.lib().ftr_simple_logprobs_fused_bwd_am_w_columns(B, T, C)
 err = (d_am - d_am2).abs().max().item() / d_am2.abs().max().item() if tf == tf else float("nan")
-print(f"B={B} T={T} S={S} C={C}: fused d_am {tf:.1f} us ({fl / tf / 1e6:.1f} TFLOP/s) | library: W {tw:.1f} + GEMM+d_am {ta:.1f} + GEMM+d_lm {tl:.1f} us | max rel diff d_am {err:.1e}")
+print(f"B={B} T={T} S={S} C={C}: fused d_am {tf:.1f} us ({fl / tf / 1e6:.1f} TFLOP/s) | W operand " + " ".join(f"{ct} cols {t:.1f} us" for ct, t in tws.items())
+      + f" (auto {auto}) | library: W {tw:.1f} + GEMM+d_am {ta:.1f} + GEMM+d_lm {tl:.1f} us | max rel diff d_am (W operand, auto) {err:.1e}")

@@ -1,4 +1,4 @@
-// csrc/capi.hip -- the extern "C" surface declared in include/ftr.h, include/ftr_lowp.h and include/ftr_kd.h: argument validation and error reporting.  No
+// csrc/capi.hip -- the extern "C" surface declared in include/ftr.h, include/ftr_lowp.h, include/ftr_kd.h and include/ftr_fused.h: argument validation and error reporting.  No
 // allocation, no host synchronisation, no CPU fallback.  Built twice: into libftr_hip.so (the product: the symbols of
 // ftr.h and ftr_lowp.h and nothing else) and, with -DFTR_DIAG, into the test-only _build/libftr_hip_diag.so, which adds the symbols of
 // include/ftr_diag.h: the "plain" kernel family (the reference's arithmetic on the device, mi_plain.hip), its
@@ -703,6 +703,39 @@ int ftr_smoothed_logprobs_fused_bwd_am_f32(const float* gpx, const float* gpy, c
                                            float* d_am, int B, int T, int S, int C, int modified, void* stream) {
   return fused_bwd_am_entry("smoothed_logprobs_fused_bwd_am", true, gpx, gpy, scale, scale_stride, scale_mul, prod, lm_probs, am_probs, symbols, boundary, termination_symbol, combined_scale, direct_scale, unigram, am_dot, am_only_scale, R, d_am, B, T, S, C, modified, stream);
 }
+
+// ---- include/ftr_fused.h: the fused d am kernel with W as an operand
+static int fused_bwd_am_w_entry(const char* what, bool smoothed, const float* gpx, const float* gpy, const float* scale,
+                                int scale_stride, float scale_mul, const float* W, const float* lm_probs,
+                                const float* am_probs, const int32_t* symbols, const int32_t* boundary,
+                                int termination_symbol, float direct_scale, const float* unigram, const float* am_dot,
+                                float am_only_scale, float* R, float* d_am, int B, int T, int S, int C, int modified,
+                                void* stream) {
+  clear_error();
+  FTR_TRY(check_builder(what, B >= 0 && T >= 1 && S >= 0 && C >= 1, termination_symbol, C, true));
+  FTR_TRY(check_scale_stride(what, scale_stride));
+  if (B == 0) return FTR_OK;
+  FTR_TRY(pointers_then_device(what, gpy && W && lm_probs && am_probs && d_am && (!smoothed || (unigram && am_dot && R)) && (gpx || S == 0) && (symbols || S == 0)));
+  return simple_fused_bwd_am_w(gpx, gpy, Scale{scale, scale_stride, scale_mul}, W, lm_probs, am_probs, symbols, boundary, termination_symbol, direct_scale, unigram, am_dot, am_only_scale, R, d_am, B, T, S, C, modified, stream_of(stream));
+}
+
+int ftr_simple_logprobs_fused_bwd_am_w_f32(const float* gpx, const float* gpy, const float* scale, int scale_stride,
+                                           float scale_mul, const float* W, const float* lm_probs, const float* am_probs,
+                                           const int32_t* symbols, const int32_t* boundary, int termination_symbol,
+                                           float* d_am, int B, int T, int S, int C, int modified, void* stream) {
+  return fused_bwd_am_w_entry("simple_logprobs_fused_bwd_am_w", false, gpx, gpy, scale, scale_stride, scale_mul, W, lm_probs, am_probs, symbols, boundary, termination_symbol, 1.0f, nullptr, nullptr, 0.0f, nullptr, d_am, B, T, S, C, modified, stream);
+}
+
+int ftr_smoothed_logprobs_fused_bwd_am_w_f32(const float* gpx, const float* gpy, const float* scale, int scale_stride,
+                                             float scale_mul, const float* W, const float* lm_probs,
+                                             const float* am_probs, const int32_t* symbols, const int32_t* boundary,
+                                             int termination_symbol, float direct_scale, const float* unigram,
+                                             const float* am_dot, float am_only_scale, float* R, float* d_am, int B, int T,
+                                             int S, int C, int modified, void* stream) {
+  return fused_bwd_am_w_entry("smoothed_logprobs_fused_bwd_am_w", true, gpx, gpy, scale, scale_stride, scale_mul, W, lm_probs, am_probs, symbols, boundary, termination_symbol, direct_scale, unigram, am_dot, am_only_scale, R, d_am, B, T, S, C, modified, stream);
+}
+
+int ftr_simple_logprobs_fused_bwd_am_w_columns(int B, int T, int C) { return simple_fused_bwd_columns(B, T, C); }
 
 int ftr_mutual_information_band_supported(int T, int S, int r) { return mi_band_supported(T, S, r); }
 

@@ -5,6 +5,7 @@
 #include <stdio.h>
 #include <stdarg.h>
 #include "../../include/ftr_kd.h"  // and, through it, ftr_lowp.h and ftr.h
+#include "../../include/ftr_fused.h"
 
 namespace ftr {
 
@@ -250,6 +251,8 @@ int normalizer_gemm_choice(int kind, int B, int T, int S1, int C, int* solution,
 int normalizer_gemm_set_choice(int kind, int B, int T, int S1, int C, int solution);
 int simple_fused_fwd(const float* am, const float* lm, const int32_t* symbols, const float* am_probs, const float* lm_probs, const float* am_max, const float* lm_max, const int32_t* boundary, int blank, double delay_penalty, const float* lmonly_norm, const float* amonly_norm, const float* ulog, float cs, float ls, float as, float* px, float* py, float* prod_out, int B, int T, int S, int C, int modified, hipStream_t st);
 int simple_fused_bwd_am(const float* gpx, const float* gpy, Scale scale, const float* prod, const float* lm_probs, const float* am_probs, const int32_t* symbols, const int32_t* boundary, int blank, float cs, float kdir, const float* uvec, const float* amdot, float as, float* Rout, float* d_am, int B, int T, int S, int C, int modified, hipStream_t st);
+int simple_fused_bwd_columns(int B, int T, int C);   // columns per workgroup (128 | 256) the W-operand kernel takes for a shape
+int simple_fused_bwd_am_w(const float* gpx, const float* gpy, Scale scale, const float* W, const float* lm_probs, const float* am_probs, const int32_t* symbols, const int32_t* boundary, int blank, float kdir, const float* uvec, const float* amdot, float as, float* Rout, float* d_am, int B, int T, int S, int C, int modified, hipStream_t st);
 int negated_reduce(const float* ans, int B, int reduction, float* out, hipStream_t st, float sign = -1.0f);   // sign = +1: the plain reduction
 // knowledge distillation on the pruned band: csrc/pruned_kd.hip (collapsed != 0: the three-class form; saved: 2 or 4 planes of [B,T,r])
 int pruned_kd_fwd(const void* logits, int dtype, const void* teacher, int teacher_dtype, const int32_t* symbols, const int32_t* ranges, const int32_t* boundary, int blank, float temperature, int collapsed, float* node, float* saved, float* utt, int B, int T, int S, int C, int r, hipStream_t st);

@@ -335,14 +335,26 @@ __global__ __launch_bounds__(256, 2) void simple_fused_fwd_kernel(
 constexpr int kBT = 64;                           // frames per workgroup
 constexpr int kBS = 16;                           // symbol rows per staged chunk (four MFMA k-steps)
 constexpr int kBLT = kBT + 4;                     // W tile row stride (floats)
-constexpr int kBCB = 16;                          // column blocks per workgroup (256 columns)
+constexpr int kBCB = 16;                          // column blocks per workgroup (256 columns), the wide tiling
 
+// USEW: `prod` is not the forward's product but the W [B,S+1,T] that simple_bwd_w_kernel (simple_logprobs.hip) has just
+// written for the d lm GEMM -- the same expression, term for term (the library is built with -ffp-contract=off), of the same
+// g_px, g_py, scale and prod, so pass 1 stages it with one 16-byte load per quad where the on-the-fly form takes three loads
+// and four divisions.  That kernel writes every cell of W: a masked cell (t = t_end of a regular lattice, the row s = S of
+// g_px) enters as an exact 0 term, and the cells outside an utterance's boundary are -cs * 0 / (prod + tiny) = (-)0 because
+// the occupancies g_px, g_py are 0 there.  What lies outside the ARRAY (rows past S and frames past T of the last tiles, read
+// through clamped addresses) is zeroed here by selection, not by a product.  W does not carry the column sums of g_px and
+// g_py: g_py is still read by the column group that owns the blank column, and both by every group when R is wanted.
+// NCB: column blocks per workgroup.  16 is 256 columns at three workgroups per CU; 8 is 128 columns with half the accumulators
+// and LDS, four workgroups per CU -- C = 500 is 1024 wide tiles on 768 slots, two rounds for 1.33 rounds of work, but 2048
+// narrow tiles on 1024 slots: two full rounds.  The launcher chooses (simple_fused_bwd_columns).
+template <int NCB>
 __host__ __device__ constexpr size_t fused_bwd_lds_bytes() {
-  return sizeof(float) * (2 * kBS * (16 * kBCB) + 2 * kBS * kBLT + 2 * kBS * kBT);
+  return sizeof(float) * (2 * kBS * (16 * NCB) + 2 * kBS * kBLT + 2 * kBS * kBT);
 }
 
-template <bool MOD>
-__global__ __launch_bounds__(256, 2) void simple_fused_bwd_am_kernel(
+template <bool MOD, bool USEW, int NCB>
+__global__ __launch_bounds__(256, NCB <= 8 ? 4 : 2) void simple_fused_bwd_am_kernel(
     const float* __restrict__ gpx, const float* __restrict__ gpy, const Scale scale, const float* __restrict__ prod,
     const float* __restrict__ lm_probs, const float* __restrict__ am_probs, const int32_t* __restrict__ symbols,
     const int32_t* __restrict__ boundary, int blank, float cs, float kdir, const float* __restrict__ uvec,
@@ -350,7 +362,8 @@ __global__ __launch_bounds__(256, 2) void simple_fused_bwd_am_kernel(
   extern __shared__ __attribute__((aligned(16))) float smem[];
   // lm tile rows are CT floats apart with no padding: a fragment read is 16 bytes per lane, 16 consecutive lanes = 256
   // contiguous bytes of one k row, and rows a multiple of 256 bytes apart keep the four rows of a k-step on disjoint banks
-  constexpr int NCB = kBCB, CT = 16 * NCB, LDC = CT, NG = NCB / 4;
+  constexpr int CT = 16 * NCB, LDC = CT, NG = NCB / 4;
+  static_assert(NCB % 4 == 0 && NCB >= 8 && NCB <= 16, "column blocks come in interleaved groups of four");
   float* lmT = smem;                               // [2][kBS][LDC]   lm_probs rows of the chunk
   float* wT = lmT + 2 * kBS * LDC;                 // [2][kBS][kBLT]  W (pass 1) / kdir * gx (pass 2) rows of the chunk
   float* csb = wT + 2 * kBS * kBLT;                // [2][kBS][kBT]   partial column sums (x, y) per staging row class
@@ -396,17 +409,21 @@ __global__ __launch_bounds__(256, 2) void simple_fused_bwd_am_kernel(
   f4 xmask;                                        // g_px counts where the forward wrote a finite px: every frame but t_end (regular)
 #pragma unroll
   for (int e = 0; e < 4; ++e) xmask[e] = (wt < T && (MOD || wt + e != te)) ? sc : 0.0f;
-  struct Stage { f4 lv[NL]; f4 x, y, pr; };
+  // USEW: the column sums are wanted by the group that holds the blank column (sum of y) and, for R, by every group (both
+  // sums); workgroup-uniform, so the loads below sit behind scalar branches
+  const bool want_y = !USEW || uvec != nullptr || (blank >= c0 && blank < c0 + CT);
+  const bool want_x = !USEW || uvec != nullptr;
+  struct Stage { f4 lv[NL]; f4 x, y, pr; };        // pr: the product's quad, or (USEW) W's
   auto load = [&](int kc, Stage& g, bool want_all) {
     const int s = kc * kBS + wrow;
     const int sy_ = min(s, S), sx_ = min(s, S > 0 ? S - 1 : 0);
     if (want_all) {
 #pragma unroll
       for (int u = 0; u < NL; ++u) g.lv[u] = *reinterpret_cast<const f4*>(lmb + (size_t)min(kc * kBS + lrow[u], S) * C + lcol[u]);
-      g.y = *reinterpret_cast<const f4u*>(gyb + (size_t)sy_ * T + wtc);
       g.pr = *reinterpret_cast<const f4u*>(prb + (size_t)sy_ * T + wtc);
+      if (want_y) g.y = *reinterpret_cast<const f4u*>(gyb + (size_t)sy_ * T + wtc);
     }
-    g.x = (S > 0) ? (f4)*reinterpret_cast<const f4u*>(gxb + (size_t)sx_ * T1 + wtc) : f4{0.f, 0.f, 0.f, 0.f};
+    if (want_x) g.x = (S > 0) ? (f4)*reinterpret_cast<const f4u*>(gxb + (size_t)sx_ * T1 + wtc) : f4{0.f, 0.f, 0.f, 0.f};
   };
   f4 sx = {0.f, 0.f, 0.f, 0.f}, sy = {0.f, 0.f, 0.f, 0.f};   // column sums of this thread's row class
 
@@ -426,11 +443,17 @@ __global__ __launch_bounds__(256, 2) void simple_fused_bwd_am_kernel(
       }
       const int s = kc * kBS + wrow;
       const float rowy = s <= S ? sc * tmask : 0.0f, rowx = s < S ? 1.0f : 0.0f;
-      const f4 x = g.x * xmask * rowx, y = g.y * rowy;
       f4 w;
+      if (USEW) {
+        w = (s <= S && wt < T) ? g.pr : f4{0.f, 0.f, 0.f, 0.f};   // a row or quad outside the array came through a clamped address
+        if (want_x) sx += g.x * xmask * rowx;
+        if (want_y) sy += g.y * rowy;
+      } else {
+        const f4 x = g.x * xmask * rowx, y = g.y * rowy;
 #pragma unroll
-      for (int e = 0; e < 4; ++e) w[e] = -cs * (x[e] + y[e]) / (g.pr[e] + kTinyF);
-      sx += x; sy += y;
+        for (int e = 0; e < 4; ++e) w[e] = -cs * (x[e] + y[e]) / (g.pr[e] + kTinyF);
+        sx += x; sy += y;
+      }
       *reinterpret_cast<f4*>(wT + (buf * kBS + wrow) * kBLT + 4 * wq) = w;
     };
     auto compute = [&](int kc) {
@@ -507,7 +530,7 @@ __global__ __launch_bounds__(256, 2) void simple_fused_bwd_am_kernel(
   // round trips to memory at S = 200 instead of thirteen (taken 16 rows at a time, as pass 1 is, this pass was a third of
   // the kernel: every iteration waited for its loads with nothing to overlap them with).
   {
-    constexpr int kB2 = 128;                       // rows per stage: kB2 * kBT floats = the lm tile area
+    constexpr int kB2 = CT / 2;                    // rows per stage: kB2 * kBT floats = the lm tile area (128 rows at 256 columns)
     static_assert(kB2 * kBT <= 2 * kBS * LDC && kB2 <= 2 * kBS * kBLT, "pass 2 reuses the tiles of pass 1");
     float* xT = lmT;                               // [kB2][kBT]
     int* sym2 = reinterpret_cast<int*>(wT);        // [kB2]
@@ -647,20 +670,57 @@ int simple_fused_bwd_supported(int T, int C) {
   return (simple_fused_supported(C) && C >= 4 && T >= 4 && (T % 4) == 0) ? 1 : 0;
 }
 
+// Column blocks per workgroup of the W-operand kernel: the tiling whose tile list fills the device's workgroup slots best.
+// A tiling of NCB blocks runs `wgs` workgroups per CU (LDS: 49 KB / 33 KB of 160); a round of the device is cus * wgs tiles
+// and lasts about wgs * NCB units of matrix-pipe time per CU, so the list costs ceil(tiles / slots) * wgs * NCB.  The narrow
+// tiling re-reads the W tile and walks the epilogue and the scatter pass twice as often per column, which the model does not
+// see, and which has not shown on MI355X: measured (scripts/fused_bwd_bench.py, us, 128 / 256 columns) where the model takes
+// the narrow tiling c3 96 / 124, c2 37 / 44, B8 T1000 S200 C256 29 / 49, c5 767 / 803, c4 461 / 490, and where it takes the
+// wide one B16 T3000 S600 C768 499 / 511 (512 / 511 on another day).  FTR_FUSED_BWD_CT = 128 | 256 forces one (A/B measurements, tests).
+int simple_fused_bwd_columns(int B, int T, int C) {
+  if (const char* e = getenv("FTR_FUSED_BWD_CT")) { const int v = atoi(e); if (v == 128 || v == 256) return v; }
+  const long long slots_cu = current_device_cus(), ft = (long long)((T + kBT - 1) / kBT) * B;
+  auto cost = [&](int ncb, int wgs) {
+    const long long tiles = ft * ((C + 16 * ncb - 1) / (16 * ncb)), slots = slots_cu * wgs;
+    return ((tiles + slots - 1) / slots) * wgs * ncb;
+  };
+  return cost(8, 4) <= cost(16, 3) ? 128 : 256;
+}
+
+template <bool USEW>
+static int fused_bwd_am_launch(const char* what, int ncb, const float* gpx, const float* gpy, Scale scale, const float* prod_or_w,
+                               const float* lm_probs, const float* am_probs, const int32_t* symbols, const int32_t* boundary,
+                               int blank, float cs, float kdir, const float* uvec, const float* amdot, float as, float* Rout,
+                               float* d_am, int B, int T, int S, int C, int modified, hipStream_t st) {
+  if (!simple_fused_bwd_supported(T, C)) {
+    set_error("%s: T = %d, C = %d is outside the fused kernel's domain (T %% 4 == 0, C %% 4 == 0)", what, T, C);
+    return FTR_ERR_UNSUPPORTED;
+  }
+  const dim3 grid((T + kBT - 1) / kBT, (C + 16 * ncb - 1) / (16 * ncb), B);
+  if (grid.z > 65535) { set_error("%s: B = %d > 65535", what, B); return FTR_ERR_UNSUPPORTED; }
+  dispatch(modified != 0, [&](auto mod) {
+    dispatch_among<8, kBCB>(ncb, [&](auto nb) {
+      constexpr int NCB = USEW ? decltype(nb)::value : kBCB;   // the product-operand entry keeps its one tiling
+      hipLaunchKernelGGL((simple_fused_bwd_am_kernel<decltype(mod)::value, USEW, NCB>), grid, dim3(256), fused_bwd_lds_bytes<NCB>(), st, gpx, gpy, scale, prod_or_w, lm_probs, am_probs, symbols, boundary, blank, cs, kdir, uvec, amdot, as, Rout, d_am, T, S, C);
+    });
+  });
+  return check_launch(what);
+}
+
 int simple_fused_bwd_am(const float* gpx, const float* gpy, Scale scale, const float* prod, const float* lm_probs,
                         const float* am_probs, const int32_t* symbols, const int32_t* boundary, int blank, float cs,
                         float kdir, const float* uvec, const float* amdot, float as, float* Rout, float* d_am, int B,
                         int T, int S, int C, int modified, hipStream_t st) {
-  if (!simple_fused_bwd_supported(T, C)) {
-    set_error("simple_logprobs_fused_bwd_am: T = %d, C = %d is outside the fused kernel's domain (T %% 4 == 0, C %% 4 == 0)", T, C);
-    return FTR_ERR_UNSUPPORTED;
-  }
-  const dim3 grid((T + kBT - 1) / kBT, (C + 16 * kBCB - 1) / (16 * kBCB), B);
-  if (grid.z > 65535) { set_error("simple_logprobs_fused_bwd_am: B = %d > 65535", B); return FTR_ERR_UNSUPPORTED; }
-  dispatch(modified != 0, [&](auto mod) {
-    hipLaunchKernelGGL(simple_fused_bwd_am_kernel<decltype(mod)::value>, grid, dim3(256), fused_bwd_lds_bytes(), st, gpx, gpy, scale, prod, lm_probs, am_probs, symbols, boundary, blank, cs, kdir, uvec, amdot, as, Rout, d_am, T, S, C);
-  });
-  return check_launch("simple_logprobs_fused_bwd_am");
+  return fused_bwd_am_launch<false>("simple_logprobs_fused_bwd_am", kBCB, gpx, gpy, scale, prod, lm_probs, am_probs, symbols, boundary, blank, cs, kdir, uvec, amdot, as, Rout, d_am, B, T, S, C, modified, st);
+}
+
+// W: what simple_logprobs_bwd_w wrote for the same gpx, gpy, scale (and combined scale): see USEW at the kernel
+int simple_fused_bwd_am_w(const float* gpx, const float* gpy, Scale scale, const float* W, const float* lm_probs,
+                          const float* am_probs, const int32_t* symbols, const int32_t* boundary, int blank, float kdir,
+                          const float* uvec, const float* amdot, float as, float* Rout, float* d_am, int B, int T, int S,
+                          int C, int modified, hipStream_t st) {
+  const int ncb = simple_fused_bwd_columns(B, T, C) / 16;
+  return fused_bwd_am_launch<true>("simple_logprobs_fused_bwd_am_w", ncb, gpx, gpy, scale, W, lm_probs, am_probs, symbols, boundary, blank, 1.0f, kdir, uvec, amdot, as, Rout, d_am, B, T, S, C, modified, st);
 }
 
 }  // namespace ftr

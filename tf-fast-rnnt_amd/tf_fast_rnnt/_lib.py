@@ -115,9 +115,17 @@ _KD_SIGNATURES = {
     "ftr_pruned_kd_bwd_scaled_dt": (_i, [_c_fp, _i, _c_fp, _i, _c_ip, _c_ip, _c_ip, _i, _f, _i, _c_fp, _c_fp, _i, _f, _c_fp, _i, _i, _i, _i, _i, _c_st]),
     "ftr_pruned_kd_reduce_f32": (_i, [_c_fp, _i, _i, _c_fp, _c_st]),
 }
+# include/ftr_fused.h, the fused d am kernel with W as an operand: the arguments of ftr_*_logprobs_fused_bwd_am_f32 with W in place
+# of prod (and no combined scale: W carries it)
+_FUSED_SIGNATURES = {
+    "ftr_simple_logprobs_fused_bwd_am_w_f32": (_i, [_c_fp, _c_fp, _c_fp, _i, _f, _c_fp, _c_fp, _c_fp, _c_ip, _c_ip, _i, _c_fp, _i, _i, _i, _i, _i, _c_st]),
+    "ftr_smoothed_logprobs_fused_bwd_am_w_f32": (_i, [_c_fp, _c_fp, _c_fp, _i, _f, _c_fp, _c_fp, _c_fp, _c_ip, _c_ip, _i, _f, _c_fp, _c_fp, _f, _c_fp, _c_fp, _i, _i, _i, _i, _i, _c_st]),
+    "ftr_simple_logprobs_fused_bwd_am_w_columns": (_i, [_i, _i, _i]),
+}
 EXPORTED_SYMBOLS = tuple(_SIGNATURES)            # the symbols of include/ftr.h
 LOWP_SYMBOLS = tuple(_LOWP_SIGNATURES)           # those of include/ftr_lowp.h
 KD_SYMBOLS = tuple(_KD_SIGNATURES)               # those of include/ftr_kd.h
+FUSED_SYMBOLS = tuple(_FUSED_SIGNATURES)         # those of include/ftr_fused.h
 FTR_KD_FULL, FTR_KD_COLLAPSED = 0, 1             # include/ftr_kd.h: the `mode` of the kd entry points
 FTR_MI_WS_CLEAN = 1   # include/ftr.h
 FTR_DTYPE_F32, FTR_DTYPE_BF16, FTR_DTYPE_FP16 = 0, 1, 2   # include/ftr_lowp.h: the `kind` of the _dt entry points
@@ -133,7 +141,7 @@ def lib() -> ctypes.CDLL:
                 f"{LIB_PATH} is missing: build the HIP extension first (python -c 'import __graft_entry__ as g; "
                 "g.build()' or make -C tf-fast-rnnt_amd/csrc).  tf_fast_rnnt has no CPU fallback.")
         handle = ctypes.CDLL(LIB_PATH)
-        for name, (restype, argtypes) in {**_SIGNATURES, **_LOWP_SIGNATURES, **_KD_SIGNATURES}.items():
+        for name, (restype, argtypes) in {**_SIGNATURES, **_LOWP_SIGNATURES, **_KD_SIGNATURES, **_FUSED_SIGNATURES}.items():
             fn = getattr(handle, name)   # AttributeError here = header/library mismatch
             fn.restype = restype
             fn.argtypes = argtypes

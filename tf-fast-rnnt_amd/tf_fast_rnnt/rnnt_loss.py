@@ -106,16 +106,31 @@ def _use_fused_builder(C: int) -> bool:
     return os.environ.get("FTR_BUILDER_GEMM", "fused") != "library" and bool(_lib.lib().ftr_simple_logprobs_fused_supported(int(C)))
 
 
-def _use_fused_builder_bwd(T: int, C: int) -> bool:
-    """The fused d am kernel (W^T lm_probs + the scatter by symbol inside one kernel, csrc/simple_fused.hip: `damp` [B,T,C]
-    never goes through memory) where it is the faster route: measured on MI355X it beats library GEMM + epilogue kernel for
-    large vocabularies (B=32 T=2000 S=300 C=1024: 644 us against 308 + 405 with the tuned GEMM) and loses at C = 500 (141 us
-    against 63 + 62; 142 against the untuned GEMM), so the default ("auto") takes it from C >= 768.  FTR_BUILDER_BWD=fused /
-    library force a route (A/B comparisons and the route-vs-route tests)."""
+# (B, T, S, C) -> is the fused d am kernel the faster route on MI355X?  The six measured points behind `auto` below.
+_FUSED_BWD_MEASURED = {
+    (32, 512, 100, 500): True,      # c2
+    (32, 1000, 200, 500): True,     # c3
+    (32, 2000, 300, 1024): True,    # c4
+    (8, 8000, 1000, 512): True,     # c5
+    (16, 3000, 600, 768): True,
+    (8, 1000, 200, 256): True,
+}
+
+
+def _use_fused_builder_bwd(T: int, C: int, B: int = 1) -> bool:
+    """The fused d am kernel (W^T lm_probs + the scatter by symbol inside one kernel, csrc/simple_fused.hip, with the W that
+    the W kernel has just written as its operand: `damp` [B,T,C] is never allocated) against library GEMM kind 2 (measured
+    kernel choice) + epilogue kernel.  Measured on MI355X, us, fused / library (profiles/fused_bwd_am_w.md): inside the step
+    c3 104 / 61 + 59, c5 813 / 477 + 367, c4 (smoothed) 528 against 545 for the kernel that formed W itself; alone, simple
+    loss (scripts/fused_bwd_bench.py) c2 37 / 46, c3 96 / 119, c4 461 / 573, c5 767 / 824, B16 T3000 S600 C768 511 / 581,
+    B8 T1000 S200 C256 29 / 36.  The fused kernel wins at every point, from C = 256 to 1024 and from 128 to 4096 tiles, so
+    the default ("auto") takes it wherever it applies (T % 4 == 0, C % 4 == 0; B does not enter the rule: it enters the
+    kernel's own choice of column tiling).  FTR_BUILDER_BWD=fused / library force a route (A/B comparisons and the
+    route-vs-route tests); outside the kernel's domain every mode takes the library route."""
     mode = os.environ.get("FTR_BUILDER_BWD", "auto")
     if mode == "library" or not _use_fused_builder(C) or not _lib.lib().ftr_simple_logprobs_fused_bwd_supported(int(T), int(C)):
         return False
-    return mode == "fused" or C >= 768
+    return True
 
 
 def _simple_builder(amc, lmc, symbols, am_probs, lm_probs, am_max, lm_max, boundary, blank, delay_penalty, px, py,
@@ -174,9 +189,9 @@ def _simple_backward(saved, meta, gpx, gpy, scale=None, stride=0, mul=1.0):
         _lib.call("ftr_simple_logprobs_bwd_w_scaled_f32", _ptr(gpx), _ptr(gpy), _ptr(scale), stride, mul,
                   _ptr(prod), _ptr(boundary), _ptr(W), _ptr(rsx), _ptr(rsy), B, T, S, modified, st)
         dlmp = _gemm(1, W, am_probs, B, T, S, C, st)         # [B,S+1,C]
-        if _use_fused_builder_bwd(T, C):                       # W^T lm_probs inside the d am kernel (opt-in)
-            _lib.call("ftr_simple_logprobs_fused_bwd_am_f32", _ptr(gpx), _ptr(gpy), _ptr(scale), stride, mul,
-                      _ptr(prod), _ptr(lm_probs), _ptr(am_probs), _ptr(symbols), _ptr(boundary), blank, _ptr(d_am),
+        if _use_fused_builder_bwd(T, C, B):                    # W^T lm_probs inside the d am kernel, W as it stands
+            _lib.call("ftr_simple_logprobs_fused_bwd_am_w_f32", _ptr(gpx), _ptr(gpy), _ptr(scale), stride, mul,
+                      _ptr(W), _ptr(lm_probs), _ptr(am_probs), _ptr(symbols), _ptr(boundary), blank, _ptr(d_am),
                       B, T, S, C, modified, st)
         else:
             damp = _gemm(2, W, lm_probs, B, T, S, C, st)    # [B,T,C]
@@ -1480,9 +1495,9 @@ def _smoothed_backward(saved, meta, gpx, gpy, scale=None, stride=0, mul=1.0):
         _lib.call("ftr_smoothed_logprobs_bwd_w_scaled_f32", _ptr(gpx), _ptr(gpy), _ptr(scale), stride, mul, _ptr(prod),
                   _ptr(boundary), cs, _ptr(W), _ptr(rsx), _ptr(rsy), B, T, S, modified, st)
         dlmp = _gemm(1, W, am_probs, B, T, S, C, st)         # [B,S+1,C]
-        if _use_fused_builder_bwd(T, C):                       # W^T lm_probs inside the d am kernel (opt-in)
-            _lib.call("ftr_smoothed_logprobs_fused_bwd_am_f32", _ptr(gpx), _ptr(gpy), _ptr(scale), stride, mul, _ptr(prod),
-                      _ptr(lm_probs), _ptr(am_probs), _ptr(symbols), _ptr(boundary), blank, cs, cs + a_s, _ptr(u),
+        if _use_fused_builder_bwd(T, C, B):                    # W^T lm_probs inside the d am kernel, W as it stands
+            _lib.call("ftr_smoothed_logprobs_fused_bwd_am_w_f32", _ptr(gpx), _ptr(gpy), _ptr(scale), stride, mul, _ptr(W),
+                      _ptr(lm_probs), _ptr(am_probs), _ptr(symbols), _ptr(boundary), blank, cs + a_s, _ptr(u),
                       _ptr(am_dot), a_s, _ptr(R), _ptr(d_am), B, T, S, C, modified, st)
         else:
             damp = _gemm(2, W, lm_probs, B, T, S, C, st)    # [B,T,C]
