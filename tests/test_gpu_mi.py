@@ -477,10 +477,9 @@ def test_absent_producer_poisons_loudly(ft, dev):
     assert torch.isnan(ans).all()
 
 
-def _band_case(ft, dev, B, T, S, r, modified, seed, offsets=False, break_end=False):
-    """Random band arrays on hand-built monotone ranges -> (band kernel results, lattice kernel results mapped to the band)."""
-    from tf_fast_rnnt import _lib
-    from band_cases import band_to_lattice, lattice_to_band
+def _band_inputs(B, T, S, r, modified, seed, offsets=False, break_end=False):
+    """Random band arrays on hand-built monotone ranges -> (s0, ranges, pxb, pyb, bd, px, py), px / py the lattices they expand to."""
+    from band_cases import band_to_lattice
     rng = np.random.default_rng(seed)
     s0 = np.zeros((B, T), np.int64)
     for b in range(B):
@@ -500,15 +499,33 @@ def _band_case(ft, dev, B, T, S, r, modified, seed, offsets=False, break_end=Fal
             sb = int(rng.integers(lo, min(lo + r, hi + 1))); se = int(rng.integers(max(sb, hi - r + 1), hi + 1))
             bd[b] = (sb, tb, se, te)
     px, py = band_to_lattice(pxb, pyb, s0, bd, S, modified)         # also writes the band builder's -inf into pxb / pyb
+    return s0, ranges, pxb, pyb, bd, px, py
+
+
+def _band_launch(dev, pxb, pyb, ranges, bd, S, modified):
+    """One launch of ftr_mutual_information_band_ws_f32 -> (ans, gx_band, gy_band) as numpy arrays."""
+    from tf_fast_rnnt import _lib
+    B, T, r = pxb.shape
     t_ = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)
     tpx, tpy, tbd, trg = t_(pxb), t_(pyb), t_(bd), t_(ranges)
-    ans = torch.empty(B, device=dev); gxb = torch.empty_like(tpx); gyb = torch.empty_like(tpy)
+    ans = torch.full((B,), 7.0, device=dev); gxb = torch.full_like(tpx, 7.0); gyb = torch.full_like(tpy, 7.0)
     st = torch.cuda.current_stream().cuda_stream
     assert _lib.lib().ftr_mutual_information_band_supported(T, S, r) in (1, 2)    # 2: the streaming kernel (long utterances)
     nws = _lib.lib().ftr_mutual_information_band_workspace_floats(B, T, S, r)
     bws = torch.empty(max(nws, 1), device=dev)
     _lib.call("ftr_mutual_information_band_ws_f32", tpx.data_ptr(), tpy.data_ptr(), trg.data_ptr(), tbd.data_ptr(), bws.data_ptr(), nws,
               ans.data_ptr(), gxb.data_ptr(), gyb.data_ptr(), B, T, S, r, int(modified), st)
+    torch.cuda.synchronize()
+    return ans.cpu().numpy(), gxb.cpu().numpy(), gyb.cpu().numpy()
+
+
+def _band_case(ft, dev, B, T, S, r, modified, seed, offsets=False, break_end=False):
+    """Random band arrays on hand-built monotone ranges -> (band kernel results, lattice kernel results mapped to the band)."""
+    from band_cases import lattice_to_band
+    s0, ranges, pxb, pyb, bd, px, py = _band_inputs(B, T, S, r, modified, seed, offsets, break_end)
+    ans, gxb, gyb = _band_launch(dev, pxb, pyb, ranges, bd, S, modified)
+    t_ = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)
+    tbd = t_(bd)
     lpx = t_(px).requires_grad_(True); lpy = t_(py).requires_grad_(True)
     lans = ft.mutual_information_recursion(lpx, lpy, tbd)
     fin = torch.isfinite(lans)
@@ -516,7 +533,7 @@ def _band_case(ft, dev, B, T, S, r, modified, seed, offsets=False, break_end=Fal
     lgx = np.zeros_like(px) if lpx.grad is None else lpx.grad.cpu().numpy()
     lgy = np.zeros_like(py) if lpy.grad is None else lpy.grad.cpu().numpy()
     egx, egy = lattice_to_band(lgx, lgy, s0, r)
-    return ans.cpu().numpy(), gxb.cpu().numpy(), gyb.cpu().numpy(), lans.detach().cpu().numpy(), egx, egy, fin.cpu().numpy()
+    return ans, gxb, gyb, lans.detach().cpu().numpy(), egx, egy, fin.cpu().numpy()
 
 
 @pytest.mark.parametrize("modified", [False, True])
@@ -540,6 +557,28 @@ def test_band_recursion_kernel_edge_cases(ft, dev, case, modified, impl, monkeyp
         assert np.abs(gx[fin] - egx[fin]).max() <= tol and np.abs(gy[fin] - egy[fin]).max() <= tol
     assert np.isfinite(gx).all() and np.isfinite(gy).all()
     assert (gx[~fin] == 0).all() and (gy[~fin] == 0).all()
+
+
+@pytest.mark.parametrize("modified", [False, True])
+@pytest.mark.parametrize("impl", ["chain", "segments"])
+def test_band_recursion_kernel_edge_cases_nan(ft, dev, modified, impl, monkeypatch):
+    """NaN in the band arrays of one utterance, on every implementation of the band recursion (the forced-stream child of
+    test_streaming_band_kernel_on_every_size selects this test too): every pxb / pyb entry of one frame of utterance 1 is NaN.
+    ans[1] is NaN and the utterance's occupancies are exactly zero (a NaN operand is counted and clamped on its way into a
+    slot, so none enters a chain; the chain kernels then inject zero occupancy at the cut, the segments' flag zeroes the
+    output); utterances 0 and 2 are bit-identical to a launch with clean inputs."""
+    monkeypatch.setenv("FTR_BAND_IMPL", impl)
+    S = 6
+    s0, ranges, pxb, pyb, bd, _, _ = _band_inputs(B=3, T=20, S=S, r=3, modified=modified, seed=2)   # a seed whose bands all hold a path, both types
+    a0, gx0, gy0 = _band_launch(dev, pxb, pyb, ranges, bd, S, modified)
+    assert np.isfinite(a0).all() and np.isfinite(gx0).all() and np.isfinite(gy0).all()
+    pxn, pyn = pxb.copy(), pyb.copy()
+    pxn[1, 9, :] = np.nan; pyn[1, 9, :] = np.nan
+    a, gx, gy = _band_launch(dev, pxn, pyn, ranges, bd, S, modified)
+    assert np.isnan(a[1])
+    assert (gx[1] == 0).all() and (gy[1] == 0).all()
+    for b in (0, 2):
+        assert a[b].tobytes() == a0[b].tobytes() and gx[b].tobytes() == gx0[b].tobytes() and gy[b].tobytes() == gy0[b].tobytes()
 
 
 def test_band_recursion_rejects_non_monotone_ranges(ft, dev):

@@ -26,7 +26,11 @@
 // the per-transition flows (= the occupancies px_grad / py_grad), which a last parallel phase stores band shaped.
 //
 // LDS (per utterance): lo[T+1] (band start per column) and three arrays of (S_n + T_n + 1) x LANES floats: OX, OY
-// (operands, later the two flow outputs) and G.  LANES = 8 while r <= 7, 16 up to r = 15 (r + 1 lanes: see in_band in the kernel).
+// (operands, later the two flow outputs) and G.  LANES = 8 while r <= 7, 16 up to r = 15 (band_lanes_for).
+//
+// What a band cell is, which of its transitions exist, where its operands go and what one step of a chain computes is
+// defined in mi_band_common.h, for the two chain kernels of this file and for the segmented route (mi_band_seg.hip) alike; this
+// file holds the two schedules: their array layouts, loops, prefetches, barriers and fences.
 //
 // The two kernels of this file that touch the joiner logits, band_gather_kernel and band_grad_banded_kernel, take the element
 // type of `logits` / `glogits` as a template argument (float, bf16_t, fp16_t; ftr_common.h): 16-bit values are up-converted on
@@ -34,6 +38,7 @@
 // kernels never see the logits and are float32 only.
 #include "ftr_common.h"
 #include "launch.h"
+#include "mi_band_common.h"
 #include <type_traits>
 #include <cstdlib>
 
@@ -41,23 +46,6 @@ namespace ftr {
 namespace {
 
 constexpr int kBandThreads = 512;   // eight waves for the parallel phases (staging, operands, store); the chains run in wave 0
-
-__device__ __forceinline__ float dpp_row_ror1(float v) {   // lane i of each 16-lane row receives lane (i-1) mod 16
-  return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x121, 0xf, 0xf, false));
-}
-template <int N>
-__device__ __forceinline__ float dpp_row_ror(float v) {
-  return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x120 + N, 0xf, 0xf, false));
-}
-__device__ __forceinline__ float row16_max(float v) {      // all-reduce over the 16 lanes of a DPP row
-  v = fmaxf(v, dpp_row_ror<8>(v)); v = fmaxf(v, dpp_row_ror<4>(v));
-  v = fmaxf(v, dpp_row_ror<2>(v)); v = fmaxf(v, dpp_row_ror<1>(v));
-  return v;
-}
-__device__ __forceinline__ float row16_sum(float v) {
-  v += dpp_row_ror<8>(v); v += dpp_row_ror<4>(v); v += dpp_row_ror<2>(v); v += dpp_row_ror<1>(v);
-  return v;
-}
 
 // ---------------------------------------------------------------------------------------- band gather
 // px_band[b,t,k] = px[b, s0+k, t], py_band[b,t,k] = py[b, s0+k, t] of get_rnnt_logprobs_pruned (rnnt_loss.py:942-1016)
@@ -160,21 +148,13 @@ __global__ __launch_bounds__(kBandThreads) void mi_band_kernel(
   const int tid = threadIdx.x;
   const int lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const Bound bd = load_boundary(boundary, b, S, T);
-  const int Sn = bd.se - bd.sb + 1, Tn = bd.te - bd.tb + 1;
+  const BandUtt utt = band_utt<MOD>(boundary, b, S, T);
   const size_t cells_g = (size_t)T * r;
   float* gx_g = gxb + (size_t)b * cells_g;
   float* gy_g = gyb + (size_t)b * cells_g;
-  if (Sn <= 0 || Tn <= 0 || Tn == 1) {
-    // empty rectangle: ans = 0 (mi_wave_bidir.hip); a single column has no frame inside the rectangle: only the
-    // one-cell lattice has a path (no transitions at all)
-    for (size_t i = tid; i < cells_g; i += kBandThreads) { gx_g[i] = 0.0f; gy_g[i] = 0.0f; }
-    if (tid == 0) ans[b] = (Sn <= 0 || Tn <= 0) ? 0.0f : ((Sn == 1) ? 0.0f : -INFINITY);
-    return;
-  }
+  if (utt.degenerate) { band_answer_flat<kBandThreads>(gx_g, gy_g, cells_g, tid, ans + b, band_degenerate_ans(utt)); return; }
   FTR_BSTAMP(0);
-  const int te = bd.te, tb = bd.tb, sb = bd.sb, se = bd.se;
-  const int D = (MOD ? 0 : (Sn - 1)) + (Tn - 1);
+  const int te = utt.bd.te, tb = utt.bd.tb, sb = utt.bd.sb, se = utt.bd.se, Sn = utt.Sn, Tn = utt.Tn, D = utt.D;
   const int jm = D >> 1;                                            // the cut, in chain A's steps; chain B meets it at D - jm
   const int rowA = 1 + 2 * kBandAhead, rowB = rowA + jm + 2;
   // ---- LDS carve-up
@@ -183,43 +163,17 @@ __global__ __launch_bounds__(kBandThreads) void mi_band_kernel(
   const int ncap = (S + T + 5 + 4 * kBandAhead) * LANES;            // fetches run up to two groups past either end
   float2* O2 = reinterpret_cast<float2*>(cutSB + 16);               // 8-byte aligned: an even number of ints in front
   float* G = reinterpret_cast<float*>(O2 + ncap);
-  float* cutA = G + ncap; float* cutB = cutA + 16; float* occ = cutB + 16;   // 16 each, indexed by s & 15
+  float* cutA = G + ncap;                                           // cutA cutB occ: 16 each, indexed by s & 15
   auto div_r = [&](int i) { return rinv ? (int)__umulhi((unsigned)i, rinv) : i; };   // i / r for 0 <= i < 2^32 / r (rinv = 0: r = 1)
 
-  // ---- band start per lattice column: the column t_end has no frame of its own, it continues the last frame's band
-  const int32_t* rg = ranges + (size_t)b * T * r;
-  for (int t0 = 0; t0 <= T; t0 += 4 * kBandThreads) {               // four independent loads in flight per lane
-    int v[4];
-#pragma unroll
-    for (int u = 0; u < 4; ++u) { const int t = t0 + u * kBandThreads + tid; v[u] = (t <= T) ? rg[(size_t)min(t, te - 1) * r] : 0; }
-#pragma unroll
-    for (int u = 0; u < 4; ++u) { const int t = t0 + u * kBandThreads + tid; if (t <= T) lo[t] = v[u]; }
-  }
+  band_load_lo<kBandThreads>(lo, ranges + (size_t)b * T * r, T, te, r, tid);
   for (int i = tid; i < ncap; i += kBandThreads) O2[i] = make_float2(kNeg, kNeg);   // slots without a cell
   if (tid < 32) cutSA[tid] = -1;
   __syncthreads();
   FTR_BSTAMP(1);
-  {
-    // the one precondition the wavefront order rests on: the band start never decreases along t (two cells of one walk
-    // step would otherwise share a slot).  A violation is answered loudly: ans = NaN, zero occupancies.
-    int bad = 0;
-    for (int t = tb + 1 + tid; t < te; t += kBandThreads) bad |= (lo[t] < lo[t - 1]);
-    if (__syncthreads_or(bad)) {
-      for (size_t i = tid; i < cells_g; i += kBandThreads) { gx_g[i] = 0.0f; gy_g[i] = 0.0f; }
-      if (tid == 0) ans[b] = __builtin_nanf("");
-      return;
-    }
-  }
+  if (band_lo_decreases<kBandThreads>(lo, tb, te, tid)) { band_answer_flat<kBandThreads>(gx_g, gy_g, cells_g, tid, ans + b, __builtin_nanf("")); return; }
   if (tid < LANES) O2[(rowA + jm + 1) * LANES + tid] = make_float2(kNeg, 0.0f);   // chain A's pad step
-  // Column t_end has no frame: its cells are where the last frame's transitions lead.  For the regular type that is the
-  // last frame's band again (py moves along a row; px inside column t_end is masked by fix_for_boundary); for the modified
-  // type px moves up one row AND one column, so the END CELL may sit one row above that band (s_end = lo + r) and still be
-  // reached -- by the last frame's top px.  (Any other cell of column t_end is a dead end and needs no slot.)
-  const bool end_above = MOD && se == lo[te] + r;
-  auto in_band = [&](int s, int t) { const int l = lo[t]; return (s >= l && s <= l + r - 1) || (end_above && t == te && s == se); };
-  // wavefront slot of a lattice cell in chain A's part / chain B's part of the arrays
-  auto slotA = [&](int s, int t) { return (rowA + (MOD ? (t - tb) : (s - sb) + (t - tb))) * LANES + ((s - sb) & (LANES - 1)); };
-  auto slotB = [&](int s, int t) { return (rowB + (MOD ? (te - t) : (se - s) + (te - t))) * LANES + ((se - s) & (LANES - 1)); };
+  const BandGeom<MOD, LANES> g(r, utt.bd, lo[te], rowA, rowB);
 
   // ---- operands, one input array at a time: the band is staged band shaped in the G region (16-byte loads, eight in
   // flight per lane) and scattered from there into wavefront order with all the masking applied:
@@ -266,32 +220,28 @@ __global__ __launch_bounds__(kBandThreads) void mi_band_kernel(
     for (int i = tid; i < Tn * r; i += kBandThreads) {
       const int q = div_r(i);
       const int t = tb + q, k = i - q * r;
-      const int s = lo[t] + k;
+      const int l0 = lo[t], lm = t > tb ? lo[t - 1] : l0, lp = t < te ? lo[t + 1] : l0;
+      const int s = l0 + k;
       if (s < sb || s > se) continue;
-      const int dg = MOD ? (t - tb) : (s - sb) + (t - tb);
+      const int dg = g.dgA(s, t);
       if (dg <= jm) {
         float av = kNeg;
-        if (ISX) { const int tx = MOD ? t - 1 : t; if (s - 1 >= sb && tx >= tb && tx <= te - 1 && in_band(s - 1, tx)) av = staged(s - 1, tx) - c2; }
-        else { if (t - 1 >= tb && in_band(s, t - 1)) av = staged(s, t - 1) - c2; if (s == sb && t == tb) av = 0.0f; }   // origin trick
-        nan_acc = max(nan_acc, __float_as_uint(av) & 0x7fffffffu);
-        O[2 * slotA(s, t)] = fmaxf(av, kNeg);
-        if (ISX && dg == jm) cutSA[(s - sb) & (LANES - 1)] = s;
+        if (ISX) { if (g.x_in(s, t, l0, lm)) av = staged(s - 1, MOD ? t - 1 : t) - c2; }
+        else { if (g.y_in(s, t, lm)) av = staged(s, t - 1) - c2; if (s == sb && t == tb) av = 0.0f; }   // origin trick
+        O[2 * g.slotA(s, t)] = band_clamp(av, nan_acc);
+        if (ISX && dg == jm) cutSA[g.laneA(s)] = s;
       }
       if (dg >= jm) {
         float bv = kNeg;
-        if (t <= te - 1) {
-          if (ISX) { const int tnx = MOD ? t + 1 : t; if (s + 1 <= se && tnx <= te && in_band(s + 1, tnx)) bv = staged(s, t) - c2; }
-          else if (in_band(s, t + 1)) bv = staged(s, t) - c2;
-        }
+        if (t <= te - 1 && (ISX ? g.x_out(s, t, l0, lp) : g.y_out(s, t, lp))) bv = staged(s, t) - c2;
         if (!ISX && s == se && t == te) bv = 0.0f;                   // chain B's origin is the end cell
-        nan_acc = max(nan_acc, __float_as_uint(bv) & 0x7fffffffu);
-        O[2 * slotB(s, t)] = fmaxf(bv, kNeg);
-        if (ISX && dg == jm) cutSB[(se - s) & (LANES - 1)] = s;
+        O[2 * g.slotB(s, t)] = band_clamp(bv, nan_acc);
+        if (ISX && dg == jm) cutSB[g.laneB(s)] = s;
       }
     }
-    // the end cell outside the band of column t_end (see in_band): chain B's origin, no outgoing transitions; its walk
-    // step D is behind the cut unless the rectangle is a single column (handled above)
-    if (end_above && tid == 0) O[2 * slotB(se, te)] = ISX ? kNeg : 0.0f;
+    // the end cell outside the band of column t_end (BandGeom::end_above): chain B's origin, no outgoing transitions; its
+    // walk step D is behind the cut unless the rectangle is a single column (handled above)
+    if (g.end_above && tid == 0) O[2 * g.slotB(se, te)] = ISX ? kNeg : 0.0f;
   };
   float sumx, cntx, sumy, cnty;
   stage(pxb);
@@ -310,7 +260,7 @@ __global__ __launch_bounds__(kBandThreads) void mi_band_kernel(
   const float cy2 = shift_from_sums<MOD>(0.0f, 0.0f, sumy, cnty, Sn, Tn).cy2;
   operands(std::false_type{}, cy2);
   const double shift_back = shift_total<MOD>(Shift{cx2, cy2}, Sn, Tn);   // what the shifts took out of ans (log2 units)
-  const bool poisoned = __syncthreads_or(nan_acc > 0x7f800000u) != 0;
+  const bool poisoned = __syncthreads_or(band_saw_nan(nan_acc)) != 0;
   FTR_BSTAMP(5);
 
   // ---- the two chains, in wave 0: chain A in DPP rows 0 and 2, chain B in DPP rows 1 and 3, and with LANES = 8 both
@@ -329,28 +279,11 @@ __global__ __launch_bounds__(kBandThreads) void mi_band_kernel(
     // a group of U steps ahead of their use, at immediate offsets from one running address.
     const int n1 = D - jm + 1;
     const int base1 = (isB ? rowB : rowA) * LANES + lg;
-    auto fwd = [&](int slot, float2 o) {
-      const float up = dpp_row_ror1(val);
-      const float a_ = up + o.x, b_ = val + o.y;
-      const float d = a_ - b_;
-      const float ex = __builtin_amdgcn_exp2f(-__builtin_fabsf(d));
-      val = fmaxf(a_, b_) + __builtin_amdgcn_logf(1.0f + ex);
-      const float rc = __builtin_amdgcn_rcpf(1.0f + ex);
-      G[slot] = (d >= 0.0f) ? rc : ex * rc;
-    };
-    // Renormalisation ("frames", as in mi_wave_bidir.hip): every 32 steps the chain's values are brought back to the
-    // neighbourhood of zero by an integer shift, the same for all lanes of the chain (a uniform shift of an anti-diagonal
-    // changes no split ratio), so that float32 keeps its resolution whatever the magnitude of the log-probabilities -- the
-    // static shift above only removes what the band's MEAN transition predicts.  The maximum is taken from a copy made 2 U
-    // steps earlier; on the chain it costs one subtraction, but the four dependent DPP maxima in front of it are not free on
-    // a lone in-order wave (every 8 steps they cost the LDS kernel 8 % and the streaming kernel 24 %), hence every 32.
-    // frame = what has been subtracted so far, added back on the cut.
+    auto fwd = [&](int slot, float2 o) { G[slot] = chain_fwd(val, o); };
+    // Renormalisation (chain_renorm) every 32 steps, from a copy of the value made 2 U steps earlier: on the chain it costs
+    // one subtraction, but the four dependent DPP maxima in front of it are not free on a lone in-order wave (every 8 steps
+    // they cost the LDS kernel 8 % and the streaming kernel 24 %), hence every 32.
     float frame = 0.0f;
-    auto renorm = [&](float snap) {   // snap: this lane's value 2 U steps ago (no shift in between: the same frame)
-      const float mx = row16_max(snap);
-      const float st = (mx > kNegThresh) ? __builtin_rintf(mx) : 0.0f;
-      val -= st; frame += st;
-    };
     {
       // two register sets, each filled half an iteration (U steps) before it is used
       float2 oa[U], ob[U];
@@ -369,32 +302,13 @@ __global__ __launch_bounds__(kBandThreads) void mi_band_kernel(
         for (int u = 0; u < U; ++u) oa[u] = O2[sl + (2 * U + u) * LANES];
 #pragma unroll
         for (int u = 0; u < U; ++u) fwd(sl + (U + u) * LANES, ob[u]);
-        if (rn) renorm(snap);
+        if (rn) chain_renorm(val, frame, snap);
       }
       for (; i < n1; ++i) fwd(base1 + i * LANES, O2[base1 + i * LANES]);
     }
     FTR_BSTAMP(6);
-    // ---- the cut: p + q per cut cell (keyed by s mod 16: at most one cut cell per residue), ans, occupancies
-    if (lane < 48) cutA[lane] = kNeg;                         // cutA, cutB, occ
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    const int scut = (isB ? cutSB : cutSA)[lg];               // lattice row of this lane's cut cell
-    if (scut >= 0) (isB ? cutB : cutA)[scut & 15] = val;
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    {
-      // both chains' frames: chain A's lanes hold theirs in DPP rows 0 / 2, chain B's in rows 1 / 3
-      const float frA = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, frame), 0));
-      const float frB = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, frame), 16));
-      const float v = cutA[l16] + cutB[l16];
-      const float m = row16_max(v);
-      const float e = exp2f(v - m);
-      const float sum = row16_sum(e);
-      const float total = m + log2f(sum);
-      const bool dead = !(total > kNegThresh);
-      if (lane < 16) occ[lane] = (dead || poisoned) ? 0.0f : e / sum;
-      if (lane == 0) ans[b] = poisoned ? __builtin_nanf("") : (dead ? -INFINITY : (float)(((double)total + (double)frA + (double)frB + shift_back) * 0.6931471805599453));
-    }
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    const float inj = (scut >= 0) ? occ[scut & 15] : 0.0f;   // the occupancy this lane injects at its cut cell
+    // ---- the cut: ans, and the occupancy this lane injects at its cut cell
+    const float inj = chain_cut(val, frame, lane, l16, lg, isB, cutSA, cutSB, cutA, cutA + 16, cutA + 32, poisoned, shift_back, ans + b);
     FTR_BSTAMP(7);
     // ---- phase 2: flow.  Each chain walks on from the cut through the other chain's half: at its step j it is on the
     // cells the other chain had at step D - j (chain B's surplus step lands on the front pad row).  No masks: a transition
@@ -405,13 +319,7 @@ __global__ __launch_bounds__(kBandThreads) void mi_band_kernel(
     float xo = 0.0f, yo = 0.0f;
     const int n2 = D - jm + 1;
     const int top = (isB ? rowA + jm : rowB + D - jm) * LANES + ((Sn - 1 - lg) & (LANES - 1));
-    auto flow = [&](int slot, float g, auto first) {
-      const float xin = dpp_row_ror1(xo), yin = yo;
-      float pg = xin + yin;
-      if (decltype(first)::value) pg += inj;
-      O2[slot] = make_float2(xin, yin);
-      xo = pg * g; yo = pg - xo;
-    };
+    auto flow = [&](int slot, float ratio, auto first) { O2[slot] = chain_flow<decltype(first)::value>(xo, yo, ratio, inj); };
     flow(top, G[top], std::true_type{});
     {
       // step i reads slot top - i * LANES, going down in memory: the 2 U rows in front of the pad row take the fetches
@@ -436,23 +344,13 @@ __global__ __launch_bounds__(kBandThreads) void mi_band_kernel(
     FTR_BSTAMP(8);
   }   // wave 0
   __syncthreads();
-  // ---- store the occupancies band shaped: gx_band[b,t,k] = px_grad[b, s0+k, t], gy_band likewise; zero elsewhere.
-  // A transition whose source cell lies in front of the cut was handled by chain B (flow kept at the source cell), one
-  // whose source lies on or behind the cut by chain A (flow kept at the destination cell).
+  // ---- store the occupancies band shaped: gx_band[b,t,k] = px_grad[b, s0+k, t], gy_band likewise; zero elsewhere
   for (int i = tid; i < T * r; i += kBandThreads) {
     const int t = div_r(i), k = i - t * r;
     float fx = 0.0f, fy = 0.0f;
     if (t >= tb && t < te) {
       const int s = lo[t] + k;
-      if (s >= sb && s <= se) {
-        const int dg = MOD ? (t - tb) : (s - sb) + (t - tb);
-        if (dg < jm) { const float2 f = O2[slotA(s, t)]; fx = f.x; fy = f.y; }
-        else {
-          const int tnx = MOD ? t + 1 : t;
-          if (s + 1 <= se && tnx <= te && in_band(s + 1, tnx)) fx = O2[slotB(s + 1, tnx)].x;
-          if (in_band(s, t + 1)) fy = O2[slotB(s, t + 1)].y;
-        }
-      }
+      if (s >= sb && s <= se) band_cell_flows(g, O2, jm, s, t, lo[t], lo[t + 1], fx, fy);
     }
     gx_g[i] = fx;
     gy_g[i] = fy;
@@ -487,18 +385,12 @@ __global__ __launch_bounds__(kBandThreads) void mi_band_stream_kernel(
   const int tid = threadIdx.x;
   const int lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const Bound bd = load_boundary(boundary, b, S, T);
-  const int Sn = bd.se - bd.sb + 1, Tn = bd.te - bd.tb + 1;
+  const BandUtt utt = band_utt<MOD>(boundary, b, S, T);
   const size_t cells_g = (size_t)T * r;
   float* gx_g = gxb + (size_t)b * cells_g;
   float* gy_g = gyb + (size_t)b * cells_g;
-  if (Sn <= 0 || Tn <= 0 || Tn == 1) {
-    for (size_t i = tid; i < cells_g; i += kBandThreads) { gx_g[i] = 0.0f; gy_g[i] = 0.0f; }
-    if (tid == 0) ans[b] = (Sn <= 0 || Tn <= 0) ? 0.0f : ((Sn == 1) ? 0.0f : -INFINITY);
-    return;
-  }
-  const int te = bd.te, tb = bd.tb, sb = bd.sb, se = bd.se;
-  const int D = (MOD ? 0 : (Sn - 1)) + (Tn - 1);
+  if (utt.degenerate) { band_answer_flat<kBandThreads>(gx_g, gy_g, cells_g, tid, ans + b, band_degenerate_ans(utt)); return; }
+  const int te = utt.bd.te, tb = utt.bd.tb, sb = utt.bd.sb, se = utt.bd.se, Sn = utt.Sn, Tn = utt.Tn, D = utt.D;
   const int jm = D >> 1;
   constexpr int P = kStreamP;
   const int rowA = 2 * P, rowB = rowA + (jm + 1) + 2 * P;          // [2P pad][A part][2P pad][B part][2P pad]
@@ -506,20 +398,13 @@ __global__ __launch_bounds__(kBandThreads) void mi_band_stream_kernel(
   // ---- LDS: lo[], cut rows, cut exchange;  global: O2 (float2 per slot), G
   int* lo = reinterpret_cast<int*>(smem);
   int* cutSA = lo + ((T + 2) & ~1); int* cutSB = cutSA + 16;
-  float* cutA = reinterpret_cast<float*>(cutSB + 16); float* cutB = cutA + 16; float* occ = cutB + 16;
+  float* cutA = reinterpret_cast<float*>(cutSB + 16);              // cutA cutB occ: 16 each
   float* wsb = ws + (size_t)b * band_stream_floats_per_utt<LANES>(T, S);
   float2* O2 = reinterpret_cast<float2*>(wsb);
   float* G = wsb + 2 * band_stream_rows<LANES>(T, S) * LANES;
   auto div_r = [&](int i) { return rinv ? (int)__umulhi((unsigned)i, rinv) : i; };
 
-  const int32_t* rg = ranges + (size_t)b * T * r;
-  for (int t0 = 0; t0 <= T; t0 += 4 * kBandThreads) {
-    int v[4];
-#pragma unroll
-    for (int u = 0; u < 4; ++u) { const int t = t0 + u * kBandThreads + tid; v[u] = (t <= T) ? rg[(size_t)min(t, te - 1) * r] : 0; }
-#pragma unroll
-    for (int u = 0; u < 4; ++u) { const int t = t0 + u * kBandThreads + tid; if (t <= T) lo[t] = v[u]; }
-  }
+  band_load_lo<kBandThreads>(lo, ranges + (size_t)b * T * r, T, te, r, tid);
   for (int i = tid; i < nrows * LANES; i += kBandThreads) { O2[i] = make_float2(kNeg, 0.0f); G[i] = 0.0f; }   // neutral slots
   if (tid < 32) cutSA[tid] = -1;
   // the utterance's shift constants (ftr_common.h, Shift) from a fixed sample of the band arrays: 2048 entries of each,
@@ -527,20 +412,8 @@ __global__ __launch_bounds__(kBandThreads) void mi_band_stream_kernel(
   const float* pxu = pxb + (size_t)b * T * r;
   const float* pyu = pyb + (size_t)b * T * r;
   {
-    const unsigned nfr = (unsigned)(te - tb) * (unsigned)r;
-    float sx = 0.0f, nx = 0.0f, sy = 0.0f, ny = 0.0f;
-    float vx[4], vy[4];
-#pragma unroll
-    for (int u = 0; u < 4; ++u) {
-      const unsigned i = (unsigned)tb * (unsigned)r + __umulhi((unsigned)(tid + kBandThreads * u) * 0x9E3779B1u, nfr);
-      vx[u] = pxu[i]; vy[u] = pyu[i];
-    }
-#pragma unroll
-    for (int u = 0; u < 4; ++u) {
-      if (shift_sample_ok(vx[u])) { sx += vx[u]; nx += 1.0f; }
-      if (shift_sample_ok(vy[u])) { sy += vy[u]; ny += 1.0f; }
-    }
-    sx = wave_sum_dpp(sx); nx = wave_sum_dpp(nx); sy = wave_sum_dpp(sy); ny = wave_sum_dpp(ny);
+    float sx, nx, sy, ny;
+    band_shift_sample<kBandThreads, 4>(pxu, pyu, tb, te, r, tid, sx, nx, sy, ny);
     if (lane == 0) { cutA[wave] = sx; cutA[8 + wave] = nx; cutA[16 + wave] = sy; cutA[24 + wave] = ny; }
   }
   __syncthreads();
@@ -552,56 +425,32 @@ __global__ __launch_bounds__(kBandThreads) void mi_band_stream_kernel(
     sh = shift_from_sums<MOD>(sx, nx, sy, ny, Sn, Tn);
   }
   const double shift_back = shift_total<MOD>(sh, Sn, Tn);
-  {
-    int bad = 0;
-    for (int t = tb + 1 + tid; t < te; t += kBandThreads) bad |= (lo[t] < lo[t - 1]);
-    if (__syncthreads_or(bad)) {     // see the LDS kernel: the band start must not decrease
-      for (size_t i = tid; i < cells_g; i += kBandThreads) { gx_g[i] = 0.0f; gy_g[i] = 0.0f; }
-      if (tid == 0) ans[b] = __builtin_nanf("");
-      return;
-    }
-  }
-  const bool end_above = MOD && se == lo[te] + r;              // see the LDS kernel
-  auto in_band = [&](int s, int t) { const int l = lo[t]; return (s >= l && s <= l + r - 1) || (end_above && t == te && s == se); };
-  auto slotA = [&](int s, int t) { return (rowA + (MOD ? (t - tb) : (s - sb) + (t - tb))) * LANES + ((s - sb) & (LANES - 1)); };
-  auto slotB = [&](int s, int t) { return (rowB + (MOD ? (te - t) : (se - s) + (te - t))) * LANES + ((se - s) & (LANES - 1)); };
-  // band value at lattice cell (s, t), frame t < te, log2 domain, shifted
-  auto at = [&](const float* src, float c2, int s, int t) { return __builtin_fmaf(src[(size_t)t * r + (s - lo[t])], kLog2e, -c2); };
+  if (band_lo_decreases<kBandThreads>(lo, tb, te, tid)) { band_answer_flat<kBandThreads>(gx_g, gy_g, cells_g, tid, ans + b, __builtin_nanf("")); return; }
+  const BandGeom<MOD, LANES> g(r, utt.bd, lo[te], rowA, rowB);
   unsigned nan_acc = 0;
-  auto put = [&](int slot, float x, float y) {
-    nan_acc = max(nan_acc, max(__float_as_uint(x) & 0x7fffffffu, __float_as_uint(y) & 0x7fffffffu));
-    O2[slot] = make_float2(fmaxf(x, kNeg), fmaxf(y, kNeg));
-  };
   // ---- operands of every band cell, both arrays in one pass, straight from global memory
   for (int i = tid; i < Tn * r; i += kBandThreads) {
     const int q = div_r(i);
     const int t = tb + q, k = i - q * r;
-    const int s = lo[t] + k;
+    const int l0 = lo[t];
+    const int s = l0 + k;
     if (s < sb || s > se) continue;
-    const int dg = MOD ? (t - tb) : (s - sb) + (t - tb);
+    const int dg = g.dgA(s, t);
     if (dg <= jm) {        // chain A: the transitions INTO the cell
-      float ax = kNeg, ay = kNeg;
-      const int tx = MOD ? t - 1 : t;
-      if (s - 1 >= sb && tx >= tb && tx <= te - 1 && in_band(s - 1, tx)) ax = at(pxu, sh.cx2, s - 1, tx);
-      if (t - 1 >= tb && in_band(s, t - 1)) ay = at(pyu, sh.cy2, s, t - 1);
-      if (s == sb && t == tb) ay = 0.0f;                               // origin trick
-      put(slotA(s, t), ax, ay);
-      if (dg == jm) cutSA[(s - sb) & (LANES - 1)] = s;
+      float ax, ay;
+      band_operands_in(g, pxu, pyu, sh.cx2, sh.cy2, s, t, l0, t > tb ? lo[t - 1] : l0, ax, ay);
+      band_put(O2, g.slotA(s, t), ax, ay, nan_acc);
+      if (dg == jm) cutSA[g.laneA(s)] = s;
     }
     if (dg >= jm) {        // chain B: the transitions OUT of the cell
-      float bx = kNeg, by = kNeg;
-      if (t <= te - 1) {
-        const int tnx = MOD ? t + 1 : t;
-        if (s + 1 <= se && tnx <= te && in_band(s + 1, tnx)) bx = at(pxu, sh.cx2, s, t);
-        if (in_band(s, t + 1)) by = at(pyu, sh.cy2, s, t);
-      }
-      if (s == se && t == te) by = 0.0f;                               // chain B's origin is the end cell
-      put(slotB(s, t), bx, by);
-      if (dg == jm) cutSB[(se - s) & (LANES - 1)] = s;
+      float bx, by;   // lo[t] is read again: carrying l0 over the cutSA store above costs the regular type 2 VGPRs
+      band_operands_out(g, pxu, pyu, sh.cx2, sh.cy2, s, t, lo[t], t < te ? lo[t + 1] : lo[t], bx, by);
+      band_put(O2, g.slotB(s, t), bx, by, nan_acc);
+      if (dg == jm) cutSB[g.laneB(s)] = s;
     }
   }
-  if (end_above && tid == 0) O2[slotB(se, te)] = make_float2(kNeg, 0.0f);
-  const bool poisoned = __syncthreads_or(nan_acc > 0x7f800000u) != 0;
+  if (g.end_above && tid == 0) O2[g.slotB(se, te)] = make_float2(kNeg, 0.0f);   // the end cell above the last frame's band
+  const bool poisoned = __syncthreads_or(band_saw_nan(nan_acc)) != 0;
   __threadfence();   // the slots were written by other waves of this workgroup: nothing stale in this CU's L1 from here on
 
   if (wave == 0) {
@@ -613,22 +462,8 @@ __global__ __launch_bounds__(kBandThreads) void mi_band_stream_kernel(
     const int n1 = D - jm + 1;
     const int nrun = ((n1 + P - 1) / P) * P;                    // both chains, whole blocks: the surplus steps are neutral
     const int base1 = (isB ? rowB : rowA) * LANES + lg;
-    auto fwd = [&](int slot, float2 o) {
-      const float up = dpp_row_ror1(val);
-      const float a_ = up + o.x, b_ = val + o.y;
-      const float d = a_ - b_;
-      const float ex = __builtin_amdgcn_exp2f(-__builtin_fabsf(d));
-      val = fmaxf(a_, b_) + __builtin_amdgcn_logf(1.0f + ex);
-      const float rc = __builtin_amdgcn_rcpf(1.0f + ex);
-      G[slot] = (d >= 0.0f) ? rc : ex * rc;
-    };
-    // renormalisation of the chains' values twice per block of P = 48 steps, see the LDS kernel
-    float frame = 0.0f;
-    auto renorm = [&](float snap) {
-      const float mx = row16_max(snap);
-      const float st = (mx > kNegThresh) ? __builtin_rintf(mx) : 0.0f;
-      val -= st; frame += st;
-    };
+    auto fwd = [&](int slot, float2 o) { G[slot] = chain_fwd(val, o); };
+    float frame = 0.0f;                                         // renormalisation (chain_renorm) twice per block of P = 48 steps
     {
       float2 o[NS][U];
 #pragma unroll
@@ -646,44 +481,18 @@ __global__ __launch_bounds__(kBandThreads) void mi_band_stream_kernel(
           for (int u = 0; u < U; ++u) o[kf][u] = O2[base1 + (i + (k + NS - 1) * U + u) * LANES];
 #pragma unroll
           for (int u = 0; u < U; ++u) fwd(base1 + (i + k * U + u) * LANES, o[k][u]);
-          if (k == NS / 2 - 1 || k == NS - 1) renorm(snap);   // every 24 steps, from a copy 8 steps old
+          if (k == NS / 2 - 1 || k == NS - 1) chain_renorm(val, frame, snap);   // every 24 steps, from a copy 8 steps old
         }
       }
     }
-    // ---- the cut (LDS), as in the LDS kernel
-    if (lane < 48) cutA[lane] = kNeg;
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    const int scut = (isB ? cutSB : cutSA)[lg];
-    if (scut >= 0) (isB ? cutB : cutA)[scut & 15] = val;
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    {
-      // both chains' frames: chain A's lanes hold theirs in DPP rows 0 / 2, chain B's in rows 1 / 3
-      const float frA = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, frame), 0));
-      const float frB = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, frame), 16));
-      const float v = cutA[l16] + cutB[l16];
-      const float m = row16_max(v);
-      const float e = exp2f(v - m);
-      const float sum = row16_sum(e);
-      const float total = m + log2f(sum);
-      const bool dead = !(total > kNegThresh);
-      if (lane < 16) occ[lane] = (dead || poisoned) ? 0.0f : e / sum;
-      if (lane == 0) ans[b] = poisoned ? __builtin_nanf("") : (dead ? -INFINITY : (float)(((double)total + (double)frA + (double)frB + shift_back) * 0.6931471805599453));
-    }
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    const float inj = (scut >= 0) ? occ[scut & 15] : 0.0f;
+    const float inj = chain_cut(val, frame, lane, l16, lg, isB, cutSA, cutSB, cutA, cutA + 16, cutA + 32, poisoned, shift_back, ans + b);   // the cut (LDS)
     __builtin_amdgcn_s_waitcnt(0);                              // the ratios of both chains are in memory before anybody reads them
     // ---- flow: each chain walks down through the other chain's part (and on into the neutral pad rows)
     float xo = 0.0f, yo = 0.0f;
     const int n2 = D - jm + 1;
     const int nrun2 = ((n2 - 1 + P - 1) / P) * P;               // steps after the first one, whole blocks
     const int top = (isB ? rowA + jm : rowB + D - jm) * LANES + ((Sn - 1 - lg) & (LANES - 1));
-    auto flow = [&](int slot, float g, auto first) {
-      const float xin = dpp_row_ror1(xo), yin = yo;
-      float pg = xin + yin;
-      if (decltype(first)::value) pg += inj;
-      O2[slot] = make_float2(xin, yin);
-      xo = pg * g; yo = pg - xo;
-    };
+    auto flow = [&](int slot, float ratio, auto first) { O2[slot] = chain_flow<decltype(first)::value>(xo, yo, ratio, inj); };
     flow(top, G[top], std::true_type{});
     {
       float g[NS][U];
@@ -711,15 +520,7 @@ __global__ __launch_bounds__(kBandThreads) void mi_band_stream_kernel(
     float fx = 0.0f, fy = 0.0f;
     if (t >= tb && t < te) {
       const int s = lo[t] + k;
-      if (s >= sb && s <= se) {
-        const int dg = MOD ? (t - tb) : (s - sb) + (t - tb);
-        if (dg < jm) { const float2 f = O2[slotA(s, t)]; fx = f.x; fy = f.y; }
-        else {
-          const int tnx = MOD ? t + 1 : t;
-          if (s + 1 <= se && tnx <= te && in_band(s + 1, tnx)) fx = O2[slotB(s + 1, tnx)].x;
-          if (in_band(s, t + 1)) fy = O2[slotB(s, t + 1)].y;
-        }
-      }
+      if (s >= sb && s <= se) band_cell_flows(g, O2, jm, s, t, lo[t], lo[t + 1], fx, fy);
     }
     gx_g[i] = fx;
     gy_g[i] = fy;
@@ -812,20 +613,14 @@ __global__ void band_grad_banded_kernel(const E* __restrict__ logits, const int3
 
 }  // namespace
 
-// 8-lane chains while the band is at most 7 rows wide (half the LDS), 16-lane chains up to 15 rows
+// the lanes of the LDS-resident kernel (band_lanes_for; 8 lanes take half the LDS), 0 where its arrays do not fit
 static int band_lanes(int T, int S, int r) {
-  if (r < 1 || T < 1 || S < 0) return 0;
-  // r + 1 lanes: the modified type may have r + 1 cells on its last walk step (the end cell one row above the last
-  // frame's band, see the kernel)
-  if (r <= 7 && band_lds_bytes<8>(T, S) <= (size_t)150 * 1024) return 8;
-  if (r <= 15 && band_lds_bytes<16>(T, S) <= (size_t)150 * 1024) return 16;
-  return 0;
+  const int lanes = band_lanes_for(r);
+  if (!lanes || T < 1 || S < 0) return 0;
+  return (lanes == 8 ? band_lds_bytes<8>(T, S) : band_lds_bytes<16>(T, S)) <= (size_t)150 * 1024 ? lanes : 0;
 }
+static int band_stream_lanes(int T, int r) { return band_stream_lds_bytes(T) > (size_t)150 * 1024 ? 0 : band_lanes_for(r); }
 // 0: not supported; 1: the LDS-resident kernel; 2: the streaming kernel (needs mi_band_workspace_floats() floats of workspace)
-static int band_stream_lanes(int T, int r) {
-  if (r < 1 || r > 15 || band_stream_lds_bytes(T) > (size_t)150 * 1024) return 0;
-  return r <= 7 ? 8 : 16;
-}
 int mi_band_supported(int T, int S, int r) {
   static const bool force_stream = getenv("FTR_BAND_FORCE_STREAM") != nullptr;   // test knob: every size through the streaming kernel
   if (!force_stream && band_lanes(T, S, r) != 0) return 1;
@@ -870,9 +665,6 @@ int band_gather(const void* logits, int dtype, const int32_t* symbols, const int
   });
   return check_launch("band_gather");
 }
-
-// the dynamic-LDS limit of the chain kernels: 156 KB, not 160 -- they also have a few bytes of static LDS (__syncthreads_or)
-constexpr size_t kBandLdsCeiling = 156 * 1024;
 
 int mi_band(const float* pxb, const float* pyb, const int32_t* ranges, const int32_t* boundary, float* ws, size_t ws_floats,
             float* ans, float* gxb, float* gyb, int B, int T, int S, int r, int modified, hipStream_t st) {

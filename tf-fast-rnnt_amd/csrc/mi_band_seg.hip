@@ -27,8 +27,11 @@
 //   band_seg_occupancy one thread per band cell: px_grad / py_grad band shaped, ans
 // The geometry (walk length D, K, steps per segment) depends on the utterance's boundary, i.e. on device data: every kernel
 // derives it the same way (seg_geom) and surplus workgroups leave.
+// What a band cell is, which of its transitions exist and where its operands go (BandGeom, band_operands_in / _out) is
+// defined in mi_band_common.h, for this route and the chain kernels of mi_band.hip alike.
 #include "ftr_common.h"
 #include "launch.h"
+#include "mi_band_common.h"
 #include <cstdlib>
 #include <cstring>
 
@@ -40,30 +43,6 @@ constexpr int kSegTarget = 64;    // steps per segment aimed at while K < kSegMa
 constexpr int kSegU = 4;          // steps per operand fetch group (as kBandAhead in mi_band.hip)
 constexpr int kSegFlagBad = 1, kSegFlagNaN = 2, kSegFlagNoOrigin = 4, kSegFlagNoEnd = 8;
 
-__device__ __forceinline__ float seg_ror1(float v) {   // lane i of each 16-lane row receives lane (i-1) mod 16
-  return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x121, 0xf, 0xf, false));
-}
-template <int N>
-__device__ __forceinline__ float seg_ror(float v) {
-  return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x120 + N, 0xf, 0xf, false));
-}
-__device__ __forceinline__ float seg_row_max(float v) {
-  v = fmaxf(v, seg_ror<8>(v)); v = fmaxf(v, seg_ror<4>(v));
-  v = fmaxf(v, seg_ror<2>(v)); v = fmaxf(v, seg_ror<1>(v));
-  return v;
-}
-
-__device__ __forceinline__ double seg_ror1d(double v) {
-  const int lo = __builtin_amdgcn_update_dpp(0, __double2loint(v), 0x121, 0xf, 0xf, false);
-  const int hi = __builtin_amdgcn_update_dpp(0, __double2hiint(v), 0x121, 0xf, 0xf, false);
-  return __hiloint2double(hi, lo);
-}
-template <int N>
-__device__ __forceinline__ double seg_rord(double v) {
-  const int lo = __builtin_amdgcn_update_dpp(0, __double2loint(v), 0x120 + N, 0xf, 0xf, false);
-  const int hi = __builtin_amdgcn_update_dpp(0, __double2hiint(v), 0x120 + N, 0xf, 0xf, false);
-  return __hiloint2double(hi, lo);
-}
 constexpr double kNegD = -1.0e30, kNegThreshD = -1.0e29;
 
 struct SegGeom { int D, K, L; };
@@ -107,16 +86,8 @@ struct SegWs {
 };
 constexpr int kRow0 = 1;   // row of walk step 0
 
-struct SegUtt { Bound bd; int Sn, Tn, D; bool degenerate; };
-template <bool MOD>
-__device__ __forceinline__ SegUtt seg_utt(const int32_t* boundary, int b, int S, int T) {
-  SegUtt u;
-  u.bd = load_boundary(boundary, b, S, T);
-  u.Sn = u.bd.se - u.bd.sb + 1; u.Tn = u.bd.te - u.bd.tb + 1;
-  u.degenerate = u.Sn <= 0 || u.Tn <= 0 || u.Tn == 1;
-  u.D = (MOD ? 0 : (u.Sn - 1)) + (u.Tn - 1);
-  return u;
-}
+// band start per lattice column, read from `ranges` (rg: the utterance's): the column t_end continues the last frame's band
+__device__ __forceinline__ int seg_lo(const int32_t* __restrict__ rg, int t, int te, int r) { return rg[(size_t)min(t, te - 1) * r]; }
 
 // ---------------------------------------------------------------------------------------- init: neutral slots, header, shift
 template <bool MOD, int LANES>
@@ -128,9 +99,9 @@ __global__ __launch_bounds__(256) void band_seg_init_kernel(const float* __restr
   const size_t n = 2 * seg_rows(T, S) * LANES;   // OA and OB are adjacent
   for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (size_t)gridDim.x * 256) w.OA[i] = make_float2(kNeg, 0.0f);
   if (blockIdx.x != 0) return;
-  // the utterance's shift constants from a fixed sample of the band arrays (as mi_band_stream_kernel: 2048 entries of each)
+  // the utterance's shift constants from a fixed sample of the band arrays
   __shared__ float red[16];
-  const SegUtt u = seg_utt<MOD>(boundary, b, S, T);
+  const BandUtt u = band_utt<MOD>(boundary, b, S, T);
   if (threadIdx.x == 0) {
     // a chain may only start from a cell that IS a band cell (a lane keeps its value over slots without a cell: a start value
     // in a lane whose first cell is not the origin would leak into whatever row takes that lane later); flags also collects
@@ -145,22 +116,8 @@ __global__ __launch_bounds__(256) void band_seg_init_kernel(const float* __restr
     *w.flags() = f;
   }
   if (u.degenerate) return;
-  const float* pxu = pxb + (size_t)b * T * r;
-  const float* pyu = pyb + (size_t)b * T * r;
-  const unsigned nfr = (unsigned)(u.bd.te - u.bd.tb) * (unsigned)r;
-  float sx = 0.0f, nx = 0.0f, sy = 0.0f, ny = 0.0f;
-  float vx[8], vy[8];
-#pragma unroll
-  for (int q = 0; q < 8; ++q) {
-    const unsigned i = (unsigned)u.bd.tb * (unsigned)r + __umulhi((unsigned)(threadIdx.x + 256 * q) * 0x9E3779B1u, nfr);
-    vx[q] = pxu[i]; vy[q] = pyu[i];
-  }
-#pragma unroll
-  for (int q = 0; q < 8; ++q) {
-    if (shift_sample_ok(vx[q])) { sx += vx[q]; nx += 1.0f; }
-    if (shift_sample_ok(vy[q])) { sy += vy[q]; ny += 1.0f; }
-  }
-  sx = wave_sum_dpp(sx); nx = wave_sum_dpp(nx); sy = wave_sum_dpp(sy); ny = wave_sum_dpp(ny);
+  float sx, nx, sy, ny;
+  band_shift_sample<256, 8>(pxb + (size_t)b * T * r, pyb + (size_t)b * T * r, u.bd.tb, u.bd.te, r, threadIdx.x, sx, nx, sy, ny);
   const int wave = threadIdx.x >> 6;
   if ((threadIdx.x & 63) == 0) { red[wave] = sx; red[4 + wave] = nx; red[8 + wave] = sy; red[12 + wave] = ny; }
   __syncthreads();
@@ -174,58 +131,17 @@ __global__ __launch_bounds__(256) void band_seg_init_kernel(const float* __restr
 }
 
 // ---------------------------------------------------------------------------------------- scatter: one thread per band cell
-// Geometry helpers shared by the scatter and the occupancy pass (the conventions are mi_band.hip's).
-template <bool MOD, int LANES>
-struct SegBand {
-  const int32_t* rg; int r, sb, tb, se, te; bool end_above; int lo_te;
-  __device__ SegBand(const int32_t* ranges, int b, int T, int r_, const Bound& bd) : rg(ranges + (size_t)b * T * r_), r(r_), sb(bd.sb), tb(bd.tb), se(bd.se), te(bd.te) {
-    lo_te = lo(te);
-    end_above = MOD && se == lo_te + r;
-  }
-  // band start per lattice column: the column t_end has no frame of its own, it continues the last frame's band
-  __device__ int lo(int t) const { return rg[(size_t)min(t, te - 1) * r]; }
-  __device__ bool in_band(int s, int t, int l) const { return (s >= l && s <= l + r - 1) || (end_above && t == te && s == se); }
-  __device__ int dgA(int s, int t) const { return MOD ? (t - tb) : (s - sb) + (t - tb); }
-  __device__ int dgB(int s, int t) const { return MOD ? (te - t) : (se - s) + (te - t); }
-  __device__ int slotA(int s, int t) const { return (kRow0 + dgA(s, t)) * LANES + ((s - sb) & (LANES - 1)); }
-  __device__ int slotB(int s, int t) const { return (kRow0 + dgB(s, t)) * LANES + ((se - s) & (LANES - 1)); }
-};
-
-// operands of band cell (s, t): (ax, ay) = the transitions INTO it (chain A's slot), (bx, by) = the transitions OUT of it
-// (chain B's slot); log2 domain, shifted; kNeg where the transition does not exist, leaves the rectangle or leaves the band.
-// l0 / lm / lp: band start of columns t, t - 1, t + 1.
-template <bool MOD, int LANES>
-__device__ __forceinline__ void seg_cell_operands(const SegBand<MOD, LANES>& g, const float* __restrict__ pxu, const float* __restrict__ pyu,
-                                                  float cx2, float cy2, int s, int t, int l0, int lm, int lp,
-                                                  float& ax, float& ay, float& bx, float& by) {
-  const int r = g.r, sb = g.sb, tb = g.tb, se = g.se, te = g.te;
-  auto at = [&](const float* src, float c2, int ss, int tt, int l) { return __builtin_fmaf(src[(size_t)tt * r + (ss - l)], kLog2e, -c2); };
-  ax = kNeg; ay = kNeg; bx = kNeg; by = kNeg;
-  {
-    const int tx = MOD ? t - 1 : t;
-    const int lx = MOD ? lm : l0;
-    if (s - 1 >= sb && tx >= tb && tx <= te - 1 && g.in_band(s - 1, tx, lx)) ax = at(pxu, cx2, s - 1, tx, lx);
-    if (t - 1 >= tb && g.in_band(s, t - 1, lm)) ay = at(pyu, cy2, s, t - 1, lm);
-    if (s == sb && t == tb) ay = 0.0f;                               // origin trick
-  }
-  if (t <= te - 1) {
-    const int tnx = MOD ? t + 1 : t;
-    const int ln = MOD ? lp : l0;
-    if (s + 1 <= se && tnx <= te && g.in_band(s + 1, tnx, ln)) bx = at(pxu, cx2, s, t, l0);
-    if (g.in_band(s, t + 1, lp)) by = at(pyu, cy2, s, t, l0);
-  }
-  if (s == se && t == te) by = 0.0f;                                 // chain B's origin is the end cell
-}
-
 template <bool MOD, int LANES>
 __global__ __launch_bounds__(256) void band_seg_scatter_kernel(const float* __restrict__ pxb, const float* __restrict__ pyb,
                                                                const int32_t* __restrict__ ranges, const int32_t* __restrict__ boundary,
                                                                float* __restrict__ ws, int T, int S, int r) {
   const int b = blockIdx.y;
-  const SegUtt u = seg_utt<MOD>(boundary, b, S, T);
+  const BandUtt u = band_utt<MOD>(boundary, b, S, T);
   if (u.degenerate) return;
   const SegWs<LANES> w(ws + (size_t)b * seg_floats_per_utt<LANES>(T, S), T, S);
-  const SegBand<MOD, LANES> g(ranges, b, T, r, u.bd);
+  const int32_t* rg = ranges + (size_t)b * T * r;
+  const int sb = u.bd.sb, tb = u.bd.tb, se = u.bd.se, te = u.bd.te;
+  const BandGeom<MOD, LANES> g(r, u.bd, seg_lo(rg, te, te, r), kRow0, kRow0);
   const int i = blockIdx.x * 256 + threadIdx.x;
   const int q = i / r, k = i - q * r;
   const int t = u.bd.tb + q;
@@ -233,32 +149,28 @@ __global__ __launch_bounds__(256) void band_seg_scatter_kernel(const float* __re
   const float cx2 = w.hdr[1], cy2 = w.hdr[2];
   const float* pxu = pxb + (size_t)b * T * r;
   const float* pyu = pyb + (size_t)b * T * r;
-  const int sb = u.bd.sb, tb = u.bd.tb, se = u.bd.se, te = u.bd.te;
-  const int l0 = g.lo(t), lm = t > tb ? g.lo(t - 1) : l0, lp = t < te ? g.lo(t + 1) : l0;
+  const int l0 = seg_lo(rg, t, te, r), lm = t > tb ? seg_lo(rg, t - 1, te, r) : l0, lp = t < te ? seg_lo(rg, t + 1, te, r) : l0;
   unsigned nan_acc = 0;
   int bad = 0;
-  if (k == 0 && t > tb && t < te && l0 < lm) bad = kSegFlagBad;   // the band start must not decrease (mi_band.hip)
-  auto at = [&](const float* src, float c2, int s, int tt, int l) { return __builtin_fmaf(src[(size_t)tt * r + (s - l)], kLog2e, -c2); };
-  auto put = [&](float2* O, int slot, float x, float y) {
-    nan_acc = max(nan_acc, max(__float_as_uint(x) & 0x7fffffffu, __float_as_uint(y) & 0x7fffffffu));
-    O[slot] = make_float2(fmaxf(x, kNeg), fmaxf(y, kNeg));
-  };
+  if (k == 0 && t > tb && t < te && l0 < lm) bad = kSegFlagBad;   // the band start must not decrease (band_lo_decreases)
   const int s = l0 + k;
   if (s >= sb && s <= se) {
     float ax, ay, bx, by;
-    seg_cell_operands<MOD, LANES>(g, pxu, pyu, cx2, cy2, s, t, l0, lm, lp, ax, ay, bx, by);
-    put(w.OA, g.slotA(s, t), ax, ay);
-    put(w.OB, g.slotB(s, t), bx, by);
+    band_operands_in(g, pxu, pyu, cx2, cy2, s, t, l0, lm, ax, ay);
+    band_operands_out(g, pxu, pyu, cx2, cy2, s, t, l0, lp, bx, by);
+    band_put(w.OA, g.slotA(s, t), ax, ay, nan_acc);
+    band_put(w.OB, g.slotB(s, t), bx, by, nan_acc);
   }
-  // the end cell outside the band of column t_end (modified type, see mi_band.hip): reached by the last frame's top px only
+  // the end cell outside the band of column t_end (BandGeom::end_above): reached by the last frame's top px only (its py
+  // does not exist: the cell is above the band of column t_end - 1), no outgoing transitions
   if (g.end_above && i == 0) {
-    float ax = kNeg;
-    const int lq = g.lo(te - 1);
-    if (se - 1 >= sb && te - 1 >= tb && g.in_band(se - 1, te - 1, lq)) ax = at(pxu, cx2, se - 1, te - 1, lq);
-    put(w.OA, g.slotA(se, te), ax, kNeg);
+    float ax, ay;
+    const int lq = seg_lo(rg, te - 1, te, r);
+    band_operands_in(g, pxu, pyu, cx2, cy2, se, te, lq, lq, ax, ay);
+    band_put(w.OA, g.slotA(se, te), ax, ay, nan_acc);
     w.OB[g.slotB(se, te)] = make_float2(kNeg, 0.0f);
   }
-  int fl = bad | ((nan_acc > 0x7f800000u) ? kSegFlagNaN : 0);
+  int fl = bad | (band_saw_nan(nan_acc) ? kSegFlagNaN : 0);
   if (__any(fl != 0)) {
     int all = 0;
     for (int bit = 1; bit <= 2; bit <<= 1) if (__any((fl & bit) != 0)) all |= bit;
@@ -269,13 +181,13 @@ __global__ __launch_bounds__(256) void band_seg_scatter_kernel(const float* __re
 // ---------------------------------------------------------------------------------------- the chain over one segment
 // Operands of the segment's rows are staged in LDS (seg[row][lg], L + 2 U rows: the fetches run two groups ahead); every
 // 16-lane DPP row of the calling waves runs its own chain over the SAME operands.  With LANES = 8 both halves of a row carry
-// the same 8-lane chain, which makes the 16-lane rotate an 8-lane one (mi_band.hip).
+// the same 8-lane chain, which makes the 16-lane rotate an 8-lane one.
 // STORE: keep every step's values in LDS (pbuf[row][lg]; written by DPP row 0 of wave 0).
 template <int LANES, bool STORE>
 __device__ __forceinline__ void seg_chain(const float2* __restrict__ seg, int L, int lg, double& val, double* __restrict__ pbuf, bool writer) {
   constexpr int U = kSegU;
   auto fwd = [&](int row, float2 o) {
-    const double up = seg_ror1d(val);
+    const double up = row16_ror<1>(val);
     const double a_ = up + (double)o.x, b_ = val + (double)o.y;
     const float d = (float)(a_ - b_);
     const float ex = __builtin_amdgcn_exp2f(-__builtin_fabsf(d));
@@ -311,7 +223,7 @@ template <bool MOD, int LANES>
 __global__ __launch_bounds__(16 * LANES) void band_seg_transfer_kernel(const int32_t* __restrict__ boundary, float* __restrict__ ws, int T, int S) {
   extern __shared__ __attribute__((aligned(16))) float2 seg[];
   const int sg = blockIdx.x, dir = blockIdx.y, b = blockIdx.z;
-  const SegUtt u = seg_utt<MOD>(boundary, b, S, T);
+  const BandUtt u = band_utt<MOD>(boundary, b, S, T);
   if (u.degenerate) return;
   const SegGeom gm = seg_geom(u.D);
   if (sg >= gm.K - 1) return;                      // nobody needs the last segment's matrix
@@ -336,7 +248,7 @@ template <bool MOD, int LANES>
 __global__ __launch_bounds__(64) void band_seg_prefix_kernel(const int32_t* __restrict__ boundary, float* __restrict__ ws, int T, int S) {
   extern __shared__ __attribute__((aligned(16))) double mats[];   // [K - 1][LANES][LANES]
   const int dir = blockIdx.x, b = blockIdx.y;
-  const SegUtt u = seg_utt<MOD>(boundary, b, S, T);
+  const BandUtt u = band_utt<MOD>(boundary, b, S, T);
   if (u.degenerate) return;
   const SegGeom gm = seg_geom(u.D);
   const SegWs<LANES> w(ws + (size_t)b * seg_floats_per_utt<LANES>(T, S), T, S);
@@ -358,7 +270,7 @@ __global__ __launch_bounds__(64) void band_seg_prefix_kernel(const int32_t* __re
       double si = val;
       switch (i) {   // compile-time rotate counts
         case 0: break;
-#define FTR_ROT(N) case N: si = seg_rord<N>(val); break;
+#define FTR_ROT(N) case N: si = row16_ror<N>(val); break;
         FTR_ROT(1) FTR_ROT(2) FTR_ROT(3) FTR_ROT(4) FTR_ROT(5) FTR_ROT(6) FTR_ROT(7) FTR_ROT(8)
         FTR_ROT(9) FTR_ROT(10) FTR_ROT(11) FTR_ROT(12) FTR_ROT(13) FTR_ROT(14) FTR_ROT(15)
 #undef FTR_ROT
@@ -384,7 +296,7 @@ template <bool MOD, int LANES>
 __global__ __launch_bounds__(64) void band_seg_final_kernel(const int32_t* __restrict__ boundary, float* __restrict__ ws, int T, int S) {
   extern __shared__ __attribute__((aligned(16))) float2 seg[];
   const int sg = blockIdx.x, dir = blockIdx.y, b = blockIdx.z;
-  const SegUtt u = seg_utt<MOD>(boundary, b, S, T);
+  const BandUtt u = band_utt<MOD>(boundary, b, S, T);
   if (u.degenerate) return;
   const SegGeom gm = seg_geom(u.D);
   if (sg >= gm.K) return;
@@ -409,16 +321,17 @@ __global__ __launch_bounds__(256) void band_seg_occupancy_kernel(const int32_t* 
   const int b = blockIdx.y;
   const int i = blockIdx.x * 256 + threadIdx.x;
   const size_t cells = (size_t)T * r;
-  const SegUtt u = seg_utt<MOD>(boundary, b, S, T);
+  const BandUtt u = band_utt<MOD>(boundary, b, S, T);
   float* gx_g = gxb + (size_t)b * cells;
   float* gy_g = gyb + (size_t)b * cells;
   if (u.degenerate) {
     if ((size_t)i < cells) { gx_g[i] = 0.0f; gy_g[i] = 0.0f; }
-    if (i == 0) ans[b] = (u.Sn <= 0 || u.Tn <= 0) ? 0.0f : ((u.Sn == 1) ? 0.0f : -INFINITY);
+    if (i == 0) ans[b] = band_degenerate_ans(u);
     return;
   }
   const SegWs<LANES> w(const_cast<float*>(ws) + (size_t)b * seg_floats_per_utt<LANES>(T, S), T, S);
-  const SegBand<MOD, LANES> g(ranges, b, T, r, u.bd);
+  const int32_t* rg = ranges + (size_t)b * T * r;
+  const BandGeom<MOD, LANES> g(r, u.bd, seg_lo(rg, u.bd.te, u.bd.te, r), kRow0, kRow0);
   const int flags = *w.flags();
   const int fl = flags & (kSegFlagBad | kSegFlagNaN);
   const int sb = u.bd.sb, tb = u.bd.tb, se = u.bd.se, te = u.bd.te;
@@ -431,8 +344,7 @@ __global__ __launch_bounds__(256) void band_seg_occupancy_kernel(const int32_t* 
   const int t = i / r, k = i - t * r;
   float fx = 0.0f, fy = 0.0f;
   if (!fl && !dead && t >= tb && t < te) {
-    const int l0 = g.lo(t);
-    const int s = l0 + k;
+    const int s = seg_lo(rg, t, te, r) + k;
     if (s >= sb && s <= se) {
       const double pa = w.PA[g.slotA(s, t)];
       if (pa > kNegThreshD) {
@@ -452,7 +364,6 @@ __global__ __launch_bounds__(256) void band_seg_occupancy_kernel(const int32_t* 
   gy_g[i] = fy;
 }
 
-inline int seg_lanes(int r) { return r <= 7 ? 8 : (r <= 15 ? 16 : 0); }
 constexpr int kSegFrom = 1100;   // S + T from which this route is taken (below: the chain kernels of mi_band.hip)
 inline size_t seg_lds_bytes(int T, int S, int lanes, bool store) {
   const size_t L = (size_t)seg_lmax(T, S);
@@ -472,7 +383,7 @@ inline size_t seg_lds_bytes(int T, int S, int lanes, bool store) {
 int mi_band_seg_supported(int T, int S, int r) {
   bool forced = false;
   if (const char* e = getenv("FTR_BAND_IMPL")) { if (!strcmp(e, "chain")) return 0; forced = !strcmp(e, "segments"); }
-  const int lanes = seg_lanes(r);
+  const int lanes = band_lanes_for(r);
   if (!lanes || T < 1 || S < 0 || r < 1) return 0;
   if (!forced && (long long)S + T < kSegFrom) return 0;
   if (seg_lds_bytes(T, S, lanes, true) > (size_t)150 * 1024) return 0;
@@ -481,7 +392,7 @@ int mi_band_seg_supported(int T, int S, int r) {
 }
 size_t mi_band_seg_workspace_floats(int B, int T, int S, int r) {
   if (!mi_band_seg_supported(T, S, r)) return 0;
-  return (size_t)B * (seg_lanes(r) == 8 ? seg_floats_per_utt<8>(T, S) : seg_floats_per_utt<16>(T, S));
+  return (size_t)B * (band_lanes_for(r) == 8 ? seg_floats_per_utt<8>(T, S) : seg_floats_per_utt<16>(T, S));
 }
 
 int mi_band_seg(const float* pxb, const float* pyb, const int32_t* ranges, const int32_t* boundary, float* ws, size_t ws_floats,
@@ -492,12 +403,11 @@ int mi_band_seg(const float* pxb, const float* pyb, const int32_t* ranges, const
     set_error("mutual_information_band (segments): workspace of %zu floats (16-byte aligned) required, got %zu", need, ws_floats);
     return FTR_ERR_INVALID_ARG;
   }
-  const int lanes = seg_lanes(r);
+  const int lanes = band_lanes_for(r);
   const size_t lds_t = seg_lds_bytes(T, S, lanes, false), lds_f = seg_lds_bytes(T, S, lanes, true);
   const unsigned cells_blocks = (unsigned)(((size_t)(T + 1) * r + 255) / 256);
   const unsigned fill_blocks = (unsigned)((2 * seg_rows(T, S) * lanes + 255) / 256);
   const dim3 gseg(kSegMaxK, 2, B);
-  constexpr size_t ceiling = 156 * 1024;   // as the chain kernels of mi_band.hip: room for a few bytes of static LDS
   const char* what = "mutual_information_band (segments)";
   const int rc = dispatch_among<8, 16>(lanes, [&](auto lv) {
     return dispatch(modified != 0, [&](auto mod) {
@@ -505,8 +415,8 @@ int mi_band_seg(const float* pxb, const float* pyb, const int32_t* ranges, const
       constexpr int LV = decltype(lv)::value;
       constexpr auto transfer = band_seg_transfer_kernel<MODV, LV>;
       constexpr auto final_k = band_seg_final_kernel<MODV, LV>;
-      int rcl = reserve_lds<transfer>(ceiling, what);
-      if (rcl == FTR_OK) rcl = reserve_lds<final_k>(ceiling, what);
+      int rcl = reserve_lds<transfer>(kBandLdsCeiling, what);
+      if (rcl == FTR_OK) rcl = reserve_lds<final_k>(kBandLdsCeiling, what);
       if (rcl != FTR_OK) return rcl;
       hipLaunchKernelGGL((band_seg_init_kernel<MODV, LV>), dim3(fill_blocks, B), dim3(256), 0, st, pxb, pyb, ranges, boundary, ws, T, S, r);
       hipLaunchKernelGGL((band_seg_scatter_kernel<MODV, LV>), dim3(cells_blocks, B), dim3(256), 0, st, pxb, pyb, ranges, boundary, ws, T, S, r);
