@@ -1065,6 +1065,68 @@ int ftr_tdt_pruned_logprobs_bwd_scaled_f32(const float* logits, const int32_t* s
                           Scale{scale, scale_stride, scale_mul}, glogits, B, T, S, C, r, stream_of(stream));
 }
 
+// ---- include/ftr_band_tdt.h: the TDT loss on the pruned band itself (csrc/mi_band_tdt.hip, csrc/tdt_logprobs.hip)
+size_t ftr_mutual_information_band_tdt_workspace_floats(int B, int T, int S, int r, int N, int Ny) {
+  return mi_band_tdt_workspace_floats(B, T, S, r, N, Ny);
+}
+int ftr_mutual_information_band_tdt_supported(int T, int S, int r, int N, int Ny) { return mi_band_tdt_supported(T, S, r, N, Ny); }
+
+int ftr_mutual_information_band_tdt_f32(const float* px_band, const float* py_band, const int32_t* ranges,
+                                        const int32_t* boundary, const int32_t* token_durations, int N,
+                                        const int32_t* blank_durations, int Ny, float* workspace, size_t workspace_floats,
+                                        float* ans, float* gx_band, float* gy_band, int B, int T, int S, int r,
+                                        void* stream) {
+  const char* what = "mutual_information_band_tdt";
+  clear_error();
+  FTR_TRY(tdt_check_list(what, "token_durations", token_durations, N, 5, 0));
+  FTR_TRY(tdt_check_list(what, "blank_durations", blank_durations, Ny, 5, 1));
+  FTR_TRY(check_sizes(what, B >= 0 && T >= 1 && S >= 0 && r >= 1));
+  if (!mi_band_tdt_supported(T, S, r, N, Ny)) {
+    set_error("%s: T=%d S=%d r=%d is outside the kernel's domain (r <= 15)", what, T, S, r);
+    return FTR_ERR_UNSUPPORTED;
+  }
+  if (B == 0) return FTR_OK;
+  FTR_TRY(check_ws_size(what, workspace_floats, mi_band_tdt_workspace_floats(B, T, S, r, N, Ny), "floats"));
+  FTR_REQUIRE(px_band && py_band && ranges && workspace && ans, "%s: null px_band / py_band / ranges / workspace / ans", what);
+  FTR_REQUIRE((gx_band != nullptr) == (gy_band != nullptr), "%s: gx_band and gy_band must both be given or both be null", what);
+  FTR_TRY(check_ws_aligned(what, workspace));
+  FTR_TRY(device_ok());
+  return mi_band_tdt(px_band, py_band, ranges, boundary, token_durations, N, blank_durations, Ny, workspace, workspace_floats, ans,
+                     gx_band, gy_band, B, T, S, r, stream_of(stream));
+}
+
+int ftr_tdt_pruned_band_fwd_f32(const float* logits, const int32_t* symbols, const int32_t* ranges,
+                                const int32_t* boundary, int termination_symbol, const int32_t* durations, int N,
+                                double sigma, double delay_penalty, float* lse_tok, float* lse_dur, float* px_band,
+                                float* py_band, int B, int T, int S, int C, int r, void* stream) {
+  const char* what = "tdt_pruned_band_fwd";
+  clear_error();
+  FTR_TRY(tdt_check_head(what, durations, N, sigma, termination_symbol, C));
+  FTR_TRY(check_sizes(what, B >= 0 && T >= 1 && S >= 0 && r >= 1));
+  FTR_TRY(check_s_range(what, r, S));
+  if (B == 0) return FTR_OK;
+  FTR_TRY(pointers_then_device(what, logits && ranges && lse_tok && lse_dur && px_band && py_band && (symbols || S == 0)));
+  return tdt_band_fwd(logits, symbols, ranges, boundary, termination_symbol, durations, N, sigma, delay_penalty, lse_tok, lse_dur,
+                      px_band, py_band, B, T, S, C, r, stream_of(stream));
+}
+
+int ftr_tdt_pruned_band_bwd_scaled_f32(const float* logits, const int32_t* symbols, const int32_t* ranges,
+                                       const int32_t* boundary, int termination_symbol, const int32_t* durations, int N,
+                                       double sigma, double delay_penalty, const float* lse_tok, const float* lse_dur,
+                                       const float* gx_band, const float* gy_band, const float* scale, int scale_stride,
+                                       float scale_mul, float* glogits, int B, int T, int S, int C, int r, void* stream) {
+  const char* what = "tdt_pruned_band_bwd_scaled";
+  clear_error();
+  (void)delay_penalty;   // a constant added to px: no gradient
+  FTR_TRY(tdt_check_head(what, durations, N, sigma, termination_symbol, C));
+  FTR_TRY(check_sizes(what, B >= 0 && T >= 1 && S >= 0 && r >= 1));
+  FTR_TRY(check_scale_stride(what, scale_stride));
+  if (B == 0) return FTR_OK;
+  FTR_TRY(pointers_then_device(what, logits && ranges && lse_tok && lse_dur && gx_band && gy_band && glogits && (symbols || S == 0)));
+  return tdt_band_bwd(logits, symbols, ranges, boundary, termination_symbol, durations, N, lse_tok, lse_dur, gx_band, gy_band,
+                      Scale{scale, scale_stride, scale_mul}, glogits, B, T, S, C, r, stream_of(stream));
+}
+
 // ---- include/ftr_kd.h: knowledge distillation on the pruned band (csrc/pruned_kd.hip)
 // element type codes, mode and temperature, before everything else
 static int kd_check_head(const char* what, int kind, int teacher_kind, int mode, float temperature) {

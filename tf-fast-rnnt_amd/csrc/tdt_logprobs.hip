@@ -11,6 +11,10 @@
 //                          g_tok[c] = -softmax_tok[c] (GX + GY) + 1[c == sym] GX + 1[c == blank] GY
 //                          g_dur[n] = -softmax_dur[n] (GX + GY) + gx_n + gy_j(n)        (no gy term for duration 0)
 // Kernels of their own, in the manner of the mb_* kernels of pruned_logprobs.hip, whose instantiations stay as they are.
+// The band-shaped twins (include/ftr_band_tdt.h; the operands and occupancies of mi_band_tdt.hip, [B,N|Ny,T,r]):
+//   tdt_to_band_kernel     px_band / py_band: the values tdt_to_lattice_kernel puts at lattice cell (ranges[b,t,0] + k, t),
+//                          by the same arithmetic, one thread per band row and no lattice write
+//   tdt_grad_kernel<.,true> the same gradient kernel reading gx_band / gy_band at the row itself
 #include "ftr_common.h"
 #include "launch.h"
 
@@ -113,7 +117,45 @@ __global__ void tdt_to_lattice_kernel(const float* __restrict__ logits, const in
   }
 }
 
-template <bool VEC>
+// one thread per band row (b,t,k) <-> lattice cell (s,t), s = (ranges[b,t,0] + k) mod (S+1) as the lattice kernel's roll
+__global__ void tdt_to_band_kernel(const float* __restrict__ logits, const int32_t* __restrict__ symbols,
+                                   const int32_t* __restrict__ ranges, const int32_t* __restrict__ boundary,
+                                   const float* __restrict__ lse_tok, const float* __restrict__ lse_dur, int blank,
+                                   const TdtCols tc, float sigma, double delay_penalty, float* __restrict__ pxb,
+                                   float* __restrict__ pyb, size_t rows, int T, int S, int C, int r) {
+  const size_t row = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (row >= rows) return;
+  const size_t bt = row / r;
+  const int k = (int)(row - bt * r);
+  const int b = (int)(bt / T);
+  const int t = (int)(bt - (size_t)b * T);
+  int s = ranges[bt * r] + k;
+  if (s > S) s -= S + 1;
+  const bool sok = s >= 0 && s <= S;
+  const int te = boundary ? boundary[4 * b + 3] : T;
+  const int W = C + tc.N, Ny = tc.N - tc.first;
+  const float* x = logits + row * W;
+  const float l = lse_tok[row] + sigma, ld = lse_dur[row];
+  const float toky = x[blank] - l;
+  float tokx = -INFINITY;
+  if (sok && s < S) tokx = x[min(max(symbols[(size_t)b * S + s], 0), C - 1)] - l;
+  double pen = 0.0;
+  if (delay_penalty > 0.0) pen = (((double)te - 1.0) / 2.0 - (double)t) * delay_penalty;
+#pragma unroll
+  for (int n = 0; n < TDT_MAXN; ++n) {
+    if (n < tc.N) {
+      const float dur = x[C + n] - ld;
+      const size_t at = (((size_t)b * tc.N + n) * T + t) * r + k;
+      float vx = (sok && s < S && t != te && t + tc.e[n] <= te) ? tokx + dur : -INFINITY;
+      if (delay_penalty > 0.0) vx += (float)pen;
+      pxb[at] = vx;
+      const int jj = n - tc.first;
+      if (jj >= 0) pyb[(((size_t)b * Ny + jj) * T + t) * r + k] = (sok && t + tc.e[n] <= te) ? toky + dur : -INFINITY;
+    }
+  }
+}
+
+template <bool VEC, bool BAND>
 __global__ void tdt_grad_kernel(const float* __restrict__ logits, const int32_t* __restrict__ symbols,
                                 const int32_t* __restrict__ ranges, const int32_t* __restrict__ boundary,
                                 const float* __restrict__ lse_tok, const float* __restrict__ lse_dur,
@@ -142,8 +184,13 @@ __global__ void tdt_grad_kernel(const float* __restrict__ logits, const int32_t*
   for (int n = 0; n < TDT_MAXN; ++n) {
     float gx = 0.0f, gy = 0.0f;
     if (n < tc.N && sok && t + tc.e[n] <= te) {     // the cells that are -inf whatever the row holds get no gradient
-      if (s < S && t != te) gx = gpx[(((size_t)b * tc.N + n) * S + s) * T1 + t] * sc;
-      if (n >= tc.first) gy = gpy[(((size_t)b * Ny + (n - tc.first)) * (S + 1) + s) * T + t] * sc;
+      if (BAND) {                                   // gpx / gpy are [B,N,T,r] / [B,Ny,T,r]: the row's own element of each plane
+        if (s < S && t != te) gx = gpx[(((size_t)b * tc.N + n) * T + t) * r + k] * sc;
+        if (n >= tc.first) gy = gpy[(((size_t)b * Ny + (n - tc.first)) * T + t) * r + k] * sc;
+      } else {
+        if (s < S && t != te) gx = gpx[(((size_t)b * tc.N + n) * S + s) * T1 + t] * sc;
+        if (n >= tc.first) gy = gpy[(((size_t)b * Ny + (n - tc.first)) * (S + 1) + s) * T + t] * sc;
+      }
     }
     gd[n] = gx + gy;
     GX += gx;
@@ -220,10 +267,44 @@ int tdt_logprobs_bwd(const float* logits, const int32_t* symbols, const int32_t*
   const unsigned blocks = (unsigned)((rows + wpb - 1) / wpb);
   const TdtCols tc = tdt_cols(durations, N);
   dispatch(((C + N) & 3) == 0, [&](auto vec) {
-    hipLaunchKernelGGL((tdt_grad_kernel<decltype(vec)::value>), dim3(blocks), dim3(64 * wpb), 0, st, logits, symbols, ranges, boundary,
+    hipLaunchKernelGGL((tdt_grad_kernel<decltype(vec)::value, false>), dim3(blocks), dim3(64 * wpb), 0, st, logits, symbols, ranges, boundary,
                        lse_tok, lse_dur, gpx, gpy, scale, blank, tc, glogits, rows, T, S, C, r);
   });
   return check_launch("tdt_grad");
+}
+
+int tdt_band_fwd(const float* logits, const int32_t* symbols, const int32_t* ranges, const int32_t* boundary, int blank,
+                 const int32_t* durations, int N, double sigma, double delay_penalty, float* lse_tok, float* lse_dur,
+                 float* pxb, float* pyb, int B, int T, int S, int C, int r, hipStream_t st) {
+  const size_t rows = (size_t)B * T * r;
+  if (rows == 0) return FTR_OK;
+  { const int rc32 = require_rows_32bit("tdt_pruned_band_fwd", rows); if (rc32 != FTR_OK) return rc32; }
+  const int wpb = 4;
+  const unsigned blocks = (unsigned)((rows + wpb - 1) / wpb);
+  dispatch(((C + N) & 3) == 0, [&](auto vec) {
+    hipLaunchKernelGGL((tdt_lse_kernel<decltype(vec)::value>), dim3(blocks), dim3(64 * wpb), 0, st, logits, lse_tok, lse_dur, rows, C, N);
+  });
+  int rc = check_launch("tdt_lse");
+  if (rc != FTR_OK) return rc;
+  hipLaunchKernelGGL(tdt_to_band_kernel, dim3((unsigned)((rows + 255) / 256)), dim3(256), 0, st, logits, symbols, ranges, boundary,
+                     lse_tok, lse_dur, blank, tdt_cols(durations, N), (float)sigma, delay_penalty, pxb, pyb, rows, T, S, C, r);
+  return check_launch("tdt_to_band");
+}
+
+int tdt_band_bwd(const float* logits, const int32_t* symbols, const int32_t* ranges, const int32_t* boundary, int blank,
+                 const int32_t* durations, int N, const float* lse_tok, const float* lse_dur, const float* gxb,
+                 const float* gyb, Scale scale, float* glogits, int B, int T, int S, int C, int r, hipStream_t st) {
+  const size_t rows = (size_t)B * T * r;
+  if (rows == 0) return FTR_OK;
+  { const int rc32 = require_rows_32bit("tdt_pruned_band_bwd", rows); if (rc32 != FTR_OK) return rc32; }
+  const int wpb = 4;
+  const unsigned blocks = (unsigned)((rows + wpb - 1) / wpb);
+  const TdtCols tc = tdt_cols(durations, N);
+  dispatch(((C + N) & 3) == 0, [&](auto vec) {
+    hipLaunchKernelGGL((tdt_grad_kernel<decltype(vec)::value, true>), dim3(blocks), dim3(64 * wpb), 0, st, logits, symbols, ranges, boundary,
+                       lse_tok, lse_dur, gxb, gyb, scale, blank, tc, glogits, rows, T, S, C, r);
+  });
+  return check_launch("tdt_band_grad");
 }
 
 }  // namespace ftr

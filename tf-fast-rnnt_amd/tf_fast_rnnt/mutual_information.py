@@ -390,6 +390,107 @@ def mutual_information_recursion_tdt(
     return (ans, (px_grad, py_grad)) if calc_gradients else ans
 
 
+def band_tdt_supported(T: int, S: int, r: int, N: int, Ny: int) -> bool:
+    """Does the band-native TDT recursion (csrc/mi_band_tdt.hip) cover these sizes?"""
+    return _lib.lib().ftr_mutual_information_band_tdt_supported(int(T), int(S), int(r), int(N), int(Ny)) != 0
+
+
+def band_tdt_forward_backward(px_band: torch.Tensor, py_band: torch.Tensor, ranges: torch.Tensor, S: int, token_durations,
+                              blank_durations, boundary: Optional[torch.Tensor], need_grads: bool):
+    """The TDT recursion on band-shaped operands, raw tensors (no autograd): one chain launch for both directions and
+    one occupancy launch on torch's current stream.  Returns (ans, gx_band|None, gy_band|None); the occupancies are
+    seeded with ones.  ``ranges`` must be a band (the caller's business: _is_band of rnnt_loss.py)."""
+    import ctypes
+    tok, blk = _check_tdt_moves(token_durations, blank_durations, 16)
+    N, Ny = len(tok), len(blk)
+    B, _, T, r = px_band.shape
+    tok_arr = (ctypes.c_int32 * N)(*tok)        # read by the launch itself: no device copy, no host synchronisation
+    blk_arr = (ctypes.c_int32 * Ny)(*blk)
+    L = _lib.lib()
+    with torch.cuda.device(px_band.device):
+        st = _stream_ptr(px_band)
+        nws = L.ftr_mutual_information_band_tdt_workspace_floats(B, T, int(S), r, N, Ny)
+        ws = torch.empty((max(nws, 2) + 1) // 2, dtype=torch.float64, device=px_band.device)
+        ans = torch.empty((B,), dtype=torch.float32, device=px_band.device)
+        gx = torch.empty_like(px_band) if need_grads else None
+        gy = torch.empty_like(py_band) if need_grads else None
+        _lib.call("ftr_mutual_information_band_tdt_f32", _ptr(px_band), _ptr(py_band), _ptr(ranges), _ptr(boundary), tok_arr, N,
+                  blk_arr, Ny, _ptr(ws), nws, _ptr(ans), _ptr(gx), _ptr(gy), B, T, int(S), r, st)
+        _lib.band_tdt_recursions += 1
+    return ans, gx, gy
+
+
+class _BandTdtRecursion(torch.autograd.Function):
+    """mutual_information_recursion_tdt_band: the occupancies are computed with the answer whenever an operand needs a
+    gradient, and backward() scales them by the upstream gradient."""
+
+    @staticmethod
+    def forward(ctx, px_band, py_band, ranges, S, tok, blk, boundary):
+        need = px_band.requires_grad or py_band.requires_grad
+        ans, gx, gy = band_tdt_forward_backward(px_band.detach().contiguous(), py_band.detach().contiguous(), ranges, S, tok,
+                                                blk, boundary, need)
+        if need:
+            ctx.save_for_backward(gx, gy)
+        return ans
+
+    @staticmethod
+    def backward(ctx, g_ans):
+        gx, gy = ctx.saved_tensors
+        g = g_ans.reshape(-1, 1, 1, 1).to(gx.dtype)
+        return gx * g, gy * g, None, None, None, None, None
+
+
+def mutual_information_recursion_tdt_band(
+    px_band: torch.Tensor,
+    py_band: torch.Tensor,
+    ranges: torch.Tensor,
+    durations,
+    blank_durations,
+    boundary: Optional[torch.Tensor] = None,
+    S: Optional[int] = None,
+) -> torch.Tensor:
+    """``mutual_information_recursion_tdt`` on the pruned band itself (MI355X addition; csrc/mi_band_tdt.hip): nothing of
+    size S*T is allocated or touched.
+
+    px_band: [B,N,T,r] and py_band: [B,Ny,T,r], float32; element (b,i,t,k) is the log-probability of move i out of
+    lattice cell (ranges[b,t,0] + k, t), i.e. what ``get_rnnt_logprobs_tdt_pruned`` puts at ``px[b,i,s,t]`` /
+    ``py[b,j,s,t]`` (its -inf rules included).  ranges: int32 [B,T,r], a band as ``get_rnnt_prune_ranges`` returns it
+    (``ranges[b,t,k] = ranges[b,t,0] + k``, non-decreasing over t), r <= 15.  S: the number of symbols (the lattice has
+    rows 0..S); when omitted it is taken to be ``ranges.max()``, the last band row, at the price of one host read.
+    durations: the N token durations,
+    strictly increasing ints in 0..16, N <= 5; blank_durations: the Ny blank durations in 1..16, Ny <= 5.
+
+    A move exists iff its source is a band cell inside the boundary rectangle and its destination is one, or the end
+    cell ``(s_end, t_end)``; the frames it skips need not be in the band.  Returns ``ans`` [B] (-inf without a path;
+    NaN for a band whose start decreases), equal to ``mutual_information_recursion_tdt`` on the band scattered into
+    full-size lattices of -inf.  Differentiable w.r.t. px_band and py_band (the occupancies times the upstream
+    gradient); asynchronous, no host read when ``S`` is given (capturable)."""
+    _require_gpu(px_band, "px_band"); _require_gpu(py_band, "py_band")
+    if px_band.dtype != torch.float32 or py_band.dtype != torch.float32:
+        raise TypeError("px_band and py_band must be float32")
+    tok, blk = _check_tdt_moves(durations, blank_durations, 16)
+    if len(tok) > 5 or len(blk) > 5:
+        raise ValueError("the band recursion takes at most 5 token durations and 5 blank durations")
+    if px_band.dim() != 4 or py_band.dim() != 4:
+        raise ValueError("px_band must be [B,N,T,r] and py_band [B,Ny,T,r]")
+    B, _, T, r = px_band.shape
+    if tuple(px_band.shape) != (B, len(tok), T, r) or tuple(py_band.shape) != (B, len(blk), T, r):
+        raise ValueError(f"px_band must have shape {(B, len(tok), T, r)} and py_band {(B, len(blk), T, r)}, got "
+                         f"{tuple(px_band.shape)} and {tuple(py_band.shape)}")
+    ranges = torch.as_tensor(ranges, device=px_band.device).to(torch.int32).contiguous()
+    if tuple(ranges.shape) != (B, T, r):
+        raise ValueError(f"ranges must have shape {(B, T, r)}, got {tuple(ranges.shape)}")
+    boundary = _as_boundary(boundary, B, px_band.device)
+    if S is None:       # the last band row: one host read (give S to stay asynchronous)
+        S = int(ranges.max().item()) if ranges.numel() else 0
+    S = int(S)
+    if S < 0 or T < 1:
+        raise ValueError(f"S={S} must not be negative and T={T} must be positive")
+    if not band_tdt_supported(T, S, r, len(tok), len(blk)):
+        raise ValueError(f"the band recursion does not cover T={T}, S={S}, r={r} (r <= 15)")
+    return _BandTdtRecursion.apply(px_band, py_band, ranges, S, tok, blk, boundary)
+
+
 def mutual_information_viterbi(px: torch.Tensor, py: torch.Tensor,
                                boundary: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor]:
     """Best-path (Viterbi) alignment over the lattice of ``mutual_information_recursion`` (MI355X addition, no reference

@@ -32,9 +32,9 @@ import os
 import torch
 
 from . import _lib
-from .mutual_information import (_as_boundary, _ptr, _require_gpu, _stream_ptr, cummin,
-                                 mb_forward_backward, mi_forward_backward, mutual_information_recursion,
-                                 mutual_information_viterbi, mutual_information_viterbi_tdt, tdt_forward_backward)
+from .mutual_information import (_as_boundary, _ptr, _require_gpu, _stream_ptr, band_tdt_forward_backward,
+                                 band_tdt_supported, cummin, mb_forward_backward, mi_forward_backward,
+                                 mutual_information_recursion, mutual_information_viterbi, mutual_information_viterbi_tdt, tdt_forward_backward)
 
 _NEG_INF = float("-inf")
 # tf.math.nextafter(0., 1.) : smallest positive float32 subnormal (rnnt_loss.py:181,1272,1280)
@@ -1200,15 +1200,31 @@ def _tdt_builder_fwd(x, symbols, ranges, boundary, blank, arr, durs, blank_durs,
     return lse_tok, lse_dur, px, py
 
 
+def _tdt_band_builder_fwd(x, symbols, ranges, boundary, blank, arr, durs, blank_durs, C, sigma, delay_penalty):
+    """_tdt_builder_fwd with band-shaped px_band [B,N,T,r] / py_band [B,Ny,T,r]: no lattice is written."""
+    B, T, r, _ = x.shape
+    S = symbols.shape[1]
+    lse_tok = torch.empty((B, T, r), dtype=torch.float32, device=x.device)
+    lse_dur = torch.empty((B, T, r), dtype=torch.float32, device=x.device)
+    pxb = torch.empty((B, len(durs), T, r), dtype=torch.float32, device=x.device)
+    pyb = torch.empty((B, len(blank_durs), T, r), dtype=torch.float32, device=x.device)
+    with torch.cuda.device(x.device):
+        _lib.call("ftr_tdt_pruned_band_fwd_f32", _ptr(x), _ptr(symbols), _ptr(ranges), _ptr(boundary), blank, arr,
+                  len(durs), float(sigma), float(delay_penalty), _ptr(lse_tok), _ptr(lse_dur), _ptr(pxb), _ptr(pyb), B, T, S, C,
+                  r, _stream_ptr(x))
+    return lse_tok, lse_dur, pxb, pyb
+
+
 def _tdt_builder_bwd(x, symbols, ranges, boundary, blank, arr, N, C, sigma, delay_penalty, lse_tok, lse_dur, gpx, gpy, scale,
-                     stride, mul):
+                     stride, mul, band=False):
+    """``band``: gpx / gpy are band-shaped occupancies [B,N,T,r] / [B,Ny,T,r], else the full-size lattices."""
     B, T, r, _ = x.shape
     S = symbols.shape[1]
     g = torch.empty_like(x)
     with torch.cuda.device(x.device):
-        _lib.call("ftr_tdt_pruned_logprobs_bwd_scaled_f32", _ptr(x), _ptr(symbols), _ptr(ranges), _ptr(boundary), blank, arr,
-                  N, float(sigma), float(delay_penalty), _ptr(lse_tok), _ptr(lse_dur), _ptr(gpx), _ptr(gpy), _ptr(scale),
-                  stride, mul, _ptr(g), B, T, S, C, r, _stream_ptr(x))
+        _lib.call("ftr_tdt_pruned_band_bwd_scaled_f32" if band else "ftr_tdt_pruned_logprobs_bwd_scaled_f32", _ptr(x),
+                  _ptr(symbols), _ptr(ranges), _ptr(boundary), blank, arr, N, float(sigma), float(delay_penalty),
+                  _ptr(lse_tok), _ptr(lse_dur), _ptr(gpx), _ptr(gpy), _ptr(scale), stride, mul, _ptr(g), B, T, S, C, r, _stream_ptr(x))
     return g
 
 
@@ -1234,19 +1250,39 @@ class _TdtLogprobs(torch.autograd.Function):
         return g, None, None, None, None, None, None, None
 
 
+def _tdt_band_path_ok(ranges, boundary, T: int, S: int, r: int, N: int, Ny: int) -> bool:
+    """_band_path_ok for the TDT loss: the same rule and the same FTR_PRUNED_ROUTE knob, the domain of
+    csrc/mi_band_tdt.hip."""
+    if os.environ.get("FTR_PRUNED_ROUTE") == "lattice":
+        return False
+    return band_tdt_supported(T, S, r, N, Ny) and _is_band(ranges, boundary)
+
+
 class _TdtLoss(torch.autograd.Function):
-    """rnnt_loss_tdt_pruned with the whole chain native, as _MultiblankLoss: log-sum-exps + gather -> TDT recursion
-    forward and backward on the full-size lattices -> in backward() one streaming kernel turns the occupancies * upstream
-    gradient into d loss / d logits."""
+    """rnnt_loss_tdt_pruned with the whole chain native, as _PrunedLoss.
+
+    Band path (the ranges are a band, r <= 15): log-sum-exps + band gather -> TDT recursion, both directions and the
+    occupancies, on the band [B,N|Ny,T,r] (ftr_mutual_information_band_tdt_f32; no full-size lattice exists) -> in
+    backward() one streaming kernel turns the band-shaped occupancies * upstream gradient into d loss / d logits.
+    Lattice path (any other ranges, FTR_PRUNED_ROUTE=lattice): log-sum-exps + band->lattice, TDT recursion forward and
+    backward on the full-size lattices, the same streaming kernel fed from the lattices."""
 
     @staticmethod
     def forward(ctx, logits, symbols, ranges, termination_symbol, durations, boundary, sigma, delay_penalty, code):
         x = logits.detach().contiguous()
         need = logits.requires_grad
         arr, durs, blank_durs, C = _tdt_args(durations, termination_symbol, x.shape[3])
-        lse_tok, lse_dur, px, py = _tdt_builder_fwd(x, symbols, ranges, boundary, int(termination_symbol), arr, durs,
-                                                    blank_durs, C, sigma, delay_penalty)
-        ans, px_grad, py_grad = tdt_forward_backward(px, py, durs, blank_durs, boundary, need)
+        B, T, r, _ = x.shape
+        S = symbols.shape[1]
+        ctx.band = _tdt_band_path_ok(ranges, boundary, T, S, r, len(durs), len(blank_durs))
+        if ctx.band:
+            lse_tok, lse_dur, px, py = _tdt_band_builder_fwd(x, symbols, ranges, boundary, int(termination_symbol), arr, durs,
+                                                             blank_durs, C, sigma, delay_penalty)
+            ans, px_grad, py_grad = band_tdt_forward_backward(px, py, ranges, S, durs, blank_durs, boundary, need)
+        else:
+            lse_tok, lse_dur, px, py = _tdt_builder_fwd(x, symbols, ranges, boundary, int(termination_symbol), arr, durs,
+                                                        blank_durs, C, sigma, delay_penalty)
+            ans, px_grad, py_grad = tdt_forward_backward(px, py, durs, blank_durs, boundary, need)
         del px, py
         if need:
             ctx.save_for_backward(x, symbols, ranges, lse_tok, lse_dur, px_grad, py_grad, boundary)
@@ -1259,7 +1295,7 @@ class _TdtLoss(torch.autograd.Function):
         blank, arr, N, C, sigma, delay_penalty, code = ctx.meta
         scale, stride, mul = _upstream_scale(g_loss, code, x.shape[0])
         g = _tdt_builder_bwd(x, symbols, ranges, boundary, blank, arr, N, C, sigma, delay_penalty, lse_tok, lse_dur, px_grad,
-                             py_grad, scale, stride, mul)
+                             py_grad, scale, stride, mul, ctx.band)
         return g, None, None, None, None, None, None, None, None
 
 
@@ -1324,6 +1360,8 @@ def rnnt_loss_tdt_pruned(
     """TDT loss on pruned joiner logits [B,T,s_range,C+N] (MI355X addition): the lattices of
     ``get_rnnt_logprobs_tdt_pruned`` through ``mutual_information_recursion_tdt``, negated and reduced.  Only
     ``rnnt_type="regular"`` exists; anything else raises ValueError, as does a bad ``durations`` or a negative ``sigma``.
+    When ``ranges`` are a band with ``s_range <= 15`` (the rule of ``rnnt_loss_pruned``, ``FTR_PRUNED_ROUTE=lattice``
+    overrides it) the same loss is computed on the band itself and no full-size lattice is allocated.
 
     Prune ranges come from the ordinary ``rnnt_loss_simple``.  They guarantee a path through the band only when
     ``durations`` contains 0 and 1 (the moves of the lattice they were computed on): with other sets a path may have to
