@@ -560,7 +560,7 @@ int ftr_multiblank_pruned_logprobs_bwd_scaled_f32(const float* logits, const int
  *     where t + d_j > t_end and outside the band.
  *   A symbol equal to termination_symbol is gathered as ftr_pruned_logprobs_fwd_f32 gathers it.
  * Recursion (csrc/mi_tdt.hip), with the two lists given separately -- token_durations: Dx >= 1 strictly increasing
- *   values in 0..16; blank_durations: Dy >= 1 strictly increasing values in 1..16; Dx + Dy <= 9; px [B,Dx,S,T+1],
+ *   values in 0..16; blank_durations: Dy >= 1 strictly increasing values in 1..16; Dx + Dy <= 10; px [B,Dx,S,T+1],
  *   py [B,Dy,S+1,T]:
  *   p[s_begin,t_begin] = 0
  *   p[s,t] = logadd( (+)_i p[s-1,t-e_i] + px[i,s-1,t-e_i],  (+)_j p[s,t-d_j] + py[j,s,t-d_j] ),  ans = p[s_end,t_end]
@@ -577,7 +577,7 @@ int ftr_multiblank_pruned_logprobs_bwd_scaled_f32(const float* logits, const int
  *   times the per-utterance scale as in ftr_pruned_logprobs_bwd_scaled_f32), GX = sum_i gx_i, GY = sum_j gy_j:
  *   g_tok[c] = -softmax_tok[c] (GX + GY) + 1[c == sym] GX + 1[c == termination_symbol] GY
  *   g_dur[n] = -softmax_dur[n] (GX + GY) + gx_n + gy_j(n)        (no gy term for duration 0)
- * Invalid, unsorted or out-of-range lists, Dx + Dy > 9 or sigma < 0 return FTR_ERR_INVALID_ARG (before any device
+ * Invalid, unsorted or out-of-range lists, Dx + Dy > 10 or sigma < 0 return FTR_ERR_INVALID_ARG (before any device
  * check) with a message naming the argument.
  */
 size_t ftr_mutual_information_tdt_workspace_floats(int B, int S, int T);

@@ -19,6 +19,7 @@ import numpy as np
 import pytest
 import torch
 
+from band_tdt_cases import _band_around, _gather, _random_path, _scatter
 from helpers import max_rel
 from tdt_restatement import blank_durations_of, tdt_dp_with_grads, tdt_loss
 from test_gpu_graph import _capture
@@ -44,53 +45,6 @@ def _n(t):
 
 
 # ------------------------------------------------------------------------------------------------- bands and operands
-def _random_path(rng, Sn, Tn, tok, blk, r):
-    """A random path (0,0) -> (Sn-1,Tn-1) of the rectangle as [(s, t, move)] that climbs at most r - 1 rows inside one
-    frame (the rows it visits at a frame must fit one band of r rows); None when there is none."""
-    # reach[s,t,c]: the end can be reached from (s,t) after c climbs inside frame t
-    reach = np.zeros((Sn + 1, Tn + 17, r + 1), bool)
-    reach[Sn - 1, Tn - 1, :r] = True
-    zero = 0 in tok
-    for t in range(Tn - 2, -1, -1):             # sources are frames before the last column
-        for s in range(Sn - 1, -1, -1):
-            on = any(reach[s + 1, t + e, 0] for e in tok if e > 0) or any(reach[s, t + d, 0] for d in blk)
-            for c in range(r - 1, -1, -1):
-                reach[s, t, c] = on or (zero and c < r - 1 and reach[s + 1, t, c + 1])
-    if not reach[0, 0, 0]:
-        return None
-    moves = [(1, e) for e in tok] + [(0, d) for d in blk]
-    s, t, c, path = 0, 0, 0, []
-    while (s, t) != (Sn - 1, Tn - 1):
-        ok = [m for m, (ds, d) in enumerate(moves) if reach[s + ds, t + d, c + 1 if (ds == 1 and d == 0) else 0]
-              and not (ds == 1 and d == 0 and c >= r - 1)]
-        m = ok[rng.integers(len(ok))]
-        path.append((s, t, m))
-        ds, d = moves[m]
-        c = c + 1 if (ds == 1 and d == 0) else 0
-        s, t = s + ds, t + d
-    return path
-
-
-def _band_around(rng, path, sb, tb, te, S, T, r):
-    """lo[t], non-decreasing, 0 <= lo <= S + 1 - r, holding every source cell of the path; flat wherever it may be."""
-    lo_min = np.zeros(T, np.int64)               # frame t: lo >= (highest row visited) - r + 1
-    lo_max = np.full(T, S + 1 - r, np.int64)     #          lo <= lowest row visited
-    for s, t, _ in path:
-        lo_min[tb + t] = max(lo_min[tb + t], sb + s - r + 1)
-        lo_max[tb + t] = min(lo_max[tb + t], sb + s)
-    for t in range(T - 2, -1, -1):               # a later frame's ceiling holds for the earlier ones (monotone)
-        lo_max[t] = min(lo_max[t], lo_max[t + 1])
-    lo = np.zeros(T, np.int64)
-    prev = 0
-    for t in range(T):
-        lb, ub = max(prev, lo_min[t]), lo_max[t]
-        assert lb <= ub
-        if rng.random() < 0.25 and tb <= t < te:       # now and then a step the path does not ask for: 1..r rows, r itself
-            lb = min(ub, lb + (r if rng.random() < 0.3 else rng.integers(1, r + 1)))      # among them
-        lo[t] = prev = lb
-    return lo
-
-
 @functools.lru_cache(maxsize=None)
 def _recursion_case(shape, moves, with_boundary):
     B, S, T, r = shape
@@ -136,32 +90,6 @@ def _recursion_case(shape, moves, with_boundary):
     py = _scatter(pyb, ranges, S, S + 1, T)
     w_ans, w_gx, w_gy = tdt_dp_with_grads(px, py, tok, blk, bdi)
     return pxb, pyb, ranges.astype(np.int32), bdi, has_path, (w_ans, _gather(w_gx, ranges), _gather(w_gy, ranges))
-
-
-def _scatter(band, ranges, S, rows, cols):
-    """band [B,P,T,r] -> lattice [B,P,rows,cols], -inf outside the band (band rows beyond the lattice are dropped)"""
-    B, P, T, r = band.shape
-    out = np.full((B, P, rows, cols), NEG, band.dtype)
-    for b in range(B):
-        for t in range(T):
-            for k in range(r):
-                s = int(ranges[b, t, k])
-                if 0 <= s < rows:
-                    out[b, :, s, t] = band[b, :, t, k]
-    return out
-
-
-def _gather(lat, ranges):
-    """lattice [B,P,rows,cols] -> band [B,P,T,r], 0 for band rows beyond the lattice"""
-    B, T, r = ranges.shape
-    out = np.zeros((B, lat.shape[1], T, r), lat.dtype)
-    for b in range(B):
-        for t in range(T):
-            for k in range(r):
-                s = int(ranges[b, t, k])
-                if 0 <= s < lat.shape[2] and t < lat.shape[3]:
-                    out[b, :, t, k] = lat[b, :, s, t]
-    return out
 
 
 def _run_recursion(ft, dev, pxb, pyb, ranges, tok, blk, bd, S, weights=None):
@@ -265,15 +193,27 @@ def test_both_routes_match_the_restatement(ft, dev, monkeypatch, shape, durs):
 # ------------------------------------------------------------------------------------------------------------ builders
 @pytest.mark.parametrize("CN", [(5, 3), (6, 5), (507, 5), (510, 2)], ids=str)      # C + N = 8, 11, 512, 512; C % 4 != 0 in all
 def test_band_builders_are_bit_identical_to_the_lattice_ones(ft, dev, CN):
+    _builders_are_bit_identical(ft, dev, CN, 5)
+
+
+@pytest.mark.parametrize("CN", [(5, 3), (6, 5), (507, 5), (510, 2)], ids=str)
+@pytest.mark.parametrize("r", [1, 2, 7, 8, 15])                  # one band row, two, and the widest bands of 8 and 16 lanes
+def test_band_builders_are_bit_identical_at_every_band_width(ft, dev, CN, r):
+    """The same at the other band widths (r = 5 keeps its name above)."""
+    _builders_are_bit_identical(ft, dev, CN, r)
+
+
+def _builders_are_bit_identical(ft, dev, CN, r):
     """px_band / py_band are the lattice builder's values at the band cells; d logits of the band gradient kernel fed the
     occupancies gathered at the band cells is that of the lattice kernel fed the same occupancies scattered (zero
-    elsewhere), per-utterance scale included."""
+    elsewhere), per-utterance scale included.  S = 9 as long as the band start has two rows to move over, r + 1 above."""
     import ctypes
     C, N = CN
     durs = {2: (0, 1), 3: (1, 2, 4), 5: (0, 1, 2, 3, 4)}[N]
     Ny = len(blank_durations_of(durs))
-    B, T, S, r, blank = 2, 24, 9, 5, 1
-    rng = np.random.default_rng(C + N)
+    B, T, S, blank = 2, 24, max(9, r + 1), 1
+    assert S + 1 - r >= 2
+    rng = np.random.default_rng(C + N if r == 5 else [C, N, r])
     logits = _t((rng.standard_normal((B, T, r, C + N)) * 2).astype(np.float32), dev)
     sym_np = rng.integers(0, C, (B, S)).astype(np.int32)
     sym_np[1, 0] = blank

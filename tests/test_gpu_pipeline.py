@@ -657,6 +657,82 @@ def test_pruned_loss_routes_by_the_data_not_by_a_mark(ft, dev, monkeypatch):
         assert np.array_equal(got, ref, equal_nan=True)
 
 
+def test_band_verdict_does_not_outlive_its_boundary(ft, dev, monkeypatch):
+    """The verdict "these ranges are a band" is earned inside the rectangles of ONE boundary (ftr_band_ranges_check_i32 looks
+    at frames [t_begin, t_end) only), and a padded batch may well step backwards in its padding frames.  The same ranges
+    tensor under a wider boundary, or under none, must be looked at again: the decrease is then inside the rectangle, where
+    the band kernels answer NaN and the lattice route, which the documentation promises for ranges that are not a band, a
+    finite loss.  Utterance 1 (s_end = S, t_end = 70 of T = 90 frames) gets frame 75 set one row below frame 74: with
+    t_end = T its path may still emit its last symbol after frame 75, so the loss stays finite."""
+    from tf_fast_rnnt import _lib
+    B, T, S, C, r = 3, 90, 33, 12, 5
+    d = synthetic(322, B, T, S, C)
+    blank = d["termination_symbol"]
+    bd_np = np.array([[0, 0, S, T], [0, 0, S, 70], [0, 0, 28, 60]], np.int32)
+    am, lm, sym, bd = (_t(a, dev) for a in (d["am"], d["lm"], d["symbols"], bd_np))
+    _, (gx, gy) = ft.rnnt_loss_simple(lm, am, sym, blank, bd, reduction="sum", calc_gradients=True)
+    ranges = ft.get_rnnt_prune_ranges(gx, gy, bd, r)
+    am_p, lm_p = ft.do_rnnt_pruning(am, lm, ranges)
+    logits = torch.tanh(am_p + lm_p).detach()
+    wide_np = bd_np.copy(); wide_np[1, 3] = T
+    wide = _t(wide_np, dev)
+    calls = []
+    real_call = _lib.call
+    monkeypatch.setattr(_lib, "call", lambda name, *a: (calls.append(name), real_call(name, *a))[1])
+
+    def lattice_route(fn, rg, boundary):
+        monkeypatch.setenv("FTR_PRUNED_ROUTE", "lattice")
+        out = fn(rg.clone(), boundary)
+        monkeypatch.delenv("FTR_PRUNED_ROUTE")
+        return out
+
+    def edited():
+        c = ranges.clone()
+        assert int(c[1, 74, 0]) >= 1
+        c[1, 75] = c[1, 74] - 1                       # a padding frame of the ragged boundary, inside the wide one
+        return c
+
+    # rnnt_loss_pruned
+    loss = lambda rg, boundary: ft.rnnt_loss_pruned(logits, sym, rg, blank, boundary, reduction="none").cpu().numpy()
+    want = loss(ranges, bd)
+    for other in (wide, None):
+        c = edited()
+        calls.clear()
+        got = loss(c, bd)
+        assert "ftr_mutual_information_band_ws_f32" in calls and "ftr_pruned_logprobs_fwd_f32" not in calls
+        assert np.array_equal(got, want) and np.isfinite(got).all()
+        calls.clear()
+        assert np.array_equal(loss(c, bd), want)
+        assert "ftr_band_ranges_check_i32" not in calls and "ftr_mutual_information_band_ws_f32" in calls     # remembered
+        calls.clear()
+        got = loss(c, other)                          # the same tensor, a boundary that the verdict does not cover
+        assert "ftr_mutual_information_band_ws_f32" not in calls and "ftr_pruned_logprobs_fwd_f32" in calls
+        ref = lattice_route(loss, c, other)
+        assert np.array_equal(got, ref) and not np.isnan(got).any()
+        assert np.isfinite(got[:2]).all() and (other is None or np.isfinite(got).all())      # utterance 2's band ends on row 28 < S
+        calls.clear()
+        assert np.array_equal(loss(c, bd), want)      # and back: under its own boundary it is a band as before
+        assert "ftr_mutual_information_band_ws_f32" in calls
+
+    # rnnt_loss_tdt_pruned, durations (0, 1)
+    durs = (0, 1)
+    tdt_logits = torch.randn((B, T, r, C + len(durs)), generator=torch.Generator().manual_seed(5)).to(dev)
+    tdt = lambda rg, boundary: ft.rnnt_loss_tdt_pruned(tdt_logits, sym, rg, blank, durs, boundary, reduction="none").cpu().numpy()
+    before = _lib.band_tdt_recursions
+    want = tdt(ranges, bd)
+    assert _lib.band_tdt_recursions == before + 1 and np.isfinite(want).all()
+    for other in (wide, None):
+        c = edited()
+        before = _lib.band_tdt_recursions
+        got = tdt(c, bd)
+        assert _lib.band_tdt_recursions == before + 1 and np.array_equal(got, want)
+        got = tdt(c, other)
+        assert _lib.band_tdt_recursions == before + 1, "a band verdict outlived the boundary it was earned under"
+        ref = lattice_route(tdt, c, other)
+        assert np.array_equal(got, ref) and not np.isnan(got).any()
+        assert np.isfinite(got[:2]).all() and (other is None or np.isfinite(got).all())
+
+
 def test_out_of_range_caller_data_does_not_fault(ft, dev):
     """Malformed boundary rows, symbols and ranges (caller data the reference never validates) must not send a kernel
     out of bounds: boundaries are clamped into the lattice, symbols into the vocabulary, gather rows into lm; rows of

@@ -65,9 +65,10 @@ def test_tdt_recursion_argument_validation_without_device(ft, name):
         assert _recursion(L, name, (0,), blk) == 0 and b"blank_durations" in err(), (blk, err())
     assert _recursion(L, name, (0,), (1,), Dx=-1) == 0 and b"token_durations" in err()
     assert _recursion(L, name, (0,), (1,), Dy=0) == 0 and b"blank_durations" in err()
-    assert _recursion(L, name, (0, 1, 2, 3, 4), (1, 2, 3, 4, 5)) == 0 and b"Dx + Dy" in err()       # 10 moves
-    # valid descriptions (9 moves among them) get as far as the size / pointer checks
-    for tok, blk in (((0, 1, 2, 3, 4), (1, 2, 3, 4)), ((0,), (1, 2, 3, 4, 5, 6, 7, 8)), ((0, 16), (3, 16)), ((1, 2), (1,))):
+    assert _recursion(L, name, (0, 1, 2, 3, 4, 5), (1, 2, 3, 4, 5)) == 0 and b"Dx + Dy" in err()    # 11 moves
+    # valid descriptions (9 moves and 10, five of each kind, among them) get as far as the size / pointer checks
+    for tok, blk in (((0, 1, 2, 3, 4), (1, 2, 3, 4)), ((0, 1, 2, 3, 4), (1, 2, 3, 4, 5)), ((1, 2, 3, 4, 8), (1, 2, 3, 4, 8)),
+                     ((0,), (1, 2, 3, 4, 5, 6, 7, 8)), ((0, 16), (3, 16)), ((1, 2), (1,))):
         assert _recursion(L, name, tok, blk) == 0
         assert b"durations" not in err() and (b"workspace" in err() or b"null" in err()), err()
 

@@ -884,10 +884,11 @@ int tdt_check_list(const char* what, const char* name, const int32_t* v, int n, 
   return FTR_OK;
 }
 int tdt_check_moves(const char* what, const int32_t* token_durations, int Dx, const int32_t* blank_durations, int Dy,
-                    int blank_hi = 16) {
+                    int blank_hi = 16, int max_moves = 9) {
   FTR_TRY(tdt_check_list(what, "token_durations", token_durations, Dx, 8, 0));
   FTR_TRY(tdt_check_list(what, "blank_durations", blank_durations, Dy, 8, 1, blank_hi));
-  FTR_REQUIRE(Dx + Dy <= 9, "%s: Dx + Dy = %d moves (token_durations and blank_durations together), at most 9", what, Dx + Dy);
+  FTR_REQUIRE(Dx + Dy <= max_moves, "%s: Dx + Dy = %d moves (token_durations and blank_durations together), at most %d", what,
+              Dx + Dy, max_moves);
   return FTR_OK;
 }
 int tdt_check_head(const char* what, const int32_t* durations, int N, double sigma, int blank, int C) {
@@ -978,7 +979,7 @@ int ftr_mutual_information_tdt_fwd_f32(const float* px, const float* py, const i
                                        void* stream) {
   const char* what = "mutual_information_tdt_fwd";
   clear_error();
-  FTR_TRY(tdt_check_moves(what, token_durations, Dx, blank_durations, Dy));
+  FTR_TRY(tdt_check_moves(what, token_durations, Dx, blank_durations, Dy, 16, 10));   // MAXM of mi_rowlane.h
   FTR_TRY(check_lattice(what, B, S, T));
   if (B == 0) return FTR_OK;
   FTR_TRY(check_ws_size(what, workspace_floats, mi_tdt_workspace_floats(B, S, T), "floats"));
@@ -995,7 +996,7 @@ int ftr_mutual_information_tdt_bwd_f32(const float* px, const float* py, const i
                                        float* py_grad, int B, int S, int T, void* stream) {
   const char* what = "mutual_information_tdt_bwd";
   clear_error();
-  FTR_TRY(tdt_check_moves(what, token_durations, Dx, blank_durations, Dy));
+  FTR_TRY(tdt_check_moves(what, token_durations, Dx, blank_durations, Dy, 16, 10));   // MAXM of mi_rowlane.h
   FTR_TRY(check_lattice(what, B, S, T));
   if (B == 0) return FTR_OK;
   FTR_TRY(check_ws_size(what, workspace_floats, mi_tdt_workspace_floats(B, S, T), "floats"));

@@ -38,7 +38,8 @@ namespace rowlane {
 constexpr int CH = 8;                  // steps per chunk
 constexpr int E = 64 + CH - 1;         // skew between consecutive waves
 constexpr int MAXW = 4;                // waves per workgroup
-constexpr int MAXM = 9;                // moves (Dx + Dy)
+constexpr int MAXM = 10;               // moves (Dx + Dy) of the recursion (mi_tdt.hip: five of each kind, as the band's)
+constexpr int MAXM_ALIGN = 9;          // ... and of the alignment (mi_viterbi_tdt.hip)
 constexpr int MAXTOK = 16;             // largest token duration
 constexpr int CW = CH + MAXTOK;        // carry window of a chunk
 

@@ -6,7 +6,7 @@
 //   ans    = p[s_end,t_end]
 //   px_grad[i,s,t] = exp(p[s,t] + px[i,s,t] + q[s+1,t+e_i] - ans)     (occupancy of symbol move i out of (s,t))
 //   py_grad[j,s,t] = exp(p[s,t] + py[j,s,t] + q[s,t+d_j]   - ans)     (occupancy of blank move j out of (s,t))
-// with e_i the Dx token durations (0..16), d_j the Dy blank durations (1..16), Dx + Dy <= 9, a term whose source lies
+// with e_i the Dx token durations (0..16), d_j the Dy blank durations (1..16), Dx + Dy <= 10, a term whose source lies
 // outside the boundary rectangle absent, and q the same recursion run from (s_end,t_end) backwards.  token_durations =
 // (0,) is the multi-blank recursion of mi_multiblank.hip, and this file follows it: one kernel for both directions (the
 // backward pass is the forward pass in mirrored coordinates r = s_end - s, t = t_end - t with the operands read at the

@@ -266,7 +266,7 @@ int mi_viterbi_tdt(const float* px, const float* py, const int32_t* boundary, co
   u64* dec = static_cast<u64*>(ws);
   float* carry = reinterpret_cast<float*>(static_cast<char*>(ws) + L.carry_off);
   const size_t lds = (size_t)QDEP * 64 * NW * sizeof(float);
-  dispatch_range<2, MAXM>(Dx + Dy, [&](auto m) {
+  dispatch_range<2, MAXM_ALIGN>(Dx + Dy, [&](auto m) {
     hipLaunchKernelGGL((mi_viterbi_tdt_kernel<decltype(m)::value>), dim3(B), dim3(64 * NW), lds, st, px, py, boundary, mv,
                        dec, carry, score, frames, durations, blank_steps, S, T, NW);
   }, [] {});   // the entry points admit no other arity

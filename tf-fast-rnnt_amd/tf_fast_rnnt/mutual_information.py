@@ -298,7 +298,9 @@ def mutual_information_recursion_multiblank(
     return (ans, (px_grad, py_grad)) if calc_gradients else ans
 
 
-def _check_tdt_moves(token_durations, blank_durations, blank_hi: int = 16) -> Tuple[Tuple[int, ...], Tuple[int, ...]]:
+def _check_tdt_moves(token_durations, blank_durations, blank_hi: int = 16,
+                     max_moves: int = 10) -> Tuple[Tuple[int, ...], Tuple[int, ...]]:
+    """``max_moves``: 10 for the recursions, lattice (mi_rowlane.h, MAXM) and band; 9 for the alignment (MAXM_ALIGN)."""
     tok = tuple(int(d) for d in token_durations)
     blk = tuple(int(d) for d in blank_durations)
     for name, v, lo, hi in (("token_durations", tok, 0, 16), ("blank_durations", blk, 1, blank_hi)):
@@ -306,19 +308,20 @@ def _check_tdt_moves(token_durations, blank_durations, blank_hi: int = 16) -> Tu
             raise ValueError(f"{name} must hold at least one value")
         if any(d < lo or d > hi for d in v) or any(b <= a for a, b in zip(v, v[1:])):
             raise ValueError(f"{name} must be strictly increasing values in {lo}..{hi}, got {v}")
-    if len(tok) + len(blk) > 9:
-        raise ValueError(f"token_durations and blank_durations hold {len(tok) + len(blk)} moves together, at most 9 are supported")
+    if len(tok) + len(blk) > max_moves:
+        raise ValueError(f"token_durations and blank_durations hold {len(tok) + len(blk)} moves together, at most {max_moves} are supported")
     return tok, blk
 
 
-def _duration_lattice_inputs(px: torch.Tensor, py: torch.Tensor, token_durations, blank_durations, blank_hi: int):
+def _duration_lattice_inputs(px: torch.Tensor, py: torch.Tensor, token_durations, blank_durations, blank_hi: int,
+                             max_moves: int = 10):
     """Validation of the TDT-shaped entries and the host arrays the launches read.  Returns
     (px, py, B, S, T, tok, blk, tok_arr, blk_arr) with px and py contiguous."""
     import ctypes
     _require_gpu(px, "px"); _require_gpu(py, "py")
     if px.dtype != torch.float32 or py.dtype != torch.float32:
         raise TypeError("px and py must be float32")
-    tok, blk = _check_tdt_moves(token_durations, blank_durations, blank_hi)
+    tok, blk = _check_tdt_moves(token_durations, blank_durations, blank_hi, max_moves)
     Dx, Dy = len(tok), len(blk)
     if px.dim() != 4 or py.dim() != 4:
         raise ValueError("px must be [B,Dx,S,T+1] and py [B,Dy,S+1,T]")
@@ -373,7 +376,7 @@ def mutual_information_recursion_tdt(
 
     px: [B,Dx,S,T+1], ``px[b,i,s,t]`` being the log-probability of the move (s,t) -> (s+1,t+token_durations[i]);
     py: [B,Dy,S+1,T], ``py[b,j,s,t]`` that of the move (s,t) -> (s,t+blank_durations[j]).  token_durations: Dx >= 1
-    strictly increasing ints in 0..16; blank_durations: Dy >= 1 strictly increasing ints in 1..16; Dx + Dy <= 9;
+    strictly increasing ints in 0..16; blank_durations: Dy >= 1 strictly increasing ints in 1..16; Dx + Dy <= 10;
     boundary: int32 [B,4] or None.
 
         p[s,t] = logadd(logadd_i p[s-1,t-e_i] + px[i,s-1,t-e_i], logadd_j p[s,t-d_j] + py[j,s,t-d_j]),  p[s_begin,t_begin] = 0
@@ -565,7 +568,7 @@ def mutual_information_viterbi_tdt(px: torch.Tensor, py: torch.Tensor, token_dur
     rectangle gives score 0 and -1 everywhere.  Not differentiable: the outputs are detached.  Asynchronous on torch's
     current stream, no host read (capturable)."""
     px, py, B, S, T, tok, blk, tok_arr, blk_arr = _duration_lattice_inputs(px.detach(), py.detach(), token_durations,
-                                                                           blank_durations, 32)   # a blank above 16: this entry alone
+                                                                           blank_durations, 32, max_moves=9)   # a blank above 16, nine moves: this entry alone
     Dx, Dy = len(tok), len(blk)
     boundary = _as_boundary(boundary, B, px.device)
     L = _lib.lib()

@@ -28,6 +28,7 @@ from typing import Optional, Tuple, Union
 
 import ctypes
 import os
+import weakref
 
 import torch
 
@@ -711,7 +712,8 @@ def rnnt_alignment_pruned(
 
 
 def _mark_band(ranges: torch.Tensor) -> None:
-    """Remembers on the tensor object that its CURRENT contents are a band (the version counter catches in-place edits)."""
+    """Remembers on the tensor object that its CURRENT contents are a band over ALL T frames, hence inside any boundary
+    (the version counter catches in-place edits)."""
     ranges._ftr_band = ranges._version
 
 
@@ -719,28 +721,55 @@ def _band_mark_valid(ranges: torch.Tensor) -> bool:
     return getattr(ranges, "_ftr_band", None) == ranges._version
 
 
-def _is_band(ranges: torch.Tensor, boundary) -> bool:
-    """Are these ranges what the band-native kernels assume (ranges[b,t,0] non-decreasing over the frames of each boundary
-    rectangle, ranges[b,t,k] = ranges[b,t,0] + k)?  Decided by the DATA: a tensor that carries no valid mark (anything but
-    the output of get_rnnt_prune_ranges itself: a clone, a slice, a .to(), a checkpoint) is checked once on the device
-    (ftr_band_ranges_check_i32, one small kernel and one host read of its flag word) and the verdict is remembered on the
-    tensor, so only the first use of an unknown tensor synchronises.  Under stream capture an unknown tensor takes the
-    lattice route (no host read inside a capture)."""
-    if _band_mark_valid(ranges):
-        return True
-    if getattr(ranges, "_ftr_not_band", None) == ranges._version:
-        return False
-    if torch.cuda.is_current_stream_capturing():
-        return False
+def _verdict_under(ranges: torch.Tensor, boundary):
+    """The verdict remembered for these ranges INSIDE THE RECTANGLES OF THIS BOUNDARY (True / False), None when there is
+    none: it holds for the boundary tensor object it was earned with, at the version it then had, and for nothing else."""
+    version, ref, bd_version, ok = getattr(ranges, "_ftr_band_under", (None, None, None, None))
+    if version == ranges._version and boundary is not None and ref() is boundary and bd_version == boundary._version:
+        return ok
+    return None
+
+
+def _band_check(ranges: torch.Tensor, boundary) -> bool:
+    """ftr_band_ranges_check_i32: one small kernel and one host read of its flag word."""
     B, T, r = ranges.shape
     flags = torch.empty((1,), dtype=torch.int32, device=ranges.device)
     with torch.cuda.device(ranges.device):
         _lib.call("ftr_band_ranges_check_i32", _ptr(ranges), _ptr(boundary), _ptr(flags), B, T, r, _stream_ptr(ranges))
-    ok = int(flags.item()) == 0
-    if ok:
-        _mark_band(ranges)
-    else:
+    return int(flags.item()) == 0
+
+
+def _is_band(ranges: torch.Tensor, boundary) -> bool:
+    """Are these ranges what the band-native kernels assume (ranges[b,t,0] non-decreasing over the frames of each boundary
+    rectangle, ranges[b,t,k] = ranges[b,t,0] + k)?  Decided by the DATA: a tensor that carries no valid mark (anything but
+    the output of get_rnnt_prune_ranges itself: a clone, a slice, a .to(), a checkpoint) is checked once on the device
+    and the verdict is remembered on the tensor, so only the first use of an unknown tensor synchronises.
+
+    A verdict is used only for a boundary it covers.  The check runs over all T frames first: a band there is a band
+    inside every rectangle, and that mark (_mark_band) is free of the boundary.  Ranges that fail it only outside the
+    rectangles (the padding frames of a padded batch may step backwards) are checked a second time inside them, and that
+    verdict, either way, is tied to the boundary tensor and its version (_verdict_under): the same ranges under a wider
+    boundary, or under none, are looked at again.  Under stream capture an unknown pair takes the lattice route (no host
+    read inside a capture)."""
+    if _band_mark_valid(ranges):
+        return True
+    if getattr(ranges, "_ftr_not_band", None) == ranges._version:      # not a band over all T frames
+        if boundary is None:
+            return False
+        known = _verdict_under(ranges, boundary)
+        if known is not None:
+            return known
+    if torch.cuda.is_current_stream_capturing():
+        return False
+    if getattr(ranges, "_ftr_not_band", None) != ranges._version:
+        if _band_check(ranges, None):
+            _mark_band(ranges)
+            return True
         ranges._ftr_not_band = ranges._version
+        if boundary is None:
+            return False
+    ok = _band_check(ranges, boundary)
+    ranges._ftr_band_under = (ranges._version, weakref.ref(boundary), boundary._version, ok)
     return ok
 
 
