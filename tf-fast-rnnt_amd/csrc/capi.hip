@@ -1068,9 +1068,11 @@ int ftr_tdt_pruned_logprobs_bwd_scaled_f32(const float* logits, const int32_t* s
 
 // ---- include/ftr_band_tdt.h: the TDT loss on the pruned band itself (csrc/mi_band_tdt.hip, csrc/tdt_logprobs.hip)
 size_t ftr_mutual_information_band_tdt_workspace_floats(int B, int T, int S, int r, int N, int Ny) {
-  return mi_band_tdt_workspace_floats(B, T, S, r, N, Ny);
+  return mi_band_tdt_workspace_floats(B, T, S, r, N, Ny, kBandTdtDomain);
 }
-int ftr_mutual_information_band_tdt_supported(int T, int S, int r, int N, int Ny) { return mi_band_tdt_supported(T, S, r, N, Ny); }
+int ftr_mutual_information_band_tdt_supported(int T, int S, int r, int N, int Ny) {
+  return mi_band_tdt_supported(T, S, r, N, Ny, kBandTdtDomain);
+}
 
 int ftr_mutual_information_band_tdt_f32(const float* px_band, const float* py_band, const int32_t* ranges,
                                         const int32_t* boundary, const int32_t* token_durations, int N,
@@ -1082,18 +1084,18 @@ int ftr_mutual_information_band_tdt_f32(const float* px_band, const float* py_ba
   FTR_TRY(tdt_check_list(what, "token_durations", token_durations, N, 5, 0));
   FTR_TRY(tdt_check_list(what, "blank_durations", blank_durations, Ny, 5, 1));
   FTR_TRY(check_sizes(what, B >= 0 && T >= 1 && S >= 0 && r >= 1));
-  if (!mi_band_tdt_supported(T, S, r, N, Ny)) {
+  if (!mi_band_tdt_supported(T, S, r, N, Ny, kBandTdtDomain)) {
     set_error("%s: T=%d S=%d r=%d is outside the kernel's domain (r <= 15)", what, T, S, r);
     return FTR_ERR_UNSUPPORTED;
   }
   if (B == 0) return FTR_OK;
-  FTR_TRY(check_ws_size(what, workspace_floats, mi_band_tdt_workspace_floats(B, T, S, r, N, Ny), "floats"));
+  FTR_TRY(check_ws_size(what, workspace_floats, mi_band_tdt_workspace_floats(B, T, S, r, N, Ny, kBandTdtDomain), "floats"));
   FTR_REQUIRE(px_band && py_band && ranges && workspace && ans, "%s: null px_band / py_band / ranges / workspace / ans", what);
   FTR_REQUIRE((gx_band != nullptr) == (gy_band != nullptr), "%s: gx_band and gy_band must both be given or both be null", what);
   FTR_TRY(check_ws_aligned(what, workspace));
   FTR_TRY(device_ok());
   return mi_band_tdt(px_band, py_band, ranges, boundary, token_durations, N, blank_durations, Ny, workspace, workspace_floats, ans,
-                     gx_band, gy_band, B, T, S, r, stream_of(stream));
+                     gx_band, gy_band, B, T, S, r, kBandTdtDomain, what, stream_of(stream));
 }
 
 int ftr_tdt_pruned_band_fwd_f32(const float* logits, const int32_t* symbols, const int32_t* ranges,
@@ -1126,6 +1128,75 @@ int ftr_tdt_pruned_band_bwd_scaled_f32(const float* logits, const int32_t* symbo
   FTR_TRY(pointers_then_device(what, logits && ranges && lse_tok && lse_dur && gx_band && gy_band && glogits && (symbols || S == 0)));
   return tdt_band_bwd(logits, symbols, ranges, boundary, termination_symbol, durations, N, lse_tok, lse_dur, gx_band, gy_band,
                       Scale{scale, scale_stride, scale_mul}, glogits, B, T, S, C, r, stream_of(stream));
+}
+
+// ---- include/ftr_band_multiblank.h: the multi-blank loss on the pruned band itself (the multi-blank domain of
+// csrc/mi_band_tdt.hip, the band-shaped mb_* kernels of csrc/pruned_logprobs.hip)
+size_t ftr_mutual_information_band_multiblank_workspace_floats(int B, int T, int S, int r, int D) {
+  return mi_band_tdt_workspace_floats(B, T, S, r, 1, D, kBandMultiblankDomain);
+}
+int ftr_mutual_information_band_multiblank_supported(int T, int S, int r, int D) {
+  return mi_band_tdt_supported(T, S, r, 1, D, kBandMultiblankDomain);
+}
+
+int ftr_mutual_information_band_multiblank_f32(const float* px_band, const float* py_band, const int32_t* ranges,
+                                               const int32_t* boundary, const int32_t* durations, int D, float* workspace,
+                                               size_t workspace_floats, float* ans, float* gx_band, float* gy_band, int B,
+                                               int T, int S, int r, void* stream) {
+  const char* what = "mutual_information_band_multiblank";
+  clear_error();
+  if (D < 1 || D > 8) {                      // the length of the list itself: the domain, before the list is read
+    set_error("%s: D = %d is outside the kernel's domain (1..8 blanks)", what, D);
+    return FTR_ERR_UNSUPPORTED;
+  }
+  FTR_TRY(mb_check_durations(what, durations, D, false));
+  FTR_TRY(check_sizes(what, B >= 0 && T >= 1 && S >= 0 && r >= 1));
+  if (!mi_band_tdt_supported(T, S, r, 1, D, kBandMultiblankDomain)) {
+    set_error("%s: T=%d S=%d r=%d is outside the kernel's domain (r <= 15)", what, T, S, r);
+    return FTR_ERR_UNSUPPORTED;
+  }
+  if (B == 0) return FTR_OK;
+  FTR_TRY(check_ws_size(what, workspace_floats, mi_band_tdt_workspace_floats(B, T, S, r, 1, D, kBandMultiblankDomain), "floats"));
+  FTR_REQUIRE(px_band && py_band && ranges && workspace && ans, "%s: null px_band / py_band / ranges / workspace / ans", what);
+  FTR_REQUIRE((gx_band != nullptr) == (gy_band != nullptr), "%s: gx_band and gy_band must both be given or both be null", what);
+  FTR_TRY(check_ws_aligned(what, workspace));
+  FTR_TRY(device_ok());
+  return mi_band_multiblank(px_band, py_band, ranges, boundary, durations, D, workspace, workspace_floats, ans, gx_band, gy_band, B,
+                            T, S, r, stream_of(stream));
+}
+
+int ftr_multiblank_pruned_band_fwd_f32(const float* logits, const int32_t* symbols, const int32_t* ranges,
+                                       const int32_t* boundary, int termination_symbol, const int32_t* big_blank_ids,
+                                       const int32_t* durations, int D, double sigma, double delay_penalty, float* lse,
+                                       float* px_band, float* py_band, int B, int T, int S, int C, int r, void* stream) {
+  const char* what = "multiblank_pruned_band_fwd";
+  clear_error();
+  FTR_TRY(mb_check_durations(what, durations, D, true));
+  FTR_TRY(mb_check_ids(what, big_blank_ids, D, termination_symbol, C));
+  FTR_TRY(check_sizes(what, B >= 0 && T >= 1 && S >= 0 && r >= 1));
+  FTR_TRY(check_s_range(what, r, S));
+  FTR_REQUIRE(sigma >= 0.0, "%s: sigma = %g must not be negative", what, sigma);
+  if (B == 0) return FTR_OK;
+  FTR_TRY(pointers_then_device(what, logits && ranges && lse && px_band && py_band && (symbols || S == 0)));
+  return multiblank_band_fwd(logits, symbols, ranges, boundary, termination_symbol, big_blank_ids, durations, D, sigma,
+                             delay_penalty, lse, px_band, py_band, B, T, S, C, r, stream_of(stream));
+}
+
+int ftr_multiblank_pruned_band_bwd_scaled_f32(const float* logits, const int32_t* symbols, const int32_t* ranges,
+                                              const int32_t* boundary, int termination_symbol, const int32_t* big_blank_ids,
+                                              const int32_t* durations, int D, const float* lse, const float* gx_band,
+                                              const float* gy_band, const float* scale, int scale_stride, float scale_mul,
+                                              float* glogits, int B, int T, int S, int C, int r, void* stream) {
+  const char* what = "multiblank_pruned_band_bwd_scaled";
+  clear_error();
+  FTR_TRY(mb_check_durations(what, durations, D, true));
+  FTR_TRY(mb_check_ids(what, big_blank_ids, D, termination_symbol, C));
+  FTR_TRY(check_sizes(what, B >= 0 && T >= 1 && S >= 0 && r >= 1));
+  FTR_TRY(check_scale_stride(what, scale_stride));
+  if (B == 0) return FTR_OK;
+  FTR_TRY(pointers_then_device(what, logits && ranges && lse && gx_band && gy_band && glogits && (symbols || S == 0)));
+  return multiblank_band_bwd(logits, symbols, ranges, boundary, termination_symbol, big_blank_ids, durations, D, lse, gx_band,
+                             gy_band, Scale{scale, scale_stride, scale_mul}, glogits, B, T, S, C, r, stream_of(stream));
 }
 
 // ---- include/ftr_kd.h: knowledge distillation on the pruned band (csrc/pruned_kd.hip)

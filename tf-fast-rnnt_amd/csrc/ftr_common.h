@@ -7,6 +7,7 @@
 #include "../../include/ftr_kd.h"  // and, through it, ftr_lowp.h and ftr.h
 #include "../../include/ftr_fused.h"
 #include "../../include/ftr_band_tdt.h"
+#include "../../include/ftr_band_multiblank.h"
 
 namespace ftr {
 
@@ -224,11 +225,21 @@ int mi_tdt_bwd(const float* px, const float* py, const int32_t* boundary, const 
 int tdt_logprobs_fwd(const float* logits, const int32_t* symbols, const int32_t* ranges, const int32_t* boundary, int blank, const int32_t* durations, int N, double sigma, double delay_penalty, float* lse_tok, float* lse_dur, float* px, float* py, int B, int T, int S, int C, int r, hipStream_t st);
 int tdt_logprobs_bwd(const float* logits, const int32_t* symbols, const int32_t* ranges, const int32_t* boundary, int blank, const int32_t* durations, int N, const float* lse_tok, const float* lse_dur, const float* gpx, const float* gpy, Scale scale, float* glogits, int B, int T, int S, int C, int r, hipStream_t st);
 // TDT on the pruned band (include/ftr_band_tdt.h): csrc/mi_band_tdt.hip and the band-shaped builders of csrc/tdt_logprobs.hip
-int mi_band_tdt_supported(int T, int S, int r, int N, int Ny);
-size_t mi_band_tdt_workspace_floats(int B, int T, int S, int r, int N, int Ny);
-int mi_band_tdt(const float* pxb, const float* pyb, const int32_t* ranges, const int32_t* boundary, const int32_t* token_durations, int N, const int32_t* blank_durations, int Ny, float* ws, size_t ws_floats, float* ans, float* gxb, float* gyb, int B, int T, int S, int r, hipStream_t st);
+// which move lists an entry point of the band chain admits: up to max_tok token and max_blk blank moves, durations up to
+// max_dur (a token of duration e reaches e + 1 steps back, a blank of duration d reaches d)
+struct BandMoveDomain { int max_tok, max_blk, max_dur; };
+constexpr BandMoveDomain kBandTdtDomain{5, 5, 16};          // include/ftr_band_tdt.h
+constexpr BandMoveDomain kBandMultiblankDomain{1, 8, 32};   // include/ftr_band_multiblank.h: one token move of duration 0
+int mi_band_tdt_supported(int T, int S, int r, int N, int Ny, BandMoveDomain dom);
+size_t mi_band_tdt_workspace_floats(int B, int T, int S, int r, int N, int Ny, BandMoveDomain dom);
+int mi_band_tdt(const float* pxb, const float* pyb, const int32_t* ranges, const int32_t* boundary, const int32_t* token_durations, int N, const int32_t* blank_durations, int Ny, float* ws, size_t ws_floats, float* ans, float* gxb, float* gyb, int B, int T, int S, int r, BandMoveDomain dom, const char* what, hipStream_t st);
 int tdt_band_fwd(const float* logits, const int32_t* symbols, const int32_t* ranges, const int32_t* boundary, int blank, const int32_t* durations, int N, double sigma, double delay_penalty, float* lse_tok, float* lse_dur, float* pxb, float* pyb, int B, int T, int S, int C, int r, hipStream_t st);
 int tdt_band_bwd(const float* logits, const int32_t* symbols, const int32_t* ranges, const int32_t* boundary, int blank, const int32_t* durations, int N, const float* lse_tok, const float* lse_dur, const float* gxb, const float* gyb, Scale scale, float* glogits, int B, int T, int S, int C, int r, hipStream_t st);
+// multi-blank on the pruned band (include/ftr_band_multiblank.h): the chain of csrc/mi_band_tdt.hip in its multi-blank
+// domain and the band-shaped builders of csrc/pruned_logprobs.hip
+int mi_band_multiblank(const float* pxb, const float* pyb, const int32_t* ranges, const int32_t* boundary, const int32_t* durations, int D, float* ws, size_t ws_floats, float* ans, float* gxb, float* gyb, int B, int T, int S, int r, hipStream_t st);
+int multiblank_band_fwd(const float* logits, const int32_t* symbols, const int32_t* ranges, const int32_t* boundary, int blank, const int32_t* big_ids, const int32_t* durations, int D, double sigma, double delay_penalty, float* lse, float* pxb, float* pyb, int B, int T, int S, int C, int r, hipStream_t st);
+int multiblank_band_bwd(const float* logits, const int32_t* symbols, const int32_t* ranges, const int32_t* boundary, int blank, const int32_t* big_ids, const int32_t* durations, int D, const float* lse, const float* gxb, const float* gyb, Scale scale, float* glogits, int B, int T, int S, int C, int r, hipStream_t st);
 // best-path alignment over the TDT / multi-blank lattice: csrc/mi_viterbi_tdt.hip; the duration lists are host arrays
 size_t mi_viterbi_tdt_workspace_bytes(int B, int S, int T);
 int mi_viterbi_tdt(const float* px, const float* py, const int32_t* boundary, const int32_t* token_durations, int Dx, const int32_t* blank_durations, int Dy, void* ws, size_t ws_bytes, float* score, int32_t* frames, int32_t* durations, int32_t* blank_steps, int B, int S, int T, hipStream_t st);

@@ -28,6 +28,11 @@
 //
 // A band whose start decreases inside the rectangle puts two cells into one slot: ans = NaN, zero occupancies, as
 // mi_band.hip answers it.
+//
+// Domain.  The kernels take any list of up to kTdtMaxMoves moves whose step offsets fit the ring; which lists an entry
+// point admits is a BandMoveDomain (ftr_common.h) that the host functions take as a parameter: (5, 5, 16) for TDT, and
+// (1, 8, 32) for the multi-blank recursion (include/ftr_band_multiblank.h), which is the same chain with one token move
+// of duration 0 and D <= 8 blank moves of durations up to 32: M = D + 1 <= 9, DEP = 64 at duration 32.
 #include "mi_band_common.h"
 #include "mi_rowlane.h"   // exp_of
 
@@ -35,8 +40,8 @@ namespace ftr {
 namespace {
 
 constexpr int kTdtThreads = 256;
-constexpr int kTdtMaxMoves = 10;   // N <= 5 token moves and Ny <= 5 blank moves
-constexpr int kTdtMaxDep = 64;     // ring steps the static LDS holds (durations up to 32 would need all of them)
+constexpr int kTdtMaxMoves = 10;   // TDT: N <= 5 token moves and Ny <= 5 blank moves; multi-blank: 1 + 8
+constexpr int kTdtMaxDep = 64;     // ring steps the static LDS holds (a duration of 32 needs all of them)
 constexpr int TCH = 4;             // steps per operand fetch
 
 // moves 0 .. Dx-1 are the token moves (px_band planes), Dx .. M-1 the blank moves (py_band planes)
@@ -226,34 +231,38 @@ BandMoves make_band_moves(const int32_t* tok, int N, const int32_t* blk, int Ny)
   return mv;
 }
 // the power of two above the largest step offset of a move (a token of duration e reads e + 1 steps back)
-int band_tdt_ring_depth(const int32_t* tok, int N, const int32_t* blk, int Ny) {
-  const int far = (tok[N - 1] + 1 > blk[Ny - 1]) ? tok[N - 1] + 1 : blk[Ny - 1];
+int ring_depth_for(int far) {
   int dep = 2;
   while (dep <= far) dep *= 2;
   return dep;
 }
+int band_tdt_ring_depth(const int32_t* tok, int N, const int32_t* blk, int Ny) {
+  return ring_depth_for((tok[N - 1] + 1 > blk[Ny - 1]) ? tok[N - 1] + 1 : blk[Ny - 1]);
+}
 
 }  // namespace
 
-// r within the band kernels' lanes, the move counts of the TDT builder, and slot indices that stay 32-bit
-int mi_band_tdt_supported(int T, int S, int r, int N, int Ny) {
+// r within the band kernels' lanes, the move counts of the entry point's domain, and slot indices that stay 32-bit
+int mi_band_tdt_supported(int T, int S, int r, int N, int Ny, BandMoveDomain dom) {
+  static_assert(kBandTdtDomain.max_tok + kBandTdtDomain.max_blk <= kTdtMaxMoves &&
+                kBandMultiblankDomain.max_tok + kBandMultiblankDomain.max_blk <= kTdtMaxMoves, "the chain is instantiated for 2..kTdtMaxMoves moves");
   const int lanes = band_lanes_for(r);
-  if (!lanes || T < 1 || S < 0 || N < 1 || N > 5 || Ny < 1 || Ny > 5) return 0;
+  if (!lanes || T < 1 || S < 0 || N < 1 || N > dom.max_tok || Ny < 1 || Ny > dom.max_blk) return 0;
   return ((uint64_t)S + T + 1 + 2 * TCH) * (uint64_t)(lanes * (N + Ny)) < (1ull << 31) ? 1 : 0;
 }
 
-size_t mi_band_tdt_workspace_floats(int B, int T, int S, int r, int N, int Ny) {
-  if (B < 0 || !mi_band_tdt_supported(T, S, r, N, Ny)) return 0;
+size_t mi_band_tdt_workspace_floats(int B, int T, int S, int r, int N, int Ny, BandMoveDomain dom) {
+  if (B < 0 || !mi_band_tdt_supported(T, S, r, N, Ny, dom)) return 0;
   return tdt_layout(B, T, S, band_lanes_for(r), N + Ny).total_floats;
 }
 
 int mi_band_tdt(const float* pxb, const float* pyb, const int32_t* ranges, const int32_t* boundary, const int32_t* tok, int N,
                 const int32_t* blk, int Ny, float* ws, size_t ws_floats, float* ans, float* gxb, float* gyb, int B, int T,
-                int S, int r, hipStream_t st) {
-  const char* what = "mutual_information_band_tdt";
+                int S, int r, BandMoveDomain dom, const char* what, hipStream_t st) {
   if (B == 0) return FTR_OK;
-  if (!mi_band_tdt_supported(T, S, r, N, Ny)) {
-    set_error("%s: T=%d S=%d r=%d N=%d Ny=%d is outside the kernel's domain (r <= 15, 1..5 moves of each kind)", what, T, S, r, N, Ny);
+  if (!mi_band_tdt_supported(T, S, r, N, Ny, dom)) {
+    set_error("%s: T=%d S=%d r=%d N=%d Ny=%d is outside the kernel's domain (r <= 15, 1..%d token and 1..%d blank moves)", what, T, S,
+              r, N, Ny, dom.max_tok, dom.max_blk);
     return FTR_ERR_UNSUPPORTED;
   }
   if (B > 65535) { set_error("%s: B = %d exceeds the 65535 utterances of one launch", what, B); return FTR_ERR_UNSUPPORTED; }
@@ -261,7 +270,11 @@ int mi_band_tdt(const float* pxb, const float* pyb, const int32_t* ranges, const
   { const int rc32 = require_rows_32bit(what, rows); if (rc32 != FTR_OK) return rc32; }
   const int lanes = band_lanes_for(r), M = N + Ny;
   const int DEP = band_tdt_ring_depth(tok, N, blk, Ny);
-  if (DEP > kTdtMaxDep) { set_error("%s: a ring of %d steps exceeds the %d this build holds", what, DEP, kTdtMaxDep); return FTR_ERR_UNSUPPORTED; }
+  static_assert(kBandTdtDomain.max_dur < kTdtMaxDep && kBandMultiblankDomain.max_dur < kTdtMaxDep, "the ring must hold the longest move");
+  if (DEP > ring_depth_for(dom.max_dur)) {
+    set_error("%s: a ring of %d steps exceeds the %d of durations up to %d", what, DEP, ring_depth_for(dom.max_dur), dom.max_dur);
+    return FTR_ERR_UNSUPPORTED;
+  }
   const TdtLayout L = tdt_layout(B, T, S, lanes, M);
   if (ws_floats < L.total_floats) {
     set_error("%s: workspace of %zu floats is too small, %zu needed", what, ws_floats, L.total_floats);
@@ -284,6 +297,16 @@ int mi_band_tdt(const float* pxb, const float* pyb, const int32_t* ranges, const
                        ranges, boundary, mv, wsd, gxb, gyb, L.p_per, rows, B, T, S, r);
   });
   return check_launch("band_tdt_occupancy");
+}
+
+// the multi-blank recursion: the same chain with one token move of duration 0 (px_band [B,T,r] is its one plane) and the
+// D blank moves of `durations`
+int mi_band_multiblank(const float* pxb, const float* pyb, const int32_t* ranges, const int32_t* boundary, const int32_t* durations,
+                       int D, float* ws, size_t ws_floats, float* ans, float* gxb, float* gyb, int B, int T, int S, int r,
+                       hipStream_t st) {
+  const int32_t tok[1] = {0};
+  return mi_band_tdt(pxb, pyb, ranges, boundary, tok, 1, durations, D, ws, ws_floats, ans, gxb, gyb, B, T, S, r,
+                     kBandMultiblankDomain, "mutual_information_band_multiblank", st);
 }
 
 }  // namespace ftr

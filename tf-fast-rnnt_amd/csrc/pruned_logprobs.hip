@@ -347,6 +347,10 @@ int pruned_logprobs_bwd(const void* logits, int dtype, const int32_t* symbols, c
 // The row is normalised by the ordinary softmax over all C columns (lse_rows, unchanged); `sigma` is subtracted from
 // every log-probability.  py has D planes [B,D,S+1,T]; py[b,j,s,t] = -inf where t + d[j] > t_end.  A symbol that is a
 // big blank gets px = -inf and no gradient.  Kernels of their own, so the ordinary instantiations above stay as they are.
+// The band-shaped twins (include/ftr_band_multiblank.h; the operands and occupancies of mi_band_tdt.hip's multi-blank
+// entry, px_band [B,T,r] and py_band [B,D,T,r]): mb_to_band_kernel writes what mb_to_lattice_kernel puts at lattice cell
+// (ranges[b,t,0] + k, t), by the same arithmetic, one thread per band row and no lattice write; mb_grad_kernel<., true>
+// is the same gradient kernel reading gx_band / gy_band at the row itself.
 namespace {
 
 struct MbCols { int id[8]; int d[8]; int D; };   // id[0] = the standard blank, d[0] = 1
@@ -400,9 +404,45 @@ __global__ void mb_to_lattice_kernel(const float* __restrict__ logits, const int
   }
 }
 
+// one thread per band row (b,t,k) <-> lattice cell (s,t), s = (ranges[b,t,0] + k) mod (S+1) as the lattice kernel's roll.
+// Every element of px_band [B,T,r] and py_band [B,D,T,r] is written.
+__global__ void mb_to_band_kernel(const float* __restrict__ logits, const int32_t* __restrict__ symbols,
+                                  const int32_t* __restrict__ ranges, const int32_t* __restrict__ boundary,
+                                  const float* __restrict__ lse, const MbCols mc, float sigma, double delay_penalty,
+                                  float* __restrict__ pxb, float* __restrict__ pyb, size_t rows, int T, int S, int C, int r) {
+  const size_t row = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (row >= rows) return;
+  const size_t bt = row / r;
+  const int k = (int)(row - bt * r);
+  const int b = (int)(bt / T);
+  const int t = (int)(bt - (size_t)b * T);
+  int s = ranges[bt * r] + k;
+  if (s > S) s -= S + 1;
+  const bool sok = s >= 0 && s <= S;
+  const int te = boundary ? boundary[4 * b + 3] : T;
+  const float l = lse[row] + sigma;
+  float vx = -INFINITY;
+  if (sok && s < S) {
+    const int c = min(max(symbols[(size_t)b * S + s], 0), C - 1);
+    if (!mb_is_big_blank(mc, c)) vx = logits[row * C + c] - l;
+  }
+  if (t == te) vx = -INFINITY;
+  if (delay_penalty > 0.0) {
+    const double offset = ((double)te - 1.0) / 2.0;
+    vx += (float)((offset - (double)t) * delay_penalty);
+  }
+  pxb[row] = vx;
+  for (int j = 0; j < mc.D; ++j) {
+    float vy = -INFINITY;
+    if (sok && t + mc.d[j] <= te) vy = logits[row * C + mc.id[j]] - l;
+    pyb[(((size_t)b * mc.D + j) * T + t) * r + k] = vy;
+  }
+}
+
 // one wave per (b,t,k) row of glogits, as band_grad_kernel: g[c] = -softmax(x)[c] (gx + sum_j gy_j) + 1[c == sym] gx
-// + sum_j 1[c == id_j] gy_j; each blank column takes its term in the lane that holds the column.
-template <bool VEC>
+// + sum_j 1[c == id_j] gy_j; each blank column takes its term in the lane that holds the column.  BAND: gpx / gpy are
+// the band-shaped occupancies [B,T,r] / [B,D,T,r], the row's own element of each plane, else the full-size lattices.
+template <bool VEC, bool BAND>
 __global__ void mb_grad_kernel(const float* __restrict__ logits, const int32_t* __restrict__ symbols,
                                const int32_t* __restrict__ ranges, const int32_t* __restrict__ boundary,
                                const float* __restrict__ lse, const float* __restrict__ gpx,
@@ -426,14 +466,15 @@ __global__ void mb_grad_kernel(const float* __restrict__ logits, const int32_t* 
   const bool sok = s >= 0 && s <= S;
   if (sok && s < S) {
     sym = min(max(symbols[(size_t)b * S + s], 0), C - 1);   // the column the forward read
-    if (t != te && !mb_is_big_blank(mc, sym)) gx = gpx[((size_t)b * S + s) * T1 + t] * sc;
+    if (t != te && !mb_is_big_blank(mc, sym)) gx = gpx[BAND ? row : ((size_t)b * S + s) * T1 + t] * sc;
   }
   float gy[8];
   float tot = gx;
 #pragma unroll
   for (int j = 0; j < 8; ++j) {
     gy[j] = 0.0f;
-    if (j < mc.D && sok && t + mc.d[j] <= te) gy[j] = gpy[(((size_t)b * mc.D + j) * (S + 1) + s) * T + t] * sc;
+    if (j < mc.D && sok && t + mc.d[j] <= te)
+      gy[j] = gpy[BAND ? (((size_t)b * mc.D + j) * T + t) * r + k : (((size_t)b * mc.D + j) * (S + 1) + s) * T + t] * sc;
     tot += gy[j];
   }
   const float l = lse[row];
@@ -510,10 +551,39 @@ int multiblank_logprobs_bwd(const float* logits, const int32_t* symbols, const i
   const unsigned blocks = (unsigned)((rows + wpb - 1) / wpb);
   const MbCols mc = mb_cols(blank, big_ids, durations, D);
   dispatch((C & 3) == 0, [&](auto vec) {
-    hipLaunchKernelGGL((mb_grad_kernel<decltype(vec)::value>), dim3(blocks), dim3(64 * wpb), 0, st, logits, symbols, ranges, boundary, lse,
+    hipLaunchKernelGGL((mb_grad_kernel<decltype(vec)::value, false>), dim3(blocks), dim3(64 * wpb), 0, st, logits, symbols, ranges, boundary, lse,
                        gpx, gpy, scale, mc, glogits, rows, T, S, C, r);
   });
   return check_launch("multiblank_grad");
+}
+
+int multiblank_band_fwd(const float* logits, const int32_t* symbols, const int32_t* ranges, const int32_t* boundary, int blank,
+                        const int32_t* big_ids, const int32_t* durations, int D, double sigma, double delay_penalty, float* lse,
+                        float* pxb, float* pyb, int B, int T, int S, int C, int r, hipStream_t st) {
+  const size_t rows = (size_t)B * T * r;
+  if (rows == 0) return FTR_OK;
+  { const int rc32 = require_rows_32bit("multiblank_pruned_band_fwd", rows); if (rc32 != FTR_OK) return rc32; }
+  int rc = lse_rows(logits, lse, rows, C, blank, 0, st);
+  if (rc != FTR_OK) return rc;
+  hipLaunchKernelGGL(mb_to_band_kernel, dim3((unsigned)((rows + 255) / 256)), dim3(256), 0, st, logits, symbols, ranges, boundary,
+                     lse, mb_cols(blank, big_ids, durations, D), (float)sigma, delay_penalty, pxb, pyb, rows, T, S, C, r);
+  return check_launch("multiblank_to_band");
+}
+
+int multiblank_band_bwd(const float* logits, const int32_t* symbols, const int32_t* ranges, const int32_t* boundary, int blank,
+                        const int32_t* big_ids, const int32_t* durations, int D, const float* lse, const float* gxb,
+                        const float* gyb, Scale scale, float* glogits, int B, int T, int S, int C, int r, hipStream_t st) {
+  const size_t rows = (size_t)B * T * r;
+  if (rows == 0) return FTR_OK;
+  { const int rc32 = require_rows_32bit("multiblank_pruned_band_bwd", rows); if (rc32 != FTR_OK) return rc32; }
+  const int wpb = 4;
+  const unsigned blocks = (unsigned)((rows + wpb - 1) / wpb);
+  const MbCols mc = mb_cols(blank, big_ids, durations, D);
+  dispatch((C & 3) == 0, [&](auto vec) {
+    hipLaunchKernelGGL((mb_grad_kernel<decltype(vec)::value, true>), dim3(blocks), dim3(64 * wpb), 0, st, logits, symbols, ranges, boundary, lse,
+                       gxb, gyb, scale, mc, glogits, rows, T, S, C, r);
+  });
+  return check_launch("multiblank_band_grad");
 }
 
 }  // namespace ftr

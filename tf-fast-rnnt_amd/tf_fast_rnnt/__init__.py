@@ -17,6 +17,7 @@ from .rnnt_loss import get_rnnt_logprobs_multiblank_joint, get_rnnt_logprobs_mul
 from .rnnt_loss import rnnt_loss_multiblank, rnnt_loss_multiblank_pruned                           # transducer loss, see there
 from .mutual_information import mutual_information_recursion_tdt           # MI355X addition: token-and-duration (TDT) lattice
 from .mutual_information import mutual_information_recursion_tdt_band      # ... and the same recursion on the pruned band itself
+from .mutual_information import mutual_information_recursion_multiblank_band   # the multi-blank recursion on the pruned band
 from .rnnt_loss import get_rnnt_logprobs_tdt_joint, get_rnnt_logprobs_tdt_pruned   # MI355X addition: TDT loss, a separate
 from .rnnt_loss import rnnt_loss_tdt, rnnt_loss_tdt_pruned                         # duration head, see there
 from .mutual_information import mutual_information_viterbi_tdt              # MI355X addition: best-path alignment over the

@@ -131,12 +131,23 @@ _BAND_TDT_SIGNATURES = {
     "ftr_tdt_pruned_band_fwd_f32": (_i, [_c_fp, _c_ip, _c_ip, _c_ip, _i, _c_hi, _i, ctypes.c_double, ctypes.c_double, _c_fp, _c_fp, _c_fp, _c_fp, _i, _i, _i, _i, _i, _c_st]),
     "ftr_tdt_pruned_band_bwd_scaled_f32": (_i, [_c_fp, _c_ip, _c_ip, _c_ip, _i, _c_hi, _i, ctypes.c_double, ctypes.c_double, _c_fp, _c_fp, _c_fp, _c_fp, _c_fp, _i, _f, _c_fp, _i, _i, _i, _i, _i, _c_st]),
 }
+# include/ftr_band_multiblank.h, the multi-blank loss on the pruned band itself: the workspace and domain queries, the
+# recursion on band-shaped operands, and the band-shaped twins of the two ftr_multiblank_pruned_logprobs_* builders
+_BAND_MULTIBLANK_SIGNATURES = {
+    "ftr_mutual_information_band_multiblank_workspace_floats": (ctypes.c_size_t, [_i, _i, _i, _i, _i]),
+    "ftr_mutual_information_band_multiblank_supported": (_i, [_i, _i, _i, _i]),
+    "ftr_mutual_information_band_multiblank_f32": (_i, [_c_fp, _c_fp, _c_ip, _c_ip, _c_hi, _i, _c_fp, ctypes.c_size_t, _c_fp, _c_fp, _c_fp, _i, _i, _i, _i, _c_st]),
+    "ftr_multiblank_pruned_band_fwd_f32": (_i, [_c_fp, _c_ip, _c_ip, _c_ip, _i, _c_hi, _c_hi, _i, ctypes.c_double, ctypes.c_double, _c_fp, _c_fp, _c_fp, _i, _i, _i, _i, _i, _c_st]),
+    "ftr_multiblank_pruned_band_bwd_scaled_f32": (_i, [_c_fp, _c_ip, _c_ip, _c_ip, _i, _c_hi, _c_hi, _i, _c_fp, _c_fp, _c_fp, _c_fp, _i, _f, _c_fp, _i, _i, _i, _i, _i, _c_st]),
+}
 EXPORTED_SYMBOLS = tuple(_SIGNATURES)            # the symbols of include/ftr.h
 LOWP_SYMBOLS = tuple(_LOWP_SIGNATURES)           # those of include/ftr_lowp.h
 KD_SYMBOLS = tuple(_KD_SIGNATURES)               # those of include/ftr_kd.h
 FUSED_SYMBOLS = tuple(_FUSED_SIGNATURES)         # those of include/ftr_fused.h
 BAND_TDT_SYMBOLS = tuple(_BAND_TDT_SIGNATURES)   # those of include/ftr_band_tdt.h
+BAND_MULTIBLANK_SYMBOLS = tuple(_BAND_MULTIBLANK_SIGNATURES)   # those of include/ftr_band_multiblank.h
 band_tdt_recursions = 0   # how many times the band-native TDT recursion has been launched from Python (tests read it)
+band_multiblank_recursions = 0   # ... and the band-native multi-blank recursion, likewise
 FTR_KD_FULL, FTR_KD_COLLAPSED = 0, 1             # include/ftr_kd.h: the `mode` of the kd entry points
 FTR_MI_WS_CLEAN = 1   # include/ftr.h
 FTR_DTYPE_F32, FTR_DTYPE_BF16, FTR_DTYPE_FP16 = 0, 1, 2   # include/ftr_lowp.h: the `kind` of the _dt entry points
@@ -153,7 +164,7 @@ def lib() -> ctypes.CDLL:
                 "g.build()' or make -C tf-fast-rnnt_amd/csrc).  tf_fast_rnnt has no CPU fallback.")
         handle = ctypes.CDLL(LIB_PATH)
         for name, (restype, argtypes) in {**_SIGNATURES, **_LOWP_SIGNATURES, **_KD_SIGNATURES, **_FUSED_SIGNATURES,
-                                            **_BAND_TDT_SIGNATURES}.items():
+                                            **_BAND_TDT_SIGNATURES, **_BAND_MULTIBLANK_SIGNATURES}.items():
             fn = getattr(handle, name)   # AttributeError here = header/library mismatch
             fn.restype = restype
             fn.argtypes = argtypes

@@ -494,6 +494,102 @@ def mutual_information_recursion_tdt_band(
     return _BandTdtRecursion.apply(px_band, py_band, ranges, S, tok, blk, boundary)
 
 
+def band_multiblank_supported(T: int, S: int, r: int, D: int) -> bool:
+    """Does the band-native multi-blank recursion (the multi-blank domain of csrc/mi_band_tdt.hip) cover these sizes?"""
+    return _lib.lib().ftr_mutual_information_band_multiblank_supported(int(T), int(S), int(r), int(D)) != 0
+
+
+def band_multiblank_forward_backward(px_band: torch.Tensor, py_band: torch.Tensor, ranges: torch.Tensor, S: int, durations,
+                                     boundary: Optional[torch.Tensor], need_grads: bool):
+    """The multi-blank recursion on band-shaped operands, raw tensors (no autograd): one chain launch for both directions
+    and one occupancy launch on torch's current stream.  Returns (ans, gx_band|None, gy_band|None); the occupancies are
+    seeded with ones.  ``ranges`` must be a band (the caller's business: _is_band of rnnt_loss.py)."""
+    import ctypes
+    durs = _check_durations(durations)
+    D = len(durs)
+    B, T, r = px_band.shape
+    dur_arr = (ctypes.c_int32 * D)(*durs)       # read by the launch itself: no device copy, no host synchronisation
+    L = _lib.lib()
+    with torch.cuda.device(px_band.device):
+        st = _stream_ptr(px_band)
+        nws = L.ftr_mutual_information_band_multiblank_workspace_floats(B, T, int(S), r, D)
+        ws = torch.empty((max(nws, 2) + 1) // 2, dtype=torch.float64, device=px_band.device)
+        ans = torch.empty((B,), dtype=torch.float32, device=px_band.device)
+        gx = torch.empty_like(px_band) if need_grads else None
+        gy = torch.empty_like(py_band) if need_grads else None
+        _lib.call("ftr_mutual_information_band_multiblank_f32", _ptr(px_band), _ptr(py_band), _ptr(ranges), _ptr(boundary),
+                  dur_arr, D, _ptr(ws), nws, _ptr(ans), _ptr(gx), _ptr(gy), B, T, int(S), r, st)
+        _lib.band_multiblank_recursions += 1
+    return ans, gx, gy
+
+
+class _BandMultiblankRecursion(torch.autograd.Function):
+    """mutual_information_recursion_multiblank_band: the occupancies are computed with the answer whenever an operand
+    needs a gradient, and backward() scales them by the upstream gradient."""
+
+    @staticmethod
+    def forward(ctx, px_band, py_band, ranges, S, durs, boundary):
+        need = px_band.requires_grad or py_band.requires_grad
+        ans, gx, gy = band_multiblank_forward_backward(px_band.detach().contiguous(), py_band.detach().contiguous(), ranges, S,
+                                                       durs, boundary, need)
+        if need:
+            ctx.save_for_backward(gx, gy)
+        return ans
+
+    @staticmethod
+    def backward(ctx, g_ans):
+        gx, gy = ctx.saved_tensors
+        g = g_ans.to(gx.dtype)
+        return gx * g.reshape(-1, 1, 1), gy * g.reshape(-1, 1, 1, 1), None, None, None, None
+
+
+def mutual_information_recursion_multiblank_band(
+    px_band: torch.Tensor,
+    py_band: torch.Tensor,
+    ranges: torch.Tensor,
+    durations,
+    boundary: Optional[torch.Tensor] = None,
+    S: Optional[int] = None,
+) -> torch.Tensor:
+    """``mutual_information_recursion_multiblank`` on the pruned band itself (MI355X addition; the multi-blank domain of
+    csrc/mi_band_tdt.hip): nothing of size S*T is allocated or touched.
+
+    px_band: [B,T,r] and py_band: [B,D,T,r], float32; element (b,t,k) / (b,j,t,k) is the log-probability of the symbol
+    move / of blank j out of lattice cell (ranges[b,t,0] + k, t), i.e. what ``get_rnnt_logprobs_multiblank_pruned`` puts
+    at ``px[b,s,t]`` / ``py[b,j,s,t]`` (its -inf rules included).  ranges: int32 [B,T,r], a band as
+    ``get_rnnt_prune_ranges`` returns it (``ranges[b,t,k] = ranges[b,t,0] + k``, non-decreasing over t), r <= 15.  S: the
+    number of symbols (the lattice has rows 0..S); when omitted it is taken to be ``ranges.max()``, the last band row, at
+    the price of one host read.  durations: the D blank durations, 1..8 strictly increasing ints in 1..32 (they need not
+    contain 1).
+
+    A move exists iff its source is a band cell inside the boundary rectangle and its destination is one, or the end
+    cell ``(s_end, t_end)``; the frames a blank skips need not be in the band.  Returns ``ans`` [B] (-inf without a path;
+    NaN for a band whose start decreases), equal to ``mutual_information_recursion_multiblank`` on the band scattered
+    into full-size lattices of -inf.  Differentiable w.r.t. px_band and py_band (the occupancies times the upstream
+    gradient); asynchronous, no host read when ``S`` is given (capturable)."""
+    _require_gpu(px_band, "px_band"); _require_gpu(py_band, "py_band")
+    if px_band.dtype != torch.float32 or py_band.dtype != torch.float32:
+        raise TypeError("px_band and py_band must be float32")
+    durs = _check_durations(durations)
+    if px_band.dim() != 3 or py_band.dim() != 4:
+        raise ValueError("px_band must be [B,T,r] and py_band [B,D,T,r]")
+    B, T, r = px_band.shape
+    if tuple(py_band.shape) != (B, len(durs), T, r):
+        raise ValueError(f"py_band must have shape {(B, len(durs), T, r)}, got {tuple(py_band.shape)}")
+    ranges = torch.as_tensor(ranges, device=px_band.device).to(torch.int32).contiguous()
+    if tuple(ranges.shape) != (B, T, r):
+        raise ValueError(f"ranges must have shape {(B, T, r)}, got {tuple(ranges.shape)}")
+    boundary = _as_boundary(boundary, B, px_band.device)
+    if S is None:       # the last band row: one host read (give S to stay asynchronous)
+        S = int(ranges.max().item()) if ranges.numel() else 0
+    S = int(S)
+    if S < 0 or T < 1:
+        raise ValueError(f"S={S} must not be negative and T={T} must be positive")
+    if not band_multiblank_supported(T, S, r, len(durs)):
+        raise ValueError(f"the band recursion does not cover T={T}, S={S}, r={r} (r <= 15)")
+    return _BandMultiblankRecursion.apply(px_band, py_band, ranges, S, durs, boundary)
+
+
 def mutual_information_viterbi(px: torch.Tensor, py: torch.Tensor,
                                boundary: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor]:
     """Best-path (Viterbi) alignment over the lattice of ``mutual_information_recursion`` (MI355X addition, no reference

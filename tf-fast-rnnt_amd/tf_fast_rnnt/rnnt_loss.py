@@ -33,8 +33,8 @@ import weakref
 import torch
 
 from . import _lib
-from .mutual_information import (_as_boundary, _ptr, _require_gpu, _stream_ptr, band_tdt_forward_backward,
-                                 band_tdt_supported, cummin, mb_forward_backward, mi_forward_backward,
+from .mutual_information import (_as_boundary, _ptr, _require_gpu, _stream_ptr, band_multiblank_forward_backward,
+                                 band_multiblank_supported, band_tdt_forward_backward, band_tdt_supported, cummin, mb_forward_backward, mi_forward_backward,
                                  mutual_information_recursion, mutual_information_viterbi, mutual_information_viterbi_tdt, tdt_forward_backward)
 
 _NEG_INF = float("-inf")
@@ -1043,14 +1043,28 @@ def _mb_builder_fwd(x, symbols, ranges, boundary, blank, ids, durs, D, sigma, de
     return lse, px, py
 
 
-def _mb_builder_bwd(x, symbols, ranges, boundary, blank, ids, durs, D, lse, gpx, gpy, scale, stride, mul):
+def _mb_band_builder_fwd(x, symbols, ranges, boundary, blank, ids, durs, D, sigma, delay_penalty):
+    """_mb_builder_fwd with band-shaped px_band [B,T,r] / py_band [B,D,T,r]: no lattice is written."""
+    B, T, r, C = x.shape
+    S = symbols.shape[1]
+    lse = torch.empty((B, T, r), dtype=torch.float32, device=x.device)
+    pxb = torch.empty((B, T, r), dtype=torch.float32, device=x.device)
+    pyb = torch.empty((B, D, T, r), dtype=torch.float32, device=x.device)
+    with torch.cuda.device(x.device):
+        _lib.call("ftr_multiblank_pruned_band_fwd_f32", _ptr(x), _ptr(symbols), _ptr(ranges), _ptr(boundary), blank, ids,
+                  durs, D, float(sigma), float(delay_penalty), _ptr(lse), _ptr(pxb), _ptr(pyb), B, T, S, C, r, _stream_ptr(x))
+    return lse, pxb, pyb
+
+
+def _mb_builder_bwd(x, symbols, ranges, boundary, blank, ids, durs, D, lse, gpx, gpy, scale, stride, mul, band=False):
+    """``band``: gpx / gpy are band-shaped occupancies [B,T,r] / [B,D,T,r], else the full-size lattices."""
     B, T, r, C = x.shape
     S = symbols.shape[1]
     g = torch.empty_like(x)
     with torch.cuda.device(x.device):
-        _lib.call("ftr_multiblank_pruned_logprobs_bwd_scaled_f32", _ptr(x), _ptr(symbols), _ptr(ranges), _ptr(boundary),
-                  blank, ids, durs, D, _ptr(lse), _ptr(gpx), _ptr(gpy), _ptr(scale), stride, mul, _ptr(g), B, T, S, C, r,
-                  _stream_ptr(x))
+        _lib.call("ftr_multiblank_pruned_band_bwd_scaled_f32" if band else "ftr_multiblank_pruned_logprobs_bwd_scaled_f32",
+                  _ptr(x), _ptr(symbols), _ptr(ranges), _ptr(boundary), blank, ids, durs, D, _ptr(lse), _ptr(gpx), _ptr(gpy),
+                  _ptr(scale), stride, mul, _ptr(g), B, T, S, C, r, _stream_ptr(x))
     return g
 
 
@@ -1075,19 +1089,39 @@ class _MultiblankLogprobs(torch.autograd.Function):
         return g, None, None, None, None, None, None
 
 
+def _mb_band_path_ok(ranges, boundary, T: int, S: int, r: int, D: int) -> bool:
+    """_band_path_ok for the multi-blank loss: the same rule and the same FTR_PRUNED_ROUTE knob, the multi-blank domain
+    of csrc/mi_band_tdt.hip."""
+    if os.environ.get("FTR_PRUNED_ROUTE") == "lattice":
+        return False
+    return band_multiblank_supported(T, S, r, D) and _is_band(ranges, boundary)
+
+
 class _MultiblankLoss(torch.autograd.Function):
-    """rnnt_loss_multiblank_pruned with the whole chain native, as _PrunedLoss's lattice route: logsumexp + gather ->
-    multi-blank recursion forward and backward on the full-size lattices -> in backward() one streaming kernel turns the
-    occupancies * upstream gradient into d loss / d logits."""
+    """rnnt_loss_multiblank_pruned with the whole chain native, as _PrunedLoss.
+
+    Band path (the ranges are a band, r <= 15): logsumexp + band gather -> multi-blank recursion, both directions and the
+    occupancies, on the band [B,T,r] / [B,D,T,r] (ftr_mutual_information_band_multiblank_f32; no full-size lattice exists)
+    -> in backward() one streaming kernel turns the band-shaped occupancies * upstream gradient into d loss / d logits.
+    Lattice path (any other ranges, FTR_PRUNED_ROUTE=lattice): logsumexp + band->lattice, multi-blank recursion forward
+    and backward on the full-size lattices, the same streaming kernel fed from the lattices."""
 
     @staticmethod
     def forward(ctx, logits, symbols, ranges, termination_symbol, big_blanks, boundary, sigma, delay_penalty, code):
         x = logits.detach().contiguous()
         need = logits.requires_grad
         ids, durs, dt = _big_blank_args(big_blanks, termination_symbol, x.shape[3])
-        lse, px, py = _mb_builder_fwd(x, symbols, ranges, boundary, int(termination_symbol), ids, durs, len(dt), sigma,
-                                      delay_penalty)
-        ans, px_grad, py_grad = mb_forward_backward(px, py, dt, boundary, need)
+        B, T, r, _ = x.shape
+        S = symbols.shape[1]
+        ctx.band = _mb_band_path_ok(ranges, boundary, T, S, r, len(dt))
+        if ctx.band:
+            lse, px, py = _mb_band_builder_fwd(x, symbols, ranges, boundary, int(termination_symbol), ids, durs, len(dt), sigma,
+                                               delay_penalty)
+            ans, px_grad, py_grad = band_multiblank_forward_backward(px, py, ranges, S, dt, boundary, need)
+        else:
+            lse, px, py = _mb_builder_fwd(x, symbols, ranges, boundary, int(termination_symbol), ids, durs, len(dt), sigma,
+                                          delay_penalty)
+            ans, px_grad, py_grad = mb_forward_backward(px, py, dt, boundary, need)
         del px, py
         if need:
             ctx.save_for_backward(x, symbols, ranges, lse, px_grad, py_grad, boundary)
@@ -1099,7 +1133,8 @@ class _MultiblankLoss(torch.autograd.Function):
         x, symbols, ranges, lse, px_grad, py_grad, boundary = ctx.saved_tensors
         blank, ids, durs, D, code = ctx.meta
         scale, stride, mul = _upstream_scale(g_loss, code, x.shape[0])
-        g = _mb_builder_bwd(x, symbols, ranges, boundary, blank, ids, durs, D, lse, px_grad, py_grad, scale, stride, mul)
+        g = _mb_builder_bwd(x, symbols, ranges, boundary, blank, ids, durs, D, lse, px_grad, py_grad, scale, stride, mul,
+                            ctx.band)
         return g, None, None, None, None, None, None, None, None
 
 
@@ -1166,7 +1201,9 @@ def rnnt_loss_multiblank_pruned(
     ``get_rnnt_logprobs_multiblank_pruned`` (with the delay penalty on px as in ``rnnt_loss_pruned``) through
     ``mutual_information_recursion_multiblank``, negated and reduced.  Prune ranges come from the ordinary
     ``rnnt_loss_simple``, as for ``hat_loss_pruned``.  Only ``rnnt_type="regular"`` exists; anything else raises
-    ValueError.  With ``big_blanks=()`` and ``sigma=0`` this is ``rnnt_loss_pruned`` on the full-size lattices."""
+    ValueError.  With ``big_blanks=()`` and ``sigma=0`` this is ``rnnt_loss_pruned``.
+    When ``ranges`` are a band with ``s_range <= 15`` (the rule of ``rnnt_loss_pruned``, ``FTR_PRUNED_ROUTE=lattice``
+    overrides it) the same loss is computed on the band itself and no full-size lattice is allocated."""
     if rnnt_type != "regular":
         raise ValueError(f"the multi-blank loss is defined for rnnt_type 'regular' only, given {rnnt_type}")
     code = _reduction_code(reduction)
