@@ -1165,6 +1165,40 @@ int ftr_mutual_information_band_multiblank_f32(const float* px_band, const float
                             T, S, r, stream_of(stream));
 }
 
+// ---- include/ftr_band_viterbi.h: best-path alignment on the pruned band itself (csrc/mi_band_viterbi.hip).  The move
+// lists are those of ftr_mutual_information_viterbi_tdt_f32: up to 8 of a kind, a blank may advance 32 frames.
+int ftr_mutual_information_band_viterbi_supported(int T, int S, int r, int N, int Ny) {
+  return mi_band_viterbi_supported(T, S, r, N, Ny);
+}
+size_t ftr_mutual_information_band_viterbi_workspace_bytes(int B, int T, int S, int r, int N, int Ny) {
+  return mi_band_viterbi_workspace_bytes(B, T, S, r, N, Ny);
+}
+
+int ftr_mutual_information_band_viterbi_f32(const float* px_band, const float* py_band, const int32_t* ranges,
+                                            const int32_t* boundary, const int32_t* token_durations, int N,
+                                            const int32_t* blank_durations, int Ny, void* workspace, size_t workspace_bytes,
+                                            float* score, int32_t* frames, int32_t* durations, int32_t* blank_steps, int B,
+                                            int T, int S, int r, void* stream) {
+  const char* what = "mutual_information_band_viterbi";
+  clear_error();
+  FTR_TRY(tdt_check_list(what, "token_durations", token_durations, N, 8, 0));
+  FTR_TRY(tdt_check_list(what, "blank_durations", blank_durations, Ny, 8, 1, 32));
+  FTR_TRY(check_sizes(what, B >= 0 && T >= 1 && S >= 0 && r >= 1));
+  if (!mi_band_viterbi_supported(T, S, r, N, Ny)) {
+    set_error("%s: T=%d S=%d r=%d N=%d Ny=%d is outside the kernel's domain (r <= 15, N + Ny <= 9)", what, T, S, r, N, Ny);
+    return FTR_ERR_UNSUPPORTED;
+  }
+  if (B == 0) return FTR_OK;
+  FTR_TRY(check_ws_size(what, workspace_bytes, mi_band_viterbi_workspace_bytes(B, T, S, r, N, Ny), "bytes"));
+  FTR_REQUIRE(px_band && py_band && ranges && workspace && score && blank_steps,
+              "%s: null px_band / py_band / ranges / workspace / score / blank_steps", what);
+  FTR_REQUIRE((frames && durations) || S == 0, "%s: null frames / durations", what);
+  FTR_TRY(check_ws_aligned(what, workspace));
+  FTR_TRY(device_ok());
+  return mi_band_viterbi(px_band, py_band, ranges, boundary, token_durations, N, blank_durations, Ny, workspace, workspace_bytes,
+                         score, frames, durations, blank_steps, B, T, S, r, stream_of(stream));
+}
+
 int ftr_multiblank_pruned_band_fwd_f32(const float* logits, const int32_t* symbols, const int32_t* ranges,
                                        const int32_t* boundary, int termination_symbol, const int32_t* big_blank_ids,
                                        const int32_t* durations, int D, double sigma, double delay_penalty, float* lse,

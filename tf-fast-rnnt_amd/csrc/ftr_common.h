@@ -8,6 +8,7 @@
 #include "../../include/ftr_fused.h"
 #include "../../include/ftr_band_tdt.h"
 #include "../../include/ftr_band_multiblank.h"
+#include "../../include/ftr_band_viterbi.h"
 
 namespace ftr {
 
@@ -243,6 +244,10 @@ int multiblank_band_bwd(const float* logits, const int32_t* symbols, const int32
 // best-path alignment over the TDT / multi-blank lattice: csrc/mi_viterbi_tdt.hip; the duration lists are host arrays
 size_t mi_viterbi_tdt_workspace_bytes(int B, int S, int T);
 int mi_viterbi_tdt(const float* px, const float* py, const int32_t* boundary, const int32_t* token_durations, int Dx, const int32_t* blank_durations, int Dy, void* ws, size_t ws_bytes, float* score, int32_t* frames, int32_t* durations, int32_t* blank_steps, int B, int S, int T, hipStream_t st);
+// best-path alignment on the pruned band (include/ftr_band_viterbi.h): csrc/mi_band_viterbi.hip; the duration lists are host arrays
+int mi_band_viterbi_supported(int T, int S, int r, int N, int Ny);
+size_t mi_band_viterbi_workspace_bytes(int B, int T, int S, int r, int N, int Ny);
+int mi_band_viterbi(const float* pxb, const float* pyb, const int32_t* ranges, const int32_t* boundary, const int32_t* token_durations, int N, const int32_t* blank_durations, int Ny, void* ws, size_t ws_bytes, float* score, int32_t* frames, int32_t* durations, int32_t* blank_steps, int B, int T, int S, int r, hipStream_t st);
 int cummin_i32(const int32_t* in, int32_t* out, int rows, int cols, hipStream_t st);
 int prune_ranges(const float* px_grad, const float* py_grad, const int32_t* boundary, int32_t* ranges, int32_t* s_begin, int B, int S, int T, int T1, int r, hipStream_t st);
 int do_pruning(const float* am, const float* lm, const int32_t* ranges, float* am_p, float* lm_p, int B, int T, int S1, int C, int r, hipStream_t st);

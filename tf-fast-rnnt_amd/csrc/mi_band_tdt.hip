@@ -33,19 +33,11 @@
 // point admits is a BandMoveDomain (ftr_common.h) that the host functions take as a parameter: (5, 5, 16) for TDT, and
 // (1, 8, 32) for the multi-blank recursion (include/ftr_band_multiblank.h), which is the same chain with one token move
 // of duration 0 and D <= 8 blank moves of durations up to 32: M = D + 1 <= 9, DEP = 64 at duration 32.
-#include "mi_band_common.h"
+#include "mi_band_tdt_common.h"
 #include "mi_rowlane.h"   // exp_of
 
 namespace ftr {
 namespace {
-
-constexpr int kTdtThreads = 256;
-constexpr int kTdtMaxMoves = 10;   // TDT: N <= 5 token moves and Ny <= 5 blank moves; multi-blank: 1 + 8
-constexpr int kTdtMaxDep = 64;     // ring steps the static LDS holds (a duration of 32 needs all of them)
-constexpr int TCH = 4;             // steps per operand fetch
-
-// moves 0 .. Dx-1 are the token moves (px_band planes), Dx .. M-1 the blank moves (py_band planes)
-struct BandMoves { int dur[kTdtMaxMoves]; int Dx, M; };
 
 // the workspace: doubles first -- head [B][2] = (ans, flat: 1 when the utterance is answered without occupancies) and
 // P [B][2][steps * LANES] (p of chain A's slots, q of chain B's) -- then the floats O [B][2][(steps + TCH) * M * LANES]
@@ -59,21 +51,6 @@ inline TdtLayout tdt_layout(int B, int T, int S, int lanes, int M) {
   L.o_off_floats = 2 * (L.p_off + (size_t)B * 2 * L.p_per);
   L.total_floats = L.o_off_floats + (size_t)B * 2 * L.o_per;
   return L;
-}
-
-// is (s,t) a cell of the walk?  (rg: the utterance's ranges)
-template <int LANES>
-__device__ __forceinline__ bool tdt_cell(const BandGeom<false, LANES>& g, const int32_t* __restrict__ rg, int s, int t) {
-  if (s < g.sb || s > g.se || t < g.tb || t > g.te) return false;
-  if (t == g.te) return s == g.se;
-  return g.in_band(s, t, rg[(size_t)t * g.r]);
-}
-// operand of move m at the frame cell (s,t)
-template <int LANES>
-__device__ __forceinline__ float tdt_operand(const BandGeom<false, LANES>& g, const int32_t* __restrict__ rg, const float* __restrict__ pxu,
-                                             const float* __restrict__ pyu, size_t plane, int Dx, int m, int s, int t) {
-  const float* src = m < Dx ? pxu + (size_t)m * plane : pyu + (size_t)(m - Dx) * plane;
-  return src[(size_t)t * g.r + (s - rg[(size_t)t * g.r])];
 }
 
 template <int LANES, int M>
@@ -93,13 +70,9 @@ __global__ void __launch_bounds__(kTdtThreads) band_tdt_chain_kernel(
   }
   const int32_t* rg = ranges + (size_t)b * T * r;
   const int sb = u.bd.sb, tb = u.bd.tb, se = u.bd.se, te = u.bd.te, D = u.D;
-  {
-    int bad = 0;
-    for (int t = tb + 1 + tid; t < te; t += kTdtThreads) bad |= (rg[(size_t)t * r] < rg[(size_t)(t - 1) * r]);
-    if (__syncthreads_or(bad)) {
-      if (!isB && tid == 0) { ans[b] = __builtin_nanf(""); head[0] = __builtin_nan(""); head[1] = 1.0; }
-      return;
-    }
+  if (tdt_band_start_decreases(rg, tb, te, r, tid)) {
+    if (!isB && tid == 0) { ans[b] = __builtin_nanf(""); head[0] = __builtin_nan(""); head[1] = 1.0; }
+    return;
   }
   const BandGeom<false, LANES> g(r, u.bd, 0, 0, 0);
   const size_t plane = (size_t)T * r;
@@ -119,23 +92,8 @@ __global__ void __launch_bounds__(kTdtThreads) band_tdt_chain_kernel(
   const int ncell = (te - tb) * r + 1;                                // the frames' band rows, and the end cell
   for (int i = tid; i < ncell; i += kTdtThreads) {
     int s, t;
-    if (i == ncell - 1) { s = se; t = te; }
-    else { t = tb + i / r; s = rg[(size_t)t * r] + (i - (t - tb) * r); }
-    if (s < sb || s > se) continue;
-    const int slot = isB ? (g.dgB(s, t) * M) * LANES + g.laneB(s) : (g.dgA(s, t) * M) * LANES + g.laneA(s);
-#pragma unroll
-    for (int m = 0; m < M; ++m) {
-      const int ds = m < Dx ? 1 : 0, d = mv.dur[m];
-      float v = NEGF;
-      if (isB) {
-        if (t < te && tdt_cell(g, rg, s + ds, t + d)) v = tdt_operand(g, rg, pxu, pyu, plane, Dx, m, s, t);
-        if (t == te && m == Dx) v = 0.0f;
-      } else {
-        if (t - d < te && tdt_cell(g, rg, s - ds, t - d)) v = tdt_operand(g, rg, pxu, pyu, plane, Dx, m, s - ds, t - d);
-        if (s == sb && t == tb && m == Dx) v = 0.0f;
-      }
-      O[slot + m * LANES] = v;
-    }
+    if (!tdt_nth_cell(rg, sb, tb, se, te, r, i, s, t)) continue;
+    tdt_scatter_cell<LANES, M>(g, rg, pxu, pyu, plane, mv, isB, O, s, t);
   }
   __syncthreads();
   if (tid >= LANES) return;
@@ -222,22 +180,6 @@ __global__ void __launch_bounds__(256) band_tdt_occupancy_kernel(
     }
     (m < Dx ? gxu + (size_t)m * plane : gyu + (size_t)(m - Dx) * plane)[cell] = occ;
   }
-}
-
-BandMoves make_band_moves(const int32_t* tok, int N, const int32_t* blk, int Ny) {
-  BandMoves mv;
-  for (int m = 0; m < kTdtMaxMoves; ++m) mv.dur[m] = m < N ? tok[m] : (m < N + Ny ? blk[m - N] : 1);
-  mv.Dx = N; mv.M = N + Ny;
-  return mv;
-}
-// the power of two above the largest step offset of a move (a token of duration e reads e + 1 steps back)
-int ring_depth_for(int far) {
-  int dep = 2;
-  while (dep <= far) dep *= 2;
-  return dep;
-}
-int band_tdt_ring_depth(const int32_t* tok, int N, const int32_t* blk, int Ny) {
-  return ring_depth_for((tok[N - 1] + 1 > blk[Ny - 1]) ? tok[N - 1] + 1 : blk[Ny - 1]);
 }
 
 }  // namespace

@@ -140,12 +140,19 @@ _BAND_MULTIBLANK_SIGNATURES = {
     "ftr_multiblank_pruned_band_fwd_f32": (_i, [_c_fp, _c_ip, _c_ip, _c_ip, _i, _c_hi, _c_hi, _i, ctypes.c_double, ctypes.c_double, _c_fp, _c_fp, _c_fp, _i, _i, _i, _i, _i, _c_st]),
     "ftr_multiblank_pruned_band_bwd_scaled_f32": (_i, [_c_fp, _c_ip, _c_ip, _c_ip, _i, _c_hi, _c_hi, _i, _c_fp, _c_fp, _c_fp, _c_fp, _i, _f, _c_fp, _i, _i, _i, _i, _i, _c_st]),
 }
+# include/ftr_band_viterbi.h, best-path alignment on the pruned band itself: the domain and workspace queries and the entry
+_BAND_VITERBI_SIGNATURES = {
+    "ftr_mutual_information_band_viterbi_supported": (_i, [_i, _i, _i, _i, _i]),
+    "ftr_mutual_information_band_viterbi_workspace_bytes": (ctypes.c_size_t, [_i, _i, _i, _i, _i, _i]),
+    "ftr_mutual_information_band_viterbi_f32": (_i, [_c_fp, _c_fp, _c_ip, _c_ip, _c_hi, _i, _c_hi, _i, ctypes.c_void_p, ctypes.c_size_t, _c_fp, _c_ip, _c_ip, _c_ip, _i, _i, _i, _i, _c_st]),
+}
 EXPORTED_SYMBOLS = tuple(_SIGNATURES)            # the symbols of include/ftr.h
 LOWP_SYMBOLS = tuple(_LOWP_SIGNATURES)           # those of include/ftr_lowp.h
 KD_SYMBOLS = tuple(_KD_SIGNATURES)               # those of include/ftr_kd.h
 FUSED_SYMBOLS = tuple(_FUSED_SIGNATURES)         # those of include/ftr_fused.h
 BAND_TDT_SYMBOLS = tuple(_BAND_TDT_SIGNATURES)   # those of include/ftr_band_tdt.h
 BAND_MULTIBLANK_SYMBOLS = tuple(_BAND_MULTIBLANK_SIGNATURES)   # those of include/ftr_band_multiblank.h
+BAND_VITERBI_SYMBOLS = tuple(_BAND_VITERBI_SIGNATURES)   # those of include/ftr_band_viterbi.h
 band_tdt_recursions = 0   # how many times the band-native TDT recursion has been launched from Python (tests read it)
 band_multiblank_recursions = 0   # ... and the band-native multi-blank recursion, likewise
 FTR_KD_FULL, FTR_KD_COLLAPSED = 0, 1             # include/ftr_kd.h: the `mode` of the kd entry points
@@ -164,7 +171,7 @@ def lib() -> ctypes.CDLL:
                 "g.build()' or make -C tf-fast-rnnt_amd/csrc).  tf_fast_rnnt has no CPU fallback.")
         handle = ctypes.CDLL(LIB_PATH)
         for name, (restype, argtypes) in {**_SIGNATURES, **_LOWP_SIGNATURES, **_KD_SIGNATURES, **_FUSED_SIGNATURES,
-                                            **_BAND_TDT_SIGNATURES, **_BAND_MULTIBLANK_SIGNATURES}.items():
+                                            **_BAND_TDT_SIGNATURES, **_BAND_MULTIBLANK_SIGNATURES, **_BAND_VITERBI_SIGNATURES}.items():
             fn = getattr(handle, name)   # AttributeError here = header/library mismatch
             fn.restype = restype
             fn.argtypes = argtypes

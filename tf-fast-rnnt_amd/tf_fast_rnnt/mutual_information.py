@@ -681,6 +681,73 @@ def mutual_information_viterbi_tdt(px: torch.Tensor, py: torch.Tensor, token_dur
     return score, frames, durations, blank_steps
 
 
+def band_viterbi_supported(T: int, S: int, r: int, N: int, Ny: int) -> bool:
+    """Does the band-native alignment (csrc/mi_band_viterbi.hip) cover these sizes?"""
+    return _lib.lib().ftr_mutual_information_band_viterbi_supported(int(T), int(S), int(r), int(N), int(Ny)) != 0
+
+
+def mutual_information_viterbi_tdt_band(px_band: torch.Tensor, py_band: torch.Tensor, ranges: torch.Tensor, token_durations,
+                                        blank_durations, boundary: Optional[torch.Tensor] = None, S: Optional[int] = None
+                                        ) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]:
+    """``mutual_information_viterbi_tdt`` on the pruned band itself (MI355X addition; ftr_mutual_information_band_viterbi_f32,
+    csrc/mi_band_viterbi.hip): nothing of size S*T is allocated or touched, one launch.
+
+    px_band: [B,N,T,r] and py_band: [B,Ny,T,r], float32, ranges: int32 [B,T,r], a band with r <= 15, and S as
+    ``mutual_information_recursion_tdt_band`` takes them (S omitted: ``ranges.max()``, one host read).  token_durations:
+    N >= 1 strictly increasing ints in 0..16; blank_durations: Ny >= 1 strictly increasing ints in 1..32; N + Ny <= 9 (the
+    domain of ``mutual_information_viterbi_tdt``).  boundary: int32 or int64 [B,4], or None.
+
+    The cells are the band cells of the frames ``t_begin <= t < t_end`` inside the rectangle and the end cell; a move
+    exists iff its source and its destination are such cells; its candidate is ``p[src] + operand`` in float32, -inf when
+    it does not exist, and the select rule is that of ``mutual_information_viterbi_tdt`` (a NaN propagates, a tie goes to
+    the lowest-index move).  Returns ``(score, frames, durations, blank_steps)`` with the shapes [B], [B,S], [B,S], [B,T]
+    and the conventions of that function; a band whose start decreases inside the rectangle gives score NaN and -1
+    everywhere.  Where the operands obey the builders' -inf rules, all four equal ``mutual_information_viterbi_tdt`` on
+    the band scattered into lattices of -inf, bit for bit -- for rectangles without NaN: on the lattice a NaN also
+    travels through cells outside the band, here only along moves that exist.  Not differentiable: the outputs are
+    detached.  Asynchronous, no host read when ``S`` is given (capturable)."""
+    import ctypes
+    _require_gpu(px_band, "px_band"); _require_gpu(py_band, "py_band")
+    if px_band.dtype != torch.float32 or py_band.dtype != torch.float32:
+        raise TypeError("px_band and py_band must be float32")
+    tok, blk = _check_tdt_moves(token_durations, blank_durations, 32, max_moves=9)
+    if px_band.dim() != 4 or py_band.dim() != 4:
+        raise ValueError("px_band must be [B,N,T,r] and py_band [B,Ny,T,r]")
+    B, _, T, r = px_band.shape
+    N, Ny = len(tok), len(blk)
+    if tuple(px_band.shape) != (B, N, T, r) or tuple(py_band.shape) != (B, Ny, T, r):
+        raise ValueError(f"px_band must have shape {(B, N, T, r)} and py_band {(B, Ny, T, r)}, got "
+                         f"{tuple(px_band.shape)} and {tuple(py_band.shape)}")
+    if py_band.device != px_band.device:
+        raise ValueError("px_band and py_band must be on the same device")
+    px_band = px_band.detach().contiguous(); py_band = py_band.detach().contiguous()
+    ranges = torch.as_tensor(ranges, device=px_band.device).to(torch.int32).contiguous()
+    if tuple(ranges.shape) != (B, T, r):
+        raise ValueError(f"ranges must have shape {(B, T, r)}, got {tuple(ranges.shape)}")
+    boundary = _as_boundary(boundary, B, px_band.device)
+    if S is None:       # the last band row: one host read (give S to stay asynchronous)
+        S = int(ranges.max().item()) if ranges.numel() else 0
+    S = int(S)
+    if S < 0 or T < 1:
+        raise ValueError(f"S={S} must not be negative and T={T} must be positive")
+    if not band_viterbi_supported(T, S, r, N, Ny):
+        raise ValueError(f"the band alignment does not cover T={T}, S={S}, r={r} (r <= 15)")
+    tok_arr = (ctypes.c_int32 * N)(*tok)        # read by the launch itself: no device copy, no host synchronisation
+    blk_arr = (ctypes.c_int32 * Ny)(*blk)
+    L = _lib.lib()
+    with torch.cuda.device(px_band.device):
+        nbytes = L.ftr_mutual_information_band_viterbi_workspace_bytes(B, T, S, r, N, Ny)
+        ws = torch.empty(((max(nbytes, 8) + 7) // 8,), dtype=torch.int64, device=px_band.device)
+        score = torch.empty((B,), dtype=torch.float32, device=px_band.device)
+        frames = torch.empty((B, S), dtype=torch.int32, device=px_band.device)
+        durations = torch.empty((B, S), dtype=torch.int32, device=px_band.device)
+        blank_steps = torch.empty((B, T), dtype=torch.int32, device=px_band.device)
+        _lib.call("ftr_mutual_information_band_viterbi_f32", _ptr(px_band), _ptr(py_band), _ptr(ranges), _ptr(boundary), tok_arr, N,
+                  blk_arr, Ny, _ptr(ws), nbytes, _ptr(score), _ptr(frames), _ptr(durations), _ptr(blank_steps), B, T, S, r,
+                  _stream_ptr(px_band))
+    return score, frames, durations, blank_steps
+
+
 def cummin(x: torch.Tensor) -> torch.Tensor:
     """Op "Cummin" (__init__.py:151-152; tf_fast_rnnt_op.cc:135-165): inclusive prefix-min along the
     last axis of an int32 [rows, cols] matrix."""

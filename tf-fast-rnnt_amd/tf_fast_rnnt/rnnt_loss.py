@@ -34,8 +34,9 @@ import torch
 
 from . import _lib
 from .mutual_information import (_as_boundary, _ptr, _require_gpu, _stream_ptr, band_multiblank_forward_backward,
-                                 band_multiblank_supported, band_tdt_forward_backward, band_tdt_supported, cummin, mb_forward_backward, mi_forward_backward,
-                                 mutual_information_recursion, mutual_information_viterbi, mutual_information_viterbi_tdt, tdt_forward_backward)
+                                 band_multiblank_supported, band_tdt_forward_backward, band_tdt_supported, band_viterbi_supported, cummin, mb_forward_backward, mi_forward_backward,
+                                 mutual_information_recursion, mutual_information_viterbi, mutual_information_viterbi_tdt, mutual_information_viterbi_tdt_band,
+                                 tdt_forward_backward)
 
 _NEG_INF = float("-inf")
 # tf.math.nextafter(0., 1.) : smallest positive float32 subnormal (rnnt_loss.py:181,1272,1280)
@@ -700,10 +701,27 @@ def rnnt_alignment_pruned(
     ``mutual_information_viterbi``.  Returns ``(score [B] float32, frames [B,S] int32)``, detached; see
     ``mutual_information_viterbi`` for their meaning (``frames[b,s]`` = the frame that emits ``symbols[b,s]``).
     Every step runs on the device with no host read, so the call can be captured into a graph.  For unpruned joiner
-    logits use ``mutual_information_viterbi(*get_rnnt_logprobs_joint(...))``."""
+    logits use ``mutual_information_viterbi(*get_rnnt_logprobs_joint(...))``.
+
+    For ``rnnt_type="regular"``, when ``ranges`` are a band with ``s_range <= 15`` (the rule of ``rnnt_loss_pruned``,
+    ``FTR_PRUNED_ROUTE=lattice`` included), no lattice is built: the band builder of the loss feeds
+    ``mutual_information_viterbi_tdt_band`` with moves (0,) / (1,), which returns the same bits (see there for the one
+    deviation, the way a NaN travels).  Everything else takes the lattice route."""
     _check_type(rnnt_type)
     with torch.no_grad():
         symbols, ranges, boundary = _pruned_inputs(logits, symbols, ranges, boundary, lowp=True)
+        B, T, r, C = logits.shape
+        S = symbols.shape[1]
+        if rnnt_type == "regular" and _align_band_path_ok(ranges, boundary, T, S, r, 1, 1):
+            x = logits.detach().contiguous()
+            lse = torch.empty((B, T, r), dtype=torch.float32, device=x.device)
+            pxb = torch.empty((B, 1, T, r), dtype=torch.float32, device=x.device)
+            pyb = torch.empty((B, 1, T, r), dtype=torch.float32, device=x.device)
+            with torch.cuda.device(x.device):
+                _pruned_call("pruned_band_fwd", False, x, (_ptr(symbols), _ptr(ranges), _ptr(boundary), int(termination_symbol), 0.0,
+                             _ptr(lse), _ptr(pxb), _ptr(pyb), B, T, S, C, r, 0), (_stream_ptr(x),))
+            score, frames, _, _ = mutual_information_viterbi_tdt_band(pxb, pyb, ranges, (0,), (1,), boundary, S=S)
+            return score, frames
         _, px, py = _pruned_builder_fwd(logits.detach().contiguous(), symbols, ranges, boundary, termination_symbol, 0.0,
                                         rnnt_type != "regular", False)
         if rnnt_type == "constrained":
@@ -771,6 +789,14 @@ def _is_band(ranges: torch.Tensor, boundary) -> bool:
     ok = _band_check(ranges, boundary)
     ranges._ftr_band_under = (ranges._version, weakref.ref(boundary), boundary._version, ok)
     return ok
+
+
+def _align_band_path_ok(ranges, boundary, T: int, S: int, r: int, N: int, Ny: int) -> bool:
+    """_band_path_ok for the three alignment wrappers: the same rule and the same FTR_PRUNED_ROUTE knob, the domain of
+    csrc/mi_band_viterbi.hip."""
+    if os.environ.get("FTR_PRUNED_ROUTE") == "lattice":
+        return False
+    return band_viterbi_supported(T, S, r, N, Ny) and _is_band(ranges, boundary)
 
 
 def _band_path_ok(ranges, boundary, T: int, S: int, r: int) -> bool:
@@ -1481,11 +1507,21 @@ def rnnt_alignment_tdt_pruned(
     a path inside the band only when ``durations`` contains 0 and 1; an utterance without one gets score -inf and -1
     everywhere.  Every step runs on the device with no host read, so the call can be captured into a graph.  For
     unpruned joiner logits use
-    ``mutual_information_viterbi_tdt(*get_rnnt_logprobs_tdt_joint(...), durations, positive durations, boundary)``."""
+    ``mutual_information_viterbi_tdt(*get_rnnt_logprobs_tdt_joint(...), durations, positive durations, boundary)``.
+
+    When ``ranges`` are a band with ``s_range <= 15`` (the rule of ``rnnt_loss_tdt_pruned``, ``FTR_PRUNED_ROUTE=lattice``
+    included) and the moves number at most nine, no lattice is built: the band builder of the loss feeds
+    ``mutual_information_viterbi_tdt_band``, which returns the same bits in memory and time of order T * s_range."""
     with torch.no_grad():
         symbols, ranges, boundary = _pruned_inputs(logits, symbols, ranges, boundary)
         arr, durs, blank_durs, C = _tdt_args(durations, termination_symbol, logits.shape[3])
         x = logits.detach().contiguous()
+        B, T, r, _ = x.shape
+        S = symbols.shape[1]
+        if _align_band_path_ok(ranges, boundary, T, S, r, len(durs), len(blank_durs)):
+            _, _, pxb, pyb = _tdt_band_builder_fwd(x, symbols, ranges, boundary, int(termination_symbol), arr, durs, blank_durs, C,
+                                                   _check_sigma(sigma), 0.0)
+            return mutual_information_viterbi_tdt_band(pxb, pyb, ranges, durs, blank_durs, boundary, S=S)
         _, _, px, py = _tdt_builder_fwd(x, symbols, ranges, boundary, int(termination_symbol), arr, durs, blank_durs, C,
                                         _check_sigma(sigma), 0.0)
         return mutual_information_viterbi_tdt(px, py, durs, blank_durs, boundary)
@@ -1505,11 +1541,18 @@ def rnnt_alignment_multiblank_pruned(
     blank durations ``(1, d_1, ...)``.  Returns ``(score, frames, durations, blank_steps)`` as
     ``rnnt_alignment_tdt_pruned`` does; ``durations`` is 0 on every valid row (a symbol stays on its frame) and
     ``blank_steps[b,t]`` tells which blank, the standard one (1) or a big one (its duration), left frame t.  No host
-    read; capturable."""
+    read; capturable.  Band ranges with ``s_range <= 15`` take the band route of ``rnnt_alignment_tdt_pruned`` (the band
+    builder of ``rnnt_loss_multiblank_pruned``, then ``mutual_information_viterbi_tdt_band``): the same bits, no lattice."""
     with torch.no_grad():
         symbols, ranges, boundary = _pruned_inputs(logits, symbols, ranges, boundary)
         x = logits.detach().contiguous()
         ids, durs, dt = _big_blank_args(tuple(map(tuple, big_blanks)), termination_symbol, x.shape[3])
+        B, T, r, _ = x.shape
+        S = symbols.shape[1]
+        if _align_band_path_ok(ranges, boundary, T, S, r, 1, len(dt)):
+            _, pxb, pyb = _mb_band_builder_fwd(x, symbols, ranges, boundary, int(termination_symbol), ids, durs, len(dt),
+                                               _check_sigma(sigma), 0.0)
+            return mutual_information_viterbi_tdt_band(pxb.unsqueeze(1), pyb, ranges, (0,), dt, boundary, S=S)
         _, px, py = _mb_builder_fwd(x, symbols, ranges, boundary, int(termination_symbol), ids, durs, len(dt),
                                     _check_sigma(sigma), 0.0)
         return mutual_information_viterbi_tdt(px.unsqueeze(1), py, (0,), dt, boundary)
