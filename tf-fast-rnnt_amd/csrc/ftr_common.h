@@ -5,6 +5,7 @@
 #include <stdio.h>
 #include <stdarg.h>
 #include "../../include/ftr_kd.h"  // and, through it, ftr_lowp.h and ftr.h
+#include "../../include/ftr_prune_sum.h"
 #include "../../include/ftr_fused.h"
 #include "../../include/ftr_band_tdt.h"
 #include "../../include/ftr_band_multiblank.h"
@@ -103,6 +104,15 @@ __device__ __forceinline__ void store4(E* row, int i, f4 v) {
 #pragma unroll
   for (int e = 0; e < 4; ++e) h[e] = elem_from_float<E>(v[e]).bits;
   reinterpret_cast<h4*>(row)[i] = h;
+}
+// store4 as a non-temporal store: for streams far beyond any cache that the kernel does not read again
+__device__ __forceinline__ void store4_nt(float* row, int i, f4 v) { __builtin_nontemporal_store(v, reinterpret_cast<f4u*>(row) + i); }
+template <typename E>
+__device__ __forceinline__ void store4_nt(E* row, int i, f4 v) {
+  h4 h;
+#pragma unroll
+  for (int e = 0; e < 4; ++e) h[e] = elem_from_float<E>(v[e]).bits;
+  __builtin_nontemporal_store(h, reinterpret_cast<h4*>(row) + i);
 }
 
 // Per-utterance factor applied to incoming lattice gradients on the fly: (p ? p[b * stride] : 1) * mul.
@@ -254,6 +264,10 @@ int do_pruning(const float* am, const float* lm, const int32_t* ranges, float* a
 size_t do_pruning_bwd_workspace_bytes(int B, int T, int S1, int C, int r);
 int do_pruning_bwd_ws(const float* g_am_p, const float* g_lm_p, const int32_t* ranges, float* d_am, float* d_lm, int B, int T, int S1, int C, int r, void* ws, size_t ws_bytes, hipStream_t st);
 int do_pruning_bwd(const float* g_am_p, const float* g_lm_p, const int32_t* ranges, float* d_am, float* d_lm, int B, int T, int S1, int C, int r, hipStream_t st);
+// the gather fused with the joiner's addition (include/ftr_prune_sum.h); dtype: the element type of am / lm / out and of g / d_am / d_lm.
+// do_pruning_sum_bwd_ws takes the routes of do_pruning_bwd_ws with one g for both inputs, and its workspace
+int do_pruning_sum(const void* am, const void* lm, int dtype, const int32_t* ranges, void* out, int B, int T, int S1, int C, int r, hipStream_t st);
+int do_pruning_sum_bwd_ws(const void* g, int dtype, const int32_t* ranges, void* d_am, void* d_lm, int B, int T, int S1, int C, int r, void* ws, size_t ws_bytes, hipStream_t st);
 // hat != 0: the HAT normalisation (lse = non-blank normaliser Z, see pruned_logprobs.hip); hat == 0: the ordinary kernels
 // dtype: the element type of logits / glogits (FTR_DTYPE_*, validated by the caller: dtype_ok)
 int pruned_logprobs_fwd(const void* logits, int dtype, const int32_t* symbols, const int32_t* ranges, const int32_t* boundary, int blank, double delay_penalty, float* lse, float* px, float* py, int B, int T, int S, int C, int r, int modified, int hat, hipStream_t st);

@@ -7,6 +7,7 @@ from ._lib import FtrError, lib as _load_native          # noqa: F401
 from .mutual_information import cummin, mutual_information_recursion, mutual_information_viterbi   # the viterbi alignment: MI355X addition
 from .mutual_information import mutual_information_recursion_multiblank   # MI355X addition: multi-blank (big blank) lattice
 from .rnnt_loss import do_rnnt_pruning
+from .rnnt_loss import do_rnnt_pruning_sum                                     # MI355X addition: am + lm[ranges] fused, f32 / bf16 / fp16
 from .rnnt_loss import get_rnnt_logprobs
 from .rnnt_loss import get_rnnt_logprobs_joint
 from .rnnt_loss import get_rnnt_logprobs_pruned

@@ -108,6 +108,12 @@ _LOWP_SIGNATURES = {
     "ftr_pruned_band_fwd_dt": (_i, [_c_fp, _i, _c_ip, _c_ip, _c_ip, _i, ctypes.c_double, _c_fp, _c_fp, _c_fp, _i, _i, _i, _i, _i, _i, _i, _c_st]),
     "ftr_pruned_band_bwd_scaled_dt": (_i, [_c_fp, _i, _c_ip, _c_ip, _c_ip, _i, _c_fp, _c_fp, _c_fp, _c_fp, _i, _f, _c_fp, _i, _i, _i, _i, _i, _i, _i, _c_st]),
 }
+# include/ftr_prune_sum.h, the prune gather fused with the joiner's first addition: (am, lm, kind = FTR_DTYPE_*, ranges, out, ...)
+# and its backward (g_out, kind, ranges, d_am, d_lm, ..., workspace, workspace_bytes, stream)
+_PRUNE_SUM_SIGNATURES = {
+    "ftr_do_pruning_sum_dt": (_i, [_c_fp, _c_fp, _i, _c_ip, _c_fp, _i, _i, _i, _i, _i, _c_st]),
+    "ftr_do_pruning_sum_bwd_ws_dt": (_i, [_c_fp, _i, _c_ip, _c_fp, _c_fp, _i, _i, _i, _i, _i, ctypes.c_void_p, ctypes.c_size_t, _c_st]),
+}
 # include/ftr_kd.h, knowledge distillation on the pruned band: (logits, kind, teacher_logits, teacher_kind, symbols, ranges,
 # boundary, termination_symbol, temperature, mode = FTR_KD_*, ...)
 _KD_SIGNATURES = {
@@ -148,6 +154,7 @@ _BAND_VITERBI_SIGNATURES = {
 }
 EXPORTED_SYMBOLS = tuple(_SIGNATURES)            # the symbols of include/ftr.h
 LOWP_SYMBOLS = tuple(_LOWP_SIGNATURES)           # those of include/ftr_lowp.h
+PRUNE_SUM_SYMBOLS = tuple(_PRUNE_SUM_SIGNATURES) # those of include/ftr_prune_sum.h
 KD_SYMBOLS = tuple(_KD_SIGNATURES)               # those of include/ftr_kd.h
 FUSED_SYMBOLS = tuple(_FUSED_SIGNATURES)         # those of include/ftr_fused.h
 BAND_TDT_SYMBOLS = tuple(_BAND_TDT_SIGNATURES)   # those of include/ftr_band_tdt.h
@@ -170,7 +177,7 @@ def lib() -> ctypes.CDLL:
                 f"{LIB_PATH} is missing: build the HIP extension first (python -c 'import __graft_entry__ as g; "
                 "g.build()' or make -C tf-fast-rnnt_amd/csrc).  tf_fast_rnnt has no CPU fallback.")
         handle = ctypes.CDLL(LIB_PATH)
-        for name, (restype, argtypes) in {**_SIGNATURES, **_LOWP_SIGNATURES, **_KD_SIGNATURES, **_FUSED_SIGNATURES,
+        for name, (restype, argtypes) in {**_SIGNATURES, **_LOWP_SIGNATURES, **_PRUNE_SUM_SIGNATURES, **_KD_SIGNATURES, **_FUSED_SIGNATURES,
                                             **_BAND_TDT_SIGNATURES, **_BAND_MULTIBLANK_SIGNATURES, **_BAND_VITERBI_SIGNATURES}.items():
             fn = getattr(handle, name)   # AttributeError here = header/library mismatch
             fn.restype = restype

@@ -568,6 +568,59 @@ def do_rnnt_pruning(am: torch.Tensor, lm: torch.Tensor, ranges: torch.Tensor, de
 _LOWP_KIND = {torch.bfloat16: _lib.FTR_DTYPE_BF16, torch.float16: _lib.FTR_DTYPE_FP16}
 
 
+class _DoPruningSum(torch.autograd.Function):
+    """am[b,t,:] + lm[b, ranges[b,t,k], :] as one launch each way plus the segment reduction (include/ftr_prune_sum.h);
+    nothing but ``ranges`` is kept for the backward."""
+
+    @staticmethod
+    def forward(ctx, am, lm, ranges):
+        B, T, r = ranges.shape
+        S1, C = lm.shape[1], lm.shape[2]
+        am_c = am.detach().contiguous(); lm_c = lm.detach().contiguous()
+        z = torch.empty((B, T, r, C), dtype=am.dtype, device=am.device)
+        with torch.cuda.device(am.device):
+            _lib.call("ftr_do_pruning_sum_dt", _ptr(am_c), _ptr(lm_c), _LOWP_KIND.get(am.dtype, _lib.FTR_DTYPE_F32), _ptr(ranges),
+                      _ptr(z), B, T, S1, C, r, _stream_ptr(am))
+        ctx.save_for_backward(ranges)
+        ctx.lm_shape = tuple(lm.shape)
+        return z
+
+    @staticmethod
+    def backward(ctx, g):
+        (ranges,) = ctx.saved_tensors
+        B, S1, C = ctx.lm_shape
+        T, r = ranges.shape[1], ranges.shape[2]
+        g = g.contiguous()
+        g_am = torch.empty((B, T, C), dtype=g.dtype, device=g.device)      # broadcast <-> sum over s_range
+        g_lm = torch.empty((B, S1, C), dtype=g.dtype, device=g.device)     # gather    <-> segment sum
+        ws_bytes = int(_lib.lib().ftr_do_pruning_bwd_workspace_bytes(B, T, S1, C, r))    # float32 partial rows for every dtype
+        ws = torch.empty(((ws_bytes + 3) // 4,), dtype=torch.float32, device=g.device) if ws_bytes else None
+        with torch.cuda.device(g.device):
+            _lib.call("ftr_do_pruning_sum_bwd_ws_dt", _ptr(g), _LOWP_KIND.get(g.dtype, _lib.FTR_DTYPE_F32), _ptr(ranges), _ptr(g_am),
+                      _ptr(g_lm), B, T, S1, C, r, _ptr(ws), ws_bytes, _stream_ptr(g))
+        return g_am, g_lm, None
+
+
+def do_rnnt_pruning_sum(am: torch.Tensor, lm: torch.Tensor, ranges: torch.Tensor) -> torch.Tensor:
+    """MI355X addition: ``sum(do_rnnt_pruning(am, lm, ranges))`` as one operation, in float32, bfloat16 or float16.
+
+    am [B,T,C], lm [B,S+1,C] (one dtype for both), ranges [B,T,s_range] -> z [B,T,s_range,C], contiguous, in that dtype:
+    ``z[b,t,k,:] = am[b,t,:] + lm[b, ranges[b,t,k], :]``, the addition every joiner starts with.  The gathered
+    ``lm_pruned`` never exists: the forward writes z once, the backward reads its gradient once.  A 16-bit tensor stands
+    for its exact float32 up-conversion: one float32 addition and one rounding to nearest-even per element; the gradients
+    are accumulated in float32, in the order of ``do_rnnt_pruning``'s backward, and rounded once into the dtype of am / lm.
+    Deterministic (no atomics), kernels only (capturable into a graph)."""
+    _require_gpu(am, "am"); _require_gpu(lm, "lm"); _require_gpu(ranges, "ranges")
+    if am.dtype != lm.dtype or (am.dtype != torch.float32 and am.dtype not in _LOWP_KIND):
+        raise TypeError("am and lm must have the same dtype: float32, bfloat16 or float16")
+    if am.dim() != 3 or lm.dim() != 3 or ranges.dim() != 3 or am.shape[2] != lm.shape[2]:
+        raise ValueError("do_rnnt_pruning_sum: am [B,T,C], lm [B,S+1,C] and ranges [B,T,s_range] expected")
+    if ranges.shape[0] != am.shape[0] or ranges.shape[0] != lm.shape[0] or am.shape[1] != ranges.shape[1]:
+        raise ValueError("do_rnnt_pruning_sum: inconsistent shapes")
+    ranges = ranges.to(torch.int32).contiguous()
+    return _DoPruningSum.apply(am, lm, ranges)
+
+
 def _pruned_call(name, hat, x, head, tail):
     """One logits-reading entry point on ``x``: ``ftr_[hat_]<name>_f32(x, *head, *tail)`` for float32 logits,
     ``ftr_<name>_dt(x, kind, *head, flags, *tail)`` for bfloat16 / float16 (``tail``: the stream)."""
