@@ -1,4 +1,4 @@
-// csrc/capi.hip -- the extern "C" surface declared in include/ftr.h, include/ftr_lowp.h, include/ftr_prune_sum.h, include/ftr_kd.h and include/ftr_fused.h: argument validation and error reporting.  No
+// csrc/capi.hip -- the extern "C" surface declared in include/ftr.h, include/ftr_lowp.h, include/ftr_prune_sum.h, include/ftr_joiner_act.h, include/ftr_kd.h and include/ftr_fused.h: argument validation and error reporting.  No
 // allocation, no host synchronisation, no CPU fallback.  Built twice: into libftr_hip.so (the product: the symbols of
 // ftr.h and ftr_lowp.h and nothing else) and, with -DFTR_DIAG, into the test-only _build/libftr_hip_diag.so, which adds the symbols of
 // include/ftr_diag.h: the "plain" kernel family (the reference's arithmetic on the device, mi_plain.hip), its
@@ -360,6 +360,36 @@ int ftr_do_pruning_sum_bwd_ws_dt(const void* g_out, int kind, const int32_t* ran
   if ((size_t)B * C == 0) return FTR_OK;
   FTR_TRY(pointers_then_device(what, g_out && ranges && d_am && d_lm));
   return do_pruning_sum_bwd_ws(g_out, kind, ranges, d_am, d_lm, B, T, S1, C, r, workspace, workspace_bytes, stream_of(stream));
+}
+
+// ---- include/ftr_joiner_act.h: the same with an activation behind the addition.  The element type code, then the activation
+// code, then the checks of ftr_do_pruning_f32 / ftr_do_pruning_bwd_ws_f32 in their order and with their replies
+static int check_act(const char* what, int act) {
+  FTR_REQUIRE(act == FTR_ACT_TANH || act == FTR_ACT_RELU, "%s: unknown activation code %d (FTR_ACT_TANH = 1, FTR_ACT_RELU = 2)", what, act);
+  return FTR_OK;
+}
+int ftr_pruned_joiner_act_dt(const void* am, const void* lm, int kind, int act, const int32_t* ranges, void* out,
+                             int B, int T, int S1, int C, int r, void* stream) {
+  clear_error();
+  FTR_TRY(check_dtype("pruned_joiner_act_dt", kind, 0));
+  FTR_TRY(check_act("pruned_joiner_act_dt", act));
+  FTR_TRY(check_sizes("do_pruning", B >= 0 && T >= 0 && S1 >= 1 && C >= 0 && r >= 0));
+  if ((size_t)B * T * r * C == 0) return FTR_OK;
+  FTR_TRY(pointers_then_device("do_pruning", am && lm && ranges && out));
+  return pruned_joiner_act(am, lm, kind, act, ranges, out, B, T, S1, C, r, stream_of(stream));
+}
+
+int ftr_pruned_joiner_act_bwd_ws_dt(const void* g_out, const void* out, int kind, int act, const int32_t* ranges,
+                                    void* d_am, void* d_lm, int B, int T, int S1, int C, int r,
+                                    void* workspace, size_t workspace_bytes, void* stream) {
+  clear_error();
+  FTR_TRY(check_dtype("pruned_joiner_act_bwd_ws_dt", kind, 0));
+  FTR_TRY(check_act("pruned_joiner_act_bwd_ws_dt", act));
+  const char* what = "do_pruning_bwd_ws";
+  FTR_TRY(check_sizes(what, B >= 0 && T >= 0 && S1 >= 1 && C >= 0 && r >= 0));
+  if ((size_t)B * C == 0) return FTR_OK;
+  FTR_TRY(pointers_then_device(what, g_out && out && ranges && d_am && d_lm));
+  return pruned_joiner_act_bwd_ws(g_out, out, kind, act, ranges, d_am, d_lm, B, T, S1, C, r, workspace, workspace_bytes, stream_of(stream));
 }
 
 // the ordinary entry point and its HAT twin (hat = 1: blank-excluded normaliser, which needs C >= 2)

@@ -6,6 +6,7 @@
 #include <stdarg.h>
 #include "../../include/ftr_kd.h"  // and, through it, ftr_lowp.h and ftr.h
 #include "../../include/ftr_prune_sum.h"
+#include "../../include/ftr_joiner_act.h"
 #include "../../include/ftr_fused.h"
 #include "../../include/ftr_band_tdt.h"
 #include "../../include/ftr_band_multiblank.h"
@@ -268,6 +269,10 @@ int do_pruning_bwd(const float* g_am_p, const float* g_lm_p, const int32_t* rang
 // do_pruning_sum_bwd_ws takes the routes of do_pruning_bwd_ws with one g for both inputs, and its workspace
 int do_pruning_sum(const void* am, const void* lm, int dtype, const int32_t* ranges, void* out, int B, int T, int S1, int C, int r, hipStream_t st);
 int do_pruning_sum_bwd_ws(const void* g, int dtype, const int32_t* ranges, void* d_am, void* d_lm, int B, int T, int S1, int C, int r, void* ws, size_t ws_bytes, hipStream_t st);
+// the same with an activation behind the addition (include/ftr_joiner_act.h); act: FTR_ACT_*, validated by the caller.  The backward
+// forms dz from g and the forward's out as it loads them; routes and workspace of do_pruning_bwd_ws
+int pruned_joiner_act(const void* am, const void* lm, int dtype, int act, const int32_t* ranges, void* out, int B, int T, int S1, int C, int r, hipStream_t st);
+int pruned_joiner_act_bwd_ws(const void* g, const void* out, int dtype, int act, const int32_t* ranges, void* d_am, void* d_lm, int B, int T, int S1, int C, int r, void* ws, size_t ws_bytes, hipStream_t st);
 // hat != 0: the HAT normalisation (lse = non-blank normaliser Z, see pruned_logprobs.hip); hat == 0: the ordinary kernels
 // dtype: the element type of logits / glogits (FTR_DTYPE_*, validated by the caller: dtype_ok)
 int pruned_logprobs_fwd(const void* logits, int dtype, const int32_t* symbols, const int32_t* ranges, const int32_t* boundary, int blank, double delay_penalty, float* lse, float* px, float* py, int B, int T, int S, int C, int r, int modified, int hat, hipStream_t st);

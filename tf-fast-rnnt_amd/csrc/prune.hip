@@ -8,11 +8,14 @@
 //   do_pruning_kernel      replaces do_rnnt_pruning (rnnt_loss.py:763-812)
 //   do_pruning_sum_kernel  the same gather fused with the joiner's am_pruned + lm_pruned, in float / bf16 / fp16, and the
 //                          do_pruning_sum_bwd_* kernels behind it (include/ftr_prune_sum.h; no reference counterpart)
+//   joiner_act_kernel      that sum with tanh / relu behind it, and the joiner_act_bwd_* kernels, which form dz from g and the
+//                          stored output as they load them (include/ftr_joiner_act.h; no reference counterpart)
 // (paths relative to /root/reference/tf_fast_rnnt/python/tf_fast_rnnt/ unless they start with csrc).
 // All integer results are bit-exact with oracle/mi_oracle.c; the float window sums use the same
 // canonical order (sequential f32 cumsum along S, additions only -> no contraction possible).
 #include "ftr_common.h"
 #include "launch.h"
+#include "act_math.h"
 #include <cstdlib>
 #include <limits.h>
 
@@ -1216,6 +1219,462 @@ __global__ __launch_bounds__(64 * RED_WAVES) void do_pruning_sum_bwd_reduce_kern
   }
 }
 
+// ---- the gather, the addition and an activation in one (include/ftr_joiner_act.h): out = act(am + lm[ranges]).
+// Written once over the element type E (float included) and the activation ACT (FTR_ACT_*, act_math.h); the kernels above
+// are not routed through these, so they keep their code.  Forward: do_pruning_sum_kernel with act_fwd4 between the addition
+// and the store.  The store is a plain one, not store4_nt: `out` is read again at once, by the layer that follows and by
+// the backward below (non-temporal stores have not been measured for this kernel).
+template <typename E, int ACT, bool VEC>
+__global__ __launch_bounds__(128) void joiner_act_kernel(const E* __restrict__ am, const E* __restrict__ lm,
+                                                         const int32_t* __restrict__ ranges, E* __restrict__ out,
+                                                         int T, int S1, int C, int r) {
+  size_t bt = blockIdx.x;
+  if ((gridDim.x & 7u) == 0) bt = (size_t)(blockIdx.x & 7u) * (gridDim.x >> 3) + (blockIdx.x >> 3);
+  const size_t b = bt / T;
+  const int32_t* rg = ranges + bt * r;
+  const E* lmb = lm + b * S1 * C;
+  const E* arow = am + bt * C;
+  E* o = out + bt * r * C;
+  if (VEC) {
+    const int n4 = C >> 2;
+    for (int c4 = threadIdx.x; c4 < n4; c4 += 128) {
+      const f4 a = load4(arow, c4);
+      for (int k0 = 0; k0 < r; k0 += 8) {
+        f4 l[8];
+#pragma unroll
+        for (int u = 0; u < 8; ++u)
+          if (k0 + u < r) l[u] = load4(lmb + (size_t)min(max(rg[k0 + u], 0), S1 - 1) * C, c4);   // caller data: kept in bounds
+#pragma unroll
+        for (int u = 0; u < 8; ++u)
+          if (k0 + u < r) store4(o + (size_t)(k0 + u) * C, c4, act_fwd4<ACT>(a + l[u]));
+      }
+    }
+  } else {
+    for (int c = threadIdx.x; c < C; c += 128) {
+      const float a = elem_to_float(arow[c]);
+      for (int k = 0; k < r; ++k)
+        o[(size_t)k * C + c] = elem_from_float<E>(act_fwd<ACT>(a + elem_to_float(lmb[(size_t)min(max(rg[k], 0), S1 - 1) * C + c])));
+    }
+  }
+}
+
+// ---- its backward: the do_pruning_sum_bwd_* kernels with dz = g act'(y) formed in registers wherever a row of g is loaded
+// (act_dz4: the same row of y is loaded beside it), pass 2's re-read of g rows included.  dz is never stored; `partial` rows
+// hold float32 sums of dz.  The summation orders are those of the kernels above, so with the float32 tensor dz as both
+// gradients ftr_do_pruning_bwd_ws_f32 gives the same bits.
+template <typename E, int ACT, bool VEC>
+__global__ void joiner_act_bwd_am_kernel(const E* __restrict__ g, const E* __restrict__ y, E* __restrict__ d_am, int C, int r, size_t total) {
+  const int per_row = VEC ? (C >> 2) : C;
+  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x) {
+    const size_t bt = i / per_row;
+    const int c = (int)(i - bt * per_row);
+    if (VEC) {
+      f4 acc = {0.f, 0.f, 0.f, 0.f};
+      for (int k = 0; k < r; ++k) acc += act_dz4<ACT>(load4(g + (bt * r + k) * C, c), load4(y + (bt * r + k) * C, c));
+      store4(d_am + bt * C, c, acc);
+    } else {
+      float acc = 0.f;
+      for (int k = 0; k < r; ++k) acc += act_dz<ACT>(elem_to_float(g[(bt * r + k) * C + c]), elem_to_float(y[(bt * r + k) * C + c]));
+      d_am[bt * C + c] = elem_from_float<E>(acc);
+    }
+  }
+}
+template <typename E, int ACT, bool VEC>
+__global__ __launch_bounds__(64) void joiner_act_bwd_lm_kernel(const E* __restrict__ g, const E* __restrict__ y, const int32_t* __restrict__ ranges,
+                                         E* __restrict__ d_lm, int T, int S1, int C, int r) {
+  extern __shared__ int lds_list[];   // [T*r] matching row indices of this wave
+  const int s = blockIdx.x, b = blockIdx.y;
+  const int n = T * r;
+  const int32_t* rg = ranges + (size_t)b * n;
+  const int lane = threadIdx.x;
+  int count = 0;
+  const unsigned long long lt = (1ull << lane) - 1ull;
+  const bool vec_ok = ((reinterpret_cast<uintptr_t>(rg) & 15) == 0);
+  constexpr int UN = 8;
+  for (int base = 0; base < n; base += 256 * UN) {
+    int v[UN][4];
+#pragma unroll
+    for (int u = 0; u < UN; ++u) {
+      const int i0 = base + 256 * u + 4 * lane;
+      if (vec_ok && i0 + 3 < n) {
+        const int4 q = *reinterpret_cast<const int4*>(rg + i0);
+        v[u][0] = q.x; v[u][1] = q.y; v[u][2] = q.z; v[u][3] = q.w;
+      } else {
+#pragma unroll
+        for (int e = 0; e < 4; ++e) v[u][e] = (i0 + e < n) ? rg[i0 + e] : -1;
+      }
+    }
+#pragma unroll
+    for (int u = 0; u < UN; ++u) {
+      const int i0 = base + 256 * u + 4 * lane;
+      bool hit[4];
+      int before = 0, total = 0;
+#pragma unroll
+      for (int e = 0; e < 4; ++e) {
+        hit[e] = (v[u][e] == s);
+        const unsigned long long m = __ballot(hit[e]);
+        before += __popcll(m & lt);
+        total += __popcll(m);
+      }
+      if (total != 0) {   // wave-uniform
+        int pos = count + before;
+#pragma unroll
+        for (int e = 0; e < 4; ++e)
+          if (hit[e]) lds_list[pos++] = i0 + e;
+        count += total;
+      }
+    }
+  }
+  __syncthreads();   // one wave per block: orders the LDS list writes before the reads below
+  const E* gb = g + (size_t)b * n * C;
+  const E* yb = y + (size_t)b * n * C;
+  E* out = d_lm + ((size_t)b * S1 + s) * C;
+  if (VEC) {
+    const int n4 = C >> 2;
+    // do_pruning_sum_bwd_lm_kernel's two column quads x eight rows, with four rows of g and y in flight at a time: the same
+    // sixteen loads per lane, and the eight partial sums in the same fixed order
+    for (int c = lane; c < n4; c += 128) {
+      const int c2 = c + 64;
+      const bool two = c2 < n4;
+      const f4 z = {0.f, 0.f, 0.f, 0.f};
+      f4 a[4] = {z, z, z, z}, d[4] = {z, z, z, z};
+      int j = 0;
+      for (; j + 7 < count; j += 8) {
+#pragma unroll
+        for (int h = 0; h < 2; ++h) {
+          f4 xg[4], xy[4], wg[4], wy[4];
+#pragma unroll
+          for (int u = 0; u < 4; ++u) {
+            const size_t row = (size_t)lds_list[j + 4 * h + u] * C;
+            xg[u] = load4(gb + row, c); xy[u] = load4(yb + row, c);
+            wg[u] = two ? load4(gb + row, c2) : z; wy[u] = two ? load4(yb + row, c2) : z;
+          }
+#pragma unroll
+          for (int u = 0; u < 4; ++u) {
+            a[u] += act_dz4<ACT>(xg[u], xy[u]); d[u] += act_dz4<ACT>(wg[u], wy[u]);
+          }
+        }
+      }
+      for (; j < count; ++j) {
+        const size_t row = (size_t)lds_list[j] * C;
+        a[0] += act_dz4<ACT>(load4(gb + row, c), load4(yb + row, c));
+        if (two) d[0] += act_dz4<ACT>(load4(gb + row, c2), load4(yb + row, c2));
+      }
+      store4(out, c, (a[0] + a[1]) + (a[2] + a[3]));
+      if (two) store4(out, c2, (d[0] + d[1]) + (d[2] + d[3]));
+    }
+  } else {
+    for (int c = lane; c < C; c += 64) {
+      float acc = 0.f;
+      for (int j = 0; j < count; ++j)
+        acc += act_dz<ACT>(elem_to_float(gb[(size_t)lds_list[j] * C + c]), elem_to_float(yb[(size_t)lds_list[j] * C + c]));
+      out[c] = elem_from_float<E>(acc);
+    }
+  }
+}
+// a quad as it is loaded: four floats, or four 16-bit elements still packed (two registers), converted when it is consumed
+template <typename E> struct raw_quad { typedef h4 type; };
+template <> struct raw_quad<float> { typedef f4 type; };
+__device__ __forceinline__ f4 load4_raw(const float* row, int i) { return load4(row, i); }
+template <typename E> __device__ __forceinline__ h4 load4_raw(const E* row, int i) { return reinterpret_cast<const h4*>(row)[i]; }
+template <typename E> __device__ __forceinline__ f4 quad_to_float(f4 v) { return v; }
+template <typename E> __device__ __forceinline__ f4 quad_to_float(h4 h) {
+  f4 v;
+#pragma unroll
+  for (int e = 0; e < 4; ++e) v[e] = elem_to_float(E{h[e]});
+  return v;
+}
+
+// pass 1 (the FUSE form: one dz for d am and d lm).  A batch is kSegRows rows of a 16-bit type and half as many of float, and
+// the quads of g and y wait in registers as they were loaded, so the bytes in flight per lane -- g and y, two batches -- and
+// the registers that hold them are those of the float kernel's g alone
+template <typename E, int ACT, int R>
+__global__ __launch_bounds__(128) void joiner_act_bwd_seg_kernel(
+    const E* __restrict__ g_out, const E* __restrict__ y_out, const int32_t* __restrict__ ranges, E* __restrict__ d_am,
+    E* __restrict__ d_lm, float* __restrict__ partial, int4* __restrict__ meta, int T, int S1, int C, int SEG) {
+  extern __shared__ int bs[];      // base[SEG]
+  __shared__ int red[8];
+  constexpr int r = R;
+  const int seg = blockIdx.x, b = blockIdx.y, nseg = gridDim.x;
+  const int t0 = seg * SEG;
+  const int nf = min(SEG, T - t0);
+  const int nrows = nf * r;
+  const int32_t* rg = ranges + ((size_t)b * T + t0) * r;
+  // the segment's ranges: lowest / highest row, and is it a band?
+  int lo = INT_MAX, hi = INT_MIN, bad = 0;
+  for (int i = threadIdx.x; i < nrows; i += 128) {
+    const int v = rg[i];
+    const int f = i / r, k = i - f * r;
+    const int v0 = rg[f * r];
+    lo = min(lo, v); hi = max(hi, v);
+    bad |= (v != v0 + k) | (v < 0) | (v >= S1);
+    if (k == 0) {
+      bs[f] = v;
+      if (f + 1 < nf) { const int nx = rg[(f + 1) * r]; bad |= (nx < v) | (nx > v + r); }
+    }
+  }
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) {
+    lo = min(lo, __shfl_xor(lo, off, 64));
+    hi = max(hi, __shfl_xor(hi, off, 64));
+    bad |= __shfl_xor(bad, off, 64);
+  }
+  if ((threadIdx.x & 63) == 0) { const int w = threadIdx.x >> 6; red[3 * w] = lo; red[3 * w + 1] = hi; red[3 * w + 2] = bad; }
+  if (threadIdx.x == 127) {   // the neighbours (wave 1 writes red[6..7], read after the barrier like the rest)
+    red[6] = t0 > 0 ? rg[-r] + r - 1 : -1;
+    red[7] = t0 + nf < T ? rg[nrows] : INT_MAX - 1;
+  }
+  __syncthreads();
+  const int smin = min(red[0], red[3]), smax = max(red[1], red[4]);
+  const int prevtop = red[6], nextbase = red[7];
+  // a band whose neighbours continue it: at most r rows shared with each side
+  const bool ok = !(red[2] | red[5]) && prevtop - (r - 1) <= smin && nextbase >= smax - (r - 1);
+  if (threadIdx.x == 0)
+    meta[(size_t)b * nseg + seg] = make_int4(min(smin, smax), max(smin, smax), ok ? prevtop : kSegIrregular, nextbase);
+  const int n4 = C >> 2;           // (an irregular segment still gives its d am rows)
+  const size_t row0 = ((size_t)b * T + t0) * r;
+  float* pseg = partial + ((size_t)b * nseg + seg) * (size_t)(2 * r) * C;
+  E* dlm_b = d_lm + (size_t)b * S1 * C;
+  const f4 z = {0.f, 0.f, 0.f, 0.f};
+  constexpr int kRows = sizeof(E) == 4 ? kSegRows / 2 : kSegRows;
+  constexpr int FB = (kRows + R - 1) / R;      // frames per batch; two batches in flight
+  for (int cb = 0; cb < n4; cb += 128) {
+    const int c4 = cb + (int)threadIdx.x;
+    const bool live = c4 < n4;
+    const int cc = live ? c4 : n4 - 1;                       // clamped: every load is issued, what it brings is not stored
+    const E* g = g_out + row0 * C + 4 * (size_t)cc;          // the quad of row i at g + 4 * (i * n4)
+    const E* y = y_out + row0 * C + 4 * (size_t)cc;
+    f4 acc[R];                                               // lattice rows cur .. cur + R - 1
+#pragma unroll
+    for (int k = 0; k < R; ++k) acc[k] = z;
+    int cur = smin;
+    auto flush = [&](int j) {                                // row cur + j is complete as far as this segment goes
+      const int row = cur + j;
+      // one store instruction per destination buffer (a pointer chosen by ?: becomes a flat access through a pointer table)
+      const int slot = row <= prevtop ? row - smin : r + row - nextbase;
+      if (row <= prevtop || row >= nextbase) {
+        if (live) store4(pseg + (size_t)slot * C, c4, acc[j]);
+      } else {
+        if (live) store4(dlm_b + (size_t)row * C, c4, acc[j]);
+      }
+    };
+    typedef typename raw_quad<E>::type Q;
+    auto load = [&](Q (&vg)[FB * R], Q (&vy)[FB * R], int f0) {
+#pragma unroll
+      for (int u = 0; u < FB * R; ++u) {
+        const size_t off = 4 * ((size_t)min(f0 * R + u, nrows - 1) * n4);
+        vg[u] = load4_raw(g + off, 0);
+        vy[u] = load4_raw(y + off, 0);
+      }
+    };
+    auto consume = [&](const Q (&vg)[FB * R], const Q (&vy)[FB * R], int f0) {
+#pragma unroll
+      for (int q = 0; q < FB; ++q) {
+        const int f = f0 + q;
+        if (f < nf) {
+          f4 v[R];
+#pragma unroll
+          for (int k = 0; k < R; ++k) v[k] = act_dz4<ACT>(quad_to_float<E>(vg[q * R + k]), quad_to_float<E>(vy[q * R + k]));
+          if (ok) {
+            const int step = __builtin_amdgcn_readfirstlane(bs[f]) - cur;   // 0 ... R in a band
+            if (step > 0) {
+#pragma unroll
+              for (int j = 0; j < R; ++j)
+                if (j < step) flush(j);
+              for (int sft = 0; sft < step; ++sft) {          // registers only: no memory instruction in this loop
+#pragma unroll
+                for (int k = 0; k + 1 < R; ++k) acc[k] = acc[k + 1];
+                acc[R - 1] = z;
+              }
+              cur += step;
+            }
+#pragma unroll
+            for (int k = 0; k < R; ++k) acc[k] += v[k];
+          }
+          f4 asum = v[0];
+#pragma unroll
+          for (int k = 1; k < R; ++k) asum += v[k];
+          if (live) store4(d_am + ((size_t)b * T + t0 + f) * C, c4, asum);
+        }
+      }
+    };
+    Q ga[FB * R], ya[FB * R], gb[FB * R], yb[FB * R];
+    load(ga, ya, 0);
+    for (int f0 = 0; f0 < nf; f0 += 2 * FB) {
+      load(gb, yb, f0 + FB);
+      consume(ga, ya, f0);
+      load(ga, ya, f0 + 2 * FB);
+      consume(gb, yb, f0 + FB);
+    }
+    if (ok) {
+#pragma unroll
+      for (int j = 0; j < R; ++j) flush(j);
+    }
+  }
+}
+// the quad c4 of an item's row: dz from a row of g and y, or a float32 row of `partial` (a branch on the item, the same for
+// every lane)
+template <typename E, int ACT>
+__device__ __forceinline__ f4 act_reduce_item_quad(const E* g, const E* y, const float* partial, unsigned it, int C, int c4) {
+  if (__builtin_amdgcn_readfirstlane(it) & 0x80000000u) {
+    const size_t row = (size_t)(it & 0x7fffffffu) * C;
+    return act_dz4<ACT>(load4(g + row, c4), load4(y + row, c4));
+  }
+  return load4(partial + (size_t)it * C, c4);
+}
+
+// pass 2
+template <typename E, int ACT>
+__global__ __launch_bounds__(64 * RED_WAVES) void joiner_act_bwd_reduce_kernel(
+    const E* __restrict__ g_out, const E* __restrict__ y_out, const int32_t* __restrict__ ranges, const float* __restrict__ partial,
+    const int4* __restrict__ meta, E* __restrict__ d_lm, int T, int S1, int C, int r, int SEG, int nseg) {
+  extern __shared__ __attribute__((aligned(16))) int dyn[];   // hits [2 * nseg], then (16-byte aligned) sums [RED_WAVES - 1][256] quads
+  __shared__ unsigned items[RED_CAP];
+  __shared__ int ctl[4];           // nh (or -1: nothing to do), hi, j0, cnt of the batch
+  int* hits = dyn;                 // segment id, partial slot of the row (or -1: rescan the segment)
+  f4* sums = reinterpret_cast<f4*>(dyn + ((2 * nseg + 3) & ~3));
+  const int s = blockIdx.x, b = blockIdx.y;
+  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+  const unsigned long long lt = (1ull << lane) - 1ull;
+  const int n4 = C >> 2;
+  if (wv == 0) {
+    const int4* mb = meta + (size_t)b * nseg;
+    int nh = 0, ndirect = 0, nresc = 0;
+    for (int c0 = 0; c0 < nseg; c0 += 64) {
+      const int sg = c0 + lane;
+      bool hit = false, direct = false, resc = false;
+      int slot = -1;
+      if (sg < nseg) {
+        const int4 m = mb[sg];
+        hit = s >= m.x && s <= m.y;
+        if (hit) {
+          if (m.z == kSegIrregular) resc = true;
+          else if (s <= m.z) slot = s - m.x;
+          else if (s >= m.w) slot = r + s - m.w;
+          else direct = true;
+        }
+      }
+      const unsigned long long mask = __ballot(hit);
+      if (hit) {
+        const int pos = nh + __popcll(mask & lt);
+        hits[2 * pos] = sg; hits[2 * pos + 1] = slot;
+      }
+      nh += __popcll(mask);
+      ndirect += __popcll(__ballot(direct));
+      nresc += __popcll(__ballot(resc));
+    }
+    const bool done = nh == 1 && ndirect == 1;                 // pass 1 wrote the row
+    const bool rescan = !done && (nresc > 0 || ndirect > 0);   // not (only) bands: take every touching segment from g and y
+    if (rescan)
+      for (int i = lane; i < nh; i += 64) hits[2 * i + 1] = -1;
+    if (lane == 0) { ctl[0] = done ? -1 : nh; ctl[1] = 0; ctl[2] = 0; }
+  }
+  __syncthreads();
+  const int nh = ctl[0];
+  if (nh < 0) return;
+  E* out = d_lm + ((size_t)b * S1 + s) * C;
+  f4 tot[4];                      // wave 0's lanes: the row's running total over the batches (4 column quads per lane and sweep)
+  for (int cb = 0; cb < n4; cb += 256) {
+#pragma unroll
+    for (int q = 0; q < 4; ++q) tot[q] = f4{0.f, 0.f, 0.f, 0.f};
+    if (wv == 0 && lane == 0) { ctl[1] = 0; ctl[2] = 0; }
+    __syncthreads();
+    while (true) {
+      // ---- wave 0: the next batch of items
+      if (wv == 0) {
+        int hi = ctl[1], j0 = ctl[2], cnt = 0;
+        while (hi < nh && cnt <= RED_CAP - 128) {
+          const int sg = hits[2 * hi], slot = hits[2 * hi + 1];
+          if (slot >= 0) {
+            if (lane == 0) items[cnt] = (unsigned)(((size_t)b * nseg + sg) * (2 * r) + slot);
+            ++cnt; ++hi;
+          } else {
+            const int t0 = sg * SEG;
+            const int nrows = min(SEG, T - t0) * r;
+            const size_t row0 = ((size_t)b * T + t0) * r;
+            while (j0 < nrows && cnt <= RED_CAP - 128) {
+              const int ja = j0 + lane, jb = j0 + 64 + lane;          // two independent loads per pass
+              const int va = ja < nrows ? ranges[row0 + ja] : -1;
+              const int vb = jb < nrows ? ranges[row0 + jb] : -1;
+              const unsigned long long ma = __ballot(va == s), mk = __ballot(vb == s);
+              if (va == s) items[cnt + __popcll(ma & lt)] = 0x80000000u | (unsigned)(row0 + ja);
+              cnt += __popcll(ma);
+              if (vb == s) items[cnt + __popcll(mk & lt)] = 0x80000000u | (unsigned)(row0 + jb);
+              cnt += __popcll(mk);
+              j0 += 128;
+            }
+            if (j0 >= nrows) { ++hi; j0 = 0; }
+          }
+        }
+        if (lane == 0) { ctl[1] = hi; ctl[2] = j0; ctl[3] = cnt; }
+      }
+      __syncthreads();
+      const int cnt = ctl[3];
+      const bool last = ctl[1] >= nh;
+      // ---- every wave: its share of the batch
+      f4 acc[4];
+#pragma unroll
+      for (int q = 0; q < 4; ++q) acc[q] = f4{0.f, 0.f, 0.f, 0.f};
+      int i = wv;
+      for (; i + 3 * RED_WAVES < cnt; i += 4 * RED_WAVES) {
+        unsigned it[4];
+#pragma unroll
+        for (int u = 0; u < 4; ++u) it[u] = items[i + u * RED_WAVES];
+        f4 v[4][4];
+#pragma unroll
+        for (int u = 0; u < 4; ++u)
+#pragma unroll
+          for (int q = 0; q < 4; ++q) {
+            const int c4 = cb + lane + 64 * q;
+            v[u][q] = (c4 < n4) ? act_reduce_item_quad<E, ACT>(g_out, y_out, partial, it[u], C, c4) : f4{0.f, 0.f, 0.f, 0.f};
+          }
+#pragma unroll
+        for (int u = 0; u < 4; ++u)
+#pragma unroll
+          for (int q = 0; q < 4; ++q) acc[q] += v[u][q];
+      }
+      for (; i < cnt; i += RED_WAVES) {
+        const unsigned it = items[i];
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+          const int c4 = cb + lane + 64 * q;
+          if (c4 < n4) acc[q] += act_reduce_item_quad<E, ACT>(g_out, y_out, partial, it, C, c4);
+        }
+      }
+      if (RED_WAVES > 1 && cnt > 1) {   // uniform over the block: a single item is wave 0's alone
+        if (wv != 0) {
+#pragma unroll
+          for (int q = 0; q < 4; ++q) {
+            const int c4 = lane + 64 * q;
+            if (cb + c4 < n4) sums[(size_t)(wv - 1) * 256 + c4] = acc[q];
+          }
+        }
+        __syncthreads();
+        if (wv == 0) {
+#pragma unroll
+          for (int q = 0; q < 4; ++q) {
+            const int c4 = lane + 64 * q;
+            if (cb + c4 < n4) tot[q] += RED_WAVES == 4 ? (acc[q] + sums[c4]) + (sums[256 + c4] + sums[512 + c4]) : acc[q] + sums[c4];
+          }
+        }
+      } else if (wv == 0) {
+#pragma unroll
+        for (int q = 0; q < 4; ++q) tot[q] += acc[q];
+      }
+      if (last) break;
+      __syncthreads();             // the batch's items and sums are consumed: wave 0 may overwrite them
+    }
+    if (wv == 0) {
+#pragma unroll
+      for (int q = 0; q < 4; ++q) {
+        const int c4 = cb + lane + 64 * q;
+        if (c4 < n4) store4(out, c4, tot[q]);
+      }
+    }
+    __syncthreads();
+  }
+}
+
 // frames per segment: a block per CU and more (two 16-row batches in flight per thread keep a wave busy: measured at c3, pass 1
 // takes 80 - 83 us with anything from 4 to 128 frames per segment, i.e. 8000 to 256 blocks), as long as possible otherwise:
 // every segment costs up to 2r partial rows where the band is flat, and pass 2 one addition per segment and shared row
@@ -1313,6 +1772,56 @@ int do_pruning_bwd_routes(const E* g_am_p, const E* g_lm_p, const int32_t* range
   return check_launch("do_pruning_bwd_reduce");
 }
 
+// the joiner_act_bwd_* family on the routes above, rule for rule (do_pruning_bwd_generic / do_pruning_bwd_routes in their
+// FUSE case, whose functions are left as they are): y, the forward's output, is one more tensor that must pass rows_vec4
+template <typename E, int ACT>
+int joiner_act_bwd_generic(const E* g, const E* y, const int32_t* ranges, E* d_am, E* d_lm, int B, int T, int S1, int C, int r,
+                           bool vec, hipStream_t st) {
+  const int threads = 256;
+  dispatch(vec, [&](auto v) {
+    const size_t total = (size_t)B * T * (decltype(v)::value ? C >> 2 : C);
+    hipLaunchKernelGGL((joiner_act_bwd_am_kernel<E, ACT, decltype(v)::value>), dim3((unsigned)((total + threads - 1) / threads)), dim3(threads), 0, st, g, y, d_am, C, r, total);
+  });
+  int rc = check_launch("do_pruning_bwd_am");
+  if (rc != FTR_OK) return rc;
+  const size_t lds = sizeof(int) * (size_t)T * r;   // worst case: every (t,k) selects the same row
+  if (lds > 150 * 1024) { set_error("do_pruning_bwd: T*s_range = %d too large for the LDS row list", T * r); return FTR_ERR_UNSUPPORTED; }
+  return dispatch(vec, [&](auto v) {
+    constexpr auto kernel = joiner_act_bwd_lm_kernel<E, ACT, decltype(v)::value>;
+    const int rcl = reserve_lds<kernel>(lds, "do_pruning_bwd", LdsText::reserve_why);
+    if (rcl != FTR_OK) return rcl;
+    hipLaunchKernelGGL(kernel, dim3(S1, B), dim3(64), lds, st, g, y, ranges, d_lm, T, S1, C, r);
+    return check_launch("do_pruning_bwd_lm");
+  });
+}
+template <typename E, int ACT>
+int joiner_act_bwd_routes(const E* g, const E* y, const int32_t* ranges, E* d_am, E* d_lm, int B, int T, int S1, int C, int r,
+                          void* ws, size_t ws_bytes, hipStream_t st) {
+  if ((size_t)B * T * C == 0) return FTR_OK;
+  const bool vec = bwd_vec4(C, g, y, d_am, d_lm);
+  if (!vec || r <= 0) return joiner_act_bwd_generic<E, ACT>(g, y, ranges, d_am, d_lm, B, T, S1, C, r, vec, st);
+  const size_t need = do_pruning_bwd_workspace_bytes(B, T, S1, C, r);
+  if (!ws || ws_bytes < need || (reinterpret_cast<uintptr_t>(ws) & 15) != 0) {
+    set_error("do_pruning_bwd_ws: workspace of %zu bytes (16-byte aligned) required, got %zu", need, ws_bytes);
+    return FTR_ERR_INVALID_ARG;
+  }
+  const int seg = seg_frames(B, T);
+  const int nseg = (T + seg - 1) / seg;
+  float* partial = reinterpret_cast<float*>(ws);
+  int4* meta = reinterpret_cast<int4*>(partial + (size_t)B * nseg * (2 * (size_t)r) * C);
+  const size_t lds = sizeof(int) * (size_t)seg;
+  if (r > kSegMaxR || lds > 60 * 1024 || (size_t)B * nseg * (2 * (size_t)r) >= 0x7fffffffull || (size_t)B * T * r >= 0x7fffffffull)
+    return joiner_act_bwd_generic<E, ACT>(g, y, ranges, d_am, d_lm, B, T, S1, C, r, vec, st);
+  dispatch_range<1, kSegMaxR>(r, [&](auto rr) {   // r <= kSegMaxR was checked above
+    hipLaunchKernelGGL((joiner_act_bwd_seg_kernel<E, ACT, decltype(rr)::value>), dim3(nseg, B), dim3(128), lds, st, g, y, ranges, d_am, d_lm, partial, meta, T, S1, C, seg);
+  }, [] {});
+  int rc = check_launch("do_pruning_bwd_seg");
+  if (rc != FTR_OK) return rc;
+  hipLaunchKernelGGL((joiner_act_bwd_reduce_kernel<E, ACT>), dim3(S1, B), dim3(64 * RED_WAVES),
+                     sizeof(int) * (size_t)((2 * nseg + 3) & ~3) + 3 * 256 * sizeof(float) * 4, st, g, y, ranges, partial, meta, d_lm, T, S1, C, r, seg, nseg);
+  return check_launch("do_pruning_bwd_reduce");
+}
+
 }  // namespace
 
 int do_pruning_bwd(const float* g_am_p, const float* g_lm_p, const int32_t* ranges, float* d_am, float* d_lm, int B,
@@ -1398,6 +1907,41 @@ int do_pruning_sum_bwd_ws(const void* g, int dtype, const int32_t* ranges, void*
     using E = typename decltype(tag)::type;
     const E* ge = static_cast<const E*>(g);
     return ftr::do_pruning_bwd_routes(ge, ge, ranges, static_cast<E*>(d_am), static_cast<E*>(d_lm), B, T, S1, C, r, ws, ws_bytes, st);
+  });
+}
+
+// act: FTR_ACT_TANH or FTR_ACT_RELU (the entries of capi.hip refuse anything else) -> the template argument
+template <typename F>
+static inline auto dispatch_act(int act, F&& f) {
+  if (act == FTR_ACT_RELU) return f(std::integral_constant<int, FTR_ACT_RELU>{});
+  return f(std::integral_constant<int, FTR_ACT_TANH>{});
+}
+
+int pruned_joiner_act(const void* am, const void* lm, int dtype, int act, const int32_t* ranges, void* out, int B, int T, int S1,
+                      int C, int r, hipStream_t st) {
+  const size_t frames = (size_t)B * T;
+  if (frames == 0 || C == 0 || r == 0) return FTR_OK;
+  { const int rc32 = require_rows_32bit("pruned_joiner_act", frames * (size_t)r); if (rc32 != FTR_OK) return rc32; }
+  dispatch_dtype(dtype, [&](auto tag) {
+    using E = typename decltype(tag)::type;
+    dispatch_act(act, [&](auto a) {
+      dispatch(rows_vec4<E>(C, am, lm) && rows_vec4<E>(C, out), [&](auto vec) {
+        hipLaunchKernelGGL((ftr::joiner_act_kernel<E, decltype(a)::value, decltype(vec)::value>), dim3((unsigned)frames), dim3(128), 0, st,
+                           static_cast<const E*>(am), static_cast<const E*>(lm), ranges, static_cast<E*>(out), T, S1, C, r);
+      });
+    });
+  });
+  return check_launch("pruned_joiner_act");
+}
+
+int pruned_joiner_act_bwd_ws(const void* g, const void* out, int dtype, int act, const int32_t* ranges, void* d_am, void* d_lm,
+                             int B, int T, int S1, int C, int r, void* ws, size_t ws_bytes, hipStream_t st) {
+  return dispatch_dtype(dtype, [&](auto tag) {
+    using E = typename decltype(tag)::type;
+    return dispatch_act(act, [&](auto a) {
+      return ftr::joiner_act_bwd_routes<E, decltype(a)::value>(static_cast<const E*>(g), static_cast<const E*>(out), ranges, static_cast<E*>(d_am),
+                                                               static_cast<E*>(d_lm), B, T, S1, C, r, ws, ws_bytes, st);
+    });
   });
 }
 

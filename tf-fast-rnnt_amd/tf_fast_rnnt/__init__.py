@@ -8,6 +8,7 @@ from .mutual_information import cummin, mutual_information_recursion, mutual_inf
 from .mutual_information import mutual_information_recursion_multiblank   # MI355X addition: multi-blank (big blank) lattice
 from .rnnt_loss import do_rnnt_pruning
 from .rnnt_loss import do_rnnt_pruning_sum                                     # MI355X addition: am + lm[ranges] fused, f32 / bf16 / fp16
+from .rnnt_loss import do_rnnt_pruning_act                                     # MI355X addition: tanh / relu of that sum, fused
 from .rnnt_loss import get_rnnt_logprobs
 from .rnnt_loss import get_rnnt_logprobs_joint
 from .rnnt_loss import get_rnnt_logprobs_pruned

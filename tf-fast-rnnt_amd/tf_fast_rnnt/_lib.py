@@ -114,6 +114,12 @@ _PRUNE_SUM_SIGNATURES = {
     "ftr_do_pruning_sum_dt": (_i, [_c_fp, _c_fp, _i, _c_ip, _c_fp, _i, _i, _i, _i, _i, _c_st]),
     "ftr_do_pruning_sum_bwd_ws_dt": (_i, [_c_fp, _i, _c_ip, _c_fp, _c_fp, _i, _i, _i, _i, _i, ctypes.c_void_p, ctypes.c_size_t, _c_st]),
 }
+# include/ftr_joiner_act.h, that sum with tanh / relu behind it: (am, lm, kind, act = FTR_ACT_*, ranges, out, ...) and its backward
+# (g_out, out, kind, act, ranges, d_am, d_lm, ..., workspace, workspace_bytes, stream)
+_JOINER_ACT_SIGNATURES = {
+    "ftr_pruned_joiner_act_dt": (_i, [_c_fp, _c_fp, _i, _i, _c_ip, _c_fp, _i, _i, _i, _i, _i, _c_st]),
+    "ftr_pruned_joiner_act_bwd_ws_dt": (_i, [_c_fp, _c_fp, _i, _i, _c_ip, _c_fp, _c_fp, _i, _i, _i, _i, _i, ctypes.c_void_p, ctypes.c_size_t, _c_st]),
+}
 # include/ftr_kd.h, knowledge distillation on the pruned band: (logits, kind, teacher_logits, teacher_kind, symbols, ranges,
 # boundary, termination_symbol, temperature, mode = FTR_KD_*, ...)
 _KD_SIGNATURES = {
@@ -155,6 +161,7 @@ _BAND_VITERBI_SIGNATURES = {
 EXPORTED_SYMBOLS = tuple(_SIGNATURES)            # the symbols of include/ftr.h
 LOWP_SYMBOLS = tuple(_LOWP_SIGNATURES)           # those of include/ftr_lowp.h
 PRUNE_SUM_SYMBOLS = tuple(_PRUNE_SUM_SIGNATURES) # those of include/ftr_prune_sum.h
+JOINER_ACT_SYMBOLS = tuple(_JOINER_ACT_SIGNATURES)   # those of include/ftr_joiner_act.h
 KD_SYMBOLS = tuple(_KD_SIGNATURES)               # those of include/ftr_kd.h
 FUSED_SYMBOLS = tuple(_FUSED_SIGNATURES)         # those of include/ftr_fused.h
 BAND_TDT_SYMBOLS = tuple(_BAND_TDT_SIGNATURES)   # those of include/ftr_band_tdt.h
@@ -165,6 +172,7 @@ band_multiblank_recursions = 0   # ... and the band-native multi-blank recursion
 FTR_KD_FULL, FTR_KD_COLLAPSED = 0, 1             # include/ftr_kd.h: the `mode` of the kd entry points
 FTR_MI_WS_CLEAN = 1   # include/ftr.h
 FTR_DTYPE_F32, FTR_DTYPE_BF16, FTR_DTYPE_FP16 = 0, 1, 2   # include/ftr_lowp.h: the `kind` of the _dt entry points
+FTR_ACT_TANH, FTR_ACT_RELU = 1, 2                          # include/ftr_joiner_act.h: the `act` of its entry points
 FTR_PRUNED_HAT = 1    # include/ftr_lowp.h: their `flags` bit
 
 
@@ -177,7 +185,7 @@ def lib() -> ctypes.CDLL:
                 f"{LIB_PATH} is missing: build the HIP extension first (python -c 'import __graft_entry__ as g; "
                 "g.build()' or make -C tf-fast-rnnt_amd/csrc).  tf_fast_rnnt has no CPU fallback.")
         handle = ctypes.CDLL(LIB_PATH)
-        for name, (restype, argtypes) in {**_SIGNATURES, **_LOWP_SIGNATURES, **_PRUNE_SUM_SIGNATURES, **_KD_SIGNATURES, **_FUSED_SIGNATURES,
+        for name, (restype, argtypes) in {**_SIGNATURES, **_LOWP_SIGNATURES, **_PRUNE_SUM_SIGNATURES, **_JOINER_ACT_SIGNATURES, **_KD_SIGNATURES, **_FUSED_SIGNATURES,
                                             **_BAND_TDT_SIGNATURES, **_BAND_MULTIBLANK_SIGNATURES, **_BAND_VITERBI_SIGNATURES}.items():
             fn = getattr(handle, name)   # AttributeError here = header/library mismatch
             fn.restype = restype

@@ -621,6 +621,66 @@ def do_rnnt_pruning_sum(am: torch.Tensor, lm: torch.Tensor, ranges: torch.Tensor
     return _DoPruningSum.apply(am, lm, ranges)
 
 
+_ACT_KIND = {"tanh": _lib.FTR_ACT_TANH, "relu": _lib.FTR_ACT_RELU}
+
+
+class _DoPruningAct(torch.autograd.Function):
+    """act(am[b,t,:] + lm[b, ranges[b,t,k], :]) (include/ftr_joiner_act.h).  ``ranges`` and the output itself are kept for
+    the backward, which forms dz = g * act'(y) as it reads g and y; neither the sum nor dz is ever in memory."""
+
+    @staticmethod
+    def forward(ctx, am, lm, ranges, act):
+        B, T, r = ranges.shape
+        S1, C = lm.shape[1], lm.shape[2]
+        am_c = am.detach().contiguous(); lm_c = lm.detach().contiguous()
+        y = torch.empty((B, T, r, C), dtype=am.dtype, device=am.device)
+        with torch.cuda.device(am.device):
+            _lib.call("ftr_pruned_joiner_act_dt", _ptr(am_c), _ptr(lm_c), _LOWP_KIND.get(am.dtype, _lib.FTR_DTYPE_F32), act, _ptr(ranges),
+                      _ptr(y), B, T, S1, C, r, _stream_ptr(am))
+        ctx.save_for_backward(ranges, y)
+        ctx.lm_shape = tuple(lm.shape)
+        ctx.act = act
+        return y
+
+    @staticmethod
+    def backward(ctx, g):
+        ranges, y = ctx.saved_tensors
+        B, S1, C = ctx.lm_shape
+        T, r = ranges.shape[1], ranges.shape[2]
+        g = g.contiguous()
+        g_am = torch.empty((B, T, C), dtype=g.dtype, device=g.device)      # broadcast <-> sum over s_range
+        g_lm = torch.empty((B, S1, C), dtype=g.dtype, device=g.device)     # gather    <-> segment sum
+        ws_bytes = int(_lib.lib().ftr_do_pruning_bwd_workspace_bytes(B, T, S1, C, r))    # float32 partial rows for every dtype
+        ws = torch.empty(((ws_bytes + 3) // 4,), dtype=torch.float32, device=g.device) if ws_bytes else None
+        with torch.cuda.device(g.device):
+            _lib.call("ftr_pruned_joiner_act_bwd_ws_dt", _ptr(g), _ptr(y), _LOWP_KIND.get(g.dtype, _lib.FTR_DTYPE_F32), ctx.act,
+                      _ptr(ranges), _ptr(g_am), _ptr(g_lm), B, T, S1, C, r, _ptr(ws), ws_bytes, _stream_ptr(g))
+        return g_am, g_lm, None, None
+
+
+def do_rnnt_pruning_act(am: torch.Tensor, lm: torch.Tensor, ranges: torch.Tensor, activation: str = "tanh") -> torch.Tensor:
+    """MI355X addition: ``act(do_rnnt_pruning_sum(am, lm, ranges))`` as one operation, ``activation`` "tanh" or "relu":
+    what a joiner hands to its output layer, ``output_linear(do_rnnt_pruning_act(am, lm, ranges))``.
+
+    am [B,T,C], lm [B,S+1,C] (one dtype for both: float32, bfloat16 or float16), ranges [B,T,s_range] -> y [B,T,s_range,C],
+    contiguous, in that dtype: ``y[b,t,k,:] = act(am[b,t,:] + lm[b, ranges[b,t,k], :])``.  The sum is one float32 addition,
+    the activation is computed in float32 and rounded once into the dtype; the sum itself is never in memory.  The backward
+    keeps y (which the next layer keeps anyway) and forms ``g * (1 - y*y)`` or ``g where y > 0`` in registers as it sums:
+    float32 accumulation in the order of ``do_rnnt_pruning``'s backward, one rounding into the dtype.  Deterministic (no
+    atomics), kernels only (capturable into a graph)."""
+    _require_gpu(am, "am"); _require_gpu(lm, "lm"); _require_gpu(ranges, "ranges")
+    if am.dtype != lm.dtype or (am.dtype != torch.float32 and am.dtype not in _LOWP_KIND):
+        raise TypeError("am and lm must have the same dtype: float32, bfloat16 or float16")
+    if activation not in _ACT_KIND:
+        raise ValueError(f"do_rnnt_pruning_act: activation must be 'tanh' or 'relu', got {activation!r}")
+    if am.dim() != 3 or lm.dim() != 3 or ranges.dim() != 3 or am.shape[2] != lm.shape[2]:
+        raise ValueError("do_rnnt_pruning_act: am [B,T,C], lm [B,S+1,C] and ranges [B,T,s_range] expected")
+    if ranges.shape[0] != am.shape[0] or ranges.shape[0] != lm.shape[0] or am.shape[1] != ranges.shape[1]:
+        raise ValueError("do_rnnt_pruning_act: inconsistent shapes")
+    ranges = ranges.to(torch.int32).contiguous()
+    return _DoPruningAct.apply(am, lm, ranges, _ACT_KIND[activation])
+
+
 def _pruned_call(name, hat, x, head, tail):
     """One logits-reading entry point on ``x``: ``ftr_[hat_]<name>_f32(x, *head, *tail)`` for float32 logits,
     ``ftr_<name>_dt(x, kind, *head, flags, *tail)`` for bfloat16 / float16 (``tail``: the stream)."""
