@@ -1,4 +1,4 @@
-// csrc/capi.hip -- the extern "C" surface declared in include/ftr.h, include/ftr_lowp.h, include/ftr_prune_sum.h, include/ftr_joiner_act.h, include/ftr_kd.h and include/ftr_fused.h: argument validation and error reporting.  No
+// csrc/capi.hip -- the extern "C" surface declared in include/ftr.h, include/ftr_lowp.h, include/ftr_prune_sum.h, include/ftr_joiner_act.h, include/ftr_kd.h, include/ftr_fused.h and include/ftr_live.h: argument validation and error reporting.  No
 // allocation, no host synchronisation, no CPU fallback.  Built twice: into libftr_hip.so (the product: the symbols of
 // ftr.h and ftr_lowp.h and nothing else) and, with -DFTR_DIAG, into the test-only _build/libftr_hip_diag.so, which adds the symbols of
 // include/ftr_diag.h: the "plain" kernel family (the reference's arithmetic on the device, mi_plain.hip), its
@@ -537,13 +537,14 @@ int ftr_smoothed_logprobs_fwd_pen_f32(const float* am, const float* lm, const in
 // the entries without a scale pass {NULL, stride 0, 1.0}, which passes the stride check and multiplies by one
 static int bwd_w_entry(const char* what, const float* gpx, const float* gpy, const float* scale, int scale_stride,
                        float scale_mul, const float* prod, const int32_t* boundary, float combined_scale, float* W,
-                       float* rsx, float* rsy, int B, int T, int S, int modified, void* stream) {
+                       float* rsx, float* rsy, int B, int T, int S, int modified, void* stream, int32_t* live = nullptr,
+                       bool want_live = false) {
   clear_error();
   FTR_TRY(check_sizes(what, B >= 0 && T >= 1 && S >= 0));
   FTR_TRY(check_scale_stride(what, scale_stride));
   if (B == 0) return FTR_OK;
-  FTR_TRY(pointers_then_device(what, gpy && prod && W && rsx && rsy && (gpx || S == 0)));
-  return simple_logprobs_bwd_w(gpx, gpy, Scale{scale, scale_stride, scale_mul}, prod, boundary, W, rsx, rsy, combined_scale, B, T, S, modified, stream_of(stream));
+  FTR_TRY(pointers_then_device(what, gpy && prod && W && rsx && rsy && (gpx || S == 0) && (live || !want_live)));
+  return simple_logprobs_bwd_w(gpx, gpy, Scale{scale, scale_stride, scale_mul}, prod, boundary, W, rsx, rsy, combined_scale, B, T, S, modified, stream_of(stream), live);
 }
 
 int ftr_simple_logprobs_bwd_w_f32(const float* gpx, const float* gpy, const float* prod, const int32_t* boundary,
@@ -767,13 +768,13 @@ static int fused_bwd_am_w_entry(const char* what, bool smoothed, const float* gp
                                 const float* am_probs, const int32_t* symbols, const int32_t* boundary,
                                 int termination_symbol, float direct_scale, const float* unigram, const float* am_dot,
                                 float am_only_scale, float* R, float* d_am, int B, int T, int S, int C, int modified,
-                                void* stream) {
+                                void* stream, const int32_t* live = nullptr, bool want_live = false) {
   clear_error();
   FTR_TRY(check_builder(what, B >= 0 && T >= 1 && S >= 0 && C >= 1, termination_symbol, C, true));
   FTR_TRY(check_scale_stride(what, scale_stride));
   if (B == 0) return FTR_OK;
-  FTR_TRY(pointers_then_device(what, gpy && W && lm_probs && am_probs && d_am && (!smoothed || (unigram && am_dot && R)) && (gpx || S == 0) && (symbols || S == 0)));
-  return simple_fused_bwd_am_w(gpx, gpy, Scale{scale, scale_stride, scale_mul}, W, lm_probs, am_probs, symbols, boundary, termination_symbol, direct_scale, unigram, am_dot, am_only_scale, R, d_am, B, T, S, C, modified, stream_of(stream));
+  FTR_TRY(pointers_then_device(what, gpy && W && lm_probs && am_probs && d_am && (!smoothed || (unigram && am_dot && R)) && (gpx || S == 0) && (symbols || S == 0) && (live || !want_live)));
+  return simple_fused_bwd_am_w(gpx, gpy, Scale{scale, scale_stride, scale_mul}, W, lm_probs, am_probs, symbols, boundary, termination_symbol, direct_scale, unigram, am_dot, am_only_scale, R, d_am, B, T, S, C, modified, stream_of(stream), live);
 }
 
 int ftr_simple_logprobs_fused_bwd_am_w_f32(const float* gpx, const float* gpy, const float* scale, int scale_stride,
@@ -793,6 +794,37 @@ int ftr_smoothed_logprobs_fused_bwd_am_w_f32(const float* gpx, const float* gpy,
 }
 
 int ftr_simple_logprobs_fused_bwd_am_w_columns(int B, int T, int C) { return simple_fused_bwd_columns(B, T, C); }
+
+// ---- include/ftr_live.h: the W kernel with its table of live frame intervals, and the fused d am kernel that reads it
+int ftr_simple_logprobs_bwd_w_live_f32(const float* gpx, const float* gpy, const float* scale, int scale_stride,
+                                       float scale_mul, const float* prod, const int32_t* boundary, float* W, float* rsx,
+                                       float* rsy, int32_t* live, int B, int T, int S, int modified, void* stream) {
+  return bwd_w_entry("simple_logprobs_bwd_w_live", gpx, gpy, scale, scale_stride, scale_mul, prod, boundary, 1.0f, W, rsx, rsy, B, T, S, modified, stream, live, true);
+}
+
+int ftr_smoothed_logprobs_bwd_w_live_f32(const float* gpx, const float* gpy, const float* scale, int scale_stride,
+                                         float scale_mul, const float* prod, const int32_t* boundary, float combined_scale,
+                                         float* W, float* rsx, float* rsy, int32_t* live, int B, int T, int S, int modified,
+                                         void* stream) {
+  return bwd_w_entry("smoothed_logprobs_bwd_w_live", gpx, gpy, scale, scale_stride, scale_mul, prod, boundary, combined_scale, W, rsx, rsy, B, T, S, modified, stream, live, true);
+}
+
+int ftr_simple_logprobs_fused_bwd_am_live_f32(const float* gpx, const float* gpy, const float* scale, int scale_stride,
+                                              float scale_mul, const float* W, const int32_t* live, const float* lm_probs,
+                                              const float* am_probs, const int32_t* symbols, const int32_t* boundary,
+                                              int termination_symbol, float* d_am, int B, int T, int S, int C, int modified,
+                                              void* stream) {
+  return fused_bwd_am_w_entry("simple_logprobs_fused_bwd_am_live", false, gpx, gpy, scale, scale_stride, scale_mul, W, lm_probs, am_probs, symbols, boundary, termination_symbol, 1.0f, nullptr, nullptr, 0.0f, nullptr, d_am, B, T, S, C, modified, stream, live, true);
+}
+
+int ftr_smoothed_logprobs_fused_bwd_am_live_f32(const float* gpx, const float* gpy, const float* scale, int scale_stride,
+                                                float scale_mul, const float* W, const int32_t* live, const float* lm_probs,
+                                                const float* am_probs, const int32_t* symbols, const int32_t* boundary,
+                                                int termination_symbol, float direct_scale, const float* unigram,
+                                                const float* am_dot, float am_only_scale, float* R, float* d_am, int B, int T,
+                                                int S, int C, int modified, void* stream) {
+  return fused_bwd_am_w_entry("smoothed_logprobs_fused_bwd_am_live", true, gpx, gpy, scale, scale_stride, scale_mul, W, lm_probs, am_probs, symbols, boundary, termination_symbol, direct_scale, unigram, am_dot, am_only_scale, R, d_am, B, T, S, C, modified, stream, live, true);
+}
 
 int ftr_mutual_information_band_supported(int T, int S, int r) { return mi_band_supported(T, S, r); }
 

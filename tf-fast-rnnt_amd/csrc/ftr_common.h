@@ -150,6 +150,16 @@ __device__ __forceinline__ float wave_max_dpp(float v) {
   v = fmaxf(v, dpp_take<0x143, 0xc, 0xf>(ninf, v));
   return __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, v), 63));
 }
+__device__ __forceinline__ int wave_max_int_dpp(int v) {   // the same ladder on integers (identity: the smallest int)
+  constexpr int lo = -2147483647 - 1;
+  v = max(v, __builtin_amdgcn_update_dpp(lo, v, 0x111, 0xf, 0xf, false));
+  v = max(v, __builtin_amdgcn_update_dpp(lo, v, 0x112, 0xf, 0xf, false));
+  v = max(v, __builtin_amdgcn_update_dpp(lo, v, 0x114, 0xf, 0xe, false));
+  v = max(v, __builtin_amdgcn_update_dpp(lo, v, 0x118, 0xf, 0xc, false));
+  v = max(v, __builtin_amdgcn_update_dpp(lo, v, 0x142, 0xa, 0xf, false));
+  v = max(v, __builtin_amdgcn_update_dpp(lo, v, 0x143, 0xc, 0xf, false));
+  return __builtin_amdgcn_readlane(v, 63);
+}
 
 // ---- per-utterance shift of the recursion's operands (mi_wave_bidir.hip, mi_band.hip)
 // The recursion is invariant under px -> px - cx, py -> py - cy with constants per utterance: every complete path takes
@@ -283,7 +293,8 @@ int simple_rowdot(const float* x, const float* v, float* dot, size_t rows, int C
 size_t simple_colsum_workspace_floats(size_t rows, int C);
 int simple_colsum_weighted(const float* x, const float* w, float* out, float* ws, size_t ws_floats, size_t rows, int C, hipStream_t st);
 int simple_logprobs_fwd(const float* am, const float* lm, const int32_t* symbols, const float* prod, const float* am_max, const float* lm_max, const int32_t* boundary, int blank, double delay_penalty, const float* lmonly_norm, const float* amonly_norm, const float* ulog, float cs, float ls, float as, float* px, float* py, int B, int T, int S, int C, int modified, hipStream_t st);
-int simple_logprobs_bwd_w(const float* gpx, const float* gpy, Scale scale, const float* prod, const int32_t* boundary, float* W, float* rsx, float* rsy, float cs, int B, int T, int S, int modified, hipStream_t st);
+int simple_logprobs_bwd_w(const float* gpx, const float* gpy, Scale scale, const float* prod, const int32_t* boundary, float* W, float* rsx, float* rsy, float cs, int B, int T, int S, int modified, hipStream_t st, int32_t* live = nullptr);   // live [B,S+1,2]: the rows' live frame intervals
+int bwd_live_dense();   // FTR_BWD_LIVE=dense: the W kernel reports every interval as [0, T)
 int simple_logprobs_bwd_am(const float* gpx, const float* gpy, Scale scale, const float* damp, const float* am_probs, const int32_t* symbols, const int32_t* boundary, int blank, float kdir, const float* uvec, const float* amdot, float as, float* Rout, float* d_am, int B, int T, int S, int C, int modified, hipStream_t st);
 int simple_logprobs_bwd_lm(const float* dlmp, const float* lm_probs, const int32_t* symbols, const float* rsx, const float* rsy, int blank, float kdir, const float* arow, const float* invsum, const float* gu, float* d_lm, int B, int S, int C, hipStream_t st);
 int simple_fused_supported(int C);
@@ -294,7 +305,7 @@ int normalizer_gemm_set_choice(int kind, int B, int T, int S1, int C, int soluti
 int simple_fused_fwd(const float* am, const float* lm, const int32_t* symbols, const float* am_probs, const float* lm_probs, const float* am_max, const float* lm_max, const int32_t* boundary, int blank, double delay_penalty, const float* lmonly_norm, const float* amonly_norm, const float* ulog, float cs, float ls, float as, float* px, float* py, float* prod_out, int B, int T, int S, int C, int modified, hipStream_t st);
 int simple_fused_bwd_am(const float* gpx, const float* gpy, Scale scale, const float* prod, const float* lm_probs, const float* am_probs, const int32_t* symbols, const int32_t* boundary, int blank, float cs, float kdir, const float* uvec, const float* amdot, float as, float* Rout, float* d_am, int B, int T, int S, int C, int modified, hipStream_t st);
 int simple_fused_bwd_columns(int B, int T, int C);   // columns per workgroup (128 | 256) the W-operand kernel takes for a shape
-int simple_fused_bwd_am_w(const float* gpx, const float* gpy, Scale scale, const float* W, const float* lm_probs, const float* am_probs, const int32_t* symbols, const int32_t* boundary, int blank, float kdir, const float* uvec, const float* amdot, float as, float* Rout, float* d_am, int B, int T, int S, int C, int modified, hipStream_t st);
+int simple_fused_bwd_am_w(const float* gpx, const float* gpy, Scale scale, const float* W, const float* lm_probs, const float* am_probs, const int32_t* symbols, const int32_t* boundary, int blank, float kdir, const float* uvec, const float* amdot, float as, float* Rout, float* d_am, int B, int T, int S, int C, int modified, hipStream_t st, const int32_t* live = nullptr);   // live: what simple_logprobs_bwd_w wrote next to W
 int negated_reduce(const float* ans, int B, int reduction, float* out, hipStream_t st, float sign = -1.0f);   // sign = +1: the plain reduction
 // knowledge distillation on the pruned band: csrc/pruned_kd.hip (collapsed != 0: the three-class form; saved: 2 or 4 planes of [B,T,r])
 int pruned_kd_fwd(const void* logits, int dtype, const void* teacher, int teacher_dtype, const int32_t* symbols, const int32_t* ranges, const int32_t* boundary, int blank, float temperature, int collapsed, float* node, float* saved, float* utt, int B, int T, int S, int C, int r, hipStream_t st);

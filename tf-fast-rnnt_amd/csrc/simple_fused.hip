@@ -354,11 +354,12 @@ __host__ __device__ constexpr size_t fused_bwd_lds_bytes() {
 }
 
 template <bool MOD, bool USEW, int NCB>
-__global__ __launch_bounds__(256, NCB <= 8 ? 4 : 2) void simple_fused_bwd_am_kernel(
+__global__ __launch_bounds__(256, NCB <= 8 ? 4 : 3) void simple_fused_bwd_am_kernel(
     const float* __restrict__ gpx, const float* __restrict__ gpy, const Scale scale, const float* __restrict__ prod,
     const float* __restrict__ lm_probs, const float* __restrict__ am_probs, const int32_t* __restrict__ symbols,
     const int32_t* __restrict__ boundary, int blank, float cs, float kdir, const float* __restrict__ uvec,
-    const float* __restrict__ amdot, float as, float* __restrict__ Rout, float* __restrict__ d_am, int T, int S, int C) {
+    const float* __restrict__ amdot, float as, float* __restrict__ Rout, float* __restrict__ d_am, int T, int S, int C,
+    const int32_t* __restrict__ live) {
   extern __shared__ __attribute__((aligned(16))) float smem[];
   // lm tile rows are CT floats apart with no padding: a fragment read is 16 bytes per lane, 16 consecutive lanes = 256
   // contiguous bytes of one k row, and rows a multiple of 256 bytes apart keep the four rows of a k-step on disjoint banks
@@ -390,6 +391,30 @@ __global__ __launch_bounds__(256, NCB <= 8 ? 4 : 2) void simple_fused_bwd_am_ker
   const float* prb = prod + (size_t)b * (S + 1) * T;
   const float* lmb = lm_probs + (size_t)b * (S + 1) * C;
   const int nk = (S + 1 + kBS - 1) / kBS;
+  // ---- the row chunks [kc_lo, kc_hi) that hold a live row for these 64 frames.  `live` [B,S+1,2] (NULL: every chunk) is
+  // the W kernel's table of frame intervals outside which a row's x, y and W are exact zeros: the chunks below the first
+  // and above the last row whose interval meets [t0, t0 + 64) would add products with an exact zero to the accumulators and
+  // exact zeros to the column sums, so neither pass stages them.  One contiguous run: on the lattices measured
+  // (profiles/live_blocks.md) the live chunks of a frame tile have no holes worth a bitmap.
+  int kc_lo = 0, kc_hi = nk;
+  if (live) {
+    const int32_t* lv = live + (size_t)b * (S + 1) * 2;
+    int smin = S + 1, smax = -1;
+    for (int s = tid; s <= S; s += 256) {
+      const int2 iv = *reinterpret_cast<const int2*>(lv + 2 * s);
+      if (iv.x < t0 + kBT && iv.y > t0) { smin = min(smin, s); smax = s; }
+    }
+    smin = -wave_max_int_dpp(-smin); smax = wave_max_int_dpp(smax);
+    int* red = reinterpret_cast<int*>(csb);
+    if (lane == 0) { red[wave] = smin; red[4 + wave] = smax; }
+    __syncthreads();
+    smin = min(min(red[0], red[1]), min(red[2], red[3]));
+    smax = max(max(red[4], red[5]), max(red[6], red[7]));
+    smin = __builtin_amdgcn_readfirstlane(smin); smax = __builtin_amdgcn_readfirstlane(smax);
+    kc_lo = smax < 0 ? 0 : smin / kBS;
+    kc_hi = smax < 0 ? 0 : smax / kBS + 1;
+    __syncthreads();                               // csb is written again after pass 1 (behind barriers of its own when pass 1 runs)
+  }
 
   // ---- staging plan.  lm tile: piece e = tid + 256 u (u < NL) = 4 columns of one of the chunk's rows (column clamped).
   constexpr int NL = (kBS * CT / 4) / 256;         // 4
@@ -482,15 +507,17 @@ __global__ __launch_bounds__(256, NCB <= 8 ? 4 : 2) void simple_fused_bwd_am_ker
         __builtin_amdgcn_sched_barrier(0);
       }
     };
-    Stage g;
-    load(0, g, true);
-    park(0, g);
-    __syncthreads();
-    for (int kc = 0; kc < nk; ++kc) {
-      if (kc + 1 < nk) load(kc + 1, g, true);
-      compute(kc);
-      if (kc + 1 < nk) park(kc + 1, g);
+    if (kc_lo < kc_hi) {
+      Stage g;
+      load(kc_lo, g, true);
+      park(kc_lo, g);
       __syncthreads();
+      for (int kc = kc_lo; kc < kc_hi; ++kc) {
+        if (kc + 1 < kc_hi) load(kc + 1, g, true);
+        compute(kc);
+        if (kc + 1 < kc_hi) park(kc + 1, g);
+        __syncthreads();
+      }
     }
   }
   // ---- column sums over s of x and y for this lane's frame (blank term, R), then acc = am_probs * (acc + u R)
@@ -542,11 +569,12 @@ __global__ __launch_bounds__(256, NCB <= 8 ? 4 : 2) void simple_fused_bwd_am_ker
     int* wcnt = reinterpret_cast<int*>(csb);                                         // [4]; the column sums have been read
     int count = 0;
     const bool listed = S <= 65535;
+    const int r_lo = min(kc_lo * kBS, S), r_hi = min(kc_hi * kBS, S);   // the live chunks' rows of g_px: the others are exact zeros here
     __syncthreads();                               // pass 1 and the column sums are done with wT / csb
     if (listed) {
-      for (int base = 0; base < S; base += 256) {
+      for (int base = r_lo; base < r_hi; base += 256) {
         const int srow = base + tid;
-        const int sy = srow < S ? min(max(symbols[(size_t)b * S + srow], 0), C - 1) : -1;
+        const int sy = srow < r_hi ? min(max(symbols[(size_t)b * S + srow], 0), C - 1) : -1;
         const bool mine = sy >= c0 && sy < c0 + CT;
         const unsigned long long m = __ballot(mine);
         if (lane == 0) wcnt[wave] = __popcll(m);
@@ -561,8 +589,8 @@ __global__ __launch_bounds__(256, NCB <= 8 ? 4 : 2) void simple_fused_bwd_am_ker
       }
     }
     const bool all_rows = !listed || count > kCap;  // (more listed rows than the list holds: every row, as before)
-    if (all_rows) count = S;
-    auto row_of = [&](int i) { return all_rows ? i : (int)rlist[i]; };
+    if (all_rows) count = r_hi - r_lo;
+    auto row_of = [&](int i) { return all_rows ? r_lo + i : (int)rlist[i]; };
     constexpr int NX = kB2 * (kBT / 4) / 256;      // 8 quads per thread and stage
     for (int r0 = 0; r0 < count; r0 += kB2) {
       f4 xv[NX];
@@ -691,7 +719,7 @@ template <bool USEW>
 static int fused_bwd_am_launch(const char* what, int ncb, const float* gpx, const float* gpy, Scale scale, const float* prod_or_w,
                                const float* lm_probs, const float* am_probs, const int32_t* symbols, const int32_t* boundary,
                                int blank, float cs, float kdir, const float* uvec, const float* amdot, float as, float* Rout,
-                               float* d_am, int B, int T, int S, int C, int modified, hipStream_t st) {
+                               float* d_am, int B, int T, int S, int C, int modified, hipStream_t st, const int32_t* live = nullptr) {
   if (!simple_fused_bwd_supported(T, C)) {
     set_error("%s: T = %d, C = %d is outside the fused kernel's domain (T %% 4 == 0, C %% 4 == 0)", what, T, C);
     return FTR_ERR_UNSUPPORTED;
@@ -701,7 +729,7 @@ static int fused_bwd_am_launch(const char* what, int ncb, const float* gpx, cons
   dispatch(modified != 0, [&](auto mod) {
     dispatch_among<8, kBCB>(ncb, [&](auto nb) {
       constexpr int NCB = USEW ? decltype(nb)::value : kBCB;   // the product-operand entry keeps its one tiling
-      hipLaunchKernelGGL((simple_fused_bwd_am_kernel<decltype(mod)::value, USEW, NCB>), grid, dim3(256), fused_bwd_lds_bytes<NCB>(), st, gpx, gpy, scale, prod_or_w, lm_probs, am_probs, symbols, boundary, blank, cs, kdir, uvec, amdot, as, Rout, d_am, T, S, C);
+      hipLaunchKernelGGL((simple_fused_bwd_am_kernel<decltype(mod)::value, USEW, NCB>), grid, dim3(256), fused_bwd_lds_bytes<NCB>(), st, gpx, gpy, scale, prod_or_w, lm_probs, am_probs, symbols, boundary, blank, cs, kdir, uvec, amdot, as, Rout, d_am, T, S, C, live);
     });
   });
   return check_launch(what);
@@ -718,9 +746,9 @@ int simple_fused_bwd_am(const float* gpx, const float* gpy, Scale scale, const f
 int simple_fused_bwd_am_w(const float* gpx, const float* gpy, Scale scale, const float* W, const float* lm_probs,
                           const float* am_probs, const int32_t* symbols, const int32_t* boundary, int blank, float kdir,
                           const float* uvec, const float* amdot, float as, float* Rout, float* d_am, int B, int T, int S,
-                          int C, int modified, hipStream_t st) {
+                          int C, int modified, hipStream_t st, const int32_t* live) {
   const int ncb = simple_fused_bwd_columns(B, T, C) / 16;
-  return fused_bwd_am_launch<true>("simple_logprobs_fused_bwd_am_w", ncb, gpx, gpy, scale, W, lm_probs, am_probs, symbols, boundary, blank, 1.0f, kdir, uvec, amdot, as, Rout, d_am, B, T, S, C, modified, st);
+  return fused_bwd_am_launch<true>("simple_logprobs_fused_bwd_am_w", ncb, gpx, gpy, scale, W, lm_probs, am_probs, symbols, boundary, blank, 1.0f, kdir, uvec, amdot, as, Rout, d_am, B, T, S, C, modified, st, live);
 }
 
 }  // namespace ftr

@@ -10,13 +10,14 @@
 //                          fix_for_boundary, penalty; px and py written once, coalesced along t.  am rows of a
 //                          32-frame tile are staged in LDS (row stride C+1: conflict-free column gathers), so
 //                          am is read from HBM exactly once, coalesced (TF transposes am through HBM for this).
-//   simple_bwd_w_kernel    W = -(gpx + gpy) / (prod + tiny)  and the row sums that feed d lm
+//   simple_bwd_w_kernel    W = -(gpx + gpy) / (prod + tiny)  and the row sums that feed d lm (+ each row's live frame interval)
 //   simple_bwd_am_kernel   d am = (W^T lm_probs) * am_probs + scatter of gpx by symbol + blank column sums;
 //                          the scatter-add over symbols happens in an LDS tile owned by the workgroup
 //                          (each accumulator cell is owned by exactly one thread: deterministic, no atomics)
 //   simple_bwd_lm_kernel   d lm = (W am_probs) * lm_probs + row sums at the symbol / blank columns
 #include "ftr_common.h"
 #include "launch.h"
+#include <string.h>
 
 namespace ftr {
 namespace {
@@ -256,12 +257,21 @@ __global__ void simple_fwd_kernel(const float* __restrict__ am, const float* __r
 // one WAVE per (b, s) row (four rows per workgroup, no barrier): W[b,s,:] and the two row sums.
 // rsx[b,s] = sum_t gpx'[b,s,t] (0 for s == S), rsy[b,s] = sum_t gpy[b,s,t]; gpx' = gpx with the overwritten cells
 // (t == T, t == t_end) masked.  Rows are only 4-byte aligned (T+1 columns): 16-byte accesses through f4u.
+// live (may be NULL) [B,S+1,2]: the half-open frame interval [tlo, thi) outside which the row is DEAD -- x, y and w all
+// exactly zero (of either sign; judged on the bits, so a NaN or a denormal is live) -- and (T, 0) for a row with no live
+// cell.  Away from the paths that carry probability the occupancies underflow to exact zeros; the contractions of the
+// backward skip the blocks no interval reaches (simple_fused.hip), which removes additions of exact zeros and nothing else.
+// live_dense: every interval is [0, T) (FTR_BWD_LIVE=dense: A/B measurements, tests).
+__device__ __forceinline__ bool any_nonzero_bits(float x, float y, float w) {
+  return ((__builtin_bit_cast(unsigned, x) | __builtin_bit_cast(unsigned, y) | __builtin_bit_cast(unsigned, w)) & 0x7fffffffu) != 0u;
+}
 template <bool MOD>
 __global__ __launch_bounds__(256) void simple_bwd_w_kernel(const float* __restrict__ gpx, const float* __restrict__ gpy,
                                                            const Scale scale, const float* __restrict__ prod,
                                                            const int32_t* __restrict__ boundary, float* __restrict__ W,
                                                            float* __restrict__ rsx, float* __restrict__ rsy, float cs,
-                                                           int T, int S, int B) {
+                                                           int T, int S, int B, int32_t* __restrict__ live,
+                                                           int live_dense) {
   const int lane = threadIdx.x & 63;
   const size_t rowid = (size_t)blockIdx.x * 4 + (threadIdx.x >> 6);     // b * (S+1) + s
   if (rowid >= (size_t)B * (S + 1)) return;
@@ -274,6 +284,7 @@ __global__ __launch_bounds__(256) void simple_bwd_w_kernel(const float* __restri
   const float sc = scale.at(b);
   const bool hasx = s < S;
   float sx = 0.0f, sy = 0.0f;
+  int tlo = T, thi = 0;                           // this lane's frames ascend: the first live one sets tlo, every one thi
   const int n4 = T >> 2;
   for (int q = lane; q < n4; q += 64) {
     const int t = 4 * q;
@@ -289,6 +300,8 @@ __global__ __launch_bounds__(256) void simple_bwd_w_kernel(const float* __restri
       const float y = gy[e] * sc;
       sx += x; sy += y;
       w[e] = -cs * (x + y) / (pr[e] + kTiny);   // cs = 1 for the simple loss
+      const bool lv = any_nonzero_bits(x, y, w[e]);
+      tlo = min(tlo, lv ? t + e : T); thi = lv ? t + e + 1 : thi;
     }
     *reinterpret_cast<f4u*>(W + rowy + t) = w;
   }
@@ -297,10 +310,17 @@ __global__ __launch_bounds__(256) void simple_bwd_w_kernel(const float* __restri
     if (hasx && (MOD || t != te)) x = gpx[rowx + t] * sc;
     const float y = gpy[rowy + t] * sc;
     sx += x; sy += y;
-    W[rowy + t] = -cs * (x + y) / (prod[rowy + t] + kTiny);
+    const float w = -cs * (x + y) / (prod[rowy + t] + kTiny);
+    W[rowy + t] = w;
+    if (any_nonzero_bits(x, y, w)) { tlo = min(tlo, t); thi = t + 1; }
   }
   sx = wave_sum(sx); sy = wave_sum(sy);
   if (lane == 0) { rsx[rowid] = sx; rsy[rowid] = sy; }
+  if (live) {
+    tlo = -wave_max_int_dpp(-tlo); thi = wave_max_int_dpp(thi);
+    if (live_dense) { tlo = 0; thi = T; }
+    if (lane == 0) { live[2 * rowid] = tlo; live[2 * rowid + 1] = thi; }
+  }
 }
 
 constexpr int kBwdAmPF = 1;   // frames whose write-out operands are fetched at the top of the kernel.  Measured (study builds,
@@ -626,12 +646,21 @@ int simple_logprobs_fwd(const float* am, const float* lm, const int32_t* symbols
   });
 }
 
+// FTR_BWD_LIVE=dense: every live interval is reported as [0, T), so the kernels that read the table walk every block, as
+// before the table existed (A/B measurements, and the tests that compare skipping with not skipping)
+int bwd_live_dense() {
+  const char* e = getenv("FTR_BWD_LIVE");
+  return (e && strcmp(e, "dense") == 0) ? 1 : 0;
+}
+
 int simple_logprobs_bwd_w(const float* gpx, const float* gpy, Scale scale, const float* prod, const int32_t* boundary,
-                          float* W, float* rsx, float* rsy, float cs, int B, int T, int S, int modified, hipStream_t st) {
+                          float* W, float* rsx, float* rsy, float cs, int B, int T, int S, int modified, hipStream_t st,
+                          int32_t* live) {
   const size_t rows = (size_t)B * (S + 1);
+  const int live_dense = bwd_live_dense();
   const dim3 grid((unsigned)((rows + 3) / 4));
   dispatch(modified != 0, [&](auto mod) {
-    hipLaunchKernelGGL(simple_bwd_w_kernel<decltype(mod)::value>, grid, dim3(256), 0, st, gpx, gpy, scale, prod, boundary, W, rsx, rsy, cs, T, S, B);
+    hipLaunchKernelGGL(simple_bwd_w_kernel<decltype(mod)::value>, grid, dim3(256), 0, st, gpx, gpy, scale, prod, boundary, W, rsx, rsy, cs, T, S, B, live, live_dense);
   });
   return check_launch("simple_logprobs_bwd_w");
 }

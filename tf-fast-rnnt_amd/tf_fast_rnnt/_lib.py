@@ -134,6 +134,14 @@ _FUSED_SIGNATURES = {
     "ftr_smoothed_logprobs_fused_bwd_am_w_f32": (_i, [_c_fp, _c_fp, _c_fp, _i, _f, _c_fp, _c_fp, _c_fp, _c_ip, _c_ip, _i, _f, _c_fp, _c_fp, _f, _c_fp, _c_fp, _i, _i, _i, _i, _i, _c_st]),
     "ftr_simple_logprobs_fused_bwd_am_w_columns": (_i, [_i, _i, _i]),
 }
+# include/ftr_live.h, the builder's backward on the live part of the lattice: the _scaled W entries with `live` [B,S+1,2] (int32)
+# behind rsy, and the W-operand d am entries with `live` behind W
+_LIVE_SIGNATURES = {
+    "ftr_simple_logprobs_bwd_w_live_f32": (_i, [_c_fp, _c_fp, _c_fp, _i, _f, _c_fp, _c_ip, _c_fp, _c_fp, _c_fp, _c_ip, _i, _i, _i, _i, _c_st]),
+    "ftr_smoothed_logprobs_bwd_w_live_f32": (_i, [_c_fp, _c_fp, _c_fp, _i, _f, _c_fp, _c_ip, _f, _c_fp, _c_fp, _c_fp, _c_ip, _i, _i, _i, _i, _c_st]),
+    "ftr_simple_logprobs_fused_bwd_am_live_f32": (_i, [_c_fp, _c_fp, _c_fp, _i, _f, _c_fp, _c_ip, _c_fp, _c_fp, _c_ip, _c_ip, _i, _c_fp, _i, _i, _i, _i, _i, _c_st]),
+    "ftr_smoothed_logprobs_fused_bwd_am_live_f32": (_i, [_c_fp, _c_fp, _c_fp, _i, _f, _c_fp, _c_ip, _c_fp, _c_fp, _c_ip, _c_ip, _i, _f, _c_fp, _c_fp, _f, _c_fp, _c_fp, _i, _i, _i, _i, _i, _c_st]),
+}
 # include/ftr_band_tdt.h, the TDT loss on the pruned band itself: the workspace and domain queries, the recursion on
 # band-shaped operands, and the band-shaped twins of the two ftr_tdt_pruned_logprobs_* builders
 _BAND_TDT_SIGNATURES = {
@@ -164,6 +172,7 @@ PRUNE_SUM_SYMBOLS = tuple(_PRUNE_SUM_SIGNATURES) # those of include/ftr_prune_su
 JOINER_ACT_SYMBOLS = tuple(_JOINER_ACT_SIGNATURES)   # those of include/ftr_joiner_act.h
 KD_SYMBOLS = tuple(_KD_SIGNATURES)               # those of include/ftr_kd.h
 FUSED_SYMBOLS = tuple(_FUSED_SIGNATURES)         # those of include/ftr_fused.h
+LIVE_SYMBOLS = tuple(_LIVE_SIGNATURES)           # those of include/ftr_live.h
 BAND_TDT_SYMBOLS = tuple(_BAND_TDT_SIGNATURES)   # those of include/ftr_band_tdt.h
 BAND_MULTIBLANK_SYMBOLS = tuple(_BAND_MULTIBLANK_SIGNATURES)   # those of include/ftr_band_multiblank.h
 BAND_VITERBI_SYMBOLS = tuple(_BAND_VITERBI_SIGNATURES)   # those of include/ftr_band_viterbi.h
@@ -185,7 +194,7 @@ def lib() -> ctypes.CDLL:
                 f"{LIB_PATH} is missing: build the HIP extension first (python -c 'import __graft_entry__ as g; "
                 "g.build()' or make -C tf-fast-rnnt_amd/csrc).  tf_fast_rnnt has no CPU fallback.")
         handle = ctypes.CDLL(LIB_PATH)
-        for name, (restype, argtypes) in {**_SIGNATURES, **_LOWP_SIGNATURES, **_PRUNE_SUM_SIGNATURES, **_JOINER_ACT_SIGNATURES, **_KD_SIGNATURES, **_FUSED_SIGNATURES,
+        for name, (restype, argtypes) in {**_SIGNATURES, **_LOWP_SIGNATURES, **_PRUNE_SUM_SIGNATURES, **_JOINER_ACT_SIGNATURES, **_KD_SIGNATURES, **_FUSED_SIGNATURES, **_LIVE_SIGNATURES,
                                             **_BAND_TDT_SIGNATURES, **_BAND_MULTIBLANK_SIGNATURES, **_BAND_VITERBI_SIGNATURES}.items():
             fn = getattr(handle, name)   # AttributeError here = header/library mismatch
             fn.restype = restype

@@ -135,6 +135,13 @@ def _use_fused_builder_bwd(T: int, C: int, B: int = 1) -> bool:
     return True
 
 
+def _live_scratch(d_lm: torch.Tensor, B: int, S: int) -> torch.Tensor:
+    """The table of live frame intervals [B,S+1,2] (int32, include/ftr_live.h) in the first bytes of d_lm's own storage: the W
+    kernel writes it, the fused d am kernel reads it, and only then does the last kernel of the backward (ftr_*_logprobs_bwd_lm_f32,
+    same stream) write d_lm [B,S+1,C], every element of it.  C >= 4 on the fused route, so the table fits; no allocation."""
+    return d_lm.view(-1)[:2 * B * (S + 1)].view(torch.int32).view(B, S + 1, 2)
+
+
 def _simple_builder(amc, lmc, symbols, am_probs, lm_probs, am_max, lm_max, boundary, blank, delay_penalty, px, py,
                     B, T, S, C, modified, st):
     """normalisers + px / py of get_rnnt_logprobs (rnnt_loss.py:180-221): one fused launch, or library GEMM + epilogue.
@@ -186,14 +193,20 @@ def _simple_backward(saved, meta, gpx, gpy, scale=None, stride=0, mul=1.0):
     rsx = torch.empty((B, S + 1), dtype=torch.float32, device=dev)
     rsy = torch.empty((B, S + 1), dtype=torch.float32, device=dev)
     d_am = torch.empty_like(am_probs); d_lm = torch.empty_like(lm_probs)
+    fused = _use_fused_builder_bwd(T, C, B)
     with torch.cuda.device(dev):
         st = _stream_ptr(am_probs)
-        _lib.call("ftr_simple_logprobs_bwd_w_scaled_f32", _ptr(gpx), _ptr(gpy), _ptr(scale), stride, mul,
-                  _ptr(prod), _ptr(boundary), _ptr(W), _ptr(rsx), _ptr(rsy), B, T, S, modified, st)
+        if fused:     # W and, per row, the frame interval outside which it and the occupancies are exact zeros
+            live = _live_scratch(d_lm, B, S)
+            _lib.call("ftr_simple_logprobs_bwd_w_live_f32", _ptr(gpx), _ptr(gpy), _ptr(scale), stride, mul,
+                      _ptr(prod), _ptr(boundary), _ptr(W), _ptr(rsx), _ptr(rsy), _ptr(live), B, T, S, modified, st)
+        else:
+            _lib.call("ftr_simple_logprobs_bwd_w_scaled_f32", _ptr(gpx), _ptr(gpy), _ptr(scale), stride, mul,
+                      _ptr(prod), _ptr(boundary), _ptr(W), _ptr(rsx), _ptr(rsy), B, T, S, modified, st)
         dlmp = _gemm(1, W, am_probs, B, T, S, C, st)         # [B,S+1,C]
-        if _use_fused_builder_bwd(T, C, B):                    # W^T lm_probs inside the d am kernel, W as it stands
-            _lib.call("ftr_simple_logprobs_fused_bwd_am_w_f32", _ptr(gpx), _ptr(gpy), _ptr(scale), stride, mul,
-                      _ptr(W), _ptr(lm_probs), _ptr(am_probs), _ptr(symbols), _ptr(boundary), blank, _ptr(d_am),
+        if fused:                                              # W^T lm_probs inside the d am kernel, over the live row chunks only
+            _lib.call("ftr_simple_logprobs_fused_bwd_am_live_f32", _ptr(gpx), _ptr(gpy), _ptr(scale), stride, mul,
+                      _ptr(W), _ptr(live), _ptr(lm_probs), _ptr(am_probs), _ptr(symbols), _ptr(boundary), blank, _ptr(d_am),
                       B, T, S, C, modified, st)
         else:
             damp = _gemm(2, W, lm_probs, B, T, S, C, st)    # [B,T,C]
@@ -1750,14 +1763,20 @@ def _smoothed_backward(saved, meta, gpx, gpy, scale=None, stride=0, mul=1.0):
     rsy = torch.empty((B, S + 1), dtype=torch.float32, device=dev)
     R = torch.empty((B, T), dtype=torch.float32, device=dev)
     d_am = torch.empty_like(am_probs); d_lm = torch.empty_like(lm_probs)
+    fused = _use_fused_builder_bwd(T, C, B)
     with torch.cuda.device(dev):
         st = _stream_ptr(am_probs)
-        _lib.call("ftr_smoothed_logprobs_bwd_w_scaled_f32", _ptr(gpx), _ptr(gpy), _ptr(scale), stride, mul, _ptr(prod),
-                  _ptr(boundary), cs, _ptr(W), _ptr(rsx), _ptr(rsy), B, T, S, modified, st)
+        if fused:     # W and, per row, the frame interval outside which it and the occupancies are exact zeros
+            live = _live_scratch(d_lm, B, S)
+            _lib.call("ftr_smoothed_logprobs_bwd_w_live_f32", _ptr(gpx), _ptr(gpy), _ptr(scale), stride, mul, _ptr(prod),
+                      _ptr(boundary), cs, _ptr(W), _ptr(rsx), _ptr(rsy), _ptr(live), B, T, S, modified, st)
+        else:
+            _lib.call("ftr_smoothed_logprobs_bwd_w_scaled_f32", _ptr(gpx), _ptr(gpy), _ptr(scale), stride, mul, _ptr(prod),
+                      _ptr(boundary), cs, _ptr(W), _ptr(rsx), _ptr(rsy), B, T, S, modified, st)
         dlmp = _gemm(1, W, am_probs, B, T, S, C, st)         # [B,S+1,C]
-        if _use_fused_builder_bwd(T, C, B):                    # W^T lm_probs inside the d am kernel, W as it stands
-            _lib.call("ftr_smoothed_logprobs_fused_bwd_am_w_f32", _ptr(gpx), _ptr(gpy), _ptr(scale), stride, mul, _ptr(W),
-                      _ptr(lm_probs), _ptr(am_probs), _ptr(symbols), _ptr(boundary), blank, cs + a_s, _ptr(u),
+        if fused:                                              # W^T lm_probs inside the d am kernel, over the live row chunks only
+            _lib.call("ftr_smoothed_logprobs_fused_bwd_am_live_f32", _ptr(gpx), _ptr(gpy), _ptr(scale), stride, mul, _ptr(W),
+                      _ptr(live), _ptr(lm_probs), _ptr(am_probs), _ptr(symbols), _ptr(boundary), blank, cs + a_s, _ptr(u),
                       _ptr(am_dot), a_s, _ptr(R), _ptr(d_am), B, T, S, C, modified, st)
         else:
             damp = _gemm(2, W, lm_probs, B, T, S, C, st)    # [B,T,C]
