@@ -1219,6 +1219,92 @@ int ftr_tdt_pruned_band_bwd_scaled_f32(const float* logits, const int32_t* symbo
                       Scale{scale, scale_stride, scale_mul}, glogits, B, T, S, C, r, stream_of(stream));
 }
 
+// ---- include/ftr_tdt_mix.h: the TDT loss mixed with the ordinary loss on the token head (the <MIX> kernels of
+// csrc/tdt_logprobs.hip).  band: the band-shaped twin.  Checked as the TDT builders are, the new arguments after sigma.
+namespace {
+int tdt_mix_fwd_entry(int band, const char* what, const float* logits, const int32_t* symbols, const int32_t* ranges,
+                      const int32_t* boundary, int termination_symbol, const int32_t* durations, int N, double sigma, int parts,
+                      double delay_penalty, float* lse_tok, float* lse_dur, float* px, float* py, float* px0, float* py0, int B,
+                      int T, int S, int C, int r, void* stream) {
+  clear_error();
+  FTR_TRY(tdt_check_head(what, durations, N, sigma, termination_symbol, C));
+  FTR_REQUIRE(parts >= 1 && parts <= 3, "%s: parts = %d, must be 1 (the TDT planes), 2 (the ordinary planes) or 3 (both)", what, parts);
+  FTR_TRY(check_sizes(what, B >= 0 && T >= 1 && S >= 0 && r >= 1));
+  FTR_TRY(check_s_range(what, r, S));
+  if (B == 0) return FTR_OK;
+  const bool lat0 = !band && S == 0;    // the lattices of shape [.,S,.] are empty then
+  const bool tdt_there = !(parts & FTR_TDT_MIX_TDT) || (py && (px || lat0));
+  const bool rnnt_there = !(parts & FTR_TDT_MIX_RNNT) || (py0 && (px0 || lat0));
+  FTR_TRY(pointers_then_device(what, logits && ranges && lse_tok && lse_dur && tdt_there && rnnt_there && (symbols || S == 0)));
+  return tdt_mix_fwd(band, logits, symbols, ranges, boundary, termination_symbol, durations, N, sigma, parts, delay_penalty, lse_tok,
+                     lse_dur, px, py, px0, py0, B, T, S, C, r, stream_of(stream));
+}
+
+int tdt_mix_bwd_entry(int band, const char* what, const float* logits, const int32_t* symbols, const int32_t* ranges,
+                      const int32_t* boundary, int termination_symbol, const int32_t* durations, int N, double sigma,
+                      const float* lse_tok, const float* lse_dur, const float* gpx, const float* gpy, const float* gpx0,
+                      const float* gpy0, const float* scale, int scale_stride, float mul_tdt, float mul_rnnt, float* glogits, int B,
+                      int T, int S, int C, int r, void* stream) {
+  clear_error();
+  FTR_TRY(tdt_check_head(what, durations, N, sigma, termination_symbol, C));
+  FTR_REQUIRE(mul_tdt - mul_tdt == 0.0f && mul_rnnt - mul_rnnt == 0.0f, "%s: mul_tdt = %g and mul_rnnt = %g must be finite", what,
+              (double)mul_tdt, (double)mul_rnnt);
+  FTR_TRY(check_sizes(what, B >= 0 && T >= 1 && S >= 0 && r >= 1));
+  FTR_TRY(check_scale_stride(what, scale_stride));
+  if (B == 0) return FTR_OK;
+  const bool lat0 = !band && S == 0;
+  const bool tdt_there = mul_tdt == 0.0f || (gpy && (gpx || lat0));     // a part with a zero multiplier is not read
+  const bool rnnt_there = mul_rnnt == 0.0f || (gpy0 && (gpx0 || lat0));
+  FTR_TRY(pointers_then_device(what, logits && ranges && lse_tok && lse_dur && tdt_there && rnnt_there && glogits && (symbols || S == 0)));
+  return tdt_mix_bwd(band, logits, symbols, ranges, boundary, termination_symbol, durations, N, lse_tok, lse_dur, gpx, gpy, gpx0, gpy0,
+                     Scale{scale, scale_stride, mul_tdt}, Scale{scale, scale_stride, mul_rnnt}, glogits, B, T, S, C, r,
+                     stream_of(stream));
+}
+}  // namespace
+
+int ftr_tdt_mix_pruned_band_fwd_f32(const float* logits, const int32_t* symbols, const int32_t* ranges,
+                                    const int32_t* boundary, int termination_symbol, const int32_t* durations, int N,
+                                    double sigma, int parts, double delay_penalty, float* lse_tok, float* lse_dur,
+                                    float* px_band, float* py_band, float* px0_band, float* py0_band, int B, int T, int S,
+                                    int C, int r, void* stream) {
+  return tdt_mix_fwd_entry(1, "tdt_mix_pruned_band_fwd", logits, symbols, ranges, boundary, termination_symbol, durations, N, sigma,
+                           parts, delay_penalty, lse_tok, lse_dur, px_band, py_band, px0_band, py0_band, B, T, S, C, r, stream);
+}
+
+int ftr_tdt_mix_pruned_logprobs_fwd_f32(const float* logits, const int32_t* symbols, const int32_t* ranges,
+                                        const int32_t* boundary, int termination_symbol, const int32_t* durations, int N,
+                                        double sigma, int parts, double delay_penalty, float* lse_tok, float* lse_dur,
+                                        float* px, float* py, float* px0, float* py0, int B, int T, int S, int C, int r,
+                                        void* stream) {
+  return tdt_mix_fwd_entry(0, "tdt_mix_pruned_logprobs_fwd", logits, symbols, ranges, boundary, termination_symbol, durations, N,
+                           sigma, parts, delay_penalty, lse_tok, lse_dur, px, py, px0, py0, B, T, S, C, r, stream);
+}
+
+int ftr_tdt_mix_pruned_band_bwd_scaled_f32(const float* logits, const int32_t* symbols, const int32_t* ranges,
+                                           const int32_t* boundary, int termination_symbol, const int32_t* durations, int N,
+                                           double sigma, double delay_penalty, const float* lse_tok, const float* lse_dur,
+                                           const float* gx_band, const float* gy_band, const float* gx0_band,
+                                           const float* gy0_band, const float* scale, int scale_stride, float mul_tdt,
+                                           float mul_rnnt, float* glogits, int B, int T, int S, int C, int r, void* stream) {
+  (void)delay_penalty;   // a constant added to px and px0: no gradient
+  return tdt_mix_bwd_entry(1, "tdt_mix_pruned_band_bwd_scaled", logits, symbols, ranges, boundary, termination_symbol, durations, N,
+                           sigma, lse_tok, lse_dur, gx_band, gy_band, gx0_band, gy0_band, scale, scale_stride, mul_tdt, mul_rnnt,
+                           glogits, B, T, S, C, r, stream);
+}
+
+int ftr_tdt_mix_pruned_logprobs_bwd_scaled_f32(const float* logits, const int32_t* symbols, const int32_t* ranges,
+                                               const int32_t* boundary, int termination_symbol, const int32_t* durations,
+                                               int N, double sigma, double delay_penalty, const float* lse_tok,
+                                               const float* lse_dur, const float* gpx, const float* gpy, const float* gpx0,
+                                               const float* gpy0, const float* scale, int scale_stride, float mul_tdt,
+                                               float mul_rnnt, float* glogits, int B, int T, int S, int C, int r,
+                                               void* stream) {
+  (void)delay_penalty;
+  return tdt_mix_bwd_entry(0, "tdt_mix_pruned_logprobs_bwd_scaled", logits, symbols, ranges, boundary, termination_symbol, durations,
+                           N, sigma, lse_tok, lse_dur, gpx, gpy, gpx0, gpy0, scale, scale_stride, mul_tdt, mul_rnnt, glogits, B, T, S,
+                           C, r, stream);
+}
+
 // ---- include/ftr_band_multiblank.h: the multi-blank loss on the pruned band itself (the multi-blank domain of
 // csrc/mi_band_tdt.hip, the band-shaped mb_* kernels of csrc/pruned_logprobs.hip)
 size_t ftr_mutual_information_band_multiblank_workspace_floats(int B, int T, int S, int r, int D) {

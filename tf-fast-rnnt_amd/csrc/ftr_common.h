@@ -9,6 +9,7 @@
 #include "../../include/ftr_joiner_act.h"
 #include "../../include/ftr_fused.h"
 #include "../../include/ftr_band_tdt.h"
+#include "../../include/ftr_tdt_mix.h"
 #include "../../include/ftr_band_multiblank.h"
 #include "../../include/ftr_band_viterbi.h"
 
@@ -257,6 +258,10 @@ size_t mi_band_tdt_workspace_floats(int B, int T, int S, int r, int N, int Ny, B
 int mi_band_tdt(const float* pxb, const float* pyb, const int32_t* ranges, const int32_t* boundary, const int32_t* token_durations, int N, const int32_t* blank_durations, int Ny, float* ws, size_t ws_floats, float* ans, float* gxb, float* gyb, int B, int T, int S, int r, BandMoveDomain dom, const char* what, hipStream_t st);
 int tdt_band_fwd(const float* logits, const int32_t* symbols, const int32_t* ranges, const int32_t* boundary, int blank, const int32_t* durations, int N, double sigma, double delay_penalty, float* lse_tok, float* lse_dur, float* pxb, float* pyb, int B, int T, int S, int C, int r, hipStream_t st);
 int tdt_band_bwd(const float* logits, const int32_t* symbols, const int32_t* ranges, const int32_t* boundary, int blank, const int32_t* durations, int N, const float* lse_tok, const float* lse_dur, const float* gxb, const float* gyb, Scale scale, float* glogits, int B, int T, int S, int C, int r, hipStream_t st);
+// the omega mix of the TDT and the ordinary loss (include/ftr_tdt_mix.h): the <MIX> instantiations of csrc/tdt_logprobs.hip;
+// band != 0: band-shaped planes, else the lattices; parts: bit 1 the TDT planes, bit 2 the ordinary ones
+int tdt_mix_fwd(int band, const float* logits, const int32_t* symbols, const int32_t* ranges, const int32_t* boundary, int blank, const int32_t* durations, int N, double sigma, int parts, double delay_penalty, float* lse_tok, float* lse_dur, float* px, float* py, float* px0, float* py0, int B, int T, int S, int C, int r, hipStream_t st);
+int tdt_mix_bwd(int band, const float* logits, const int32_t* symbols, const int32_t* ranges, const int32_t* boundary, int blank, const int32_t* durations, int N, const float* lse_tok, const float* lse_dur, const float* gpx, const float* gpy, const float* gpx0, const float* gpy0, Scale scale, Scale scale0, float* glogits, int B, int T, int S, int C, int r, hipStream_t st);
 // multi-blank on the pruned band (include/ftr_band_multiblank.h): the chain of csrc/mi_band_tdt.hip in its multi-blank
 // domain and the band-shaped builders of csrc/pruned_logprobs.hip
 int mi_band_multiblank(const float* pxb, const float* pyb, const int32_t* ranges, const int32_t* boundary, const int32_t* durations, int D, float* ws, size_t ws_floats, float* ans, float* gxb, float* gyb, int B, int T, int S, int r, hipStream_t st);

@@ -22,6 +22,7 @@ from .mutual_information import mutual_information_recursion_tdt_band      # ...
 from .mutual_information import mutual_information_recursion_multiblank_band   # the multi-blank recursion on the pruned band
 from .rnnt_loss import get_rnnt_logprobs_tdt_joint, get_rnnt_logprobs_tdt_pruned   # MI355X addition: TDT loss, a separate
 from .rnnt_loss import rnnt_loss_tdt, rnnt_loss_tdt_pruned                         # duration head, see there
+from .rnnt_loss import rnnt_loss_tdt_mixed, rnnt_loss_tdt_mixed_pruned             # ... mixed with the ordinary loss (omega)
 from .mutual_information import mutual_information_viterbi_tdt              # MI355X addition: best-path alignment over the
 from .mutual_information import mutual_information_viterbi_tdt_band         # ... and the same alignment on the pruned band itself
 from .rnnt_loss import rnnt_alignment_tdt_pruned, rnnt_alignment_multiblank_pruned   # TDT / multi-blank lattices, see there

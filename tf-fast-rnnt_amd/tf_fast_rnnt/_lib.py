@@ -151,6 +151,16 @@ _BAND_TDT_SIGNATURES = {
     "ftr_tdt_pruned_band_fwd_f32": (_i, [_c_fp, _c_ip, _c_ip, _c_ip, _i, _c_hi, _i, ctypes.c_double, ctypes.c_double, _c_fp, _c_fp, _c_fp, _c_fp, _i, _i, _i, _i, _i, _c_st]),
     "ftr_tdt_pruned_band_bwd_scaled_f32": (_i, [_c_fp, _c_ip, _c_ip, _c_ip, _i, _c_hi, _i, ctypes.c_double, ctypes.c_double, _c_fp, _c_fp, _c_fp, _c_fp, _c_fp, _i, _f, _c_fp, _i, _i, _i, _i, _i, _c_st]),
 }
+# include/ftr_tdt_mix.h, the TDT loss mixed with the ordinary loss on the token head (omega): the two builders that also write
+# the ordinary operands, band shaped and lattice shaped, and the two gradient entries that take both sets of occupancies
+_TDT_MIX_FWD = [_c_fp, _c_ip, _c_ip, _c_ip, _i, _c_hi, _i, ctypes.c_double, _i, ctypes.c_double, _c_fp, _c_fp, _c_fp, _c_fp, _c_fp, _c_fp, _i, _i, _i, _i, _i, _c_st]
+_TDT_MIX_BWD = [_c_fp, _c_ip, _c_ip, _c_ip, _i, _c_hi, _i, ctypes.c_double, ctypes.c_double, _c_fp, _c_fp, _c_fp, _c_fp, _c_fp, _c_fp, _c_fp, _i, _f, _f, _c_fp, _i, _i, _i, _i, _i, _c_st]
+_TDT_MIX_SIGNATURES = {
+    "ftr_tdt_mix_pruned_band_fwd_f32": (_i, _TDT_MIX_FWD),
+    "ftr_tdt_mix_pruned_logprobs_fwd_f32": (_i, _TDT_MIX_FWD),
+    "ftr_tdt_mix_pruned_band_bwd_scaled_f32": (_i, _TDT_MIX_BWD),
+    "ftr_tdt_mix_pruned_logprobs_bwd_scaled_f32": (_i, _TDT_MIX_BWD),
+}
 # include/ftr_band_multiblank.h, the multi-blank loss on the pruned band itself: the workspace and domain queries, the
 # recursion on band-shaped operands, and the band-shaped twins of the two ftr_multiblank_pruned_logprobs_* builders
 _BAND_MULTIBLANK_SIGNATURES = {
@@ -174,6 +184,7 @@ KD_SYMBOLS = tuple(_KD_SIGNATURES)               # those of include/ftr_kd.h
 FUSED_SYMBOLS = tuple(_FUSED_SIGNATURES)         # those of include/ftr_fused.h
 LIVE_SYMBOLS = tuple(_LIVE_SIGNATURES)           # those of include/ftr_live.h
 BAND_TDT_SYMBOLS = tuple(_BAND_TDT_SIGNATURES)   # those of include/ftr_band_tdt.h
+TDT_MIX_SYMBOLS = tuple(_TDT_MIX_SIGNATURES)     # those of include/ftr_tdt_mix.h
 BAND_MULTIBLANK_SYMBOLS = tuple(_BAND_MULTIBLANK_SIGNATURES)   # those of include/ftr_band_multiblank.h
 BAND_VITERBI_SYMBOLS = tuple(_BAND_VITERBI_SIGNATURES)   # those of include/ftr_band_viterbi.h
 band_tdt_recursions = 0   # how many times the band-native TDT recursion has been launched from Python (tests read it)
@@ -183,6 +194,7 @@ FTR_MI_WS_CLEAN = 1   # include/ftr.h
 FTR_DTYPE_F32, FTR_DTYPE_BF16, FTR_DTYPE_FP16 = 0, 1, 2   # include/ftr_lowp.h: the `kind` of the _dt entry points
 FTR_ACT_TANH, FTR_ACT_RELU = 1, 2                          # include/ftr_joiner_act.h: the `act` of its entry points
 FTR_PRUNED_HAT = 1    # include/ftr_lowp.h: their `flags` bit
+FTR_TDT_MIX_TDT, FTR_TDT_MIX_RNNT = 1, 2                   # include/ftr_tdt_mix.h: the `parts` bits of its builders
 
 
 def lib() -> ctypes.CDLL:
@@ -195,7 +207,7 @@ def lib() -> ctypes.CDLL:
                 "g.build()' or make -C tf-fast-rnnt_amd/csrc).  tf_fast_rnnt has no CPU fallback.")
         handle = ctypes.CDLL(LIB_PATH)
         for name, (restype, argtypes) in {**_SIGNATURES, **_LOWP_SIGNATURES, **_PRUNE_SUM_SIGNATURES, **_JOINER_ACT_SIGNATURES, **_KD_SIGNATURES, **_FUSED_SIGNATURES, **_LIVE_SIGNATURES,
-                                            **_BAND_TDT_SIGNATURES, **_BAND_MULTIBLANK_SIGNATURES, **_BAND_VITERBI_SIGNATURES}.items():
+                                            **_BAND_TDT_SIGNATURES, **_TDT_MIX_SIGNATURES, **_BAND_MULTIBLANK_SIGNATURES, **_BAND_VITERBI_SIGNATURES}.items():
             fn = getattr(handle, name)   # AttributeError here = header/library mismatch
             fn.restype = restype
             fn.argtypes = argtypes

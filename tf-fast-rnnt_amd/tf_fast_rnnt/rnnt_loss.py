@@ -1583,8 +1583,8 @@ def rnnt_loss_tdt_pruned(
 
     Prune ranges come from the ordinary ``rnnt_loss_simple``.  They guarantee a path through the band only when
     ``durations`` contains 0 and 1 (the moves of the lattice they were computed on): with other sets a path may have to
-    leave the band, and an utterance without one gets a loss of +inf and zero gradients.  NeMo's ``omega`` is not
-    built in: mix in ``rnnt_loss_pruned`` on the token columns yourself."""
+    leave the band, and an utterance without one gets a loss of +inf and zero gradients.  NeMo's ``omega``, the mix with
+    the ordinary loss on the token columns, is ``rnnt_loss_tdt_mixed_pruned``."""
     if rnnt_type != "regular":
         raise ValueError(f"the TDT loss is defined for rnnt_type 'regular' only, given {rnnt_type}")
     code = _reduction_code(reduction)
@@ -1612,6 +1612,159 @@ def rnnt_loss_tdt(
     return rnnt_loss_tdt_pruned(logits=logits, symbols=symbols, ranges=ranges, termination_symbol=termination_symbol,
                                 durations=durations, boundary=boundary, sigma=sigma, delay_penalty=delay_penalty,
                                 reduction=reduction)
+
+
+# ---- the TDT loss mixed with the ordinary loss on the token head (NeMo's omega; include/ftr_tdt_mix.h)
+
+def _check_omega(omega) -> float:
+    omega = float(omega)
+    if not 0.0 <= omega <= 1.0:        # NaN fails both comparisons
+        raise ValueError(f"omega must be in [0, 1], given {omega}")
+    return omega
+
+
+def _tdt_mix_builder_fwd(x, symbols, ranges, boundary, blank, arr, durs, blank_durs, C, sigma, parts, delay_penalty, band):
+    """The two log-sum-exps and one gather launch for both losses.  ``band``: band-shaped planes (px / py [B,N|Ny,T,r],
+    px0 / py0 [B,T,r]), else the lattices.  Only the planes of ``parts`` exist; the others are None."""
+    B, T, r, _ = x.shape
+    S = symbols.shape[1]
+    new = lambda *shape: torch.empty(shape, dtype=torch.float32, device=x.device)
+    lse_tok, lse_dur = new(B, T, r), new(B, T, r)
+    px = py = px0 = py0 = None
+    if parts & _lib.FTR_TDT_MIX_TDT:
+        px = new(B, len(durs), T, r) if band else new(B, len(durs), S, T + 1)
+        py = new(B, len(blank_durs), T, r) if band else new(B, len(blank_durs), S + 1, T)
+    if parts & _lib.FTR_TDT_MIX_RNNT:
+        px0 = new(B, T, r) if band else new(B, S, T + 1)
+        py0 = new(B, T, r) if band else new(B, S + 1, T)
+    with torch.cuda.device(x.device):
+        _lib.call("ftr_tdt_mix_pruned_band_fwd_f32" if band else "ftr_tdt_mix_pruned_logprobs_fwd_f32", _ptr(x), _ptr(symbols),
+                  _ptr(ranges), _ptr(boundary), blank, arr, len(durs), float(sigma), int(parts), float(delay_penalty),
+                  _ptr(lse_tok), _ptr(lse_dur), _ptr(px), _ptr(py), _ptr(px0), _ptr(py0), B, T, S, C, r, _stream_ptr(x))
+    return lse_tok, lse_dur, px, py, px0, py0
+
+
+class _TdtMixedLoss(torch.autograd.Function):
+    """rnnt_loss_tdt_mixed_pruned for 0 < omega <= 1, the whole chain native and on one stream: one pass over the logits
+    builds the operands of both losses (the ordinary one shares lse_tok), the TDT recursion and the ordinary recursion run
+    back to back (band route: ftr_mutual_information_band_tdt_f32 and ftr_mutual_information_band_ws_f32; lattice route:
+    the full-size twins), ``ans = (1 - omega) ans_tdt + omega ans0`` is formed on the device, and backward() is one
+    launch that turns both sets of occupancies into d loss / d logits.  omega == 1 builds and runs the ordinary part only.
+    ``omega`` is a host float: which branch a call takes is decided on the host, so a captured step keeps its branch."""
+
+    @staticmethod
+    def forward(ctx, logits, symbols, ranges, termination_symbol, durations, omega, boundary, sigma, delay_penalty, code):
+        x = logits.detach().contiguous()
+        need = logits.requires_grad
+        arr, durs, blank_durs, C = _tdt_args(durations, termination_symbol, x.shape[3])
+        B, T, r, _ = x.shape
+        S = symbols.shape[1]
+        blank = int(termination_symbol)
+        tdt = omega < 1.0
+        parts = _lib.FTR_TDT_MIX_RNNT | (_lib.FTR_TDT_MIX_TDT if tdt else 0)
+        ctx.band = (_tdt_band_path_ok(ranges, boundary, T, S, r, len(durs), len(blank_durs))
+                    and _band_path_ok(ranges, boundary, T, S, r))
+        lse_tok, lse_dur, px, py, px0, py0 = _tdt_mix_builder_fwd(x, symbols, ranges, boundary, blank, arr, durs, blank_durs, C,
+                                                                  sigma, parts, delay_penalty, ctx.band)
+        ans_tdt = gx = gy = None
+        if ctx.band:
+            if tdt:
+                ans_tdt, gx, gy = band_tdt_forward_backward(px, py, ranges, S, durs, blank_durs, boundary, need)
+            gx0 = torch.empty((B, T, r), dtype=torch.float32, device=x.device)
+            gy0 = torch.empty((B, T, r), dtype=torch.float32, device=x.device)
+            ans0 = torch.empty((B,), dtype=torch.float32, device=x.device)
+            with torch.cuda.device(x.device):
+                nws = _lib.lib().ftr_mutual_information_band_workspace_floats(B, T, S, r)   # 0: the LDS-resident kernel
+                bws = torch.empty((nws,), dtype=torch.float32, device=x.device) if nws else None
+                _lib.call("ftr_mutual_information_band_ws_f32", _ptr(px0), _ptr(py0), _ptr(ranges), _ptr(boundary), _ptr(bws),
+                          nws, _ptr(ans0), _ptr(gx0), _ptr(gy0), B, T, S, r, 0, _stream_ptr(x))
+                del bws
+        else:
+            if tdt:
+                ans_tdt, gx, gy = tdt_forward_backward(px, py, durs, blank_durs, boundary, need)
+            ans0, gx0, gy0 = mi_forward_backward(px0, py0, boundary, need, ans_grad_is_one=True)
+        del px, py, px0, py0
+        # both factors are finite and, where the TDT part exists, positive: -inf (no TDT path) stays -inf, no 0 * inf
+        ans = torch.add(ans_tdt * (1.0 - omega), ans0, alpha=omega) if tdt else ans0
+        if need:
+            ctx.save_for_backward(x, symbols, ranges, lse_tok, lse_dur, gx, gy, gx0, gy0, boundary)
+        ctx.meta = (blank, arr, len(durs), C, sigma, delay_penalty, int(code), omega)
+        return _negated_reduce_native(ans, code)
+
+    @staticmethod
+    def backward(ctx, g_loss):
+        x, symbols, ranges, lse_tok, lse_dur, gx, gy, gx0, gy0, boundary = ctx.saved_tensors
+        blank, arr, N, C, sigma, delay_penalty, code, omega = ctx.meta
+        scale, stride, mul = _upstream_scale(g_loss, code, x.shape[0])
+        B, T, r, _ = x.shape
+        S = symbols.shape[1]
+        g = torch.empty_like(x)
+        with torch.cuda.device(x.device):
+            _lib.call("ftr_tdt_mix_pruned_band_bwd_scaled_f32" if ctx.band else "ftr_tdt_mix_pruned_logprobs_bwd_scaled_f32",
+                      _ptr(x), _ptr(symbols), _ptr(ranges), _ptr(boundary), blank, arr, N, float(sigma), float(delay_penalty),
+                      _ptr(lse_tok), _ptr(lse_dur), _ptr(gx), _ptr(gy), _ptr(gx0), _ptr(gy0), _ptr(scale), stride,
+                      (1.0 - omega) * mul, omega * mul, _ptr(g), B, T, S, C, r, _stream_ptr(x))
+        return g, None, None, None, None, None, None, None, None, None
+
+
+def rnnt_loss_tdt_mixed_pruned(
+    logits: torch.Tensor,
+    symbols: torch.Tensor,
+    ranges: torch.Tensor,
+    termination_symbol: int,
+    durations,
+    omega: float,
+    boundary: torch.Tensor = None,
+    sigma: float = 0.0,
+    delay_penalty: float = 0.0,
+    reduction: Optional[str] = "mean",
+) -> torch.Tensor:
+    """The TDT loss mixed with the ordinary transducer loss on the token head of the same joiner rows (NeMo's ``omega``;
+    MI355X addition, regular type only).  logits [B,T,s_range,C+N] float32 as for ``rnnt_loss_tdt_pruned``; per utterance
+
+        L[b] = (1 - omega) * L_tdt[b] + omega * L_rnnt[b],        0 <= omega <= 1 (else ValueError)
+
+    ``L_tdt`` is ``rnnt_loss_tdt_pruned(..., reduction="none")`` with the same ``durations``, ``sigma`` and ``delay_penalty``;
+    ``L_rnnt`` is ``rnnt_loss_pruned(logits[..., :C], symbols, ranges, termination_symbol, boundary, "regular",
+    delay_penalty, reduction="none")``: its operands are ``tok[sym]`` and ``tok[blank]`` with ``tok = log_softmax(row[:C])``,
+    without ``sigma``.  This is the deterministic mix, the expectation of a per-step sampled choice between the two losses;
+    it is not claimed to be bit-compatible with NeMo.  A caller that samples passes omega = 0 or 1 per step.
+
+    Both losses come out of one pass: the ordinary loss's normaliser is the token log-sum-exp the TDT builder computes
+    anyway, its operands are written by the same gather, and one gradient launch serves both, so no copy of the token
+    columns and no second [B,T,s_range,C] gradient exist.  ``omega == 0`` is ``rnnt_loss_tdt_pruned`` itself,
+    bit for bit.  ``omega == 1`` builds and runs the ordinary part only; the duration columns get exact zeros.  An utterance
+    without a TDT path inside the band has ``L_tdt = +inf``: with ``omega < 1`` its loss is +inf and its gradient is that
+    of the ordinary part alone.  The band route is taken when the ranges are a band that both band recursions cover
+    (``FTR_PRUNED_ROUTE=lattice`` overrides it); otherwise both parts run on full-size lattices."""
+    omega = _check_omega(omega)
+    if omega == 0.0:
+        return rnnt_loss_tdt_pruned(logits, symbols, ranges, termination_symbol, durations, boundary=boundary, sigma=sigma,
+                                    delay_penalty=delay_penalty, reduction=reduction)
+    code = _reduction_code(reduction)
+    symbols_i, ranges_i, boundary_i = _pruned_inputs(logits, symbols, ranges, boundary)
+    _tdt_args(durations, termination_symbol, logits.shape[3])
+    return _TdtMixedLoss.apply(logits, symbols_i, ranges_i, termination_symbol, tuple(durations), omega, boundary_i,
+                               _check_sigma(sigma), _penalty(delay_penalty), code)
+
+
+def rnnt_loss_tdt_mixed(
+    logits: torch.Tensor,
+    symbols: torch.Tensor,
+    termination_symbol: int,
+    durations,
+    omega: float,
+    boundary: Optional[torch.Tensor] = None,
+    sigma: float = 0.0,
+    delay_penalty: float = 0.0,
+    reduction: Optional[str] = "mean",
+) -> torch.Tensor:
+    """``rnnt_loss_tdt_mixed_pruned`` for unpruned joiner logits [B,T,S+1,C+N], through identity ranges."""
+    omega = _check_omega(omega)
+    ranges = _joint_inputs(logits, symbols)
+    return rnnt_loss_tdt_mixed_pruned(logits=logits, symbols=symbols, ranges=ranges, termination_symbol=termination_symbol,
+                                      durations=durations, omega=omega, boundary=boundary, sigma=sigma,
+                                      delay_penalty=delay_penalty, reduction=reduction)
 
 
 # ---- best-path alignment over the TDT and multi-blank lattices (MI355X addition, no reference counterpart)
