@@ -1,4 +1,4 @@
-// csrc/capi.hip -- the extern "C" surface declared in include/ftr.h, include/ftr_lowp.h, include/ftr_prune_sum.h, include/ftr_joiner_act.h, include/ftr_kd.h, include/ftr_fused.h and include/ftr_live.h: argument validation and error reporting.  No
+// csrc/capi.hip -- the extern "C" surface declared in include/ftr.h, include/ftr_lowp.h, include/ftr_prune_sum.h, include/ftr_joiner_act.h, include/ftr_kd.h, include/ftr_kd_fact.h, include/ftr_fused.h and include/ftr_live.h: argument validation and error reporting.  No
 // allocation, no host synchronisation, no CPU fallback.  Built twice: into libftr_hip.so (the product: the symbols of
 // ftr.h and ftr_lowp.h and nothing else) and, with -DFTR_DIAG, into the test-only _build/libftr_hip_diag.so, which adds the symbols of
 // include/ftr_diag.h: the "plain" kernel family (the reference's arithmetic on the device, mi_plain.hip), its
@@ -1453,6 +1453,59 @@ int ftr_pruned_kd_reduce_f32(const float* utt_loss, int B, int reduction, float*
   FTR_REQUIRE(B >= 1 && reduction >= 0 && reduction <= 2, "pruned_kd_reduce: bad arguments B=%d reduction=%d", B, reduction);
   FTR_TRY(pointers_then_device("pruned_kd_reduce", utt_loss && out));
   return negated_reduce(utt_loss, B, reduction, out, stream_of(stream), 1.0f);
+}
+
+// ---- include/ftr_kd_fact.h: its factored forms (csrc/pruned_kd_fact.hip)
+// kd_check_head, then the factorization and what belongs to it: still before everything else
+static int kd_fact_check_head(const char* what, int kind, int teacher_kind, int mode, float temperature, int factorization,
+                              int n_dur, float dur_weight, int C) {
+  FTR_TRY(kd_check_head(what, kind, teacher_kind, mode, temperature));
+  FTR_REQUIRE(factorization == FTR_KD_FACT_SOFTMAX || factorization == FTR_KD_FACT_HAT || factorization == FTR_KD_FACT_TDT,
+              "%s: unknown factorization %d (FTR_KD_FACT_SOFTMAX = 0, FTR_KD_FACT_HAT = 1, FTR_KD_FACT_TDT = 2)", what, factorization);
+  if (factorization != FTR_KD_FACT_TDT) {
+    FTR_REQUIRE(n_dur == 0, "%s: n_dur = %d, only FTR_KD_FACT_TDT has duration columns", what, n_dur);
+    return FTR_OK;
+  }
+  FTR_REQUIRE(n_dur >= 1 && n_dur <= FTR_KD_FACT_MAX_DUR, "%s: n_dur = %d not in [1,%d]", what, n_dur, FTR_KD_FACT_MAX_DUR);
+  FTR_REQUIRE(n_dur < C, "%s: n_dur = %d leaves no token column in a row of C = %d", what, n_dur, C);
+  FTR_REQUIRE(dur_weight >= 0.0f && dur_weight <= 3.0e38f, "%s: dur_weight %g is not a finite number >= 0", what, (double)dur_weight);
+  return FTR_OK;
+}
+
+int ftr_pruned_kd_fact_fwd_dt(const void* logits, int kind, const void* teacher_logits, int teacher_kind,
+                              const int32_t* symbols, const int32_t* ranges, const int32_t* boundary,
+                              int termination_symbol, float temperature, int mode, float* node_loss, float* saved,
+                              float* utt_loss, int B, int T, int S, int C, int r, int factorization, int n_dur,
+                              float dur_weight, const float* node_weights, void* stream) {
+  const char* what = "pruned_kd_fact_fwd_dt";
+  clear_error();
+  FTR_TRY(kd_fact_check_head(what, kind, teacher_kind, mode, temperature, factorization, n_dur, dur_weight, C));
+  const int hat = factorization == FTR_KD_FACT_HAT;
+  FTR_TRY(check_builder(what, B >= 0 && T >= 1 && S >= 0 && C >= 1 && r >= 1, termination_symbol, C - n_dur, false, hat));
+  if (B == 0) return FTR_OK;
+  FTR_TRY(pointers_then_device(what, logits && teacher_logits && ranges && node_loss && saved && utt_loss && (symbols || S == 0)));
+  return pruned_kd_fact_fwd(logits, kind, teacher_logits, teacher_kind, symbols, ranges, boundary, termination_symbol, temperature,
+                            mode == FTR_KD_COLLAPSED, hat, n_dur, dur_weight, node_weights, node_loss, saved, utt_loss, B, T, S, C, r,
+                            stream_of(stream));
+}
+
+int ftr_pruned_kd_fact_bwd_scaled_dt(const void* logits, int kind, const void* teacher_logits, int teacher_kind,
+                                     const int32_t* symbols, const int32_t* ranges, const int32_t* boundary,
+                                     int termination_symbol, float temperature, int mode, const float* saved,
+                                     const float* scale, int scale_stride, float scale_mul, void* glogits, int B, int T,
+                                     int S, int C, int r, int factorization, int n_dur, float dur_weight,
+                                     const float* node_weights, void* stream) {
+  const char* what = "pruned_kd_fact_bwd_scaled_dt";
+  clear_error();
+  FTR_TRY(kd_fact_check_head(what, kind, teacher_kind, mode, temperature, factorization, n_dur, dur_weight, C));
+  const int hat = factorization == FTR_KD_FACT_HAT;
+  FTR_TRY(check_builder(what, B >= 0 && T >= 1 && S >= 0 && C >= 1 && r >= 1, termination_symbol, C - n_dur, true, hat));
+  FTR_TRY(check_scale_stride(what, scale_stride));
+  if (B == 0) return FTR_OK;
+  FTR_TRY(pointers_then_device(what, logits && teacher_logits && ranges && saved && glogits && (symbols || S == 0)));
+  return pruned_kd_fact_bwd(logits, kind, teacher_logits, teacher_kind, symbols, ranges, boundary, termination_symbol, temperature,
+                            mode == FTR_KD_COLLAPSED, hat, n_dur, dur_weight, node_weights, saved, Scale{scale, scale_stride, scale_mul},
+                            glogits, B, T, S, C, r, stream_of(stream));
 }
 
 int ftr_selftest(void* scratch_dev, void* stream) {

@@ -382,4 +382,10 @@ int pruned_kd_bwd(const void* logits, int dtype, const void* teacher, int teache
   return check_launch("pruned_kd_bwd");
 }
 
+// kd_utt_sum_kernel for the factored forms of pruned_kd_fact.hip: the same kernel, the same summation tree
+int pruned_kd_utt_sum(const float* node, float* utt, int B, int per, hipStream_t st) {
+  hipLaunchKernelGGL(kd_utt_sum_kernel, dim3(B), dim3(256), 0, st, node, utt, per);
+  return check_launch("pruned_kd_utt_sum");
+}
+
 }  // namespace ftr

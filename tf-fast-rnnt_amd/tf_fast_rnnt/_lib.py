@@ -127,6 +127,12 @@ _KD_SIGNATURES = {
     "ftr_pruned_kd_bwd_scaled_dt": (_i, [_c_fp, _i, _c_fp, _i, _c_ip, _c_ip, _c_ip, _i, _f, _i, _c_fp, _c_fp, _i, _f, _c_fp, _i, _i, _i, _i, _i, _c_st]),
     "ftr_pruned_kd_reduce_f32": (_i, [_c_fp, _i, _i, _c_fp, _c_st]),
 }
+# include/ftr_kd_fact.h, its factored forms (HAT, TDT, node weights): the two lists above with (factorization = FTR_KD_FACT_*,
+# n_dur, dur_weight, node_weights) in front of the stream
+_KD_FACT_SIGNATURES = {
+    "ftr_pruned_kd_fact_fwd_dt": (_i, _KD_SIGNATURES["ftr_pruned_kd_fwd_dt"][1][:-1] + [_i, _i, _f, _c_fp, _c_st]),
+    "ftr_pruned_kd_fact_bwd_scaled_dt": (_i, _KD_SIGNATURES["ftr_pruned_kd_bwd_scaled_dt"][1][:-1] + [_i, _i, _f, _c_fp, _c_st]),
+}
 # include/ftr_fused.h, the fused d am kernel with W as an operand: the arguments of ftr_*_logprobs_fused_bwd_am_f32 with W in place
 # of prod (and no combined scale: W carries it)
 _FUSED_SIGNATURES = {
@@ -181,6 +187,7 @@ LOWP_SYMBOLS = tuple(_LOWP_SIGNATURES)           # those of include/ftr_lowp.h
 PRUNE_SUM_SYMBOLS = tuple(_PRUNE_SUM_SIGNATURES) # those of include/ftr_prune_sum.h
 JOINER_ACT_SYMBOLS = tuple(_JOINER_ACT_SIGNATURES)   # those of include/ftr_joiner_act.h
 KD_SYMBOLS = tuple(_KD_SIGNATURES)               # those of include/ftr_kd.h
+KD_FACT_SYMBOLS = tuple(_KD_FACT_SIGNATURES)     # those of include/ftr_kd_fact.h
 FUSED_SYMBOLS = tuple(_FUSED_SIGNATURES)         # those of include/ftr_fused.h
 LIVE_SYMBOLS = tuple(_LIVE_SIGNATURES)           # those of include/ftr_live.h
 BAND_TDT_SYMBOLS = tuple(_BAND_TDT_SIGNATURES)   # those of include/ftr_band_tdt.h
@@ -190,6 +197,8 @@ BAND_VITERBI_SYMBOLS = tuple(_BAND_VITERBI_SIGNATURES)   # those of include/ftr_
 band_tdt_recursions = 0   # how many times the band-native TDT recursion has been launched from Python (tests read it)
 band_multiblank_recursions = 0   # ... and the band-native multi-blank recursion, likewise
 FTR_KD_FULL, FTR_KD_COLLAPSED = 0, 1             # include/ftr_kd.h: the `mode` of the kd entry points
+FTR_KD_FACT_SOFTMAX, FTR_KD_FACT_HAT, FTR_KD_FACT_TDT = 0, 1, 2   # include/ftr_kd_fact.h: the `factorization` of its entry points
+FTR_KD_FACT_MAX_DUR = 5
 FTR_MI_WS_CLEAN = 1   # include/ftr.h
 FTR_DTYPE_F32, FTR_DTYPE_BF16, FTR_DTYPE_FP16 = 0, 1, 2   # include/ftr_lowp.h: the `kind` of the _dt entry points
 FTR_ACT_TANH, FTR_ACT_RELU = 1, 2                          # include/ftr_joiner_act.h: the `act` of its entry points
@@ -206,7 +215,7 @@ def lib() -> ctypes.CDLL:
                 f"{LIB_PATH} is missing: build the HIP extension first (python -c 'import __graft_entry__ as g; "
                 "g.build()' or make -C tf-fast-rnnt_amd/csrc).  tf_fast_rnnt has no CPU fallback.")
         handle = ctypes.CDLL(LIB_PATH)
-        for name, (restype, argtypes) in {**_SIGNATURES, **_LOWP_SIGNATURES, **_PRUNE_SUM_SIGNATURES, **_JOINER_ACT_SIGNATURES, **_KD_SIGNATURES, **_FUSED_SIGNATURES, **_LIVE_SIGNATURES,
+        for name, (restype, argtypes) in {**_SIGNATURES, **_LOWP_SIGNATURES, **_PRUNE_SUM_SIGNATURES, **_JOINER_ACT_SIGNATURES, **_KD_SIGNATURES, **_KD_FACT_SIGNATURES, **_FUSED_SIGNATURES, **_LIVE_SIGNATURES,
                                             **_BAND_TDT_SIGNATURES, **_TDT_MIX_SIGNATURES, **_BAND_MULTIBLANK_SIGNATURES, **_BAND_VITERBI_SIGNATURES}.items():
             fn = getattr(handle, name)   # AttributeError here = header/library mismatch
             fn.restype = restype

@@ -15,7 +15,8 @@ What runs where:
 * ``get_hat_logprobs_pruned`` / ``get_hat_logprobs_joint`` / ``hat_loss_pruned`` / ``hat_loss`` (MI355X addition, no
   reference counterpart): the same kernels and routes with the HAT normalisation of the joiner output.
 * ``rnnt_kd_loss_pruned`` (MI355X addition, no reference counterpart): knowledge distillation on the pruned band, two
-  stream kernels of its own (include/ftr_kd.h, csrc/pruned_kd.hip).
+  stream kernels of its own (include/ftr_kd.h, csrc/pruned_kd.hip); ``rnnt_kd_loss_pruned_factored``: the same for HAT and
+  TDT rows and with node weights (include/ftr_kd_fact.h, csrc/pruned_kd_fact.hip).
 
 Reference bugs that are NOT reproduced: ``rnnt_loss_simple(reduction="mean")``
 raises NameError there (rnnt_loss.py:331) -- here it is the mean; ``boundary=None`` works; the
@@ -1160,6 +1161,159 @@ def rnnt_kd_loss_pruned(
         raise ValueError("teacher_logits and logits must be on the same device")
     return _PrunedKdLoss.apply(logits, teacher_logits, symbols, ranges, int(termination_symbol), boundary, _KD_MODES[mode],
                                temperature, code)
+
+
+_KD_FACTORIZATIONS = {"softmax": _lib.FTR_KD_FACT_SOFTMAX, "hat": _lib.FTR_KD_FACT_HAT, "tdt": _lib.FTR_KD_FACT_TDT}
+
+
+class _PrunedKdFactLoss(torch.autograd.Function):
+    """rnnt_kd_loss_pruned_factored as one node, in the manner of _PrunedKdLoss: the entries of include/ftr_kd_fact.h.
+    Neither the teacher nor the node weights get a gradient."""
+
+    @staticmethod
+    def forward(ctx, logits, teacher_logits, symbols, ranges, termination_symbol, boundary, mode, temperature, code, fact,
+                n_dur, dur_weight, weights):
+        B, T, r, C = logits.shape
+        S = symbols.shape[1]
+        x = logits.detach().contiguous()
+        y = teacher_logits.detach().contiguous()
+        planes = (4 if mode == _lib.FTR_KD_COLLAPSED else 2) + (2 if n_dur > 0 else 0)
+        node = torch.empty((B, T, r), dtype=torch.float32, device=x.device)
+        saved = torch.empty((planes, B, T, r), dtype=torch.float32, device=x.device)
+        utt = torch.empty((B,), dtype=torch.float32, device=x.device)
+        out = utt
+        with torch.cuda.device(x.device):
+            st = _stream_ptr(x)
+            _lib.call("ftr_pruned_kd_fact_fwd_dt", *_kd_head(x, y), _ptr(symbols), _ptr(ranges), _ptr(boundary),
+                      int(termination_symbol), float(temperature), mode, _ptr(node), _ptr(saved), _ptr(utt), B, T, S, C, r,
+                      fact, n_dur, float(dur_weight), _ptr(weights), st)
+            if code != 0:
+                out = torch.empty((), dtype=torch.float32, device=x.device)
+                _lib.call("ftr_pruned_kd_reduce_f32", _ptr(utt), B, code, _ptr(out), st)
+        if logits.requires_grad:
+            ctx.save_for_backward(x, y, symbols, ranges, saved, boundary, weights)
+        ctx.meta = (int(termination_symbol), mode, float(temperature), int(code), fact, n_dur, float(dur_weight))
+        return out
+
+    @staticmethod
+    def backward(ctx, g_loss):
+        x, y, symbols, ranges, saved, boundary, weights = ctx.saved_tensors
+        blank, mode, temperature, code, fact, n_dur, dur_weight = ctx.meta
+        B, T, r, C = x.shape
+        scale, stride, mul = _upstream_scale(g_loss, code, B)   # its multiplier negates: this loss is not a negated score
+        g = torch.empty_like(x)
+        with torch.cuda.device(x.device):
+            _lib.call("ftr_pruned_kd_fact_bwd_scaled_dt", *_kd_head(x, y), _ptr(symbols), _ptr(ranges), _ptr(boundary), blank,
+                      temperature, mode, _ptr(saved), _ptr(scale), stride, -mul, _ptr(g), B, T, symbols.shape[1], C, r,
+                      fact, n_dur, dur_weight, _ptr(weights), _stream_ptr(x))
+        return (g,) + (None,) * 12
+
+
+def rnnt_kd_loss_pruned_factored(
+    logits: torch.Tensor,
+    teacher_logits: torch.Tensor,
+    symbols: torch.Tensor,
+    ranges: torch.Tensor,
+    termination_symbol: int,
+    boundary: Optional[torch.Tensor] = None,
+    factorization: str = "softmax",
+    num_durations: int = 0,
+    mode: str = "full",
+    temperature: float = 1.0,
+    duration_weight: float = 1.0,
+    node_weights: Optional[torch.Tensor] = None,
+    reduction: Optional[str] = "mean",
+) -> torch.Tensor:
+    """``rnnt_kd_loss_pruned`` for joiner rows that are not one softmax, and with per-node weights (MI355X addition, no
+    reference counterpart).  Everything not said here -- shapes, dtypes, validity of a node, ``mode``, ``temperature`` (no
+    temperature ** 2 factor), ``reduction``, NaN and -inf, no teacher gradient -- is as in ``rnnt_kd_loss_pruned``.
+    Below a = student row / temperature, b = teacher row / temperature, Bk = ``termination_symbol``.
+
+    ``factorization="softmax"``: the loss of ``rnnt_kd_loss_pruned``; without ``node_weights``, bit for bit.
+
+    ``factorization="hat"`` (the rows of ``hat_loss_pruned``; C >= 2): the blank is a sigmoid of its own column,
+    qb = sigmoid(a_Bk), and the symbols a softmax u over the columns c != Bk; pb and v likewise from the teacher.
+    ``mode="full"``: KL(Bernoulli(pb) || Bernoulli(qb)) + (1 - pb) sum_{c != Bk} v_c (log v_c - log u_c).
+    ``mode="collapsed"``: the KL over three classes of masses pb, (1 - pb) v_sym and (1 - pb) (1 - v_sym), the last summed
+    over the columns that are neither the blank nor the correct symbol::
+
+        loss = hat_loss_pruned(logits, ...) + lam * rnnt_kd_loss_pruned_factored(logits, teacher_logits, symbols, ranges,
+                                                                                 blank, boundary, factorization="hat")
+
+    ``factorization="tdt"`` (the rows of ``rnnt_loss_tdt_pruned`` / ``rnnt_loss_tdt_mixed_pruned``): the last dimension
+    is C + N with N = ``num_durations`` in 1..5; the first C columns are the token head (``termination_symbol`` < C), the
+    last N the duration head.  Node loss = KL_tok + ``duration_weight`` * KL_dur: KL_tok is the loss of
+    ``rnnt_kd_loss_pruned`` in the given ``mode`` over the token columns, KL_dur always the full KL of the two duration
+    softmaxes; with ``duration_weight=1`` and ``mode="full"`` that is the KL of the joint token x duration distributions.
+    The logits are read where they are: no ``logits[..., :C].contiguous()``.  ``duration_weight`` must be finite and
+    >= 0; with 0 the duration columns are ignored, whatever they hold, and get exact zeros.  For the other two factorizations
+    ``num_durations`` must be 0::
+
+        loss = rnnt_loss_tdt_pruned(logits, ...) + lam * rnnt_kd_loss_pruned_factored(
+            logits, teacher_logits, symbols, ranges, blank, boundary, factorization="tdt", num_durations=len(durations))
+
+    ``node_weights``: None, or a float32 [B,T,s_range] tensor on the device (made contiguous; it never gets a
+    gradient).  The loss of node (b,t,k) and its gradient row are multiplied by w[b,t,k]; a weight of exactly 0 makes
+    the node invalid -- its rows are not read and its loss and gradient row are zeros, whatever the rows hold -- and a
+    NaN weight on an otherwise valid node makes its utterance's loss NaN.  Weights are the caller's contract (finite,
+    >= 0): nothing is checked on the host and nothing synchronises.  The intended use is to distil where the student's
+    own alignment is, with the detached band occupancies that ``rnnt_loss_simple(..., calc_gradients=True)`` returned as
+    ``px_grad`` [B,S,T+1] / ``py_grad`` [B,S+1,T]::
+
+        idx = ranges.long().transpose(1, 2)                                        # [B,s_range,T], rows s of the band
+        w = torch.gather(py_grad.detach(), 1, idx).transpose(1, 2).contiguous()    # occupancy of the blank arc at (s,t)
+        # and / or the symbol arcs: torch.gather(px_grad.detach()[:, :, :T], 1, idx.clamp(max=S - 1))
+        kd = rnnt_kd_loss_pruned_factored(logits, teacher_logits, symbols, ranges, blank, boundary, node_weights=w)
+    """
+    for name, t in (("logits", logits), ("teacher_logits", teacher_logits)):
+        if t.dtype not in _KD_DTYPES:
+            raise TypeError(f"{name} must be float32, bfloat16 or float16, got {t.dtype}")
+    if logits.dim() != 4:
+        raise ValueError("logits must be [B,T,s_range,C]")
+    if tuple(teacher_logits.shape) != tuple(logits.shape):
+        raise ValueError(f"teacher_logits must have the shape of logits {tuple(logits.shape)}, got {tuple(teacher_logits.shape)}")
+    if factorization not in _KD_FACTORIZATIONS:
+        raise ValueError(f"factorization should be ('softmax' | 'hat' | 'tdt'), given {factorization}")
+    if mode not in _KD_MODES:
+        raise ValueError(f"mode should be ('full' | 'collapsed'), given {mode}")
+    temperature = float(temperature)
+    if not (0.0 < temperature < float("inf")):
+        raise ValueError(f"temperature must be a finite number > 0, given {temperature}")
+    W = logits.shape[3]
+    num_durations = int(num_durations)
+    duration_weight = float(duration_weight)
+    if factorization == "tdt":
+        if not 1 <= num_durations <= _lib.FTR_KD_FACT_MAX_DUR:
+            raise ValueError(f"num_durations must be in [1,{_lib.FTR_KD_FACT_MAX_DUR}] for factorization 'tdt', given {num_durations}")
+        if num_durations >= W:
+            raise ValueError(f"num_durations {num_durations} leaves no token column in rows of {W}")
+        if not (0.0 <= duration_weight < float("inf")):
+            raise ValueError(f"duration_weight must be a finite number >= 0, given {duration_weight}")
+    elif num_durations != 0:
+        raise ValueError(f"num_durations must be 0 for factorization '{factorization}', given {num_durations}")
+    C = W - num_durations
+    if factorization == "hat" and C < 2:
+        raise ValueError(f"factorization 'hat' needs a blank and at least one other column, got C = {C}")
+    code = _reduction_code(reduction)
+    if not 0 <= int(termination_symbol) < C:
+        raise ValueError(f"termination_symbol {termination_symbol} not in [0,{C})")
+    if node_weights is not None:
+        if node_weights.dtype != torch.float32:
+            raise TypeError(f"node_weights must be float32, got {node_weights.dtype}")
+        if tuple(node_weights.shape) != tuple(logits.shape[:3]):
+            raise ValueError(f"node_weights must be [B,T,s_range] = {tuple(logits.shape[:3])}, got {tuple(node_weights.shape)}")
+    symbols, ranges, boundary = _pruned_inputs(logits, symbols, ranges, boundary, lowp=True)
+    _require_gpu(teacher_logits, "teacher_logits")
+    if teacher_logits.device != logits.device:
+        raise ValueError("teacher_logits and logits must be on the same device")
+    if node_weights is not None:
+        _require_gpu(node_weights, "node_weights")
+        if node_weights.device != logits.device:
+            raise ValueError("node_weights and logits must be on the same device")
+        node_weights = node_weights.detach().contiguous()
+    return _PrunedKdFactLoss.apply(logits, teacher_logits, symbols, ranges, int(termination_symbol), boundary, _KD_MODES[mode],
+                                   temperature, code, _KD_FACTORIZATIONS[factorization], num_durations, duration_weight,
+                                   node_weights)
 
 
 # ---- multi-blank transducer (MI355X addition, no reference counterpart): big blanks that advance several frames
