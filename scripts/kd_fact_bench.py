@@ -12,7 +12,7 @@ multiple of four), and (b) runs on a tensor of that same width.
 
 (a) is what one would write without the op: float32 log_softmax / logsigmoid of both tensors, the blank masked out of the
 HAT softmax, kl_div (full) or gathers and a masked logsumexp (collapsed), the duration head's kl_div, the validity mask, the
-sums -- and autograd's backward of that.  (b) is code this script's subject does not touch.
+sums -- and autograd's backward of that.  (b) is the plain row form of the same kernels (csrc/pruned_kd.hip).
 Per variant <dtype>_<fact>_<mode>: _fused / _torch / _kd medians, minima and the lowest and highest block median;
 _fused_over_torch and _fused_over_kd (medians); _condition: the fused op's slowest block median is below the composition's
 fastest.  --zero-share S adds a line (first config only) with node weights that are exact zeros on a share S of the nodes:

@@ -3,9 +3,10 @@ definition (tests/kd_restatement.py) on the up-converted values.
 
 Geometry (tests/kd_cases.py): B=2 T=12 S=5 r=3, boundary [[0,0,5,12],[0,0,3,9]], a hand-built band; utterance 1 has invalid
 nodes both by frame and by s > s_end.  C crosses every path of the kernels: 8 (vector path, 2 of 64 lanes live), 37 (element
-path), 500 (c3's vocabulary, 16-bit rows 8- but not 16-byte aligned), 2048 (the largest register-resident row), 2056 (the
-two-pass form).  Inputs are standard normal x 3 rounded to the dtype; in collapsed mode ln C is added to the blank and the
-correct-symbol columns of both tensors so that all three classes carry mass.
+path), 500 (c3's vocabulary, 16-bit rows 8- but not 16-byte aligned), 1000 (four quads per lane, the register width of c4's
+vocabulary), 2048 (the largest register-resident row), 2056 (the two-pass form).  Inputs are standard normal x 3 rounded to
+the dtype; in collapsed mode ln C is added to the blank and the correct-symbol columns of both tensors so that all three
+classes carry mass.
 
 Tolerances, none of them measured from the code under test:
   loss      |err| <= 1e-4 |ref| + 1e-5 per utterance: the project's tolerance against float64
@@ -26,7 +27,7 @@ pytestmark = pytest.mark.gpu
 
 DT = {"f32": (torch.float32, 0.0, 0.0), "bf16": (torch.bfloat16, 2.0 ** -8, 0.0), "fp16": (torch.float16, 2.0 ** -11, 2.0 ** -25)}
 PAIRS = [("f32", "f32"), ("bf16", "bf16"), ("fp16", "fp16"), ("f32", "bf16"), ("bf16", "f32")]   # (student, teacher)
-CS = [8, 37, 500, 2048, 2056]
+CS = [8, 37, 500, 1000, 2048, 2056]
 MODES = ["full", "collapsed"]
 VALID = R.valid_nodes(K.band_ranges(), K.BOUNDARY, K.S)
 _WORST = {}
@@ -117,6 +118,29 @@ def test_loss_and_gradient(ft, dev, C, mode, blank_last, tau, sdt, tdt):
     assert g.dtype == x.dtype and g.shape == x.shape
     frac, gerr = check_grad(g, g64, sdt, what)
     _note(f"{mode} {sdt}/{tdt}", loss_rel_err=rel, grad_err_over_bound=frac, grad_err_over_max=gerr)
+
+
+@pytest.mark.parametrize("mode", MODES)
+@pytest.mark.parametrize("C", [8, 37, 500])
+def test_plain_c_entries_are_the_op_bit_for_bit(ft, dev, C, mode):
+    """ftr_pruned_kd_fwd_dt and ftr_pruned_kd_bwd_scaled_dt (include/ftr_kd.h) called directly, upstream scale 1: the op itself
+    goes through the entries of include/ftr_kd_fact.h, so this is what runs the plain ones on the device."""
+    x, y, sym, blank = inputs(C, mode, False, "f32", "f32")
+    x, y = x.to(dev), y.to(dev)
+    loss, g = run(ft, dev, x, y, sym, blank, mode, 2.0)
+    symd, rg, bd = torch.from_numpy(sym).to(dev), torch.from_numpy(K.band_ranges()).to(dev), torch.from_numpy(K.BOUNDARY).to(dev)
+    code = ft._lib.FTR_KD_COLLAPSED if mode == "collapsed" else ft._lib.FTR_KD_FULL
+    f32 = ft._lib.FTR_DTYPE_F32
+    node = torch.empty((K.B, K.T, K.R), device=dev)
+    saved = torch.empty((4 if mode == "collapsed" else 2, K.B, K.T, K.R), device=dev)
+    utt, gx, one = torch.empty(K.B, device=dev), torch.empty_like(x), torch.ones(K.B, device=dev)
+    st = torch.cuda.current_stream().cuda_stream
+    ft._lib.call("ftr_pruned_kd_fwd_dt", x.data_ptr(), f32, y.data_ptr(), f32, symd.data_ptr(), rg.data_ptr(), bd.data_ptr(), blank,
+                 2.0, code, node.data_ptr(), saved.data_ptr(), utt.data_ptr(), K.B, K.T, K.S, C, K.R, st)
+    ft._lib.call("ftr_pruned_kd_bwd_scaled_dt", x.data_ptr(), f32, y.data_ptr(), f32, symd.data_ptr(), rg.data_ptr(), bd.data_ptr(),
+                 blank, 2.0, code, saved.data_ptr(), one.data_ptr(), 1, 1.0, gx.data_ptr(), K.B, K.T, K.S, C, K.R, st)
+    assert torch.isfinite(utt).all() and (utt > 0).all() and gx.abs().max() > 0
+    assert torch.equal(utt, loss) and torch.equal(gx, g)
 
 
 @pytest.mark.parametrize("sdt,tdt", [("f32", "f32"), ("bf16", "f32")])

@@ -4,7 +4,8 @@ against the float64 restatement of the definition (tests/kd_fact_restatement.py)
 Geometry (tests/kd_fact_cases.py): B=2 T=6 S=4 r=3, boundary [[0,0,4,6],[0,0,2,4]]; utterance 1 has invalid nodes both by
 frame and by s > s_end, and in every loss / gradient comparison here every invalid row of BOTH tensors is NaN.  Row widths W
 (tdt: C = W - N token columns): 12 (register form, one quad per lane), 41 (element by element), 504 with N = 4 and 505 with
-N = 5 (vector against element at c3's vocabulary), 2052 (the two-pass vector form).  Inputs are standard normal x 3 rounded
+N = 5 (vector against element at c3's vocabulary), 2052 (the two-pass vector form); the hat and tdt forms also at 1000 and
+1004 (four quads per lane, the register width of c4's vocabulary).  Inputs are standard normal x 3 rounded
 to the dtype; in collapsed mode ln C is added to the blank and the correct-symbol columns of both tensors.
 
 Tolerances, those of tests/test_gpu_kd.py, none measured from the code under test:
@@ -28,7 +29,7 @@ DT = {"f32": (torch.float32, 0.0, 0.0), "bf16": (torch.bfloat16, 2.0 ** -8, 0.0)
 PAIRS = [("f32", "f32"), ("bf16", "bf16"), ("fp16", "f32"), ("bf16", "fp16")]   # (student, teacher)
 MODES = ["full", "collapsed"]
 WIDTHS = [(12, 4), (41, 4), (504, 4), (505, 5), (2052, 4)]                        # (W, N of the tdt form)
-FORMS = [(fact, W, N if fact == "tdt" else 0) for fact in K.FACTS for W, N in WIDTHS]
+FORMS = [(fact, W, N if fact == "tdt" else 0) for fact in K.FACTS for W, N in WIDTHS] + [("tdt", 1004, 4), ("hat", 1000, 0)]
 MID = {"softmax": (504, 0), "hat": (504, 0), "tdt": (504, 4)}
 # (tau, blank_last, duration_weight): each value of each of the three occurs
 SETTINGS = [(1.0, False, 1.0), (2.0, True, 0.3)]

@@ -1408,58 +1408,14 @@ int ftr_multiblank_pruned_band_bwd_scaled_f32(const float* logits, const int32_t
                              gy_band, Scale{scale, scale_stride, scale_mul}, glogits, B, T, S, C, r, stream_of(stream));
 }
 
-// ---- include/ftr_kd.h: knowledge distillation on the pruned band (csrc/pruned_kd.hip)
-// element type codes, mode and temperature, before everything else
-static int kd_check_head(const char* what, int kind, int teacher_kind, int mode, float temperature) {
+// ---- include/ftr_kd.h, include/ftr_kd_fact.h: knowledge distillation on the pruned band (csrc/pruned_kd.hip)
+// element type codes, mode and temperature, then the factorization and what belongs to it: before everything else
+static int kd_check_head(const char* what, int kind, int teacher_kind, int mode, float temperature, int factorization,
+                         int n_dur, float dur_weight, int C) {
   FTR_TRY(check_dtype(what, kind, 0));
   FTR_TRY(check_dtype(what, teacher_kind, 0));
   FTR_REQUIRE(mode == FTR_KD_FULL || mode == FTR_KD_COLLAPSED, "%s: unknown mode %d (FTR_KD_FULL = 0, FTR_KD_COLLAPSED = 1)", what, mode);
   FTR_REQUIRE(temperature > 0.0f && temperature <= 3.0e38f, "%s: temperature %g is not a finite number > 0", what, (double)temperature);
-  return FTR_OK;
-}
-
-int ftr_pruned_kd_fwd_dt(const void* logits, int kind, const void* teacher_logits, int teacher_kind,
-                         const int32_t* symbols, const int32_t* ranges, const int32_t* boundary, int termination_symbol,
-                         float temperature, int mode, float* node_loss, float* saved, float* utt_loss, int B, int T, int S,
-                         int C, int r, void* stream) {
-  const char* what = "pruned_kd_fwd_dt";
-  clear_error();
-  FTR_TRY(kd_check_head(what, kind, teacher_kind, mode, temperature));
-  FTR_TRY(check_builder(what, B >= 0 && T >= 1 && S >= 0 && C >= 1 && r >= 1, termination_symbol, C));
-  if (B == 0) return FTR_OK;
-  FTR_TRY(pointers_then_device(what, logits && teacher_logits && ranges && node_loss && saved && utt_loss && (symbols || S == 0)));
-  return pruned_kd_fwd(logits, kind, teacher_logits, teacher_kind, symbols, ranges, boundary, termination_symbol, temperature,
-                       mode == FTR_KD_COLLAPSED, node_loss, saved, utt_loss, B, T, S, C, r, stream_of(stream));
-}
-
-int ftr_pruned_kd_bwd_scaled_dt(const void* logits, int kind, const void* teacher_logits, int teacher_kind,
-                                const int32_t* symbols, const int32_t* ranges, const int32_t* boundary,
-                                int termination_symbol, float temperature, int mode, const float* saved,
-                                const float* scale, int scale_stride, float scale_mul, void* glogits, int B, int T, int S,
-                                int C, int r, void* stream) {
-  const char* what = "pruned_kd_bwd_scaled_dt";
-  clear_error();
-  FTR_TRY(kd_check_head(what, kind, teacher_kind, mode, temperature));
-  FTR_TRY(check_builder(what, B >= 0 && T >= 1 && S >= 0 && C >= 1 && r >= 1, termination_symbol, C, true));
-  FTR_TRY(check_scale_stride(what, scale_stride));
-  if (B == 0) return FTR_OK;
-  FTR_TRY(pointers_then_device(what, logits && teacher_logits && ranges && saved && glogits && (symbols || S == 0)));
-  return pruned_kd_bwd(logits, kind, teacher_logits, teacher_kind, symbols, ranges, boundary, termination_symbol, temperature,
-                       mode == FTR_KD_COLLAPSED, saved, Scale{scale, scale_stride, scale_mul}, glogits, B, T, S, C, r, stream_of(stream));
-}
-
-int ftr_pruned_kd_reduce_f32(const float* utt_loss, int B, int reduction, float* out, void* stream) {
-  clear_error();
-  FTR_REQUIRE(B >= 1 && reduction >= 0 && reduction <= 2, "pruned_kd_reduce: bad arguments B=%d reduction=%d", B, reduction);
-  FTR_TRY(pointers_then_device("pruned_kd_reduce", utt_loss && out));
-  return negated_reduce(utt_loss, B, reduction, out, stream_of(stream), 1.0f);
-}
-
-// ---- include/ftr_kd_fact.h: its factored forms (csrc/pruned_kd_fact.hip)
-// kd_check_head, then the factorization and what belongs to it: still before everything else
-static int kd_fact_check_head(const char* what, int kind, int teacher_kind, int mode, float temperature, int factorization,
-                              int n_dur, float dur_weight, int C) {
-  FTR_TRY(kd_check_head(what, kind, teacher_kind, mode, temperature));
   FTR_REQUIRE(factorization == FTR_KD_FACT_SOFTMAX || factorization == FTR_KD_FACT_HAT || factorization == FTR_KD_FACT_TDT,
               "%s: unknown factorization %d (FTR_KD_FACT_SOFTMAX = 0, FTR_KD_FACT_HAT = 1, FTR_KD_FACT_TDT = 2)", what, factorization);
   if (factorization != FTR_KD_FACT_TDT) {
@@ -1472,21 +1428,73 @@ static int kd_fact_check_head(const char* what, int kind, int teacher_kind, int 
   return FTR_OK;
 }
 
+// the body of both forward entries, under the entry's own `what`; the plain entry is FTR_KD_FACT_SOFTMAX, 0, 0, NULL
+static int kd_fwd(const char* what, const void* logits, int kind, const void* teacher_logits, int teacher_kind,
+                  const int32_t* symbols, const int32_t* ranges, const int32_t* boundary, int termination_symbol,
+                  float temperature, int mode, float* node_loss, float* saved, float* utt_loss, int B, int T, int S, int C,
+                  int r, int factorization, int n_dur, float dur_weight, const float* node_weights, void* stream) {
+  clear_error();
+  FTR_TRY(kd_check_head(what, kind, teacher_kind, mode, temperature, factorization, n_dur, dur_weight, C));
+  const int hat = factorization == FTR_KD_FACT_HAT;
+  FTR_TRY(check_builder(what, B >= 0 && T >= 1 && S >= 0 && C >= 1 && r >= 1, termination_symbol, C - n_dur, false, hat));
+  if (B == 0) return FTR_OK;
+  FTR_TRY(pointers_then_device(what, logits && teacher_logits && ranges && node_loss && saved && utt_loss && (symbols || S == 0)));
+  return pruned_kd_fwd(logits, kind, teacher_logits, teacher_kind, symbols, ranges, boundary, termination_symbol, temperature,
+                       mode == FTR_KD_COLLAPSED, hat, n_dur, dur_weight, node_weights, node_loss, saved, utt_loss, B, T, S, C, r,
+                       stream_of(stream));
+}
+
+// and of both backward entries
+static int kd_bwd(const char* what, const void* logits, int kind, const void* teacher_logits, int teacher_kind,
+                  const int32_t* symbols, const int32_t* ranges, const int32_t* boundary, int termination_symbol,
+                  float temperature, int mode, const float* saved, const float* scale, int scale_stride, float scale_mul,
+                  void* glogits, int B, int T, int S, int C, int r, int factorization, int n_dur, float dur_weight,
+                  const float* node_weights, void* stream) {
+  clear_error();
+  FTR_TRY(kd_check_head(what, kind, teacher_kind, mode, temperature, factorization, n_dur, dur_weight, C));
+  const int hat = factorization == FTR_KD_FACT_HAT;
+  FTR_TRY(check_builder(what, B >= 0 && T >= 1 && S >= 0 && C >= 1 && r >= 1, termination_symbol, C - n_dur, true, hat));
+  FTR_TRY(check_scale_stride(what, scale_stride));
+  if (B == 0) return FTR_OK;
+  FTR_TRY(pointers_then_device(what, logits && teacher_logits && ranges && saved && glogits && (symbols || S == 0)));
+  return pruned_kd_bwd(logits, kind, teacher_logits, teacher_kind, symbols, ranges, boundary, termination_symbol, temperature,
+                       mode == FTR_KD_COLLAPSED, hat, n_dur, dur_weight, node_weights, saved, Scale{scale, scale_stride, scale_mul},
+                       glogits, B, T, S, C, r, stream_of(stream));
+}
+
+int ftr_pruned_kd_fwd_dt(const void* logits, int kind, const void* teacher_logits, int teacher_kind,
+                         const int32_t* symbols, const int32_t* ranges, const int32_t* boundary, int termination_symbol,
+                         float temperature, int mode, float* node_loss, float* saved, float* utt_loss, int B, int T, int S,
+                         int C, int r, void* stream) {
+  return kd_fwd("pruned_kd_fwd_dt", logits, kind, teacher_logits, teacher_kind, symbols, ranges, boundary, termination_symbol,
+                temperature, mode, node_loss, saved, utt_loss, B, T, S, C, r, FTR_KD_FACT_SOFTMAX, 0, 0.0f, NULL, stream);
+}
+
+int ftr_pruned_kd_bwd_scaled_dt(const void* logits, int kind, const void* teacher_logits, int teacher_kind,
+                                const int32_t* symbols, const int32_t* ranges, const int32_t* boundary,
+                                int termination_symbol, float temperature, int mode, const float* saved,
+                                const float* scale, int scale_stride, float scale_mul, void* glogits, int B, int T, int S,
+                                int C, int r, void* stream) {
+  return kd_bwd("pruned_kd_bwd_scaled_dt", logits, kind, teacher_logits, teacher_kind, symbols, ranges, boundary,
+                termination_symbol, temperature, mode, saved, scale, scale_stride, scale_mul, glogits, B, T, S, C, r,
+                FTR_KD_FACT_SOFTMAX, 0, 0.0f, NULL, stream);
+}
+
+int ftr_pruned_kd_reduce_f32(const float* utt_loss, int B, int reduction, float* out, void* stream) {
+  clear_error();
+  FTR_REQUIRE(B >= 1 && reduction >= 0 && reduction <= 2, "pruned_kd_reduce: bad arguments B=%d reduction=%d", B, reduction);
+  FTR_TRY(pointers_then_device("pruned_kd_reduce", utt_loss && out));
+  return negated_reduce(utt_loss, B, reduction, out, stream_of(stream), 1.0f);
+}
+
 int ftr_pruned_kd_fact_fwd_dt(const void* logits, int kind, const void* teacher_logits, int teacher_kind,
                               const int32_t* symbols, const int32_t* ranges, const int32_t* boundary,
                               int termination_symbol, float temperature, int mode, float* node_loss, float* saved,
                               float* utt_loss, int B, int T, int S, int C, int r, int factorization, int n_dur,
                               float dur_weight, const float* node_weights, void* stream) {
-  const char* what = "pruned_kd_fact_fwd_dt";
-  clear_error();
-  FTR_TRY(kd_fact_check_head(what, kind, teacher_kind, mode, temperature, factorization, n_dur, dur_weight, C));
-  const int hat = factorization == FTR_KD_FACT_HAT;
-  FTR_TRY(check_builder(what, B >= 0 && T >= 1 && S >= 0 && C >= 1 && r >= 1, termination_symbol, C - n_dur, false, hat));
-  if (B == 0) return FTR_OK;
-  FTR_TRY(pointers_then_device(what, logits && teacher_logits && ranges && node_loss && saved && utt_loss && (symbols || S == 0)));
-  return pruned_kd_fact_fwd(logits, kind, teacher_logits, teacher_kind, symbols, ranges, boundary, termination_symbol, temperature,
-                            mode == FTR_KD_COLLAPSED, hat, n_dur, dur_weight, node_weights, node_loss, saved, utt_loss, B, T, S, C, r,
-                            stream_of(stream));
+  return kd_fwd("pruned_kd_fact_fwd_dt", logits, kind, teacher_logits, teacher_kind, symbols, ranges, boundary,
+                termination_symbol, temperature, mode, node_loss, saved, utt_loss, B, T, S, C, r, factorization, n_dur, dur_weight,
+                node_weights, stream);
 }
 
 int ftr_pruned_kd_fact_bwd_scaled_dt(const void* logits, int kind, const void* teacher_logits, int teacher_kind,
@@ -1495,17 +1503,9 @@ int ftr_pruned_kd_fact_bwd_scaled_dt(const void* logits, int kind, const void* t
                                      const float* scale, int scale_stride, float scale_mul, void* glogits, int B, int T,
                                      int S, int C, int r, int factorization, int n_dur, float dur_weight,
                                      const float* node_weights, void* stream) {
-  const char* what = "pruned_kd_fact_bwd_scaled_dt";
-  clear_error();
-  FTR_TRY(kd_fact_check_head(what, kind, teacher_kind, mode, temperature, factorization, n_dur, dur_weight, C));
-  const int hat = factorization == FTR_KD_FACT_HAT;
-  FTR_TRY(check_builder(what, B >= 0 && T >= 1 && S >= 0 && C >= 1 && r >= 1, termination_symbol, C - n_dur, true, hat));
-  FTR_TRY(check_scale_stride(what, scale_stride));
-  if (B == 0) return FTR_OK;
-  FTR_TRY(pointers_then_device(what, logits && teacher_logits && ranges && saved && glogits && (symbols || S == 0)));
-  return pruned_kd_fact_bwd(logits, kind, teacher_logits, teacher_kind, symbols, ranges, boundary, termination_symbol, temperature,
-                            mode == FTR_KD_COLLAPSED, hat, n_dur, dur_weight, node_weights, saved, Scale{scale, scale_stride, scale_mul},
-                            glogits, B, T, S, C, r, stream_of(stream));
+  return kd_bwd("pruned_kd_fact_bwd_scaled_dt", logits, kind, teacher_logits, teacher_kind, symbols, ranges, boundary,
+                termination_symbol, temperature, mode, saved, scale, scale_stride, scale_mul, glogits, B, T, S, C, r, factorization,
+                n_dur, dur_weight, node_weights, stream);
 }
 
 int ftr_selftest(void* scratch_dev, void* stream) {

@@ -312,13 +312,9 @@ int simple_fused_bwd_am(const float* gpx, const float* gpy, Scale scale, const f
 int simple_fused_bwd_columns(int B, int T, int C);   // columns per workgroup (128 | 256) the W-operand kernel takes for a shape
 int simple_fused_bwd_am_w(const float* gpx, const float* gpy, Scale scale, const float* W, const float* lm_probs, const float* am_probs, const int32_t* symbols, const int32_t* boundary, int blank, float kdir, const float* uvec, const float* amdot, float as, float* Rout, float* d_am, int B, int T, int S, int C, int modified, hipStream_t st, const int32_t* live = nullptr);   // live: what simple_logprobs_bwd_w wrote next to W
 int negated_reduce(const float* ans, int B, int reduction, float* out, hipStream_t st, float sign = -1.0f);   // sign = +1: the plain reduction
-// knowledge distillation on the pruned band: csrc/pruned_kd.hip (collapsed != 0: the three-class form; saved: 2 or 4 planes of [B,T,r])
-int pruned_kd_fwd(const void* logits, int dtype, const void* teacher, int teacher_dtype, const int32_t* symbols, const int32_t* ranges, const int32_t* boundary, int blank, float temperature, int collapsed, float* node, float* saved, float* utt, int B, int T, int S, int C, int r, hipStream_t st);
-int pruned_kd_bwd(const void* logits, int dtype, const void* teacher, int teacher_dtype, const int32_t* symbols, const int32_t* ranges, const int32_t* boundary, int blank, float temperature, int collapsed, const float* saved, Scale scale, void* glogits, int B, int T, int S, int C, int r, hipStream_t st);
-int pruned_kd_utt_sum(const float* node, float* utt, int B, int per, hipStream_t st);
-// its factored forms: csrc/pruned_kd_fact.hip (hat != 0: the HAT rows; n_dur: duration columns at the end of a row of width W; weights [B,T,r] or NULL; saved: 2 + 2 collapsed + 2 with n_dur > 0 planes)
-int pruned_kd_fact_fwd(const void* logits, int dtype, const void* teacher, int teacher_dtype, const int32_t* symbols, const int32_t* ranges, const int32_t* boundary, int blank, float temperature, int collapsed, int hat, int n_dur, float dur_weight, const float* weights, float* node, float* saved, float* utt, int B, int T, int S, int W, int r, hipStream_t st);
-int pruned_kd_fact_bwd(const void* logits, int dtype, const void* teacher, int teacher_dtype, const int32_t* symbols, const int32_t* ranges, const int32_t* boundary, int blank, float temperature, int collapsed, int hat, int n_dur, float dur_weight, const float* weights, const float* saved, Scale scale, void* glogits, int B, int T, int S, int W, int r, hipStream_t st);
+// knowledge distillation on the pruned band: csrc/pruned_kd.hip (collapsed != 0: the three-class form; hat != 0: the HAT rows; n_dur: duration columns at the end of a row of width W; weights [B,T,r] or NULL; saved: 2 + 2 collapsed + 2 with n_dur > 0 planes of [B,T,r]; hat = n_dur = 0 and weights = NULL: the plain form)
+int pruned_kd_fwd(const void* logits, int dtype, const void* teacher, int teacher_dtype, const int32_t* symbols, const int32_t* ranges, const int32_t* boundary, int blank, float temperature, int collapsed, int hat, int n_dur, float dur_weight, const float* weights, float* node, float* saved, float* utt, int B, int T, int S, int W, int r, hipStream_t st);
+int pruned_kd_bwd(const void* logits, int dtype, const void* teacher, int teacher_dtype, const int32_t* symbols, const int32_t* ranges, const int32_t* boundary, int blank, float temperature, int collapsed, int hat, int n_dur, float dur_weight, const float* weights, const float* saved, Scale scale, void* glogits, int B, int T, int S, int W, int r, hipStream_t st);
 int lse_rows(const float* logits, float* lse, size_t rows, int C, int blank, int hat, hipStream_t st);
 int lse_rows_dtype(const void* logits, int dtype, float* lse, size_t rows, int C, int blank, int hat, hipStream_t st);
 int mi_band_supported(int T, int S, int r);

@@ -1,17 +1,37 @@
-// csrc/pruned_kd.hip -- knowledge distillation on the pruned band (MI355X addition, no reference counterpart), gfx950.
-// Student and teacher joiner logits x, y [B,T,r,C] on the same `ranges`; per valid node (b,t,k) the loss is KL(p || q) with
-// p = softmax(y / tau), q = softmax(x / tau) over the C columns ("full"), or over three classes -- blank, the correct next
-// symbol, everything else -- ("collapsed", Panchapagesan et al., ICASSP 2021).  No tau^2 factor.
-//   kd_fwd_reg_kernel  one wave per row, both rows held in registers (C % 4 == 0, C <= 256 * NQ), every load issued
-//                      before the first use, one pass: as lse_rows_reg_kernel of pruned_logprobs.hip, twice the registers
-//   kd_fwd_kernel      any C: two passes over the row (the second hits L1/L2), four elements at a time or one by one
+// csrc/pruned_kd.hip -- knowledge distillation on the pruned band (include/ftr_kd.h, include/ftr_kd_fact.h; MI355X addition,
+// no reference counterpart), gfx950.
+// Student and teacher joiner logits x, y [B,T,r,W] on the same `ranges`; per valid node (b,t,k) the loss is KL(p || q) with
+// p = softmax(y / tau), q = softmax(x / tau) over the columns ("full"), or over three classes -- blank, the correct next
+// symbol, everything else -- ("collapsed", Panchapagesan et al., ICASSP 2021).  No tau^2 factor.  A row is one of three forms,
+// a compile-time parameter of every kernel:
+//   KD_PLAIN one softmax over all W columns, no node weights, no duration columns: all three known at compile time, so
+//            neither the weight, nor the column mask, nor a tail is in its code
+//   KD_HAT   the blank column Bk is a sigmoid of its own, the other columns a softmax over c != Bk:
+//            full       KL(Bern(pb) || Bern(qb)) + (1 - pb) sum_{c != Bk} v_c (log v_c - log u_c)
+//            collapsed  the same with the non-blank softmax collapsed to {symbol, rest}
+//   KD_TDT   a row of width W = Ct + N: a token softmax over the first Ct columns (the plain loss on them, either mode) and a
+//            duration softmax over the last N <= 5, whose full KL is added with the multiplier dur_weight.  N is a run-time
+//            argument, and N = 0 is how one softmax with node weights runs
+// and, in the last two, optional per-node weights w [B,T,r] (a run-time pointer): node loss and gradient row times w, and
+// w == 0 makes the node invalid.
+//   kd_fwd_reg_kernel  one wave per row, both rows held in registers (W % 4 == 0, W <= 256 * NQ), every load issued
+//                      before the first use, one pass, last rows first: as lse_rows_reg_kernel of pruned_logprobs.hip,
+//                      twice the registers
+//   kd_fwd_kernel      any W: two passes over the row (the second hits L1/L2), four elements at a time or one by one
 //   kd_utt_sum_kernel  node losses -> per-utterance loss, one block per utterance, fixed summation tree
-//   kd_bwd_kernel      one streaming pass: d loss / d x from x, y and the normalisers the forward saved (no reduction)
-// A node is valid iff t_begin <= t < t_end and s_begin <= ranges[b,t,k] <= s_end; validity is decided from ranges and
-// boundary BEFORE any logits load, an invalid row is never read (padding frames of a joiner hold garbage), its node loss
-// and normalisers are 0 and its gradient row is written as zeros.
-// Saved normalisers, float32 planes of [B,T,r]: 0 = logsumexp(x / tau), 1 = logsumexp(y / tau), and in collapsed mode
-// 2, 3 = the same over the "rest" columns only (a masked logsumexp with its own maximum, never log(1 - ...)).
+//   kd_bwd_kernel      one streaming pass: d loss / d x from x, y and the normalisers the forward saved (no reduction); it
+//                      writes all W columns of the gradient row
+// The three forms share the column -> lane mapping and the order of every sum.  The columns that are not part of the main
+// sums (HAT: the blank; TDT: the duration columns; collapsed: the class columns) are masked to -inf in registers, as
+// tdt_lse_kernel of tdt_logprobs.hip masks 4 * i + e >= C.  What is left at the end of a row: HAT, the Bernoulli term from
+// the two blank logits (the softplus / hat_sigmoids arithmetic of ftr_common.h, as the HAT builder forms its log-sigmoids),
+// student and teacher on two lanes at once; TDT, the duration head from at most five columns of each row, one per lane.
+// A node is valid iff t_begin <= t < t_end and s_begin <= ranges[b,t,k] <= s_end and its weight is not 0; validity is
+// decided from ranges, boundary and the weight BEFORE any logits load, an invalid row is never read (padding frames of a
+// joiner hold garbage), its node loss and normalisers are 0 and its gradient row is written as zeros.
+// Saved normalisers, float32 planes of [B,T,r]: 0, 1 = the logsumexps of the main softmax (student, teacher); collapsed:
+// 2, 3 = the same over the "rest" columns only (a masked logsumexp with its own maximum, never log(1 - ...)); TDT with
+// N > 0: the last two = those of the duration head (written as 0 and never read when dur_weight == 0).
 // Element types of x and y are independent (float, bf16_t, fp16_t); a row is read four elements at a time only when BOTH
 // tensors pass rows_vec4.  All arithmetic is float32; the gradient row is rounded once when it is stored in x's type.
 #include "ftr_common.h"
@@ -20,16 +40,20 @@
 namespace ftr {
 namespace {
 
+constexpr int KD_PLAIN = 0, KD_HAT = 1, KD_TDT = 2;
+constexpr int KF_MAXN = FTR_KD_FACT_MAX_DUR;
+
 __device__ __forceinline__ float wave_max(float v) { return wave_max_dpp(v); }
 __device__ __forceinline__ float wave_sum(float v) { return wave_sum_dpp(v); }
 
-// what a wave knows about its row before it touches the logits: is the node valid, whose utterance is it, and (collapsed)
-// the columns of the blank class k0 and of the symbol class k1 (-1: the node has no symbol class)
-struct KdRow { bool valid; int b, k0, k1; };
+// what a wave knows about its row before it touches the logits: is the node valid, whose utterance is it, its weight (1
+// without weights), the blank column k0 and (collapsed) the symbol column k1 (-1: the node has no symbol class)
+struct KdRow { bool valid; int b, k0, k1; float w; };
 
 template <bool COLL>
 __device__ __forceinline__ KdRow kd_row(size_t row, const int32_t* __restrict__ symbols, const int32_t* __restrict__ ranges,
-                                        const int32_t* __restrict__ boundary, int blank, int T, int S, int C, int r) {
+                                        const int32_t* __restrict__ boundary, const float* __restrict__ weights, int blank,
+                                        int T, int S, int Ct, int r) {
   KdRow g;
   const unsigned bt = (unsigned)row / (unsigned)r;   // rows < 2^31 (require_rows_32bit): 32-bit divisions, a tenth of the 64-bit ones
   g.b = (int)(bt / (unsigned)T);
@@ -37,10 +61,15 @@ __device__ __forceinline__ KdRow kd_row(size_t row, const int32_t* __restrict__ 
   const int s = ranges[row];
   const Bound bd = load_boundary(boundary, g.b, S, T);   // clamped into the lattice: s < se implies s < S below
   g.valid = t >= bd.tb && t < bd.te && s >= bd.sb && s <= bd.se;
+  g.w = 1.0f;
+  if (weights) {
+    g.w = weights[row];
+    g.valid = g.valid && g.w != 0.0f;   // a NaN weight compares unequal: the node stays valid and its loss becomes NaN
+  }
   g.k0 = blank;
   g.k1 = -1;
   if (COLL && g.valid && s < bd.se) {
-    const int c = min(max(symbols[(size_t)g.b * S + s], 0), C - 1);   // symbol kept in bounds, as the pruned builders do
+    const int c = min(max(symbols[(size_t)g.b * S + s], 0), Ct - 1);   // symbol kept among the token columns, as the pruned builders do
     if (c != blank) g.k1 = c;
   }
   return g;
@@ -55,60 +84,166 @@ __device__ __forceinline__ float lse3(float a, float b, float c) {
   return m + __logf(__expf(a - m) + __expf(b - m) + __expf(c - m));   // a NaN among a, b, c comes out of the sum
 }
 
+// a maximum to subtract that is never -inf (a row, or a rest class, of -inf only: exp(-inf - 0) = 0, not exp(NaN))
+__device__ __forceinline__ float kd_safe_max(float m) { return m == -INFINITY ? 0.0f : m; }
+
+// the number of saved planes: 2, + 2 collapsed, + 2 with a duration head
 template <bool COLL>
-__device__ __forceinline__ void kd_store(float* __restrict__ node, float* __restrict__ saved, size_t rows, size_t row,
-                                         float loss, float Ls, float Lt, float Rs, float Rt) {
-  node[row] = loss;
+__device__ __forceinline__ int kd_planes(int N) { return (COLL ? 4 : 2) + (N > 0 ? 2 : 0); }
+
+template <bool COLL>
+__device__ __forceinline__ void kd_store_invalid(float* __restrict__ node, float* __restrict__ saved, size_t rows, size_t row, int N) {
+  node[row] = 0.0f;
+  for (int p = 0; p < kd_planes<COLL>(N); ++p) saved[(size_t)p * rows + row] = 0.0f;
+}
+
+// ---- the duration head (TDT), one column per lane: lane j < 8 takes column W - 8 + j of both rows if that is a duration
+// column (N <= 5 < 8), one load per tensor issued with the class logits before the first use of the row; the head's maxima
+// and sums are then three DPP steps over lanes 0..7 (the first three of wave_max_dpp / wave_sum_dpp), read from lane 7.
+// A serial loop over the N columns on lane 0 was built first: with its 2 N loads and its chain of N exponentials behind the
+// row's own reductions, the forward kernel took 150 - 190 us at c3 where the plain kd_fwd_reg_kernel takes 112 - 135.
+static_assert(KF_MAXN <= 8, "the duration head is reduced over lanes 0..7");
+__device__ __forceinline__ float oct_max(float v) {
+  constexpr float ninf = -__builtin_inff();
+  v = fmaxf(v, dpp_take<0x111, 0xf, 0xf>(ninf, v));   // row_shr:1
+  v = fmaxf(v, dpp_take<0x112, 0xf, 0xf>(ninf, v));   // row_shr:2
+  v = fmaxf(v, dpp_take<0x114, 0xf, 0xf>(ninf, v));   // row_shr:4 -> lane 7 holds the maximum of lanes 0..7
+  return __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, v), 7));
+}
+__device__ __forceinline__ float oct_sum(float v) {
+  v += dpp_take<0x111, 0xf, 0xf>(0.0f, v);
+  v += dpp_take<0x112, 0xf, 0xf>(0.0f, v);
+  v += dpp_take<0x114, 0xf, 0xf>(0.0f, v);
+  return __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, v), 7));
+}
+
+// this lane's duration column of both rows (scaled), -inf on the lanes that have none
+struct KfDurLane { float x, y; };
+template <typename ES, typename ET>
+__device__ __forceinline__ KfDurLane kf_load_dur(const ES* xr, const ET* yr, int lane, int W, int Ct, bool on, float inv_tau) {
+  KfDurLane d = {-INFINITY, -INFINITY};
+  const int c = W - 8 + lane;
+  if (on && lane < 8 && c >= Ct) {   // Ct >= 1: c is inside the row
+    d.x = elem_to_float(xr[c]) * inv_tau;
+    d.y = elem_to_float(yr[c]) * inv_tau;
+  }
+  return d;
+}
+// the head's full KL, by every lane of the wave: *Ds, *Dt = the two logsumexps, the return value KL(teacher || student)
+__device__ __forceinline__ float kf_dur_kl(const KfDurLane d, float* Ds, float* Dt) {
+  const float md = kd_safe_max(oct_max(d.x)), me = kd_safe_max(oct_max(d.y));
+  const float p = __expf(d.y - me);
+  const float sd = oct_sum(__expf(d.x - md)), se = oct_sum(p), kl = oct_sum(kd_term(p, d.y - d.x));
+  *Ds = md + __logf(sd);
+  *Dt = me + __logf(se);
+  return kl / se - (*Dt - *Ds);
+}
+
+// softplus(v) and softplus(-v) of ftr_common.h from one exponential and one log1pf (the two calls share
+// log1pf(expf(-|v|)): the values are theirs bit for bit), and, if asked for, hat_sigmoids(v) from the same exponential
+__device__ __forceinline__ void hat_softplus_pair(float v, float* pos, float* neg, float* sp = nullptr, float* sn = nullptr) {
+  const float e = expf(-fabsf(v)), t = log1pf(e);
+  *pos = fmaxf(v, 0.0f) + t;
+  *neg = fmaxf(-v, 0.0f) + t;
+  if (sp) {
+    const float big = 1.0f / (1.0f + e), small = e / (1.0f + e);
+    *sp = v >= 0.0f ? big : small;
+    *sn = v >= 0.0f ? small : big;
+  }
+}
+
+// HAT: KL(Bern(pb) || Bern(qb)) from the two blank logits, and pn = 1 - pb = sigmoid(-yb), the mass the KL of the non-blank
+// softmaxes carries.  By every lane of the wave: the even lanes evaluate the student's logit and the odd lanes the teacher's,
+// so the library expf / log1pf and the divisions are issued once for both, and lanes 0 and 1 hand the results to all.  The
+// forward kernels are bound by the instructions they issue, not by this tail's latency: with both logits evaluated one after
+// the other the HAT forms took 149 - 187 us at c3 where the TDT forms took 125 - 165, whether the term stood after the
+// row's reductions on lane 0 or ahead of them in the shadow of the row loads.
+struct KfBern { float kl, pn; };
+__device__ __forceinline__ float lane_value(float v, int lane) { return __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, v), lane)); }
+__device__ __forceinline__ KfBern kf_hat_bern(float xb, float yb, int lane) {
+  float pos, neg, sp, sn;   // pos = softplus(z) = -log sigmoid(-z), neg = softplus(-z) = -log sigmoid(z), sp / sn = sigmoid(+-z)
+  hat_softplus_pair((lane & 1) ? yb : xb, &pos, &neg, &sp, &sn);
+  const float spx = lane_value(pos, 0), snx = lane_value(neg, 0), spy = lane_value(pos, 1), sny = lane_value(neg, 1);
+  const float pb = lane_value(sp, 1), pn = lane_value(sn, 1);
+  return KfBern{kd_term(pb, snx - sny) + kd_term(pn, spx - spy), pn};
+}
+
+// The end of a forward row (lane 0), from the wave-reduced sums over the columns of the main softmax that are not masked.
+// ms, mt: the maxima the sums were taken against; ss, st: sums of exp(. - max); full: over all columns, kl = sum exp(y - mt)
+// (y - x); collapsed: over the rest columns, and xb, yb are the blank logits, xs, ys the symbol logits (-inf without a symbol
+// class).  Everything is already divided by tau.  bern: the HAT tail; dur_kl, Ds, Dt: the TDT tail; w: the node's weight.
+template <int FORM, bool COLL>
+__device__ __forceinline__ void kd_finish(float* __restrict__ node, float* __restrict__ saved, size_t rows, size_t row,
+                                          float ms, float ss, float mt, float st, float kl, float xb, float xs, float yb,
+                                          float ys, const KfBern bern, float dur_kl, float Ds, float Dt, int N, float dw, float w) {
+  constexpr bool HAT = FORM == KD_HAT;
+  float loss, Ls, Lt, Rs = 0.0f, Rt = 0.0f;
+  if (!COLL) {
+    Ls = ms + __logf(ss);
+    Lt = mt + __logf(st);
+    loss = kl / st - (Lt - Ls);
+  } else {
+    Rs = ms + __logf(ss);   // no rest column at all: -inf + log 0 = -inf
+    Rt = mt + __logf(st);
+    // HAT: the blank is no class of this softmax
+    const float cb_s = HAT ? -INFINITY : xb, cb_t = HAT ? -INFINITY : yb;
+    Ls = lse3(Rs, cb_s, xs);
+    Lt = lse3(Rt, cb_t, ys);
+    const float lpb = cb_t - Lt, lps = ys - Lt, lpr = Rt - Lt;
+    // the hardware exp / log, as in the sums: this tail runs once per row, and with the library forms it took longer than the row
+    loss = kd_term(__expf(lpb), lpb - (cb_s - Ls)) + kd_term(__expf(lps), lps - (xs - Ls)) + kd_term(__expf(lpr), lpr - (Rs - Ls));
+  }
+  // HAT: loss so far is the KL of the non-blank softmaxes; it carries the teacher's non-blank mass 1 - pb (mass 0 adds
+  // nothing, but a NaN row stays NaN)
+  if (HAT) loss = bern.kl + ((bern.pn == 0.0f && loss == loss) ? 0.0f : bern.pn * loss);
   saved[row] = Ls;
   saved[rows + row] = Lt;
   if (COLL) {
     saved[2 * rows + row] = Rs;
     saved[3 * rows + row] = Rt;
   }
-}
-
-// The end of a forward row, from the wave-reduced sums.  ms, mt: the maxima the sums were taken against; ss, st: sums of
-// exp(. - max); full: over all columns, kl = sum exp(y - mt) (y - x); collapsed: over the rest columns, and xb, xs, yb,
-// ys are the blank and symbol logits (xs = ys = -inf without a symbol class).  Everything is already divided by tau.
-template <bool COLL>
-__device__ __forceinline__ void kd_finish(float* __restrict__ node, float* __restrict__ saved, size_t rows, size_t row,
-                                          float ms, float ss, float mt, float st, float kl, float xb, float xs, float yb,
-                                          float ys) {
-  if (!COLL) {
-    const float Ls = ms + __logf(ss), Lt = mt + __logf(st);
-    kd_store<false>(node, saved, rows, row, kl / st - (Lt - Ls), Ls, Lt, 0.0f, 0.0f);
-  } else {
-    const float Rs = ms + __logf(ss), Rt = mt + __logf(st);   // no rest column at all: -inf + log 0 = -inf
-    const float Ls = lse3(Rs, xb, xs), Lt = lse3(Rt, yb, ys);
-    const float lpb = yb - Lt, lps = ys - Lt, lpr = Rt - Lt;
-    // the hardware exp / log, as in the sums: this tail runs once per row, and with the library forms it took longer than the row
-    const float loss = kd_term(__expf(lpb), lpb - (xb - Ls)) + kd_term(__expf(lps), lps - (xs - Ls)) + kd_term(__expf(lpr), lpr - (Rs - Ls));
-    kd_store<true>(node, saved, rows, row, loss, Ls, Lt, Rs, Rt);
+  if (FORM == KD_TDT && N > 0) {   // dur_weight == 0: the head was not looked at, dur_kl = Ds = Dt = 0
+    if (dw != 0.0f) loss += dw * dur_kl;
+    const int p0 = COLL ? 4 : 2;
+    saved[(size_t)p0 * rows + row] = Ds;
+    saved[(size_t)(p0 + 1) * rows + row] = Dt;
   }
+  node[row] = FORM == KD_PLAIN ? loss : loss * w;
 }
 
-// a maximum to subtract that is never -inf (a row, or a rest class, of -inf only: exp(-inf - 0) = 0, not exp(NaN))
-__device__ __forceinline__ float kd_safe_max(float m) { return m == -INFINITY ? 0.0f : m; }
+// is column c outside the sums of the main softmax?
+template <int FORM, bool COLL>
+__device__ __forceinline__ bool kd_masked(int c, int Ct, int k0, int k1) {
+  return (FORM == KD_TDT && c >= Ct) || ((FORM == KD_HAT || COLL) && c == k0) || (COLL && c == k1);
+}
 
-template <typename ES, typename ET, int NQ, bool COLL>
+template <typename ES, typename ET, int NQ, int FORM, bool COLL>
 __global__ __launch_bounds__(256) void kd_fwd_reg_kernel(const ES* __restrict__ x, const ET* __restrict__ y,
                                                          const int32_t* __restrict__ symbols, const int32_t* __restrict__ ranges,
-                                                         const int32_t* __restrict__ boundary, int blank, float inv_tau,
-                                                         float* __restrict__ node, float* __restrict__ saved, size_t rows,
-                                                         int T, int S, int C, int r) {
+                                                         const int32_t* __restrict__ boundary, const float* __restrict__ weights,
+                                                         int blank, float inv_tau, float dw, float* __restrict__ node,
+                                                         float* __restrict__ saved, size_t rows, int T, int S, int W, int N, int r) {
+  constexpr bool HAT = FORM == KD_HAT;
+  if (FORM == KD_PLAIN) { weights = nullptr; N = 0; }   // known at compile time: what hangs on them is not in the plain form's code
   const int lane = threadIdx.x & 63;
   const size_t rowi = (size_t)blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
   if (rowi >= rows) return;
   const size_t row = rows - 1 - rowi;   // last rows first: the tail of a tensor that was just written is what the cache still holds
-  const KdRow g = kd_row<COLL>(row, symbols, ranges, boundary, blank, T, S, C, r);
+  const int Ct = W - N;
+  const KdRow g = kd_row<COLL>(row, symbols, ranges, boundary, weights, blank, T, S, Ct, r);
   if (!g.valid) {
-    if (lane == 0) kd_store<COLL>(node, saved, rows, row, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f);
+    if (lane == 0) kd_store_invalid<COLL>(node, saved, rows, row, N);
     return;
   }
-  const int n4 = C >> 2;
+  const int n4 = W >> 2;
   const f4 ninf = {-INFINITY, -INFINITY, -INFINITY, -INFINITY};
-  const ES* xr = x + row * C;
-  const ET* yr = y + row * C;
+  const ES* xr = x + row * W;
+  const ET* yr = y + row * W;
+  float xb = -INFINITY, xs = -INFINITY, yb = -INFINITY, ys = -INFINITY;
+  if (HAT) {   // the two logits of the Bernoulli term
+    xb = elem_to_float(xr[g.k0]) * inv_tau;
+    yb = elem_to_float(yr[g.k0]) * inv_tau;
+  }
   f4 v[NQ], w[NQ];
 #pragma unroll
   for (int q = 0; q < NQ; ++q) {
@@ -120,24 +255,24 @@ __global__ __launch_bounds__(256) void kd_fwd_reg_kernel(const ES* __restrict__ 
     const int i = lane + 64 * q;
     w[q] = (i < n4) ? load4(yr, i) : ninf;
   }
-  float xb = -INFINITY, xs = -INFINITY, yb = -INFINITY, ys = -INFINITY;
-  if (COLL) {   // the class logits, by every lane from the same address: lines this wave is fetching anyway
+  if (!HAT && COLL) {   // the class logits, by every lane from the same address: lines this wave is fetching anyway
     xb = elem_to_float(xr[g.k0]) * inv_tau;
     yb = elem_to_float(yr[g.k0]) * inv_tau;
-    if (g.k1 >= 0) {
-      xs = elem_to_float(xr[g.k1]) * inv_tau;
-      ys = elem_to_float(yr[g.k1]) * inv_tau;
-    }
   }
+  if (COLL && g.k1 >= 0) {
+    xs = elem_to_float(xr[g.k1]) * inv_tau;
+    ys = elem_to_float(yr[g.k1]) * inv_tau;
+  }
+  const bool dur_on = FORM == KD_TDT && N > 0 && dw != 0.0f;   // the same for every wave of the launch
+  const KfDurLane dur = kf_load_dur(xr, yr, lane, W, Ct, dur_on, inv_tau);
   float ms = -INFINITY, mt = -INFINITY;
 #pragma unroll
   for (int q = 0; q < NQ; ++q) {
 #pragma unroll
     for (int e = 0; e < 4; ++e) {
-      const int c = 4 * (lane + 64 * q) + e;
-      const bool cls = COLL && (c == g.k0 || c == g.k1);   // collapsed: the sums run over the rest columns
-      v[q][e] = cls ? -INFINITY : v[q][e] * inv_tau;
-      w[q][e] = cls ? -INFINITY : w[q][e] * inv_tau;
+      const bool out = kd_masked<FORM, COLL>(4 * (lane + 64 * q) + e, Ct, g.k0, g.k1);
+      v[q][e] = out ? -INFINITY : v[q][e] * inv_tau;
+      w[q][e] = out ? -INFINITY : w[q][e] * inv_tau;
     }
     ms = fmaxf(fmaxf(ms, fmaxf(v[q][0], v[q][1])), fmaxf(v[q][2], v[q][3]));
     mt = fmaxf(fmaxf(mt, fmaxf(w[q][0], w[q][1])), fmaxf(w[q][2], w[q][3]));
@@ -148,7 +283,7 @@ __global__ __launch_bounds__(256) void kd_fwd_reg_kernel(const ES* __restrict__ 
 #pragma unroll
   for (int q = 0; q < NQ; ++q) {
 #pragma unroll
-    for (int e = 0; e < 4; ++e) {   // lanes past the row hold -inf: exp gives 0 and the kl term is skipped
+    for (int e = 0; e < 4; ++e) {   // masked columns and lanes past the row hold -inf: exp gives 0 and the kl term is skipped
       ss += __expf(v[q][e] - ms);
       const float p = __expf(w[q][e] - mt);
       st += p;
@@ -158,45 +293,53 @@ __global__ __launch_bounds__(256) void kd_fwd_reg_kernel(const ES* __restrict__ 
   ss = wave_sum(ss);
   st = wave_sum(st);
   if (!COLL) kl = wave_sum(kl);
-  if (lane == 0) kd_finish<COLL>(node, saved, rows, row, ms, ss, mt, st, kl, xb, xs, yb, ys);
+  KfBern bern = {0.0f, 1.0f};
+  if (HAT) bern = kf_hat_bern(xb, yb, lane);   // after the row: its registers are free by now
+  float dur_kl = 0.0f, Ds = 0.0f, Dt = 0.0f;
+  if (dur_on) dur_kl = kf_dur_kl(dur, &Ds, &Dt);
+  if (lane == 0) kd_finish<FORM, COLL>(node, saved, rows, row, ms, ss, mt, st, kl, xb, xs, yb, ys, bern, dur_kl, Ds, Dt, N, dw, g.w);
 }
 
-// any C, one wave per row, two passes (the second hits L1/L2: a row is a few KB)
-template <typename ES, typename ET, bool VEC, bool COLL>
+// any W, one wave per row, two passes (the second hits L1/L2: a row is a few KB)
+template <typename ES, typename ET, bool VEC, int FORM, bool COLL>
 __global__ void kd_fwd_kernel(const ES* __restrict__ x, const ET* __restrict__ y, const int32_t* __restrict__ symbols,
-                              const int32_t* __restrict__ ranges, const int32_t* __restrict__ boundary, int blank,
-                              float inv_tau, float* __restrict__ node, float* __restrict__ saved, size_t rows, int T, int S,
-                              int C, int r) {
+                              const int32_t* __restrict__ ranges, const int32_t* __restrict__ boundary,
+                              const float* __restrict__ weights, int blank, float inv_tau, float dw, float* __restrict__ node,
+                              float* __restrict__ saved, size_t rows, int T, int S, int W, int N, int r) {
+  constexpr bool HAT = FORM == KD_HAT;
+  if (FORM == KD_PLAIN) { weights = nullptr; N = 0; }
   const int lane = threadIdx.x & 63;
   const size_t row = (size_t)blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
   if (row >= rows) return;
-  const KdRow g = kd_row<COLL>(row, symbols, ranges, boundary, blank, T, S, C, r);
+  const int Ct = W - N;
+  const KdRow g = kd_row<COLL>(row, symbols, ranges, boundary, weights, blank, T, S, Ct, r);
   if (!g.valid) {
-    if (lane == 0) kd_store<COLL>(node, saved, rows, row, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f);
+    if (lane == 0) kd_store_invalid<COLL>(node, saved, rows, row, N);
     return;
   }
-  const ES* xr = x + row * C;
-  const ET* yr = y + row * C;
+  const ES* xr = x + row * W;
+  const ET* yr = y + row * W;
   float xb = -INFINITY, xs = -INFINITY, yb = -INFINITY, ys = -INFINITY;
-  if (COLL) {
+  if (HAT || COLL) {
     xb = elem_to_float(xr[g.k0]) * inv_tau;
     yb = elem_to_float(yr[g.k0]) * inv_tau;
-    if (g.k1 >= 0) {
-      xs = elem_to_float(xr[g.k1]) * inv_tau;
-      ys = elem_to_float(yr[g.k1]) * inv_tau;
-    }
   }
+  if (COLL && g.k1 >= 0) {
+    xs = elem_to_float(xr[g.k1]) * inv_tau;
+    ys = elem_to_float(yr[g.k1]) * inv_tau;
+  }
+  const bool dur_on = FORM == KD_TDT && N > 0 && dw != 0.0f;   // the same for every wave of the launch
+  const KfDurLane dur = kf_load_dur(xr, yr, lane, W, Ct, dur_on, inv_tau);
   float ms = -INFINITY, mt = -INFINITY, ss = 0.0f, st = 0.0f, kl = 0.0f;
   if (VEC) {
-    const int n4 = C >> 2;
+    const int n4 = W >> 2;
     for (int i = lane; i < n4; i += 64) {
       const f4 v = load4(xr, i), w = load4(yr, i);
 #pragma unroll
       for (int e = 0; e < 4; ++e) {
-        const int c = 4 * i + e;
-        const bool cls = COLL && (c == g.k0 || c == g.k1);
-        ms = fmaxf(ms, cls ? -INFINITY : v[e] * inv_tau);
-        mt = fmaxf(mt, cls ? -INFINITY : w[e] * inv_tau);
+        const bool out = kd_masked<FORM, COLL>(4 * i + e, Ct, g.k0, g.k1);
+        ms = fmaxf(ms, out ? -INFINITY : v[e] * inv_tau);
+        mt = fmaxf(mt, out ? -INFINITY : w[e] * inv_tau);
       }
     }
     ms = kd_safe_max(wave_max(ms));
@@ -205,9 +348,8 @@ __global__ void kd_fwd_kernel(const ES* __restrict__ x, const ET* __restrict__ y
       const f4 v = load4(xr, i), w = load4(yr, i);
 #pragma unroll
       for (int e = 0; e < 4; ++e) {
-        const int c = 4 * i + e;
-        const bool cls = COLL && (c == g.k0 || c == g.k1);
-        const float a = cls ? -INFINITY : v[e] * inv_tau, b = cls ? -INFINITY : w[e] * inv_tau;
+        const bool out = kd_masked<FORM, COLL>(4 * i + e, Ct, g.k0, g.k1);
+        const float a = out ? -INFINITY : v[e] * inv_tau, b = out ? -INFINITY : w[e] * inv_tau;
         ss += __expf(a - ms);
         const float p = __expf(b - mt);
         st += p;
@@ -215,16 +357,16 @@ __global__ void kd_fwd_kernel(const ES* __restrict__ x, const ET* __restrict__ y
       }
     }
   } else {
-    for (int c = lane; c < C; c += 64) {
-      const bool cls = COLL && (c == g.k0 || c == g.k1);
-      ms = fmaxf(ms, cls ? -INFINITY : elem_to_float(xr[c]) * inv_tau);
-      mt = fmaxf(mt, cls ? -INFINITY : elem_to_float(yr[c]) * inv_tau);
+    for (int c = lane; c < Ct; c += 64) {   // the duration columns lie past Ct: not visited at all
+      const bool out = kd_masked<FORM, COLL>(c, Ct, g.k0, g.k1);
+      ms = fmaxf(ms, out ? -INFINITY : elem_to_float(xr[c]) * inv_tau);
+      mt = fmaxf(mt, out ? -INFINITY : elem_to_float(yr[c]) * inv_tau);
     }
     ms = kd_safe_max(wave_max(ms));
     mt = kd_safe_max(wave_max(mt));
-    for (int c = lane; c < C; c += 64) {
-      const bool cls = COLL && (c == g.k0 || c == g.k1);
-      const float a = cls ? -INFINITY : elem_to_float(xr[c]) * inv_tau, b = cls ? -INFINITY : elem_to_float(yr[c]) * inv_tau;
+    for (int c = lane; c < Ct; c += 64) {
+      const bool out = kd_masked<FORM, COLL>(c, Ct, g.k0, g.k1);
+      const float a = out ? -INFINITY : elem_to_float(xr[c]) * inv_tau, b = out ? -INFINITY : elem_to_float(yr[c]) * inv_tau;
       ss += __expf(a - ms);
       const float p = __expf(b - mt);
       st += p;
@@ -234,7 +376,11 @@ __global__ void kd_fwd_kernel(const ES* __restrict__ x, const ET* __restrict__ y
   ss = wave_sum(ss);
   st = wave_sum(st);
   if (!COLL) kl = wave_sum(kl);
-  if (lane == 0) kd_finish<COLL>(node, saved, rows, row, ms, ss, mt, st, kl, xb, xs, yb, ys);
+  KfBern bern = {0.0f, 1.0f};
+  if (HAT) bern = kf_hat_bern(xb, yb, lane);   // after the row: its registers are free by now
+  float dur_kl = 0.0f, Ds = 0.0f, Dt = 0.0f;
+  if (dur_on) dur_kl = kf_dur_kl(dur, &Ds, &Dt);
+  if (lane == 0) kd_finish<FORM, COLL>(node, saved, rows, row, ms, ss, mt, st, kl, xb, xs, yb, ys, bern, dur_kl, Ds, Dt, N, dw, g.w);
 }
 
 // utt[b] = sum of the T * r node losses of utterance b: one block per utterance, a fixed summation tree (deterministic)
@@ -249,69 +395,95 @@ __global__ __launch_bounds__(256) void kd_utt_sum_kernel(const float* __restrict
   if (threadIdx.x == 0) utt[blockIdx.x] = (red[0] + red[1]) + (red[2] + red[3]);
 }
 
-// d loss / d x[c] of one element, a = x[c] / tau.  k = upstream gradient / tau.
-//   full:      k (q_c - p_c)
-//   collapsed: k (Q_j - P_j) w_c for c in class j, Q / P the student's / teacher's class masses and w_c the share of column
-//              c in its class: 1 for the blank and the symbol, exp(a - Rs) for a rest column (q_c = Q_rest exp(a - Rs))
-// Either way a student that equals the teacher gets exact zeros: both sides of every difference are computed alike.
+// d loss / d x[c] of one element, a = x[c] / tau, b = y[c] / tau.  k = upstream gradient * weight / tau.
+//   main softmax, full:       kk (q_c - p_c)
+//                 collapsed:  kk (Q_j - P_j) w_c for c in class j, Q / P the student's / teacher's class masses and w_c the
+//                             share of column c in its class: 1 for the blank and the symbol, exp(a - Rs) for a rest column
+//                             (q_c = Q_rest exp(a - Rs))
+//                 kk = k, or k (1 - pb) for HAT, whose blank column gets k (qb - pb) instead
+//   duration column (TDT):    k dur_weight (qd_n - pd_n); exact zeros when dur_weight == 0
+// A student that equals the teacher gets exact zeros: both sides of every difference are computed alike.
 struct KdGrad {
-  float k, Ls, Lt, Rs, db, ds, dr;
-  int k0, k1;
-  template <bool COLL>
+  float k, kk, kdur, Ls, Lt, Rs, Ds, Dt, db, ds, dr;
+  int k0, k1, Ct;
+  bool dur_on;
+  template <int FORM, bool COLL>
   __device__ __forceinline__ float at(int c, float a, float b) const {
-    if (!COLL) return k * (__expf(a - Ls) - __expf(b - Lt));
-    return k * (c == k0 ? db : c == k1 ? ds : (dr == 0.0f ? 0.0f : dr * __expf(a - Rs)));
+    if (FORM == KD_TDT && c >= Ct) return dur_on ? kdur * (__expf(a - Ds) - __expf(b - Dt)) : 0.0f;
+    if (FORM == KD_HAT && c == k0) return k * db;
+    if (!COLL) return kk * (__expf(a - Ls) - __expf(b - Lt));
+    return kk * (c == k0 ? db : c == k1 ? ds : (dr == 0.0f ? 0.0f : dr * __expf(a - Rs)));
   }
 };
 
-template <typename ES, typename ET, bool VEC, bool COLL>
+template <typename ES, typename ET, bool VEC, int FORM, bool COLL>
 __global__ void kd_bwd_kernel(const ES* __restrict__ x, const ET* __restrict__ y, const int32_t* __restrict__ symbols,
-                              const int32_t* __restrict__ ranges, const int32_t* __restrict__ boundary, int blank,
-                              float inv_tau, const float* __restrict__ saved, const Scale scale, ES* __restrict__ gx,
-                              size_t rows, int T, int S, int C, int r) {
+                              const int32_t* __restrict__ ranges, const int32_t* __restrict__ boundary,
+                              const float* __restrict__ weights, int blank, float inv_tau, float dw,
+                              const float* __restrict__ saved, const Scale scale, ES* __restrict__ gx, size_t rows, int T,
+                              int S, int W, int N, int r) {
+  constexpr bool HAT = FORM == KD_HAT;
+  if (FORM == KD_PLAIN) { weights = nullptr; N = 0; }
   const int lane = threadIdx.x & 63;
   const size_t row = (size_t)blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
   if (row >= rows) return;
-  const KdRow g = kd_row<COLL>(row, symbols, ranges, boundary, blank, T, S, C, r);
-  ES* gr = gx + row * C;
+  const int Ct = W - N;
+  const KdRow g = kd_row<COLL>(row, symbols, ranges, boundary, weights, blank, T, S, Ct, r);
+  ES* gr = gx + row * W;
   if (!g.valid) {   // zeros, without a look at the logits
     if (VEC) {
       const f4 zero = {0.0f, 0.0f, 0.0f, 0.0f};
-      for (int i = lane; i < (C >> 2); i += 64) store4(gr, i, zero);
+      for (int i = lane; i < (W >> 2); i += 64) store4(gr, i, zero);
     } else {
-      for (int c = lane; c < C; c += 64) gr[c] = elem_from_float<ES>(0.0f);
+      for (int c = lane; c < W; c += 64) gr[c] = elem_from_float<ES>(0.0f);
     }
     return;
   }
-  const ES* xr = x + row * C;
-  const ET* yr = y + row * C;
+  const ES* xr = x + row * W;
+  const ET* yr = y + row * W;
   KdGrad d;
   d.k = scale.at(g.b) * inv_tau;
+  if (weights) d.k *= g.w;
+  d.kk = d.k;
   d.Ls = saved[row];
   d.Lt = saved[rows + row];
-  d.Rs = 0.0f; d.db = 0.0f; d.ds = 0.0f; d.dr = 0.0f;
-  d.k0 = g.k0; d.k1 = g.k1;
-  if (COLL) {   // the teacher enters through its three class masses only: two of its logits and Rt, not its row
+  d.Rs = 0.0f; d.Ds = 0.0f; d.Dt = 0.0f; d.db = 0.0f; d.ds = 0.0f; d.dr = 0.0f; d.kdur = 0.0f;
+  d.k0 = g.k0; d.k1 = g.k1; d.Ct = Ct;
+  d.dur_on = FORM == KD_TDT && N > 0 && dw != 0.0f;
+  if (d.dur_on) {
+    const int p0 = COLL ? 4 : 2;
+    d.Ds = saved[(size_t)p0 * rows + row];
+    d.Dt = saved[(size_t)(p0 + 1) * rows + row];
+    d.kdur = d.k * dw;
+  }
+  if (HAT) {
+    float qb, qn, pb, pn;
+    hat_sigmoids(elem_to_float(xr[g.k0]) * inv_tau, &qb, &qn);
+    hat_sigmoids(elem_to_float(yr[g.k0]) * inv_tau, &pb, &pn);
+    d.db = qb - pb;
+    d.kk = d.k * pn;
+  }
+  if (COLL) {   // the teacher enters through its class masses only: its class logits and Rt, not its row
     d.Rs = saved[2 * rows + row];
-    d.db = __expf(elem_to_float(xr[g.k0]) * inv_tau - d.Ls) - __expf(elem_to_float(yr[g.k0]) * inv_tau - d.Lt);
+    if (!HAT) d.db = __expf(elem_to_float(xr[g.k0]) * inv_tau - d.Ls) - __expf(elem_to_float(yr[g.k0]) * inv_tau - d.Lt);
     if (g.k1 >= 0) d.ds = __expf(elem_to_float(xr[g.k1]) * inv_tau - d.Ls) - __expf(elem_to_float(yr[g.k1]) * inv_tau - d.Lt);
     d.dr = __expf(d.Rs - d.Ls) - __expf(saved[3 * rows + row] - d.Lt);
   }
   if (VEC) {
-    const int n4 = C >> 2;
+    const int n4 = W >> 2;
     for (int i = lane; i < n4; i += 64) {
       const f4 v = load4(xr, i);
       f4 w = {0.0f, 0.0f, 0.0f, 0.0f};
-      if (!COLL) w = load4(yr, i);
+      if (!COLL || (d.dur_on && 4 * i + 3 >= Ct)) w = load4(yr, i);   // collapsed: only the quads with a duration column
       f4 o;
 #pragma unroll
-      for (int e = 0; e < 4; ++e) o[e] = d.at<COLL>(4 * i + e, v[e] * inv_tau, w[e] * inv_tau);
+      for (int e = 0; e < 4; ++e) o[e] = d.at<FORM, COLL>(4 * i + e, v[e] * inv_tau, w[e] * inv_tau);
       store4(gr, i, o);
     }
   } else {
-    for (int c = lane; c < C; c += 64) {
-      const float b = COLL ? 0.0f : elem_to_float(yr[c]) * inv_tau;
-      gr[c] = elem_from_float<ES>(d.at<COLL>(c, elem_to_float(xr[c]) * inv_tau, b));
+    for (int c = lane; c < W; c += 64) {
+      const float b = (!COLL || (d.dur_on && c >= Ct)) ? elem_to_float(yr[c]) * inv_tau : 0.0f;
+      gr[c] = elem_from_float<ES>(d.at<FORM, COLL>(c, elem_to_float(xr[c]) * inv_tau, b));
     }
   }
 }
@@ -322,14 +494,20 @@ inline auto dispatch_dtype2(int dtype, int teacher_dtype, F&& f) {
   return dispatch_dtype(dtype, [&](auto s) { return dispatch_dtype(teacher_dtype, [&](auto t) { return f(s, t); }); });
 }
 
+// the row form of a call: one softmax without weights is the plain form; with weights it runs as TDT with n_dur = 0
+inline int kd_form(int hat, int n_dur, const float* weights) { return hat ? KD_HAT : (n_dur > 0 || weights) ? KD_TDT : KD_PLAIN; }
+
 }  // namespace
 
 int pruned_kd_fwd(const void* logits, int dtype, const void* teacher, int teacher_dtype, const int32_t* symbols,
-                  const int32_t* ranges, const int32_t* boundary, int blank, float temperature, int collapsed,
-                  float* node, float* saved, float* utt, int B, int T, int S, int C, int r, hipStream_t st) {
+                  const int32_t* ranges, const int32_t* boundary, int blank, float temperature, int collapsed, int hat,
+                  int n_dur, float dur_weight, const float* weights, float* node, float* saved, float* utt, int B, int T,
+                  int S, int W, int r, hipStream_t st) {
+  const int form = kd_form(hat, n_dur, weights);
+  const char* name = form == KD_PLAIN ? "pruned_kd_fwd" : "pruned_kd_fact_fwd";   // the names the messages have always carried
   const size_t rows = (size_t)B * T * r;
   if (rows == 0) return FTR_OK;
-  { const int rc32 = require_rows_32bit("pruned_kd_fwd", rows); if (rc32 != FTR_OK) return rc32; }
+  { const int rc32 = require_rows_32bit(name, rows); if (rc32 != FTR_OK) return rc32; }
   const int wpb = 4;
   const unsigned blocks = (unsigned)((rows + wpb - 1) / wpb);
   const float inv_tau = 1.0f / temperature;
@@ -338,32 +516,38 @@ int pruned_kd_fwd(const void* logits, int dtype, const void* teacher, int teache
     using ET = typename decltype(ttag)::type;
     const ES* x = static_cast<const ES*>(logits);
     const ET* y = static_cast<const ET*>(teacher);
-    const bool vec4 = rows_vec4<ES>(C, x) && rows_vec4<ET>(C, y);
-    dispatch(collapsed != 0, [&](auto coll) {
-      constexpr bool COLL = decltype(coll)::value;
-      if (vec4 && C <= 2048)   // both rows fit the registers of a wave: 1, 2, 4 or 8 quads of elements per lane and tensor
-        dispatch_among<1, 2, 4, 8>(C <= 256 ? 1 : C <= 512 ? 2 : C <= 1024 ? 4 : 8, [&](auto n) {
-          hipLaunchKernelGGL((kd_fwd_reg_kernel<ES, ET, decltype(n)::value, COLL>), dim3(blocks), dim3(64 * wpb), 0, st, x, y, symbols,
-                             ranges, boundary, blank, inv_tau, node, saved, rows, T, S, C, r);
-        });
-      else
-        dispatch(vec4, [&](auto vec) {
-          hipLaunchKernelGGL((kd_fwd_kernel<ES, ET, decltype(vec)::value, COLL>), dim3(blocks), dim3(64 * wpb), 0, st, x, y, symbols,
-                             ranges, boundary, blank, inv_tau, node, saved, rows, T, S, C, r);
-        });
+    const bool vec4 = rows_vec4<ES>(W, x) && rows_vec4<ET>(W, y);
+    dispatch_among<KD_PLAIN, KD_HAT, KD_TDT>(form, [&](auto f) {
+      dispatch(collapsed != 0, [&](auto coll) {
+        constexpr int FORM = decltype(f)::value;
+        constexpr bool COLL = decltype(coll)::value;
+        if (vec4 && W <= 2048)   // both rows fit the registers of a wave: 1, 2, 4 or 8 quads of elements per lane and tensor
+          dispatch_among<1, 2, 4, 8>(W <= 256 ? 1 : W <= 512 ? 2 : W <= 1024 ? 4 : 8, [&](auto n) {
+            hipLaunchKernelGGL((kd_fwd_reg_kernel<ES, ET, decltype(n)::value, FORM, COLL>), dim3(blocks), dim3(64 * wpb), 0, st, x, y,
+                               symbols, ranges, boundary, weights, blank, inv_tau, dur_weight, node, saved, rows, T, S, W, n_dur, r);
+          });
+        else
+          dispatch(vec4, [&](auto vec) {
+            hipLaunchKernelGGL((kd_fwd_kernel<ES, ET, decltype(vec)::value, FORM, COLL>), dim3(blocks), dim3(64 * wpb), 0, st, x, y,
+                               symbols, ranges, boundary, weights, blank, inv_tau, dur_weight, node, saved, rows, T, S, W, n_dur, r);
+          });
+      });
     });
   });
-  { const int rc = check_launch("pruned_kd_fwd"); if (rc != FTR_OK) return rc; }
+  { const int rc = check_launch(name); if (rc != FTR_OK) return rc; }
   hipLaunchKernelGGL(kd_utt_sum_kernel, dim3(B), dim3(256), 0, st, node, utt, T * r);
   return check_launch("pruned_kd_utt_sum");
 }
 
 int pruned_kd_bwd(const void* logits, int dtype, const void* teacher, int teacher_dtype, const int32_t* symbols,
-                  const int32_t* ranges, const int32_t* boundary, int blank, float temperature, int collapsed,
-                  const float* saved, Scale scale, void* glogits, int B, int T, int S, int C, int r, hipStream_t st) {
+                  const int32_t* ranges, const int32_t* boundary, int blank, float temperature, int collapsed, int hat,
+                  int n_dur, float dur_weight, const float* weights, const float* saved, Scale scale, void* glogits, int B,
+                  int T, int S, int W, int r, hipStream_t st) {
+  const int form = kd_form(hat, n_dur, weights);
+  const char* name = form == KD_PLAIN ? "pruned_kd_bwd" : "pruned_kd_fact_bwd";
   const size_t rows = (size_t)B * T * r;
   if (rows == 0) return FTR_OK;
-  { const int rc32 = require_rows_32bit("pruned_kd_bwd", rows); if (rc32 != FTR_OK) return rc32; }
+  { const int rc32 = require_rows_32bit(name, rows); if (rc32 != FTR_OK) return rc32; }
   const int wpb = 4;
   const unsigned blocks = (unsigned)((rows + wpb - 1) / wpb);
   const float inv_tau = 1.0f / temperature;
@@ -372,20 +556,17 @@ int pruned_kd_bwd(const void* logits, int dtype, const void* teacher, int teache
     using ET = typename decltype(ttag)::type;
     const ES* x = static_cast<const ES*>(logits);
     const ET* y = static_cast<const ET*>(teacher);
-    dispatch(rows_vec4<ES>(C, x, glogits) && rows_vec4<ET>(C, y), [&](auto vec) {
-      dispatch(collapsed != 0, [&](auto coll) {
-        hipLaunchKernelGGL((kd_bwd_kernel<ES, ET, decltype(vec)::value, decltype(coll)::value>), dim3(blocks), dim3(64 * wpb), 0, st, x, y,
-                           symbols, ranges, boundary, blank, inv_tau, saved, scale, static_cast<ES*>(glogits), rows, T, S, C, r);
+    dispatch(rows_vec4<ES>(W, x, glogits) && rows_vec4<ET>(W, y), [&](auto vec) {
+      dispatch_among<KD_PLAIN, KD_HAT, KD_TDT>(form, [&](auto f) {
+        dispatch(collapsed != 0, [&](auto coll) {
+          hipLaunchKernelGGL((kd_bwd_kernel<ES, ET, decltype(vec)::value, decltype(f)::value, decltype(coll)::value>), dim3(blocks),
+                             dim3(64 * wpb), 0, st, x, y, symbols, ranges, boundary, weights, blank, inv_tau, dur_weight, saved, scale,
+                             static_cast<ES*>(glogits), rows, T, S, W, n_dur, r);
+        });
       });
     });
   });
-  return check_launch("pruned_kd_bwd");
-}
-
-// kd_utt_sum_kernel for the factored forms of pruned_kd_fact.hip: the same kernel, the same summation tree
-int pruned_kd_utt_sum(const float* node, float* utt, int B, int per, hipStream_t st) {
-  hipLaunchKernelGGL(kd_utt_sum_kernel, dim3(B), dim3(256), 0, st, node, utt, per);
-  return check_launch("pruned_kd_utt_sum");
+  return check_launch(name);
 }
 
 }  // namespace ftr

@@ -16,7 +16,7 @@ What runs where:
   reference counterpart): the same kernels and routes with the HAT normalisation of the joiner output.
 * ``rnnt_kd_loss_pruned`` (MI355X addition, no reference counterpart): knowledge distillation on the pruned band, two
   stream kernels of its own (include/ftr_kd.h, csrc/pruned_kd.hip); ``rnnt_kd_loss_pruned_factored``: the same for HAT and
-  TDT rows and with node weights (include/ftr_kd_fact.h, csrc/pruned_kd_fact.hip).
+  TDT rows and with node weights (include/ftr_kd_fact.h, the same kernels in their other two row forms).
 
 Reference bugs that are NOT reproduced: ``rnnt_loss_simple(reduction="mean")``
 raises NameError there (rnnt_loss.py:331) -- here it is the mean; ``boundary=None`` works; the
@@ -1066,47 +1066,6 @@ def _kd_head(x, y):
     return (_ptr(x), _LOWP_KIND.get(x.dtype, _lib.FTR_DTYPE_F32), _ptr(y), _LOWP_KIND.get(y.dtype, _lib.FTR_DTYPE_F32))
 
 
-class _PrunedKdLoss(torch.autograd.Function):
-    """rnnt_kd_loss_pruned as one node: forward = one pass over both tensors (node losses and the row normalisers the
-    backward needs) + the per-utterance sum [+ the batch reduction]; backward = one streaming pass that writes d loss / d
-    logits in the student's dtype, the upstream gradient folded in.  The teacher gets no gradient."""
-
-    @staticmethod
-    def forward(ctx, logits, teacher_logits, symbols, ranges, termination_symbol, boundary, mode, temperature, code):
-        B, T, r, C = logits.shape
-        S = symbols.shape[1]
-        x = logits.detach().contiguous()
-        y = teacher_logits.detach().contiguous()
-        node = torch.empty((B, T, r), dtype=torch.float32, device=x.device)
-        saved = torch.empty((4 if mode == _lib.FTR_KD_COLLAPSED else 2, B, T, r), dtype=torch.float32, device=x.device)
-        utt = torch.empty((B,), dtype=torch.float32, device=x.device)
-        out = utt
-        with torch.cuda.device(x.device):
-            st = _stream_ptr(x)
-            _lib.call("ftr_pruned_kd_fwd_dt", *_kd_head(x, y), _ptr(symbols), _ptr(ranges), _ptr(boundary),
-                      int(termination_symbol), float(temperature), mode, _ptr(node), _ptr(saved), _ptr(utt), B, T, S, C, r, st)
-            if code != 0:
-                out = torch.empty((), dtype=torch.float32, device=x.device)
-                _lib.call("ftr_pruned_kd_reduce_f32", _ptr(utt), B, code, _ptr(out), st)
-        if logits.requires_grad:
-            ctx.save_for_backward(x, y, symbols, ranges, saved, boundary)
-        ctx.meta = (int(termination_symbol), mode, float(temperature), int(code))
-        return out
-
-    @staticmethod
-    def backward(ctx, g_loss):
-        x, y, symbols, ranges, saved, boundary = ctx.saved_tensors
-        blank, mode, temperature, code = ctx.meta
-        B, T, r, C = x.shape
-        scale, stride, mul = _upstream_scale(g_loss, code, B)   # its multiplier negates: this loss is not a negated score
-        g = torch.empty_like(x)
-        with torch.cuda.device(x.device):
-            _lib.call("ftr_pruned_kd_bwd_scaled_dt", *_kd_head(x, y), _ptr(symbols), _ptr(ranges), _ptr(boundary), blank,
-                      temperature, mode, _ptr(saved), _ptr(scale), stride, -mul, _ptr(g), B, T, symbols.shape[1], C, r,
-                      _stream_ptr(x))
-        return g, None, None, None, None, None, None, None, None
-
-
 def rnnt_kd_loss_pruned(
     logits: torch.Tensor,
     teacher_logits: torch.Tensor,
@@ -1140,35 +1099,18 @@ def rnnt_kd_loss_pruned(
     batch).  Float32, bit-identical from run to run.  The gradient goes to ``logits`` only, in its dtype (computed in
     float32, rounded once); ``teacher_logits`` never gets one.  A NaN in a valid row makes its utterance's loss NaN; a
     student logit of -inf where the teacher has mass makes it +inf."""
-    for name, t in (("logits", logits), ("teacher_logits", teacher_logits)):
-        if t.dtype not in _KD_DTYPES:
-            raise TypeError(f"{name} must be float32, bfloat16 or float16, got {t.dtype}")
-    if logits.dim() != 4:
-        raise ValueError("logits must be [B,T,s_range,C]")
-    if tuple(teacher_logits.shape) != tuple(logits.shape):
-        raise ValueError(f"teacher_logits must have the shape of logits {tuple(logits.shape)}, got {tuple(teacher_logits.shape)}")
-    if mode not in _KD_MODES:
-        raise ValueError(f"mode should be ('full' | 'collapsed'), given {mode}")
-    temperature = float(temperature)
-    if not (0.0 < temperature < float("inf")):
-        raise ValueError(f"temperature must be a finite number > 0, given {temperature}")
-    code = _reduction_code(reduction)
-    if not 0 <= int(termination_symbol) < logits.shape[3]:
-        raise ValueError(f"termination_symbol {termination_symbol} not in [0,{logits.shape[3]})")
-    symbols, ranges, boundary = _pruned_inputs(logits, symbols, ranges, boundary, lowp=True)
-    _require_gpu(teacher_logits, "teacher_logits")
-    if teacher_logits.device != logits.device:
-        raise ValueError("teacher_logits and logits must be on the same device")
-    return _PrunedKdLoss.apply(logits, teacher_logits, symbols, ranges, int(termination_symbol), boundary, _KD_MODES[mode],
-                               temperature, code)
+    return rnnt_kd_loss_pruned_factored(logits, teacher_logits, symbols, ranges, termination_symbol, boundary,
+                                        factorization="softmax", mode=mode, temperature=temperature, reduction=reduction)
 
 
 _KD_FACTORIZATIONS = {"softmax": _lib.FTR_KD_FACT_SOFTMAX, "hat": _lib.FTR_KD_FACT_HAT, "tdt": _lib.FTR_KD_FACT_TDT}
 
 
-class _PrunedKdFactLoss(torch.autograd.Function):
-    """rnnt_kd_loss_pruned_factored as one node, in the manner of _PrunedKdLoss: the entries of include/ftr_kd_fact.h.
-    Neither the teacher nor the node weights get a gradient."""
+class _PrunedKdLoss(torch.autograd.Function):
+    """rnnt_kd_loss_pruned_factored as one node (the entries of include/ftr_kd_fact.h): forward = one pass over both tensors
+    (node losses and the row normalisers the backward needs) + the per-utterance sum [+ the batch reduction]; backward = one
+    streaming pass that writes d loss / d logits in the student's dtype, the upstream gradient folded in.  Neither the
+    teacher nor the node weights get a gradient."""
 
     @staticmethod
     def forward(ctx, logits, teacher_logits, symbols, ranges, termination_symbol, boundary, mode, temperature, code, fact,
@@ -1311,9 +1253,8 @@ def rnnt_kd_loss_pruned_factored(
         if node_weights.device != logits.device:
             raise ValueError("node_weights and logits must be on the same device")
         node_weights = node_weights.detach().contiguous()
-    return _PrunedKdFactLoss.apply(logits, teacher_logits, symbols, ranges, int(termination_symbol), boundary, _KD_MODES[mode],
-                                   temperature, code, _KD_FACTORIZATIONS[factorization], num_durations, duration_weight,
-                                   node_weights)
+    return _PrunedKdLoss.apply(logits, teacher_logits, symbols, ranges, int(termination_symbol), boundary, _KD_MODES[mode],
+                               temperature, code, _KD_FACTORIZATIONS[factorization], num_durations, duration_weight, node_weights)
 
 
 # ---- multi-blank transducer (MI355X addition, no reference counterpart): big blanks that advance several frames
