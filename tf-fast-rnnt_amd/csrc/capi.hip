@@ -1,4 +1,4 @@
-// csrc/capi.hip -- the extern "C" surface declared in include/ftr.h, include/ftr_lowp.h, include/ftr_prune_sum.h, include/ftr_joiner_act.h, include/ftr_kd.h, include/ftr_kd_fact.h, include/ftr_fused.h and include/ftr_live.h: argument validation and error reporting.  No
+// csrc/capi.hip -- the extern "C" surface declared in include/ftr.h, include/ftr_lowp.h, include/ftr_prune_sum.h, include/ftr_joiner_act.h, include/ftr_kd.h, include/ftr_kd_fact.h, include/ftr_kd_loss.h, include/ftr_fused.h and include/ftr_live.h: argument validation and error reporting.  No
 // allocation, no host synchronisation, no CPU fallback.  Built twice: into libftr_hip.so (the product: the symbols of
 // ftr.h and ftr_lowp.h and nothing else) and, with -DFTR_DIAG, into the test-only _build/libftr_hip_diag.so, which adds the symbols of
 // include/ftr_diag.h: the "plain" kernel family (the reference's arithmetic on the device, mi_plain.hip), its
@@ -1506,6 +1506,48 @@ int ftr_pruned_kd_fact_bwd_scaled_dt(const void* logits, int kind, const void* t
   return kd_bwd("pruned_kd_fact_bwd_scaled_dt", logits, kind, teacher_logits, teacher_kind, symbols, ranges, boundary,
                 termination_symbol, temperature, mode, saved, scale, scale_stride, scale_mul, glogits, B, T, S, C, r, factorization,
                 n_dur, dur_weight, node_weights, stream);
+}
+
+// ---- include/ftr_kd_loss.h: the transducer loss on the band and the plain distillation loss in one pass (csrc/pruned_kd.hip)
+int ftr_pruned_band_kd_fwd_dt(const void* logits, int kind, const void* teacher_logits, int teacher_kind,
+                              const int32_t* symbols, const int32_t* ranges, const int32_t* boundary, int termination_symbol,
+                              float temperature, int mode, double delay_penalty, int modified, float* lse, float* px_band,
+                              float* py_band, float* node_loss, float* saved, float* utt_loss, int B, int T, int S, int C,
+                              int r, void* stream) {
+  const char* what = "pruned_band_kd_fwd_dt";
+  clear_error();
+  FTR_TRY(kd_check_head(what, kind, teacher_kind, mode, temperature, FTR_KD_FACT_SOFTMAX, 0, 0.0f, C));
+  FTR_TRY(check_builder(what, B >= 0 && T >= 1 && S >= 0 && C >= 1 && r >= 1, termination_symbol, C));
+  if (B == 0) return FTR_OK;
+  FTR_TRY(pointers_then_device(what, logits && teacher_logits && ranges && lse && px_band && py_band && node_loss && saved &&
+                                         utt_loss && (symbols || S == 0)));
+  return pruned_band_kd_fwd(logits, kind, teacher_logits, teacher_kind, symbols, ranges, boundary, termination_symbol, temperature,
+                            mode == FTR_KD_COLLAPSED, delay_penalty, modified, lse, px_band, py_band, node_loss, saved, utt_loss, B, T,
+                            S, C, r, stream_of(stream));
+}
+
+int ftr_pruned_band_kd_bwd_scaled_dt(const void* logits, int kind, const void* teacher_logits, int teacher_kind,
+                                     const int32_t* symbols, const int32_t* ranges, const int32_t* boundary,
+                                     int termination_symbol, float temperature, int mode, const float* lse,
+                                     const float* gx_band, const float* gy_band, const float* loss_scale,
+                                     int loss_scale_stride, float loss_scale_mul, const float* saved, const float* kd_scale,
+                                     int kd_scale_stride, float kd_scale_mul, void* glogits, int B, int T, int S, int C,
+                                     int r, void* stream) {
+  const char* what = "pruned_band_kd_bwd_scaled_dt";
+  clear_error();
+  FTR_TRY(kd_check_head(what, kind, teacher_kind, mode, temperature, FTR_KD_FACT_SOFTMAX, 0, 0.0f, C));
+  FTR_REQUIRE(loss_scale_mul >= -3.0e38f && loss_scale_mul <= 3.0e38f && kd_scale_mul >= -3.0e38f && kd_scale_mul <= 3.0e38f,
+              "%s: the multipliers %g and %g must be finite", what, (double)loss_scale_mul, (double)kd_scale_mul);
+  FTR_TRY(check_builder(what, B >= 0 && T >= 1 && S >= 0 && C >= 1 && r >= 1, termination_symbol, C, true));
+  FTR_TRY(check_scale_stride(what, loss_scale_stride));
+  FTR_TRY(check_scale_stride(what, kd_scale_stride));
+  if (B == 0) return FTR_OK;
+  const bool loss_on = loss_scale_mul != 0.0f, kd_on = kd_scale_mul != 0.0f;
+  FTR_TRY(pointers_then_device(what, logits && ranges && glogits && (symbols || S == 0) && (!loss_on || (lse && gx_band && gy_band)) &&
+                                         (!kd_on || (teacher_logits && saved))));
+  return pruned_band_kd_bwd(logits, kind, teacher_logits, teacher_kind, symbols, ranges, boundary, termination_symbol, temperature,
+                            mode == FTR_KD_COLLAPSED, lse, gx_band, gy_band, Scale{loss_scale, loss_scale_stride, loss_scale_mul}, saved,
+                            Scale{kd_scale, kd_scale_stride, kd_scale_mul}, glogits, B, T, S, C, r, stream_of(stream));
 }
 
 int ftr_selftest(void* scratch_dev, void* stream) {

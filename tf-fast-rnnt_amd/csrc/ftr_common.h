@@ -5,6 +5,7 @@
 #include <stdio.h>
 #include <stdarg.h>
 #include "../../include/ftr_kd_fact.h"  // and, through it, ftr_kd.h, ftr_lowp.h and ftr.h
+#include "../../include/ftr_kd_loss.h"
 #include "../../include/ftr_prune_sum.h"
 #include "../../include/ftr_joiner_act.h"
 #include "../../include/ftr_fused.h"
@@ -315,6 +316,9 @@ int negated_reduce(const float* ans, int B, int reduction, float* out, hipStream
 // knowledge distillation on the pruned band: csrc/pruned_kd.hip (collapsed != 0: the three-class form; hat != 0: the HAT rows; n_dur: duration columns at the end of a row of width W; weights [B,T,r] or NULL; saved: 2 + 2 collapsed + 2 with n_dur > 0 planes of [B,T,r]; hat = n_dur = 0 and weights = NULL: the plain form)
 int pruned_kd_fwd(const void* logits, int dtype, const void* teacher, int teacher_dtype, const int32_t* symbols, const int32_t* ranges, const int32_t* boundary, int blank, float temperature, int collapsed, int hat, int n_dur, float dur_weight, const float* weights, float* node, float* saved, float* utt, int B, int T, int S, int W, int r, hipStream_t st);
 int pruned_kd_bwd(const void* logits, int dtype, const void* teacher, int teacher_dtype, const int32_t* symbols, const int32_t* ranges, const int32_t* boundary, int blank, float temperature, int collapsed, int hat, int n_dur, float dur_weight, const float* weights, const float* saved, Scale scale, void* glogits, int B, int T, int S, int W, int r, hipStream_t st);
+// the same pass carrying the transducer loss on the band (include/ftr_kd_loss.h; plain form): the forward also writes lse and the band operands, the backward adds the band gradient; a Scale with mul == 0: that part is not read
+int pruned_band_kd_fwd(const void* logits, int dtype, const void* teacher, int teacher_dtype, const int32_t* symbols, const int32_t* ranges, const int32_t* boundary, int blank, float temperature, int collapsed, double delay_penalty, int modified, float* lse, float* pxb, float* pyb, float* node, float* saved, float* utt, int B, int T, int S, int W, int r, hipStream_t st);
+int pruned_band_kd_bwd(const void* logits, int dtype, const void* teacher, int teacher_dtype, const int32_t* symbols, const int32_t* ranges, const int32_t* boundary, int blank, float temperature, int collapsed, const float* lse, const float* gxb, const float* gyb, Scale scale, const float* saved, Scale kd_scale, void* glogits, int B, int T, int S, int W, int r, hipStream_t st);
 int lse_rows(const float* logits, float* lse, size_t rows, int C, int blank, int hat, hipStream_t st);
 int lse_rows_dtype(const void* logits, int dtype, float* lse, size_t rows, int C, int blank, int hat, hipStream_t st);
 int mi_band_supported(int T, int S, int r);

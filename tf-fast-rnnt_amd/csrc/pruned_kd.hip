@@ -1,4 +1,4 @@
-// csrc/pruned_kd.hip -- knowledge distillation on the pruned band (include/ftr_kd.h, include/ftr_kd_fact.h; MI355X addition,
+// csrc/pruned_kd.hip -- knowledge distillation on the pruned band (include/ftr_kd.h, include/ftr_kd_fact.h, include/ftr_kd_loss.h; MI355X addition,
 // no reference counterpart), gfx950.
 // Student and teacher joiner logits x, y [B,T,r,W] on the same `ranges`; per valid node (b,t,k) the loss is KL(p || q) with
 // p = softmax(y / tau), q = softmax(x / tau) over the columns ("full"), or over three classes -- blank, the correct next
@@ -21,6 +21,9 @@
 //   kd_utt_sum_kernel  node losses -> per-utterance loss, one block per utterance, fixed summation tree
 //   kd_bwd_kernel      one streaming pass: d loss / d x from x, y and the normalisers the forward saved (no reduction); it
 //                      writes all W columns of the gradient row
+// The three row kernels also have a loss-carrying instantiation of the plain form (LOSS; include/ftr_kd_loss.h): the forward
+// writes the student's temperature-1 logsumexp for the transducer loss on the band as well, the backward adds that loss's
+// gradient row; see KdLossOut and KdLossIn below.
 // The three forms share the column -> lane mapping and the order of every sum.  The columns that are not part of the main
 // sums (HAT: the blank; TDT: the duration columns; collapsed: the class columns) are masked to -inf in registers, as
 // tdt_lse_kernel of tdt_logprobs.hip masks 4 * i + e >= C.  What is left at the end of a row: HAT, the Bernoulli term from
@@ -48,7 +51,9 @@ __device__ __forceinline__ float wave_sum(float v) { return wave_sum_dpp(v); }
 
 // what a wave knows about its row before it touches the logits: is the node valid, whose utterance is it, its weight (1
 // without weights), the blank column k0 and (collapsed) the symbol column k1 (-1: the node has no symbol class)
-struct KdRow { bool valid; int b, k0, k1; float w; };
+// (lrow, s: for the loss-carrying instantiations only -- does the band recursion look at this row's px / py at all, i.e. is
+// t inside the frames of the rectangle and s inside the lattice; and the node's lattice row)
+struct KdRow { bool valid, lrow; int b, s, k0, k1; float w; };
 
 template <bool COLL>
 __device__ __forceinline__ KdRow kd_row(size_t row, const int32_t* __restrict__ symbols, const int32_t* __restrict__ ranges,
@@ -61,6 +66,8 @@ __device__ __forceinline__ KdRow kd_row(size_t row, const int32_t* __restrict__ 
   const int s = ranges[row];
   const Bound bd = load_boundary(boundary, g.b, S, T);   // clamped into the lattice: s < se implies s < S below
   g.valid = t >= bd.tb && t < bd.te && s >= bd.sb && s <= bd.se;
+  g.lrow = t >= bd.tb && t < bd.te && s >= 0 && s <= S;
+  g.s = s;
   g.w = 1.0f;
   if (weights) {
     g.w = weights[row];
@@ -217,12 +224,81 @@ __device__ __forceinline__ bool kd_masked(int c, int Ct, int k0, int k1) {
   return (FORM == KD_TDT && c >= Ct) || ((FORM == KD_HAT || COLL) && c == k0) || (COLL && c == k1);
 }
 
-template <typename ES, typename ET, int NQ, int FORM, bool COLL>
+// ---- the loss-carrying instantiations (include/ftr_kd_loss.h; LOSS, plain form only): the forward kernels also write lse1,
+// the temperature-1 logsumexp of the student row over all W columns, which is the normaliser of the transducer loss
+// (band_gather_kernel and band_grad_banded_kernel of mi_band.hip read it).  What they take on top is a trailing parameter
+// pack, empty for every other instantiation, as tdt_logprobs.hip does for MIX.
+// lse1 restates lse_rows_reg_kernel / lse_rows_kernel of pruned_logprobs.hip operation for operation -- the raw maximum (no
+// kd_safe_max: a row of -inf gives NaN there too), the exponentials of a quad added left to right and then to the lane's
+// sum, the lanes' sums through the same DPP ladder -- so that the loss is the loss of rnnt_loss_pruned bit for bit.
+// Which rows carry it: every node the band recursion looks at, and that is more than the valid nodes -- its shift constants
+// (ftr_common.h, Shift) are means over ALL band entries of the frames [t_begin, t_end), the rows past s_end included.  Such a
+// row (KdRow::lrow and not valid) has its student row read for lse1 alone; the teacher's is not.  Outside those frames
+// nothing is read and lse1 = 0: the recursion never looks there.
+struct KdLossOut { float* lse; };
+template <typename A> __device__ __forceinline__ const A& kd_loss_arg(const A& a) { return a; }
+
+template <int NQ>
+__device__ __forceinline__ float lse1_lane_max(const f4 (&v)[NQ]) {
+  float m = -INFINITY;
+#pragma unroll
+  for (int q = 0; q < NQ; ++q) m = fmaxf(fmaxf(m, fmaxf(v[q][0], v[q][1])), fmaxf(v[q][2], v[q][3]));
+  return m;
+}
+template <int NQ>
+__device__ __forceinline__ float lse1_lane_sum(const f4 (&v)[NQ], float m, int lane, int n4) {
+  float sum = 0.0f;
+#pragma unroll
+  for (int q = 0; q < NQ; ++q) {
+    if (lane + 64 * q < n4)
+      sum += __expf(v[q][0] - m) + __expf(v[q][1] - m) + __expf(v[q][2] - m) + __expf(v[q][3] - m);
+  }
+  return sum;
+}
+// a row that only the loss needs, register resident (W % 4 == 0, W <= 256 * NQ)
+template <typename ES, int NQ>
+__device__ __forceinline__ float lse1_reg(const ES* xr, int lane, int n4) {
+  const f4 ninf = {-INFINITY, -INFINITY, -INFINITY, -INFINITY};
+  f4 v[NQ];
+#pragma unroll
+  for (int q = 0; q < NQ; ++q) {
+    const int i = lane + 64 * q;
+    v[q] = (i < n4) ? load4(xr, i) : ninf;
+  }
+  const float m = wave_max(lse1_lane_max<NQ>(v));
+  return m + __logf(wave_sum(lse1_lane_sum<NQ>(v, m, lane, n4)));
+}
+// any W, two passes: lse_rows_kernel
+template <typename ES, bool VEC>
+__device__ __forceinline__ float lse1_two_pass(const ES* xr, int lane, int W) {
+  float m = -INFINITY, s = 0.0f;
+  if (VEC) {
+    const int n4 = W >> 2;
+    for (int i = lane; i < n4; i += 64) {
+      const f4 v = load4(xr, i);
+      m = fmaxf(fmaxf(m, fmaxf(v[0], v[1])), fmaxf(v[2], v[3]));
+    }
+    m = wave_max(m);
+    for (int i = lane; i < n4; i += 64) {
+      const f4 v = load4(xr, i);
+      s += __expf(v[0] - m) + __expf(v[1] - m) + __expf(v[2] - m) + __expf(v[3] - m);
+    }
+  } else {
+    for (int i = lane; i < W; i += 64) m = fmaxf(m, elem_to_float(xr[i]));
+    m = wave_max(m);
+    for (int i = lane; i < W; i += 64) s += __expf(elem_to_float(xr[i]) - m);
+  }
+  return m + __logf(wave_sum(s));
+}
+
+template <typename ES, typename ET, int NQ, int FORM, bool COLL, bool LOSS = false, typename... L>
 __global__ __launch_bounds__(256) void kd_fwd_reg_kernel(const ES* __restrict__ x, const ET* __restrict__ y,
                                                          const int32_t* __restrict__ symbols, const int32_t* __restrict__ ranges,
                                                          const int32_t* __restrict__ boundary, const float* __restrict__ weights,
                                                          int blank, float inv_tau, float dw, float* __restrict__ node,
-                                                         float* __restrict__ saved, size_t rows, int T, int S, int W, int N, int r) {
+                                                         float* __restrict__ saved, size_t rows, int T, int S, int W, int N, int r,
+                                                         const L... lo) {
+  static_assert(sizeof...(L) == (LOSS ? 1 : 0) && (!LOSS || FORM == KD_PLAIN), "one KdLossOut when LOSS (plain form), else nothing");
   constexpr bool HAT = FORM == KD_HAT;
   if (FORM == KD_PLAIN) { weights = nullptr; N = 0; }   // known at compile time: what hangs on them is not in the plain form's code
   const int lane = threadIdx.x & 63;
@@ -231,13 +307,18 @@ __global__ __launch_bounds__(256) void kd_fwd_reg_kernel(const ES* __restrict__ 
   const size_t row = rows - 1 - rowi;   // last rows first: the tail of a tensor that was just written is what the cache still holds
   const int Ct = W - N;
   const KdRow g = kd_row<COLL>(row, symbols, ranges, boundary, weights, blank, T, S, Ct, r);
+  const int n4 = W >> 2;
+  const ES* xr = x + row * W;
   if (!g.valid) {
+    if constexpr (LOSS) {   // a row of the rectangle's frames past s_end / before s_begin: the student row, for lse1 alone
+      float l1 = 0.0f;
+      if (g.lrow) l1 = lse1_reg<ES, NQ>(xr, lane, n4);
+      if (lane == 0) kd_loss_arg(lo...).lse[row] = l1;
+    }
     if (lane == 0) kd_store_invalid<COLL>(node, saved, rows, row, N);
     return;
   }
-  const int n4 = W >> 2;
   const f4 ninf = {-INFINITY, -INFINITY, -INFINITY, -INFINITY};
-  const ES* xr = x + row * W;
   const ET* yr = y + row * W;
   float xb = -INFINITY, xs = -INFINITY, yb = -INFINITY, ys = -INFINITY;
   if (HAT) {   // the two logits of the Bernoulli term
@@ -265,6 +346,16 @@ __global__ __launch_bounds__(256) void kd_fwd_reg_kernel(const ES* __restrict__ 
   }
   const bool dur_on = FORM == KD_TDT && N > 0 && dw != 0.0f;   // the same for every wave of the launch
   const KfDurLane dur = kf_load_dur(xr, yr, lane, W, Ct, dur_on, inv_tau);
+  // LOSS: lse1 from the registers that hold the student row, before they are scaled and masked.  `share`: full mode at
+  // temperature 1 -- no column is masked, v * 1 is v and ms below is m1, so the exponentials of the student's sum ARE those
+  // of lse1; they are added up a second time in lse1's order instead of being evaluated twice.
+  float m1 = 0.0f, s1 = 0.0f;
+  bool share = false;
+  if constexpr (LOSS) {
+    m1 = wave_max(lse1_lane_max<NQ>(v));
+    share = !COLL && inv_tau == 1.0f && m1 > -INFINITY;   // -inf: ms is kd_safe_max's 0, not m1; NaN compares false
+    if (!share) s1 = lse1_lane_sum<NQ>(v, m1, lane, n4);
+  }
   float ms = -INFINITY, mt = -INFINITY;
 #pragma unroll
   for (int q = 0; q < NQ; ++q) {
@@ -282,17 +373,26 @@ __global__ __launch_bounds__(256) void kd_fwd_reg_kernel(const ES* __restrict__ 
   float ss = 0.0f, st = 0.0f, kl = 0.0f;
 #pragma unroll
   for (int q = 0; q < NQ; ++q) {
+    float ex[4];
 #pragma unroll
     for (int e = 0; e < 4; ++e) {   // masked columns and lanes past the row hold -inf: exp gives 0 and the kl term is skipped
-      ss += __expf(v[q][e] - ms);
+      ex[e] = __expf(v[q][e] - ms);
+      ss += ex[e];
       const float p = __expf(w[q][e] - mt);
       st += p;
       if (!COLL) kl += kd_term(p, w[q][e] - v[q][e]);
+    }
+    if constexpr (LOSS) {
+      if (share && lane + 64 * q < n4) s1 += ex[0] + ex[1] + ex[2] + ex[3];
     }
   }
   ss = wave_sum(ss);
   st = wave_sum(st);
   if (!COLL) kl = wave_sum(kl);
+  if constexpr (LOSS) {
+    s1 = wave_sum(s1);
+    if (lane == 0) kd_loss_arg(lo...).lse[row] = m1 + __logf(s1);
+  }
   KfBern bern = {0.0f, 1.0f};
   if (HAT) bern = kf_hat_bern(xb, yb, lane);   // after the row: its registers are free by now
   float dur_kl = 0.0f, Ds = 0.0f, Dt = 0.0f;
@@ -301,11 +401,12 @@ __global__ __launch_bounds__(256) void kd_fwd_reg_kernel(const ES* __restrict__ 
 }
 
 // any W, one wave per row, two passes (the second hits L1/L2: a row is a few KB)
-template <typename ES, typename ET, bool VEC, int FORM, bool COLL>
+template <typename ES, typename ET, bool VEC, int FORM, bool COLL, bool LOSS = false, typename... L>
 __global__ void kd_fwd_kernel(const ES* __restrict__ x, const ET* __restrict__ y, const int32_t* __restrict__ symbols,
                               const int32_t* __restrict__ ranges, const int32_t* __restrict__ boundary,
                               const float* __restrict__ weights, int blank, float inv_tau, float dw, float* __restrict__ node,
-                              float* __restrict__ saved, size_t rows, int T, int S, int W, int N, int r) {
+                              float* __restrict__ saved, size_t rows, int T, int S, int W, int N, int r, const L... lo) {
+  static_assert(sizeof...(L) == (LOSS ? 1 : 0) && (!LOSS || FORM == KD_PLAIN), "one KdLossOut when LOSS (plain form), else nothing");
   constexpr bool HAT = FORM == KD_HAT;
   if (FORM == KD_PLAIN) { weights = nullptr; N = 0; }
   const int lane = threadIdx.x & 63;
@@ -313,11 +414,16 @@ __global__ void kd_fwd_kernel(const ES* __restrict__ x, const ET* __restrict__ y
   if (row >= rows) return;
   const int Ct = W - N;
   const KdRow g = kd_row<COLL>(row, symbols, ranges, boundary, weights, blank, T, S, Ct, r);
+  const ES* xr = x + row * W;
+  if constexpr (LOSS) {   // lse1 by two passes of its own, in lse_rows_kernel's order: this kernel is the slow path, and the row stays in L1
+    float l1 = 0.0f;
+    if (g.lrow) l1 = lse1_two_pass<ES, VEC>(xr, lane, W);
+    if (lane == 0) kd_loss_arg(lo...).lse[row] = l1;
+  }
   if (!g.valid) {
     if (lane == 0) kd_store_invalid<COLL>(node, saved, rows, row, N);
     return;
   }
-  const ES* xr = x + row * W;
   const ET* yr = y + row * W;
   float xb = -INFINITY, xs = -INFINITY, yb = -INFINITY, ys = -INFINITY;
   if (HAT || COLL) {
@@ -416,17 +522,32 @@ struct KdGrad {
   }
 };
 
-template <typename ES, typename ET, bool VEC, int FORM, bool COLL>
+// LOSS (include/ftr_kd_loss.h; plain form only): the same pass also adds the gradient of the transducer loss on the band,
+//   g[c] = a_b (-(gx + gy) exp(x[c] - lse1) + 1[c == sym] gx + 1[c == blank] gy) + k_b (d kd_node / d x[c]),
+// the first term being the row of band_grad_banded_kernel (mi_band.hip) operation for operation: gx / gy are the band-shaped
+// occupancies of the row itself times a_b = scale.at(b), gx only where s < S.  (That kernel also drops gx at t == t_end of the
+// regular type; a valid node has t < t_end.)  Its other masks cost nothing here: an invalid node has zero occupancies -- the
+// band recursion stores flows only for t_begin <= t < t_end and s_begin <= s <= s_end (band_cell_flows under exactly that
+// test in both kernels of mi_band.hip, the flow store of mi_band_seg.hip likewise, zeros elsewhere) -- so the zero row it
+// gets without a look at its logits is its loss gradient too.  `loss` / `kd`: is the part there at all; a part with a zero
+// multiplier is never read (its planes, and for kd the teacher rows), the rule of TdtMixIn::tdt / rnnt in tdt_logprobs.hip.
+// With one part absent the row is the other kernel's row bit for bit.  Last rows first, as band_grad_banded_kernel and for
+// its reason.
+struct KdLossIn { const float* lse; const float* gxb; const float* gyb; Scale scale; bool loss, kd; };
+
+template <typename ES, typename ET, bool VEC, int FORM, bool COLL, bool LOSS = false, typename... L>
 __global__ void kd_bwd_kernel(const ES* __restrict__ x, const ET* __restrict__ y, const int32_t* __restrict__ symbols,
                               const int32_t* __restrict__ ranges, const int32_t* __restrict__ boundary,
                               const float* __restrict__ weights, int blank, float inv_tau, float dw,
                               const float* __restrict__ saved, const Scale scale, ES* __restrict__ gx, size_t rows, int T,
-                              int S, int W, int N, int r) {
+                              int S, int W, int N, int r, const L... li) {
+  static_assert(sizeof...(L) == (LOSS ? 1 : 0) && (!LOSS || FORM == KD_PLAIN), "one KdLossIn when LOSS (plain form), else nothing");
   constexpr bool HAT = FORM == KD_HAT;
   if (FORM == KD_PLAIN) { weights = nullptr; N = 0; }
   const int lane = threadIdx.x & 63;
-  const size_t row = (size_t)blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
+  size_t row = (size_t)blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
   if (row >= rows) return;
+  if (LOSS) row = rows - 1 - row;
   const int Ct = W - N;
   const KdRow g = kd_row<COLL>(row, symbols, ranges, boundary, weights, blank, T, S, Ct, r);
   ES* gr = gx + row * W;
@@ -441,12 +562,51 @@ __global__ void kd_bwd_kernel(const ES* __restrict__ x, const ET* __restrict__ y
   }
   const ES* xr = x + row * W;
   const ET* yr = y + row * W;
+  bool kd_on = true;                       // LOSS: is there a distillation part at all?
+  float tgx = 0.0f, tgy = 0.0f, ttot = 0.0f, l1 = 0.0f;   // LOSS: the transducer term of this row
+  int sym = -1;
+  bool loss_on = false;
+  if constexpr (LOSS) {
+    const KdLossIn& in = kd_loss_arg(li...);
+    kd_on = in.kd;
+    loss_on = in.loss;
+    if (loss_on) {
+      const float sc = in.scale.at(g.b);
+      if (g.s < S) {
+        sym = symbols[(size_t)g.b * S + g.s];
+        tgx = in.gxb[row] * sc;
+      }
+      tgy = in.gyb[row] * sc;
+      ttot = tgx + tgy;
+      l1 = in.lse[row];
+    }
+  }
+  // one column of the row: v = x[c], a = v / tau, b = y[c] / tau
+  auto column = [&](const KdGrad& d, int c, float v, float a, float b) -> float {
+    if constexpr (!LOSS) return d.template at<FORM, COLL>(c, a, b);
+    else {
+      float val = 0.0f;
+      if (loss_on) {
+        val = -ttot * __expf(v - l1);
+        if (c == sym) val += tgx;
+        if (c == blank) val += tgy;
+      }
+      if (kd_on) {
+        const float kv = d.template at<FORM, COLL>(c, a, b);
+        val = loss_on ? val + kv : kv;
+      }
+      return val;
+    }
+  };
   KdGrad d;
-  d.k = scale.at(g.b) * inv_tau;
-  if (weights) d.k *= g.w;
+  d.k = 0.0f; d.Ls = 0.0f; d.Lt = 0.0f;
+  if (kd_on) {
+    d.k = scale.at(g.b) * inv_tau;
+    if (weights) d.k *= g.w;
+    d.Ls = saved[row];
+    d.Lt = saved[rows + row];
+  }
   d.kk = d.k;
-  d.Ls = saved[row];
-  d.Lt = saved[rows + row];
   d.Rs = 0.0f; d.Ds = 0.0f; d.Dt = 0.0f; d.db = 0.0f; d.ds = 0.0f; d.dr = 0.0f; d.kdur = 0.0f;
   d.k0 = g.k0; d.k1 = g.k1; d.Ct = Ct;
   d.dur_on = FORM == KD_TDT && N > 0 && dw != 0.0f;
@@ -463,7 +623,7 @@ __global__ void kd_bwd_kernel(const ES* __restrict__ x, const ET* __restrict__ y
     d.db = qb - pb;
     d.kk = d.k * pn;
   }
-  if (COLL) {   // the teacher enters through its class masses only: its class logits and Rt, not its row
+  if (COLL && kd_on) {   // the teacher enters through its class masses only: its class logits and Rt, not its row
     d.Rs = saved[2 * rows + row];
     if (!HAT) d.db = __expf(elem_to_float(xr[g.k0]) * inv_tau - d.Ls) - __expf(elem_to_float(yr[g.k0]) * inv_tau - d.Lt);
     if (g.k1 >= 0) d.ds = __expf(elem_to_float(xr[g.k1]) * inv_tau - d.Ls) - __expf(elem_to_float(yr[g.k1]) * inv_tau - d.Lt);
@@ -474,16 +634,17 @@ __global__ void kd_bwd_kernel(const ES* __restrict__ x, const ET* __restrict__ y
     for (int i = lane; i < n4; i += 64) {
       const f4 v = load4(xr, i);
       f4 w = {0.0f, 0.0f, 0.0f, 0.0f};
-      if (!COLL || (d.dur_on && 4 * i + 3 >= Ct)) w = load4(yr, i);   // collapsed: only the quads with a duration column
+      if (kd_on && (!COLL || (d.dur_on && 4 * i + 3 >= Ct))) w = load4(yr, i);   // collapsed: only the quads with a duration column
       f4 o;
 #pragma unroll
-      for (int e = 0; e < 4; ++e) o[e] = d.at<FORM, COLL>(4 * i + e, v[e] * inv_tau, w[e] * inv_tau);
+      for (int e = 0; e < 4; ++e) o[e] = column(d, 4 * i + e, v[e], v[e] * inv_tau, w[e] * inv_tau);
       store4(gr, i, o);
     }
   } else {
     for (int c = lane; c < W; c += 64) {
-      const float b = (!COLL || (d.dur_on && c >= Ct)) ? elem_to_float(yr[c]) * inv_tau : 0.0f;
-      gr[c] = elem_from_float<ES>(d.at<FORM, COLL>(c, elem_to_float(xr[c]) * inv_tau, b));
+      const float b = (kd_on && (!COLL || (d.dur_on && c >= Ct))) ? elem_to_float(yr[c]) * inv_tau : 0.0f;
+      const float v = elem_to_float(xr[c]);
+      gr[c] = elem_from_float<ES>(column(d, c, v, v * inv_tau, b));
     }
   }
 }
@@ -497,17 +658,12 @@ inline auto dispatch_dtype2(int dtype, int teacher_dtype, F&& f) {
 // the row form of a call: one softmax without weights is the plain form; with weights it runs as TDT with n_dur = 0
 inline int kd_form(int hat, int n_dur, const float* weights) { return hat ? KD_HAT : (n_dur > 0 || weights) ? KD_TDT : KD_PLAIN; }
 
-}  // namespace
-
-int pruned_kd_fwd(const void* logits, int dtype, const void* teacher, int teacher_dtype, const int32_t* symbols,
-                  const int32_t* ranges, const int32_t* boundary, int blank, float temperature, int collapsed, int hat,
-                  int n_dur, float dur_weight, const float* weights, float* node, float* saved, float* utt, int B, int T,
-                  int S, int W, int r, hipStream_t st) {
-  const int form = kd_form(hat, n_dur, weights);
-  const char* name = form == KD_PLAIN ? "pruned_kd_fwd" : "pruned_kd_fact_fwd";   // the names the messages have always carried
-  const size_t rows = (size_t)B * T * r;
-  if (rows == 0) return FTR_OK;
-  { const int rc32 = require_rows_32bit(name, rows); if (rc32 != FTR_OK) return rc32; }
+// The forward row kernel of a call.  lo: the loss-carrying instantiation (plain form) with this output, nullptr: the kernel
+// as it is without it.
+int kd_fwd_rows(const char* name, int form, const void* logits, int dtype, const void* teacher, int teacher_dtype,
+                const int32_t* symbols, const int32_t* ranges, const int32_t* boundary, int blank, float temperature,
+                int collapsed, int n_dur, float dur_weight, const float* weights, float* node, float* saved, const KdLossOut* lo,
+                size_t rows, int T, int S, int W, int r, hipStream_t st) {
   const int wpb = 4;
   const unsigned blocks = (unsigned)((rows + wpb - 1) / wpb);
   const float inv_tau = 1.0f / temperature;
@@ -523,31 +679,46 @@ int pruned_kd_fwd(const void* logits, int dtype, const void* teacher, int teache
         constexpr bool COLL = decltype(coll)::value;
         if (vec4 && W <= 2048)   // both rows fit the registers of a wave: 1, 2, 4 or 8 quads of elements per lane and tensor
           dispatch_among<1, 2, 4, 8>(W <= 256 ? 1 : W <= 512 ? 2 : W <= 1024 ? 4 : 8, [&](auto n) {
+            if constexpr (FORM == KD_PLAIN) {
+              if (lo) {
+                hipLaunchKernelGGL((kd_fwd_reg_kernel<ES, ET, decltype(n)::value, FORM, COLL, true, KdLossOut>), dim3(blocks), dim3(64 * wpb),
+                                   0, st, x, y, symbols, ranges, boundary, weights, blank, inv_tau, dur_weight, node, saved, rows, T, S, W,
+                                   n_dur, r, *lo);
+                return;
+              }
+            }
             hipLaunchKernelGGL((kd_fwd_reg_kernel<ES, ET, decltype(n)::value, FORM, COLL>), dim3(blocks), dim3(64 * wpb), 0, st, x, y,
                                symbols, ranges, boundary, weights, blank, inv_tau, dur_weight, node, saved, rows, T, S, W, n_dur, r);
           });
         else
           dispatch(vec4, [&](auto vec) {
+            if constexpr (FORM == KD_PLAIN) {
+              if (lo) {
+                hipLaunchKernelGGL((kd_fwd_kernel<ES, ET, decltype(vec)::value, FORM, COLL, true, KdLossOut>), dim3(blocks), dim3(64 * wpb),
+                                   0, st, x, y, symbols, ranges, boundary, weights, blank, inv_tau, dur_weight, node, saved, rows, T, S, W,
+                                   n_dur, r, *lo);
+                return;
+              }
+            }
             hipLaunchKernelGGL((kd_fwd_kernel<ES, ET, decltype(vec)::value, FORM, COLL>), dim3(blocks), dim3(64 * wpb), 0, st, x, y,
                                symbols, ranges, boundary, weights, blank, inv_tau, dur_weight, node, saved, rows, T, S, W, n_dur, r);
           });
       });
     });
   });
-  { const int rc = check_launch(name); if (rc != FTR_OK) return rc; }
-  hipLaunchKernelGGL(kd_utt_sum_kernel, dim3(B), dim3(256), 0, st, node, utt, T * r);
+  return check_launch(name);
+}
+
+int kd_utt_sum(const float* node, float* utt, int B, int per, hipStream_t st) {
+  hipLaunchKernelGGL(kd_utt_sum_kernel, dim3(B), dim3(256), 0, st, node, utt, per);
   return check_launch("pruned_kd_utt_sum");
 }
 
-int pruned_kd_bwd(const void* logits, int dtype, const void* teacher, int teacher_dtype, const int32_t* symbols,
-                  const int32_t* ranges, const int32_t* boundary, int blank, float temperature, int collapsed, int hat,
-                  int n_dur, float dur_weight, const float* weights, const float* saved, Scale scale, void* glogits, int B,
-                  int T, int S, int W, int r, hipStream_t st) {
-  const int form = kd_form(hat, n_dur, weights);
-  const char* name = form == KD_PLAIN ? "pruned_kd_bwd" : "pruned_kd_fact_bwd";
-  const size_t rows = (size_t)B * T * r;
-  if (rows == 0) return FTR_OK;
-  { const int rc32 = require_rows_32bit(name, rows); if (rc32 != FTR_OK) return rc32; }
+// The backward kernel of a call.  li: the loss-carrying instantiation (plain form), nullptr: the kernel as it is without it.
+int kd_bwd_rows(const char* name, int form, const void* logits, int dtype, const void* teacher, int teacher_dtype,
+                const int32_t* symbols, const int32_t* ranges, const int32_t* boundary, int blank, float temperature,
+                int collapsed, int n_dur, float dur_weight, const float* weights, const float* saved, Scale scale,
+                const KdLossIn* li, void* glogits, size_t rows, int T, int S, int W, int r, hipStream_t st) {
   const int wpb = 4;
   const unsigned blocks = (unsigned)((rows + wpb - 1) / wpb);
   const float inv_tau = 1.0f / temperature;
@@ -559,14 +730,94 @@ int pruned_kd_bwd(const void* logits, int dtype, const void* teacher, int teache
     dispatch(rows_vec4<ES>(W, x, glogits) && rows_vec4<ET>(W, y), [&](auto vec) {
       dispatch_among<KD_PLAIN, KD_HAT, KD_TDT>(form, [&](auto f) {
         dispatch(collapsed != 0, [&](auto coll) {
-          hipLaunchKernelGGL((kd_bwd_kernel<ES, ET, decltype(vec)::value, decltype(f)::value, decltype(coll)::value>), dim3(blocks),
-                             dim3(64 * wpb), 0, st, x, y, symbols, ranges, boundary, weights, blank, inv_tau, dur_weight, saved, scale,
-                             static_cast<ES*>(glogits), rows, T, S, W, n_dur, r);
+          constexpr bool V = decltype(vec)::value, COLL = decltype(coll)::value;
+          constexpr int FORM = decltype(f)::value;
+          if constexpr (FORM == KD_PLAIN) {
+            if (li) {
+              hipLaunchKernelGGL((kd_bwd_kernel<ES, ET, V, FORM, COLL, true, KdLossIn>), dim3(blocks), dim3(64 * wpb), 0, st, x, y, symbols,
+                                 ranges, boundary, weights, blank, inv_tau, dur_weight, saved, scale, static_cast<ES*>(glogits), rows, T, S,
+                                 W, n_dur, r, *li);
+              return;
+            }
+          }
+          hipLaunchKernelGGL((kd_bwd_kernel<ES, ET, V, FORM, COLL>), dim3(blocks), dim3(64 * wpb), 0, st, x, y, symbols, ranges, boundary,
+                             weights, blank, inv_tau, dur_weight, saved, scale, static_cast<ES*>(glogits), rows, T, S, W, n_dur, r);
         });
       });
     });
   });
   return check_launch(name);
+}
+
+}  // namespace
+
+int pruned_kd_fwd(const void* logits, int dtype, const void* teacher, int teacher_dtype, const int32_t* symbols,
+                  const int32_t* ranges, const int32_t* boundary, int blank, float temperature, int collapsed, int hat,
+                  int n_dur, float dur_weight, const float* weights, float* node, float* saved, float* utt, int B, int T,
+                  int S, int W, int r, hipStream_t st) {
+  const int form = kd_form(hat, n_dur, weights);
+  const char* name = form == KD_PLAIN ? "pruned_kd_fwd" : "pruned_kd_fact_fwd";   // the names the messages have always carried
+  const size_t rows = (size_t)B * T * r;
+  if (rows == 0) return FTR_OK;
+  { const int rc32 = require_rows_32bit(name, rows); if (rc32 != FTR_OK) return rc32; }
+  { const int rc = kd_fwd_rows(name, form, logits, dtype, teacher, teacher_dtype, symbols, ranges, boundary, blank, temperature,
+                               collapsed, n_dur, dur_weight, weights, node, saved, nullptr, rows, T, S, W, r, st);
+    if (rc != FTR_OK) return rc; }
+  return kd_utt_sum(node, utt, B, T * r, st);
+}
+
+// include/ftr_kd_loss.h: the row kernel that also writes lse1, the band gather of the transducer loss, the utterance sums.
+// Where the student alone may be read four elements at a time and the teacher may not, the row kernel would sum lse1 in
+// another order than lse_rows does for that student; the logsumexp then runs as lse_rows' own launch, in front of the
+// ordinary row kernel.
+int pruned_band_kd_fwd(const void* logits, int dtype, const void* teacher, int teacher_dtype, const int32_t* symbols,
+                       const int32_t* ranges, const int32_t* boundary, int blank, float temperature, int collapsed,
+                       double delay_penalty, int modified, float* lse, float* pxb, float* pyb, float* node, float* saved, float* utt,
+                       int B, int T, int S, int W, int r, hipStream_t st) {
+  const char* name = "pruned_band_kd_fwd";
+  const size_t rows = (size_t)B * T * r;
+  if (rows == 0) return FTR_OK;
+  { const int rc32 = require_rows_32bit(name, rows); if (rc32 != FTR_OK) return rc32; }
+  const bool svec = dispatch_dtype(dtype, [&](auto tag) { return rows_vec4<typename decltype(tag)::type>(W, logits); });
+  const bool tvec = dispatch_dtype(teacher_dtype, [&](auto tag) { return rows_vec4<typename decltype(tag)::type>(W, teacher); });
+  const KdLossOut lo{lse};
+  const bool fused = !svec || tvec;
+  if (!fused) { const int rc = lse_rows_dtype(logits, dtype, lse, rows, W, blank, 0, st); if (rc != FTR_OK) return rc; }
+  { const int rc = kd_fwd_rows(name, KD_PLAIN, logits, dtype, teacher, teacher_dtype, symbols, ranges, boundary, blank, temperature,
+                               collapsed, 0, 0.0f, nullptr, node, saved, fused ? &lo : nullptr, rows, T, S, W, r, st);
+    if (rc != FTR_OK) return rc; }
+  { const int rc = band_gather(logits, dtype, symbols, ranges, boundary, lse, blank, delay_penalty, pxb, pyb, B, T, S, W, r, modified, 0, st);
+    if (rc != FTR_OK) return rc; }
+  return kd_utt_sum(node, utt, B, T * r, st);
+}
+
+int pruned_kd_bwd(const void* logits, int dtype, const void* teacher, int teacher_dtype, const int32_t* symbols,
+                  const int32_t* ranges, const int32_t* boundary, int blank, float temperature, int collapsed, int hat,
+                  int n_dur, float dur_weight, const float* weights, const float* saved, Scale scale, void* glogits, int B,
+                  int T, int S, int W, int r, hipStream_t st) {
+  const int form = kd_form(hat, n_dur, weights);
+  const char* name = form == KD_PLAIN ? "pruned_kd_bwd" : "pruned_kd_fact_bwd";
+  const size_t rows = (size_t)B * T * r;
+  if (rows == 0) return FTR_OK;
+  { const int rc32 = require_rows_32bit(name, rows); if (rc32 != FTR_OK) return rc32; }
+  return kd_bwd_rows(name, form, logits, dtype, teacher, teacher_dtype, symbols, ranges, boundary, blank, temperature, collapsed,
+                     n_dur, dur_weight, weights, saved, scale, nullptr, glogits, rows, T, S, W, r, st);
+}
+
+// scale: a_b of the transducer term, kd_scale: k_b of the distillation term; a multiplier of zero: that part is not read
+int pruned_band_kd_bwd(const void* logits, int dtype, const void* teacher, int teacher_dtype, const int32_t* symbols,
+                       const int32_t* ranges, const int32_t* boundary, int blank, float temperature, int collapsed,
+                       const float* lse, const float* gxb, const float* gyb, Scale scale, const float* saved, Scale kd_scale,
+                       void* glogits, int B, int T, int S, int W, int r, hipStream_t st) {
+  const char* name = "pruned_band_kd_bwd";
+  const size_t rows = (size_t)B * T * r;
+  if (rows == 0) return FTR_OK;
+  { const int rc32 = require_rows_32bit(name, rows); if (rc32 != FTR_OK) return rc32; }
+  const KdLossIn li{lse, gxb, gyb, scale, scale.mul != 0.0f, kd_scale.mul != 0.0f};
+  // without a distillation part the teacher is not read: its alignment must not cost the student the 4-element path
+  if (!li.kd) { teacher = logits; teacher_dtype = dtype; }
+  return kd_bwd_rows(name, KD_PLAIN, logits, dtype, teacher, teacher_dtype, symbols, ranges, boundary, blank, temperature, collapsed,
+                     0, 0.0f, nullptr, saved, kd_scale, &li, glogits, rows, T, S, W, r, st);
 }
 
 }  // namespace ftr

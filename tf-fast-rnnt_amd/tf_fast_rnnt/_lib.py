@@ -133,6 +133,13 @@ _KD_FACT_SIGNATURES = {
     "ftr_pruned_kd_fact_fwd_dt": (_i, _KD_SIGNATURES["ftr_pruned_kd_fwd_dt"][1][:-1] + [_i, _i, _f, _c_fp, _c_st]),
     "ftr_pruned_kd_fact_bwd_scaled_dt": (_i, _KD_SIGNATURES["ftr_pruned_kd_bwd_scaled_dt"][1][:-1] + [_i, _i, _f, _c_fp, _c_st]),
 }
+# include/ftr_kd_loss.h, the transducer loss on the band and that distillation loss in one pass: the head of the kd entries, then
+# (delay_penalty, modified, lse, px_band, py_band, node_loss, saved, utt_loss, ...) forward and (lse, gx_band, gy_band, the loss's
+# scale triple, saved, the kd scale triple, glogits, ...) backward
+_KD_LOSS_SIGNATURES = {
+    "ftr_pruned_band_kd_fwd_dt": (_i, [_c_fp, _i, _c_fp, _i, _c_ip, _c_ip, _c_ip, _i, _f, _i, ctypes.c_double, _i, _c_fp, _c_fp, _c_fp, _c_fp, _c_fp, _c_fp, _i, _i, _i, _i, _i, _c_st]),
+    "ftr_pruned_band_kd_bwd_scaled_dt": (_i, [_c_fp, _i, _c_fp, _i, _c_ip, _c_ip, _c_ip, _i, _f, _i, _c_fp, _c_fp, _c_fp, _c_fp, _i, _f, _c_fp, _c_fp, _i, _f, _c_fp, _i, _i, _i, _i, _i, _c_st]),
+}
 # include/ftr_fused.h, the fused d am kernel with W as an operand: the arguments of ftr_*_logprobs_fused_bwd_am_f32 with W in place
 # of prod (and no combined scale: W carries it)
 _FUSED_SIGNATURES = {
@@ -188,6 +195,7 @@ PRUNE_SUM_SYMBOLS = tuple(_PRUNE_SUM_SIGNATURES) # those of include/ftr_prune_su
 JOINER_ACT_SYMBOLS = tuple(_JOINER_ACT_SIGNATURES)   # those of include/ftr_joiner_act.h
 KD_SYMBOLS = tuple(_KD_SIGNATURES)               # those of include/ftr_kd.h
 KD_FACT_SYMBOLS = tuple(_KD_FACT_SIGNATURES)     # those of include/ftr_kd_fact.h
+KD_LOSS_SYMBOLS = tuple(_KD_LOSS_SIGNATURES)     # those of include/ftr_kd_loss.h
 FUSED_SYMBOLS = tuple(_FUSED_SIGNATURES)         # those of include/ftr_fused.h
 LIVE_SYMBOLS = tuple(_LIVE_SIGNATURES)           # those of include/ftr_live.h
 BAND_TDT_SYMBOLS = tuple(_BAND_TDT_SIGNATURES)   # those of include/ftr_band_tdt.h
@@ -215,7 +223,7 @@ def lib() -> ctypes.CDLL:
                 f"{LIB_PATH} is missing: build the HIP extension first (python -c 'import __graft_entry__ as g; "
                 "g.build()' or make -C tf-fast-rnnt_amd/csrc).  tf_fast_rnnt has no CPU fallback.")
         handle = ctypes.CDLL(LIB_PATH)
-        for name, (restype, argtypes) in {**_SIGNATURES, **_LOWP_SIGNATURES, **_PRUNE_SUM_SIGNATURES, **_JOINER_ACT_SIGNATURES, **_KD_SIGNATURES, **_KD_FACT_SIGNATURES, **_FUSED_SIGNATURES, **_LIVE_SIGNATURES,
+        for name, (restype, argtypes) in {**_SIGNATURES, **_LOWP_SIGNATURES, **_PRUNE_SUM_SIGNATURES, **_JOINER_ACT_SIGNATURES, **_KD_SIGNATURES, **_KD_FACT_SIGNATURES, **_KD_LOSS_SIGNATURES, **_FUSED_SIGNATURES, **_LIVE_SIGNATURES,
                                             **_BAND_TDT_SIGNATURES, **_TDT_MIX_SIGNATURES, **_BAND_MULTIBLANK_SIGNATURES, **_BAND_VITERBI_SIGNATURES}.items():
             fn = getattr(handle, name)   # AttributeError here = header/library mismatch
             fn.restype = restype

@@ -1082,7 +1082,7 @@ def rnnt_kd_loss_pruned(
 
         loss = rnnt_loss_pruned(logits, ...) + lam * rnnt_kd_loss_pruned(logits, teacher_logits, ...)
 
-    ``logits`` (student) and ``teacher_logits`` are both [B,T,s_range,C], the teacher's joiner evaluated on the student's
+    (``rnnt_loss_pruned_kd`` returns these two values from one pass over the student.)  ``logits`` (student) and ``teacher_logits`` are both [B,T,s_range,C], the teacher's joiner evaluated on the student's
     ``ranges``; each is float32, bfloat16 or float16, independently (a 16-bit tensor means its exact float32 values).
 
     Node (b,t,k) with s = ranges[b,t,k] is valid iff t_begin <= t < t_end and s_begin <= s <= s_end (``boundary[b]`` =
@@ -1255,6 +1255,129 @@ def rnnt_kd_loss_pruned_factored(
         node_weights = node_weights.detach().contiguous()
     return _PrunedKdLoss.apply(logits, teacher_logits, symbols, ranges, int(termination_symbol), boundary, _KD_MODES[mode],
                                temperature, code, _KD_FACTORIZATIONS[factorization], num_durations, duration_weight, node_weights)
+
+
+class _PrunedLossKd(torch.autograd.Function):
+    """rnnt_loss_pruned (band route) and rnnt_kd_loss_pruned as one node (the entries of include/ftr_kd_loss.h): forward =
+    one pass over both tensors (node losses, the saved normalisers and the student's logsumexp) + band gather + the
+    per-utterance sum, then the band recursion and the two reductions, which are the launches of the two ops; backward =
+    one streaming pass that writes the sum of both gradients, each under its own upstream gradient, in the student's dtype."""
+
+    @staticmethod
+    def forward(ctx, logits, teacher_logits, symbols, ranges, termination_symbol, boundary, mode, temperature, modified,
+                delay_penalty, code):
+        B, T, r, C = logits.shape
+        S = symbols.shape[1]
+        x = logits.detach().contiguous()
+        y = teacher_logits.detach().contiguous()
+        dev = x.device
+        band = lambda: torch.empty((B, T, r), dtype=torch.float32, device=dev)
+        lse, pxb, pyb, gxb, gyb, node = band(), band(), band(), band(), band(), band()
+        saved = torch.empty((4 if mode == _lib.FTR_KD_COLLAPSED else 2, B, T, r), dtype=torch.float32, device=dev)
+        utt = torch.empty((B,), dtype=torch.float32, device=dev)
+        ans = torch.empty((B,), dtype=torch.float32, device=dev)
+        kd = utt
+        with torch.cuda.device(dev):
+            st = _stream_ptr(x)
+            _lib.call("ftr_pruned_band_kd_fwd_dt", *_kd_head(x, y), _ptr(symbols), _ptr(ranges), _ptr(boundary),
+                      int(termination_symbol), float(temperature), mode, float(delay_penalty), int(modified), _ptr(lse),
+                      _ptr(pxb), _ptr(pyb), _ptr(node), _ptr(saved), _ptr(utt), B, T, S, C, r, st)
+            nws = _lib.lib().ftr_mutual_information_band_workspace_floats(B, T, S, r)   # 0: the LDS-resident kernel
+            bws = torch.empty((nws,), dtype=torch.float32, device=dev) if nws else None
+            _lib.call("ftr_mutual_information_band_ws_f32", _ptr(pxb), _ptr(pyb), _ptr(ranges), _ptr(boundary), _ptr(bws),
+                      nws, _ptr(ans), _ptr(gxb), _ptr(gyb), B, T, S, r, int(modified), st)
+            del bws
+            if code != 0:
+                kd = torch.empty((), dtype=torch.float32, device=dev)
+                _lib.call("ftr_pruned_kd_reduce_f32", _ptr(utt), B, code, _ptr(kd), st)
+        del pxb, pyb, node
+        if logits.requires_grad:
+            ctx.save_for_backward(x, y, symbols, ranges, lse, gxb, gyb, saved, boundary)
+        ctx.meta = (int(termination_symbol), mode, float(temperature), int(code))
+        ctx.set_materialize_grads(False)      # a part nobody differentiates arrives as None and is not read at all
+        return _negated_reduce_native(ans, code), kd
+
+    @staticmethod
+    def backward(ctx, g_loss, g_kd):
+        x, y, symbols, ranges, lse, gxb, gyb, saved, boundary = ctx.saved_tensors
+        blank, mode, temperature, code = ctx.meta
+        B, T, r, C = x.shape
+        if g_loss is None and g_kd is None:
+            return (None,) * 11
+        # (pointer tensor, stride, multiplier) of each part; an absent part: multiplier 0, nothing of it is read
+        ls, lstride, lmul = _upstream_scale(g_loss, code, B) if g_loss is not None else (None, 0, 0.0)
+        ks, kstride, kmul = _upstream_scale(g_kd, code, B) if g_kd is not None else (None, 0, 0.0)
+        g = torch.empty_like(x)
+        with torch.cuda.device(x.device):
+            _lib.call("ftr_pruned_band_kd_bwd_scaled_dt", *_kd_head(x, y), _ptr(symbols), _ptr(ranges), _ptr(boundary), blank,
+                      temperature, mode, _ptr(lse), _ptr(gxb), _ptr(gyb), _ptr(ls), lstride, lmul, _ptr(saved), _ptr(ks),
+                      kstride, -kmul, _ptr(g), B, T, symbols.shape[1], C, r, _stream_ptr(x))   # -kmul: kd is not a negated score
+        return (g,) + (None,) * 10
+
+
+def rnnt_loss_pruned_kd(
+    logits: torch.Tensor,
+    teacher_logits: torch.Tensor,
+    symbols: torch.Tensor,
+    ranges: torch.Tensor,
+    termination_symbol: int,
+    boundary: Optional[torch.Tensor] = None,
+    mode: str = "full",
+    temperature: float = 1.0,
+    rnnt_type: str = "regular",
+    delay_penalty: float = 0.0,
+    reduction: Optional[str] = "mean",
+) -> Tuple[torch.Tensor, torch.Tensor]:
+    """The transducer loss and the distillation loss of one student tensor in one pass (MI355X addition, no reference
+    counterpart)::
+
+        loss, kd = rnnt_loss_pruned_kd(logits, teacher_logits, symbols, ranges, blank, boundary)
+        (loss + lam * kd).backward()
+
+    ``loss`` is what ``rnnt_loss_pruned(logits, symbols, ranges, termination_symbol, boundary, rnnt_type, delay_penalty,
+    reduction)`` returns and ``kd`` what ``rnnt_kd_loss_pruned(logits, teacher_logits, symbols, ranges, termination_symbol,
+    boundary, mode, temperature, reduction)`` returns -- both float32, both under the one ``reduction``, both bit for bit
+    -- and the argument checks, dtype rules (student and teacher float32 / bfloat16 / float16, independently; a 16-bit
+    tensor means its exact float32 values) and error texts are those of the two functions.  Two outputs, not a weighted
+    sum: the caller forms ``loss + lam * kd`` and logs both.
+
+    What one pass saves: the student's row logsumexp is formed once, from the registers that hold the row for the KL (the
+    composition forms it twice), and the backward writes ONE gradient tensor in the dtype of ``logits``, each part under
+    its own upstream gradient, where the composition writes two and autograd adds them into a third.  The row is computed
+    in float32 and rounded once, so it is not the composition's gradient bit for bit (that one rounds each part, then the
+    sum).  A part that receives no gradient (``kd.backward()`` alone, ``loss.backward()`` alone) is not read at all --
+    neither its occupancies or normalisers nor, for the distillation part, the teacher -- and the row is then that of the
+    single op.  The teacher never gets a gradient.
+
+    One difference in what is read: ``rnnt_kd_loss_pruned`` never reads the rows of an invalid node.  Here the STUDENT
+    rows of the frames t_begin <= t < t_end whose s lies outside [s_begin, s_end] are read for the transducer loss, as
+    ``rnnt_loss_pruned`` reads them (the band recursion conditions its arithmetic on the mean of all band entries of
+    those frames); rows of other frames, and every teacher row of an invalid node, stay unread.  Invalid nodes get exact
+    zeros in the gradient, whatever their rows hold.
+
+    The fused kernels serve the band route of ``rnnt_loss_pruned``: ranges that are a band with s_range <= 15 (what
+    ``get_rnnt_prune_ranges`` returns), ``rnnt_type`` "regular" or "modified", FTR_PRUNED_ROUTE not "lattice".  In every
+    other case -- ranges that are no band, s_range >= 16, "constrained", ranges of unknown content under stream capture --
+    the two existing functions are called and their two values returned unchanged.  Measured against that composition
+    (profiles/kd_loss_bench_c3_c4_c5.jsonl)."""
+    _check_type(rnnt_type)
+    args = (logits, symbols, ranges, termination_symbol, boundary)
+    fused = rnnt_type != "constrained" and isinstance(logits, torch.Tensor) and isinstance(teacher_logits, torch.Tensor) \
+        and logits.dtype in _KD_DTYPES and teacher_logits.dtype in _KD_DTYPES and logits.dim() == 4 \
+        and tuple(teacher_logits.shape) == tuple(logits.shape) and logits.is_cuda and teacher_logits.is_cuda \
+        and teacher_logits.device == logits.device and mode in _KD_MODES and reduction in _REDUCTIONS \
+        and 0.0 < float(temperature) < float("inf") and 0 <= int(termination_symbol) < logits.shape[3]
+    if fused:   # everything the two functions would refuse is refused by them below, in their words
+        symbols_i, ranges_i, boundary_i = _pruned_inputs(logits, symbols, ranges, boundary, lowp=True)
+        B, T, r, C = logits.shape
+        if _band_path_ok(ranges_i, boundary_i, T, symbols_i.shape[1], r):
+            return _PrunedLossKd.apply(logits, teacher_logits, symbols_i, ranges_i, int(termination_symbol), boundary_i,
+                                       _KD_MODES[mode], float(temperature), rnnt_type != "regular", _penalty(delay_penalty),
+                                       _REDUCTIONS[reduction])
+        args = (logits, symbols_i, ranges_i, termination_symbol, boundary_i)   # the verdict on the ranges travels with them
+    loss = rnnt_loss_pruned(*args, rnnt_type=rnnt_type, delay_penalty=delay_penalty, reduction=reduction)
+    kd = rnnt_kd_loss_pruned(args[0], teacher_logits, *args[1:], mode=mode, temperature=temperature, reduction=reduction)
+    return loss, kd
 
 
 # ---- multi-blank transducer (MI355X addition, no reference counterpart): big blanks that advance several frames
