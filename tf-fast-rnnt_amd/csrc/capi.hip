@@ -1,4 +1,4 @@
-// csrc/capi.hip -- the extern "C" surface declared in include/ftr.h, include/ftr_lowp.h, include/ftr_prune_sum.h, include/ftr_joiner_act.h, include/ftr_kd.h, include/ftr_kd_fact.h, include/ftr_kd_loss.h, include/ftr_fused.h and include/ftr_live.h: argument validation and error reporting.  No
+// csrc/capi.hip -- the extern "C" surface declared in include/ftr.h, include/ftr_lowp.h, include/ftr_prune_sum.h, include/ftr_joiner_act.h, include/ftr_kd.h, include/ftr_kd_fact.h, include/ftr_kd_loss.h, include/ftr_kd_topk.h, include/ftr_fused.h and include/ftr_live.h: argument validation and error reporting.  No
 // allocation, no host synchronisation, no CPU fallback.  Built twice: into libftr_hip.so (the product: the symbols of
 // ftr.h and ftr_lowp.h and nothing else) and, with -DFTR_DIAG, into the test-only _build/libftr_hip_diag.so, which adds the symbols of
 // include/ftr_diag.h: the "plain" kernel family (the reference's arithmetic on the device, mi_plain.hip), its
@@ -1548,6 +1548,52 @@ int ftr_pruned_band_kd_bwd_scaled_dt(const void* logits, int kind, const void* t
   return pruned_band_kd_bwd(logits, kind, teacher_logits, teacher_kind, symbols, ranges, boundary, termination_symbol, temperature,
                             mode == FTR_KD_COLLAPSED, lse, gx_band, gy_band, Scale{loss_scale, loss_scale_stride, loss_scale_mul}, saved,
                             Scale{kd_scale, kd_scale_stride, kd_scale_mul}, glogits, B, T, S, C, r, stream_of(stream));
+}
+
+// ---- include/ftr_kd_topk.h: distillation from a stored top-K teacher on the teacher's own band (csrc/pruned_kd_topk.hip)
+// element kinds and temperature, then the sizes: the head of both entries
+static int kd_topk_check_head(const char* what, int kind, int teacher_kind, float temperature, const int32_t* teacher_ranges,
+                              int B, int T, int S, int C, int r, int r_t, int K) {
+  FTR_TRY(check_dtype(what, kind, 0));
+  FTR_TRY(check_dtype(what, teacher_kind, 0));
+  FTR_REQUIRE(temperature > 0.0f && temperature <= 3.0e38f, "%s: temperature %g is not a finite number > 0", what, (double)temperature);
+  FTR_TRY(check_sizes(what, B >= 0 && T >= 1 && S >= 0 && C >= 1 && r >= 1 && r_t >= 1));
+  FTR_REQUIRE(K >= 1 && K <= FTR_KD_TOPK_MAX_K, "%s: K = %d not in [1,%d]", what, K, FTR_KD_TOPK_MAX_K);
+  FTR_REQUIRE(teacher_ranges || r_t == r, "%s: r_t = %d, but without teacher_ranges the cache lies on the student's ranges of r = %d rows",
+              what, r_t, r);
+  return FTR_OK;
+}
+
+int ftr_pruned_kd_topk_fwd_dt(const void* logits, int kind, const void* teacher_values, int teacher_kind,
+                              const int32_t* teacher_indices, const int32_t* ranges, const int32_t* teacher_ranges,
+                              const int32_t* boundary, const float* teacher_rest, const float* node_weights,
+                              float temperature, float* node_loss, float* saved, float* utt_loss, int B, int T, int S,
+                              int C, int r, int r_t, int K, void* stream) {
+  const char* what = "pruned_kd_topk_fwd_dt";
+  clear_error();
+  FTR_TRY(kd_topk_check_head(what, kind, teacher_kind, temperature, teacher_ranges, B, T, S, C, r, r_t, K));
+  if (B == 0) return FTR_OK;
+  FTR_TRY(pointers_then_device(what, logits && teacher_values && teacher_indices && ranges && node_loss && saved && utt_loss));
+  return pruned_kd_topk_fwd(logits, kind, teacher_values, teacher_kind, teacher_indices, ranges, teacher_ranges, boundary,
+                            teacher_rest, node_weights, temperature, node_loss, saved, utt_loss, B, T, S, C, r, r_t, K,
+                            stream_of(stream));
+}
+
+int ftr_pruned_kd_topk_bwd_scaled_dt(const void* logits, int kind, const void* teacher_values, int teacher_kind,
+                                     const int32_t* teacher_indices, const int32_t* ranges, const int32_t* teacher_ranges,
+                                     const int32_t* boundary, const float* teacher_rest, const float* node_weights,
+                                     float temperature, const float* saved, const float* scale, int scale_stride,
+                                     float scale_mul, void* glogits, int B, int T, int S, int C, int r, int r_t, int K,
+                                     void* stream) {
+  const char* what = "pruned_kd_topk_bwd_scaled_dt";
+  clear_error();
+  FTR_TRY(kd_topk_check_head(what, kind, teacher_kind, temperature, teacher_ranges, B, T, S, C, r, r_t, K));
+  FTR_TRY(check_scale_stride(what, scale_stride));
+  if (B == 0) return FTR_OK;
+  FTR_TRY(pointers_then_device(what, logits && teacher_values && teacher_indices && ranges && saved && glogits));
+  return pruned_kd_topk_bwd(logits, kind, teacher_values, teacher_kind, teacher_indices, ranges, teacher_ranges, boundary,
+                            teacher_rest, node_weights, temperature, saved, Scale{scale, scale_stride, scale_mul}, glogits, B, T, S,
+                            C, r, r_t, K, stream_of(stream));
 }
 
 int ftr_selftest(void* scratch_dev, void* stream) {

@@ -6,6 +6,7 @@
 #include <stdarg.h>
 #include "../../include/ftr_kd_fact.h"  // and, through it, ftr_kd.h, ftr_lowp.h and ftr.h
 #include "../../include/ftr_kd_loss.h"
+#include "../../include/ftr_kd_topk.h"
 #include "../../include/ftr_prune_sum.h"
 #include "../../include/ftr_joiner_act.h"
 #include "../../include/ftr_fused.h"
@@ -319,6 +320,10 @@ int pruned_kd_bwd(const void* logits, int dtype, const void* teacher, int teache
 // the same pass carrying the transducer loss on the band (include/ftr_kd_loss.h; plain form): the forward also writes lse and the band operands, the backward adds the band gradient; a Scale with mul == 0: that part is not read
 int pruned_band_kd_fwd(const void* logits, int dtype, const void* teacher, int teacher_dtype, const int32_t* symbols, const int32_t* ranges, const int32_t* boundary, int blank, float temperature, int collapsed, double delay_penalty, int modified, float* lse, float* pxb, float* pyb, float* node, float* saved, float* utt, int B, int T, int S, int W, int r, hipStream_t st);
 int pruned_band_kd_bwd(const void* logits, int dtype, const void* teacher, int teacher_dtype, const int32_t* symbols, const int32_t* ranges, const int32_t* boundary, int blank, float temperature, int collapsed, const float* lse, const float* gxb, const float* gyb, Scale scale, const float* saved, Scale kd_scale, void* glogits, int B, int T, int S, int W, int r, hipStream_t st);
+int kd_utt_sum(const float* node, float* utt, int B, int per, hipStream_t st);   // utt[b] = the sum of utterance b's `per` node losses, a fixed summation tree
+// the same loss from a stored top-K teacher on the teacher's own band: csrc/pruned_kd_topk.hip (include/ftr_kd_topk.h; tranges NULL: the student's ranges; rest, weights: NULL or [B,T,r_t] / [B,T,r]; saved: 3 planes of [B,T,r])
+int pruned_kd_topk_fwd(const void* logits, int dtype, const void* tvalues, int teacher_dtype, const int32_t* tindices, const int32_t* ranges, const int32_t* tranges, const int32_t* boundary, const float* rest, const float* weights, float temperature, float* node, float* saved, float* utt, int B, int T, int S, int C, int r, int rt, int K, hipStream_t st);
+int pruned_kd_topk_bwd(const void* logits, int dtype, const void* tvalues, int teacher_dtype, const int32_t* tindices, const int32_t* ranges, const int32_t* tranges, const int32_t* boundary, const float* rest, const float* weights, float temperature, const float* saved, Scale scale, void* glogits, int B, int T, int S, int C, int r, int rt, int K, hipStream_t st);
 int lse_rows(const float* logits, float* lse, size_t rows, int C, int blank, int hat, hipStream_t st);
 int lse_rows_dtype(const void* logits, int dtype, float* lse, size_t rows, int C, int blank, int hat, hipStream_t st);
 int mi_band_supported(int T, int S, int r);

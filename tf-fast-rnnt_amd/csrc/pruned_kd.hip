@@ -709,11 +709,6 @@ int kd_fwd_rows(const char* name, int form, const void* logits, int dtype, const
   return check_launch(name);
 }
 
-int kd_utt_sum(const float* node, float* utt, int B, int per, hipStream_t st) {
-  hipLaunchKernelGGL(kd_utt_sum_kernel, dim3(B), dim3(256), 0, st, node, utt, per);
-  return check_launch("pruned_kd_utt_sum");
-}
-
 // The backward kernel of a call.  li: the loss-carrying instantiation (plain form), nullptr: the kernel as it is without it.
 int kd_bwd_rows(const char* name, int form, const void* logits, int dtype, const void* teacher, int teacher_dtype,
                 const int32_t* symbols, const int32_t* ranges, const int32_t* boundary, int blank, float temperature,
@@ -750,6 +745,12 @@ int kd_bwd_rows(const char* name, int form, const void* logits, int dtype, const
 }
 
 }  // namespace
+
+// shared with csrc/pruned_kd_topk.hip
+int kd_utt_sum(const float* node, float* utt, int B, int per, hipStream_t st) {
+  hipLaunchKernelGGL(kd_utt_sum_kernel, dim3(B), dim3(256), 0, st, node, utt, per);
+  return check_launch("pruned_kd_utt_sum");
+}
 
 int pruned_kd_fwd(const void* logits, int dtype, const void* teacher, int teacher_dtype, const int32_t* symbols,
                   const int32_t* ranges, const int32_t* boundary, int blank, float temperature, int collapsed, int hat,

@@ -140,6 +140,13 @@ _KD_LOSS_SIGNATURES = {
     "ftr_pruned_band_kd_fwd_dt": (_i, [_c_fp, _i, _c_fp, _i, _c_ip, _c_ip, _c_ip, _i, _f, _i, ctypes.c_double, _i, _c_fp, _c_fp, _c_fp, _c_fp, _c_fp, _c_fp, _i, _i, _i, _i, _i, _c_st]),
     "ftr_pruned_band_kd_bwd_scaled_dt": (_i, [_c_fp, _i, _c_fp, _i, _c_ip, _c_ip, _c_ip, _i, _f, _i, _c_fp, _c_fp, _c_fp, _c_fp, _i, _f, _c_fp, _c_fp, _i, _f, _c_fp, _i, _i, _i, _i, _i, _c_st]),
 }
+# include/ftr_kd_topk.h, that distillation loss from a stored top-K teacher on the teacher's own band: (logits, kind, teacher_values,
+# teacher_kind, teacher_indices, ranges, teacher_ranges, boundary, teacher_rest, node_weights, temperature, ...) and (..., B, T, S, C,
+# r, r_t, K, stream)
+_KD_TOPK_SIGNATURES = {
+    "ftr_pruned_kd_topk_fwd_dt": (_i, [_c_fp, _i, _c_fp, _i, _c_ip, _c_ip, _c_ip, _c_ip, _c_fp, _c_fp, _f, _c_fp, _c_fp, _c_fp, _i, _i, _i, _i, _i, _i, _i, _c_st]),
+    "ftr_pruned_kd_topk_bwd_scaled_dt": (_i, [_c_fp, _i, _c_fp, _i, _c_ip, _c_ip, _c_ip, _c_ip, _c_fp, _c_fp, _f, _c_fp, _c_fp, _i, _f, _c_fp, _i, _i, _i, _i, _i, _i, _i, _c_st]),
+}
 # include/ftr_fused.h, the fused d am kernel with W as an operand: the arguments of ftr_*_logprobs_fused_bwd_am_f32 with W in place
 # of prod (and no combined scale: W carries it)
 _FUSED_SIGNATURES = {
@@ -196,6 +203,7 @@ JOINER_ACT_SYMBOLS = tuple(_JOINER_ACT_SIGNATURES)   # those of include/ftr_join
 KD_SYMBOLS = tuple(_KD_SIGNATURES)               # those of include/ftr_kd.h
 KD_FACT_SYMBOLS = tuple(_KD_FACT_SIGNATURES)     # those of include/ftr_kd_fact.h
 KD_LOSS_SYMBOLS = tuple(_KD_LOSS_SIGNATURES)     # those of include/ftr_kd_loss.h
+KD_TOPK_SYMBOLS = tuple(_KD_TOPK_SIGNATURES)     # those of include/ftr_kd_topk.h
 FUSED_SYMBOLS = tuple(_FUSED_SIGNATURES)         # those of include/ftr_fused.h
 LIVE_SYMBOLS = tuple(_LIVE_SIGNATURES)           # those of include/ftr_live.h
 BAND_TDT_SYMBOLS = tuple(_BAND_TDT_SIGNATURES)   # those of include/ftr_band_tdt.h
@@ -207,6 +215,7 @@ band_multiblank_recursions = 0   # ... and the band-native multi-blank recursion
 FTR_KD_FULL, FTR_KD_COLLAPSED = 0, 1             # include/ftr_kd.h: the `mode` of the kd entry points
 FTR_KD_FACT_SOFTMAX, FTR_KD_FACT_HAT, FTR_KD_FACT_TDT = 0, 1, 2   # include/ftr_kd_fact.h: the `factorization` of its entry points
 FTR_KD_FACT_MAX_DUR = 5
+FTR_KD_TOPK_MAX_K = 64                           # include/ftr_kd_topk.h: the most stored columns per teacher row
 FTR_MI_WS_CLEAN = 1   # include/ftr.h
 FTR_DTYPE_F32, FTR_DTYPE_BF16, FTR_DTYPE_FP16 = 0, 1, 2   # include/ftr_lowp.h: the `kind` of the _dt entry points
 FTR_ACT_TANH, FTR_ACT_RELU = 1, 2                          # include/ftr_joiner_act.h: the `act` of its entry points
@@ -223,7 +232,7 @@ def lib() -> ctypes.CDLL:
                 f"{LIB_PATH} is missing: build the HIP extension first (python -c 'import __graft_entry__ as g; "
                 "g.build()' or make -C tf-fast-rnnt_amd/csrc).  tf_fast_rnnt has no CPU fallback.")
         handle = ctypes.CDLL(LIB_PATH)
-        for name, (restype, argtypes) in {**_SIGNATURES, **_LOWP_SIGNATURES, **_PRUNE_SUM_SIGNATURES, **_JOINER_ACT_SIGNATURES, **_KD_SIGNATURES, **_KD_FACT_SIGNATURES, **_KD_LOSS_SIGNATURES, **_FUSED_SIGNATURES, **_LIVE_SIGNATURES,
+        for name, (restype, argtypes) in {**_SIGNATURES, **_LOWP_SIGNATURES, **_PRUNE_SUM_SIGNATURES, **_JOINER_ACT_SIGNATURES, **_KD_SIGNATURES, **_KD_FACT_SIGNATURES, **_KD_LOSS_SIGNATURES, **_KD_TOPK_SIGNATURES, **_FUSED_SIGNATURES, **_LIVE_SIGNATURES,
                                             **_BAND_TDT_SIGNATURES, **_TDT_MIX_SIGNATURES, **_BAND_MULTIBLANK_SIGNATURES, **_BAND_VITERBI_SIGNATURES}.items():
             fn = getattr(handle, name)   # AttributeError here = header/library mismatch
             fn.restype = restype

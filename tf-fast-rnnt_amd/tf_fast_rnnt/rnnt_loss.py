@@ -16,7 +16,9 @@ What runs where:
   reference counterpart): the same kernels and routes with the HAT normalisation of the joiner output.
 * ``rnnt_kd_loss_pruned`` (MI355X addition, no reference counterpart): knowledge distillation on the pruned band, two
   stream kernels of its own (include/ftr_kd.h, csrc/pruned_kd.hip); ``rnnt_kd_loss_pruned_factored``: the same for HAT and
-  TDT rows and with node weights (include/ftr_kd_fact.h, the same kernels in their other two row forms).
+  TDT rows and with node weights (include/ftr_kd_fact.h, the same kernels in their other two row forms);
+  ``rnnt_kd_loss_pruned_topk``: the same loss from a stored top-K teacher on the teacher's own ranges (include/ftr_kd_topk.h,
+  csrc/pruned_kd_topk.hip), ``rnnt_kd_topk_teacher`` (plain torch) writes that cache.
 
 Reference bugs that are NOT reproduced: ``rnnt_loss_simple(reduction="mean")``
 raises NameError there (rnnt_loss.py:331) -- here it is the mean; ``boundary=None`` works; the
@@ -1255,6 +1257,178 @@ def rnnt_kd_loss_pruned_factored(
         node_weights = node_weights.detach().contiguous()
     return _PrunedKdLoss.apply(logits, teacher_logits, symbols, ranges, int(termination_symbol), boundary, _KD_MODES[mode],
                                temperature, code, _KD_FACTORIZATIONS[factorization], num_durations, duration_weight, node_weights)
+
+
+_KD_TOPK_S = 2 ** 31 - 1   # the `S` of the ftr_pruned_kd_topk_* entries: the op takes no symbols, the boundary alone bounds s
+
+
+class _PrunedKdTopkLoss(torch.autograd.Function):
+    """rnnt_kd_loss_pruned_topk as one node (the entries of include/ftr_kd_topk.h): forward = one pass over the student and
+    the cache (node losses and the three row normalisers the backward needs) + the per-utterance sum [+ the batch
+    reduction]; backward = one streaming pass that writes d loss / d logits in the student's dtype, the upstream gradient
+    folded in.  Nothing of the teacher cache, nor the node weights, gets a gradient."""
+
+    @staticmethod
+    def forward(ctx, logits, values, indices, ranges, tranges, boundary, rest, weights, temperature, code):
+        B, T, r, C = logits.shape
+        rt, K = values.shape[2], values.shape[3]
+        x = logits.detach().contiguous()
+        node = torch.empty((B, T, r), dtype=torch.float32, device=x.device)
+        saved = torch.empty((3, B, T, r), dtype=torch.float32, device=x.device)
+        utt = torch.empty((B,), dtype=torch.float32, device=x.device)
+        out = utt
+        with torch.cuda.device(x.device):
+            st = _stream_ptr(x)
+            _lib.call("ftr_pruned_kd_topk_fwd_dt", *_kd_head(x, values), _ptr(indices), _ptr(ranges), _ptr(tranges), _ptr(boundary),
+                      _ptr(rest), _ptr(weights), float(temperature), _ptr(node), _ptr(saved), _ptr(utt), B, T, _KD_TOPK_S, C, r,
+                      rt, K, st)
+            if code != 0:
+                out = torch.empty((), dtype=torch.float32, device=x.device)
+                _lib.call("ftr_pruned_kd_reduce_f32", _ptr(utt), B, code, _ptr(out), st)
+        if logits.requires_grad:
+            ctx.save_for_backward(x, values, indices, ranges, saved, tranges, boundary, rest, weights)
+        ctx.meta = (float(temperature), int(code))
+        return out
+
+    @staticmethod
+    def backward(ctx, g_loss):
+        x, values, indices, ranges, saved, tranges, boundary, rest, weights = ctx.saved_tensors
+        temperature, code = ctx.meta
+        B, T, r, C = x.shape
+        scale, stride, mul = _upstream_scale(g_loss, code, B)   # its multiplier negates: this loss is not a negated score
+        g = torch.empty_like(x)
+        with torch.cuda.device(x.device):
+            _lib.call("ftr_pruned_kd_topk_bwd_scaled_dt", *_kd_head(x, values), _ptr(indices), _ptr(ranges), _ptr(tranges),
+                      _ptr(boundary), _ptr(rest), _ptr(weights), temperature, _ptr(saved), _ptr(scale), stride, -mul, _ptr(g), B, T,
+                      _KD_TOPK_S, C, r, values.shape[2], values.shape[3], _stream_ptr(x))
+        return (g,) + (None,) * 9
+
+
+def rnnt_kd_loss_pruned_topk(
+    logits: torch.Tensor,
+    teacher_values: torch.Tensor,
+    teacher_indices: torch.Tensor,
+    ranges: torch.Tensor,
+    boundary: Optional[torch.Tensor] = None,
+    teacher_ranges: Optional[torch.Tensor] = None,
+    teacher_rest: Optional[torch.Tensor] = None,
+    temperature: float = 1.0,
+    node_weights: Optional[torch.Tensor] = None,
+    reduction: Optional[str] = "mean",
+) -> torch.Tensor:
+    """``rnnt_kd_loss_pruned`` (full mode) against a STORED teacher: the top-K logits of every teacher row, their columns and,
+    optionally, the mass of everything else -- a cache written by ``rnnt_kd_topk_teacher`` on the teacher's OWN prune
+    ranges, read where it lies (MI355X addition, no reference counterpart).  No dense teacher tensor is built, and the
+    teacher's joiner is not evaluated on the student's ranges.
+
+    ``logits`` [B,T,s_range,C] is the student on ``ranges`` [B,T,s_range]; float32, bfloat16 or float16.
+    ``teacher_values`` [B,T,r_t,K], 1 <= K <= 64: the raw teacher logits at the stored columns, float32, bfloat16 or
+    float16 independently of the student (a 16-bit tensor means its exact float32 values).  ``teacher_indices``
+    [B,T,r_t,K] int32: those columns, clamped into [0,C); I is the set of a row's indices.  A row with fewer than K
+    entries is padded with value -inf; an index may repeat a real entry's only with value -inf.  ``teacher_ranges``
+    [B,T,r_t] int32: the teacher's band, of which only ``teacher_ranges[b,t,0]`` is read -- the rows of a frame are taken to
+    be consecutive, which is what ``get_rnnt_prune_ranges`` returns; None = the student's ``ranges`` (then r_t must be
+    s_range).  ``teacher_rest`` [B,T,r_t] float32: logsumexp over c not in I of teacher_row[c] / temperature, the
+    unnormalised mass of the columns that were not stored, AT THE TEMPERATURE OF THIS CALL; None (= -inf everywhere) is the
+    renormalised top-K form, the KL against the softmax over the stored columns alone.
+
+    Node (b,t,k) with s = ranges[b,t,k] is distilled iff it is valid as in ``rnnt_kd_loss_pruned`` (``boundary`` None =
+    every frame and every s >= 0: this op takes no symbols and does not know S), its weight is not 0, and
+    k' = s - teacher_ranges[b,t,0] lies in [0, r_t); its teacher row is (b,t,k').  Any other node adds nothing, gets an
+    exact zero gradient row, and neither its student row nor any teacher row is read for it.  With a = student row /
+    temperature, v = values / temperature, R = rest::
+
+        L = logaddexp(logsumexp_k v_k, R);  p_k = exp(v_k - L);  p_R = exp(R - L)
+        q_k = softmax(a)[idx_k];  log q_R = logsumexp_{c not in I} a_c - logsumexp_c a_c
+        node loss = w * (sum_k xlogy(p_k, p_k / q_k) + xlogy(p_R, p_R / q_R))
+
+    -- the KL between the teacher and the student, both coarsened to the K stored columns plus one "rest" class; with
+    K = C it is the loss of ``rnnt_kd_loss_pruned``.  Terms of teacher mass 0 are 0; there is no temperature ** 2 factor; a
+    stored column where the student has -inf gives +inf.  ``node_weights`` (None or float32 [B,T,s_range]): as in
+    ``rnnt_kd_loss_pruned_factored`` -- an exact 0 takes the node out, a NaN poisons its utterance.  ``reduction`` and the
+    loss of an utterance (the sum over its distilled nodes): as in ``rnnt_kd_loss_pruned``.  Float32, bit-identical from run
+    to run, launches only (a step can be captured in a graph).  The gradient goes to ``logits`` only, in its dtype.
+
+    A band that rarely overlaps the teacher's distils nothing, silently.  The number to watch is the per-utterance count of
+    distilled nodes::
+
+        t = torch.arange(T, device=ranges.device)[None, :, None]
+        sb, tb, se, te = (boundary[:, i, None, None] for i in range(4))          # None: 0, 0, S, T
+        valid = (t >= tb) & (t < te) & (ranges >= sb) & (ranges <= se)
+        kp = ranges - teacher_ranges[:, :, :1]
+        distilled = (valid & (kp >= 0) & (kp < teacher_ranges.shape[2])).sum((1, 2))    # [B]
+    """
+    for name, t in (("logits", logits), ("teacher_values", teacher_values)):
+        if t.dtype not in _KD_DTYPES:
+            raise TypeError(f"{name} must be float32, bfloat16 or float16, got {t.dtype}")
+    if teacher_indices.dtype != torch.int32:
+        raise TypeError(f"teacher_indices must be int32, got {teacher_indices.dtype}")
+    for name, t in (("teacher_rest", teacher_rest), ("node_weights", node_weights)):
+        if t is not None and t.dtype != torch.float32:
+            raise TypeError(f"{name} must be float32, got {t.dtype}")
+    if logits.dim() != 4:
+        raise ValueError("logits must be [B,T,s_range,C]")
+    B, T, r, C = logits.shape
+    if teacher_values.dim() != 4 or tuple(teacher_values.shape[:2]) != (B, T) or teacher_values.shape[2] < 1:
+        raise ValueError(f"teacher_values must be [B,T,r_t,K] with B, T = {B}, {T} and r_t >= 1, got {tuple(teacher_values.shape)}")
+    rt, K = teacher_values.shape[2], teacher_values.shape[3]
+    if not 1 <= K <= _lib.FTR_KD_TOPK_MAX_K:
+        raise ValueError(f"K = {K} stored columns per row, must be in [1,{_lib.FTR_KD_TOPK_MAX_K}]")
+    if tuple(teacher_indices.shape) != tuple(teacher_values.shape):
+        raise ValueError(f"teacher_indices must have the shape of teacher_values {tuple(teacher_values.shape)}, got {tuple(teacher_indices.shape)}")
+    if teacher_ranges is None:
+        if rt != r:
+            raise ValueError(f"without teacher_ranges the cache lies on the student's ranges: r_t = {rt} must be s_range = {r}")
+    elif not isinstance(teacher_ranges, torch.Tensor) or tuple(teacher_ranges.shape) != (B, T, rt):
+        raise ValueError(f"teacher_ranges must be a [B,T,r_t] = {(B, T, rt)} tensor")
+    if teacher_rest is not None and tuple(teacher_rest.shape) != (B, T, rt):
+        raise ValueError(f"teacher_rest must be [B,T,r_t] = {(B, T, rt)}, got {tuple(teacher_rest.shape)}")
+    if node_weights is not None and tuple(node_weights.shape) != (B, T, r):
+        raise ValueError(f"node_weights must be [B,T,s_range] = {(B, T, r)}, got {tuple(node_weights.shape)}")
+    temperature = float(temperature)
+    if not (0.0 < temperature < float("inf")):
+        raise ValueError(f"temperature must be a finite number > 0, given {temperature}")
+    code = _reduction_code(reduction)
+    _require_gpu(logits, "logits")
+    ranges = torch.as_tensor(ranges, device=logits.device).to(torch.int32).contiguous()
+    if tuple(ranges.shape) != (B, T, r):
+        raise ValueError(f"ranges must have shape {(B, T, r)}, got {tuple(ranges.shape)}")
+    boundary = _as_boundary(boundary, B, logits.device)
+    others = [("teacher_values", teacher_values), ("teacher_indices", teacher_indices), ("teacher_ranges", teacher_ranges),
+              ("teacher_rest", teacher_rest), ("node_weights", node_weights)]
+    for name, t in others:
+        if t is not None:
+            _require_gpu(t, name)
+            if t.device != logits.device:
+                raise ValueError(f"{name} and logits must be on the same device")
+    values, indices, tranges, rest, weights = (None if t is None else t.detach().contiguous() for _, t in others)
+    if tranges is not None and tranges.dtype != torch.int32:
+        tranges = tranges.to(torch.int32)
+    return _PrunedKdTopkLoss.apply(logits, values, indices, ranges, tranges, boundary, rest, weights, temperature, code)
+
+
+def rnnt_kd_topk_teacher(teacher_logits: torch.Tensor, k: int, temperature: float = 1.0,
+                         with_rest: bool = True) -> Tuple[torch.Tensor, torch.Tensor, Optional[torch.Tensor]]:
+    """The cache ``rnnt_kd_loss_pruned_topk`` reads, from dense teacher logits [..., C] (the teacher's joiner on the teacher's
+    own ranges, [B,T,r_t,C]): ``(values, indices, rest)``.  ``values`` [..., k]: the k largest raw logits of every row, in
+    the dtype of ``teacher_logits``; ``indices`` [..., k] int32: their columns; ``rest`` [...] float32 (None without
+    ``with_rest``): logsumexp of the other columns / ``temperature`` -- -inf when k = C -- which is only right for a loss
+    evaluated at that same temperature.  Plain torch (``topk`` and a masked ``logsumexp``), any device: it runs where the
+    cache is written, not in the training step."""
+    k = int(k)
+    C = teacher_logits.shape[-1]
+    if not 1 <= k <= min(C, _lib.FTR_KD_TOPK_MAX_K):
+        raise ValueError(f"k = {k} must be in [1, min(C, {_lib.FTR_KD_TOPK_MAX_K})] for rows of C = {C}")
+    temperature = float(temperature)
+    if not (0.0 < temperature < float("inf")):
+        raise ValueError(f"temperature must be a finite number > 0, given {temperature}")
+    with torch.no_grad():
+        values, idx = torch.topk(teacher_logits, k, dim=-1)
+        rest = None
+        if with_rest:
+            others = (teacher_logits.to(torch.float32) / temperature).scatter(-1, idx, _NEG_INF)
+            rest = torch.logsumexp(others, dim=-1)
+    return values, idx.to(torch.int32), rest
 
 
 class _PrunedLossKd(torch.autograd.Function):
