@@ -6,6 +6,7 @@
 #include <stdarg.h>
 #include "../../include/ftr_kd_fact.h"  // and, through it, ftr_kd.h, ftr_lowp.h and ftr.h
 #include "../../include/ftr_kd_loss.h"
+#include "../../include/ftr_kd_loss_fact.h"
 #include "../../include/ftr_kd_topk.h"
 #include "../../include/ftr_prune_sum.h"
 #include "../../include/ftr_joiner_act.h"
@@ -318,8 +319,10 @@ int negated_reduce(const float* ans, int B, int reduction, float* out, hipStream
 int pruned_kd_fwd(const void* logits, int dtype, const void* teacher, int teacher_dtype, const int32_t* symbols, const int32_t* ranges, const int32_t* boundary, int blank, float temperature, int collapsed, int hat, int n_dur, float dur_weight, const float* weights, float* node, float* saved, float* utt, int B, int T, int S, int W, int r, hipStream_t st);
 int pruned_kd_bwd(const void* logits, int dtype, const void* teacher, int teacher_dtype, const int32_t* symbols, const int32_t* ranges, const int32_t* boundary, int blank, float temperature, int collapsed, int hat, int n_dur, float dur_weight, const float* weights, const float* saved, Scale scale, void* glogits, int B, int T, int S, int W, int r, hipStream_t st);
 // the same pass carrying the transducer loss on the band (include/ftr_kd_loss.h; plain form): the forward also writes lse and the band operands, the backward adds the band gradient; a Scale with mul == 0: that part is not read
-int pruned_band_kd_fwd(const void* logits, int dtype, const void* teacher, int teacher_dtype, const int32_t* symbols, const int32_t* ranges, const int32_t* boundary, int blank, float temperature, int collapsed, double delay_penalty, int modified, float* lse, float* pxb, float* pyb, float* node, float* saved, float* utt, int B, int T, int S, int W, int r, hipStream_t st);
-int pruned_band_kd_bwd(const void* logits, int dtype, const void* teacher, int teacher_dtype, const int32_t* symbols, const int32_t* ranges, const int32_t* boundary, int blank, float temperature, int collapsed, const float* lse, const float* gxb, const float* gyb, Scale scale, const float* saved, Scale kd_scale, void* glogits, int B, int T, int S, int W, int r, hipStream_t st);
+int pruned_band_kd_fact_fwd(const void* logits, int dtype, const void* teacher, int teacher_dtype, const int32_t* symbols, const int32_t* ranges, const int32_t* boundary, int blank, float temperature, int collapsed, double delay_penalty, int modified, float* lse, float* pxb, float* pyb, float* node, float* saved, float* utt, int B, int T, int S, int W, int r, int hat, const float* weights, hipStream_t st);
+int pruned_band_kd_fact_bwd(const void* logits, int dtype, const void* teacher, int teacher_dtype, const int32_t* symbols, const int32_t* ranges, const int32_t* boundary, int blank, float temperature, int collapsed, const float* lse, const float* gxb, const float* gyb, Scale scale, const float* saved, Scale kd_scale, void* glogits, int B, int T, int S, int W, int r, int hat, const float* weights, hipStream_t st);
+int pruned_kd_weighted_utt_sum(const float* node, const float* weights, float* utt, int B, int per, hipStream_t st);   // utt[b] = sum of w * node in kd_utt_sum's tree
+int band_node_occupancy(const float* gxb, const float* gyb, const int32_t* ranges, const int32_t* boundary, float* occ, int B, int T, int S, int r, hipStream_t st);
 int kd_utt_sum(const float* node, float* utt, int B, int per, hipStream_t st);   // utt[b] = the sum of utterance b's `per` node losses, a fixed summation tree
 // the same loss from a stored top-K teacher on the teacher's own band: csrc/pruned_kd_topk.hip (include/ftr_kd_topk.h; tranges NULL: the student's ranges; rest, weights: NULL or [B,T,r_t] / [B,T,r]; saved: 3 planes of [B,T,r])
 int pruned_kd_topk_fwd(const void* logits, int dtype, const void* tvalues, int teacher_dtype, const int32_t* tindices, const int32_t* ranges, const int32_t* tranges, const int32_t* boundary, const float* rest, const float* weights, float temperature, float* node, float* saved, float* utt, int B, int T, int S, int C, int r, int rt, int K, hipStream_t st);

@@ -21,9 +21,10 @@
 //   kd_utt_sum_kernel  node losses -> per-utterance loss, one block per utterance, fixed summation tree
 //   kd_bwd_kernel      one streaming pass: d loss / d x from x, y and the normalisers the forward saved (no reduction); it
 //                      writes all W columns of the gradient row
-// The three row kernels also have a loss-carrying instantiation of the plain form (LOSS; include/ftr_kd_loss.h): the forward
-// writes the student's temperature-1 logsumexp for the transducer loss on the band as well, the backward adds that loss's
-// gradient row; see KdLossOut and KdLossIn below.
+// The three row kernels also have loss-carrying instantiations (LOSS; include/ftr_kd_loss.h the plain form,
+// include/ftr_kd_loss_fact.h the HAT form and the weighted softmax, which is KD_TDT with N = 0): the forward writes the
+// normaliser of the transducer loss on the band as well, the backward adds that loss's gradient row; see KdLossOut and
+// KdLossIn below.
 // The three forms share the column -> lane mapping and the order of every sum.  The columns that are not part of the main
 // sums (HAT: the blank; TDT: the duration columns; collapsed: the class columns) are masked to -inf in registers, as
 // tdt_lse_kernel of tdt_logprobs.hip masks 4 * i + e >= C.  What is left at the end of a row: HAT, the Bernoulli term from
@@ -52,8 +53,9 @@ __device__ __forceinline__ float wave_sum(float v) { return wave_sum_dpp(v); }
 // what a wave knows about its row before it touches the logits: is the node valid, whose utterance is it, its weight (1
 // without weights), the blank column k0 and (collapsed) the symbol column k1 (-1: the node has no symbol class)
 // (lrow, s: for the loss-carrying instantiations only -- does the band recursion look at this row's px / py at all, i.e. is
-// t inside the frames of the rectangle and s inside the lattice; and the node's lattice row)
-struct KdRow { bool valid, lrow; int b, s, k0, k1; float w; };
+// t inside the frames of the rectangle and s inside the lattice; the node's lattice row; and `geo`, valid but for its
+// weight: a node of weight 0 is out of the distillation only, the transducer loss still owns its gradient row)
+struct KdRow { bool valid, lrow, geo; int b, s, k0, k1; float w; };
 
 template <bool COLL>
 __device__ __forceinline__ KdRow kd_row(size_t row, const int32_t* __restrict__ symbols, const int32_t* __restrict__ ranges,
@@ -67,6 +69,7 @@ __device__ __forceinline__ KdRow kd_row(size_t row, const int32_t* __restrict__ 
   const Bound bd = load_boundary(boundary, g.b, S, T);   // clamped into the lattice: s < se implies s < S below
   g.valid = t >= bd.tb && t < bd.te && s >= bd.sb && s <= bd.se;
   g.lrow = t >= bd.tb && t < bd.te && s >= 0 && s <= S;
+  g.geo = g.valid;
   g.s = s;
   g.w = 1.0f;
   if (weights) {
@@ -235,6 +238,10 @@ __device__ __forceinline__ bool kd_masked(int c, int Ct, int k0, int k1) {
 // (ftr_common.h, Shift) are means over ALL band entries of the frames [t_begin, t_end), the rows past s_end included.  Such a
 // row (KdRow::lrow and not valid) has its student row read for lse1 alone; the teacher's is not.  Outside those frames
 // nothing is read and lse1 = 0: the recursion never looks there.
+// HAT (include/ftr_kd_loss_fact.h): the normaliser is Z, the logsumexp over c != blank, and what is restated is
+// lse_rows_*<., ., HAT = true>: the blank column set to -inf before the maximum and the sum, nothing else changed.  At
+// temperature 1 in full mode that is the very masking of the KD_HAT sums, so the sharing below holds for it as it stands.
+// A node of weight 0 is a row that only the loss needs, like the rows past s_end.
 struct KdLossOut { float* lse; };
 template <typename A> __device__ __forceinline__ const A& kd_loss_arg(const A& a) { return a; }
 
@@ -256,8 +263,16 @@ __device__ __forceinline__ float lse1_lane_sum(const f4 (&v)[NQ], float m, int l
   return sum;
 }
 // a row that only the loss needs, register resident (W % 4 == 0, W <= 256 * NQ)
-template <typename ES, int NQ>
-__device__ __forceinline__ float lse1_reg(const ES* xr, int lane, int n4) {
+template <int NQ>
+__device__ __forceinline__ void lse1_mask_blank(f4 (&v)[NQ], int lane, int blank) {
+#pragma unroll
+  for (int q = 0; q < NQ; ++q) {
+#pragma unroll
+    for (int e = 0; e < 4; ++e) v[q][e] = (4 * (lane + 64 * q) + e == blank) ? -INFINITY : v[q][e];
+  }
+}
+template <typename ES, int NQ, bool HAT = false>
+__device__ __forceinline__ float lse1_reg(const ES* xr, int lane, int n4, int blank = -1) {
   const f4 ninf = {-INFINITY, -INFINITY, -INFINITY, -INFINITY};
   f4 v[NQ];
 #pragma unroll
@@ -265,28 +280,37 @@ __device__ __forceinline__ float lse1_reg(const ES* xr, int lane, int n4) {
     const int i = lane + 64 * q;
     v[q] = (i < n4) ? load4(xr, i) : ninf;
   }
+  if (HAT) lse1_mask_blank<NQ>(v, lane, blank);
   const float m = wave_max(lse1_lane_max<NQ>(v));
   return m + __logf(wave_sum(lse1_lane_sum<NQ>(v, m, lane, n4)));
 }
 // any W, two passes: lse_rows_kernel
-template <typename ES, bool VEC>
-__device__ __forceinline__ float lse1_two_pass(const ES* xr, int lane, int W) {
+template <typename ES, bool VEC, bool HAT = false>
+__device__ __forceinline__ float lse1_two_pass(const ES* xr, int lane, int W, int blank = -1) {
   float m = -INFINITY, s = 0.0f;
   if (VEC) {
     const int n4 = W >> 2;
     for (int i = lane; i < n4; i += 64) {
-      const f4 v = load4(xr, i);
+      f4 v = load4(xr, i);
+      if (HAT) {
+#pragma unroll
+        for (int e = 0; e < 4; ++e) v[e] = (4 * i + e == blank) ? -INFINITY : v[e];
+      }
       m = fmaxf(fmaxf(m, fmaxf(v[0], v[1])), fmaxf(v[2], v[3]));
     }
     m = wave_max(m);
     for (int i = lane; i < n4; i += 64) {
-      const f4 v = load4(xr, i);
+      f4 v = load4(xr, i);
+      if (HAT) {
+#pragma unroll
+        for (int e = 0; e < 4; ++e) v[e] = (4 * i + e == blank) ? -INFINITY : v[e];
+      }
       s += __expf(v[0] - m) + __expf(v[1] - m) + __expf(v[2] - m) + __expf(v[3] - m);
     }
   } else {
-    for (int i = lane; i < W; i += 64) m = fmaxf(m, elem_to_float(xr[i]));
+    for (int i = lane; i < W; i += 64) m = fmaxf(m, (HAT && i == blank) ? -INFINITY : elem_to_float(xr[i]));
     m = wave_max(m);
-    for (int i = lane; i < W; i += 64) s += __expf(elem_to_float(xr[i]) - m);
+    for (int i = lane; i < W; i += 64) s += __expf(((HAT && i == blank) ? -INFINITY : elem_to_float(xr[i])) - m);
   }
   return m + __logf(wave_sum(s));
 }
@@ -298,7 +322,7 @@ __global__ __launch_bounds__(256) void kd_fwd_reg_kernel(const ES* __restrict__ 
                                                          int blank, float inv_tau, float dw, float* __restrict__ node,
                                                          float* __restrict__ saved, size_t rows, int T, int S, int W, int N, int r,
                                                          const L... lo) {
-  static_assert(sizeof...(L) == (LOSS ? 1 : 0) && (!LOSS || FORM == KD_PLAIN), "one KdLossOut when LOSS (plain form), else nothing");
+  static_assert(sizeof...(L) == (LOSS ? 1 : 0), "one KdLossOut when LOSS, else nothing");   // LOSS with KD_TDT: N = 0 only (the hosts)
   constexpr bool HAT = FORM == KD_HAT;
   if (FORM == KD_PLAIN) { weights = nullptr; N = 0; }   // known at compile time: what hangs on them is not in the plain form's code
   const int lane = threadIdx.x & 63;
@@ -312,7 +336,7 @@ __global__ __launch_bounds__(256) void kd_fwd_reg_kernel(const ES* __restrict__ 
   if (!g.valid) {
     if constexpr (LOSS) {   // a row of the rectangle's frames past s_end / before s_begin: the student row, for lse1 alone
       float l1 = 0.0f;
-      if (g.lrow) l1 = lse1_reg<ES, NQ>(xr, lane, n4);
+      if (g.lrow) l1 = lse1_reg<ES, NQ, HAT>(xr, lane, n4, blank);
       if (lane == 0) kd_loss_arg(lo...).lse[row] = l1;
     }
     if (lane == 0) kd_store_invalid<COLL>(node, saved, rows, row, N);
@@ -352,6 +376,7 @@ __global__ __launch_bounds__(256) void kd_fwd_reg_kernel(const ES* __restrict__ 
   float m1 = 0.0f, s1 = 0.0f;
   bool share = false;
   if constexpr (LOSS) {
+    if (HAT) lse1_mask_blank<NQ>(v, lane, blank);   // Z; the column is masked in the sums below anyway
     m1 = wave_max(lse1_lane_max<NQ>(v));
     share = !COLL && inv_tau == 1.0f && m1 > -INFINITY;   // -inf: ms is kd_safe_max's 0, not m1; NaN compares false
     if (!share) s1 = lse1_lane_sum<NQ>(v, m1, lane, n4);
@@ -406,7 +431,7 @@ __global__ void kd_fwd_kernel(const ES* __restrict__ x, const ET* __restrict__ y
                               const int32_t* __restrict__ ranges, const int32_t* __restrict__ boundary,
                               const float* __restrict__ weights, int blank, float inv_tau, float dw, float* __restrict__ node,
                               float* __restrict__ saved, size_t rows, int T, int S, int W, int N, int r, const L... lo) {
-  static_assert(sizeof...(L) == (LOSS ? 1 : 0) && (!LOSS || FORM == KD_PLAIN), "one KdLossOut when LOSS (plain form), else nothing");
+  static_assert(sizeof...(L) == (LOSS ? 1 : 0), "one KdLossOut when LOSS, else nothing");   // LOSS with KD_TDT: N = 0 only (the hosts)
   constexpr bool HAT = FORM == KD_HAT;
   if (FORM == KD_PLAIN) { weights = nullptr; N = 0; }
   const int lane = threadIdx.x & 63;
@@ -417,7 +442,7 @@ __global__ void kd_fwd_kernel(const ES* __restrict__ x, const ET* __restrict__ y
   const ES* xr = x + row * W;
   if constexpr (LOSS) {   // lse1 by two passes of its own, in lse_rows_kernel's order: this kernel is the slow path, and the row stays in L1
     float l1 = 0.0f;
-    if (g.lrow) l1 = lse1_two_pass<ES, VEC>(xr, lane, W);
+    if (g.lrow) l1 = lse1_two_pass<ES, VEC, HAT>(xr, lane, W, blank);
     if (lane == 0) kd_loss_arg(lo...).lse[row] = l1;
   }
   if (!g.valid) {
@@ -501,6 +526,46 @@ __global__ __launch_bounds__(256) void kd_utt_sum_kernel(const float* __restrict
   if (threadIdx.x == 0) utt[blockIdx.x] = (red[0] + red[1]) + (red[2] + red[3]);
 }
 
+// the same tree over w * node (include/ftr_kd_loss_fact.h): what kd_utt_sum_kernel adds up when the row kernel itself
+// multiplied by w as its last step.  w == 0: the node is out, whatever its loss (an infinite one included)
+__global__ __launch_bounds__(256) void kd_utt_sum_weighted_kernel(const float* __restrict__ node, const float* __restrict__ wts,
+                                                                  float* __restrict__ utt, int per) {
+  __shared__ float red[4];
+  const float* p = node + (size_t)blockIdx.x * per;
+  const float* w = wts + (size_t)blockIdx.x * per;
+  float s = 0.0f;
+  for (int i = threadIdx.x; i < per; i += 256) {
+    const float wi = w[i];
+    s += wi == 0.0f ? 0.0f : p[i] * wi;
+  }
+  s = wave_sum(s);
+  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s;
+  __syncthreads();
+  if (threadIdx.x == 0) utt[blockIdx.x] = (red[0] + red[1]) + (red[2] + red[3]);
+}
+
+// occ[b,t,k] = gx + gy, the occupancies of the two arcs that leave lattice node (ranges[b,t,k], t), under the masks of
+// band_grad_banded_kernel (mi_band.hip): gx only where s < S (its other mask, t == t_end of the regular type, lies outside
+// the rectangle).  Exact zeros for a node outside the boundary rectangle or outside the lattice, whatever the two arrays
+// hold there.  One thread per node.
+__global__ void band_node_occupancy_kernel(const float* __restrict__ gxb, const float* __restrict__ gyb,
+                                           const int32_t* __restrict__ ranges, const int32_t* __restrict__ boundary,
+                                           float* __restrict__ occ, size_t rows, int T, int S, int r) {
+  const size_t row = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (row >= rows) return;
+  const size_t bt = row / r;
+  const int b = (int)(bt / T);
+  const int t = (int)(bt - (size_t)b * T);
+  const int s = ranges[row];
+  const Bound bd = load_boundary(boundary, b, S, T);
+  float v = 0.0f;
+  if (t >= bd.tb && t < bd.te && s >= bd.sb && s <= bd.se) {
+    const float gx = s < S ? gxb[row] : 0.0f;
+    v = gx + gyb[row];
+  }
+  occ[row] = v;
+}
+
 // d loss / d x[c] of one element, a = x[c] / tau, b = y[c] / tau.  k = upstream gradient * weight / tau.
 //   main softmax, full:       kk (q_c - p_c)
 //                 collapsed:  kk (Q_j - P_j) w_c for c in class j, Q / P the student's / teacher's class masses and w_c the
@@ -533,6 +598,10 @@ struct KdGrad {
 // multiplier is never read (its planes, and for kd the teacher rows), the rule of TdtMixIn::tdt / rnnt in tdt_logprobs.hip.
 // With one part absent the row is the other kernel's row bit for bit.  Last rows first, as band_grad_banded_kernel and for
 // its reason.
+// The other forms (include/ftr_kd_loss_fact.h).  KD_HAT: the first term is the row of band_grad_banded_kernel<., ., HAT>,
+//   gx (1[c == sym] - exp(x[c] - Z)) for c != blank, gy sigmoid(-x[blank]) - gx sigmoid(x[blank]) at the blank, gx = 0 where
+// the symbol is the blank.  Node weights (KD_HAT, or KD_TDT with N = 0): a weight of 0 drops the distillation part of the
+// row -- its planes and the teacher's row are not read -- and leaves the transducer part, which the weights never touch.
 struct KdLossIn { const float* lse; const float* gxb; const float* gyb; Scale scale; bool loss, kd; };
 
 template <typename ES, typename ET, bool VEC, int FORM, bool COLL, bool LOSS = false, typename... L>
@@ -541,7 +610,7 @@ __global__ void kd_bwd_kernel(const ES* __restrict__ x, const ET* __restrict__ y
                               const float* __restrict__ weights, int blank, float inv_tau, float dw,
                               const float* __restrict__ saved, const Scale scale, ES* __restrict__ gx, size_t rows, int T,
                               int S, int W, int N, int r, const L... li) {
-  static_assert(sizeof...(L) == (LOSS ? 1 : 0) && (!LOSS || FORM == KD_PLAIN), "one KdLossIn when LOSS (plain form), else nothing");
+  static_assert(sizeof...(L) == (LOSS ? 1 : 0), "one KdLossIn when LOSS, else nothing");   // LOSS with KD_TDT: N = 0 only (the hosts)
   constexpr bool HAT = FORM == KD_HAT;
   if (FORM == KD_PLAIN) { weights = nullptr; N = 0; }
   const int lane = threadIdx.x & 63;
@@ -551,7 +620,12 @@ __global__ void kd_bwd_kernel(const ES* __restrict__ x, const ET* __restrict__ y
   const int Ct = W - N;
   const KdRow g = kd_row<COLL>(row, symbols, ranges, boundary, weights, blank, T, S, Ct, r);
   ES* gr = gx + row * W;
-  if (!g.valid) {   // zeros, without a look at the logits
+  bool zero_row = !g.valid;
+  if constexpr (LOSS && FORM != KD_PLAIN) {   // a weight of 0 takes the node out of the distillation part only
+    const KdLossIn& in = kd_loss_arg(li...);
+    zero_row = !g.geo || !(in.loss || (in.kd && g.valid));
+  }
+  if (zero_row) {   // zeros, without a look at the logits
     if (VEC) {
       const f4 zero = {0.0f, 0.0f, 0.0f, 0.0f};
       for (int i = lane; i < (W >> 2); i += 64) store4(gr, i, zero);
@@ -569,15 +643,20 @@ __global__ void kd_bwd_kernel(const ES* __restrict__ x, const ET* __restrict__ y
   if constexpr (LOSS) {
     const KdLossIn& in = kd_loss_arg(li...);
     kd_on = in.kd;
+    if constexpr (FORM != KD_PLAIN) kd_on = kd_on && g.valid;
     loss_on = in.loss;
     if (loss_on) {
       const float sc = in.scale.at(g.b);
       if (g.s < S) {
         sym = symbols[(size_t)g.b * S + g.s];
         tgx = in.gxb[row] * sc;
+        if (HAT) {   // band_grad_banded_kernel<., ., HAT>: the column the forward read; px is -inf where it is the blank
+          sym = min(max(sym, 0), W - 1);
+          if (sym == blank) tgx = 0.0f;
+        }
       }
       tgy = in.gyb[row] * sc;
-      ttot = tgx + tgy;
+      ttot = HAT ? tgx : tgx + tgy;
       l1 = in.lse[row];
     }
   }
@@ -589,7 +668,15 @@ __global__ void kd_bwd_kernel(const ES* __restrict__ x, const ET* __restrict__ y
       if (loss_on) {
         val = -ttot * __expf(v - l1);
         if (c == sym) val += tgx;
-        if (c == blank) val += tgy;
+        if (c == blank) {
+          if (HAT) {   // gy sigmoid(-x_b) - gx sigmoid(x_b), by the lane that holds the blank column
+            float sp, sn;
+            hat_sigmoids(v, &sp, &sn);
+            val = tgy * sn - tgx * sp;
+          } else {
+            val += tgy;
+          }
+        }
       }
       if (kd_on) {
         const float kv = d.template at<FORM, COLL>(c, a, b);
@@ -616,7 +703,7 @@ __global__ void kd_bwd_kernel(const ES* __restrict__ x, const ET* __restrict__ y
     d.Dt = saved[(size_t)(p0 + 1) * rows + row];
     d.kdur = d.k * dw;
   }
-  if (HAT) {
+  if (HAT && kd_on) {
     float qb, qn, pb, pn;
     hat_sigmoids(elem_to_float(xr[g.k0]) * inv_tau, &qb, &qn);
     hat_sigmoids(elem_to_float(yr[g.k0]) * inv_tau, &pb, &pn);
@@ -658,8 +745,8 @@ inline auto dispatch_dtype2(int dtype, int teacher_dtype, F&& f) {
 // the row form of a call: one softmax without weights is the plain form; with weights it runs as TDT with n_dur = 0
 inline int kd_form(int hat, int n_dur, const float* weights) { return hat ? KD_HAT : (n_dur > 0 || weights) ? KD_TDT : KD_PLAIN; }
 
-// The forward row kernel of a call.  lo: the loss-carrying instantiation (plain form) with this output, nullptr: the kernel
-// as it is without it.
+// The forward row kernel of a call.  lo: the loss-carrying instantiation with this output (n_dur must be 0), nullptr: the
+// kernel as it is without it.
 int kd_fwd_rows(const char* name, int form, const void* logits, int dtype, const void* teacher, int teacher_dtype,
                 const int32_t* symbols, const int32_t* ranges, const int32_t* boundary, int blank, float temperature,
                 int collapsed, int n_dur, float dur_weight, const float* weights, float* node, float* saved, const KdLossOut* lo,
@@ -679,26 +766,22 @@ int kd_fwd_rows(const char* name, int form, const void* logits, int dtype, const
         constexpr bool COLL = decltype(coll)::value;
         if (vec4 && W <= 2048)   // both rows fit the registers of a wave: 1, 2, 4 or 8 quads of elements per lane and tensor
           dispatch_among<1, 2, 4, 8>(W <= 256 ? 1 : W <= 512 ? 2 : W <= 1024 ? 4 : 8, [&](auto n) {
-            if constexpr (FORM == KD_PLAIN) {
-              if (lo) {
-                hipLaunchKernelGGL((kd_fwd_reg_kernel<ES, ET, decltype(n)::value, FORM, COLL, true, KdLossOut>), dim3(blocks), dim3(64 * wpb),
-                                   0, st, x, y, symbols, ranges, boundary, weights, blank, inv_tau, dur_weight, node, saved, rows, T, S, W,
-                                   n_dur, r, *lo);
-                return;
-              }
+            if (lo) {
+              hipLaunchKernelGGL((kd_fwd_reg_kernel<ES, ET, decltype(n)::value, FORM, COLL, true, KdLossOut>), dim3(blocks), dim3(64 * wpb),
+                                 0, st, x, y, symbols, ranges, boundary, weights, blank, inv_tau, dur_weight, node, saved, rows, T, S, W,
+                                 n_dur, r, *lo);
+              return;
             }
             hipLaunchKernelGGL((kd_fwd_reg_kernel<ES, ET, decltype(n)::value, FORM, COLL>), dim3(blocks), dim3(64 * wpb), 0, st, x, y,
                                symbols, ranges, boundary, weights, blank, inv_tau, dur_weight, node, saved, rows, T, S, W, n_dur, r);
           });
         else
           dispatch(vec4, [&](auto vec) {
-            if constexpr (FORM == KD_PLAIN) {
-              if (lo) {
-                hipLaunchKernelGGL((kd_fwd_kernel<ES, ET, decltype(vec)::value, FORM, COLL, true, KdLossOut>), dim3(blocks), dim3(64 * wpb),
-                                   0, st, x, y, symbols, ranges, boundary, weights, blank, inv_tau, dur_weight, node, saved, rows, T, S, W,
-                                   n_dur, r, *lo);
-                return;
-              }
+            if (lo) {
+              hipLaunchKernelGGL((kd_fwd_kernel<ES, ET, decltype(vec)::value, FORM, COLL, true, KdLossOut>), dim3(blocks), dim3(64 * wpb),
+                                 0, st, x, y, symbols, ranges, boundary, weights, blank, inv_tau, dur_weight, node, saved, rows, T, S, W,
+                                 n_dur, r, *lo);
+              return;
             }
             hipLaunchKernelGGL((kd_fwd_kernel<ES, ET, decltype(vec)::value, FORM, COLL>), dim3(blocks), dim3(64 * wpb), 0, st, x, y,
                                symbols, ranges, boundary, weights, blank, inv_tau, dur_weight, node, saved, rows, T, S, W, n_dur, r);
@@ -709,7 +792,7 @@ int kd_fwd_rows(const char* name, int form, const void* logits, int dtype, const
   return check_launch(name);
 }
 
-// The backward kernel of a call.  li: the loss-carrying instantiation (plain form), nullptr: the kernel as it is without it.
+// The backward kernel of a call.  li: the loss-carrying instantiation (n_dur must be 0), nullptr: the kernel as it is without it.
 int kd_bwd_rows(const char* name, int form, const void* logits, int dtype, const void* teacher, int teacher_dtype,
                 const int32_t* symbols, const int32_t* ranges, const int32_t* boundary, int blank, float temperature,
                 int collapsed, int n_dur, float dur_weight, const float* weights, const float* saved, Scale scale,
@@ -727,13 +810,11 @@ int kd_bwd_rows(const char* name, int form, const void* logits, int dtype, const
         dispatch(collapsed != 0, [&](auto coll) {
           constexpr bool V = decltype(vec)::value, COLL = decltype(coll)::value;
           constexpr int FORM = decltype(f)::value;
-          if constexpr (FORM == KD_PLAIN) {
-            if (li) {
-              hipLaunchKernelGGL((kd_bwd_kernel<ES, ET, V, FORM, COLL, true, KdLossIn>), dim3(blocks), dim3(64 * wpb), 0, st, x, y, symbols,
-                                 ranges, boundary, weights, blank, inv_tau, dur_weight, saved, scale, static_cast<ES*>(glogits), rows, T, S,
-                                 W, n_dur, r, *li);
-              return;
-            }
+          if (li) {
+            hipLaunchKernelGGL((kd_bwd_kernel<ES, ET, V, FORM, COLL, true, KdLossIn>), dim3(blocks), dim3(64 * wpb), 0, st, x, y, symbols,
+                               ranges, boundary, weights, blank, inv_tau, dur_weight, saved, scale, static_cast<ES*>(glogits), rows, T, S,
+                               W, n_dur, r, *li);
+            return;
           }
           hipLaunchKernelGGL((kd_bwd_kernel<ES, ET, V, FORM, COLL>), dim3(blocks), dim3(64 * wpb), 0, st, x, y, symbols, ranges, boundary,
                              weights, blank, inv_tau, dur_weight, saved, scale, static_cast<ES*>(glogits), rows, T, S, W, n_dur, r);
@@ -771,11 +852,14 @@ int pruned_kd_fwd(const void* logits, int dtype, const void* teacher, int teache
 // Where the student alone may be read four elements at a time and the teacher may not, the row kernel would sum lse1 in
 // another order than lse_rows does for that student; the logsumexp then runs as lse_rows' own launch, in front of the
 // ordinary row kernel.
-int pruned_band_kd_fwd(const void* logits, int dtype, const void* teacher, int teacher_dtype, const int32_t* symbols,
-                       const int32_t* ranges, const int32_t* boundary, int blank, float temperature, int collapsed,
-                       double delay_penalty, int modified, float* lse, float* pxb, float* pyb, float* node, float* saved, float* utt,
-                       int B, int T, int S, int W, int r, hipStream_t st) {
-  const char* name = "pruned_band_kd_fwd";
+// include/ftr_kd_loss_fact.h: `hat` (lse is Z, the gather is the HAT one) and / or node weights; utt == nullptr: no utterance
+// sums (the caller weights the node losses afterwards, pruned_kd_weighted_utt_sum).  Without either, ftr_kd_loss.h's call.
+int pruned_band_kd_fact_fwd(const void* logits, int dtype, const void* teacher, int teacher_dtype, const int32_t* symbols,
+                            const int32_t* ranges, const int32_t* boundary, int blank, float temperature, int collapsed,
+                            double delay_penalty, int modified, float* lse, float* pxb, float* pyb, float* node, float* saved,
+                            float* utt, int B, int T, int S, int W, int r, int hat, const float* weights, hipStream_t st) {
+  const int form = kd_form(hat, 0, weights);
+  const char* name = form == KD_PLAIN ? "pruned_band_kd_fwd" : "pruned_band_kd_fact_fwd";
   const size_t rows = (size_t)B * T * r;
   if (rows == 0) return FTR_OK;
   { const int rc32 = require_rows_32bit(name, rows); if (rc32 != FTR_OK) return rc32; }
@@ -783,13 +867,28 @@ int pruned_band_kd_fwd(const void* logits, int dtype, const void* teacher, int t
   const bool tvec = dispatch_dtype(teacher_dtype, [&](auto tag) { return rows_vec4<typename decltype(tag)::type>(W, teacher); });
   const KdLossOut lo{lse};
   const bool fused = !svec || tvec;
-  if (!fused) { const int rc = lse_rows_dtype(logits, dtype, lse, rows, W, blank, 0, st); if (rc != FTR_OK) return rc; }
-  { const int rc = kd_fwd_rows(name, KD_PLAIN, logits, dtype, teacher, teacher_dtype, symbols, ranges, boundary, blank, temperature,
-                               collapsed, 0, 0.0f, nullptr, node, saved, fused ? &lo : nullptr, rows, T, S, W, r, st);
+  if (!fused) { const int rc = lse_rows_dtype(logits, dtype, lse, rows, W, blank, hat, st); if (rc != FTR_OK) return rc; }
+  { const int rc = kd_fwd_rows(name, form, logits, dtype, teacher, teacher_dtype, symbols, ranges, boundary, blank, temperature,
+                               collapsed, 0, 0.0f, weights, node, saved, fused ? &lo : nullptr, rows, T, S, W, r, st);
     if (rc != FTR_OK) return rc; }
-  { const int rc = band_gather(logits, dtype, symbols, ranges, boundary, lse, blank, delay_penalty, pxb, pyb, B, T, S, W, r, modified, 0, st);
+  { const int rc = band_gather(logits, dtype, symbols, ranges, boundary, lse, blank, delay_penalty, pxb, pyb, B, T, S, W, r, modified, hat, st);
     if (rc != FTR_OK) return rc; }
-  return kd_utt_sum(node, utt, B, T * r, st);
+  return utt ? kd_utt_sum(node, utt, B, T * r, st) : FTR_OK;
+}
+
+int pruned_kd_weighted_utt_sum(const float* node, const float* weights, float* utt, int B, int per, hipStream_t st) {
+  hipLaunchKernelGGL(kd_utt_sum_weighted_kernel, dim3(B), dim3(256), 0, st, node, weights, utt, per);
+  return check_launch("pruned_kd_weighted_utt_sum");
+}
+
+int band_node_occupancy(const float* gxb, const float* gyb, const int32_t* ranges, const int32_t* boundary, float* occ, int B,
+                        int T, int S, int r, hipStream_t st) {
+  const size_t rows = (size_t)B * T * r;
+  if (rows == 0) return FTR_OK;
+  { const int rc32 = require_rows_32bit("band_node_occupancy", rows); if (rc32 != FTR_OK) return rc32; }
+  hipLaunchKernelGGL(band_node_occupancy_kernel, dim3((unsigned)((rows + 255) / 256)), dim3(256), 0, st, gxb, gyb, ranges, boundary,
+                     occ, rows, T, S, r);
+  return check_launch("band_node_occupancy");
 }
 
 int pruned_kd_bwd(const void* logits, int dtype, const void* teacher, int teacher_dtype, const int32_t* symbols,
@@ -806,19 +905,21 @@ int pruned_kd_bwd(const void* logits, int dtype, const void* teacher, int teache
 }
 
 // scale: a_b of the transducer term, kd_scale: k_b of the distillation term; a multiplier of zero: that part is not read
-int pruned_band_kd_bwd(const void* logits, int dtype, const void* teacher, int teacher_dtype, const int32_t* symbols,
-                       const int32_t* ranges, const int32_t* boundary, int blank, float temperature, int collapsed,
-                       const float* lse, const float* gxb, const float* gyb, Scale scale, const float* saved, Scale kd_scale,
-                       void* glogits, int B, int T, int S, int W, int r, hipStream_t st) {
-  const char* name = "pruned_band_kd_bwd";
+// (hat, weights: as in the forward)
+int pruned_band_kd_fact_bwd(const void* logits, int dtype, const void* teacher, int teacher_dtype, const int32_t* symbols,
+                            const int32_t* ranges, const int32_t* boundary, int blank, float temperature, int collapsed,
+                            const float* lse, const float* gxb, const float* gyb, Scale scale, const float* saved, Scale kd_scale,
+                            void* glogits, int B, int T, int S, int W, int r, int hat, const float* weights, hipStream_t st) {
+  const int form = kd_form(hat, 0, weights);
+  const char* name = form == KD_PLAIN ? "pruned_band_kd_bwd" : "pruned_band_kd_fact_bwd";
   const size_t rows = (size_t)B * T * r;
   if (rows == 0) return FTR_OK;
   { const int rc32 = require_rows_32bit(name, rows); if (rc32 != FTR_OK) return rc32; }
   const KdLossIn li{lse, gxb, gyb, scale, scale.mul != 0.0f, kd_scale.mul != 0.0f};
   // without a distillation part the teacher is not read: its alignment must not cost the student the 4-element path
   if (!li.kd) { teacher = logits; teacher_dtype = dtype; }
-  return kd_bwd_rows(name, KD_PLAIN, logits, dtype, teacher, teacher_dtype, symbols, ranges, boundary, blank, temperature, collapsed,
-                     0, 0.0f, nullptr, saved, kd_scale, &li, glogits, rows, T, S, W, r, st);
+  return kd_bwd_rows(name, form, logits, dtype, teacher, teacher_dtype, symbols, ranges, boundary, blank, temperature, collapsed,
+                     0, 0.0f, weights, saved, kd_scale, &li, glogits, rows, T, S, W, r, st);
 }
 
 }  // namespace ftr

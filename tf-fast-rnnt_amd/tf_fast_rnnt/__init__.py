@@ -31,7 +31,8 @@ from .rnnt_loss import rnnt_loss_pruned
 from .rnnt_loss import rnnt_kd_loss_pruned                                     # MI355X addition: distillation on the pruned band, see its docstring
 from .rnnt_loss import rnnt_kd_loss_pruned_factored                            # ... for HAT and TDT rows, with node weights
 from .rnnt_loss import rnnt_loss_pruned_kd                                     # ... and rnnt_loss_pruned + that loss in one pass over the student
-from .rnnt_loss import rnnt_kd_loss_pruned_topk, rnnt_kd_topk_teacher          # ... and from a stored top-K teacher on the teacher's own band
+from .rnnt_loss import rnnt_loss_pruned_kd_factored, rnnt_node_occupancy_pruned   # ... the same for HAT rows, node and occupancy weights
+from .rnnt_loss import rnnt_kd_loss_pruned_topk, rnnt_kd_topk_teacher         # ... and from a stored top-K teacher on the teacher's own band
 from .rnnt_loss import rnnt_alignment_pruned                           # MI355X addition: best-path alignment, see its docstring
 from .rnnt_loss import rnnt_loss_simple
 from .rnnt_loss import rnnt_loss_smoothed

@@ -140,6 +140,15 @@ _KD_LOSS_SIGNATURES = {
     "ftr_pruned_band_kd_fwd_dt": (_i, [_c_fp, _i, _c_fp, _i, _c_ip, _c_ip, _c_ip, _i, _f, _i, ctypes.c_double, _i, _c_fp, _c_fp, _c_fp, _c_fp, _c_fp, _c_fp, _i, _i, _i, _i, _i, _c_st]),
     "ftr_pruned_band_kd_bwd_scaled_dt": (_i, [_c_fp, _i, _c_fp, _i, _c_ip, _c_ip, _c_ip, _i, _f, _i, _c_fp, _c_fp, _c_fp, _c_fp, _i, _f, _c_fp, _c_fp, _i, _f, _c_fp, _i, _i, _i, _i, _i, _c_st]),
 }
+# include/ftr_kd_loss_fact.h, that pass with HAT rows and node weights: the two lists above with (factorization, node_weights) in
+# front of the stream; the node occupancies (gx_band, gy_band, ranges, boundary, occ, B, T, S, r, stream) and the weighted
+# utterance sums (node_loss, node_weights, utt_loss, B, T, r, stream)
+_KD_LOSS_FACT_SIGNATURES = {
+    "ftr_pruned_band_kd_fact_fwd_dt": (_i, _KD_LOSS_SIGNATURES["ftr_pruned_band_kd_fwd_dt"][1][:-1] + [_i, _c_fp, _c_st]),
+    "ftr_pruned_band_kd_fact_bwd_scaled_dt": (_i, _KD_LOSS_SIGNATURES["ftr_pruned_band_kd_bwd_scaled_dt"][1][:-1] + [_i, _c_fp, _c_st]),
+    "ftr_band_node_occupancy_f32": (_i, [_c_fp, _c_fp, _c_ip, _c_ip, _c_fp, _i, _i, _i, _i, _c_st]),
+    "ftr_pruned_kd_weighted_utt_sum_f32": (_i, [_c_fp, _c_fp, _c_fp, _i, _i, _i, _c_st]),
+}
 # include/ftr_kd_topk.h, that distillation loss from a stored top-K teacher on the teacher's own band: (logits, kind, teacher_values,
 # teacher_kind, teacher_indices, ranges, teacher_ranges, boundary, teacher_rest, node_weights, temperature, ...) and (..., B, T, S, C,
 # r, r_t, K, stream)
@@ -203,6 +212,7 @@ JOINER_ACT_SYMBOLS = tuple(_JOINER_ACT_SIGNATURES)   # those of include/ftr_join
 KD_SYMBOLS = tuple(_KD_SIGNATURES)               # those of include/ftr_kd.h
 KD_FACT_SYMBOLS = tuple(_KD_FACT_SIGNATURES)     # those of include/ftr_kd_fact.h
 KD_LOSS_SYMBOLS = tuple(_KD_LOSS_SIGNATURES)     # those of include/ftr_kd_loss.h
+KD_LOSS_FACT_SYMBOLS = tuple(_KD_LOSS_FACT_SIGNATURES)   # those of include/ftr_kd_loss_fact.h
 KD_TOPK_SYMBOLS = tuple(_KD_TOPK_SIGNATURES)     # those of include/ftr_kd_topk.h
 FUSED_SYMBOLS = tuple(_FUSED_SIGNATURES)         # those of include/ftr_fused.h
 LIVE_SYMBOLS = tuple(_LIVE_SIGNATURES)           # those of include/ftr_live.h
@@ -232,7 +242,7 @@ def lib() -> ctypes.CDLL:
                 f"{LIB_PATH} is missing: build the HIP extension first (python -c 'import __graft_entry__ as g; "
                 "g.build()' or make -C tf-fast-rnnt_amd/csrc).  tf_fast_rnnt has no CPU fallback.")
         handle = ctypes.CDLL(LIB_PATH)
-        for name, (restype, argtypes) in {**_SIGNATURES, **_LOWP_SIGNATURES, **_PRUNE_SUM_SIGNATURES, **_JOINER_ACT_SIGNATURES, **_KD_SIGNATURES, **_KD_FACT_SIGNATURES, **_KD_LOSS_SIGNATURES, **_KD_TOPK_SIGNATURES, **_FUSED_SIGNATURES, **_LIVE_SIGNATURES,
+        for name, (restype, argtypes) in {**_SIGNATURES, **_LOWP_SIGNATURES, **_PRUNE_SUM_SIGNATURES, **_JOINER_ACT_SIGNATURES, **_KD_SIGNATURES, **_KD_FACT_SIGNATURES, **_KD_LOSS_SIGNATURES, **_KD_LOSS_FACT_SIGNATURES, **_KD_TOPK_SIGNATURES, **_FUSED_SIGNATURES, **_LIVE_SIGNATURES,
                                             **_BAND_TDT_SIGNATURES, **_TDT_MIX_SIGNATURES, **_BAND_MULTIBLANK_SIGNATURES, **_BAND_VITERBI_SIGNATURES}.items():
             fn = getattr(handle, name)   # AttributeError here = header/library mismatch
             fn.restype = restype

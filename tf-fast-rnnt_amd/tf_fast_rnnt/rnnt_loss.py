@@ -1208,6 +1208,11 @@ def rnnt_kd_loss_pruned_factored(
         w = torch.gather(py_grad.detach(), 1, idx).transpose(1, 2).contiguous()    # occupancy of the blank arc at (s,t)
         # and / or the symbol arcs: torch.gather(px_grad.detach()[:, :, :T], 1, idx.clamp(max=S - 1))
         kd = rnnt_kd_loss_pruned_factored(logits, teacher_logits, symbols, ranges, blank, boundary, node_weights=w)
+
+    Those occupancies are the simple model's (``am + lm``) and cover the blank arcs.  The exact node occupancies of the
+    joiner being trained come from ``rnnt_node_occupancy_pruned(logits, symbols, ranges, blank, boundary)``, and
+    ``rnnt_loss_pruned_kd_factored(..., node_weights="occupancy")`` returns the transducer loss and this loss weighted by
+    them from one pass over the student: the recommended form.
     """
     for name, t in (("logits", logits), ("teacher_logits", teacher_logits)):
         if t.dtype not in _KD_DTYPES:
@@ -1551,6 +1556,248 @@ def rnnt_loss_pruned_kd(
         args = (logits, symbols_i, ranges_i, termination_symbol, boundary_i)   # the verdict on the ranges travels with them
     loss = rnnt_loss_pruned(*args, rnnt_type=rnnt_type, delay_penalty=delay_penalty, reduction=reduction)
     kd = rnnt_kd_loss_pruned(args[0], teacher_logits, *args[1:], mode=mode, temperature=temperature, reduction=reduction)
+    return loss, kd
+
+
+def _band_occupancy(gxb, gyb, ranges, boundary, S):
+    """occ [B,T,r] = gx + gy of the band recursion's occupancies under the masks of the band gradient kernel; one launch."""
+    B, T, r = ranges.shape
+    occ = torch.empty((B, T, r), dtype=torch.float32, device=gxb.device)
+    with torch.cuda.device(gxb.device):
+        _lib.call("ftr_band_node_occupancy_f32", _ptr(gxb), _ptr(gyb), _ptr(ranges), _ptr(boundary), _ptr(occ), B, T, S, r,
+                  _stream_ptr(gxb))
+    return occ
+
+
+def _lattice_occupancy(px_grad, py_grad, ranges, boundary, S):
+    """The same from the full-size occupancies of ``mutual_information_recursion``: px_grad [B,S,T(+1)], py_grad [B,S+1,T]
+    gathered onto the band, zeros outside the boundary rectangle and outside the lattice."""
+    B, T, r = ranges.shape
+    s = ranges.long()
+    t = torch.arange(T, device=ranges.device).reshape(1, T, 1)
+    if boundary is None:
+        valid = (s >= 0) & (s <= S)
+    else:
+        bd = boundary.long().reshape(B, 1, 1, 4)
+        sb, tb, se, te = bd[..., 0].clamp(min=0), bd[..., 1].clamp(min=0), bd[..., 2].clamp(max=S), bd[..., 3].clamp(max=T)
+        valid = (t >= tb) & (t < te) & (s >= sb) & (s <= se)
+    idx = s.clamp(0, S).transpose(1, 2)                                         # [B,r,T], rows s of the band
+    occ = torch.gather(py_grad, 1, idx).transpose(1, 2)
+    if S > 0:
+        gx = torch.gather(px_grad[:, :, :T], 1, idx.clamp(max=S - 1)).transpose(1, 2)
+        occ = occ + torch.where(s < S, gx, torch.zeros_like(gx))
+    return torch.where(valid, occ, torch.zeros_like(occ)).contiguous()
+
+
+def _check_loss_kd_factorization(factorization, name):
+    if factorization == "tdt":
+        raise ValueError(f"{name}: factorization 'tdt' is out of scope here (its transducer gradient needs the occupancies of "
+                         "every duration and its logits are float32 only); use rnnt_loss_tdt_pruned + rnnt_kd_loss_pruned_factored")
+    if factorization not in ("softmax", "hat"):
+        raise ValueError(f"factorization should be ('softmax' | 'hat'), given {factorization}")
+
+
+def rnnt_node_occupancy_pruned(
+    logits: torch.Tensor,
+    symbols: torch.Tensor,
+    ranges: torch.Tensor,
+    termination_symbol: int,
+    boundary: Optional[torch.Tensor] = None,
+    factorization: str = "softmax",
+    rnnt_type: str = "regular",
+    delay_penalty: float = 0.0,
+) -> torch.Tensor:
+    """The student's own node occupancies on the pruned band (MI355X addition, no reference counterpart): float32
+    [B,T,s_range], detached.  ``occ[b,t,k]`` is the probability, under the transducer loss of THIS joiner output, that an
+    alignment passes through lattice node (ranges[b,t,k], t): the sum of the occupancies of the two arcs that leave the
+    node, the symbol arc only where s < S -- exactly what the band gradient kernel multiplies the node's row by.  Nodes
+    outside ``boundary`` or outside the lattice get exact zeros.  ``factorization="softmax"``: the loss is
+    ``rnnt_loss_pruned``; ``"hat"``: ``hat_loss_pruned``; ``rnnt_type`` and ``delay_penalty`` as there.
+
+    The intended use is as ``node_weights`` of a distillation loss: distil where the student's alignment is.
+    ``rnnt_loss_pruned_kd_factored(..., node_weights="occupancy")`` does that in one pass, without this call.
+
+    Cost on the band route (ranges that are a band with s_range <= 15, "regular" / "modified"): the band forward, the band
+    recursion and one small kernel; no gradient is formed.  Everywhere else the full-size lattices are built and the
+    occupancies of ``mutual_information_recursion`` gathered onto the band.  No gradient flows through the result."""
+    _check_type(rnnt_type)
+    _check_loss_kd_factorization(factorization, "rnnt_node_occupancy_pruned")
+    hat = factorization == "hat"
+    with torch.no_grad():
+        symbols, ranges, boundary = _pruned_inputs(logits, symbols, ranges, boundary, lowp=True)
+        B, T, r, C = logits.shape
+        S = symbols.shape[1]
+        if hat and C < 2:
+            raise ValueError(f"factorization 'hat' needs a blank and at least one other column, got C = {C}")
+        if not 0 <= int(termination_symbol) < C:
+            raise ValueError(f"termination_symbol {termination_symbol} not in [0,{C})")
+        x = logits.detach().contiguous()
+        modified = rnnt_type != "regular"
+        penalty = _penalty(delay_penalty)
+        if rnnt_type != "constrained" and _band_path_ok(ranges, boundary, T, S, r):
+            dev = x.device
+            lse, pxb, pyb, gxb, gyb = (torch.empty((B, T, r), dtype=torch.float32, device=dev) for _ in range(5))
+            ans = torch.empty((B,), dtype=torch.float32, device=dev)
+            with torch.cuda.device(dev):
+                st = _stream_ptr(x)
+                _pruned_call("pruned_band_fwd", hat, x, (_ptr(symbols), _ptr(ranges), _ptr(boundary), int(termination_symbol),
+                             penalty, _ptr(lse), _ptr(pxb), _ptr(pyb), B, T, S, C, r, int(modified)), (st,))
+                nws = _lib.lib().ftr_mutual_information_band_workspace_floats(B, T, S, r)
+                bws = torch.empty((nws,), dtype=torch.float32, device=dev) if nws else None
+                _lib.call("ftr_mutual_information_band_ws_f32", _ptr(pxb), _ptr(pyb), _ptr(ranges), _ptr(boundary), _ptr(bws),
+                          nws, _ptr(ans), _ptr(gxb), _ptr(gyb), B, T, S, r, int(modified), st)
+                del bws
+            return _band_occupancy(gxb, gyb, ranges, boundary, S)
+        if rnnt_type == "constrained":
+            _, px, py = _pruned_builder_fwd(x, symbols, ranges, boundary, termination_symbol, 0.0, modified, hat)
+            px = _apply_delay_penalty(px + py[:, 1:, :], boundary, rnnt_type, delay_penalty)
+        else:
+            _, px, py = _pruned_builder_fwd(x, symbols, ranges, boundary, termination_symbol, penalty, modified, hat)
+        _, px_grad, py_grad = mi_forward_backward(px, py, boundary, True, ans_grad_is_one=True)
+        return _lattice_occupancy(px_grad, py_grad, ranges, boundary, S)
+
+
+class _PrunedLossKdFact(torch.autograd.Function):
+    """_PrunedLossKd for the entries of include/ftr_kd_loss_fact.h: a HAT row (``fact``), node weights (``weights``), or the
+    student's own occupancies as weights (``occupancy``): then the row kernel runs without weights and without utterance
+    sums, the occupancies are formed from what the band recursion returned, they weight the node losses in the utterance
+    sums' own tree, and the backward takes them as its weights."""
+
+    @staticmethod
+    def forward(ctx, logits, teacher_logits, symbols, ranges, termination_symbol, boundary, mode, temperature, modified,
+                delay_penalty, code, fact, weights, occupancy):
+        B, T, r, C = logits.shape
+        S = symbols.shape[1]
+        x = logits.detach().contiguous()
+        y = teacher_logits.detach().contiguous()
+        dev = x.device
+        band = lambda: torch.empty((B, T, r), dtype=torch.float32, device=dev)
+        lse, pxb, pyb, gxb, gyb, node = band(), band(), band(), band(), band(), band()
+        saved = torch.empty((4 if mode == _lib.FTR_KD_COLLAPSED else 2, B, T, r), dtype=torch.float32, device=dev)
+        utt = torch.empty((B,), dtype=torch.float32, device=dev)
+        ans = torch.empty((B,), dtype=torch.float32, device=dev)
+        kd = utt
+        with torch.cuda.device(dev):
+            st = _stream_ptr(x)
+            _lib.call("ftr_pruned_band_kd_fact_fwd_dt", *_kd_head(x, y), _ptr(symbols), _ptr(ranges), _ptr(boundary),
+                      int(termination_symbol), float(temperature), mode, float(delay_penalty), int(modified), _ptr(lse),
+                      _ptr(pxb), _ptr(pyb), _ptr(node), _ptr(saved), None if occupancy else _ptr(utt), B, T, S, C, r, fact,
+                      _ptr(weights), st)
+            nws = _lib.lib().ftr_mutual_information_band_workspace_floats(B, T, S, r)   # 0: the LDS-resident kernel
+            bws = torch.empty((nws,), dtype=torch.float32, device=dev) if nws else None
+            _lib.call("ftr_mutual_information_band_ws_f32", _ptr(pxb), _ptr(pyb), _ptr(ranges), _ptr(boundary), _ptr(bws),
+                      nws, _ptr(ans), _ptr(gxb), _ptr(gyb), B, T, S, r, int(modified), st)
+            del bws
+            if occupancy:
+                weights = _band_occupancy(gxb, gyb, ranges, boundary, S)
+                _lib.call("ftr_pruned_kd_weighted_utt_sum_f32", _ptr(node), _ptr(weights), _ptr(utt), B, T, r, st)
+            if code != 0:
+                kd = torch.empty((), dtype=torch.float32, device=dev)
+                _lib.call("ftr_pruned_kd_reduce_f32", _ptr(utt), B, code, _ptr(kd), st)
+        del pxb, pyb, node
+        if logits.requires_grad:
+            ctx.save_for_backward(x, y, symbols, ranges, lse, gxb, gyb, saved, boundary, weights)
+        ctx.meta = (int(termination_symbol), mode, float(temperature), int(code), fact)
+        ctx.set_materialize_grads(False)      # a part nobody differentiates arrives as None and is not read at all
+        return _negated_reduce_native(ans, code), kd
+
+    @staticmethod
+    def backward(ctx, g_loss, g_kd):
+        x, y, symbols, ranges, lse, gxb, gyb, saved, boundary, weights = ctx.saved_tensors
+        blank, mode, temperature, code, fact = ctx.meta
+        B, T, r, C = x.shape
+        if g_loss is None and g_kd is None:
+            return (None,) * 14
+        ls, lstride, lmul = _upstream_scale(g_loss, code, B) if g_loss is not None else (None, 0, 0.0)
+        ks, kstride, kmul = _upstream_scale(g_kd, code, B) if g_kd is not None else (None, 0, 0.0)
+        g = torch.empty_like(x)
+        with torch.cuda.device(x.device):
+            _lib.call("ftr_pruned_band_kd_fact_bwd_scaled_dt", *_kd_head(x, y), _ptr(symbols), _ptr(ranges), _ptr(boundary),
+                      blank, temperature, mode, _ptr(lse), _ptr(gxb), _ptr(gyb), _ptr(ls), lstride, lmul, _ptr(saved), _ptr(ks),
+                      kstride, -kmul, _ptr(g), B, T, symbols.shape[1], C, r, fact, _ptr(weights), _stream_ptr(x))
+        return (g,) + (None,) * 13
+
+
+def rnnt_loss_pruned_kd_factored(
+    logits: torch.Tensor,
+    teacher_logits: torch.Tensor,
+    symbols: torch.Tensor,
+    ranges: torch.Tensor,
+    termination_symbol: int,
+    boundary: Optional[torch.Tensor] = None,
+    factorization: str = "softmax",
+    mode: str = "full",
+    temperature: float = 1.0,
+    node_weights=None,
+    rnnt_type: str = "regular",
+    delay_penalty: float = 0.0,
+    reduction: Optional[str] = "mean",
+) -> Tuple[torch.Tensor, torch.Tensor]:
+    """``rnnt_loss_pruned_kd`` for HAT students and with node weights (MI355X addition, no reference counterpart): the
+    transducer loss and the factored distillation loss of one student tensor in one pass::
+
+        loss, kd = rnnt_loss_pruned_kd_factored(logits, teacher_logits, symbols, ranges, blank, boundary,
+                                                factorization="hat", node_weights="occupancy")
+        (loss + lam * kd).backward()
+
+    ``factorization="softmax"``: ``loss`` is ``rnnt_loss_pruned(logits, symbols, ranges, termination_symbol, boundary,
+    rnnt_type, delay_penalty, reduction)``; ``"hat"``: ``hat_loss_pruned`` of the same arguments.  ``"tdt"`` raises
+    ValueError: it is out of scope here.  ``kd`` is ``rnnt_kd_loss_pruned_factored(logits, teacher_logits, symbols,
+    ranges, termination_symbol, boundary, factorization=factorization, mode=mode, temperature=temperature,
+    node_weights=w, reduction=reduction)``.  Both float32, both bit for bit, and the argument checks, dtype rules and
+    error texts are those of the functions composed.
+
+    ``node_weights``: None (every node weighs 1); a float32 [B,T,s_range] tensor with the semantics of
+    ``rnnt_kd_loss_pruned_factored`` (it multiplies the node's distillation loss and gradient row, a weight of exactly 0
+    takes the node out of the distillation, it never gets a gradient); or the string ``"occupancy"``: the weights are the
+    detached node occupancies of this student under this loss, ``rnnt_node_occupancy_pruned(logits, symbols, ranges,
+    termination_symbol, boundary, factorization, rnnt_type, delay_penalty)``, taken from the very recursion the loss
+    runs -- ``kd`` is then, bit for bit, what ``rnnt_kd_loss_pruned_factored`` returns given that tensor.  No gradient
+    flows through the occupancy weights.  With ``factorization="softmax"`` and ``node_weights=None`` this is
+    ``rnnt_loss_pruned_kd``, the same kernels and the same bits.
+
+    The gradient is one launch: the row is computed in float32 and rounded once in the dtype of ``logits``, each part under
+    its own upstream gradient; a part that receives none is not read at all, and the row is then the single op's.  What is
+    read is as in ``rnnt_loss_pruned_kd``, plus the weights: the student rows of the rectangle's frames are read for the
+    transducer loss even where the distillation weight is 0; the teacher row of a node that is invalid or has weight 0 is
+    never read, and in the backward the distillation part of such a row is skipped.
+
+    The fused kernels serve the route of ``rnnt_loss_pruned_kd``: ranges that are a band with s_range <= 15, ``rnnt_type``
+    "regular" or "modified", FTR_PRUNED_ROUTE not "lattice".  In every other case the existing functions are called and
+    their values returned unchanged (the occupancy weights then come from ``rnnt_node_occupancy_pruned``).  Measured
+    against that composition: DESIGN.md section 4t, profiles/kd_loss_fact_bench_c3_c4_c5.jsonl."""
+    _check_type(rnnt_type)
+    _check_loss_kd_factorization(factorization, "rnnt_loss_pruned_kd_factored")
+    occupancy = isinstance(node_weights, str)
+    if occupancy and node_weights != "occupancy":
+        raise ValueError(f"node_weights should be None, a float32 [B,T,s_range] tensor or 'occupancy', given '{node_weights}'")
+    hat = factorization == "hat"
+    if not hat and node_weights is None:
+        return rnnt_loss_pruned_kd(logits, teacher_logits, symbols, ranges, termination_symbol, boundary, mode=mode,
+                                   temperature=temperature, rnnt_type=rnnt_type, delay_penalty=delay_penalty, reduction=reduction)
+    w = None if occupancy else node_weights
+    args = (logits, symbols, ranges, termination_symbol, boundary)
+    fused = rnnt_type != "constrained" and isinstance(logits, torch.Tensor) and isinstance(teacher_logits, torch.Tensor) \
+        and logits.dtype in _KD_DTYPES and teacher_logits.dtype in _KD_DTYPES and logits.dim() == 4 \
+        and tuple(teacher_logits.shape) == tuple(logits.shape) and logits.is_cuda and teacher_logits.is_cuda \
+        and teacher_logits.device == logits.device and mode in _KD_MODES and reduction in _REDUCTIONS \
+        and 0.0 < float(temperature) < float("inf") and 0 <= int(termination_symbol) < logits.shape[3] \
+        and not (hat and logits.shape[3] < 2) and (w is None or (isinstance(w, torch.Tensor) and w.dtype == torch.float32 and w.device == logits.device
+                           and tuple(w.shape) == tuple(logits.shape[:3])))
+    if fused:   # everything the composed functions would refuse is refused by them below, in their words
+        symbols_i, ranges_i, boundary_i = _pruned_inputs(logits, symbols, ranges, boundary, lowp=True)
+        B, T, r, C = logits.shape
+        if _band_path_ok(ranges_i, boundary_i, T, symbols_i.shape[1], r):
+            return _PrunedLossKdFact.apply(logits, teacher_logits, symbols_i, ranges_i, int(termination_symbol), boundary_i,
+                                           _KD_MODES[mode], float(temperature), rnnt_type != "regular", _penalty(delay_penalty),
+                                           _REDUCTIONS[reduction], _KD_FACTORIZATIONS[factorization],
+                                           None if w is None else w.detach().contiguous(), occupancy)
+        args = (logits, symbols_i, ranges_i, termination_symbol, boundary_i)   # the verdict on the ranges travels with them
+    loss = _pruned_loss(*args, rnnt_type, delay_penalty, reduction, hat)
+    if occupancy:
+        w = rnnt_node_occupancy_pruned(*args, factorization=factorization, rnnt_type=rnnt_type, delay_penalty=delay_penalty)
+    kd = rnnt_kd_loss_pruned_factored(args[0], teacher_logits, *args[1:], factorization=factorization, mode=mode,
+                                      temperature=temperature, node_weights=w, reduction=reduction)
     return loss, kd
 
 
