@@ -1508,89 +1508,48 @@ int ftr_pruned_kd_fact_bwd_scaled_dt(const void* logits, int kind, const void* t
                 n_dur, dur_weight, node_weights, stream);
 }
 
-// ---- include/ftr_kd_loss.h: the transducer loss on the band and the plain distillation loss in one pass (csrc/pruned_kd.hip)
-int ftr_pruned_band_kd_fwd_dt(const void* logits, int kind, const void* teacher_logits, int teacher_kind,
-                              const int32_t* symbols, const int32_t* ranges, const int32_t* boundary, int termination_symbol,
-                              float temperature, int mode, double delay_penalty, int modified, float* lse, float* px_band,
-                              float* py_band, float* node_loss, float* saved, float* utt_loss, int B, int T, int S, int C,
-                              int r, void* stream) {
-  const char* what = "pruned_band_kd_fwd_dt";
-  clear_error();
+// ---- include/ftr_kd_loss.h, include/ftr_kd_loss_fact.h: the transducer loss on the band and the distillation loss in one
+// pass (csrc/pruned_kd.hip); the factored entries add a HAT row, node weights, and the student's own occupancies as weights
+// element kinds, mode and temperature as above, which is all the plain entries check; then the factorization, of which TDT is
+// known and refused
+static int kd_loss_check_head(const char* what, int kind, int teacher_kind, int mode, float temperature, int factorization, int C,
+                              bool fact_entry) {
   FTR_TRY(kd_check_head(what, kind, teacher_kind, mode, temperature, FTR_KD_FACT_SOFTMAX, 0, 0.0f, C));
-  FTR_TRY(check_builder(what, B >= 0 && T >= 1 && S >= 0 && C >= 1 && r >= 1, termination_symbol, C));
-  if (B == 0) return FTR_OK;
-  FTR_TRY(pointers_then_device(what, logits && teacher_logits && ranges && lse && px_band && py_band && node_loss && saved &&
-                                         utt_loss && (symbols || S == 0)));
-  return pruned_band_kd_fact_fwd(logits, kind, teacher_logits, teacher_kind, symbols, ranges, boundary, termination_symbol, temperature,
-                                 mode == FTR_KD_COLLAPSED, delay_penalty, modified, lse, px_band, py_band, node_loss, saved, utt_loss, B,
-                                 T, S, C, r, 0, nullptr, stream_of(stream));
-}
-
-int ftr_pruned_band_kd_bwd_scaled_dt(const void* logits, int kind, const void* teacher_logits, int teacher_kind,
-                                     const int32_t* symbols, const int32_t* ranges, const int32_t* boundary,
-                                     int termination_symbol, float temperature, int mode, const float* lse,
-                                     const float* gx_band, const float* gy_band, const float* loss_scale,
-                                     int loss_scale_stride, float loss_scale_mul, const float* saved, const float* kd_scale,
-                                     int kd_scale_stride, float kd_scale_mul, void* glogits, int B, int T, int S, int C,
-                                     int r, void* stream) {
-  const char* what = "pruned_band_kd_bwd_scaled_dt";
-  clear_error();
-  FTR_TRY(kd_check_head(what, kind, teacher_kind, mode, temperature, FTR_KD_FACT_SOFTMAX, 0, 0.0f, C));
-  FTR_REQUIRE(loss_scale_mul >= -3.0e38f && loss_scale_mul <= 3.0e38f && kd_scale_mul >= -3.0e38f && kd_scale_mul <= 3.0e38f,
-              "%s: the multipliers %g and %g must be finite", what, (double)loss_scale_mul, (double)kd_scale_mul);
-  FTR_TRY(check_builder(what, B >= 0 && T >= 1 && S >= 0 && C >= 1 && r >= 1, termination_symbol, C, true));
-  FTR_TRY(check_scale_stride(what, loss_scale_stride));
-  FTR_TRY(check_scale_stride(what, kd_scale_stride));
-  if (B == 0) return FTR_OK;
-  const bool loss_on = loss_scale_mul != 0.0f, kd_on = kd_scale_mul != 0.0f;
-  FTR_TRY(pointers_then_device(what, logits && ranges && glogits && (symbols || S == 0) && (!loss_on || (lse && gx_band && gy_band)) &&
-                                         (!kd_on || (teacher_logits && saved))));
-  return pruned_band_kd_fact_bwd(logits, kind, teacher_logits, teacher_kind, symbols, ranges, boundary, termination_symbol, temperature,
-                                 mode == FTR_KD_COLLAPSED, lse, gx_band, gy_band, Scale{loss_scale, loss_scale_stride, loss_scale_mul},
-                                 saved, Scale{kd_scale, kd_scale_stride, kd_scale_mul}, glogits, B, T, S, C, r, 0, nullptr,
-                                 stream_of(stream));
-}
-
-// ---- include/ftr_kd_loss_fact.h: that pass with a HAT row, node weights, and the student's own occupancies as weights
-// element kinds, mode and temperature as above; then the factorization, of which TDT is known and refused
-static int kd_loss_fact_check_head(const char* what, int kind, int teacher_kind, int mode, float temperature, int factorization, int C) {
-  FTR_TRY(kd_check_head(what, kind, teacher_kind, mode, temperature, FTR_KD_FACT_SOFTMAX, 0, 0.0f, C));
+  if (!fact_entry) return FTR_OK;
   FTR_REQUIRE(factorization == FTR_KD_FACT_SOFTMAX || factorization == FTR_KD_FACT_HAT || factorization == FTR_KD_FACT_TDT,
               "%s: unknown factorization %d (FTR_KD_FACT_SOFTMAX = 0, FTR_KD_FACT_HAT = 1)", what, factorization);
   FTR_REQUIRE(factorization != FTR_KD_FACT_TDT, "%s: FTR_KD_FACT_TDT is out of scope for the one-pass entries (FTR_KD_FACT_SOFTMAX = 0, FTR_KD_FACT_HAT = 1)", what);
   return FTR_OK;
 }
 
-int ftr_pruned_band_kd_fact_fwd_dt(const void* logits, int kind, const void* teacher_logits, int teacher_kind,
-                                   const int32_t* symbols, const int32_t* ranges, const int32_t* boundary,
-                                   int termination_symbol, float temperature, int mode, double delay_penalty, int modified,
-                                   float* lse, float* px_band, float* py_band, float* node_loss, float* saved, float* utt_loss,
-                                   int B, int T, int S, int C, int r, int factorization, const float* node_weights,
-                                   void* stream) {
-  const char* what = "pruned_band_kd_fact_fwd_dt";
+// the body of both forward entries, under the entry's own `what`; the plain entry is FTR_KD_FACT_SOFTMAX, NULL and requires
+// utt_loss, which the factored one may leave out
+static int kd_loss_fwd(const char* what, const void* logits, int kind, const void* teacher_logits, int teacher_kind,
+                       const int32_t* symbols, const int32_t* ranges, const int32_t* boundary, int termination_symbol,
+                       float temperature, int mode, double delay_penalty, int modified, float* lse, float* px_band,
+                       float* py_band, float* node_loss, float* saved, float* utt_loss, int B, int T, int S, int C, int r,
+                       int factorization, const float* node_weights, bool fact_entry, void* stream) {
   clear_error();
-  FTR_TRY(kd_loss_fact_check_head(what, kind, teacher_kind, mode, temperature, factorization, C));
+  FTR_TRY(kd_loss_check_head(what, kind, teacher_kind, mode, temperature, factorization, C, fact_entry));
   const int hat = factorization == FTR_KD_FACT_HAT;
   FTR_TRY(check_builder(what, B >= 0 && T >= 1 && S >= 0 && C >= 1 && r >= 1, termination_symbol, C, false, hat));
   if (B == 0) return FTR_OK;
   FTR_TRY(pointers_then_device(what, logits && teacher_logits && ranges && lse && px_band && py_band && node_loss && saved &&
-                                         (symbols || S == 0)));
+                                         (utt_loss || fact_entry) && (symbols || S == 0)));
   return pruned_band_kd_fact_fwd(logits, kind, teacher_logits, teacher_kind, symbols, ranges, boundary, termination_symbol,
                                  temperature, mode == FTR_KD_COLLAPSED, delay_penalty, modified, lse, px_band, py_band, node_loss,
                                  saved, utt_loss, B, T, S, C, r, hat, node_weights, stream_of(stream));
 }
 
-int ftr_pruned_band_kd_fact_bwd_scaled_dt(const void* logits, int kind, const void* teacher_logits, int teacher_kind,
-                                          const int32_t* symbols, const int32_t* ranges, const int32_t* boundary,
-                                          int termination_symbol, float temperature, int mode, const float* lse,
-                                          const float* gx_band, const float* gy_band, const float* loss_scale,
-                                          int loss_scale_stride, float loss_scale_mul, const float* saved,
-                                          const float* kd_scale, int kd_scale_stride, float kd_scale_mul, void* glogits, int B,
-                                          int T, int S, int C, int r, int factorization, const float* node_weights,
-                                          void* stream) {
-  const char* what = "pruned_band_kd_fact_bwd_scaled_dt";
+// and of both backward entries
+static int kd_loss_bwd(const char* what, const void* logits, int kind, const void* teacher_logits, int teacher_kind,
+                       const int32_t* symbols, const int32_t* ranges, const int32_t* boundary, int termination_symbol,
+                       float temperature, int mode, const float* lse, const float* gx_band, const float* gy_band,
+                       const float* loss_scale, int loss_scale_stride, float loss_scale_mul, const float* saved,
+                       const float* kd_scale, int kd_scale_stride, float kd_scale_mul, void* glogits, int B, int T, int S, int C,
+                       int r, int factorization, const float* node_weights, bool fact_entry, void* stream) {
   clear_error();
-  FTR_TRY(kd_loss_fact_check_head(what, kind, teacher_kind, mode, temperature, factorization, C));
+  FTR_TRY(kd_loss_check_head(what, kind, teacher_kind, mode, temperature, factorization, C, fact_entry));
   FTR_REQUIRE(loss_scale_mul >= -3.0e38f && loss_scale_mul <= 3.0e38f && kd_scale_mul >= -3.0e38f && kd_scale_mul <= 3.0e38f,
               "%s: the multipliers %g and %g must be finite", what, (double)loss_scale_mul, (double)kd_scale_mul);
   const int hat = factorization == FTR_KD_FACT_HAT;
@@ -1605,6 +1564,53 @@ int ftr_pruned_band_kd_fact_bwd_scaled_dt(const void* logits, int kind, const vo
                                  temperature, mode == FTR_KD_COLLAPSED, lse, gx_band, gy_band,
                                  Scale{loss_scale, loss_scale_stride, loss_scale_mul}, saved, Scale{kd_scale, kd_scale_stride, kd_scale_mul},
                                  glogits, B, T, S, C, r, hat, node_weights, stream_of(stream));
+}
+
+int ftr_pruned_band_kd_fwd_dt(const void* logits, int kind, const void* teacher_logits, int teacher_kind,
+                              const int32_t* symbols, const int32_t* ranges, const int32_t* boundary, int termination_symbol,
+                              float temperature, int mode, double delay_penalty, int modified, float* lse, float* px_band,
+                              float* py_band, float* node_loss, float* saved, float* utt_loss, int B, int T, int S, int C,
+                              int r, void* stream) {
+  return kd_loss_fwd("pruned_band_kd_fwd_dt", logits, kind, teacher_logits, teacher_kind, symbols, ranges, boundary,
+                     termination_symbol, temperature, mode, delay_penalty, modified, lse, px_band, py_band, node_loss, saved,
+                     utt_loss, B, T, S, C, r, FTR_KD_FACT_SOFTMAX, NULL, false, stream);
+}
+
+int ftr_pruned_band_kd_bwd_scaled_dt(const void* logits, int kind, const void* teacher_logits, int teacher_kind,
+                                     const int32_t* symbols, const int32_t* ranges, const int32_t* boundary,
+                                     int termination_symbol, float temperature, int mode, const float* lse,
+                                     const float* gx_band, const float* gy_band, const float* loss_scale,
+                                     int loss_scale_stride, float loss_scale_mul, const float* saved, const float* kd_scale,
+                                     int kd_scale_stride, float kd_scale_mul, void* glogits, int B, int T, int S, int C,
+                                     int r, void* stream) {
+  return kd_loss_bwd("pruned_band_kd_bwd_scaled_dt", logits, kind, teacher_logits, teacher_kind, symbols, ranges, boundary,
+                     termination_symbol, temperature, mode, lse, gx_band, gy_band, loss_scale, loss_scale_stride, loss_scale_mul,
+                     saved, kd_scale, kd_scale_stride, kd_scale_mul, glogits, B, T, S, C, r, FTR_KD_FACT_SOFTMAX, NULL, false, stream);
+}
+
+int ftr_pruned_band_kd_fact_fwd_dt(const void* logits, int kind, const void* teacher_logits, int teacher_kind,
+                                   const int32_t* symbols, const int32_t* ranges, const int32_t* boundary,
+                                   int termination_symbol, float temperature, int mode, double delay_penalty, int modified,
+                                   float* lse, float* px_band, float* py_band, float* node_loss, float* saved, float* utt_loss,
+                                   int B, int T, int S, int C, int r, int factorization, const float* node_weights,
+                                   void* stream) {
+  return kd_loss_fwd("pruned_band_kd_fact_fwd_dt", logits, kind, teacher_logits, teacher_kind, symbols, ranges, boundary,
+                     termination_symbol, temperature, mode, delay_penalty, modified, lse, px_band, py_band, node_loss, saved,
+                     utt_loss, B, T, S, C, r, factorization, node_weights, true, stream);
+}
+
+int ftr_pruned_band_kd_fact_bwd_scaled_dt(const void* logits, int kind, const void* teacher_logits, int teacher_kind,
+                                          const int32_t* symbols, const int32_t* ranges, const int32_t* boundary,
+                                          int termination_symbol, float temperature, int mode, const float* lse,
+                                          const float* gx_band, const float* gy_band, const float* loss_scale,
+                                          int loss_scale_stride, float loss_scale_mul, const float* saved,
+                                          const float* kd_scale, int kd_scale_stride, float kd_scale_mul, void* glogits, int B,
+                                          int T, int S, int C, int r, int factorization, const float* node_weights,
+                                          void* stream) {
+  return kd_loss_bwd("pruned_band_kd_fact_bwd_scaled_dt", logits, kind, teacher_logits, teacher_kind, symbols, ranges, boundary,
+                     termination_symbol, temperature, mode, lse, gx_band, gy_band, loss_scale, loss_scale_stride, loss_scale_mul,
+                     saved, kd_scale, kd_scale_stride, kd_scale_mul, glogits, B, T, S, C, r, factorization, node_weights, true,
+                     stream);
 }
 
 int ftr_band_node_occupancy_f32(const float* gx_band, const float* gy_band, const int32_t* ranges, const int32_t* boundary,

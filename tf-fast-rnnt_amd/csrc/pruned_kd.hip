@@ -38,8 +38,7 @@
 // N > 0: the last two = those of the duration head (written as 0 and never read when dur_weight == 0).
 // Element types of x and y are independent (float, bf16_t, fp16_t); a row is read four elements at a time only when BOTH
 // tensors pass rows_vec4.  All arithmetic is float32; the gradient row is rounded once when it is stored in x's type.
-#include "ftr_common.h"
-#include "launch.h"
+#include "kd_common.h"
 
 namespace ftr {
 namespace {
@@ -61,41 +60,24 @@ template <bool COLL>
 __device__ __forceinline__ KdRow kd_row(size_t row, const int32_t* __restrict__ symbols, const int32_t* __restrict__ ranges,
                                         const int32_t* __restrict__ boundary, const float* __restrict__ weights, int blank,
                                         int T, int S, int Ct, int r) {
+  const KdNode n = kd_node(row, ranges, boundary, weights, T, S, r);
   KdRow g;
-  const unsigned bt = (unsigned)row / (unsigned)r;   // rows < 2^31 (require_rows_32bit): 32-bit divisions, a tenth of the 64-bit ones
-  g.b = (int)(bt / (unsigned)T);
-  const int t = (int)(bt - (unsigned)g.b * (unsigned)T);
-  const int s = ranges[row];
-  const Bound bd = load_boundary(boundary, g.b, S, T);   // clamped into the lattice: s < se implies s < S below
-  g.valid = t >= bd.tb && t < bd.te && s >= bd.sb && s <= bd.se;
-  g.lrow = t >= bd.tb && t < bd.te && s >= 0 && s <= S;
-  g.geo = g.valid;
-  g.s = s;
-  g.w = 1.0f;
-  if (weights) {
-    g.w = weights[row];
-    g.valid = g.valid && g.w != 0.0f;   // a NaN weight compares unequal: the node stays valid and its loss becomes NaN
-  }
+  g.valid = n.valid; g.geo = n.geo; g.b = n.b; g.s = n.s; g.w = n.w;
+  g.lrow = n.t >= n.bd.tb && n.t < n.bd.te && n.s >= 0 && n.s <= S;
   g.k0 = blank;
   g.k1 = -1;
-  if (COLL && g.valid && s < bd.se) {
-    const int c = min(max(symbols[(size_t)g.b * S + s], 0), Ct - 1);   // symbol kept among the token columns, as the pruned builders do
+  if (COLL && g.valid && n.s < n.bd.se) {
+    const int c = min(max(symbols[(size_t)g.b * S + n.s], 0), Ct - 1);   // symbol kept among the token columns, as the pruned builders do
     if (c != blank) g.k1 = c;
   }
   return g;
 }
-
-// x log(x / y) with the xlogy convention: a class of teacher mass 0 adds nothing, whatever the student says; NaN stays NaN
-__device__ __forceinline__ float kd_term(float p, float logp_minus_logq) { return p == 0.0f ? 0.0f : p * logp_minus_logq; }
 
 __device__ __forceinline__ float lse3(float a, float b, float c) {
   const float m = fmaxf(fmaxf(a, b), c);
   if (m == -INFINITY) return -INFINITY;
   return m + __logf(__expf(a - m) + __expf(b - m) + __expf(c - m));   // a NaN among a, b, c comes out of the sum
 }
-
-// a maximum to subtract that is never -inf (a row, or a rest class, of -inf only: exp(-inf - 0) = 0, not exp(NaN))
-__device__ __forceinline__ float kd_safe_max(float m) { return m == -INFINITY ? 0.0f : m; }
 
 // the number of saved planes: 2, + 2 collapsed, + 2 with a duration head
 template <bool COLL>
@@ -626,12 +608,7 @@ __global__ void kd_bwd_kernel(const ES* __restrict__ x, const ET* __restrict__ y
     zero_row = !g.geo || !(in.loss || (in.kd && g.valid));
   }
   if (zero_row) {   // zeros, without a look at the logits
-    if (VEC) {
-      const f4 zero = {0.0f, 0.0f, 0.0f, 0.0f};
-      for (int i = lane; i < (W >> 2); i += 64) store4(gr, i, zero);
-    } else {
-      for (int c = lane; c < W; c += 64) gr[c] = elem_from_float<ES>(0.0f);
-    }
+    kd_zero_row<ES, VEC>(gr, lane, W);
     return;
   }
   const ES* xr = x + row * W;
@@ -736,24 +713,17 @@ __global__ void kd_bwd_kernel(const ES* __restrict__ x, const ET* __restrict__ y
   }
 }
 
-// both element types -> one call of f(elem_tag<ES>, elem_tag<ET>)
-template <typename F>
-inline auto dispatch_dtype2(int dtype, int teacher_dtype, F&& f) {
-  return dispatch_dtype(dtype, [&](auto s) { return dispatch_dtype(teacher_dtype, [&](auto t) { return f(s, t); }); });
-}
-
 // the row form of a call: one softmax without weights is the plain form; with weights it runs as TDT with n_dur = 0
 inline int kd_form(int hat, int n_dur, const float* weights) { return hat ? KD_HAT : (n_dur > 0 || weights) ? KD_TDT : KD_PLAIN; }
 
 // The forward row kernel of a call.  lo: the loss-carrying instantiation with this output (n_dur must be 0), nullptr: the
 // kernel as it is without it.
 int kd_fwd_rows(const char* name, int form, const void* logits, int dtype, const void* teacher, int teacher_dtype,
-                const int32_t* symbols, const int32_t* ranges, const int32_t* boundary, int blank, float temperature,
-                int collapsed, int n_dur, float dur_weight, const float* weights, float* node, float* saved, const KdLossOut* lo,
-                size_t rows, int T, int S, int W, int r, hipStream_t st) {
-  const int wpb = 4;
-  const unsigned blocks = (unsigned)((rows + wpb - 1) / wpb);
-  const float inv_tau = 1.0f / temperature;
+                const int32_t* symbols, const int32_t* ranges, const int32_t* boundary, int blank, int collapsed, int n_dur,
+                float dur_weight, const float* weights, float* node, float* saved, const KdLossOut* lo, const KdLaunch& kl, int T,
+                int S, int W, int r, hipStream_t st) {
+  const size_t rows = kl.rows;
+  const float inv_tau = kl.inv_tau;
   dispatch_dtype2(dtype, teacher_dtype, [&](auto stag, auto ttag) {
     using ES = typename decltype(stag)::type;
     using ET = typename decltype(ttag)::type;
@@ -767,23 +737,23 @@ int kd_fwd_rows(const char* name, int form, const void* logits, int dtype, const
         if (vec4 && W <= 2048)   // both rows fit the registers of a wave: 1, 2, 4 or 8 quads of elements per lane and tensor
           dispatch_among<1, 2, 4, 8>(W <= 256 ? 1 : W <= 512 ? 2 : W <= 1024 ? 4 : 8, [&](auto n) {
             if (lo) {
-              hipLaunchKernelGGL((kd_fwd_reg_kernel<ES, ET, decltype(n)::value, FORM, COLL, true, KdLossOut>), dim3(blocks), dim3(64 * wpb),
+              hipLaunchKernelGGL((kd_fwd_reg_kernel<ES, ET, decltype(n)::value, FORM, COLL, true, KdLossOut>), dim3(kl.blocks), dim3(64 * KD_WPB),
                                  0, st, x, y, symbols, ranges, boundary, weights, blank, inv_tau, dur_weight, node, saved, rows, T, S, W,
                                  n_dur, r, *lo);
               return;
             }
-            hipLaunchKernelGGL((kd_fwd_reg_kernel<ES, ET, decltype(n)::value, FORM, COLL>), dim3(blocks), dim3(64 * wpb), 0, st, x, y,
+            hipLaunchKernelGGL((kd_fwd_reg_kernel<ES, ET, decltype(n)::value, FORM, COLL>), dim3(kl.blocks), dim3(64 * KD_WPB), 0, st, x, y,
                                symbols, ranges, boundary, weights, blank, inv_tau, dur_weight, node, saved, rows, T, S, W, n_dur, r);
           });
         else
           dispatch(vec4, [&](auto vec) {
             if (lo) {
-              hipLaunchKernelGGL((kd_fwd_kernel<ES, ET, decltype(vec)::value, FORM, COLL, true, KdLossOut>), dim3(blocks), dim3(64 * wpb),
+              hipLaunchKernelGGL((kd_fwd_kernel<ES, ET, decltype(vec)::value, FORM, COLL, true, KdLossOut>), dim3(kl.blocks), dim3(64 * KD_WPB),
                                  0, st, x, y, symbols, ranges, boundary, weights, blank, inv_tau, dur_weight, node, saved, rows, T, S, W,
                                  n_dur, r, *lo);
               return;
             }
-            hipLaunchKernelGGL((kd_fwd_kernel<ES, ET, decltype(vec)::value, FORM, COLL>), dim3(blocks), dim3(64 * wpb), 0, st, x, y,
+            hipLaunchKernelGGL((kd_fwd_kernel<ES, ET, decltype(vec)::value, FORM, COLL>), dim3(kl.blocks), dim3(64 * KD_WPB), 0, st, x, y,
                                symbols, ranges, boundary, weights, blank, inv_tau, dur_weight, node, saved, rows, T, S, W, n_dur, r);
           });
       });
@@ -794,12 +764,11 @@ int kd_fwd_rows(const char* name, int form, const void* logits, int dtype, const
 
 // The backward kernel of a call.  li: the loss-carrying instantiation (n_dur must be 0), nullptr: the kernel as it is without it.
 int kd_bwd_rows(const char* name, int form, const void* logits, int dtype, const void* teacher, int teacher_dtype,
-                const int32_t* symbols, const int32_t* ranges, const int32_t* boundary, int blank, float temperature,
-                int collapsed, int n_dur, float dur_weight, const float* weights, const float* saved, Scale scale,
-                const KdLossIn* li, void* glogits, size_t rows, int T, int S, int W, int r, hipStream_t st) {
-  const int wpb = 4;
-  const unsigned blocks = (unsigned)((rows + wpb - 1) / wpb);
-  const float inv_tau = 1.0f / temperature;
+                const int32_t* symbols, const int32_t* ranges, const int32_t* boundary, int blank, int collapsed, int n_dur,
+                float dur_weight, const float* weights, const float* saved, Scale scale, const KdLossIn* li, void* glogits,
+                const KdLaunch& kl, int T, int S, int W, int r, hipStream_t st) {
+  const size_t rows = kl.rows;
+  const float inv_tau = kl.inv_tau;
   dispatch_dtype2(dtype, teacher_dtype, [&](auto stag, auto ttag) {
     using ES = typename decltype(stag)::type;
     using ET = typename decltype(ttag)::type;
@@ -811,12 +780,12 @@ int kd_bwd_rows(const char* name, int form, const void* logits, int dtype, const
           constexpr bool V = decltype(vec)::value, COLL = decltype(coll)::value;
           constexpr int FORM = decltype(f)::value;
           if (li) {
-            hipLaunchKernelGGL((kd_bwd_kernel<ES, ET, V, FORM, COLL, true, KdLossIn>), dim3(blocks), dim3(64 * wpb), 0, st, x, y, symbols,
+            hipLaunchKernelGGL((kd_bwd_kernel<ES, ET, V, FORM, COLL, true, KdLossIn>), dim3(kl.blocks), dim3(64 * KD_WPB), 0, st, x, y, symbols,
                                ranges, boundary, weights, blank, inv_tau, dur_weight, saved, scale, static_cast<ES*>(glogits), rows, T, S,
                                W, n_dur, r, *li);
             return;
           }
-          hipLaunchKernelGGL((kd_bwd_kernel<ES, ET, V, FORM, COLL>), dim3(blocks), dim3(64 * wpb), 0, st, x, y, symbols, ranges, boundary,
+          hipLaunchKernelGGL((kd_bwd_kernel<ES, ET, V, FORM, COLL>), dim3(kl.blocks), dim3(64 * KD_WPB), 0, st, x, y, symbols, ranges, boundary,
                              weights, blank, inv_tau, dur_weight, saved, scale, static_cast<ES*>(glogits), rows, T, S, W, n_dur, r);
         });
       });
@@ -839,11 +808,10 @@ int pruned_kd_fwd(const void* logits, int dtype, const void* teacher, int teache
                   int S, int W, int r, hipStream_t st) {
   const int form = kd_form(hat, n_dur, weights);
   const char* name = form == KD_PLAIN ? "pruned_kd_fwd" : "pruned_kd_fact_fwd";   // the names the messages have always carried
-  const size_t rows = (size_t)B * T * r;
-  if (rows == 0) return FTR_OK;
-  { const int rc32 = require_rows_32bit(name, rows); if (rc32 != FTR_OK) return rc32; }
-  { const int rc = kd_fwd_rows(name, form, logits, dtype, teacher, teacher_dtype, symbols, ranges, boundary, blank, temperature,
-                               collapsed, n_dur, dur_weight, weights, node, saved, nullptr, rows, T, S, W, r, st);
+  const KdLaunch kl = kd_launch(name, B, T, r, temperature);
+  if (kl.done) return kl.rc;
+  { const int rc = kd_fwd_rows(name, form, logits, dtype, teacher, teacher_dtype, symbols, ranges, boundary, blank, collapsed, n_dur,
+                               dur_weight, weights, node, saved, nullptr, kl, T, S, W, r, st);
     if (rc != FTR_OK) return rc; }
   return kd_utt_sum(node, utt, B, T * r, st);
 }
@@ -860,16 +828,15 @@ int pruned_band_kd_fact_fwd(const void* logits, int dtype, const void* teacher, 
                             float* utt, int B, int T, int S, int W, int r, int hat, const float* weights, hipStream_t st) {
   const int form = kd_form(hat, 0, weights);
   const char* name = form == KD_PLAIN ? "pruned_band_kd_fwd" : "pruned_band_kd_fact_fwd";
-  const size_t rows = (size_t)B * T * r;
-  if (rows == 0) return FTR_OK;
-  { const int rc32 = require_rows_32bit(name, rows); if (rc32 != FTR_OK) return rc32; }
+  const KdLaunch kl = kd_launch(name, B, T, r, temperature);
+  if (kl.done) return kl.rc;
   const bool svec = dispatch_dtype(dtype, [&](auto tag) { return rows_vec4<typename decltype(tag)::type>(W, logits); });
   const bool tvec = dispatch_dtype(teacher_dtype, [&](auto tag) { return rows_vec4<typename decltype(tag)::type>(W, teacher); });
   const KdLossOut lo{lse};
   const bool fused = !svec || tvec;
-  if (!fused) { const int rc = lse_rows_dtype(logits, dtype, lse, rows, W, blank, hat, st); if (rc != FTR_OK) return rc; }
-  { const int rc = kd_fwd_rows(name, form, logits, dtype, teacher, teacher_dtype, symbols, ranges, boundary, blank, temperature,
-                               collapsed, 0, 0.0f, weights, node, saved, fused ? &lo : nullptr, rows, T, S, W, r, st);
+  if (!fused) { const int rc = lse_rows_dtype(logits, dtype, lse, kl.rows, W, blank, hat, st); if (rc != FTR_OK) return rc; }
+  { const int rc = kd_fwd_rows(name, form, logits, dtype, teacher, teacher_dtype, symbols, ranges, boundary, blank, collapsed, 0,
+                               0.0f, weights, node, saved, fused ? &lo : nullptr, kl, T, S, W, r, st);
     if (rc != FTR_OK) return rc; }
   { const int rc = band_gather(logits, dtype, symbols, ranges, boundary, lse, blank, delay_penalty, pxb, pyb, B, T, S, W, r, modified, hat, st);
     if (rc != FTR_OK) return rc; }
@@ -897,11 +864,10 @@ int pruned_kd_bwd(const void* logits, int dtype, const void* teacher, int teache
                   int T, int S, int W, int r, hipStream_t st) {
   const int form = kd_form(hat, n_dur, weights);
   const char* name = form == KD_PLAIN ? "pruned_kd_bwd" : "pruned_kd_fact_bwd";
-  const size_t rows = (size_t)B * T * r;
-  if (rows == 0) return FTR_OK;
-  { const int rc32 = require_rows_32bit(name, rows); if (rc32 != FTR_OK) return rc32; }
-  return kd_bwd_rows(name, form, logits, dtype, teacher, teacher_dtype, symbols, ranges, boundary, blank, temperature, collapsed,
-                     n_dur, dur_weight, weights, saved, scale, nullptr, glogits, rows, T, S, W, r, st);
+  const KdLaunch kl = kd_launch(name, B, T, r, temperature);
+  if (kl.done) return kl.rc;
+  return kd_bwd_rows(name, form, logits, dtype, teacher, teacher_dtype, symbols, ranges, boundary, blank, collapsed, n_dur,
+                     dur_weight, weights, saved, scale, nullptr, glogits, kl, T, S, W, r, st);
 }
 
 // scale: a_b of the transducer term, kd_scale: k_b of the distillation term; a multiplier of zero: that part is not read
@@ -912,14 +878,13 @@ int pruned_band_kd_fact_bwd(const void* logits, int dtype, const void* teacher, 
                             void* glogits, int B, int T, int S, int W, int r, int hat, const float* weights, hipStream_t st) {
   const int form = kd_form(hat, 0, weights);
   const char* name = form == KD_PLAIN ? "pruned_band_kd_bwd" : "pruned_band_kd_fact_bwd";
-  const size_t rows = (size_t)B * T * r;
-  if (rows == 0) return FTR_OK;
-  { const int rc32 = require_rows_32bit(name, rows); if (rc32 != FTR_OK) return rc32; }
+  const KdLaunch kl = kd_launch(name, B, T, r, temperature);
+  if (kl.done) return kl.rc;
   const KdLossIn li{lse, gxb, gyb, scale, scale.mul != 0.0f, kd_scale.mul != 0.0f};
   // without a distillation part the teacher is not read: its alignment must not cost the student the 4-element path
   if (!li.kd) { teacher = logits; teacher_dtype = dtype; }
-  return kd_bwd_rows(name, form, logits, dtype, teacher, teacher_dtype, symbols, ranges, boundary, blank, temperature, collapsed,
-                     0, 0.0f, weights, saved, kd_scale, &li, glogits, rows, T, S, W, r, st);
+  return kd_bwd_rows(name, form, logits, dtype, teacher, teacher_dtype, symbols, ranges, boundary, blank, collapsed, 0, 0.0f,
+                     weights, saved, kd_scale, &li, glogits, kl, T, S, W, r, st);
 }
 
 }  // namespace ftr

@@ -33,22 +33,17 @@
 // The element types of x and of the values are independent (float, bf16_t, fp16_t); the student row is read four elements
 // at a time under rows_vec4, the K values always one per lane.  All arithmetic is float32; the gradient row is rounded once
 // when it is stored in x's type.
-#include "ftr_common.h"
-#include "launch.h"
+#include "kd_common.h"
 
 namespace ftr {
 namespace {
 
 constexpr int KT_CH = 2048;   // columns per slot table: the longest register-resident row
-constexpr int KT_WPB = 4;     // waves (rows) per block
+constexpr int KT_WPB = KD_WPB;   // waves (rows) per block
 static_assert(FTR_KD_TOPK_MAX_K == 64, "one teacher entry per lane of a wave; the slot byte holds k + 1 <= 64");
 
 __device__ __forceinline__ float wave_max(float v) { return wave_max_dpp(v); }
 __device__ __forceinline__ float wave_sum(float v) { return wave_sum_dpp(v); }
-// x log(x / y) with the xlogy convention: teacher mass 0 adds nothing, whatever the student says; NaN stays NaN
-__device__ __forceinline__ float kt_term(float p, float logp_minus_logq) { return p == 0.0f ? 0.0f : p * logp_minus_logq; }
-// a maximum to subtract that is never -inf
-__device__ __forceinline__ float kt_safe_max(float m) { return m == -INFINITY ? 0.0f : m; }
 // orders the LDS traffic of one wave in the program's order (the hardware completes it in order; this holds the compiler to it)
 __device__ __forceinline__ void kt_wave_sync() { __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront"); }
 
@@ -58,21 +53,13 @@ struct KtRow { bool on; int b; size_t trow; float w; };
 __device__ __forceinline__ KtRow kt_row(size_t row, const int32_t* __restrict__ ranges, const int32_t* __restrict__ tranges,
                                         const int32_t* __restrict__ boundary, const float* __restrict__ weights, int T, int S,
                                         int r, int rt) {
+  const KdNode n = kd_node(row, ranges, boundary, weights, T, S, r);
   KtRow g;
-  const unsigned bt = (unsigned)row / (unsigned)r;   // rows < 2^31 (require_rows_32bit)
-  g.b = (int)(bt / (unsigned)T);
-  const int t = (int)(bt - (unsigned)g.b * (unsigned)T);
-  const int s = ranges[row];
-  const Bound bd = load_boundary(boundary, g.b, S, T);
-  g.on = t >= bd.tb && t < bd.te && s >= bd.sb && s <= bd.se;
-  g.w = 1.0f;
-  if (weights) {
-    g.w = weights[row];
-    g.on = g.on && g.w != 0.0f;   // a NaN weight compares unequal: the node stays and its loss becomes NaN
-  }
+  g.b = n.b; g.w = n.w;
+  const unsigned bt = (unsigned)row / (unsigned)r;   // the frame, as kd_node splits the row index
   // the teacher's band at this frame starts at its first element, rows consecutive (as every kernel here derives s)
-  const long long kp = (long long)s - (long long)(tranges ? tranges[(size_t)bt * rt] : ranges[(size_t)bt * r]);
-  g.on = g.on && kp >= 0 && kp < (long long)rt;
+  const long long kp = (long long)n.s - (long long)(tranges ? tranges[(size_t)bt * rt] : ranges[(size_t)bt * r]);
+  g.on = n.valid && kp >= 0 && kp < (long long)rt;
   g.trow = (size_t)bt * rt + (size_t)(g.on ? kp : 0);
   return g;
 }
@@ -139,23 +126,23 @@ __device__ __forceinline__ void kt_store_off(float* __restrict__ node, float* __
 }
 
 // The end of a forward row, by every lane of the wave.  mr_raw: the maximum of the columns NOT in I (-inf: there is none);
-// sr: their sum of exp(. - kt_safe_max(mr_raw)) -- the one exponential a column costs.  The columns of I are K at most and
+// sr: their sum of exp(. - kd_safe_max(mr_raw)) -- the one exponential a column costs.  The columns of I are K at most and
 // each has one owner lane (own; xk = a[idx_k] on lane k), so the full logsumexp takes the rest's sum as it is, moved to the
 // full maximum (mr <= ms: the factor is at most 1), and adds the owners' terms.
 __device__ __forceinline__ void kt_finish(float* __restrict__ node, float* __restrict__ saved, size_t rows, size_t row, int lane,
                                           float mr_raw, float sr, bool own, const KtEntry e, float xk, float R, bool weighted,
                                           float w) {
-  const float mr = kt_safe_max(mr_raw);
-  const float ms = kt_safe_max(fmaxf(mr_raw, wave_max(own ? xk : -INFINITY)));
+  const float mr = kd_safe_max(mr_raw);
+  const float ms = kd_safe_max(fmaxf(mr_raw, wave_max(own ? xk : -INFINITY)));
   const float ss = (sr == 0.0f ? 0.0f : sr * __expf(mr - ms)) + wave_sum(own ? __expf(xk - ms) : 0.0f);
   const float Ls = ms + __logf(ss);
   const float Rs = mr + __logf(sr);   // every column stored: 0 + log 0 = -inf
-  const float mt = kt_safe_max(fmaxf(wave_max(e.v), R));
+  const float mt = kd_safe_max(fmaxf(wave_max(e.v), R));
   const float L = mt + __logf(wave_sum(__expf(e.v - mt)) + __expf(R - mt));
   const float lp = e.v - L;           // the lanes past K: -inf, mass 0
-  float kl = wave_sum(kt_term(__expf(lp), lp - (xk - Ls)));
+  float kl = wave_sum(kd_term(__expf(lp), lp - (xk - Ls)));
   const float lpr = R - L;
-  kl += kt_term(__expf(lpr), lpr - (Rs - Ls));
+  kl += kd_term(__expf(lpr), lpr - (Rs - Ls));
   if (lane == 0) {
     node[row] = weighted ? kl * w : kl;
     saved[row] = Ls;
@@ -206,7 +193,7 @@ __global__ __launch_bounds__(64 * KT_WPB) void kt_fwd_reg_kernel(const ES* __res
 #pragma unroll
   for (int q = 0; q < NQ; ++q) mr = fmaxf(fmaxf(mr, fmaxf(v[q][0], v[q][1])), fmaxf(v[q][2], v[q][3]));
   const float mr_raw = wave_max(mr);
-  mr = kt_safe_max(mr_raw);
+  mr = kd_safe_max(mr_raw);
   float sr = 0.0f;
 #pragma unroll
   for (int q = 0; q < NQ; ++q) {
@@ -242,7 +229,7 @@ __global__ __launch_bounds__(64 * KT_WPB) void kt_fwd_kernel(const ES* __restric
   float mr = -INFINITY;
   const bool own = kt_sweep<ES, VEC>(xr, tab, lane, C, e, inv_tau, [&](float a, uint32_t slot) { mr = fmaxf(mr, slot ? -INFINITY : a); });
   const float mr_raw = wave_max(mr);
-  mr = kt_safe_max(mr_raw);
+  mr = kd_safe_max(mr_raw);
   float sr = 0.0f;
   kt_sweep<ES, VEC>(xr, tab, lane, C, e, inv_tau, [&](float a, uint32_t slot) { sr += slot ? 0.0f : __expf(a - mr); });
   sr = wave_sum(sr);
@@ -266,12 +253,7 @@ __global__ __launch_bounds__(64 * KT_WPB) void kt_bwd_kernel(const ES* __restric
   const KtRow g = kt_row(row, ranges, tranges, boundary, weights, T, S, r, rt);
   ES* gr = gx + row * C;
   if (!g.on) {   // zeros, without a look at the logits or the cache
-    if (VEC) {
-      const f4 zero = {0.0f, 0.0f, 0.0f, 0.0f};
-      for (int i = lane; i < (C >> 2); i += 64) store4(gr, i, zero);
-    } else {
-      for (int c = lane; c < C; c += 64) gr[c] = elem_from_float<ES>(0.0f);
-    }
+    kd_zero_row<ES, VEC>(gr, lane, C);
     return;
   }
   const ES* xr = x + row * C;
@@ -315,12 +297,6 @@ __global__ __launch_bounds__(64 * KT_WPB) void kt_bwd_kernel(const ES* __restric
   }
 }
 
-// both element types -> one call of f(elem_tag<ES>, elem_tag<ET>)
-template <typename F>
-inline auto dispatch_dtype2(int dtype, int teacher_dtype, F&& f) {
-  return dispatch_dtype(dtype, [&](auto s) { return dispatch_dtype(teacher_dtype, [&](auto t) { return f(s, t); }); });
-}
-
 }  // namespace
 
 int pruned_kd_topk_fwd(const void* logits, int dtype, const void* tvalues, int teacher_dtype, const int32_t* tindices,
@@ -328,11 +304,8 @@ int pruned_kd_topk_fwd(const void* logits, int dtype, const void* tvalues, int t
                        const float* weights, float temperature, float* node, float* saved, float* utt, int B, int T, int S,
                        int C, int r, int rt, int K, hipStream_t st) {
   const char* name = "pruned_kd_topk_fwd";
-  const size_t rows = (size_t)B * T * r;
-  if (rows == 0) return FTR_OK;
-  { const int rc32 = require_rows_32bit(name, rows); if (rc32 != FTR_OK) return rc32; }
-  const unsigned blocks = (unsigned)((rows + KT_WPB - 1) / KT_WPB);
-  const float inv_tau = 1.0f / temperature;
+  const KdLaunch kl = kd_launch(name, B, T, r, temperature);
+  if (kl.done) return kl.rc;
   dispatch_dtype2(dtype, teacher_dtype, [&](auto stag, auto ttag) {
     using ES = typename decltype(stag)::type;
     using ET = typename decltype(ttag)::type;
@@ -341,13 +314,13 @@ int pruned_kd_topk_fwd(const void* logits, int dtype, const void* tvalues, int t
     const bool vec4 = rows_vec4<ES>(C, x);
     if (vec4 && C <= KT_CH)   // the row fits the registers of a wave: 1, 2, 4 or 8 quads of elements per lane
       dispatch_among<1, 2, 4, 8>(C <= 256 ? 1 : C <= 512 ? 2 : C <= 1024 ? 4 : 8, [&](auto n) {
-        hipLaunchKernelGGL((kt_fwd_reg_kernel<ES, ET, decltype(n)::value>), dim3(blocks), dim3(64 * KT_WPB), 0, st, x, tv, tindices,
-                           ranges, tranges, boundary, rest, weights, inv_tau, node, saved, rows, T, S, C, r, rt, K);
+        hipLaunchKernelGGL((kt_fwd_reg_kernel<ES, ET, decltype(n)::value>), dim3(kl.blocks), dim3(64 * KT_WPB), 0, st, x, tv, tindices,
+                           ranges, tranges, boundary, rest, weights, kl.inv_tau, node, saved, kl.rows, T, S, C, r, rt, K);
       });
     else
       dispatch(vec4, [&](auto vec) {
-        hipLaunchKernelGGL((kt_fwd_kernel<ES, ET, decltype(vec)::value>), dim3(blocks), dim3(64 * KT_WPB), 0, st, x, tv, tindices,
-                           ranges, tranges, boundary, rest, weights, inv_tau, node, saved, rows, T, S, C, r, rt, K);
+        hipLaunchKernelGGL((kt_fwd_kernel<ES, ET, decltype(vec)::value>), dim3(kl.blocks), dim3(64 * KT_WPB), 0, st, x, tv, tindices,
+                           ranges, tranges, boundary, rest, weights, kl.inv_tau, node, saved, kl.rows, T, S, C, r, rt, K);
       });
   });
   { const int rc = check_launch(name); if (rc != FTR_OK) return rc; }
@@ -359,19 +332,16 @@ int pruned_kd_topk_bwd(const void* logits, int dtype, const void* tvalues, int t
                        const float* weights, float temperature, const float* saved, Scale scale, void* glogits, int B, int T,
                        int S, int C, int r, int rt, int K, hipStream_t st) {
   const char* name = "pruned_kd_topk_bwd";
-  const size_t rows = (size_t)B * T * r;
-  if (rows == 0) return FTR_OK;
-  { const int rc32 = require_rows_32bit(name, rows); if (rc32 != FTR_OK) return rc32; }
-  const unsigned blocks = (unsigned)((rows + KT_WPB - 1) / KT_WPB);
-  const float inv_tau = 1.0f / temperature;
+  const KdLaunch kl = kd_launch(name, B, T, r, temperature);
+  if (kl.done) return kl.rc;
   dispatch_dtype2(dtype, teacher_dtype, [&](auto stag, auto ttag) {
     using ES = typename decltype(stag)::type;
     using ET = typename decltype(ttag)::type;
     const ES* x = static_cast<const ES*>(logits);
     dispatch(rows_vec4<ES>(C, x, glogits), [&](auto vec) {
-      hipLaunchKernelGGL((kt_bwd_kernel<ES, ET, decltype(vec)::value>), dim3(blocks), dim3(64 * KT_WPB), 0, st, x,
-                         static_cast<const ET*>(tvalues), tindices, ranges, tranges, boundary, rest, weights, inv_tau, saved, scale,
-                         static_cast<ES*>(glogits), rows, T, S, C, r, rt, K);
+      hipLaunchKernelGGL((kt_bwd_kernel<ES, ET, decltype(vec)::value>), dim3(kl.blocks), dim3(64 * KT_WPB), 0, st, x,
+                         static_cast<const ET*>(tvalues), tindices, ranges, tranges, boundary, rest, weights, kl.inv_tau, saved, scale,
+                         static_cast<ES*>(glogits), kl.rows, T, S, C, r, rt, K);
     });
   });
   return check_launch(name);

@@ -393,6 +393,25 @@ def mutual_information_recursion_tdt(
     return (ans, (px_grad, py_grad)) if calc_gradients else ans
 
 
+def band_forward_backward(px_band: torch.Tensor, py_band: torch.Tensor, ranges: torch.Tensor, S: int,
+                          boundary: Optional[torch.Tensor], modified):
+    """The ordinary recursion on band-shaped operands [B,T,r], raw tensors (no autograd): forward recursion, cut and backward
+    recursion in one launch on torch's current stream; its workspace (none for the LDS-resident kernel) is a local and goes
+    with the return.  Returns (ans, gx_band, gy_band); the occupancies are seeded with ones.  ``ranges`` must be a band the
+    kernels cover (the caller's business: _band_path_ok of rnnt_loss.py)."""
+    B, T, r = px_band.shape
+    dev = px_band.device
+    ans = torch.empty((B,), dtype=torch.float32, device=dev)
+    gx = torch.empty_like(px_band)
+    gy = torch.empty_like(py_band)
+    with torch.cuda.device(dev):
+        nws = _lib.lib().ftr_mutual_information_band_workspace_floats(B, T, int(S), r)   # 0: the LDS-resident kernel
+        ws = torch.empty((nws,), dtype=torch.float32, device=dev) if nws else None
+        _lib.call("ftr_mutual_information_band_ws_f32", _ptr(px_band), _ptr(py_band), _ptr(ranges), _ptr(boundary), _ptr(ws), nws,
+                  _ptr(ans), _ptr(gx), _ptr(gy), B, T, int(S), r, int(modified), _stream_ptr(px_band))
+    return ans, gx, gy
+
+
 def band_tdt_supported(T: int, S: int, r: int, N: int, Ny: int) -> bool:
     """Does the band-native TDT recursion (csrc/mi_band_tdt.hip) cover these sizes?"""
     return _lib.lib().ftr_mutual_information_band_tdt_supported(int(T), int(S), int(r), int(N), int(Ny)) != 0

@@ -36,7 +36,7 @@ import weakref
 import torch
 
 from . import _lib
-from .mutual_information import (_as_boundary, _ptr, _require_gpu, _stream_ptr, band_multiblank_forward_backward,
+from .mutual_information import (_as_boundary, _ptr, _require_gpu, _stream_ptr, band_forward_backward, band_multiblank_forward_backward,
                                  band_multiblank_supported, band_tdt_forward_backward, band_tdt_supported, band_viterbi_supported, cummin, mb_forward_backward, mi_forward_backward,
                                  mutual_information_recursion, mutual_information_viterbi, mutual_information_viterbi_tdt, mutual_information_viterbi_tdt_band,
                                  tdt_forward_backward)
@@ -955,22 +955,12 @@ class _PrunedLoss(torch.autograd.Function):
         need = logits.requires_grad
         ctx.band = _band_path_ok(ranges, boundary, T, S, r)
         if ctx.band:
-            lse = torch.empty((B, T, r), dtype=torch.float32, device=x.device)
-            pxb = torch.empty((B, T, r), dtype=torch.float32, device=x.device)
-            pyb = torch.empty((B, T, r), dtype=torch.float32, device=x.device)
-            gxb = torch.empty((B, T, r), dtype=torch.float32, device=x.device)
-            gyb = torch.empty((B, T, r), dtype=torch.float32, device=x.device)
-            ans = torch.empty((B,), dtype=torch.float32, device=x.device)
+            lse, pxb, pyb = (torch.empty((B, T, r), dtype=torch.float32, device=x.device) for _ in range(3))
             with torch.cuda.device(x.device):
-                st = _stream_ptr(x)
                 _pruned_call("pruned_band_fwd", hat, x, (_ptr(symbols), _ptr(ranges), _ptr(boundary),
                              int(termination_symbol), float(delay_penalty), _ptr(lse), _ptr(pxb), _ptr(pyb),
-                             B, T, S, C, r, int(modified)), (st,))
-                nws = _lib.lib().ftr_mutual_information_band_workspace_floats(B, T, S, r)   # 0: the LDS-resident kernel
-                bws = torch.empty((nws,), dtype=torch.float32, device=x.device) if nws else None
-                _lib.call("ftr_mutual_information_band_ws_f32", _ptr(pxb), _ptr(pyb), _ptr(ranges), _ptr(boundary), _ptr(bws),
-                          nws, _ptr(ans), _ptr(gxb), _ptr(gyb), B, T, S, r, int(modified), st)
-                del bws
+                             B, T, S, C, r, int(modified)), (_stream_ptr(x),))
+            ans, gxb, gyb = band_forward_backward(pxb, pyb, ranges, S, boundary, modified)
             del pxb, pyb
             if need:
                 ctx.save_for_backward(x, symbols, ranges, lse, gxb, gyb, boundary)
@@ -1068,6 +1058,39 @@ def _kd_head(x, y):
     return (_ptr(x), _LOWP_KIND.get(x.dtype, _lib.FTR_DTYPE_F32), _ptr(y), _LOWP_KIND.get(y.dtype, _lib.FTR_DTYPE_F32))
 
 
+def _check_kd_dtype(name, t) -> None:
+    if t.dtype not in _KD_DTYPES:
+        raise TypeError(f"{name} must be float32, bfloat16 or float16, got {t.dtype}")
+
+
+def _temperature_ok(temperature) -> bool:
+    return 0.0 < float(temperature) < float("inf")
+
+
+def _check_temperature(temperature) -> float:
+    temperature = float(temperature)
+    if not _temperature_ok(temperature):
+        raise ValueError(f"temperature must be a finite number > 0, given {temperature}")
+    return temperature
+
+
+def _check_node_weights(node_weights, shape) -> None:
+    """the dtype, then the shape against (B, T, s_range)"""
+    if node_weights.dtype != torch.float32:
+        raise TypeError(f"node_weights must be float32, got {node_weights.dtype}")
+    if tuple(node_weights.shape) != tuple(shape):
+        raise ValueError(f"node_weights must be [B,T,s_range] = {tuple(shape)}, got {tuple(node_weights.shape)}")
+
+
+def _kd_reduce(utt, code, st):
+    """the utterance losses [B] under the reduction: themselves for "none", else their mean / sum, one launch on stream ``st``"""
+    if code == 0:
+        return utt
+    out = torch.empty((), dtype=torch.float32, device=utt.device)
+    _lib.call("ftr_pruned_kd_reduce_f32", _ptr(utt), utt.shape[0], code, _ptr(out), st)
+    return out
+
+
 def rnnt_kd_loss_pruned(
     logits: torch.Tensor,
     teacher_logits: torch.Tensor,
@@ -1125,15 +1148,12 @@ class _PrunedKdLoss(torch.autograd.Function):
         node = torch.empty((B, T, r), dtype=torch.float32, device=x.device)
         saved = torch.empty((planes, B, T, r), dtype=torch.float32, device=x.device)
         utt = torch.empty((B,), dtype=torch.float32, device=x.device)
-        out = utt
         with torch.cuda.device(x.device):
             st = _stream_ptr(x)
             _lib.call("ftr_pruned_kd_fact_fwd_dt", *_kd_head(x, y), _ptr(symbols), _ptr(ranges), _ptr(boundary),
                       int(termination_symbol), float(temperature), mode, _ptr(node), _ptr(saved), _ptr(utt), B, T, S, C, r,
                       fact, n_dur, float(dur_weight), _ptr(weights), st)
-            if code != 0:
-                out = torch.empty((), dtype=torch.float32, device=x.device)
-                _lib.call("ftr_pruned_kd_reduce_f32", _ptr(utt), B, code, _ptr(out), st)
+            out = _kd_reduce(utt, code, st)
         if logits.requires_grad:
             ctx.save_for_backward(x, y, symbols, ranges, saved, boundary, weights)
         ctx.meta = (int(termination_symbol), mode, float(temperature), int(code), fact, n_dur, float(dur_weight))
@@ -1214,9 +1234,8 @@ def rnnt_kd_loss_pruned_factored(
     ``rnnt_loss_pruned_kd_factored(..., node_weights="occupancy")`` returns the transducer loss and this loss weighted by
     them from one pass over the student: the recommended form.
     """
-    for name, t in (("logits", logits), ("teacher_logits", teacher_logits)):
-        if t.dtype not in _KD_DTYPES:
-            raise TypeError(f"{name} must be float32, bfloat16 or float16, got {t.dtype}")
+    _check_kd_dtype("logits", logits)
+    _check_kd_dtype("teacher_logits", teacher_logits)
     if logits.dim() != 4:
         raise ValueError("logits must be [B,T,s_range,C]")
     if tuple(teacher_logits.shape) != tuple(logits.shape):
@@ -1225,9 +1244,7 @@ def rnnt_kd_loss_pruned_factored(
         raise ValueError(f"factorization should be ('softmax' | 'hat' | 'tdt'), given {factorization}")
     if mode not in _KD_MODES:
         raise ValueError(f"mode should be ('full' | 'collapsed'), given {mode}")
-    temperature = float(temperature)
-    if not (0.0 < temperature < float("inf")):
-        raise ValueError(f"temperature must be a finite number > 0, given {temperature}")
+    temperature = _check_temperature(temperature)
     W = logits.shape[3]
     num_durations = int(num_durations)
     duration_weight = float(duration_weight)
@@ -1247,10 +1264,7 @@ def rnnt_kd_loss_pruned_factored(
     if not 0 <= int(termination_symbol) < C:
         raise ValueError(f"termination_symbol {termination_symbol} not in [0,{C})")
     if node_weights is not None:
-        if node_weights.dtype != torch.float32:
-            raise TypeError(f"node_weights must be float32, got {node_weights.dtype}")
-        if tuple(node_weights.shape) != tuple(logits.shape[:3]):
-            raise ValueError(f"node_weights must be [B,T,s_range] = {tuple(logits.shape[:3])}, got {tuple(node_weights.shape)}")
+        _check_node_weights(node_weights, logits.shape[:3])
     symbols, ranges, boundary = _pruned_inputs(logits, symbols, ranges, boundary, lowp=True)
     _require_gpu(teacher_logits, "teacher_logits")
     if teacher_logits.device != logits.device:
@@ -1281,15 +1295,12 @@ class _PrunedKdTopkLoss(torch.autograd.Function):
         node = torch.empty((B, T, r), dtype=torch.float32, device=x.device)
         saved = torch.empty((3, B, T, r), dtype=torch.float32, device=x.device)
         utt = torch.empty((B,), dtype=torch.float32, device=x.device)
-        out = utt
         with torch.cuda.device(x.device):
             st = _stream_ptr(x)
             _lib.call("ftr_pruned_kd_topk_fwd_dt", *_kd_head(x, values), _ptr(indices), _ptr(ranges), _ptr(tranges), _ptr(boundary),
                       _ptr(rest), _ptr(weights), float(temperature), _ptr(node), _ptr(saved), _ptr(utt), B, T, _KD_TOPK_S, C, r,
                       rt, K, st)
-            if code != 0:
-                out = torch.empty((), dtype=torch.float32, device=x.device)
-                _lib.call("ftr_pruned_kd_reduce_f32", _ptr(utt), B, code, _ptr(out), st)
+            out = _kd_reduce(utt, code, st)
         if logits.requires_grad:
             ctx.save_for_backward(x, values, indices, ranges, saved, tranges, boundary, rest, weights)
         ctx.meta = (float(temperature), int(code))
@@ -1363,9 +1374,8 @@ def rnnt_kd_loss_pruned_topk(
         kp = ranges - teacher_ranges[:, :, :1]
         distilled = (valid & (kp >= 0) & (kp < teacher_ranges.shape[2])).sum((1, 2))    # [B]
     """
-    for name, t in (("logits", logits), ("teacher_values", teacher_values)):
-        if t.dtype not in _KD_DTYPES:
-            raise TypeError(f"{name} must be float32, bfloat16 or float16, got {t.dtype}")
+    _check_kd_dtype("logits", logits)
+    _check_kd_dtype("teacher_values", teacher_values)
     if teacher_indices.dtype != torch.int32:
         raise TypeError(f"teacher_indices must be int32, got {teacher_indices.dtype}")
     for name, t in (("teacher_rest", teacher_rest), ("node_weights", node_weights)):
@@ -1388,11 +1398,9 @@ def rnnt_kd_loss_pruned_topk(
         raise ValueError(f"teacher_ranges must be a [B,T,r_t] = {(B, T, rt)} tensor")
     if teacher_rest is not None and tuple(teacher_rest.shape) != (B, T, rt):
         raise ValueError(f"teacher_rest must be [B,T,r_t] = {(B, T, rt)}, got {tuple(teacher_rest.shape)}")
-    if node_weights is not None and tuple(node_weights.shape) != (B, T, r):
-        raise ValueError(f"node_weights must be [B,T,s_range] = {(B, T, r)}, got {tuple(node_weights.shape)}")
-    temperature = float(temperature)
-    if not (0.0 < temperature < float("inf")):
-        raise ValueError(f"temperature must be a finite number > 0, given {temperature}")
+    if node_weights is not None:
+        _check_node_weights(node_weights, (B, T, r))   # its dtype has answered above, with teacher_rest's
+    temperature = _check_temperature(temperature)
     code = _reduction_code(reduction)
     _require_gpu(logits, "logits")
     ranges = torch.as_tensor(ranges, device=logits.device).to(torch.int32).contiguous()
@@ -1424,9 +1432,7 @@ def rnnt_kd_topk_teacher(teacher_logits: torch.Tensor, k: int, temperature: floa
     C = teacher_logits.shape[-1]
     if not 1 <= k <= min(C, _lib.FTR_KD_TOPK_MAX_K):
         raise ValueError(f"k = {k} must be in [1, min(C, {_lib.FTR_KD_TOPK_MAX_K})] for rows of C = {C}")
-    temperature = float(temperature)
-    if not (0.0 < temperature < float("inf")):
-        raise ValueError(f"temperature must be a finite number > 0, given {temperature}")
+    temperature = _check_temperature(temperature)
     with torch.no_grad():
         values, idx = torch.topk(teacher_logits, k, dim=-1)
         rest = None
@@ -1437,61 +1443,63 @@ def rnnt_kd_topk_teacher(teacher_logits: torch.Tensor, k: int, temperature: floa
 
 
 class _PrunedLossKd(torch.autograd.Function):
-    """rnnt_loss_pruned (band route) and rnnt_kd_loss_pruned as one node (the entries of include/ftr_kd_loss.h): forward =
-    one pass over both tensors (node losses, the saved normalisers and the student's logsumexp) + band gather + the
-    per-utterance sum, then the band recursion and the two reductions, which are the launches of the two ops; backward =
-    one streaming pass that writes the sum of both gradients, each under its own upstream gradient, in the student's dtype."""
+    """rnnt_loss_pruned / hat_loss_pruned (band route) and rnnt_kd_loss_pruned_factored as one node: forward = one pass over
+    both tensors (node losses, the saved normalisers and the student's logsumexp) + band gather + the per-utterance sum,
+    then the band recursion and the two reductions, which are the launches of the two ops; backward = one streaming pass
+    that writes the sum of both gradients, each under its own upstream gradient, in the student's dtype.
+    One softmax (``fact``) without weights runs through the entries of include/ftr_kd_loss.h; a HAT row, node weights
+    (``weights``) or the student's own occupancies as weights (``occupancy``) through those of include/ftr_kd_loss_fact.h.
+    With ``occupancy`` the row kernel runs without weights and without utterance sums, the occupancies are formed from what
+    the band recursion returned, they weight the node losses in the utterance sums' own tree, and the backward takes them
+    as its weights."""
 
     @staticmethod
     def forward(ctx, logits, teacher_logits, symbols, ranges, termination_symbol, boundary, mode, temperature, modified,
-                delay_penalty, code):
+                delay_penalty, code, fact, weights, occupancy):
         B, T, r, C = logits.shape
         S = symbols.shape[1]
         x = logits.detach().contiguous()
         y = teacher_logits.detach().contiguous()
         dev = x.device
-        band = lambda: torch.empty((B, T, r), dtype=torch.float32, device=dev)
-        lse, pxb, pyb, gxb, gyb, node = band(), band(), band(), band(), band(), band()
+        lse, pxb, pyb, node = (torch.empty((B, T, r), dtype=torch.float32, device=dev) for _ in range(4))
         saved = torch.empty((4 if mode == _lib.FTR_KD_COLLAPSED else 2, B, T, r), dtype=torch.float32, device=dev)
         utt = torch.empty((B,), dtype=torch.float32, device=dev)
-        ans = torch.empty((B,), dtype=torch.float32, device=dev)
-        kd = utt
+        plain = fact == _lib.FTR_KD_FACT_SOFTMAX and weights is None and not occupancy
         with torch.cuda.device(dev):
             st = _stream_ptr(x)
-            _lib.call("ftr_pruned_band_kd_fwd_dt", *_kd_head(x, y), _ptr(symbols), _ptr(ranges), _ptr(boundary),
-                      int(termination_symbol), float(temperature), mode, float(delay_penalty), int(modified), _ptr(lse),
-                      _ptr(pxb), _ptr(pyb), _ptr(node), _ptr(saved), _ptr(utt), B, T, S, C, r, st)
-            nws = _lib.lib().ftr_mutual_information_band_workspace_floats(B, T, S, r)   # 0: the LDS-resident kernel
-            bws = torch.empty((nws,), dtype=torch.float32, device=dev) if nws else None
-            _lib.call("ftr_mutual_information_band_ws_f32", _ptr(pxb), _ptr(pyb), _ptr(ranges), _ptr(boundary), _ptr(bws),
-                      nws, _ptr(ans), _ptr(gxb), _ptr(gyb), B, T, S, r, int(modified), st)
-            del bws
-            if code != 0:
-                kd = torch.empty((), dtype=torch.float32, device=dev)
-                _lib.call("ftr_pruned_kd_reduce_f32", _ptr(utt), B, code, _ptr(kd), st)
+            _lib.call("ftr_pruned_band_kd_fwd_dt" if plain else "ftr_pruned_band_kd_fact_fwd_dt", *_kd_head(x, y), _ptr(symbols),
+                      _ptr(ranges), _ptr(boundary), int(termination_symbol), float(temperature), mode, float(delay_penalty),
+                      int(modified), _ptr(lse), _ptr(pxb), _ptr(pyb), _ptr(node), _ptr(saved), None if occupancy else _ptr(utt),
+                      B, T, S, C, r, *(() if plain else (fact, _ptr(weights))), st)
+            ans, gxb, gyb = band_forward_backward(pxb, pyb, ranges, S, boundary, modified)
+            if occupancy:
+                weights = _band_occupancy(gxb, gyb, ranges, boundary, S)
+                _lib.call("ftr_pruned_kd_weighted_utt_sum_f32", _ptr(node), _ptr(weights), _ptr(utt), B, T, r, st)
+            kd = _kd_reduce(utt, code, st)
         del pxb, pyb, node
         if logits.requires_grad:
-            ctx.save_for_backward(x, y, symbols, ranges, lse, gxb, gyb, saved, boundary)
-        ctx.meta = (int(termination_symbol), mode, float(temperature), int(code))
+            ctx.save_for_backward(x, y, symbols, ranges, lse, gxb, gyb, saved, boundary, weights)
+        ctx.meta = (int(termination_symbol), mode, float(temperature), int(code), fact, plain)
         ctx.set_materialize_grads(False)      # a part nobody differentiates arrives as None and is not read at all
         return _negated_reduce_native(ans, code), kd
 
     @staticmethod
     def backward(ctx, g_loss, g_kd):
-        x, y, symbols, ranges, lse, gxb, gyb, saved, boundary = ctx.saved_tensors
-        blank, mode, temperature, code = ctx.meta
+        x, y, symbols, ranges, lse, gxb, gyb, saved, boundary, weights = ctx.saved_tensors
+        blank, mode, temperature, code, fact, plain = ctx.meta
         B, T, r, C = x.shape
         if g_loss is None and g_kd is None:
-            return (None,) * 11
+            return (None,) * 14
         # (pointer tensor, stride, multiplier) of each part; an absent part: multiplier 0, nothing of it is read
         ls, lstride, lmul = _upstream_scale(g_loss, code, B) if g_loss is not None else (None, 0, 0.0)
         ks, kstride, kmul = _upstream_scale(g_kd, code, B) if g_kd is not None else (None, 0, 0.0)
         g = torch.empty_like(x)
         with torch.cuda.device(x.device):
-            _lib.call("ftr_pruned_band_kd_bwd_scaled_dt", *_kd_head(x, y), _ptr(symbols), _ptr(ranges), _ptr(boundary), blank,
-                      temperature, mode, _ptr(lse), _ptr(gxb), _ptr(gyb), _ptr(ls), lstride, lmul, _ptr(saved), _ptr(ks),
-                      kstride, -kmul, _ptr(g), B, T, symbols.shape[1], C, r, _stream_ptr(x))   # -kmul: kd is not a negated score
-        return (g,) + (None,) * 10
+            _lib.call("ftr_pruned_band_kd_bwd_scaled_dt" if plain else "ftr_pruned_band_kd_fact_bwd_scaled_dt", *_kd_head(x, y),
+                      _ptr(symbols), _ptr(ranges), _ptr(boundary), blank, temperature, mode, _ptr(lse), _ptr(gxb), _ptr(gyb),
+                      _ptr(ls), lstride, lmul, _ptr(saved), _ptr(ks), kstride, -kmul, _ptr(g), B, T, symbols.shape[1], C, r,
+                      *(() if plain else (fact, _ptr(weights))), _stream_ptr(x))   # -kmul: kd is not a negated score
+        return (g,) + (None,) * 13
 
 
 def rnnt_loss_pruned_kd(
@@ -1540,22 +1548,39 @@ def rnnt_loss_pruned_kd(
     the two existing functions are called and their two values returned unchanged.  Measured against that composition
     (profiles/kd_loss_bench_c3_c4_c5.jsonl)."""
     _check_type(rnnt_type)
+    return _loss_pruned_kd(logits, teacher_logits, symbols, ranges, termination_symbol, boundary, "softmax", mode, temperature,
+                           None, rnnt_type, delay_penalty, reduction)
+
+
+def _loss_pruned_kd(logits, teacher_logits, symbols, ranges, termination_symbol, boundary, factorization, mode, temperature,
+                    node_weights, rnnt_type, delay_penalty, reduction):
+    """rnnt_loss_pruned_kd and rnnt_loss_pruned_kd_factored behind their own first checks: the fused node where it serves,
+    else the functions composed.  ``node_weights``: None, a tensor or "occupancy"."""
+    occupancy = isinstance(node_weights, str)
+    hat = factorization == "hat"
+    w = None if occupancy else node_weights
     args = (logits, symbols, ranges, termination_symbol, boundary)
     fused = rnnt_type != "constrained" and isinstance(logits, torch.Tensor) and isinstance(teacher_logits, torch.Tensor) \
         and logits.dtype in _KD_DTYPES and teacher_logits.dtype in _KD_DTYPES and logits.dim() == 4 \
         and tuple(teacher_logits.shape) == tuple(logits.shape) and logits.is_cuda and teacher_logits.is_cuda \
         and teacher_logits.device == logits.device and mode in _KD_MODES and reduction in _REDUCTIONS \
-        and 0.0 < float(temperature) < float("inf") and 0 <= int(termination_symbol) < logits.shape[3]
-    if fused:   # everything the two functions would refuse is refused by them below, in their words
+        and _temperature_ok(temperature) and 0 <= int(termination_symbol) < logits.shape[3] \
+        and not (hat and logits.shape[3] < 2) and (w is None or (isinstance(w, torch.Tensor) and w.dtype == torch.float32 and w.device == logits.device
+                           and tuple(w.shape) == tuple(logits.shape[:3])))
+    if fused:   # everything the composed functions would refuse is refused by them below, in their words
         symbols_i, ranges_i, boundary_i = _pruned_inputs(logits, symbols, ranges, boundary, lowp=True)
         B, T, r, C = logits.shape
         if _band_path_ok(ranges_i, boundary_i, T, symbols_i.shape[1], r):
             return _PrunedLossKd.apply(logits, teacher_logits, symbols_i, ranges_i, int(termination_symbol), boundary_i,
                                        _KD_MODES[mode], float(temperature), rnnt_type != "regular", _penalty(delay_penalty),
-                                       _REDUCTIONS[reduction])
+                                       _REDUCTIONS[reduction], _KD_FACTORIZATIONS[factorization],
+                                       None if w is None else w.detach().contiguous(), occupancy)
         args = (logits, symbols_i, ranges_i, termination_symbol, boundary_i)   # the verdict on the ranges travels with them
-    loss = rnnt_loss_pruned(*args, rnnt_type=rnnt_type, delay_penalty=delay_penalty, reduction=reduction)
-    kd = rnnt_kd_loss_pruned(args[0], teacher_logits, *args[1:], mode=mode, temperature=temperature, reduction=reduction)
+    loss = _pruned_loss(*args, rnnt_type, delay_penalty, reduction, hat)
+    if occupancy:
+        w = rnnt_node_occupancy_pruned(*args, factorization=factorization, rnnt_type=rnnt_type, delay_penalty=delay_penalty)
+    kd = rnnt_kd_loss_pruned_factored(args[0], teacher_logits, *args[1:], factorization=factorization, mode=mode,
+                                      temperature=temperature, node_weights=w, reduction=reduction)
     return loss, kd
 
 
@@ -1636,17 +1661,11 @@ def rnnt_node_occupancy_pruned(
         penalty = _penalty(delay_penalty)
         if rnnt_type != "constrained" and _band_path_ok(ranges, boundary, T, S, r):
             dev = x.device
-            lse, pxb, pyb, gxb, gyb = (torch.empty((B, T, r), dtype=torch.float32, device=dev) for _ in range(5))
-            ans = torch.empty((B,), dtype=torch.float32, device=dev)
+            lse, pxb, pyb = (torch.empty((B, T, r), dtype=torch.float32, device=dev) for _ in range(3))
             with torch.cuda.device(dev):
-                st = _stream_ptr(x)
                 _pruned_call("pruned_band_fwd", hat, x, (_ptr(symbols), _ptr(ranges), _ptr(boundary), int(termination_symbol),
-                             penalty, _ptr(lse), _ptr(pxb), _ptr(pyb), B, T, S, C, r, int(modified)), (st,))
-                nws = _lib.lib().ftr_mutual_information_band_workspace_floats(B, T, S, r)
-                bws = torch.empty((nws,), dtype=torch.float32, device=dev) if nws else None
-                _lib.call("ftr_mutual_information_band_ws_f32", _ptr(pxb), _ptr(pyb), _ptr(ranges), _ptr(boundary), _ptr(bws),
-                          nws, _ptr(ans), _ptr(gxb), _ptr(gyb), B, T, S, r, int(modified), st)
-                del bws
+                             penalty, _ptr(lse), _ptr(pxb), _ptr(pyb), B, T, S, C, r, int(modified)), (_stream_ptr(x),))
+            _, gxb, gyb = band_forward_backward(pxb, pyb, ranges, S, boundary, modified)
             return _band_occupancy(gxb, gyb, ranges, boundary, S)
         if rnnt_type == "constrained":
             _, px, py = _pruned_builder_fwd(x, symbols, ranges, boundary, termination_symbol, 0.0, modified, hat)
@@ -1655,67 +1674,6 @@ def rnnt_node_occupancy_pruned(
             _, px, py = _pruned_builder_fwd(x, symbols, ranges, boundary, termination_symbol, penalty, modified, hat)
         _, px_grad, py_grad = mi_forward_backward(px, py, boundary, True, ans_grad_is_one=True)
         return _lattice_occupancy(px_grad, py_grad, ranges, boundary, S)
-
-
-class _PrunedLossKdFact(torch.autograd.Function):
-    """_PrunedLossKd for the entries of include/ftr_kd_loss_fact.h: a HAT row (``fact``), node weights (``weights``), or the
-    student's own occupancies as weights (``occupancy``): then the row kernel runs without weights and without utterance
-    sums, the occupancies are formed from what the band recursion returned, they weight the node losses in the utterance
-    sums' own tree, and the backward takes them as its weights."""
-
-    @staticmethod
-    def forward(ctx, logits, teacher_logits, symbols, ranges, termination_symbol, boundary, mode, temperature, modified,
-                delay_penalty, code, fact, weights, occupancy):
-        B, T, r, C = logits.shape
-        S = symbols.shape[1]
-        x = logits.detach().contiguous()
-        y = teacher_logits.detach().contiguous()
-        dev = x.device
-        band = lambda: torch.empty((B, T, r), dtype=torch.float32, device=dev)
-        lse, pxb, pyb, gxb, gyb, node = band(), band(), band(), band(), band(), band()
-        saved = torch.empty((4 if mode == _lib.FTR_KD_COLLAPSED else 2, B, T, r), dtype=torch.float32, device=dev)
-        utt = torch.empty((B,), dtype=torch.float32, device=dev)
-        ans = torch.empty((B,), dtype=torch.float32, device=dev)
-        kd = utt
-        with torch.cuda.device(dev):
-            st = _stream_ptr(x)
-            _lib.call("ftr_pruned_band_kd_fact_fwd_dt", *_kd_head(x, y), _ptr(symbols), _ptr(ranges), _ptr(boundary),
-                      int(termination_symbol), float(temperature), mode, float(delay_penalty), int(modified), _ptr(lse),
-                      _ptr(pxb), _ptr(pyb), _ptr(node), _ptr(saved), None if occupancy else _ptr(utt), B, T, S, C, r, fact,
-                      _ptr(weights), st)
-            nws = _lib.lib().ftr_mutual_information_band_workspace_floats(B, T, S, r)   # 0: the LDS-resident kernel
-            bws = torch.empty((nws,), dtype=torch.float32, device=dev) if nws else None
-            _lib.call("ftr_mutual_information_band_ws_f32", _ptr(pxb), _ptr(pyb), _ptr(ranges), _ptr(boundary), _ptr(bws),
-                      nws, _ptr(ans), _ptr(gxb), _ptr(gyb), B, T, S, r, int(modified), st)
-            del bws
-            if occupancy:
-                weights = _band_occupancy(gxb, gyb, ranges, boundary, S)
-                _lib.call("ftr_pruned_kd_weighted_utt_sum_f32", _ptr(node), _ptr(weights), _ptr(utt), B, T, r, st)
-            if code != 0:
-                kd = torch.empty((), dtype=torch.float32, device=dev)
-                _lib.call("ftr_pruned_kd_reduce_f32", _ptr(utt), B, code, _ptr(kd), st)
-        del pxb, pyb, node
-        if logits.requires_grad:
-            ctx.save_for_backward(x, y, symbols, ranges, lse, gxb, gyb, saved, boundary, weights)
-        ctx.meta = (int(termination_symbol), mode, float(temperature), int(code), fact)
-        ctx.set_materialize_grads(False)      # a part nobody differentiates arrives as None and is not read at all
-        return _negated_reduce_native(ans, code), kd
-
-    @staticmethod
-    def backward(ctx, g_loss, g_kd):
-        x, y, symbols, ranges, lse, gxb, gyb, saved, boundary, weights = ctx.saved_tensors
-        blank, mode, temperature, code, fact = ctx.meta
-        B, T, r, C = x.shape
-        if g_loss is None and g_kd is None:
-            return (None,) * 14
-        ls, lstride, lmul = _upstream_scale(g_loss, code, B) if g_loss is not None else (None, 0, 0.0)
-        ks, kstride, kmul = _upstream_scale(g_kd, code, B) if g_kd is not None else (None, 0, 0.0)
-        g = torch.empty_like(x)
-        with torch.cuda.device(x.device):
-            _lib.call("ftr_pruned_band_kd_fact_bwd_scaled_dt", *_kd_head(x, y), _ptr(symbols), _ptr(ranges), _ptr(boundary),
-                      blank, temperature, mode, _ptr(lse), _ptr(gxb), _ptr(gyb), _ptr(ls), lstride, lmul, _ptr(saved), _ptr(ks),
-                      kstride, -kmul, _ptr(g), B, T, symbols.shape[1], C, r, fact, _ptr(weights), _stream_ptr(x))
-        return (g,) + (None,) * 13
 
 
 def rnnt_loss_pruned_kd_factored(
@@ -1771,34 +1729,8 @@ def rnnt_loss_pruned_kd_factored(
     occupancy = isinstance(node_weights, str)
     if occupancy and node_weights != "occupancy":
         raise ValueError(f"node_weights should be None, a float32 [B,T,s_range] tensor or 'occupancy', given '{node_weights}'")
-    hat = factorization == "hat"
-    if not hat and node_weights is None:
-        return rnnt_loss_pruned_kd(logits, teacher_logits, symbols, ranges, termination_symbol, boundary, mode=mode,
-                                   temperature=temperature, rnnt_type=rnnt_type, delay_penalty=delay_penalty, reduction=reduction)
-    w = None if occupancy else node_weights
-    args = (logits, symbols, ranges, termination_symbol, boundary)
-    fused = rnnt_type != "constrained" and isinstance(logits, torch.Tensor) and isinstance(teacher_logits, torch.Tensor) \
-        and logits.dtype in _KD_DTYPES and teacher_logits.dtype in _KD_DTYPES and logits.dim() == 4 \
-        and tuple(teacher_logits.shape) == tuple(logits.shape) and logits.is_cuda and teacher_logits.is_cuda \
-        and teacher_logits.device == logits.device and mode in _KD_MODES and reduction in _REDUCTIONS \
-        and 0.0 < float(temperature) < float("inf") and 0 <= int(termination_symbol) < logits.shape[3] \
-        and not (hat and logits.shape[3] < 2) and (w is None or (isinstance(w, torch.Tensor) and w.dtype == torch.float32 and w.device == logits.device
-                           and tuple(w.shape) == tuple(logits.shape[:3])))
-    if fused:   # everything the composed functions would refuse is refused by them below, in their words
-        symbols_i, ranges_i, boundary_i = _pruned_inputs(logits, symbols, ranges, boundary, lowp=True)
-        B, T, r, C = logits.shape
-        if _band_path_ok(ranges_i, boundary_i, T, symbols_i.shape[1], r):
-            return _PrunedLossKdFact.apply(logits, teacher_logits, symbols_i, ranges_i, int(termination_symbol), boundary_i,
-                                           _KD_MODES[mode], float(temperature), rnnt_type != "regular", _penalty(delay_penalty),
-                                           _REDUCTIONS[reduction], _KD_FACTORIZATIONS[factorization],
-                                           None if w is None else w.detach().contiguous(), occupancy)
-        args = (logits, symbols_i, ranges_i, termination_symbol, boundary_i)   # the verdict on the ranges travels with them
-    loss = _pruned_loss(*args, rnnt_type, delay_penalty, reduction, hat)
-    if occupancy:
-        w = rnnt_node_occupancy_pruned(*args, factorization=factorization, rnnt_type=rnnt_type, delay_penalty=delay_penalty)
-    kd = rnnt_kd_loss_pruned_factored(args[0], teacher_logits, *args[1:], factorization=factorization, mode=mode,
-                                      temperature=temperature, node_weights=w, reduction=reduction)
-    return loss, kd
+    return _loss_pruned_kd(logits, teacher_logits, symbols, ranges, termination_symbol, boundary, factorization, mode, temperature,
+                           node_weights, rnnt_type, delay_penalty, reduction)
 
 
 # ---- multi-blank transducer (MI355X addition, no reference counterpart): big blanks that advance several frames
@@ -2309,15 +2241,7 @@ class _TdtMixedLoss(torch.autograd.Function):
         if ctx.band:
             if tdt:
                 ans_tdt, gx, gy = band_tdt_forward_backward(px, py, ranges, S, durs, blank_durs, boundary, need)
-            gx0 = torch.empty((B, T, r), dtype=torch.float32, device=x.device)
-            gy0 = torch.empty((B, T, r), dtype=torch.float32, device=x.device)
-            ans0 = torch.empty((B,), dtype=torch.float32, device=x.device)
-            with torch.cuda.device(x.device):
-                nws = _lib.lib().ftr_mutual_information_band_workspace_floats(B, T, S, r)   # 0: the LDS-resident kernel
-                bws = torch.empty((nws,), dtype=torch.float32, device=x.device) if nws else None
-                _lib.call("ftr_mutual_information_band_ws_f32", _ptr(px0), _ptr(py0), _ptr(ranges), _ptr(boundary), _ptr(bws),
-                          nws, _ptr(ans0), _ptr(gx0), _ptr(gy0), B, T, S, r, 0, _stream_ptr(x))
-                del bws
+            ans0, gx0, gy0 = band_forward_backward(px0, py0, ranges, S, boundary, 0)
         else:
             if tdt:
                 ans_tdt, gx, gy = tdt_forward_backward(px, py, durs, blank_durs, boundary, need)
