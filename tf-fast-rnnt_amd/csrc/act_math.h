@@ -47,8 +47,16 @@ __device__ __forceinline__ float act_tanh(float z) {
 // NaN stays NaN (z < 0 is false for it), as torch.relu
 __device__ __forceinline__ float act_relu(float z) { return z < 0.0f ? 0.0f : z; }
 
+// no activation: what the gather-sum kernels of prune.hip are instantiated with for the plain sum (include/ftr_prune_sum.h).
+// Internal to csrc, not an FTR_ACT_* code: the entries of capi.hip go on refusing everything but tanh and relu.
+constexpr int ACT_NONE = 0;
+static_assert(ACT_NONE != FTR_ACT_TANH && ACT_NONE != FTR_ACT_RELU, "ACT_NONE must not be a public activation code");
+
 template <int ACT>
-__device__ __forceinline__ float act_fwd(float z) { return ACT == FTR_ACT_TANH ? act_tanh(z) : act_relu(z); }
+__device__ __forceinline__ float act_fwd(float z) {
+  if constexpr (ACT == ACT_NONE) return z;
+  else return ACT == FTR_ACT_TANH ? act_tanh(z) : act_relu(z);
+}
 template <int ACT>
 __device__ __forceinline__ f4 act_fwd4(f4 z) {
   f4 y;
@@ -57,9 +65,11 @@ __device__ __forceinline__ f4 act_fwd4(f4 z) {
   return y;
 }
 
-// dz = g act'(y).  tanh: three separately rounded float32 operations (never an fma); relu: torch's rule, a NaN y passes g
+// dz = g act'(y).  tanh: three separately rounded float32 operations (never an fma); relu: torch's rule, a NaN y passes g;
+// none: g, whatever y is
 template <int ACT>
 __device__ __forceinline__ float act_dz(float g, float y) {
+  if (ACT == ACT_NONE) return g;
   if (ACT == FTR_ACT_TANH) return __fmul_rn(g, __fsub_rn(1.0f, __fmul_rn(y, y)));
   return y <= 0.0f ? 0.0f : g;
 }

@@ -284,11 +284,13 @@ size_t do_pruning_bwd_workspace_bytes(int B, int T, int S1, int C, int r);
 int do_pruning_bwd_ws(const float* g_am_p, const float* g_lm_p, const int32_t* ranges, float* d_am, float* d_lm, int B, int T, int S1, int C, int r, void* ws, size_t ws_bytes, hipStream_t st);
 int do_pruning_bwd(const float* g_am_p, const float* g_lm_p, const int32_t* ranges, float* d_am, float* d_lm, int B, int T, int S1, int C, int r, hipStream_t st);
 // the gather fused with the joiner's addition (include/ftr_prune_sum.h); dtype: the element type of am / lm / out and of g / d_am / d_lm.
-// do_pruning_sum_bwd_ws takes the routes of do_pruning_bwd_ws with one g for both inputs, and its workspace
+// do_pruning_sum_bwd_ws takes the routes of do_pruning_bwd_ws with one g for both inputs, and its workspace: float32 through the
+// do_pruning_bwd_* kernels themselves, a 16-bit type through gather_sum_bwd_* with no activation (prune.hip)
 int do_pruning_sum(const void* am, const void* lm, int dtype, const int32_t* ranges, void* out, int B, int T, int S1, int C, int r, hipStream_t st);
 int do_pruning_sum_bwd_ws(const void* g, int dtype, const int32_t* ranges, void* d_am, void* d_lm, int B, int T, int S1, int C, int r, void* ws, size_t ws_bytes, hipStream_t st);
 // the same with an activation behind the addition (include/ftr_joiner_act.h); act: FTR_ACT_*, validated by the caller.  The backward
-// forms dz from g and the forward's out as it loads them; routes and workspace of do_pruning_bwd_ws
+// forms dz from g and the forward's out as it loads them; routes and workspace of do_pruning_bwd_ws.  The same kernel family as the
+// sum (gather_sum_kernel, gather_sum_bwd_*), instantiated with the activation
 int pruned_joiner_act(const void* am, const void* lm, int dtype, int act, const int32_t* ranges, void* out, int B, int T, int S1, int C, int r, hipStream_t st);
 int pruned_joiner_act_bwd_ws(const void* g, const void* out, int dtype, int act, const int32_t* ranges, void* d_am, void* d_lm, int B, int T, int S1, int C, int r, void* ws, size_t ws_bytes, hipStream_t st);
 // hat != 0: the HAT normalisation (lse = non-blank normaliser Z, see pruned_logprobs.hip); hat == 0: the ordinary kernels
