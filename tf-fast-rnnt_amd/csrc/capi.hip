@@ -1,4 +1,4 @@
-// csrc/capi.hip -- the extern "C" surface declared in include/ftr.h, include/ftr_lowp.h, include/ftr_prune_sum.h, include/ftr_joiner_act.h, include/ftr_kd.h, include/ftr_kd_fact.h, include/ftr_kd_loss.h, include/ftr_kd_topk.h, include/ftr_fused.h and include/ftr_live.h: argument validation and error reporting.  No
+// csrc/capi.hip -- the extern "C" surface declared in include/ftr.h, include/ftr_lowp.h, include/ftr_prune_sum.h, include/ftr_joiner_act.h, include/ftr_kd.h, include/ftr_kd_fact.h, include/ftr_kd_loss.h, include/ftr_kd_topk.h, include/ftr_kd_topk_teacher.h, include/ftr_fused.h and include/ftr_live.h: argument validation and error reporting.  No
 // allocation, no host synchronisation, no CPU fallback.  Built twice: into libftr_hip.so (the product: the symbols of
 // ftr.h and ftr_lowp.h and nothing else) and, with -DFTR_DIAG, into the test-only _build/libftr_hip_diag.so, which adds the symbols of
 // include/ftr_diag.h: the "plain" kernel family (the reference's arithmetic on the device, mi_plain.hip), its
@@ -1677,6 +1677,21 @@ int ftr_pruned_kd_topk_bwd_scaled_dt(const void* logits, int kind, const void* t
   return pruned_kd_topk_bwd(logits, kind, teacher_values, teacher_kind, teacher_indices, ranges, teacher_ranges, boundary,
                             teacher_rest, node_weights, temperature, saved, Scale{scale, scale_stride, scale_mul}, glogits, B, T, S,
                             C, r, r_t, K, stream_of(stream));
+}
+
+// ---- include/ftr_kd_topk_teacher.h: the cache those entries read, written in one pass (csrc/kd_topk_teacher.hip)
+int ftr_kd_teacher_topk_dt(const void* logits, int kind, const int32_t* boundary, void* values, int32_t* indices, float* rest,
+                           float temperature, int B, int T, int r, long long rows, int C, int K, void* stream) {
+  const char* what = "kd_teacher_topk_dt";
+  clear_error();
+  FTR_TRY(check_dtype(what, kind, 0));
+  FTR_REQUIRE(C >= 1, "%s: C = %d, a row needs at least one column", what, C);
+  FTR_REQUIRE(K >= 1 && K <= FTR_KD_TOPK_MAX_K && K <= C, "%s: K = %d not in [1,min(C = %d, %d)]", what, K, C, FTR_KD_TOPK_MAX_K);
+  FTR_REQUIRE(temperature > 0.0f && temperature <= 3.0e38f, "%s: temperature %g is not a finite number > 0", what, (double)temperature);
+  FTR_TRY(check_sizes(what, rows >= 0 && (!boundary || (B >= 0 && T >= 1 && r >= 1 && rows == (long long)B * T * r))));
+  if (rows == 0) return FTR_OK;
+  FTR_TRY(pointers_then_device(what, logits && values && indices));
+  return kd_teacher_topk(logits, kind, boundary, values, indices, rest, temperature, T, r, (size_t)rows, C, K, stream_of(stream));
 }
 
 int ftr_selftest(void* scratch_dev, void* stream) {

@@ -8,6 +8,7 @@
 #include "../../include/ftr_kd_loss.h"
 #include "../../include/ftr_kd_loss_fact.h"
 #include "../../include/ftr_kd_topk.h"
+#include "../../include/ftr_kd_topk_teacher.h"
 #include "../../include/ftr_prune_sum.h"
 #include "../../include/ftr_joiner_act.h"
 #include "../../include/ftr_fused.h"
@@ -329,6 +330,8 @@ int kd_utt_sum(const float* node, float* utt, int B, int per, hipStream_t st);  
 // the same loss from a stored top-K teacher on the teacher's own band: csrc/pruned_kd_topk.hip (include/ftr_kd_topk.h; tranges NULL: the student's ranges; rest, weights: NULL or [B,T,r_t] / [B,T,r]; saved: 3 planes of [B,T,r])
 int pruned_kd_topk_fwd(const void* logits, int dtype, const void* tvalues, int teacher_dtype, const int32_t* tindices, const int32_t* ranges, const int32_t* tranges, const int32_t* boundary, const float* rest, const float* weights, float temperature, float* node, float* saved, float* utt, int B, int T, int S, int C, int r, int rt, int K, hipStream_t st);
 int pruned_kd_topk_bwd(const void* logits, int dtype, const void* tvalues, int teacher_dtype, const int32_t* tindices, const int32_t* ranges, const int32_t* tranges, const int32_t* boundary, const float* rest, const float* weights, float temperature, const float* saved, Scale scale, void* glogits, int B, int T, int S, int C, int r, int rt, int K, hipStream_t st);
+// the cache those two read, written in one pass: csrc/kd_topk_teacher.hip (include/ftr_kd_topk_teacher.h; boundary NULL: every row; rest NULL: not wanted; T, r: read with a boundary only)
+int kd_teacher_topk(const void* logits, int dtype, const int32_t* boundary, void* values, int32_t* indices, float* rest, float temperature, int T, int r, size_t rows, int C, int K, hipStream_t st);
 int lse_rows(const float* logits, float* lse, size_t rows, int C, int blank, int hat, hipStream_t st);
 int lse_rows_dtype(const void* logits, int dtype, float* lse, size_t rows, int C, int blank, int hat, hipStream_t st);
 int mi_band_supported(int T, int S, int r);

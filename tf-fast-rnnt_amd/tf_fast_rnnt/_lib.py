@@ -156,6 +156,11 @@ _KD_TOPK_SIGNATURES = {
     "ftr_pruned_kd_topk_fwd_dt": (_i, [_c_fp, _i, _c_fp, _i, _c_ip, _c_ip, _c_ip, _c_ip, _c_fp, _c_fp, _f, _c_fp, _c_fp, _c_fp, _i, _i, _i, _i, _i, _i, _i, _c_st]),
     "ftr_pruned_kd_topk_bwd_scaled_dt": (_i, [_c_fp, _i, _c_fp, _i, _c_ip, _c_ip, _c_ip, _c_ip, _c_fp, _c_fp, _f, _c_fp, _c_fp, _i, _f, _c_fp, _i, _i, _i, _i, _i, _i, _i, _c_st]),
 }
+# include/ftr_kd_topk_teacher.h, the one-pass writer of that cache: (logits, kind, boundary, values, indices, rest, temperature, B, T,
+# r, rows, C, K, stream)
+_KD_TOPK_TEACHER_SIGNATURES = {
+    "ftr_kd_teacher_topk_dt": (_i, [_c_fp, _i, _c_ip, _c_fp, _c_ip, _c_fp, _f, _i, _i, _i, ctypes.c_longlong, _i, _i, _c_st]),
+}
 # include/ftr_fused.h, the fused d am kernel with W as an operand: the arguments of ftr_*_logprobs_fused_bwd_am_f32 with W in place
 # of prod (and no combined scale: W carries it)
 _FUSED_SIGNATURES = {
@@ -214,6 +219,7 @@ KD_FACT_SYMBOLS = tuple(_KD_FACT_SIGNATURES)     # those of include/ftr_kd_fact.
 KD_LOSS_SYMBOLS = tuple(_KD_LOSS_SIGNATURES)     # those of include/ftr_kd_loss.h
 KD_LOSS_FACT_SYMBOLS = tuple(_KD_LOSS_FACT_SIGNATURES)   # those of include/ftr_kd_loss_fact.h
 KD_TOPK_SYMBOLS = tuple(_KD_TOPK_SIGNATURES)     # those of include/ftr_kd_topk.h
+KD_TOPK_TEACHER_SYMBOLS = tuple(_KD_TOPK_TEACHER_SIGNATURES)   # those of include/ftr_kd_topk_teacher.h
 FUSED_SYMBOLS = tuple(_FUSED_SIGNATURES)         # those of include/ftr_fused.h
 LIVE_SYMBOLS = tuple(_LIVE_SIGNATURES)           # those of include/ftr_live.h
 BAND_TDT_SYMBOLS = tuple(_BAND_TDT_SIGNATURES)   # those of include/ftr_band_tdt.h
@@ -242,7 +248,7 @@ def lib() -> ctypes.CDLL:
                 f"{LIB_PATH} is missing: build the HIP extension first (python -c 'import __graft_entry__ as g; "
                 "g.build()' or make -C tf-fast-rnnt_amd/csrc).  tf_fast_rnnt has no CPU fallback.")
         handle = ctypes.CDLL(LIB_PATH)
-        for name, (restype, argtypes) in {**_SIGNATURES, **_LOWP_SIGNATURES, **_PRUNE_SUM_SIGNATURES, **_JOINER_ACT_SIGNATURES, **_KD_SIGNATURES, **_KD_FACT_SIGNATURES, **_KD_LOSS_SIGNATURES, **_KD_LOSS_FACT_SIGNATURES, **_KD_TOPK_SIGNATURES, **_FUSED_SIGNATURES, **_LIVE_SIGNATURES,
+        for name, (restype, argtypes) in {**_SIGNATURES, **_LOWP_SIGNATURES, **_PRUNE_SUM_SIGNATURES, **_JOINER_ACT_SIGNATURES, **_KD_SIGNATURES, **_KD_FACT_SIGNATURES, **_KD_LOSS_SIGNATURES, **_KD_LOSS_FACT_SIGNATURES, **_KD_TOPK_SIGNATURES, **_KD_TOPK_TEACHER_SIGNATURES, **_FUSED_SIGNATURES, **_LIVE_SIGNATURES,
                                             **_BAND_TDT_SIGNATURES, **_TDT_MIX_SIGNATURES, **_BAND_MULTIBLANK_SIGNATURES, **_BAND_VITERBI_SIGNATURES}.items():
             fn = getattr(handle, name)   # AttributeError here = header/library mismatch
             fn.restype = restype

@@ -18,7 +18,8 @@ What runs where:
   stream kernels of its own (include/ftr_kd.h, csrc/pruned_kd.hip); ``rnnt_kd_loss_pruned_factored``: the same for HAT and
   TDT rows and with node weights (include/ftr_kd_fact.h, the same kernels in their other two row forms);
   ``rnnt_kd_loss_pruned_topk``: the same loss from a stored top-K teacher on the teacher's own ranges (include/ftr_kd_topk.h,
-  csrc/pruned_kd_topk.hip), ``rnnt_kd_topk_teacher`` (plain torch) writes that cache.
+  csrc/pruned_kd_topk.hip), ``rnnt_kd_topk_teacher`` (plain torch) writes that cache, ``rnnt_kd_topk_cache`` writes it in one
+  pass of one HIP kernel (include/ftr_kd_topk_teacher.h, csrc/kd_topk_teacher.hip).
 
 Reference bugs that are NOT reproduced: ``rnnt_loss_simple(reduction="mean")``
 raises NameError there (rnnt_loss.py:331) -- here it is the mean; ``boundary=None`` works; the
@@ -1440,6 +1441,48 @@ def rnnt_kd_topk_teacher(teacher_logits: torch.Tensor, k: int, temperature: floa
             others = (teacher_logits.to(torch.float32) / temperature).scatter(-1, idx, _NEG_INF)
             rest = torch.logsumexp(others, dim=-1)
     return values, idx.to(torch.int32), rest
+
+
+def rnnt_kd_topk_cache(teacher_logits: torch.Tensor, k: int, temperature: float = 1.0, with_rest: bool = True,
+                       boundary: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor, Optional[torch.Tensor]]:
+    """The cache of ``rnnt_kd_topk_teacher`` in ONE pass of one HIP kernel over the teacher's logits (include/
+    ftr_kd_topk_teacher.h, csrc/kd_topk_teacher.hip; MI355X addition): for a teacher that runs next to the student and
+    rewrites its cache every step.  ``teacher_logits`` [..., C] float32, bfloat16 or float16 on the GPU (made contiguous; a
+    16-bit tensor means its exact float32 values), 1 <= k <= min(C, 64), temperature > 0.  Returns ``(values, indices,
+    rest)``: ``values`` [..., k] in the dtype of the logits, the selected elements themselves, bit for bit; ``indices``
+    [..., k] int32, their columns, distinct, in [0, C); ``rest`` [...] float32 (None without ``with_rest``), the float32
+    logsumexp of ``x[c] / temperature`` over the columns that were not selected, against its own maximum: exactly -inf when
+    k = C or all of them are -inf, NaN when one is NaN, else +inf when one is +inf.
+
+    The order is defined completely, so the cache is the same bits on every run: elements are taken in descending order of
+    value compared as float32, -0.0 and +0.0 equal, every NaN above +inf (``torch.topk``'s rule) and equal to every other
+    NaN, and among equal elements the lower column first; slot j holds the j-th element of that order.
+    (``rnnt_kd_topk_teacher`` leaves ties to ``torch.topk``.)
+
+    ``boundary`` (None or [B,4], only with a 4-D ``teacher_logits`` [B,T,r_t,C]): the rows of the frames t < t_begin or
+    t >= t_end are never read and get the filler ``values = 0, indices[j] = j, rest = 0`` --
+    ``rnnt_kd_loss_pruned_topk`` never reads those nodes.  Launches only, no workspace (capturable in a graph); no
+    gradient."""
+    _check_kd_dtype("teacher_logits", teacher_logits)
+    k = int(k)
+    C = teacher_logits.shape[-1]
+    if not 1 <= k <= min(C, _lib.FTR_KD_TOPK_MAX_K):
+        raise ValueError(f"k = {k} must be in [1, min(C, {_lib.FTR_KD_TOPK_MAX_K})] for rows of C = {C}")
+    temperature = _check_temperature(temperature)
+    if boundary is not None and teacher_logits.dim() != 4:
+        raise ValueError(f"boundary needs teacher_logits [B,T,r_t,C], got {tuple(teacher_logits.shape)}")
+    _require_gpu(teacher_logits, "teacher_logits")
+    x = teacher_logits.detach().contiguous()
+    lead = tuple(x.shape[:-1])
+    B, T, r = lead if boundary is not None else (0, 0, 0)
+    boundary = _as_boundary(boundary, B, x.device)
+    values = torch.empty(lead + (k,), dtype=x.dtype, device=x.device)
+    indices = torch.empty(lead + (k,), dtype=torch.int32, device=x.device)
+    rest = torch.empty(lead, dtype=torch.float32, device=x.device) if with_rest else None
+    with torch.cuda.device(x.device):
+        _lib.call("ftr_kd_teacher_topk_dt", _ptr(x), _LOWP_KIND.get(x.dtype, _lib.FTR_DTYPE_F32), _ptr(boundary), _ptr(values),
+                  _ptr(indices), _ptr(rest), temperature, B, T, r, x.numel() // C, C, k, _stream_ptr(x))
+    return values, indices, rest
 
 
 class _PrunedLossKd(torch.autograd.Function):
