@@ -1,4 +1,4 @@
-// csrc/capi.hip -- the extern "C" surface declared in include/ftr.h, include/ftr_lowp.h, include/ftr_prune_sum.h, include/ftr_joiner_act.h, include/ftr_kd.h, include/ftr_kd_fact.h, include/ftr_kd_loss.h, include/ftr_kd_topk.h, include/ftr_kd_topk_teacher.h, include/ftr_fused.h and include/ftr_live.h: argument validation and error reporting.  No
+// csrc/capi.hip -- the extern "C" surface declared in include/ftr.h, include/ftr_lowp.h, include/ftr_prune_sum.h, include/ftr_joiner_act.h, include/ftr_kd.h, include/ftr_kd_fact.h, include/ftr_kd_loss.h, include/ftr_kd_topk.h, include/ftr_kd_topk_teacher.h, include/ftr_fused.h, include/ftr_live.h and include/ftr_band_constrained.h: argument validation and error reporting.  No
 // allocation, no host synchronisation, no CPU fallback.  Built twice: into libftr_hip.so (the product: the symbols of
 // ftr.h and ftr_lowp.h and nothing else) and, with -DFTR_DIAG, into the test-only _build/libftr_hip_diag.so, which adds the symbols of
 // include/ftr_diag.h: the "plain" kernel family (the reference's arithmetic on the device, mi_plain.hip), its
@@ -930,6 +930,46 @@ int ftr_pruned_band_bwd_scaled_dt(const void* logits, int kind, const int32_t* s
   clear_error();
   FTR_TRY(check_dtype("pruned_band_bwd_scaled_dt", kind, flags));
   return pruned_band_bwd_scaled_entry(logits, kind, symbols, ranges, boundary, termination_symbol, lse, gx_band, gy_band, scale, scale_stride, scale_mul, glogits, B, T, S, C, r, modified, flags & FTR_PRUNED_HAT, stream);
+}
+
+// ---- include/ftr_band_constrained.h: the constrained type on the pruned band (csrc/pruned_constrained.hip).  The order of
+// ftr_pruned_band_fwd_dt / _bwd_scaled_dt, with the domain of the frame-group kernel (one wave per band row) behind the sizes
+static int check_constrained_rows(const char* what, int r) {
+  if (r <= 15) return FTR_OK;
+  set_error("%s: s_range %d is outside the kernel's domain (r <= 15)", what, r);
+  return FTR_ERR_UNSUPPORTED;
+}
+
+int ftr_pruned_band_constrained_fwd_dt(const void* logits, int kind, const int32_t* symbols, const int32_t* ranges,
+                                       const int32_t* boundary, int termination_symbol, double delay_penalty, float* lse,
+                                       float* px_band, float* py_band, int B, int T, int S, int C, int r, int flags,
+                                       void* stream) {
+  const int hat = flags & FTR_PRUNED_HAT;
+  const char* what = hat ? "hat_pruned_band_constrained_fwd" : "pruned_band_constrained_fwd";
+  clear_error();
+  FTR_TRY(check_dtype("pruned_band_constrained_fwd_dt", kind, flags));
+  FTR_TRY(check_builder(what, B >= 0 && T >= 1 && S >= 0 && C >= 1 && r >= 1, termination_symbol, C, false, hat));
+  FTR_TRY(check_constrained_rows(what, r));
+  if (B == 0) return FTR_OK;
+  FTR_TRY(pointers_then_device(what, logits && ranges && lse && px_band && py_band && (symbols || S == 0)));
+  return band_constrained_fwd(logits, kind, symbols, ranges, boundary, termination_symbol, delay_penalty, lse, px_band, py_band, B, T, S, C, r, hat, stream_of(stream));
+}
+
+int ftr_pruned_band_constrained_bwd_scaled_dt(const void* logits, int kind, const int32_t* symbols, const int32_t* ranges,
+                                              const int32_t* boundary, int termination_symbol, const float* lse,
+                                              const float* gx_band, const float* gy_band, const float* scale,
+                                              int scale_stride, float scale_mul, void* glogits, int B, int T, int S, int C,
+                                              int r, int flags, void* stream) {
+  const int hat = flags & FTR_PRUNED_HAT;
+  const char* what = hat ? "hat_pruned_band_constrained_bwd_scaled" : "pruned_band_constrained_bwd_scaled";
+  clear_error();
+  FTR_TRY(check_dtype("pruned_band_constrained_bwd_scaled_dt", kind, flags));
+  FTR_TRY(check_builder(what, B >= 0 && T >= 1 && S >= 0 && C >= 1 && r >= 1, termination_symbol, C, true, hat));
+  FTR_TRY(check_constrained_rows(what, r));
+  FTR_TRY(check_scale_stride(what, scale_stride));
+  if (B == 0) return FTR_OK;
+  FTR_TRY(pointers_then_device(what, logits && ranges && lse && gx_band && gy_band && glogits && (symbols || S == 0)));
+  return band_constrained_bwd(logits, kind, symbols, ranges, boundary, termination_symbol, lse, gx_band, gy_band, Scale{scale, scale_stride, scale_mul}, glogits, B, T, S, C, r, hat, stream_of(stream));
 }
 
 // ---- multi-blank transducer (MI355X addition; csrc/mi_multiblank.hip, the mb_* kernels of csrc/pruned_logprobs.hip).

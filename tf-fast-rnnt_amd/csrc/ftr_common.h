@@ -16,6 +16,7 @@
 #include "../../include/ftr_tdt_mix.h"
 #include "../../include/ftr_band_multiblank.h"
 #include "../../include/ftr_band_viterbi.h"
+#include "../../include/ftr_band_constrained.h"
 
 namespace ftr {
 
@@ -343,6 +344,9 @@ size_t mi_band_seg_workspace_floats(int B, int T, int S, int r);
 int mi_band_seg(const float* pxb, const float* pyb, const int32_t* ranges, const int32_t* boundary, float* ws, size_t ws_floats, float* ans, float* gxb, float* gyb, int B, int T, int S, int r, int modified, hipStream_t st);
 int mi_band(const float* pxb, const float* pyb, const int32_t* ranges, const int32_t* boundary, float* ws, size_t ws_floats, float* ans, float* gxb, float* gyb, int B, int T, int S, int r, int modified, hipStream_t st);
 int band_grad_banded(const void* logits, int dtype, const int32_t* symbols, const int32_t* ranges, const int32_t* boundary, int blank, const float* lse, const float* gxb, const float* gyb, Scale scale, void* glogits, int B, int T, int S, int C, int r, int modified, int hat, hipStream_t st);
+// the constrained type on the pruned band (include/ftr_band_constrained.h): csrc/pruned_constrained.hip
+int band_constrained_fwd(const void* logits, int dtype, const int32_t* symbols, const int32_t* ranges, const int32_t* boundary, int blank, double delay_penalty, float* lse, float* pxb, float* pyb, int B, int T, int S, int C, int r, int hat, hipStream_t st);
+int band_constrained_bwd(const void* logits, int dtype, const int32_t* symbols, const int32_t* ranges, const int32_t* boundary, int blank, const float* lse, const float* gxb, const float* gyb, Scale scale, void* glogits, int B, int T, int S, int C, int r, int hat, hipStream_t st);
 int selftest(hipStream_t st, int* result_dev);
 int debug_stamps(unsigned long long* out16);
 int debug_trace(unsigned long long* out, int n);

@@ -210,6 +210,12 @@ _BAND_VITERBI_SIGNATURES = {
     "ftr_mutual_information_band_viterbi_workspace_bytes": (ctypes.c_size_t, [_i, _i, _i, _i, _i, _i]),
     "ftr_mutual_information_band_viterbi_f32": (_i, [_c_fp, _c_fp, _c_ip, _c_ip, _c_hi, _i, _c_hi, _i, ctypes.c_void_p, ctypes.c_size_t, _c_fp, _c_ip, _c_ip, _c_ip, _i, _i, _i, _i, _c_st]),
 }
+# include/ftr_band_constrained.h, the constrained type on the pruned band: the frame-group builder and its gradient entry,
+# (logits, kind = FTR_DTYPE_*, ...the arguments of the _dt band builders without `modified`..., flags = FTR_PRUNED_HAT, stream)
+_BAND_CONSTRAINED_SIGNATURES = {
+    "ftr_pruned_band_constrained_fwd_dt": (_i, [_c_fp, _i, _c_ip, _c_ip, _c_ip, _i, ctypes.c_double, _c_fp, _c_fp, _c_fp, _i, _i, _i, _i, _i, _i, _c_st]),
+    "ftr_pruned_band_constrained_bwd_scaled_dt": (_i, [_c_fp, _i, _c_ip, _c_ip, _c_ip, _i, _c_fp, _c_fp, _c_fp, _c_fp, _i, _f, _c_fp, _i, _i, _i, _i, _i, _i, _c_st]),
+}
 EXPORTED_SYMBOLS = tuple(_SIGNATURES)            # the symbols of include/ftr.h
 LOWP_SYMBOLS = tuple(_LOWP_SIGNATURES)           # those of include/ftr_lowp.h
 PRUNE_SUM_SYMBOLS = tuple(_PRUNE_SUM_SIGNATURES) # those of include/ftr_prune_sum.h
@@ -226,6 +232,7 @@ BAND_TDT_SYMBOLS = tuple(_BAND_TDT_SIGNATURES)   # those of include/ftr_band_tdt
 TDT_MIX_SYMBOLS = tuple(_TDT_MIX_SIGNATURES)     # those of include/ftr_tdt_mix.h
 BAND_MULTIBLANK_SYMBOLS = tuple(_BAND_MULTIBLANK_SIGNATURES)   # those of include/ftr_band_multiblank.h
 BAND_VITERBI_SYMBOLS = tuple(_BAND_VITERBI_SIGNATURES)   # those of include/ftr_band_viterbi.h
+BAND_CONSTRAINED_SYMBOLS = tuple(_BAND_CONSTRAINED_SIGNATURES)   # those of include/ftr_band_constrained.h
 band_tdt_recursions = 0   # how many times the band-native TDT recursion has been launched from Python (tests read it)
 band_multiblank_recursions = 0   # ... and the band-native multi-blank recursion, likewise
 FTR_KD_FULL, FTR_KD_COLLAPSED = 0, 1             # include/ftr_kd.h: the `mode` of the kd entry points
@@ -249,7 +256,7 @@ def lib() -> ctypes.CDLL:
                 "g.build()' or make -C tf-fast-rnnt_amd/csrc).  tf_fast_rnnt has no CPU fallback.")
         handle = ctypes.CDLL(LIB_PATH)
         for name, (restype, argtypes) in {**_SIGNATURES, **_LOWP_SIGNATURES, **_PRUNE_SUM_SIGNATURES, **_JOINER_ACT_SIGNATURES, **_KD_SIGNATURES, **_KD_FACT_SIGNATURES, **_KD_LOSS_SIGNATURES, **_KD_LOSS_FACT_SIGNATURES, **_KD_TOPK_SIGNATURES, **_KD_TOPK_TEACHER_SIGNATURES, **_FUSED_SIGNATURES, **_LIVE_SIGNATURES,
-                                            **_BAND_TDT_SIGNATURES, **_TDT_MIX_SIGNATURES, **_BAND_MULTIBLANK_SIGNATURES, **_BAND_VITERBI_SIGNATURES}.items():
+                                            **_BAND_TDT_SIGNATURES, **_TDT_MIX_SIGNATURES, **_BAND_MULTIBLANK_SIGNATURES, **_BAND_VITERBI_SIGNATURES, **_BAND_CONSTRAINED_SIGNATURES}.items():
             fn = getattr(handle, name)   # AttributeError here = header/library mismatch
             fn.restype = restype
             fn.argtypes = argtypes

@@ -836,7 +836,8 @@ def rnnt_alignment_pruned(
     For ``rnnt_type="regular"``, when ``ranges`` are a band with ``s_range <= 15`` (the rule of ``rnnt_loss_pruned``,
     ``FTR_PRUNED_ROUTE=lattice`` included), no lattice is built: the band builder of the loss feeds
     ``mutual_information_viterbi_tdt_band`` with moves (0,) / (1,), which returns the same bits (see there for the one
-    deviation, the way a NaN travels).  Everything else takes the lattice route."""
+    deviation, the way a NaN travels).  ``rnnt_type="constrained"`` on such a band likewise: the frame-group builder of
+    the constrained loss (px_band = px'(k) + py(k+1)) and the moves (1,) / (1,).  Everything else takes the lattice route."""
     _check_type(rnnt_type)
     with torch.no_grad():
         symbols, ranges, boundary = _pruned_inputs(logits, symbols, ranges, boundary, lowp=True)
@@ -851,6 +852,10 @@ def rnnt_alignment_pruned(
                 _pruned_call("pruned_band_fwd", False, x, (_ptr(symbols), _ptr(ranges), _ptr(boundary), int(termination_symbol), 0.0,
                              _ptr(lse), _ptr(pxb), _ptr(pyb), B, T, S, C, r, 0), (_stream_ptr(x),))
             score, frames, _, _ = mutual_information_viterbi_tdt_band(pxb, pyb, ranges, (0,), (1,), boundary, S=S)
+            return score, frames
+        if rnnt_type == "constrained" and _align_band_path_ok(ranges, boundary, T, S, r, 1, 1):
+            _, pxb, pyb = _constrained_band_fwd(logits.detach().contiguous(), symbols, ranges, boundary, termination_symbol, 0.0, False)
+            score, frames, _, _ = mutual_information_viterbi_tdt_band(pxb.unsqueeze(1), pyb.unsqueeze(1), ranges, (1,), (1,), boundary, S=S)
             return score, frames
         _, px, py = _pruned_builder_fwd(logits.detach().contiguous(), symbols, ranges, boundary, termination_symbol, 0.0,
                                         rnnt_type != "regular", False)
@@ -984,6 +989,48 @@ class _PrunedLoss(torch.autograd.Function):
         return g, None, None, None, None, None, None, None, None
 
 
+def _constrained_band_fwd(x, symbols, ranges, boundary, blank, delay_penalty, hat):
+    """lse and the band operands of the constrained type, px_band = px'(k) + py(k+1), all [B,T,r]: one launch of the
+    frame-group kernel (include/ftr_band_constrained.h), one read of ``x``."""
+    B, T, r, C = x.shape
+    lse, pxb, pyb = (torch.empty((B, T, r), dtype=torch.float32, device=x.device) for _ in range(3))
+    with torch.cuda.device(x.device):
+        _lib.call("ftr_pruned_band_constrained_fwd_dt", _ptr(x), _LOWP_KIND.get(x.dtype, _lib.FTR_DTYPE_F32), _ptr(symbols),
+                  _ptr(ranges), _ptr(boundary), int(blank), float(delay_penalty), _ptr(lse), _ptr(pxb), _ptr(pyb),
+                  B, T, symbols.shape[1], C, r, _lib.FTR_PRUNED_HAT if hat else 0, _stream_ptr(x))
+    return lse, pxb, pyb
+
+
+class _PrunedLossConstrained(torch.autograd.Function):
+    """rnnt_loss_pruned / hat_loss_pruned for the constrained type on a band (the caller has asked _band_path_ok): the
+    frame-group builder -> the band recursion of the modified type (ftr_mutual_information_band_ws_f32) -> in backward() one
+    gradient launch that folds the forced blank of row k-1 into row k.  Nothing of size S * T exists."""
+
+    @staticmethod
+    def forward(ctx, logits, symbols, ranges, termination_symbol, boundary, delay_penalty, code, hat):
+        x = logits.detach().contiguous()
+        lse, pxb, pyb = _constrained_band_fwd(x, symbols, ranges, boundary, termination_symbol, delay_penalty, hat)
+        ans, gxb, gyb = band_forward_backward(pxb, pyb, ranges, symbols.shape[1], boundary, True)
+        del pxb, pyb
+        if logits.requires_grad:
+            ctx.save_for_backward(x, symbols, ranges, lse, gxb, gyb, boundary)
+        ctx.meta = (int(termination_symbol), int(code), bool(hat))
+        return _negated_reduce_native(ans, code)
+
+    @staticmethod
+    def backward(ctx, g_loss):
+        x, symbols, ranges, lse, gxb, gyb, boundary = ctx.saved_tensors
+        blank, code, hat = ctx.meta
+        B, T, r, C = x.shape
+        scale, stride, mul = _upstream_scale(g_loss, code, B)
+        g = torch.empty_like(x)
+        with torch.cuda.device(x.device):
+            _lib.call("ftr_pruned_band_constrained_bwd_scaled_dt", _ptr(x), _LOWP_KIND.get(x.dtype, _lib.FTR_DTYPE_F32),
+                      _ptr(symbols), _ptr(ranges), _ptr(boundary), blank, _ptr(lse), _ptr(gxb), _ptr(gyb), _ptr(scale), stride,
+                      mul, _ptr(g), B, T, symbols.shape[1], C, r, _lib.FTR_PRUNED_HAT if hat else 0, _stream_ptr(x))
+        return g, None, None, None, None, None, None, None
+
+
 def rnnt_loss_pruned(
     logits: torch.Tensor,
     symbols: torch.Tensor,
@@ -996,7 +1043,11 @@ def rnnt_loss_pruned(
     calc_gradients: bool = False,
 ) -> torch.Tensor:
     """rnnt_loss.py:1022-1130.  Returns the loss only (``calc_gradients`` is accepted and, as in the
-    reference, only selects whether the op computes occupancies; here that follows ``requires_grad``)."""
+    reference, only selects whether the op computes occupancies; here that follows ``requires_grad``).
+
+    All three ``rnnt_type`` values take the band-native route (no S * T lattice, one gradient launch) when ``ranges`` are a
+    band with ``s_range <= 15``; "constrained" forms its operands frame by frame (include/ftr_band_constrained.h).  Any
+    other ranges, ``FTR_PRUNED_ROUTE=lattice`` and ranges of unknown content under stream capture go through the lattices."""
     return _pruned_loss(logits, symbols, ranges, termination_symbol, boundary, rnnt_type, delay_penalty, reduction, False)
 
 
@@ -1005,6 +1056,10 @@ def _pruned_loss(logits, symbols, ranges, termination_symbol, boundary, rnnt_typ
     code = _reduction_code(reduction)
     symbols_i, ranges_i, boundary_i = _pruned_inputs(logits, symbols, ranges, boundary, lowp=True)
     if rnnt_type == "constrained":
+        B, T, r, _ = logits.shape
+        if _band_path_ok(ranges_i, boundary_i, T, symbols_i.shape[1], r):     # band-native: no S * T lattice
+            return _PrunedLossConstrained.apply(logits, symbols_i, ranges_i, termination_symbol, boundary_i,
+                                                _penalty(delay_penalty), code, hat)
         px, py = _pruned_logprobs(logits, symbols_i, ranges_i, termination_symbol, boundary_i, rnnt_type, hat)
         px = _apply_delay_penalty(px, boundary_i, rnnt_type, delay_penalty)
         negated_loss = mutual_information_recursion(px=px, py=py, boundary=boundary_i, calc_gradients=False)
