@@ -1,4 +1,4 @@
-// csrc/capi.hip -- the extern "C" surface declared in include/ftr.h, include/ftr_lowp.h, include/ftr_prune_sum.h, include/ftr_joiner_act.h, include/ftr_kd.h, include/ftr_kd_fact.h, include/ftr_kd_loss.h, include/ftr_kd_topk.h, include/ftr_kd_topk_teacher.h, include/ftr_fused.h, include/ftr_live.h and include/ftr_band_constrained.h: argument validation and error reporting.  No
+// csrc/capi.hip -- the extern "C" surface declared in include/ftr.h, include/ftr_lowp.h, include/ftr_prune_sum.h, include/ftr_joiner_act.h, include/ftr_kd.h, include/ftr_kd_fact.h, include/ftr_kd_loss.h, include/ftr_kd_topk.h, include/ftr_kd_topk_teacher.h, include/ftr_fused.h, include/ftr_live.h, include/ftr_band_constrained.h and include/ftr_path.h: argument validation and error reporting.  No
 // allocation, no host synchronisation, no CPU fallback.  Built twice: into libftr_hip.so (the product: the symbols of
 // ftr.h and ftr_lowp.h and nothing else) and, with -DFTR_DIAG, into the test-only _build/libftr_hip_diag.so, which adds the symbols of
 // include/ftr_diag.h: the "plain" kernel family (the reference's arithmetic on the device, mi_plain.hip), its
@@ -970,6 +970,36 @@ int ftr_pruned_band_constrained_bwd_scaled_dt(const void* logits, int kind, cons
   if (B == 0) return FTR_OK;
   FTR_TRY(pointers_then_device(what, logits && ranges && lse && gx_band && gy_band && glogits && (symbols || S == 0)));
   return band_constrained_bwd(logits, kind, symbols, ranges, boundary, termination_symbol, lse, gx_band, gy_band, Scale{scale, scale_stride, scale_mul}, glogits, B, T, S, C, r, hat, stream_of(stream));
+}
+
+// ---- include/ftr_path.h: the log-probability of one given alignment on the pruned joiner output (csrc/pruned_path.hip)
+static int check_path_head(const char* dt_name, const char* what, int kind, int flags, int B, int T, int S, int C, int r, int blank) {
+  FTR_TRY(check_dtype(dt_name, kind, 0));
+  FTR_REQUIRE((flags & ~(FTR_PRUNED_HAT | FTR_PATH_MODIFIED)) == 0, "%s: unknown bits in flags %d", dt_name, flags);
+  return check_builder(what, B >= 0 && T >= 1 && S >= 0 && C >= 1 && r >= 1, blank, C, false, flags & FTR_PRUNED_HAT);
+}
+
+int ftr_pruned_path_logprob_fwd_dt(const void* logits, int kind, const int32_t* symbols, const int32_t* ranges,
+                                   const int32_t* boundary, const int32_t* frames, int termination_symbol, float* arc_lp,
+                                   float* arc_lse, float* logprob, int B, int T, int S, int C, int r, int flags, void* stream) {
+  const char* what = (flags & FTR_PRUNED_HAT) ? "hat_pruned_path_logprob_fwd" : "pruned_path_logprob_fwd";
+  clear_error();
+  FTR_TRY(check_path_head("pruned_path_logprob_fwd_dt", what, kind, flags, B, T, S, C, r, termination_symbol));
+  if (B == 0) return FTR_OK;
+  FTR_TRY(pointers_then_device(what, logits && ranges && arc_lp && arc_lse && logprob && ((symbols && frames) || S == 0)));
+  return pruned_path_fwd(logits, kind, symbols, ranges, boundary, frames, termination_symbol, arc_lp, arc_lse, logprob, B, T, S, C, r, (flags & FTR_PATH_MODIFIED) != 0, flags & FTR_PRUNED_HAT, stream_of(stream));
+}
+
+int ftr_pruned_path_logprob_bwd_dt(const void* logits, int kind, const int32_t* symbols, const int32_t* ranges,
+                                   const int32_t* boundary, const int32_t* frames, int termination_symbol,
+                                   const float* arc_lse, const float* logprob, const float* logprob_grad, void* glogits, int B,
+                                   int T, int S, int C, int r, int flags, void* stream) {
+  const char* what = (flags & FTR_PRUNED_HAT) ? "hat_pruned_path_logprob_bwd" : "pruned_path_logprob_bwd";
+  clear_error();
+  FTR_TRY(check_path_head("pruned_path_logprob_bwd_dt", what, kind, flags, B, T, S, C, r, termination_symbol));
+  if (B == 0) return FTR_OK;
+  FTR_TRY(pointers_then_device(what, logits && ranges && arc_lse && logprob && logprob_grad && glogits && ((symbols && frames) || S == 0)));
+  return pruned_path_bwd(logits, kind, symbols, ranges, boundary, frames, termination_symbol, arc_lse, logprob, logprob_grad, glogits, B, T, S, C, r, (flags & FTR_PATH_MODIFIED) != 0, flags & FTR_PRUNED_HAT, stream_of(stream));
 }
 
 // ---- multi-blank transducer (MI355X addition; csrc/mi_multiblank.hip, the mb_* kernels of csrc/pruned_logprobs.hip).

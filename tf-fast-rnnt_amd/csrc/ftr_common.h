@@ -17,6 +17,7 @@
 #include "../../include/ftr_band_multiblank.h"
 #include "../../include/ftr_band_viterbi.h"
 #include "../../include/ftr_band_constrained.h"
+#include "../../include/ftr_path.h"
 
 namespace ftr {
 
@@ -347,6 +348,9 @@ int band_grad_banded(const void* logits, int dtype, const int32_t* symbols, cons
 // the constrained type on the pruned band (include/ftr_band_constrained.h): csrc/pruned_constrained.hip
 int band_constrained_fwd(const void* logits, int dtype, const int32_t* symbols, const int32_t* ranges, const int32_t* boundary, int blank, double delay_penalty, float* lse, float* pxb, float* pyb, int B, int T, int S, int C, int r, int hat, hipStream_t st);
 int band_constrained_bwd(const void* logits, int dtype, const int32_t* symbols, const int32_t* ranges, const int32_t* boundary, int blank, const float* lse, const float* gxb, const float* gyb, Scale scale, void* glogits, int B, int T, int S, int C, int r, int hat, hipStream_t st);
+// one given alignment's log-probability under the pruned joiner and its gradient (include/ftr_path.h): csrc/pruned_path.hip
+int pruned_path_fwd(const void* logits, int dtype, const int32_t* symbols, const int32_t* ranges, const int32_t* boundary, const int32_t* frames, int blank, float* arc_lp, float* arc_lse, float* logprob, int B, int T, int S, int C, int r, int modified, int hat, hipStream_t st);
+int pruned_path_bwd(const void* logits, int dtype, const int32_t* symbols, const int32_t* ranges, const int32_t* boundary, const int32_t* frames, int blank, const float* arc_lse, const float* logprob, const float* upstream, void* glogits, int B, int T, int S, int C, int r, int modified, int hat, hipStream_t st);
 int selftest(hipStream_t st, int* result_dev);
 int debug_stamps(unsigned long long* out16);
 int debug_trace(unsigned long long* out, int n);

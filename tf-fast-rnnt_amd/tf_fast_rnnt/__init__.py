@@ -35,6 +35,7 @@ from .rnnt_loss import rnnt_loss_pruned_kd_factored, rnnt_node_occupancy_pruned 
 from .rnnt_loss import rnnt_kd_loss_pruned_topk, rnnt_kd_topk_teacher         # ... and from a stored top-K teacher on the teacher's own band
 from .rnnt_loss import rnnt_kd_topk_cache                                      # ... that cache written by one HIP row kernel, in one pass
 from .rnnt_loss import rnnt_alignment_pruned                      # MI355X addition: best-path alignment, see its docstring
+from .rnnt_loss import rnnt_path_logprob_pruned                   # MI355X addition: log-prob of a GIVEN alignment, one wave per arc
 from .rnnt_loss import rnnt_loss_simple
 from .rnnt_loss import rnnt_loss_smoothed
 from .rnnt_loss import tune_normalizer_gemms, normalizer_gemm_choice, set_normalizer_gemm_choice                # MI355X addition: library-GEMM kernel selection, see its docstring

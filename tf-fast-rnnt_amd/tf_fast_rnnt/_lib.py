@@ -216,6 +216,13 @@ _BAND_CONSTRAINED_SIGNATURES = {
     "ftr_pruned_band_constrained_fwd_dt": (_i, [_c_fp, _i, _c_ip, _c_ip, _c_ip, _i, ctypes.c_double, _c_fp, _c_fp, _c_fp, _i, _i, _i, _i, _i, _i, _c_st]),
     "ftr_pruned_band_constrained_bwd_scaled_dt": (_i, [_c_fp, _i, _c_ip, _c_ip, _c_ip, _i, _c_fp, _c_fp, _c_fp, _c_fp, _i, _f, _c_fp, _i, _i, _i, _i, _i, _i, _c_st]),
 }
+# include/ftr_path.h, the log-probability of one given alignment and its gradient: (logits, kind = FTR_DTYPE_*, symbols, ranges,
+# boundary, frames, termination_symbol, ...) with (arc_lp, arc_lse, logprob) forward and (arc_lse, logprob, logprob_grad, glogits)
+# backward, then (B, T, S, C, r, flags = FTR_PRUNED_HAT | FTR_PATH_MODIFIED, stream)
+_PATH_SIGNATURES = {
+    "ftr_pruned_path_logprob_fwd_dt": (_i, [_c_fp, _i, _c_ip, _c_ip, _c_ip, _c_ip, _i, _c_fp, _c_fp, _c_fp, _i, _i, _i, _i, _i, _i, _c_st]),
+    "ftr_pruned_path_logprob_bwd_dt": (_i, [_c_fp, _i, _c_ip, _c_ip, _c_ip, _c_ip, _i, _c_fp, _c_fp, _c_fp, _c_fp, _i, _i, _i, _i, _i, _i, _c_st]),
+}
 EXPORTED_SYMBOLS = tuple(_SIGNATURES)            # the symbols of include/ftr.h
 LOWP_SYMBOLS = tuple(_LOWP_SIGNATURES)           # those of include/ftr_lowp.h
 PRUNE_SUM_SYMBOLS = tuple(_PRUNE_SUM_SIGNATURES) # those of include/ftr_prune_sum.h
@@ -233,6 +240,7 @@ TDT_MIX_SYMBOLS = tuple(_TDT_MIX_SIGNATURES)     # those of include/ftr_tdt_mix.
 BAND_MULTIBLANK_SYMBOLS = tuple(_BAND_MULTIBLANK_SIGNATURES)   # those of include/ftr_band_multiblank.h
 BAND_VITERBI_SYMBOLS = tuple(_BAND_VITERBI_SIGNATURES)   # those of include/ftr_band_viterbi.h
 BAND_CONSTRAINED_SYMBOLS = tuple(_BAND_CONSTRAINED_SIGNATURES)   # those of include/ftr_band_constrained.h
+PATH_SYMBOLS = tuple(_PATH_SIGNATURES)           # those of include/ftr_path.h
 band_tdt_recursions = 0   # how many times the band-native TDT recursion has been launched from Python (tests read it)
 band_multiblank_recursions = 0   # ... and the band-native multi-blank recursion, likewise
 FTR_KD_FULL, FTR_KD_COLLAPSED = 0, 1             # include/ftr_kd.h: the `mode` of the kd entry points
@@ -243,6 +251,7 @@ FTR_MI_WS_CLEAN = 1   # include/ftr.h
 FTR_DTYPE_F32, FTR_DTYPE_BF16, FTR_DTYPE_FP16 = 0, 1, 2   # include/ftr_lowp.h: the `kind` of the _dt entry points
 FTR_ACT_TANH, FTR_ACT_RELU = 1, 2                          # include/ftr_joiner_act.h: the `act` of its entry points
 FTR_PRUNED_HAT = 1    # include/ftr_lowp.h: their `flags` bit
+FTR_PATH_MODIFIED = 2  # include/ftr_path.h: the modified type, the second `flags` bit of its entry points
 FTR_TDT_MIX_TDT, FTR_TDT_MIX_RNNT = 1, 2                   # include/ftr_tdt_mix.h: the `parts` bits of its builders
 
 
@@ -256,7 +265,7 @@ def lib() -> ctypes.CDLL:
                 "g.build()' or make -C tf-fast-rnnt_amd/csrc).  tf_fast_rnnt has no CPU fallback.")
         handle = ctypes.CDLL(LIB_PATH)
         for name, (restype, argtypes) in {**_SIGNATURES, **_LOWP_SIGNATURES, **_PRUNE_SUM_SIGNATURES, **_JOINER_ACT_SIGNATURES, **_KD_SIGNATURES, **_KD_FACT_SIGNATURES, **_KD_LOSS_SIGNATURES, **_KD_LOSS_FACT_SIGNATURES, **_KD_TOPK_SIGNATURES, **_KD_TOPK_TEACHER_SIGNATURES, **_FUSED_SIGNATURES, **_LIVE_SIGNATURES,
-                                            **_BAND_TDT_SIGNATURES, **_TDT_MIX_SIGNATURES, **_BAND_MULTIBLANK_SIGNATURES, **_BAND_VITERBI_SIGNATURES, **_BAND_CONSTRAINED_SIGNATURES}.items():
+                                            **_BAND_TDT_SIGNATURES, **_TDT_MIX_SIGNATURES, **_BAND_MULTIBLANK_SIGNATURES, **_BAND_VITERBI_SIGNATURES, **_BAND_CONSTRAINED_SIGNATURES, **_PATH_SIGNATURES}.items():
             fn = getattr(handle, name)   # AttributeError here = header/library mismatch
             fn.restype = restype
             fn.argtypes = argtypes

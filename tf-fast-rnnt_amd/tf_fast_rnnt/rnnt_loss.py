@@ -864,6 +864,93 @@ def rnnt_alignment_pruned(
         return mutual_information_viterbi(px, py, boundary)
 
 
+class _PathLogprob(torch.autograd.Function):
+    """rnnt_path_logprob_pruned: the arc and sum kernels forward, the row kernel backward (include/ftr_path.h)."""
+
+    @staticmethod
+    def forward(ctx, logits, symbols, ranges, frames, boundary, termination_symbol, flags):
+        x = logits.detach().contiguous()
+        B, T, r, C = x.shape
+        S = symbols.shape[1]
+        arc_lp = torch.empty((B, S + T), dtype=torch.float32, device=x.device)
+        arc_lse = torch.empty((B, 2, S + T), dtype=torch.float32, device=x.device)   # the row's maximum and log sum exp(x - max)
+        logprob = torch.empty((B,), dtype=torch.float32, device=x.device)
+        ctx.meta = (int(termination_symbol), (B, T, S, C, r, flags))
+        with torch.cuda.device(x.device):
+            _lib.call("ftr_pruned_path_logprob_fwd_dt", _ptr(x), _LOWP_KIND.get(x.dtype, _lib.FTR_DTYPE_F32), _ptr(symbols), _ptr(ranges),
+                      _ptr(boundary), _ptr(frames), ctx.meta[0], _ptr(arc_lp), _ptr(arc_lse), _ptr(logprob), *ctx.meta[1], _stream_ptr(x))
+        ctx.save_for_backward(x, symbols, ranges, frames, boundary, arc_lse, logprob)
+        return logprob
+
+    @staticmethod
+    def backward(ctx, g_logprob):
+        x, symbols, ranges, frames, boundary, arc_lse, logprob = ctx.saved_tensors
+        up = g_logprob.to(torch.float32).contiguous()
+        g = torch.empty_like(x)
+        with torch.cuda.device(x.device):
+            _lib.call("ftr_pruned_path_logprob_bwd_dt", _ptr(x), _LOWP_KIND.get(x.dtype, _lib.FTR_DTYPE_F32), _ptr(symbols), _ptr(ranges),
+                      _ptr(boundary), _ptr(frames), ctx.meta[0], _ptr(arc_lse), _ptr(logprob), _ptr(up), _ptr(g), *ctx.meta[1], _stream_ptr(x))
+        return g, None, None, None, None, None, None
+
+
+def rnnt_path_logprob_pruned(
+    logits: torch.Tensor,
+    symbols: torch.Tensor,
+    ranges: torch.Tensor,
+    termination_symbol: int,
+    frames: torch.Tensor,
+    boundary: Optional[torch.Tensor] = None,
+    rnnt_type: str = "regular",
+    factorization: str = "softmax",
+) -> torch.Tensor:
+    """The log-probability of ONE given alignment under the pruned joiner output (MI355X addition, no reference
+    counterpart): what Viterbi / forced-alignment training, the self-alignment latency regulariser (the model's own best
+    path moved one frame to the left) and the scoring of somebody else's alignment all need.  Returns ``logprob`` [B]
+    float32, <= 0, not reduced and not negated; differentiable w.r.t. ``logits`` only (the gradient has the dtype of
+    ``logits``, computed in float32 and rounded once).
+
+    ``logits`` [B,T,s_range,C] float32 / bfloat16 / float16 (a 16-bit tensor means ``logits.float()``); ``symbols`` [B,S];
+    ``ranges`` [B,T,s_range] -- ANY ranges and any s_range, not only a band: node (s,t) is the first slot k with
+    ``ranges[b,t,k] == s``; ``boundary`` None or [B,4] = (s_begin, t_begin, s_end, t_end); ``frames`` [B,S] int32 / int64
+    in the convention of ``mutual_information_viterbi`` and ``rnnt_alignment_pruned``: ``frames[b,s]`` is the frame that
+    emits ``symbols[b,s]`` (entries outside [s_begin, s_end) are ignored).
+
+    ``rnnt_type="regular"``: non-decreasing frames; one blank arc for every t in [t_begin, t_end), leaving row s_begin +
+    #{s : frames[s] <= t}.  ``"modified"``: strictly increasing frames; a frame that emits a symbol has no blank arc, the
+    others have theirs at row s_begin + #{s : frames[s] < t}.  ``"constrained"`` is refused: a constrained path IS a regular
+    path with strictly increasing frames (px_c = px' + py[s+1]: the symbol arc and the blank arc forced behind it are the
+    regular path's two arcs of that frame), so score it with ``rnnt_type="regular"``.
+    ``factorization="softmax"``: an arc is x[target] - logsumexp(row); ``"hat"``: the row of ``hat_loss_pruned``, log
+    sigmoid(x[blank]) for a blank arc and log sigmoid(-x[blank]) + x[sym] - logsumexp over c != blank for a symbol arc.  The
+    target column of a symbol arc is min(max(symbols[b,s],0),C-1), as in the builders; there is no delay penalty (this is
+    not a sum over paths).
+
+    An utterance whose path is not a path -- a frame outside [t_begin, t_end), frames not monotone as the type requires, or
+    a node that ``ranges`` does not hold -- gets exactly -inf and an exactly zero gradient, and nothing is read out of
+    range; an inverted rectangle gives 0.  Of the T * s_range rows of an utterance the forward reads the S + T on the path
+    (one wave per arc, csrc/pruned_path.hip) and the backward reads those and writes exact zeros everywhere else.  Kernels
+    only, no host read: the call can be captured in a graph, and it returns the same bits on every run."""
+    if rnnt_type == "constrained":
+        raise ValueError("rnnt_path_logprob_pruned: a constrained path is a regular path with strictly increasing frames "
+                         "(px_c = px' + py[s+1]); pass rnnt_type='regular'")
+    if rnnt_type not in ("regular", "modified"):
+        raise ValueError(f"rnnt_type should be ('regular' | 'modified'), given {rnnt_type}")
+    if factorization not in ("softmax", "hat"):
+        raise ValueError(f"factorization should be ('softmax' | 'hat'), given {factorization}")
+    symbols, ranges, boundary = _pruned_inputs(logits, symbols, ranges, boundary, lowp=True)
+    frames = torch.as_tensor(frames, device=logits.device)
+    if frames.dtype not in (torch.int32, torch.int64):
+        raise TypeError("frames must be int32 or int64")
+    if tuple(frames.shape) != tuple(symbols.shape):
+        raise ValueError(f"frames must have the shape of symbols {tuple(symbols.shape)}, got {tuple(frames.shape)}")
+    C = logits.shape[3]
+    if not 0 <= int(termination_symbol) < C or (factorization == "hat" and C < 2):
+        raise ValueError(f"termination_symbol {termination_symbol} must be in [0, {C}) (HAT: C >= 2)")
+    frames = frames.to(torch.int32).contiguous()
+    flags = (_lib.FTR_PRUNED_HAT if factorization == "hat" else 0) | (_lib.FTR_PATH_MODIFIED if rnnt_type == "modified" else 0)
+    return _PathLogprob.apply(logits, symbols, ranges, frames, boundary, int(termination_symbol), flags)
+
+
 def _mark_band(ranges: torch.Tensor) -> None:
     """Remembers on the tensor object that its CURRENT contents are a band over ALL T frames, hence inside any boundary
     (the version counter catches in-place edits)."""
