@@ -57,7 +57,7 @@ def _setup(which, B, T, S, C, r, sym, ranges, bd, blank, dev):
     """(the wrapper call, (px_band, py_band, token durations, blank durations) of its band builder).  The operands of the
     two chain candidates have to be what the wrappers feed their kernel, and the package has no public band builder: they
     are made with the private helpers the wrappers themselves call (rnnt_loss._pruned_inputs, with a dummy logits tensor
-    for its shape checks, _tdt_args / _tdt_band_builder_fwd, _big_blank_args / _mb_band_builder_fwd, _pruned_call).  A
+    for its shape checks, _tdt_args / _tdt_builder_fwd, _big_blank_args / _mb_builder_fwd, _pruned_call).  A
     refactor of rnnt_loss.py that renames them has to follow here."""
     g = torch.Generator(device="cpu").manual_seed(2000)
     with torch.no_grad():
@@ -65,13 +65,13 @@ def _setup(which, B, T, S, C, r, sym, ranges, bd, blank, dev):
         if which == "tdt":
             logits = torch.randn((B, T, r, C + len(TDT_DURATIONS)), generator=g, dtype=torch.float32).to(dev)
             arr, durs, blk, Cc = rl._tdt_args(TDT_DURATIONS, blank, logits.shape[3])
-            _, _, pxb, pyb = rl._tdt_band_builder_fwd(logits, sym, ranges, bd, blank, arr, durs, blk, Cc, 0.0, 0.0)
+            _, _, pxb, pyb = rl._tdt_builder_fwd(logits, sym, ranges, bd, blank, arr, durs, blk, Cc, 0.0, 0.0, band=True)
             return (lambda: ft.rnnt_alignment_tdt_pruned(logits, sym, ranges, blank, TDT_DURATIONS, bd)), (pxb, pyb, durs, blk)
         logits = torch.randn((B, T, r, C), generator=g, dtype=torch.float32).to(dev)
         if which == "multiblank":
             big = tuple(zip((C - 3, C - 2, C - 1), BIG_BLANK_DURATIONS))             # no symbol is one of them (run)
             ids_arr, durs_arr, dt = rl._big_blank_args(big, blank, C)
-            _, pxb, pyb = rl._mb_band_builder_fwd(logits, sym, ranges, bd, blank, ids_arr, durs_arr, len(dt), 0.0, 0.0)
+            _, pxb, pyb = rl._mb_builder_fwd(logits, sym, ranges, bd, blank, ids_arr, durs_arr, len(dt), 0.0, 0.0, band=True)
             return (lambda: ft.rnnt_alignment_multiblank_pruned(logits, sym, ranges, blank, big, bd)), (pxb.unsqueeze(1), pyb, (0,), dt)
         lse = torch.empty((B, T, r), dtype=torch.float32, device=dev)
         pxb, pyb = torch.empty_like(lse), torch.empty_like(lse)

@@ -1002,17 +1002,25 @@ int ftr_pruned_path_logprob_bwd_dt(const void* logits, int kind, const int32_t* 
   return pruned_path_bwd(logits, kind, symbols, ranges, boundary, frames, termination_symbol, arc_lse, logprob, logprob_grad, glogits, B, T, S, C, r, (flags & FTR_PATH_MODIFIED) != 0, flags & FTR_PRUNED_HAT, stream_of(stream));
 }
 
-// ---- multi-blank transducer (MI355X addition; csrc/mi_multiblank.hip, the mb_* kernels of csrc/pruned_logprobs.hip).
-// D, the durations and the big-blank ids are host data and are validated first, then sizes and pointers, then the device.
+// ---- the duration lattices: multi-blank (csrc/mi_multiblank.hip, the mb_* kernels of csrc/pruned_logprobs.hip), TDT
+// (csrc/mi_tdt.hip, csrc/tdt_logprobs.hip), their band-native forms (csrc/mi_band_tdt.hip) and the alignments
+// (csrc/mi_viterbi_tdt.hip, csrc/mi_band_viterbi.hip); MI355X additions.  The duration lists and the big-blank ids are host
+// data and are validated first, then sizes and pointers, then the device.  Each group of entry points has one body below,
+// run under the entry's own `what`; band: the band-shaped twin, whose planes exist when S == 0 too.
 namespace {
+// the values of one duration list, after its length: every text here is the same for both families
+int check_duration_values(const char* what, const char* name, const int32_t* v, int n, int lo, int hi) {
+  FTR_REQUIRE(v, "%s: null %s", what, name);
+  for (int j = 0; j < n; ++j) {
+    FTR_REQUIRE(v[j] >= lo && v[j] <= hi, "%s: %s[%d] = %d is outside %d..%d", what, name, j, v[j], lo, hi);
+    FTR_REQUIRE(j == 0 || v[j] > v[j - 1], "%s: %s must be strictly increasing (%s[%d] = %d after %d)", what, name, name, j,
+                v[j], v[j - 1]);
+  }
+  return FTR_OK;
+}
 int mb_check_durations(const char* what, const int32_t* durations, int D, bool first_is_one) {
   FTR_REQUIRE(D >= 1 && D <= 8, "%s: D = %d, the number of blanks must be in 1..8", what, D);
-  FTR_REQUIRE(durations, "%s: null durations", what);
-  for (int j = 0; j < D; ++j) {
-    FTR_REQUIRE(durations[j] >= 1 && durations[j] <= 32, "%s: durations[%d] = %d is outside 1..32", what, j, durations[j]);
-    FTR_REQUIRE(j == 0 || durations[j] > durations[j - 1], "%s: durations must be strictly increasing (durations[%d] = %d after %d)",
-                what, j, durations[j], durations[j - 1]);
-  }
+  FTR_TRY(check_duration_values(what, "durations", durations, D, 1, 32));
   FTR_REQUIRE(!first_is_one || durations[0] == 1, "%s: durations[0] = %d, the standard blank advances one frame", what, durations[0]);
   return FTR_OK;
 }
@@ -1027,25 +1035,19 @@ int mb_check_ids(const char* what, const int32_t* ids, int D, int blank, int C) 
   }
   return FTR_OK;
 }
-}  // namespace
-
-// ---- token-and-duration transducer, TDT (MI355X addition; csrc/mi_tdt.hip, csrc/tdt_logprobs.hip).  The duration lists
-// are host data and are validated first, then sizes and pointers, then the device.
-namespace {
 int tdt_check_list(const char* what, const char* name, const int32_t* v, int n, int nmax, int lo, int hi = 16) {
   FTR_REQUIRE(n >= 1 && n <= nmax, "%s: %s holds %d values, must be 1..%d", what, name, n, nmax);
-  FTR_REQUIRE(v, "%s: null %s", what, name);
-  for (int j = 0; j < n; ++j) {
-    FTR_REQUIRE(v[j] >= lo && v[j] <= hi, "%s: %s[%d] = %d is outside %d..%d", what, name, j, v[j], lo, hi);
-    FTR_REQUIRE(j == 0 || v[j] > v[j - 1], "%s: %s must be strictly increasing (%s[%d] = %d after %d)", what, name, name, j,
-                v[j], v[j - 1]);
-  }
-  return FTR_OK;
+  return check_duration_values(what, name, v, n, lo, hi);
+}
+// the two move lists of a recursion or an alignment: up to nmax of a kind, a blank advancing up to blank_hi frames
+int tdt_check_lists(const char* what, const int32_t* token_durations, int Dx, const int32_t* blank_durations, int Dy, int nmax,
+                    int blank_hi) {
+  FTR_TRY(tdt_check_list(what, "token_durations", token_durations, Dx, nmax, 0));
+  return tdt_check_list(what, "blank_durations", blank_durations, Dy, nmax, 1, blank_hi);
 }
 int tdt_check_moves(const char* what, const int32_t* token_durations, int Dx, const int32_t* blank_durations, int Dy,
-                    int blank_hi = 16, int max_moves = 9) {
-  FTR_TRY(tdt_check_list(what, "token_durations", token_durations, Dx, 8, 0));
-  FTR_TRY(tdt_check_list(what, "blank_durations", blank_durations, Dy, 8, 1, blank_hi));
+                    int blank_hi, int max_moves) {
+  FTR_TRY(tdt_check_lists(what, token_durations, Dx, blank_durations, Dy, 8, blank_hi));
   FTR_REQUIRE(Dx + Dy <= max_moves, "%s: Dx + Dy = %d moves (token_durations and blank_durations together), at most %d", what,
               Dx + Dy, max_moves);
   return FTR_OK;
@@ -1057,8 +1059,121 @@ int tdt_check_head(const char* what, const int32_t* durations, int N, double sig
   FTR_REQUIRE(C >= 1 && blank >= 0 && blank < C, "%s: termination_symbol %d not in [0,%d)", what, blank, C);
   return FTR_OK;
 }
+
+extern "C++" {   // templates: the callables passed in are the entry's own lambdas
+// The lattice recursions, forward (ans) and backward (px_grad / py_grad).  lists: the entry's check of its duration lists;
+// ws_floats: its workspace query; run: the launch.
+template <typename Lists, typename Run>
+int mi_duration_entry(const char* what, bool bwd, Lists lists, size_t (*ws_floats)(int, int, int), Run run, const float* px,
+                      const float* py, const float* workspace, size_t workspace_floats, const float* ans, const float* px_grad,
+                      const float* py_grad, int B, int S, int T) {
+  clear_error();
+  FTR_TRY(lists());
+  FTR_TRY(check_lattice(what, B, S, T));
+  if (B == 0) return FTR_OK;
+  FTR_TRY(check_ws_size(what, workspace_floats, ws_floats(B, S, T), "floats"));
+  if (bwd) {
+    FTR_REQUIRE(workspace && (py || T == 0) && (px || S == 0), "%s: null px / py / workspace", what);
+    FTR_REQUIRE((py_grad || T == 0) && (px_grad || S == 0), "%s: null px_grad / py_grad", what);
+  } else {
+    FTR_REQUIRE(workspace && ans && (py || T == 0) && (px || S == 0), "%s: null px / py / workspace / ans", what);
+  }
+  FTR_TRY(check_ws_aligned(what, workspace));
+  FTR_TRY(device_ok());
+  return run();
+}
+
+// The band recursions: the chain of csrc/mi_band_tdt.hip in the entry's domain.  lists: the entry's check of its lists.
+template <typename Lists>
+int mi_band_duration_entry(const char* what, BandMoveDomain dom, Lists lists, const float* px_band, const float* py_band,
+                           const int32_t* ranges, const int32_t* boundary, const int32_t* token_durations, int N,
+                           const int32_t* blank_durations, int Ny, float* workspace, size_t workspace_floats, float* ans,
+                           float* gx_band, float* gy_band, int B, int T, int S, int r, void* stream) {
+  clear_error();
+  FTR_TRY(lists());
+  FTR_TRY(check_sizes(what, B >= 0 && T >= 1 && S >= 0 && r >= 1));
+  if (!mi_band_tdt_supported(T, S, r, N, Ny, dom)) {
+    set_error("%s: T=%d S=%d r=%d is outside the kernel's domain (r <= 15)", what, T, S, r);
+    return FTR_ERR_UNSUPPORTED;
+  }
+  if (B == 0) return FTR_OK;
+  FTR_TRY(check_ws_size(what, workspace_floats, mi_band_tdt_workspace_floats(B, T, S, r, N, Ny, dom), "floats"));
+  FTR_REQUIRE(px_band && py_band && ranges && workspace && ans, "%s: null px_band / py_band / ranges / workspace / ans", what);
+  FTR_REQUIRE((gx_band != nullptr) == (gy_band != nullptr), "%s: gx_band and gy_band must both be given or both be null", what);
+  FTR_TRY(check_ws_aligned(what, workspace));
+  FTR_TRY(device_ok());
+  return mi_band_tdt(px_band, py_band, ranges, boundary, token_durations, N, blank_durations, Ny, workspace, workspace_floats, ans,
+                     gx_band, gy_band, B, T, S, r, dom, what, stream_of(stream));
+}
+}  // extern "C++"
+
+// The multi-blank builders.  sigma is checked by the forward alone, where it always was: after the sizes.
+int mb_builder_fwd_entry(int band, const char* what, const float* logits, const int32_t* symbols, const int32_t* ranges,
+                         const int32_t* boundary, int termination_symbol, const int32_t* big_blank_ids, const int32_t* durations,
+                         int D, double sigma, double delay_penalty, float* lse, float* px, float* py, int B, int T, int S, int C,
+                         int r, void* stream) {
+  clear_error();
+  FTR_TRY(mb_check_durations(what, durations, D, true));
+  FTR_TRY(mb_check_ids(what, big_blank_ids, D, termination_symbol, C));
+  FTR_TRY(check_sizes(what, B >= 0 && T >= 1 && S >= 0 && r >= 1));
+  FTR_TRY(check_s_range(what, r, S));
+  FTR_REQUIRE(sigma >= 0.0, "%s: sigma = %g must not be negative", what, sigma);
+  if (B == 0) return FTR_OK;
+  const bool lat0 = !band && S == 0;    // the lattice of shape [.,S,.] is empty then
+  FTR_TRY(pointers_then_device(what, logits && ranges && lse && py && (px || lat0) && (symbols || S == 0)));
+  return multiblank_builder_fwd(band != 0, logits, symbols, ranges, boundary, termination_symbol, big_blank_ids, durations, D, sigma,
+                                delay_penalty, lse, px, py, B, T, S, C, r, stream_of(stream));
+}
+
+int mb_builder_bwd_entry(int band, const char* what, const float* logits, const int32_t* symbols, const int32_t* ranges,
+                         const int32_t* boundary, int termination_symbol, const int32_t* big_blank_ids, const int32_t* durations,
+                         int D, const float* lse, const float* gpx, const float* gpy, const float* scale, int scale_stride,
+                         float scale_mul, float* glogits, int B, int T, int S, int C, int r, void* stream) {
+  clear_error();
+  FTR_TRY(mb_check_durations(what, durations, D, true));
+  FTR_TRY(mb_check_ids(what, big_blank_ids, D, termination_symbol, C));
+  FTR_TRY(check_sizes(what, B >= 0 && T >= 1 && S >= 0 && r >= 1));
+  FTR_TRY(check_scale_stride(what, scale_stride));
+  if (B == 0) return FTR_OK;
+  const bool lat0 = !band && S == 0;
+  FTR_TRY(pointers_then_device(what, logits && ranges && lse && gpy && (gpx || lat0) && glogits && (symbols || S == 0)));
+  return multiblank_builder_bwd(band != 0, logits, symbols, ranges, boundary, termination_symbol, big_blank_ids, durations, D, lse,
+                                gpx, gpy, Scale{scale, scale_stride, scale_mul}, glogits, B, T, S, C, r, stream_of(stream));
+}
+
+// The TDT builders.
+int tdt_builder_fwd_entry(int band, const char* what, const float* logits, const int32_t* symbols, const int32_t* ranges,
+                          const int32_t* boundary, int termination_symbol, const int32_t* durations, int N, double sigma,
+                          double delay_penalty, float* lse_tok, float* lse_dur, float* px, float* py, int B, int T, int S, int C,
+                          int r, void* stream) {
+  clear_error();
+  FTR_TRY(tdt_check_head(what, durations, N, sigma, termination_symbol, C));
+  FTR_TRY(check_sizes(what, B >= 0 && T >= 1 && S >= 0 && r >= 1));
+  FTR_TRY(check_s_range(what, r, S));
+  if (B == 0) return FTR_OK;
+  const bool lat0 = !band && S == 0;
+  FTR_TRY(pointers_then_device(what, logits && ranges && lse_tok && lse_dur && py && (px || lat0) && (symbols || S == 0)));
+  return tdt_builder_fwd(band != 0, logits, symbols, ranges, boundary, termination_symbol, durations, N, sigma, delay_penalty,
+                         lse_tok, lse_dur, px, py, B, T, S, C, r, stream_of(stream));
+}
+
+int tdt_builder_bwd_entry(int band, const char* what, const float* logits, const int32_t* symbols, const int32_t* ranges,
+                          const int32_t* boundary, int termination_symbol, const int32_t* durations, int N, double sigma,
+                          const float* lse_tok, const float* lse_dur, const float* gpx, const float* gpy, const float* scale,
+                          int scale_stride, float scale_mul, float* glogits, int B, int T, int S, int C, int r, void* stream) {
+  clear_error();
+  FTR_TRY(tdt_check_head(what, durations, N, sigma, termination_symbol, C));
+  FTR_TRY(check_sizes(what, B >= 0 && T >= 1 && S >= 0 && r >= 1));
+  FTR_TRY(check_scale_stride(what, scale_stride));
+  if (B == 0) return FTR_OK;
+  const bool lat0 = !band && S == 0;
+  FTR_TRY(pointers_then_device(what, logits && ranges && lse_tok && lse_dur && gpy && (gpx || lat0) && glogits && (symbols || S == 0)));
+  return tdt_builder_bwd(band != 0, logits, symbols, ranges, boundary, termination_symbol, durations, N, lse_tok, lse_dur, gpx, gpy,
+                         Scale{scale, scale_stride, scale_mul}, glogits, B, T, S, C, r, stream_of(stream));
+}
 }  // namespace
 
+// ---- multi-blank transducer
 size_t ftr_mutual_information_multiblank_workspace_floats(int B, int S, int T) {
   return mi_multiblank_workspace_floats(B, S, T);
 }
@@ -1067,15 +1182,9 @@ int ftr_mutual_information_multiblank_fwd_f32(const float* px, const float* py, 
                                               const int32_t* durations, int D, float* workspace, size_t workspace_floats,
                                               float* ans, int B, int S, int T, void* stream) {
   const char* what = "mutual_information_multiblank_fwd";
-  clear_error();
-  FTR_TRY(mb_check_durations(what, durations, D, false));
-  FTR_TRY(check_lattice(what, B, S, T));
-  if (B == 0) return FTR_OK;
-  FTR_TRY(check_ws_size(what, workspace_floats, mi_multiblank_workspace_floats(B, S, T), "floats"));
-  FTR_REQUIRE(workspace && ans && (py || T == 0) && (px || S == 0), "%s: null px / py / workspace / ans", what);
-  FTR_TRY(check_ws_aligned(what, workspace));
-  FTR_TRY(device_ok());
-  return mi_multiblank_fwd(px, py, boundary, durations, D, workspace, workspace_floats, ans, B, S, T, stream_of(stream));
+  return mi_duration_entry(what, false, [&] { return mb_check_durations(what, durations, D, false); }, mi_multiblank_workspace_floats,
+                           [&] { return mi_multiblank_fwd(px, py, boundary, durations, D, workspace, workspace_floats, ans, B, S, T, stream_of(stream)); },
+                           px, py, workspace, workspace_floats, ans, nullptr, nullptr, B, S, T);
 }
 
 int ftr_mutual_information_multiblank_bwd_f32(const float* px, const float* py, const int32_t* boundary,
@@ -1083,33 +1192,17 @@ int ftr_mutual_information_multiblank_bwd_f32(const float* px, const float* py, 
                                               const float* ans_grad, float* px_grad, float* py_grad, int B, int S, int T,
                                               void* stream) {
   const char* what = "mutual_information_multiblank_bwd";
-  clear_error();
-  FTR_TRY(mb_check_durations(what, durations, D, false));
-  FTR_TRY(check_lattice(what, B, S, T));
-  if (B == 0) return FTR_OK;
-  FTR_TRY(check_ws_size(what, workspace_floats, mi_multiblank_workspace_floats(B, S, T), "floats"));
-  FTR_REQUIRE(workspace && (py || T == 0) && (px || S == 0), "%s: null px / py / workspace", what);
-  FTR_REQUIRE((py_grad || T == 0) && (px_grad || S == 0), "%s: null px_grad / py_grad", what);
-  FTR_TRY(check_ws_aligned(what, workspace));
-  FTR_TRY(device_ok());
-  return mi_multiblank_bwd(px, py, boundary, durations, D, workspace, workspace_floats, ans_grad, px_grad, py_grad, B, S, T, stream_of(stream));
+  return mi_duration_entry(what, true, [&] { return mb_check_durations(what, durations, D, false); }, mi_multiblank_workspace_floats,
+                           [&] { return mi_multiblank_bwd(px, py, boundary, durations, D, workspace, workspace_floats, ans_grad, px_grad, py_grad, B, S, T, stream_of(stream)); },
+                           px, py, workspace, workspace_floats, nullptr, px_grad, py_grad, B, S, T);
 }
 
 int ftr_multiblank_pruned_logprobs_fwd_f32(const float* logits, const int32_t* symbols, const int32_t* ranges,
                                            const int32_t* boundary, int termination_symbol, const int32_t* big_blank_ids,
                                            const int32_t* durations, int D, double sigma, double delay_penalty, float* lse,
                                            float* px, float* py, int B, int T, int S, int C, int r, void* stream) {
-  const char* what = "multiblank_pruned_logprobs_fwd";
-  clear_error();
-  FTR_TRY(mb_check_durations(what, durations, D, true));
-  FTR_TRY(mb_check_ids(what, big_blank_ids, D, termination_symbol, C));
-  FTR_TRY(check_sizes(what, B >= 0 && T >= 1 && S >= 0 && r >= 1));
-  FTR_TRY(check_s_range(what, r, S));
-  FTR_REQUIRE(sigma >= 0.0, "%s: sigma = %g must not be negative", what, sigma);
-  if (B == 0) return FTR_OK;
-  FTR_TRY(pointers_then_device(what, logits && ranges && lse && py && (symbols || S == 0) && (px || S == 0)));
-  return multiblank_logprobs_fwd(logits, symbols, ranges, boundary, termination_symbol, big_blank_ids, durations, D, sigma,
-                                 delay_penalty, lse, px, py, B, T, S, C, r, stream_of(stream));
+  return mb_builder_fwd_entry(0, "multiblank_pruned_logprobs_fwd", logits, symbols, ranges, boundary, termination_symbol, big_blank_ids,
+                              durations, D, sigma, delay_penalty, lse, px, py, B, T, S, C, r, stream);
 }
 
 int ftr_multiblank_pruned_logprobs_bwd_scaled_f32(const float* logits, const int32_t* symbols, const int32_t* ranges,
@@ -1118,18 +1211,11 @@ int ftr_multiblank_pruned_logprobs_bwd_scaled_f32(const float* logits, const int
                                                   const float* lse, const float* gpx, const float* gpy, const float* scale,
                                                   int scale_stride, float scale_mul, float* glogits, int B, int T, int S,
                                                   int C, int r, void* stream) {
-  const char* what = "multiblank_pruned_logprobs_bwd_scaled";
-  clear_error();
-  FTR_TRY(mb_check_durations(what, durations, D, true));
-  FTR_TRY(mb_check_ids(what, big_blank_ids, D, termination_symbol, C));
-  FTR_TRY(check_sizes(what, B >= 0 && T >= 1 && S >= 0 && r >= 1));
-  FTR_TRY(check_scale_stride(what, scale_stride));
-  if (B == 0) return FTR_OK;
-  FTR_TRY(pointers_then_device(what, logits && ranges && lse && gpy && glogits && (symbols || S == 0) && (gpx || S == 0)));
-  return multiblank_logprobs_bwd(logits, symbols, ranges, boundary, termination_symbol, big_blank_ids, durations, D, lse, gpx,
-                                 gpy, Scale{scale, scale_stride, scale_mul}, glogits, B, T, S, C, r, stream_of(stream));
+  return mb_builder_bwd_entry(0, "multiblank_pruned_logprobs_bwd_scaled", logits, symbols, ranges, boundary, termination_symbol,
+                              big_blank_ids, durations, D, lse, gpx, gpy, scale, scale_stride, scale_mul, glogits, B, T, S, C, r, stream);
 }
 
+// ---- token-and-duration transducer, TDT
 size_t ftr_mutual_information_tdt_workspace_floats(int B, int S, int T) { return mi_tdt_workspace_floats(B, S, T); }
 
 int ftr_mutual_information_tdt_fwd_f32(const float* px, const float* py, const int32_t* boundary,
@@ -1137,16 +1223,10 @@ int ftr_mutual_information_tdt_fwd_f32(const float* px, const float* py, const i
                                        float* workspace, size_t workspace_floats, float* ans, int B, int S, int T,
                                        void* stream) {
   const char* what = "mutual_information_tdt_fwd";
-  clear_error();
-  FTR_TRY(tdt_check_moves(what, token_durations, Dx, blank_durations, Dy, 16, 10));   // MAXM of mi_rowlane.h
-  FTR_TRY(check_lattice(what, B, S, T));
-  if (B == 0) return FTR_OK;
-  FTR_TRY(check_ws_size(what, workspace_floats, mi_tdt_workspace_floats(B, S, T), "floats"));
-  FTR_REQUIRE(workspace && ans && (py || T == 0) && (px || S == 0), "%s: null px / py / workspace / ans", what);
-  FTR_TRY(check_ws_aligned(what, workspace));
-  FTR_TRY(device_ok());
-  return mi_tdt_fwd(px, py, boundary, token_durations, Dx, blank_durations, Dy, workspace, workspace_floats, ans, B, S, T,
-                    stream_of(stream));
+  return mi_duration_entry(what, false, [&] { return tdt_check_moves(what, token_durations, Dx, blank_durations, Dy, 16, 10); },   // MAXM of mi_rowlane.h
+                           mi_tdt_workspace_floats,
+                           [&] { return mi_tdt_fwd(px, py, boundary, token_durations, Dx, blank_durations, Dy, workspace, workspace_floats, ans, B, S, T, stream_of(stream)); },
+                           px, py, workspace, workspace_floats, ans, nullptr, nullptr, B, S, T);
 }
 
 int ftr_mutual_information_tdt_bwd_f32(const float* px, const float* py, const int32_t* boundary,
@@ -1154,21 +1234,14 @@ int ftr_mutual_information_tdt_bwd_f32(const float* px, const float* py, const i
                                        float* workspace, size_t workspace_floats, const float* ans_grad, float* px_grad,
                                        float* py_grad, int B, int S, int T, void* stream) {
   const char* what = "mutual_information_tdt_bwd";
-  clear_error();
-  FTR_TRY(tdt_check_moves(what, token_durations, Dx, blank_durations, Dy, 16, 10));   // MAXM of mi_rowlane.h
-  FTR_TRY(check_lattice(what, B, S, T));
-  if (B == 0) return FTR_OK;
-  FTR_TRY(check_ws_size(what, workspace_floats, mi_tdt_workspace_floats(B, S, T), "floats"));
-  FTR_REQUIRE(workspace && (py || T == 0) && (px || S == 0), "%s: null px / py / workspace", what);
-  FTR_REQUIRE((py_grad || T == 0) && (px_grad || S == 0), "%s: null px_grad / py_grad", what);
-  FTR_TRY(check_ws_aligned(what, workspace));
-  FTR_TRY(device_ok());
-  return mi_tdt_bwd(px, py, boundary, token_durations, Dx, blank_durations, Dy, workspace, workspace_floats, ans_grad,
-                    px_grad, py_grad, B, S, T, stream_of(stream));
+  return mi_duration_entry(what, true, [&] { return tdt_check_moves(what, token_durations, Dx, blank_durations, Dy, 16, 10); },   // MAXM of mi_rowlane.h
+                           mi_tdt_workspace_floats,
+                           [&] { return mi_tdt_bwd(px, py, boundary, token_durations, Dx, blank_durations, Dy, workspace, workspace_floats, ans_grad, px_grad, py_grad, B, S, T, stream_of(stream)); },
+                           px, py, workspace, workspace_floats, nullptr, px_grad, py_grad, B, S, T);
 }
 
 // Best-path alignment over the TDT / multi-blank lattice (csrc/mi_viterbi_tdt.hip).  A blank may advance 32 frames here,
-// as a big blank of the multi-blank builder does.
+// as a big blank of the multi-blank builder does; nine moves at most (MAXM_ALIGN).
 size_t ftr_mutual_information_viterbi_tdt_workspace_bytes(int B, int S, int T) {
   return mi_viterbi_tdt_workspace_bytes(B, S, T);
 }
@@ -1179,7 +1252,7 @@ int ftr_mutual_information_viterbi_tdt_f32(const float* px, const float* py, con
                                            int32_t* durations, int32_t* blank_steps, int B, int S, int T, void* stream) {
   const char* what = "mutual_information_viterbi_tdt";
   clear_error();
-  FTR_TRY(tdt_check_moves(what, token_durations, Dx, blank_durations, Dy, 32));
+  FTR_TRY(tdt_check_moves(what, token_durations, Dx, blank_durations, Dy, 32, 9));
   FTR_TRY(check_lattice(what, B, S, T));
   if (B == 0) return FTR_OK;
   FTR_TRY(check_ws_size(what, workspace_bytes, mi_viterbi_tdt_workspace_bytes(B, S, T), "bytes"));
@@ -1196,15 +1269,8 @@ int ftr_tdt_pruned_logprobs_fwd_f32(const float* logits, const int32_t* symbols,
                                     const int32_t* boundary, int termination_symbol, const int32_t* durations, int N,
                                     double sigma, double delay_penalty, float* lse_tok, float* lse_dur, float* px,
                                     float* py, int B, int T, int S, int C, int r, void* stream) {
-  const char* what = "tdt_pruned_logprobs_fwd";
-  clear_error();
-  FTR_TRY(tdt_check_head(what, durations, N, sigma, termination_symbol, C));
-  FTR_TRY(check_sizes(what, B >= 0 && T >= 1 && S >= 0 && r >= 1));
-  FTR_TRY(check_s_range(what, r, S));
-  if (B == 0) return FTR_OK;
-  FTR_TRY(pointers_then_device(what, logits && ranges && lse_tok && lse_dur && py && (symbols || S == 0) && (px || S == 0)));
-  return tdt_logprobs_fwd(logits, symbols, ranges, boundary, termination_symbol, durations, N, sigma, delay_penalty, lse_tok,
-                          lse_dur, px, py, B, T, S, C, r, stream_of(stream));
+  return tdt_builder_fwd_entry(0, "tdt_pruned_logprobs_fwd", logits, symbols, ranges, boundary, termination_symbol, durations, N, sigma,
+                               delay_penalty, lse_tok, lse_dur, px, py, B, T, S, C, r, stream);
 }
 
 int ftr_tdt_pruned_logprobs_bwd_scaled_f32(const float* logits, const int32_t* symbols, const int32_t* ranges,
@@ -1213,16 +1279,9 @@ int ftr_tdt_pruned_logprobs_bwd_scaled_f32(const float* logits, const int32_t* s
                                            const float* lse_dur, const float* gpx, const float* gpy, const float* scale,
                                            int scale_stride, float scale_mul, float* glogits, int B, int T, int S, int C,
                                            int r, void* stream) {
-  const char* what = "tdt_pruned_logprobs_bwd_scaled";
-  clear_error();
   (void)delay_penalty;   // a constant added to px: no gradient
-  FTR_TRY(tdt_check_head(what, durations, N, sigma, termination_symbol, C));
-  FTR_TRY(check_sizes(what, B >= 0 && T >= 1 && S >= 0 && r >= 1));
-  FTR_TRY(check_scale_stride(what, scale_stride));
-  if (B == 0) return FTR_OK;
-  FTR_TRY(pointers_then_device(what, logits && ranges && lse_tok && lse_dur && gpy && glogits && (symbols || S == 0) && (gpx || S == 0)));
-  return tdt_logprobs_bwd(logits, symbols, ranges, boundary, termination_symbol, durations, N, lse_tok, lse_dur, gpx, gpy,
-                          Scale{scale, scale_stride, scale_mul}, glogits, B, T, S, C, r, stream_of(stream));
+  return tdt_builder_bwd_entry(0, "tdt_pruned_logprobs_bwd_scaled", logits, symbols, ranges, boundary, termination_symbol, durations, N,
+                               sigma, lse_tok, lse_dur, gpx, gpy, scale, scale_stride, scale_mul, glogits, B, T, S, C, r, stream);
 }
 
 // ---- include/ftr_band_tdt.h: the TDT loss on the pruned band itself (csrc/mi_band_tdt.hip, csrc/tdt_logprobs.hip)
@@ -1239,37 +1298,17 @@ int ftr_mutual_information_band_tdt_f32(const float* px_band, const float* py_ba
                                         float* ans, float* gx_band, float* gy_band, int B, int T, int S, int r,
                                         void* stream) {
   const char* what = "mutual_information_band_tdt";
-  clear_error();
-  FTR_TRY(tdt_check_list(what, "token_durations", token_durations, N, 5, 0));
-  FTR_TRY(tdt_check_list(what, "blank_durations", blank_durations, Ny, 5, 1));
-  FTR_TRY(check_sizes(what, B >= 0 && T >= 1 && S >= 0 && r >= 1));
-  if (!mi_band_tdt_supported(T, S, r, N, Ny, kBandTdtDomain)) {
-    set_error("%s: T=%d S=%d r=%d is outside the kernel's domain (r <= 15)", what, T, S, r);
-    return FTR_ERR_UNSUPPORTED;
-  }
-  if (B == 0) return FTR_OK;
-  FTR_TRY(check_ws_size(what, workspace_floats, mi_band_tdt_workspace_floats(B, T, S, r, N, Ny, kBandTdtDomain), "floats"));
-  FTR_REQUIRE(px_band && py_band && ranges && workspace && ans, "%s: null px_band / py_band / ranges / workspace / ans", what);
-  FTR_REQUIRE((gx_band != nullptr) == (gy_band != nullptr), "%s: gx_band and gy_band must both be given or both be null", what);
-  FTR_TRY(check_ws_aligned(what, workspace));
-  FTR_TRY(device_ok());
-  return mi_band_tdt(px_band, py_band, ranges, boundary, token_durations, N, blank_durations, Ny, workspace, workspace_floats, ans,
-                     gx_band, gy_band, B, T, S, r, kBandTdtDomain, what, stream_of(stream));
+  return mi_band_duration_entry(what, kBandTdtDomain, [&] { return tdt_check_lists(what, token_durations, N, blank_durations, Ny, 5, 16); },
+                                px_band, py_band, ranges, boundary, token_durations, N, blank_durations, Ny, workspace, workspace_floats,
+                                ans, gx_band, gy_band, B, T, S, r, stream);
 }
 
 int ftr_tdt_pruned_band_fwd_f32(const float* logits, const int32_t* symbols, const int32_t* ranges,
                                 const int32_t* boundary, int termination_symbol, const int32_t* durations, int N,
                                 double sigma, double delay_penalty, float* lse_tok, float* lse_dur, float* px_band,
                                 float* py_band, int B, int T, int S, int C, int r, void* stream) {
-  const char* what = "tdt_pruned_band_fwd";
-  clear_error();
-  FTR_TRY(tdt_check_head(what, durations, N, sigma, termination_symbol, C));
-  FTR_TRY(check_sizes(what, B >= 0 && T >= 1 && S >= 0 && r >= 1));
-  FTR_TRY(check_s_range(what, r, S));
-  if (B == 0) return FTR_OK;
-  FTR_TRY(pointers_then_device(what, logits && ranges && lse_tok && lse_dur && px_band && py_band && (symbols || S == 0)));
-  return tdt_band_fwd(logits, symbols, ranges, boundary, termination_symbol, durations, N, sigma, delay_penalty, lse_tok, lse_dur,
-                      px_band, py_band, B, T, S, C, r, stream_of(stream));
+  return tdt_builder_fwd_entry(1, "tdt_pruned_band_fwd", logits, symbols, ranges, boundary, termination_symbol, durations, N, sigma,
+                               delay_penalty, lse_tok, lse_dur, px_band, py_band, B, T, S, C, r, stream);
 }
 
 int ftr_tdt_pruned_band_bwd_scaled_f32(const float* logits, const int32_t* symbols, const int32_t* ranges,
@@ -1277,16 +1316,9 @@ int ftr_tdt_pruned_band_bwd_scaled_f32(const float* logits, const int32_t* symbo
                                        double sigma, double delay_penalty, const float* lse_tok, const float* lse_dur,
                                        const float* gx_band, const float* gy_band, const float* scale, int scale_stride,
                                        float scale_mul, float* glogits, int B, int T, int S, int C, int r, void* stream) {
-  const char* what = "tdt_pruned_band_bwd_scaled";
-  clear_error();
   (void)delay_penalty;   // a constant added to px: no gradient
-  FTR_TRY(tdt_check_head(what, durations, N, sigma, termination_symbol, C));
-  FTR_TRY(check_sizes(what, B >= 0 && T >= 1 && S >= 0 && r >= 1));
-  FTR_TRY(check_scale_stride(what, scale_stride));
-  if (B == 0) return FTR_OK;
-  FTR_TRY(pointers_then_device(what, logits && ranges && lse_tok && lse_dur && gx_band && gy_band && glogits && (symbols || S == 0)));
-  return tdt_band_bwd(logits, symbols, ranges, boundary, termination_symbol, durations, N, lse_tok, lse_dur, gx_band, gy_band,
-                      Scale{scale, scale_stride, scale_mul}, glogits, B, T, S, C, r, stream_of(stream));
+  return tdt_builder_bwd_entry(1, "tdt_pruned_band_bwd_scaled", logits, symbols, ranges, boundary, termination_symbol, durations, N,
+                               sigma, lse_tok, lse_dur, gx_band, gy_band, scale, scale_stride, scale_mul, glogits, B, T, S, C, r, stream);
 }
 
 // ---- include/ftr_tdt_mix.h: the TDT loss mixed with the ordinary loss on the token head (the <MIX> kernels of
@@ -1389,25 +1421,16 @@ int ftr_mutual_information_band_multiblank_f32(const float* px_band, const float
                                                size_t workspace_floats, float* ans, float* gx_band, float* gy_band, int B,
                                                int T, int S, int r, void* stream) {
   const char* what = "mutual_information_band_multiblank";
-  clear_error();
-  if (D < 1 || D > 8) {                      // the length of the list itself: the domain, before the list is read
-    set_error("%s: D = %d is outside the kernel's domain (1..8 blanks)", what, D);
-    return FTR_ERR_UNSUPPORTED;
-  }
-  FTR_TRY(mb_check_durations(what, durations, D, false));
-  FTR_TRY(check_sizes(what, B >= 0 && T >= 1 && S >= 0 && r >= 1));
-  if (!mi_band_tdt_supported(T, S, r, 1, D, kBandMultiblankDomain)) {
-    set_error("%s: T=%d S=%d r=%d is outside the kernel's domain (r <= 15)", what, T, S, r);
-    return FTR_ERR_UNSUPPORTED;
-  }
-  if (B == 0) return FTR_OK;
-  FTR_TRY(check_ws_size(what, workspace_floats, mi_band_tdt_workspace_floats(B, T, S, r, 1, D, kBandMultiblankDomain), "floats"));
-  FTR_REQUIRE(px_band && py_band && ranges && workspace && ans, "%s: null px_band / py_band / ranges / workspace / ans", what);
-  FTR_REQUIRE((gx_band != nullptr) == (gy_band != nullptr), "%s: gx_band and gy_band must both be given or both be null", what);
-  FTR_TRY(check_ws_aligned(what, workspace));
-  FTR_TRY(device_ok());
-  return mi_band_multiblank(px_band, py_band, ranges, boundary, durations, D, workspace, workspace_floats, ans, gx_band, gy_band, B,
-                            T, S, r, stream_of(stream));
+  const int32_t tok[1] = {0};    // the chain's one token move, of duration 0: px_band [B,T,r] is its one plane
+  const auto lists = [&] {
+    if (D < 1 || D > 8) {                      // the length of the list itself: the domain, before the list is read
+      set_error("%s: D = %d is outside the kernel's domain (1..8 blanks)", what, D);
+      return (int)FTR_ERR_UNSUPPORTED;
+    }
+    return mb_check_durations(what, durations, D, false);
+  };
+  return mi_band_duration_entry(what, kBandMultiblankDomain, lists, px_band, py_band, ranges, boundary, tok, 1, durations, D, workspace,
+                                workspace_floats, ans, gx_band, gy_band, B, T, S, r, stream);
 }
 
 // ---- include/ftr_band_viterbi.h: best-path alignment on the pruned band itself (csrc/mi_band_viterbi.hip).  The move
@@ -1426,8 +1449,7 @@ int ftr_mutual_information_band_viterbi_f32(const float* px_band, const float* p
                                             int T, int S, int r, void* stream) {
   const char* what = "mutual_information_band_viterbi";
   clear_error();
-  FTR_TRY(tdt_check_list(what, "token_durations", token_durations, N, 8, 0));
-  FTR_TRY(tdt_check_list(what, "blank_durations", blank_durations, Ny, 8, 1, 32));
+  FTR_TRY(tdt_check_lists(what, token_durations, N, blank_durations, Ny, 8, 32));
   FTR_TRY(check_sizes(what, B >= 0 && T >= 1 && S >= 0 && r >= 1));
   if (!mi_band_viterbi_supported(T, S, r, N, Ny)) {
     set_error("%s: T=%d S=%d r=%d N=%d Ny=%d is outside the kernel's domain (r <= 15, N + Ny <= 9)", what, T, S, r, N, Ny);
@@ -1448,17 +1470,8 @@ int ftr_multiblank_pruned_band_fwd_f32(const float* logits, const int32_t* symbo
                                        const int32_t* boundary, int termination_symbol, const int32_t* big_blank_ids,
                                        const int32_t* durations, int D, double sigma, double delay_penalty, float* lse,
                                        float* px_band, float* py_band, int B, int T, int S, int C, int r, void* stream) {
-  const char* what = "multiblank_pruned_band_fwd";
-  clear_error();
-  FTR_TRY(mb_check_durations(what, durations, D, true));
-  FTR_TRY(mb_check_ids(what, big_blank_ids, D, termination_symbol, C));
-  FTR_TRY(check_sizes(what, B >= 0 && T >= 1 && S >= 0 && r >= 1));
-  FTR_TRY(check_s_range(what, r, S));
-  FTR_REQUIRE(sigma >= 0.0, "%s: sigma = %g must not be negative", what, sigma);
-  if (B == 0) return FTR_OK;
-  FTR_TRY(pointers_then_device(what, logits && ranges && lse && px_band && py_band && (symbols || S == 0)));
-  return multiblank_band_fwd(logits, symbols, ranges, boundary, termination_symbol, big_blank_ids, durations, D, sigma,
-                             delay_penalty, lse, px_band, py_band, B, T, S, C, r, stream_of(stream));
+  return mb_builder_fwd_entry(1, "multiblank_pruned_band_fwd", logits, symbols, ranges, boundary, termination_symbol, big_blank_ids,
+                              durations, D, sigma, delay_penalty, lse, px_band, py_band, B, T, S, C, r, stream);
 }
 
 int ftr_multiblank_pruned_band_bwd_scaled_f32(const float* logits, const int32_t* symbols, const int32_t* ranges,
@@ -1466,16 +1479,9 @@ int ftr_multiblank_pruned_band_bwd_scaled_f32(const float* logits, const int32_t
                                               const int32_t* durations, int D, const float* lse, const float* gx_band,
                                               const float* gy_band, const float* scale, int scale_stride, float scale_mul,
                                               float* glogits, int B, int T, int S, int C, int r, void* stream) {
-  const char* what = "multiblank_pruned_band_bwd_scaled";
-  clear_error();
-  FTR_TRY(mb_check_durations(what, durations, D, true));
-  FTR_TRY(mb_check_ids(what, big_blank_ids, D, termination_symbol, C));
-  FTR_TRY(check_sizes(what, B >= 0 && T >= 1 && S >= 0 && r >= 1));
-  FTR_TRY(check_scale_stride(what, scale_stride));
-  if (B == 0) return FTR_OK;
-  FTR_TRY(pointers_then_device(what, logits && ranges && lse && gx_band && gy_band && glogits && (symbols || S == 0)));
-  return multiblank_band_bwd(logits, symbols, ranges, boundary, termination_symbol, big_blank_ids, durations, D, lse, gx_band,
-                             gy_band, Scale{scale, scale_stride, scale_mul}, glogits, B, T, S, C, r, stream_of(stream));
+  return mb_builder_bwd_entry(1, "multiblank_pruned_band_bwd_scaled", logits, symbols, ranges, boundary, termination_symbol,
+                              big_blank_ids, durations, D, lse, gx_band, gy_band, scale, scale_stride, scale_mul, glogits, B, T, S, C, r,
+                              stream);
 }
 
 // ---- include/ftr_kd.h, include/ftr_kd_fact.h: knowledge distillation on the pruned band (csrc/pruned_kd.hip)

@@ -241,14 +241,4 @@ int mi_band_tdt(const float* pxb, const float* pyb, const int32_t* ranges, const
   return check_launch("band_tdt_occupancy");
 }
 
-// the multi-blank recursion: the same chain with one token move of duration 0 (px_band [B,T,r] is its one plane) and the
-// D blank moves of `durations`
-int mi_band_multiblank(const float* pxb, const float* pyb, const int32_t* ranges, const int32_t* boundary, const int32_t* durations,
-                       int D, float* ws, size_t ws_floats, float* ans, float* gxb, float* gyb, int B, int T, int S, int r,
-                       hipStream_t st) {
-  const int32_t tok[1] = {0};
-  return mi_band_tdt(pxb, pyb, ranges, boundary, tok, 1, durations, D, ws, ws_floats, ans, gxb, gyb, B, T, S, r,
-                     kBandMultiblankDomain, "mutual_information_band_multiblank", st);
-}
-
 }  // namespace ftr

@@ -524,66 +524,44 @@ MbCols mb_cols(int blank, const int32_t* big_ids, const int32_t* durations, int 
 }
 }  // namespace
 
-int multiblank_logprobs_fwd(const float* logits, const int32_t* symbols, const int32_t* ranges, const int32_t* boundary,
-                            int blank, const int32_t* big_ids, const int32_t* durations, int D, double sigma,
-                            double delay_penalty, float* lse, float* px, float* py, int B, int T, int S, int C, int r,
-                            hipStream_t st) {
+// band: px / py and gpx / gpy are the band-shaped planes [B,T,r] / [B,D,T,r] (include/ftr_band_multiblank.h), else the lattices
+int multiblank_builder_fwd(bool band, const float* logits, const int32_t* symbols, const int32_t* ranges, const int32_t* boundary,
+                           int blank, const int32_t* big_ids, const int32_t* durations, int D, double sigma, double delay_penalty,
+                           float* lse, float* px, float* py, int B, int T, int S, int C, int r, hipStream_t st) {
   const size_t rows = (size_t)B * T * r;
   if (rows == 0) return FTR_OK;
-  { const int rc32 = require_rows_32bit("multiblank_logprobs_fwd", rows); if (rc32 != FTR_OK) return rc32; }
+  { const int rc32 = require_rows_32bit(band ? "multiblank_pruned_band_fwd" : "multiblank_logprobs_fwd", rows); if (rc32 != FTR_OK) return rc32; }
   int rc = lse_rows(logits, lse, rows, C, blank, 0, st);
   if (rc != FTR_OK) return rc;
+  const MbCols mc = mb_cols(blank, big_ids, durations, D);
+  if (band) {
+    hipLaunchKernelGGL(mb_to_band_kernel, dim3((unsigned)((rows + 255) / 256)), dim3(256), 0, st, logits, symbols, ranges, boundary,
+                       lse, mc, (float)sigma, delay_penalty, px, py, rows, T, S, C, r);
+    return check_launch("multiblank_to_band");
+  }
   const int threads = 256;
   const dim3 grid((T + 1 + threads - 1) / threads, S + 1, B);
-  hipLaunchKernelGGL(mb_to_lattice_kernel, grid, dim3(threads), 0, st, logits, symbols, ranges, boundary, lse,
-                     mb_cols(blank, big_ids, durations, D), (float)sigma, delay_penalty, px, py, T, S, C, r);
+  hipLaunchKernelGGL(mb_to_lattice_kernel, grid, dim3(threads), 0, st, logits, symbols, ranges, boundary, lse, mc, (float)sigma,
+                     delay_penalty, px, py, T, S, C, r);
   return check_launch("multiblank_to_lattice");
 }
 
-int multiblank_logprobs_bwd(const float* logits, const int32_t* symbols, const int32_t* ranges, const int32_t* boundary,
-                            int blank, const int32_t* big_ids, const int32_t* durations, int D, const float* lse,
-                            const float* gpx, const float* gpy, Scale scale, float* glogits, int B, int T, int S, int C,
-                            int r, hipStream_t st) {
+int multiblank_builder_bwd(bool band, const float* logits, const int32_t* symbols, const int32_t* ranges, const int32_t* boundary,
+                           int blank, const int32_t* big_ids, const int32_t* durations, int D, const float* lse, const float* gpx,
+                           const float* gpy, Scale scale, float* glogits, int B, int T, int S, int C, int r, hipStream_t st) {
   const size_t rows = (size_t)B * T * r;
   if (rows == 0) return FTR_OK;
-  { const int rc32 = require_rows_32bit("multiblank_logprobs_bwd", rows); if (rc32 != FTR_OK) return rc32; }
+  { const int rc32 = require_rows_32bit(band ? "multiblank_pruned_band_bwd" : "multiblank_logprobs_bwd", rows); if (rc32 != FTR_OK) return rc32; }
   const int wpb = 4;
   const unsigned blocks = (unsigned)((rows + wpb - 1) / wpb);
   const MbCols mc = mb_cols(blank, big_ids, durations, D);
   dispatch((C & 3) == 0, [&](auto vec) {
-    hipLaunchKernelGGL((mb_grad_kernel<decltype(vec)::value, false>), dim3(blocks), dim3(64 * wpb), 0, st, logits, symbols, ranges, boundary, lse,
-                       gpx, gpy, scale, mc, glogits, rows, T, S, C, r);
+    dispatch(band, [&](auto bnd) {
+      hipLaunchKernelGGL((mb_grad_kernel<decltype(vec)::value, decltype(bnd)::value>), dim3(blocks), dim3(64 * wpb), 0, st, logits,
+                         symbols, ranges, boundary, lse, gpx, gpy, scale, mc, glogits, rows, T, S, C, r);
+    });
   });
-  return check_launch("multiblank_grad");
-}
-
-int multiblank_band_fwd(const float* logits, const int32_t* symbols, const int32_t* ranges, const int32_t* boundary, int blank,
-                        const int32_t* big_ids, const int32_t* durations, int D, double sigma, double delay_penalty, float* lse,
-                        float* pxb, float* pyb, int B, int T, int S, int C, int r, hipStream_t st) {
-  const size_t rows = (size_t)B * T * r;
-  if (rows == 0) return FTR_OK;
-  { const int rc32 = require_rows_32bit("multiblank_pruned_band_fwd", rows); if (rc32 != FTR_OK) return rc32; }
-  int rc = lse_rows(logits, lse, rows, C, blank, 0, st);
-  if (rc != FTR_OK) return rc;
-  hipLaunchKernelGGL(mb_to_band_kernel, dim3((unsigned)((rows + 255) / 256)), dim3(256), 0, st, logits, symbols, ranges, boundary,
-                     lse, mb_cols(blank, big_ids, durations, D), (float)sigma, delay_penalty, pxb, pyb, rows, T, S, C, r);
-  return check_launch("multiblank_to_band");
-}
-
-int multiblank_band_bwd(const float* logits, const int32_t* symbols, const int32_t* ranges, const int32_t* boundary, int blank,
-                        const int32_t* big_ids, const int32_t* durations, int D, const float* lse, const float* gxb,
-                        const float* gyb, Scale scale, float* glogits, int B, int T, int S, int C, int r, hipStream_t st) {
-  const size_t rows = (size_t)B * T * r;
-  if (rows == 0) return FTR_OK;
-  { const int rc32 = require_rows_32bit("multiblank_pruned_band_bwd", rows); if (rc32 != FTR_OK) return rc32; }
-  const int wpb = 4;
-  const unsigned blocks = (unsigned)((rows + wpb - 1) / wpb);
-  const MbCols mc = mb_cols(blank, big_ids, durations, D);
-  dispatch((C & 3) == 0, [&](auto vec) {
-    hipLaunchKernelGGL((mb_grad_kernel<decltype(vec)::value, true>), dim3(blocks), dim3(64 * wpb), 0, st, logits, symbols, ranges, boundary, lse,
-                       gxb, gyb, scale, mc, glogits, rows, T, S, C, r);
-  });
-  return check_launch("multiblank_band_grad");
+  return check_launch(band ? "multiblank_band_grad" : "multiblank_grad");
 }
 
 }  // namespace ftr

@@ -394,32 +394,19 @@ int tdt_bwd_launch(bool band, const char* what, const float* logits, const int32
 }
 }  // namespace
 
-int tdt_logprobs_fwd(const float* logits, const int32_t* symbols, const int32_t* ranges, const int32_t* boundary, int blank,
-                     const int32_t* durations, int N, double sigma, double delay_penalty, float* lse_tok, float* lse_dur,
-                     float* px, float* py, int B, int T, int S, int C, int r, hipStream_t st) {
-  return tdt_fwd_launch(false, "tdt_logprobs_fwd", logits, symbols, ranges, boundary, blank, durations, N, sigma, delay_penalty,
-                        lse_tok, lse_dur, px, py, nullptr, B, T, S, C, r, st);
+// band: px / py and gpx / gpy are the band-shaped planes [B,N,T,r] / [B,Ny,T,r] (include/ftr_band_tdt.h), else the lattices
+int tdt_builder_fwd(bool band, const float* logits, const int32_t* symbols, const int32_t* ranges, const int32_t* boundary, int blank,
+                    const int32_t* durations, int N, double sigma, double delay_penalty, float* lse_tok, float* lse_dur,
+                    float* px, float* py, int B, int T, int S, int C, int r, hipStream_t st) {
+  return tdt_fwd_launch(band, band ? "tdt_pruned_band_fwd" : "tdt_logprobs_fwd", logits, symbols, ranges, boundary, blank, durations, N,
+                        sigma, delay_penalty, lse_tok, lse_dur, px, py, nullptr, B, T, S, C, r, st);
 }
 
-int tdt_logprobs_bwd(const float* logits, const int32_t* symbols, const int32_t* ranges, const int32_t* boundary, int blank,
-                     const int32_t* durations, int N, const float* lse_tok, const float* lse_dur, const float* gpx,
-                     const float* gpy, Scale scale, float* glogits, int B, int T, int S, int C, int r, hipStream_t st) {
-  return tdt_bwd_launch(false, "tdt_logprobs_bwd", logits, symbols, ranges, boundary, blank, durations, N, lse_tok, lse_dur, gpx,
-                        gpy, scale, nullptr, glogits, B, T, S, C, r, st);
-}
-
-int tdt_band_fwd(const float* logits, const int32_t* symbols, const int32_t* ranges, const int32_t* boundary, int blank,
-                 const int32_t* durations, int N, double sigma, double delay_penalty, float* lse_tok, float* lse_dur,
-                 float* pxb, float* pyb, int B, int T, int S, int C, int r, hipStream_t st) {
-  return tdt_fwd_launch(true, "tdt_pruned_band_fwd", logits, symbols, ranges, boundary, blank, durations, N, sigma, delay_penalty,
-                        lse_tok, lse_dur, pxb, pyb, nullptr, B, T, S, C, r, st);
-}
-
-int tdt_band_bwd(const float* logits, const int32_t* symbols, const int32_t* ranges, const int32_t* boundary, int blank,
-                 const int32_t* durations, int N, const float* lse_tok, const float* lse_dur, const float* gxb,
-                 const float* gyb, Scale scale, float* glogits, int B, int T, int S, int C, int r, hipStream_t st) {
-  return tdt_bwd_launch(true, "tdt_pruned_band_bwd", logits, symbols, ranges, boundary, blank, durations, N, lse_tok, lse_dur, gxb,
-                        gyb, scale, nullptr, glogits, B, T, S, C, r, st);
+int tdt_builder_bwd(bool band, const float* logits, const int32_t* symbols, const int32_t* ranges, const int32_t* boundary, int blank,
+                    const int32_t* durations, int N, const float* lse_tok, const float* lse_dur, const float* gpx,
+                    const float* gpy, Scale scale, float* glogits, int B, int T, int S, int C, int r, hipStream_t st) {
+  return tdt_bwd_launch(band, band ? "tdt_pruned_band_bwd" : "tdt_logprobs_bwd", logits, symbols, ranges, boundary, blank, durations, N,
+                        lse_tok, lse_dur, gpx, gpy, scale, nullptr, glogits, B, T, S, C, r, st);
 }
 
 // include/ftr_tdt_mix.h.  band: the band-shaped planes, else the lattices; parts: TDT_PART_* bits, which planes are written

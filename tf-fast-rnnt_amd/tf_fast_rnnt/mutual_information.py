@@ -17,6 +17,7 @@ Differences from the reference, all deliberate (SURVEY.md section 7 "hard parts"
 """
 from __future__ import annotations
 
+import ctypes
 from typing import Optional, Tuple, Union
 
 import torch
@@ -106,7 +107,6 @@ def check_workspace_status() -> int:
     """Synchronises and reads the sticky status word of every cached workspace (ftr_mutual_information_status): returns
     the OR of them and drops the workspaces that report a problem, so that the next launch starts from a clean one.
     0 = fine.  Diagnostic: a non-zero value means a launch gave up waiting for a producer and answered NaN."""
-    import ctypes
     L = _lib.lib()
     bad = 0
     for key, w in list(_Workspace._cache.items()):
@@ -235,10 +235,14 @@ def _check_durations(durations) -> Tuple[int, ...]:
     return durs
 
 
-def mb_forward_backward(px: torch.Tensor, py: torch.Tensor, durations, boundary: Optional[torch.Tensor], need_grads: bool):
-    """The multi-blank recursion on raw tensors (no autograd): forward and, when wanted, the backward seeded with ones,
-    back to back on torch's current stream.  Returns (ans, px_grad|None, py_grad|None)."""
-    import ctypes
+def _f64_workspace(nws: int, device) -> torch.Tensor:
+    """At least ``nws`` floats, never empty, as float64: the 8-byte alignment the duration entries ask of a workspace."""
+    return torch.empty((max(nws, 2) + 1) // 2, dtype=torch.float64, device=device)
+
+
+def _multiblank_lattice_inputs(px: torch.Tensor, py: torch.Tensor, durations):
+    """Validation of the multi-blank lattice and the host array the launches read.  Returns (px, py, B, S, T, lists) with
+    px and py contiguous and ``lists`` = (durations, D) as the entries take them."""
     _require_gpu(px, "px"); _require_gpu(py, "py")
     if px.dtype != torch.float32 or py.dtype != torch.float32:
         raise TypeError("px and py must be float32")
@@ -252,24 +256,7 @@ def mb_forward_backward(px: torch.Tensor, py: torch.Tensor, durations, boundary:
         raise ValueError(f"px.shape[-1]={T1} must be T+1 with T=py.shape[-1]={T} (regular type only)")
     if tuple(py.shape) != (B, D, S + 1, T):
         raise ValueError(f"py must have shape {(B, D, S + 1, T)}, got {tuple(py.shape)}")
-    px = px.contiguous(); py = py.contiguous()
-    boundary = _as_boundary(boundary, B, px.device)
-    dur_arr = (ctypes.c_int32 * D)(*durs)       # read by the launch itself: no device copy, no host synchronisation
-    L = _lib.lib()
-    with torch.cuda.device(px.device):
-        st = _stream_ptr(px)
-        nws = L.ftr_mutual_information_multiblank_workspace_floats(B, S, T)
-        ws = torch.empty((max(nws, 2) + 1) // 2, dtype=torch.float64, device=px.device)
-        ans = torch.empty((B,), dtype=torch.float32, device=px.device)
-        _lib.call("ftr_mutual_information_multiblank_fwd_f32", _ptr(px), _ptr(py), _ptr(boundary), dur_arr, D, _ptr(ws), nws,
-                  _ptr(ans), B, S, T, st)
-        if not need_grads:
-            return ans, None, None
-        px_grad = torch.empty_like(px)
-        py_grad = torch.empty_like(py)
-        _lib.call("ftr_mutual_information_multiblank_bwd_f32", _ptr(px), _ptr(py), _ptr(boundary), dur_arr, D, _ptr(ws), nws,
-                  None, _ptr(px_grad), _ptr(py_grad), B, S, T, st)
-    return ans, px_grad, py_grad
+    return px.contiguous(), py.contiguous(), B, S, T, ((ctypes.c_int32 * D)(*durs), D)    # read by the launch itself: no device copy
 
 
 def mutual_information_recursion_multiblank(
@@ -294,7 +281,7 @@ def mutual_information_recursion_multiblank(
     w.r.t. px and py; asynchronous on torch's current stream, no host read (capturable)."""
     durations = tuple(durations)
     ans, px_grad, py_grad = _Occupancies.apply(px, py, calc_gradients, "mutual_information_recursion_multiblank",
-                                               lambda x, y, need: mb_forward_backward(x, y, durations, boundary, need))
+                                               lambda x, y, need: duration_forward_backward(x, y, None, durations, boundary, need))
     return (ans, (px_grad, py_grad)) if calc_gradients else ans
 
 
@@ -317,7 +304,6 @@ def _duration_lattice_inputs(px: torch.Tensor, py: torch.Tensor, token_durations
                              max_moves: int = 10):
     """Validation of the TDT-shaped entries and the host arrays the launches read.  Returns
     (px, py, B, S, T, tok, blk, tok_arr, blk_arr) with px and py contiguous."""
-    import ctypes
     _require_gpu(px, "px"); _require_gpu(py, "py")
     if px.dtype != torch.float32 or py.dtype != torch.float32:
         raise TypeError("px and py must be float32")
@@ -338,27 +324,33 @@ def _duration_lattice_inputs(px: torch.Tensor, py: torch.Tensor, token_durations
     return px.contiguous(), py.contiguous(), B, S, T, tok, blk, tok_arr, blk_arr
 
 
-def tdt_forward_backward(px: torch.Tensor, py: torch.Tensor, token_durations, blank_durations,
-                         boundary: Optional[torch.Tensor], need_grads: bool):
-    """The TDT recursion on raw tensors (no autograd): forward and, when wanted, the backward seeded with ones, back to
-    back on torch's current stream.  Returns (ans, px_grad|None, py_grad|None)."""
-    px, py, B, S, T, tok, blk, tok_arr, blk_arr = _duration_lattice_inputs(px, py, token_durations, blank_durations, 16)
-    Dx, Dy = len(tok), len(blk)
+def duration_forward_backward(px: torch.Tensor, py: torch.Tensor, token_durations, blank_durations,
+                              boundary: Optional[torch.Tensor], need_grads: bool):
+    """The multi-blank (``token_durations`` None: px [B,S,T+1], the blanks of ``blank_durations``) or the TDT recursion on
+    raw tensors (no autograd): forward and, when wanted, the backward seeded with ones, back to back on torch's current
+    stream.  Returns (ans, px_grad|None, py_grad|None)."""
+    if token_durations is None:
+        entry = "multiblank"
+        px, py, B, S, T, lists = _multiblank_lattice_inputs(px, py, blank_durations)
+    else:
+        entry = "tdt"
+        px, py, B, S, T, tok, blk, tok_arr, blk_arr = _duration_lattice_inputs(px, py, token_durations, blank_durations, 16)
+        lists = (tok_arr, len(tok), blk_arr, len(blk))
     boundary = _as_boundary(boundary, B, px.device)
     L = _lib.lib()
     with torch.cuda.device(px.device):
         st = _stream_ptr(px)
-        nws = L.ftr_mutual_information_tdt_workspace_floats(B, S, T)
-        ws = torch.empty((max(nws, 2) + 1) // 2, dtype=torch.float64, device=px.device)
+        nws = getattr(L, f"ftr_mutual_information_{entry}_workspace_floats")(B, S, T)
+        ws = _f64_workspace(nws, px.device)
         ans = torch.empty((B,), dtype=torch.float32, device=px.device)
-        _lib.call("ftr_mutual_information_tdt_fwd_f32", _ptr(px), _ptr(py), _ptr(boundary), tok_arr, Dx, blk_arr, Dy,
-                  _ptr(ws), nws, _ptr(ans), B, S, T, st)
+        _lib.call(f"ftr_mutual_information_{entry}_fwd_f32", _ptr(px), _ptr(py), _ptr(boundary), *lists, _ptr(ws), nws, _ptr(ans),
+                  B, S, T, st)
         if not need_grads:
             return ans, None, None
         px_grad = torch.empty_like(px)
         py_grad = torch.empty_like(py)
-        _lib.call("ftr_mutual_information_tdt_bwd_f32", _ptr(px), _ptr(py), _ptr(boundary), tok_arr, Dx, blk_arr, Dy,
-                  _ptr(ws), nws, None, _ptr(px_grad), _ptr(py_grad), B, S, T, st)
+        _lib.call(f"ftr_mutual_information_{entry}_bwd_f32", _ptr(px), _ptr(py), _ptr(boundary), *lists, _ptr(ws), nws, None,
+                  _ptr(px_grad), _ptr(py_grad), B, S, T, st)
     return ans, px_grad, py_grad
 
 
@@ -389,7 +381,7 @@ def mutual_information_recursion_tdt(
     current stream, no host read (capturable)."""
     tok, blk = tuple(token_durations), tuple(blank_durations)
     ans, px_grad, py_grad = _Occupancies.apply(px, py, calc_gradients, "mutual_information_recursion_tdt",
-                                               lambda x, y, need: tdt_forward_backward(x, y, tok, blk, boundary, need))
+                                               lambda x, y, need: duration_forward_backward(x, y, tok, blk, boundary, need))
     return (ans, (px_grad, py_grad)) if calc_gradients else ans
 
 
@@ -417,40 +409,49 @@ def band_tdt_supported(T: int, S: int, r: int, N: int, Ny: int) -> bool:
     return _lib.lib().ftr_mutual_information_band_tdt_supported(int(T), int(S), int(r), int(N), int(Ny)) != 0
 
 
-def band_tdt_forward_backward(px_band: torch.Tensor, py_band: torch.Tensor, ranges: torch.Tensor, S: int, token_durations,
-                              blank_durations, boundary: Optional[torch.Tensor], need_grads: bool):
-    """The TDT recursion on band-shaped operands, raw tensors (no autograd): one chain launch for both directions and
-    one occupancy launch on torch's current stream.  Returns (ans, gx_band|None, gy_band|None); the occupancies are
-    seeded with ones.  ``ranges`` must be a band (the caller's business: _is_band of rnnt_loss.py)."""
-    import ctypes
-    tok, blk = _check_tdt_moves(token_durations, blank_durations, 16)
-    N, Ny = len(tok), len(blk)
-    B, _, T, r = px_band.shape
-    tok_arr = (ctypes.c_int32 * N)(*tok)        # read by the launch itself: no device copy, no host synchronisation
-    blk_arr = (ctypes.c_int32 * Ny)(*blk)
+def band_multiblank_supported(T: int, S: int, r: int, D: int) -> bool:
+    """Does the band-native multi-blank recursion (the multi-blank domain of csrc/mi_band_tdt.hip) cover these sizes?"""
+    return _lib.lib().ftr_mutual_information_band_multiblank_supported(int(T), int(S), int(r), int(D)) != 0
+
+
+def band_duration_forward_backward(px_band: torch.Tensor, py_band: torch.Tensor, ranges: torch.Tensor, S: int, token_durations,
+                                   blank_durations, boundary: Optional[torch.Tensor], need_grads: bool):
+    """The multi-blank (``token_durations`` None: px_band [B,T,r]) or the TDT recursion on band-shaped operands, raw
+    tensors (no autograd): one chain launch for both directions and one occupancy launch on torch's current stream.
+    Returns (ans, gx_band|None, gy_band|None); the occupancies are seeded with ones.  ``ranges`` must be a band (the
+    caller's business: _is_band of rnnt_loss.py)."""
+    if token_durations is None:
+        entry = "multiblank"
+        durs = _check_durations(blank_durations)
+        lists = ((ctypes.c_int32 * len(durs))(*durs), len(durs))     # read by the launch itself: no device copy, no host synchronisation
+    else:
+        entry = "tdt"
+        tok, blk = _check_tdt_moves(token_durations, blank_durations, 16)
+        lists = ((ctypes.c_int32 * len(tok))(*tok), len(tok), (ctypes.c_int32 * len(blk))(*blk), len(blk))
+    B, (T, r) = px_band.shape[0], px_band.shape[-2:]
     L = _lib.lib()
     with torch.cuda.device(px_band.device):
         st = _stream_ptr(px_band)
-        nws = L.ftr_mutual_information_band_tdt_workspace_floats(B, T, int(S), r, N, Ny)
-        ws = torch.empty((max(nws, 2) + 1) // 2, dtype=torch.float64, device=px_band.device)
+        nws = getattr(L, f"ftr_mutual_information_band_{entry}_workspace_floats")(B, T, int(S), r, *lists[1::2])   # the lengths
+        ws = _f64_workspace(nws, px_band.device)
         ans = torch.empty((B,), dtype=torch.float32, device=px_band.device)
         gx = torch.empty_like(px_band) if need_grads else None
         gy = torch.empty_like(py_band) if need_grads else None
-        _lib.call("ftr_mutual_information_band_tdt_f32", _ptr(px_band), _ptr(py_band), _ptr(ranges), _ptr(boundary), tok_arr, N,
-                  blk_arr, Ny, _ptr(ws), nws, _ptr(ans), _ptr(gx), _ptr(gy), B, T, int(S), r, st)
-        _lib.band_tdt_recursions += 1
+        _lib.call(f"ftr_mutual_information_band_{entry}_f32", _ptr(px_band), _ptr(py_band), _ptr(ranges), _ptr(boundary), *lists,
+                  _ptr(ws), nws, _ptr(ans), _ptr(gx), _ptr(gy), B, T, int(S), r, st)
+        setattr(_lib, f"band_{entry}_recursions", getattr(_lib, f"band_{entry}_recursions") + 1)
     return ans, gx, gy
 
 
-class _BandTdtRecursion(torch.autograd.Function):
-    """mutual_information_recursion_tdt_band: the occupancies are computed with the answer whenever an operand needs a
-    gradient, and backward() scales them by the upstream gradient."""
+class _BandDurationRecursion(torch.autograd.Function):
+    """mutual_information_recursion_tdt_band and _multiblank_band (``tok`` None): the occupancies are computed with the
+    answer whenever an operand needs a gradient, and backward() scales them by the upstream gradient."""
 
     @staticmethod
     def forward(ctx, px_band, py_band, ranges, S, tok, blk, boundary):
         need = px_band.requires_grad or py_band.requires_grad
-        ans, gx, gy = band_tdt_forward_backward(px_band.detach().contiguous(), py_band.detach().contiguous(), ranges, S, tok,
-                                                blk, boundary, need)
+        ans, gx, gy = band_duration_forward_backward(px_band.detach().contiguous(), py_band.detach().contiguous(), ranges, S,
+                                                     tok, blk, boundary, need)
         if need:
             ctx.save_for_backward(gx, gy)
         return ans
@@ -458,8 +459,27 @@ class _BandTdtRecursion(torch.autograd.Function):
     @staticmethod
     def backward(ctx, g_ans):
         gx, gy = ctx.saved_tensors
-        g = g_ans.reshape(-1, 1, 1, 1).to(gx.dtype)
-        return gx * g, gy * g, None, None, None, None, None
+        g = g_ans.to(gx.dtype)
+        return gx * g.reshape((-1,) + (1,) * (gx.dim() - 1)), gy * g.reshape(-1, 1, 1, 1), None, None, None, None, None
+
+
+def _band_recursion_inputs(px_band: torch.Tensor, ranges, boundary, S: Optional[int], supported, what: str = "recursion"):
+    """What the band ops check alike, behind the checks of their own operands and lists: ranges [B,T,r] (made int32), the
+    boundary, S (``ranges.max()`` when omitted: one host read) and the sizes, which ``supported(T, S, r)`` must cover.
+    Returns (ranges, boundary, S)."""
+    B, (T, r) = px_band.shape[0], px_band.shape[-2:]
+    ranges = torch.as_tensor(ranges, device=px_band.device).to(torch.int32).contiguous()
+    if tuple(ranges.shape) != (B, T, r):
+        raise ValueError(f"ranges must have shape {(B, T, r)}, got {tuple(ranges.shape)}")
+    boundary = _as_boundary(boundary, B, px_band.device)
+    if S is None:       # the last band row: one host read (give S to stay asynchronous)
+        S = int(ranges.max().item()) if ranges.numel() else 0
+    S = int(S)
+    if S < 0 or T < 1:
+        raise ValueError(f"S={S} must not be negative and T={T} must be positive")
+    if not supported(T, S, r):
+        raise ValueError(f"the band {what} does not cover T={T}, S={S}, r={r} (r <= 15)")
+    return ranges, boundary, S
 
 
 def mutual_information_recursion_tdt_band(
@@ -499,67 +519,9 @@ def mutual_information_recursion_tdt_band(
     if tuple(px_band.shape) != (B, len(tok), T, r) or tuple(py_band.shape) != (B, len(blk), T, r):
         raise ValueError(f"px_band must have shape {(B, len(tok), T, r)} and py_band {(B, len(blk), T, r)}, got "
                          f"{tuple(px_band.shape)} and {tuple(py_band.shape)}")
-    ranges = torch.as_tensor(ranges, device=px_band.device).to(torch.int32).contiguous()
-    if tuple(ranges.shape) != (B, T, r):
-        raise ValueError(f"ranges must have shape {(B, T, r)}, got {tuple(ranges.shape)}")
-    boundary = _as_boundary(boundary, B, px_band.device)
-    if S is None:       # the last band row: one host read (give S to stay asynchronous)
-        S = int(ranges.max().item()) if ranges.numel() else 0
-    S = int(S)
-    if S < 0 or T < 1:
-        raise ValueError(f"S={S} must not be negative and T={T} must be positive")
-    if not band_tdt_supported(T, S, r, len(tok), len(blk)):
-        raise ValueError(f"the band recursion does not cover T={T}, S={S}, r={r} (r <= 15)")
-    return _BandTdtRecursion.apply(px_band, py_band, ranges, S, tok, blk, boundary)
-
-
-def band_multiblank_supported(T: int, S: int, r: int, D: int) -> bool:
-    """Does the band-native multi-blank recursion (the multi-blank domain of csrc/mi_band_tdt.hip) cover these sizes?"""
-    return _lib.lib().ftr_mutual_information_band_multiblank_supported(int(T), int(S), int(r), int(D)) != 0
-
-
-def band_multiblank_forward_backward(px_band: torch.Tensor, py_band: torch.Tensor, ranges: torch.Tensor, S: int, durations,
-                                     boundary: Optional[torch.Tensor], need_grads: bool):
-    """The multi-blank recursion on band-shaped operands, raw tensors (no autograd): one chain launch for both directions
-    and one occupancy launch on torch's current stream.  Returns (ans, gx_band|None, gy_band|None); the occupancies are
-    seeded with ones.  ``ranges`` must be a band (the caller's business: _is_band of rnnt_loss.py)."""
-    import ctypes
-    durs = _check_durations(durations)
-    D = len(durs)
-    B, T, r = px_band.shape
-    dur_arr = (ctypes.c_int32 * D)(*durs)       # read by the launch itself: no device copy, no host synchronisation
-    L = _lib.lib()
-    with torch.cuda.device(px_band.device):
-        st = _stream_ptr(px_band)
-        nws = L.ftr_mutual_information_band_multiblank_workspace_floats(B, T, int(S), r, D)
-        ws = torch.empty((max(nws, 2) + 1) // 2, dtype=torch.float64, device=px_band.device)
-        ans = torch.empty((B,), dtype=torch.float32, device=px_band.device)
-        gx = torch.empty_like(px_band) if need_grads else None
-        gy = torch.empty_like(py_band) if need_grads else None
-        _lib.call("ftr_mutual_information_band_multiblank_f32", _ptr(px_band), _ptr(py_band), _ptr(ranges), _ptr(boundary),
-                  dur_arr, D, _ptr(ws), nws, _ptr(ans), _ptr(gx), _ptr(gy), B, T, int(S), r, st)
-        _lib.band_multiblank_recursions += 1
-    return ans, gx, gy
-
-
-class _BandMultiblankRecursion(torch.autograd.Function):
-    """mutual_information_recursion_multiblank_band: the occupancies are computed with the answer whenever an operand
-    needs a gradient, and backward() scales them by the upstream gradient."""
-
-    @staticmethod
-    def forward(ctx, px_band, py_band, ranges, S, durs, boundary):
-        need = px_band.requires_grad or py_band.requires_grad
-        ans, gx, gy = band_multiblank_forward_backward(px_band.detach().contiguous(), py_band.detach().contiguous(), ranges, S,
-                                                       durs, boundary, need)
-        if need:
-            ctx.save_for_backward(gx, gy)
-        return ans
-
-    @staticmethod
-    def backward(ctx, g_ans):
-        gx, gy = ctx.saved_tensors
-        g = g_ans.to(gx.dtype)
-        return gx * g.reshape(-1, 1, 1), gy * g.reshape(-1, 1, 1, 1), None, None, None, None
+    ranges, boundary, S = _band_recursion_inputs(px_band, ranges, boundary, S,
+                                                 lambda T, S, r: band_tdt_supported(T, S, r, len(tok), len(blk)))
+    return _BandDurationRecursion.apply(px_band, py_band, ranges, S, tok, blk, boundary)
 
 
 def mutual_information_recursion_multiblank_band(
@@ -595,18 +557,9 @@ def mutual_information_recursion_multiblank_band(
     B, T, r = px_band.shape
     if tuple(py_band.shape) != (B, len(durs), T, r):
         raise ValueError(f"py_band must have shape {(B, len(durs), T, r)}, got {tuple(py_band.shape)}")
-    ranges = torch.as_tensor(ranges, device=px_band.device).to(torch.int32).contiguous()
-    if tuple(ranges.shape) != (B, T, r):
-        raise ValueError(f"ranges must have shape {(B, T, r)}, got {tuple(ranges.shape)}")
-    boundary = _as_boundary(boundary, B, px_band.device)
-    if S is None:       # the last band row: one host read (give S to stay asynchronous)
-        S = int(ranges.max().item()) if ranges.numel() else 0
-    S = int(S)
-    if S < 0 or T < 1:
-        raise ValueError(f"S={S} must not be negative and T={T} must be positive")
-    if not band_multiblank_supported(T, S, r, len(durs)):
-        raise ValueError(f"the band recursion does not cover T={T}, S={S}, r={r} (r <= 15)")
-    return _BandMultiblankRecursion.apply(px_band, py_band, ranges, S, durs, boundary)
+    ranges, boundary, S = _band_recursion_inputs(px_band, ranges, boundary, S,
+                                                 lambda T, S, r: band_multiblank_supported(T, S, r, len(durs)))
+    return _BandDurationRecursion.apply(px_band, py_band, ranges, S, None, durs, boundary)
 
 
 def mutual_information_viterbi(px: torch.Tensor, py: torch.Tensor,
@@ -725,7 +678,6 @@ def mutual_information_viterbi_tdt_band(px_band: torch.Tensor, py_band: torch.Te
     the band scattered into lattices of -inf, bit for bit -- for rectangles without NaN: on the lattice a NaN also
     travels through cells outside the band, here only along moves that exist.  Not differentiable: the outputs are
     detached.  Asynchronous, no host read when ``S`` is given (capturable)."""
-    import ctypes
     _require_gpu(px_band, "px_band"); _require_gpu(py_band, "py_band")
     if px_band.dtype != torch.float32 or py_band.dtype != torch.float32:
         raise TypeError("px_band and py_band must be float32")
@@ -740,17 +692,8 @@ def mutual_information_viterbi_tdt_band(px_band: torch.Tensor, py_band: torch.Te
     if py_band.device != px_band.device:
         raise ValueError("px_band and py_band must be on the same device")
     px_band = px_band.detach().contiguous(); py_band = py_band.detach().contiguous()
-    ranges = torch.as_tensor(ranges, device=px_band.device).to(torch.int32).contiguous()
-    if tuple(ranges.shape) != (B, T, r):
-        raise ValueError(f"ranges must have shape {(B, T, r)}, got {tuple(ranges.shape)}")
-    boundary = _as_boundary(boundary, B, px_band.device)
-    if S is None:       # the last band row: one host read (give S to stay asynchronous)
-        S = int(ranges.max().item()) if ranges.numel() else 0
-    S = int(S)
-    if S < 0 or T < 1:
-        raise ValueError(f"S={S} must not be negative and T={T} must be positive")
-    if not band_viterbi_supported(T, S, r, N, Ny):
-        raise ValueError(f"the band alignment does not cover T={T}, S={S}, r={r} (r <= 15)")
+    ranges, boundary, S = _band_recursion_inputs(px_band, ranges, boundary, S,
+                                                 lambda T, S, r: band_viterbi_supported(T, S, r, N, Ny), "alignment")
     tok_arr = (ctypes.c_int32 * N)(*tok)        # read by the launch itself: no device copy, no host synchronisation
     blk_arr = (ctypes.c_int32 * Ny)(*blk)
     L = _lib.lib()

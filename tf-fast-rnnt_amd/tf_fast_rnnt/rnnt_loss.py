@@ -37,10 +37,9 @@ import weakref
 import torch
 
 from . import _lib
-from .mutual_information import (_as_boundary, _ptr, _require_gpu, _stream_ptr, band_forward_backward, band_multiblank_forward_backward,
-                                 band_multiblank_supported, band_tdt_forward_backward, band_tdt_supported, band_viterbi_supported, cummin, mb_forward_backward, mi_forward_backward,
-                                 mutual_information_recursion, mutual_information_viterbi, mutual_information_viterbi_tdt, mutual_information_viterbi_tdt_band,
-                                 tdt_forward_backward)
+from .mutual_information import (_as_boundary, _ptr, _require_gpu, _stream_ptr, band_duration_forward_backward, band_forward_backward,
+                                 band_multiblank_supported, band_tdt_supported, band_viterbi_supported, cummin, duration_forward_backward, mi_forward_backward,
+                                 mutual_information_recursion, mutual_information_viterbi, mutual_information_viterbi_tdt, mutual_information_viterbi_tdt_band)
 
 _NEG_INF = float("-inf")
 # tf.math.nextafter(0., 1.) : smallest positive float32 subnormal (rnnt_loss.py:181,1272,1280)
@@ -843,7 +842,7 @@ def rnnt_alignment_pruned(
         symbols, ranges, boundary = _pruned_inputs(logits, symbols, ranges, boundary, lowp=True)
         B, T, r, C = logits.shape
         S = symbols.shape[1]
-        if rnnt_type == "regular" and _align_band_path_ok(ranges, boundary, T, S, r, 1, 1):
+        if rnnt_type == "regular" and _band_path_ok(ranges, boundary, T, S, r, band_viterbi_supported(T, S, r, 1, 1)):
             x = logits.detach().contiguous()
             lse = torch.empty((B, T, r), dtype=torch.float32, device=x.device)
             pxb = torch.empty((B, 1, T, r), dtype=torch.float32, device=x.device)
@@ -853,7 +852,7 @@ def rnnt_alignment_pruned(
                              _ptr(lse), _ptr(pxb), _ptr(pyb), B, T, S, C, r, 0), (_stream_ptr(x),))
             score, frames, _, _ = mutual_information_viterbi_tdt_band(pxb, pyb, ranges, (0,), (1,), boundary, S=S)
             return score, frames
-        if rnnt_type == "constrained" and _align_band_path_ok(ranges, boundary, T, S, r, 1, 1):
+        if rnnt_type == "constrained" and _band_path_ok(ranges, boundary, T, S, r, band_viterbi_supported(T, S, r, 1, 1)):
             _, pxb, pyb = _constrained_band_fwd(logits.detach().contiguous(), symbols, ranges, boundary, termination_symbol, 0.0, False)
             score, frames, _, _ = mutual_information_viterbi_tdt_band(pxb.unsqueeze(1), pyb.unsqueeze(1), ranges, (1,), (1,), boundary, S=S)
             return score, frames
@@ -1013,20 +1012,16 @@ def _is_band(ranges: torch.Tensor, boundary) -> bool:
     return ok
 
 
-def _align_band_path_ok(ranges, boundary, T: int, S: int, r: int, N: int, Ny: int) -> bool:
-    """_band_path_ok for the three alignment wrappers: the same rule and the same FTR_PRUNED_ROUTE knob, the domain of
-    csrc/mi_band_viterbi.hip."""
+def _band_path_ok(ranges, boundary, T: int, S: int, r: int, supported: Optional[bool] = None) -> bool:
+    """The route of every loss node and alignment wrapper.  A band-native recursion needs a band that its kernels cover
+    (r <= 15) and ranges that ARE a band (_is_band).  ``supported``: the verdict of the op's own ``*_supported`` query
+    (the multi-blank, TDT and alignment domains); None: that of the ordinary band recursion.  FTR_PRUNED_ROUTE=lattice (a
+    test knob, read at call time) sends everything through the full-size lattices."""
     if os.environ.get("FTR_PRUNED_ROUTE") == "lattice":
         return False
-    return band_viterbi_supported(T, S, r, N, Ny) and _is_band(ranges, boundary)
-
-
-def _band_path_ok(ranges, boundary, T: int, S: int, r: int) -> bool:
-    """The band-native recursion needs a band that its kernels cover (r <= 15) and ranges that ARE a band (_is_band).
-    FTR_PRUNED_ROUTE=lattice (a test knob, read at call time) sends everything through the full-size lattices."""
-    if os.environ.get("FTR_PRUNED_ROUTE") == "lattice":
-        return False
-    return _lib.lib().ftr_mutual_information_band_supported(int(T), int(S), int(r)) != 0 and _is_band(ranges, boundary)
+    if supported is None:
+        supported = _lib.lib().ftr_mutual_information_band_supported(int(T), int(S), int(r)) != 0
+    return supported and _is_band(ranges, boundary)
 
 
 class _PrunedLoss(torch.autograd.Function):
@@ -1938,30 +1933,19 @@ def _big_blank_args(big_blanks, termination_symbol: int, C: int):
     return (ctypes.c_int32 * max(D - 1, 1))(*ids), (ctypes.c_int32 * D)(*durs), tuple(durs)
 
 
-def _mb_builder_fwd(x, symbols, ranges, boundary, blank, ids, durs, D, sigma, delay_penalty):
+def _mb_builder_fwd(x, symbols, ranges, boundary, blank, ids, durs, D, sigma, delay_penalty, band=False):
+    """``band``: band-shaped px_band [B,T,r] / py_band [B,D,T,r] and no lattice is written, else the full-size lattices."""
     B, T, r, C = x.shape
     S = symbols.shape[1]
-    lse = torch.empty((B, T, r), dtype=torch.float32, device=x.device)
-    px = torch.empty((B, S, T + 1), dtype=torch.float32, device=x.device)
-    py = torch.empty((B, D, S + 1, T), dtype=torch.float32, device=x.device)
+    new = lambda *shape: torch.empty(shape, dtype=torch.float32, device=x.device)
+    lse = new(B, T, r)
+    px = new(B, T, r) if band else new(B, S, T + 1)
+    py = new(B, D, T, r) if band else new(B, D, S + 1, T)
     with torch.cuda.device(x.device):
-        _lib.call("ftr_multiblank_pruned_logprobs_fwd_f32", _ptr(x), _ptr(symbols), _ptr(ranges), _ptr(boundary), blank,
-                  ids, durs, D, float(sigma), float(delay_penalty), _ptr(lse), _ptr(px), _ptr(py), B, T, S, C, r,
-                  _stream_ptr(x))
+        _lib.call("ftr_multiblank_pruned_band_fwd_f32" if band else "ftr_multiblank_pruned_logprobs_fwd_f32", _ptr(x), _ptr(symbols),
+                  _ptr(ranges), _ptr(boundary), blank, ids, durs, D, float(sigma), float(delay_penalty), _ptr(lse), _ptr(px), _ptr(py),
+                  B, T, S, C, r, _stream_ptr(x))
     return lse, px, py
-
-
-def _mb_band_builder_fwd(x, symbols, ranges, boundary, blank, ids, durs, D, sigma, delay_penalty):
-    """_mb_builder_fwd with band-shaped px_band [B,T,r] / py_band [B,D,T,r]: no lattice is written."""
-    B, T, r, C = x.shape
-    S = symbols.shape[1]
-    lse = torch.empty((B, T, r), dtype=torch.float32, device=x.device)
-    pxb = torch.empty((B, T, r), dtype=torch.float32, device=x.device)
-    pyb = torch.empty((B, D, T, r), dtype=torch.float32, device=x.device)
-    with torch.cuda.device(x.device):
-        _lib.call("ftr_multiblank_pruned_band_fwd_f32", _ptr(x), _ptr(symbols), _ptr(ranges), _ptr(boundary), blank, ids,
-                  durs, D, float(sigma), float(delay_penalty), _ptr(lse), _ptr(pxb), _ptr(pyb), B, T, S, C, r, _stream_ptr(x))
-    return lse, pxb, pyb
 
 
 def _mb_builder_bwd(x, symbols, ranges, boundary, blank, ids, durs, D, lse, gpx, gpy, scale, stride, mul, band=False):
@@ -1997,14 +1981,6 @@ class _MultiblankLogprobs(torch.autograd.Function):
         return g, None, None, None, None, None, None
 
 
-def _mb_band_path_ok(ranges, boundary, T: int, S: int, r: int, D: int) -> bool:
-    """_band_path_ok for the multi-blank loss: the same rule and the same FTR_PRUNED_ROUTE knob, the multi-blank domain
-    of csrc/mi_band_tdt.hip."""
-    if os.environ.get("FTR_PRUNED_ROUTE") == "lattice":
-        return False
-    return band_multiblank_supported(T, S, r, D) and _is_band(ranges, boundary)
-
-
 class _MultiblankLoss(torch.autograd.Function):
     """rnnt_loss_multiblank_pruned with the whole chain native, as _PrunedLoss.
 
@@ -2021,15 +1997,13 @@ class _MultiblankLoss(torch.autograd.Function):
         ids, durs, dt = _big_blank_args(big_blanks, termination_symbol, x.shape[3])
         B, T, r, _ = x.shape
         S = symbols.shape[1]
-        ctx.band = _mb_band_path_ok(ranges, boundary, T, S, r, len(dt))
+        ctx.band = _band_path_ok(ranges, boundary, T, S, r, band_multiblank_supported(T, S, r, len(dt)))
+        lse, px, py = _mb_builder_fwd(x, symbols, ranges, boundary, int(termination_symbol), ids, durs, len(dt), sigma,
+                                      delay_penalty, ctx.band)
         if ctx.band:
-            lse, px, py = _mb_band_builder_fwd(x, symbols, ranges, boundary, int(termination_symbol), ids, durs, len(dt), sigma,
-                                               delay_penalty)
-            ans, px_grad, py_grad = band_multiblank_forward_backward(px, py, ranges, S, dt, boundary, need)
+            ans, px_grad, py_grad = band_duration_forward_backward(px, py, ranges, S, None, dt, boundary, need)
         else:
-            lse, px, py = _mb_builder_fwd(x, symbols, ranges, boundary, int(termination_symbol), ids, durs, len(dt), sigma,
-                                          delay_penalty)
-            ans, px_grad, py_grad = mb_forward_backward(px, py, dt, boundary, need)
+            ans, px_grad, py_grad = duration_forward_backward(px, py, None, dt, boundary, need)
         del px, py
         if need:
             ctx.save_for_backward(x, symbols, ranges, lse, px_grad, py_grad, boundary)
@@ -2160,33 +2134,19 @@ def _tdt_args(durations, termination_symbol: int, width: int):
     return (ctypes.c_int32 * len(durs))(*durs), durs, tuple(d for d in durs if d > 0), C
 
 
-def _tdt_builder_fwd(x, symbols, ranges, boundary, blank, arr, durs, blank_durs, C, sigma, delay_penalty):
+def _tdt_builder_fwd(x, symbols, ranges, boundary, blank, arr, durs, blank_durs, C, sigma, delay_penalty, band=False):
+    """``band``: band-shaped px_band [B,N,T,r] / py_band [B,Ny,T,r] and no lattice is written, else the full-size lattices."""
     B, T, r, _ = x.shape
     S = symbols.shape[1]
-    lse_tok = torch.empty((B, T, r), dtype=torch.float32, device=x.device)
-    lse_dur = torch.empty((B, T, r), dtype=torch.float32, device=x.device)
-    px = torch.empty((B, len(durs), S, T + 1), dtype=torch.float32, device=x.device)
-    py = torch.empty((B, len(blank_durs), S + 1, T), dtype=torch.float32, device=x.device)
+    new = lambda *shape: torch.empty(shape, dtype=torch.float32, device=x.device)
+    lse_tok, lse_dur = new(B, T, r), new(B, T, r)
+    px = new(B, len(durs), T, r) if band else new(B, len(durs), S, T + 1)
+    py = new(B, len(blank_durs), T, r) if band else new(B, len(blank_durs), S + 1, T)
     with torch.cuda.device(x.device):
-        _lib.call("ftr_tdt_pruned_logprobs_fwd_f32", _ptr(x), _ptr(symbols), _ptr(ranges), _ptr(boundary), blank, arr,
-                  len(durs), float(sigma), float(delay_penalty), _ptr(lse_tok), _ptr(lse_dur), _ptr(px), _ptr(py), B, T, S, C,
-                  r, _stream_ptr(x))
+        _lib.call("ftr_tdt_pruned_band_fwd_f32" if band else "ftr_tdt_pruned_logprobs_fwd_f32", _ptr(x), _ptr(symbols), _ptr(ranges),
+                  _ptr(boundary), blank, arr, len(durs), float(sigma), float(delay_penalty), _ptr(lse_tok), _ptr(lse_dur), _ptr(px),
+                  _ptr(py), B, T, S, C, r, _stream_ptr(x))
     return lse_tok, lse_dur, px, py
-
-
-def _tdt_band_builder_fwd(x, symbols, ranges, boundary, blank, arr, durs, blank_durs, C, sigma, delay_penalty):
-    """_tdt_builder_fwd with band-shaped px_band [B,N,T,r] / py_band [B,Ny,T,r]: no lattice is written."""
-    B, T, r, _ = x.shape
-    S = symbols.shape[1]
-    lse_tok = torch.empty((B, T, r), dtype=torch.float32, device=x.device)
-    lse_dur = torch.empty((B, T, r), dtype=torch.float32, device=x.device)
-    pxb = torch.empty((B, len(durs), T, r), dtype=torch.float32, device=x.device)
-    pyb = torch.empty((B, len(blank_durs), T, r), dtype=torch.float32, device=x.device)
-    with torch.cuda.device(x.device):
-        _lib.call("ftr_tdt_pruned_band_fwd_f32", _ptr(x), _ptr(symbols), _ptr(ranges), _ptr(boundary), blank, arr,
-                  len(durs), float(sigma), float(delay_penalty), _ptr(lse_tok), _ptr(lse_dur), _ptr(pxb), _ptr(pyb), B, T, S, C,
-                  r, _stream_ptr(x))
-    return lse_tok, lse_dur, pxb, pyb
 
 
 def _tdt_builder_bwd(x, symbols, ranges, boundary, blank, arr, N, C, sigma, delay_penalty, lse_tok, lse_dur, gpx, gpy, scale,
@@ -2224,14 +2184,6 @@ class _TdtLogprobs(torch.autograd.Function):
         return g, None, None, None, None, None, None, None
 
 
-def _tdt_band_path_ok(ranges, boundary, T: int, S: int, r: int, N: int, Ny: int) -> bool:
-    """_band_path_ok for the TDT loss: the same rule and the same FTR_PRUNED_ROUTE knob, the domain of
-    csrc/mi_band_tdt.hip."""
-    if os.environ.get("FTR_PRUNED_ROUTE") == "lattice":
-        return False
-    return band_tdt_supported(T, S, r, N, Ny) and _is_band(ranges, boundary)
-
-
 class _TdtLoss(torch.autograd.Function):
     """rnnt_loss_tdt_pruned with the whole chain native, as _PrunedLoss.
 
@@ -2248,15 +2200,13 @@ class _TdtLoss(torch.autograd.Function):
         arr, durs, blank_durs, C = _tdt_args(durations, termination_symbol, x.shape[3])
         B, T, r, _ = x.shape
         S = symbols.shape[1]
-        ctx.band = _tdt_band_path_ok(ranges, boundary, T, S, r, len(durs), len(blank_durs))
+        ctx.band = _band_path_ok(ranges, boundary, T, S, r, band_tdt_supported(T, S, r, len(durs), len(blank_durs)))
+        lse_tok, lse_dur, px, py = _tdt_builder_fwd(x, symbols, ranges, boundary, int(termination_symbol), arr, durs, blank_durs,
+                                                    C, sigma, delay_penalty, ctx.band)
         if ctx.band:
-            lse_tok, lse_dur, px, py = _tdt_band_builder_fwd(x, symbols, ranges, boundary, int(termination_symbol), arr, durs,
-                                                             blank_durs, C, sigma, delay_penalty)
-            ans, px_grad, py_grad = band_tdt_forward_backward(px, py, ranges, S, durs, blank_durs, boundary, need)
+            ans, px_grad, py_grad = band_duration_forward_backward(px, py, ranges, S, durs, blank_durs, boundary, need)
         else:
-            lse_tok, lse_dur, px, py = _tdt_builder_fwd(x, symbols, ranges, boundary, int(termination_symbol), arr, durs,
-                                                        blank_durs, C, sigma, delay_penalty)
-            ans, px_grad, py_grad = tdt_forward_backward(px, py, durs, blank_durs, boundary, need)
+            ans, px_grad, py_grad = duration_forward_backward(px, py, durs, blank_durs, boundary, need)
         del px, py
         if need:
             ctx.save_for_backward(x, symbols, ranges, lse_tok, lse_dur, px_grad, py_grad, boundary)
@@ -2418,18 +2368,18 @@ class _TdtMixedLoss(torch.autograd.Function):
         blank = int(termination_symbol)
         tdt = omega < 1.0
         parts = _lib.FTR_TDT_MIX_RNNT | (_lib.FTR_TDT_MIX_TDT if tdt else 0)
-        ctx.band = (_tdt_band_path_ok(ranges, boundary, T, S, r, len(durs), len(blank_durs))
+        ctx.band = (_band_path_ok(ranges, boundary, T, S, r, band_tdt_supported(T, S, r, len(durs), len(blank_durs)))
                     and _band_path_ok(ranges, boundary, T, S, r))
         lse_tok, lse_dur, px, py, px0, py0 = _tdt_mix_builder_fwd(x, symbols, ranges, boundary, blank, arr, durs, blank_durs, C,
                                                                   sigma, parts, delay_penalty, ctx.band)
         ans_tdt = gx = gy = None
         if ctx.band:
             if tdt:
-                ans_tdt, gx, gy = band_tdt_forward_backward(px, py, ranges, S, durs, blank_durs, boundary, need)
+                ans_tdt, gx, gy = band_duration_forward_backward(px, py, ranges, S, durs, blank_durs, boundary, need)
             ans0, gx0, gy0 = band_forward_backward(px0, py0, ranges, S, boundary, 0)
         else:
             if tdt:
-                ans_tdt, gx, gy = tdt_forward_backward(px, py, durs, blank_durs, boundary, need)
+                ans_tdt, gx, gy = duration_forward_backward(px, py, durs, blank_durs, boundary, need)
             ans0, gx0, gy0 = mi_forward_backward(px0, py0, boundary, need, ans_grad_is_one=True)
         del px, py, px0, py0
         # both factors are finite and, where the TDT part exists, positive: -inf (no TDT path) stays -inf, no 0 * inf
@@ -2517,6 +2467,13 @@ def rnnt_loss_tdt_mixed(
 
 # ---- best-path alignment over the TDT and multi-blank lattices (MI355X addition, no reference counterpart)
 
+def _duration_alignment(px, py, ranges, token_durations, blank_durations, boundary, S, band):
+    """The alignment of either route: ``band``: px / py are band-shaped and no lattice exists."""
+    if band:
+        return mutual_information_viterbi_tdt_band(px, py, ranges, token_durations, blank_durations, boundary, S=S)
+    return mutual_information_viterbi_tdt(px, py, token_durations, blank_durations, boundary)
+
+
 def rnnt_alignment_tdt_pruned(
     logits: torch.Tensor,
     symbols: torch.Tensor,
@@ -2545,13 +2502,10 @@ def rnnt_alignment_tdt_pruned(
         x = logits.detach().contiguous()
         B, T, r, _ = x.shape
         S = symbols.shape[1]
-        if _align_band_path_ok(ranges, boundary, T, S, r, len(durs), len(blank_durs)):
-            _, _, pxb, pyb = _tdt_band_builder_fwd(x, symbols, ranges, boundary, int(termination_symbol), arr, durs, blank_durs, C,
-                                                   _check_sigma(sigma), 0.0)
-            return mutual_information_viterbi_tdt_band(pxb, pyb, ranges, durs, blank_durs, boundary, S=S)
+        band = _band_path_ok(ranges, boundary, T, S, r, band_viterbi_supported(T, S, r, len(durs), len(blank_durs)))
         _, _, px, py = _tdt_builder_fwd(x, symbols, ranges, boundary, int(termination_symbol), arr, durs, blank_durs, C,
-                                        _check_sigma(sigma), 0.0)
-        return mutual_information_viterbi_tdt(px, py, durs, blank_durs, boundary)
+                                        _check_sigma(sigma), 0.0, band)
+        return _duration_alignment(px, py, ranges, durs, blank_durs, boundary, S, band)
 
 
 def rnnt_alignment_multiblank_pruned(
@@ -2576,13 +2530,10 @@ def rnnt_alignment_multiblank_pruned(
         ids, durs, dt = _big_blank_args(tuple(map(tuple, big_blanks)), termination_symbol, x.shape[3])
         B, T, r, _ = x.shape
         S = symbols.shape[1]
-        if _align_band_path_ok(ranges, boundary, T, S, r, 1, len(dt)):
-            _, pxb, pyb = _mb_band_builder_fwd(x, symbols, ranges, boundary, int(termination_symbol), ids, durs, len(dt),
-                                               _check_sigma(sigma), 0.0)
-            return mutual_information_viterbi_tdt_band(pxb.unsqueeze(1), pyb, ranges, (0,), dt, boundary, S=S)
+        band = _band_path_ok(ranges, boundary, T, S, r, band_viterbi_supported(T, S, r, 1, len(dt)))
         _, px, py = _mb_builder_fwd(x, symbols, ranges, boundary, int(termination_symbol), ids, durs, len(dt),
-                                    _check_sigma(sigma), 0.0)
-        return mutual_information_viterbi_tdt(px.unsqueeze(1), py, (0,), dt, boundary)
+                                    _check_sigma(sigma), 0.0, band)
+        return _duration_alignment(px.unsqueeze(1), py, ranges, (0,), dt, boundary, S, band)
 
 
 def _colsum_weighted(x: torch.Tensor, w: torch.Tensor, rows: int, C: int, st) -> torch.Tensor:
